@@ -13,11 +13,15 @@ in the reference's batch format before the timed region starts (coordinates / fe
 uploaded inside the step exactly as the reference's ME.SparseTensor(...).to(device) does).
 One process per GPU, weak scaling: every rank has its own 4 pairs (seed = rank).
 
-Rank 0 prints ONE JSON line; besides the contract keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract keys (metric,
+value, unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step) with the run's config.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+--full adds what takes runs of its own (each still switchable off with its --no-* option):
   roofline     : the dominant kernel (fp32-MFMA gather-GEMM of the level-1 96->96 block conv)
                  timed live with HIP events, algorithmic FLOPs / launch time vs the 157.3 TFLOP/s
                  fp32 matrix peak (MI355X_MICROARCH.md); `kernels` lists the other hot kernels
-                 incl. the HBM-bound ones against the 8 TB/s peak
+                 incl. the HBM-bound ones against the 8 TB/s peak; `families` the in-step cost per family
+  extra        : the other single-GPU BASELINE configurations and the fp32-MFMA-only build of the step, N=1 only
   cpu_baseline : the CPU oracle's identical iteration on a bounded sample (1 pair), N=1 only.
 """
 import argparse
@@ -552,6 +556,43 @@ def family_table(trainer, it, timers, batch, device, sets=6, layer_times_path=No
           "families": out}
 
 
+DUMP_SAMPLE = 1 << 22  # entries kept of a larger flat array: 16 MB of float32
+
+
+def dump_outputs(out_dir, res, trainer):
+  """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy -- every loss value it returned
+  (float64, shape [1]), the parameters after its SGD update (params.npy) and the gradient that update applied
+  (grads.npy), float32 in model.parameters() order.  A flat array of more than DUMP_SAMPLE entries is stored as a fixed
+  sample: the entries at np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False), in ascending order."""
+  import torch
+  os.makedirs(out_dir, exist_ok=True)
+  for k, v in res.items():
+    np.save(os.path.join(out_dir, "%s.npy" % k), np.asarray([float(v)], dtype=np.float64))
+  params = trainer.flat.params
+  for name, flat in (("params", torch.cat([p.detach().reshape(-1) for p in params])),
+                     ("grads", torch.cat([p.grad.detach().reshape(-1) for p in params]))):
+    n = flat.numel()
+    if n > DUMP_SAMPLE:
+      idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+      flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, "%s.npy" % name), flat.float().cpu().numpy())
+  log("outputs of the last timed step written to %s" % out_dir)
+
+
+def build():
+  """__graft_entry__.build(), also in a tree this user cannot write to (built by another user), whatever build module
+  the tree has: where its lock file cannot be created, the build's own up-to-date check runs without it -- a current
+  library is used as it is, a stale one fails at its first write -- and the package is imported as build() does."""
+  import __graft_entry__
+  try:
+    __graft_entry__.build()
+  except PermissionError:
+    from pointcontrast_amd import build as b
+    b._build_locked(False, False)
+    from pointcontrast_amd import _lib
+    assert _lib.version() >= 100
+
+
 def fp32_instruction_leg(args, steps=10, warmup=5, limit_s=240):
   """The same iteration with every split-precision kernel switched off (PCMI_CONV16_X3=0 PCMI_WGRAD_X3T=0 PCMI_NCE_X3=0:
   the fp32 MFMA instruction throughout -- literally the reference's arithmetic), in a child process of this run."""
@@ -584,20 +625,24 @@ def main():
   ap.add_argument("--loss", choices=["nce", "hardest"], default="nce")
   ap.add_argument("--model", default="Res16UNet34C")
   ap.add_argument("--engine", choices=["native", "autograd"], default="native")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure what takes runs of its own: rooflines / families, the extra legs, the CPU baseline")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-roofline", action="store_true")
-  ap.add_argument("--no-extra", action="store_true", help="skip the extra.hardest / extra.voxel_1cm legs (N = 1 default run)")
+  ap.add_argument("--no-extra", action="store_true", help="skip the extra.hardest / extra.voxel_1cm legs (N = 1 --full run)")
   ap.add_argument("--layer-table", default=None, help="write the per-layer work table to this path")
+  ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/*.npy")
   ap.add_argument("--set", action="append", default=[], metavar="a.b=c", help="extra config override (A/B experiments)")
   args = ap.parse_args()
+  if not args.full:
+    args.no_cpu_baseline = args.no_roofline = args.no_extra = True
 
-  import __graft_entry__
   if "WORLD_SIZE" not in os.environ and args.gpus > 1:
     # No external launcher: start the N ranks ourselves, as the reference's entry point does (pc/ddp_train.py:57-59 ->
     # lib/multiprocessing.py:36-56).  The library is built ONCE, here, before any rank exists; every rank is this same
     # script with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in its environment; a failing rank stops the others and its
     # exit code becomes ours.  Rank 0 inherits this stdout, so the JSON line arrives where the caller reads it.
-    __graft_entry__.build()
+    build()
     from pointcontrast_amd.lib.multiprocessing import launch_script_ranks
     sys.exit(launch_script_ranks(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:]))
   import torch
@@ -605,7 +650,7 @@ def main():
   assert torch.cuda.is_available(), "bench.py measures the HIP path and needs an MI355X (no CPU fallback)"
   world = int(os.environ.get("WORLD_SIZE", "1"))
   rank = int(os.environ.get("RANK", "0"))
-  __graft_entry__.build()  # every rank: an exclusive file lock inside serialises them, all but the first find it built
+  build()  # every rank: an exclusive file lock inside serialises them, all but the first find it built
   from pointcontrast_amd.lib import distributed as du
   forced = any(a.replace(" ", "") in ("misc.force_reducer=True", "misc.force_reducer=1") for a in args.set)
   if world > 1:
@@ -676,13 +721,18 @@ def main():
     elapsed = float(tt.item())
 
   if rank == 0:
+    if args.dump_outputs:  # before anything below runs the model again
+      dump_outputs(args.dump_outputs, res, trainer)
     n0, n1 = batch["sinput0_C"].shape[0], batch["sinput1_C"].shape[0]
-    if args.engine == "native":  # per-layer pair counts are recorded by the module path: one untimed forward
-      import pointcontrast_amd.minkowski as ME
-      with torch.no_grad():
-        trainer.model(ME.SparseTensor(batch["sinput1_F"], coords=batch["sinput1_C"]).to(device))
-      torch.cuda.synchronize()
-    flops, byts, rows = conv_work(trainer.model)  # cloud 1
+    work = {}
+    if args.full or args.layer_table:
+      if args.engine == "native":  # per-layer pair counts are recorded by the module path: one untimed forward
+        import pointcontrast_amd.minkowski as ME
+        with torch.no_grad():
+          trainer.model(ME.SparseTensor(batch["sinput1_F"], coords=batch["sinput1_C"]).to(device))
+        torch.cuda.synchronize()
+      flops, byts, rows = conv_work(trainer.model)  # cloud 1
+      work = {"conv_gflop_per_forward": round(flops * 1e-9, 2), "conv_algo_gb_per_forward": round(byts * 1e-9, 3)}
     out = {
         "metric": "scene-pairs/sec, ScanNet %s Res16UNet34C %s" % (
             "2.5cm" if abs(args.voxel - 0.025) < 1e-9 else "%gcm" % (args.voxel * 100),
@@ -709,7 +759,7 @@ def main():
                       if getattr(trainer.engine, "pair_marks", None) else {}),
                    **({"host_phase_ms_per_step": {k: round(v / (args.steps + args.warmup), 3) for k, v in trainer.host_ms.items()}}
                       if trainer.host_ms else {}),
-                   "conv_gflop_per_forward": round(flops * 1e-9, 2), "conv_algo_gb_per_forward": round(byts * 1e-9, 3),
+                   **work,
                    # N > 1: what RCCL saw -- ranks, backend, gradient buckets, and how much of the all-reduce was hidden
                    "collective": ({"ranks": dist.get_world_size(), "backend": dist.get_backend(),
                                    "allreduce_mb_per_step": round(trainer.flat.numel * 4 / 2 ** 20, 1),

@@ -66,10 +66,16 @@ def build_lib(force=False, verbose=False):
   """Compiles what changed and links libpcmi.so.  Safe to call from several processes at once (the ranks of a
   multi-GPU run all call it): an exclusive file lock serialises them, the first one builds, the others find the
   digests matching; the library is linked under a temporary name and renamed into place, so a process that is
-  loading it never sees a half-written file."""
+  loading it never sees a half-written file.  In a tree this user cannot write to (built by another user) there is no
+  lock to take and nobody can build concurrently: the same up-to-date check runs without it, so a current library is
+  returned with nothing written and a stale one fails at its first write."""
   import fcntl
-  os.makedirs(BUILD, exist_ok=True)
-  with open(os.path.join(BUILD, ".lock"), "w") as lock:
+  try:
+    os.makedirs(BUILD, exist_ok=True)
+    lock = open(os.path.join(BUILD, ".lock"), "w")
+  except PermissionError:
+    return _build_locked(force, verbose)
+  with lock:
     fcntl.flock(lock, fcntl.LOCK_EX)
     try:
       return _build_locked(force, verbose)

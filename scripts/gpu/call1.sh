@@ -10,7 +10,7 @@ mkdir -p $O
 python -c "import __graft_entry__ as g; g.build()" > $O/build.txt 2>&1
 timeout 900 python -m pytest tests -m gpu -q --durations=12 > $O/gpu_tests.txt 2>&1; echo "pytest rc $?" >> $O/gpu_tests.txt
 tail -5 $O/gpu_tests.txt
-timeout 400 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"
+timeout 400 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"
 B="python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-roofline --no-extra"
 for r in a b; do
   timeout 150 $B > $O/plain_$r.json 2>> $O/ab.err

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out/r04n; O=gpurun_out/r04n
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_h -o p -- python $R/bench.py --loss hardest --steps 10 --warmup 3 --no-extra --no-cpu-baseline > $R/$O/hardest_line.json 2>/dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_h -o p -- python $R/bench.py --full --loss hardest --steps 10 --warmup 3 --no-extra --no-cpu-baseline > $R/$O/hardest_line.json 2>/dev/null
 f=$(find /tmp/prof_h -name "*kernel_stats.csv" | head -1); cp $f $R/$O/hardest_kernel_stats.csv
 cd $R
 python - <<'PY'

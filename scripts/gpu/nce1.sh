@@ -7,7 +7,7 @@ for n in 4096 1024 8192; do
   PCMI_NCE_X3=0 timeout 120 env PYTHONPATH=. python scripts/loss_bench.py $n >> $O/loss_bench_valu.txt 2>&1
 done
 for i in 1; do
-  timeout 200 python bench.py --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('x3  ', d['value'], d['ms_per_step'])" >> $O/ab.txt
-  PCMI_NCE_X3=0 timeout 200 python bench.py --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('valu', d['value'], d['ms_per_step'])" >> $O/ab.txt
+  timeout 200 python bench.py --full --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('x3  ', d['value'], d['ms_per_step'])" >> $O/ab.txt
+  PCMI_NCE_X3=0 timeout 200 python bench.py --full --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('valu', d['value'], d['ms_per_step'])" >> $O/ab.txt
 done
 cat $O/pytest_nce.log $O/loss_bench.txt $O/loss_bench_valu.txt $O/ab.txt

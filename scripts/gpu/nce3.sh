@@ -9,8 +9,8 @@ for v in 1; do
 done
 cd /root/repo
 for i in 1 2; do
-  timeout 200 python bench.py --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('x3  ', d['value'], d['ms_per_step'])" >> $O/ab3.txt
-  PCMI_NCE_X3=0 timeout 200 python bench.py --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('valu', d['value'], d['ms_per_step'])" >> $O/ab3.txt
+  timeout 200 python bench.py --full --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('x3  ', d['value'], d['ms_per_step'])" >> $O/ab3.txt
+  PCMI_NCE_X3=0 timeout 200 python bench.py --full --steps 30 --warmup 10 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('valu', d['value'], d['ms_per_step'])" >> $O/ab3.txt
 done
 cat $O/pytest_nce.log $O/ab3.txt
 python - <<'PY'

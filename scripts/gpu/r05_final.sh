@@ -15,7 +15,7 @@ stamp() { echo "[$(( $(date +%s) - T0 )) s] $*" | tee -a $O/stages.log; }
 python -c "import __graft_entry__ as g; g.build()" > $O/build.txt 2>&1
 B="python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-roofline --no-extra"
 stamp "1 bench as the driver runs it"
-timeout 700 python bench.py --layer-table $O/layer_table.tsv > $O/bench_line.json 2> $O/bench.err
+timeout 700 python bench.py --full --layer-table $O/layer_table.tsv > $O/bench_line.json 2> $O/bench.err
 echo "bench exit $?" >> $O/stages.log; cut -c1-300 $O/bench_line.json; echo
 stamp "2 rocprofv3 kernel stats"
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o bench -- \

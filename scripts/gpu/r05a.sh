@@ -19,7 +19,7 @@ stamp "1 new / changed GPU tests first"
 timeout 900 python -m pytest tests/test_gpu_bucket_sync.py tests/test_gpu_trace.py -m gpu -q --tb=short -p no:cacheprovider -s > $O/pytest_new.log 2>&1
 echo "pytest(new) exit $?" | tee -a $O/stages.log; grep -E "passed|failed|skipped" $O/pytest_new.log | tail -3
 stamp "2 bench as the driver runs it"
-timeout 700 python bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 700 python bench.py --full > $O/bench_line.json 2> $O/bench.err
 echo "bench exit $?" >> $O/stages.log; cut -c1-400 $O/bench_line.json; echo
 B="python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-roofline --no-extra"
 run() {  # label, env...

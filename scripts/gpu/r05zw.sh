@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 O=$ROOT/gpurun_out/r05zw
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.build()" > $O/build.txt 2>&1
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err
 echo "bench exit $?"; cut -c1-200 $O/bench_line.json
 python - <<'PY'
 import json

@@ -18,7 +18,7 @@ timeout 900 python -m pytest tests/test_gpu_timing.py "tests/test_gpu_fullsize.p
   -m gpu -q --tb=short -p no:cacheprovider -s --durations=6 > $O/pytest_sel.log 2>&1
 echo "pytest(sel) exit $?" | tee -a $O/stages.log; grep -E "passed|failed|skipped" $O/pytest_sel.log | tail -3; grep -E "^FAILED|^ERROR|worst gradient|level-1 tensors|chain ops" $O/pytest_sel.log | head -20
 stamp "2 bench as the driver runs it"
-timeout 900 python bench.py --layer-table $O/layer_table.tsv > $O/bench_line.json 2> $O/bench.err
+timeout 900 python bench.py --full --layer-table $O/layer_table.tsv > $O/bench_line.json 2> $O/bench.err
 echo "bench exit $?" >> $O/stages.log; cut -c1-300 $O/bench_line.json; echo
 python - <<PY
 import json

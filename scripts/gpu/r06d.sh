@@ -37,8 +37,8 @@ run rule_on 3 PCMI_NOP=1
 run rule_off 1 PCMI_KSPLIT_RULE=0
 run rule_on 1 PCMI_NOP=1
 stamp "2 per-layer in-step times"
-PCMI_KSPLIT_RULE=0 timeout 300 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_rule_off.tsv > $O/line_rule_off.json 2>> $O/bench.err
-timeout 300 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_rule_on.tsv > $O/line_rule_on.json 2>> $O/bench.err
+PCMI_KSPLIT_RULE=0 timeout 300 python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_rule_off.tsv > $O/line_rule_off.json 2>> $O/bench.err
+timeout 300 python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_rule_on.tsv > $O/line_rule_on.json 2>> $O/bench.err
 python - <<PY | tee $O/layers_ab.txt
 def load(p):
   rows = {}

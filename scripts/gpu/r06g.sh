@@ -42,8 +42,8 @@ for i in 1 2 3; do
   ENVV="PCMI_NOP=1" run1 relu_bits $i
 done
 stamp "3 per-layer in-step times"
-PCMI_BN_RELU_BITS=0 timeout 300 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_off.tsv > $O/line_off.json 2>> $O/bench.err
-timeout 300 python bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_on.tsv > $O/line_on.json 2>> $O/bench.err
+PCMI_BN_RELU_BITS=0 timeout 300 python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_off.tsv > $O/line_off.json 2>> $O/bench.err
+timeout 300 python bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-extra --layer-table $O/layers_on.tsv > $O/line_on.json 2>> $O/bench.err
 python - <<PY | tee $O/layers_ab.txt
 import json
 for name in ("off", "on"):

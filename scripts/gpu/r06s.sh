@@ -27,7 +27,7 @@ PY
 done
 for v in oldbn product; do
   if [ $v = product ]; then L=$ROOT/pointcontrast_amd/libpcmi.so; else L=$ROOT/pointcontrast_amd/libpcmi_$v.so; fi
-  PCMI_LIB=$L timeout 200 python bench.py --steps 10 --warmup 4 --no-cpu-baseline --no-extra > $O/fam_$v.json 2>> $O/bench.err
+  PCMI_LIB=$L timeout 200 python bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --no-extra > $O/fam_$v.json 2>> $O/bench.err
   python - $O/fam_$v.json $v <<'PY' | tee -a $O/families.txt
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

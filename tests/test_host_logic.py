@@ -334,33 +334,31 @@ def test_checkpoint_prefixes_and_kernel_order_switch(built_lib):
   assert torch.equal(m2.state_dict()["block4.0.conv2.kernel"], sd["block4.0.conv2.kernel"])
 
 
-def test_semseg_scheduler_and_metrics_against_reference_source(built_lib):
-  """downstream/semseg pieces restated in pointcontrast_amd/downstream/semseg.py: PolyLR against the reference's own
-  class (lib/solvers.py imports only torch: executed from /root/reference where present), metrics against hand counts."""
-  import importlib.util
-  from pointcontrast_amd.downstream import semseg as ss
-  p = torch.nn.Parameter(torch.zeros(3))
-  opt = torch.optim.SGD([p], lr=0.1, momentum=0.9)
-  sch = ss.PolyLR(opt, max_iter=100, power=0.9)
+GOLDEN_HOST_REF = os.path.join(ROOT, "tests", "golden", "golden_host_ref.json")
+
+
+def poly_lrs(poly_cls, opt):
+  """Learning rates of five SGD steps under poly_cls(opt, max_iter=100, power=0.9)."""
+  sch = poly_cls(opt, max_iter=100, power=0.9)
   lrs = []
   for _ in range(5):
     opt.step()
     sch.step()
     lrs.append(sch.get_last_lr()[0])
+  return lrs
+
+
+def test_semseg_scheduler_and_metrics_against_reference_source(built_lib):
+  """downstream/semseg pieces restated in pointcontrast_amd/downstream/semseg.py: PolyLR against the learning rates the
+  reference's own class produces (lib/solvers.py, recorded in tests/golden/golden_host_ref.json by
+  make_golden_host_ref.py), metrics against hand counts."""
+  import json
+  from pointcontrast_amd.downstream import semseg as ss
+  lrs = poly_lrs(ss.PolyLR, torch.optim.SGD([torch.nn.Parameter(torch.zeros(3))], lr=0.1, momentum=0.9))
   assert abs(lrs[0] - 0.1 * (1 - 1 / 101) ** 0.9) < 1e-12 and lrs == sorted(lrs, reverse=True)
-  ref_path = "/root/reference/downstream/semseg/lib/solvers.py"
-  if os.path.isfile(ref_path):
-    spec = importlib.util.spec_from_file_location("ref_semseg_solvers", ref_path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    opt2 = torch.optim.SGD([torch.nn.Parameter(torch.zeros(3))], lr=0.1, momentum=0.9)
-    sch2 = mod.PolyLR(opt2, max_iter=100, power=0.9)
-    ref_lrs = []
-    for _ in range(5):
-      opt2.step()
-      sch2.step()
-      ref_lrs.append(sch2.get_last_lr()[0])
-    assert ref_lrs == lrs
+  with open(GOLDEN_HOST_REF) as f:
+    ref_lrs = json.load(f)["poly_lr"]
+  assert ref_lrs == lrs
   pred = np.array([0, 1, 1, 2, 2, 2, 0])
   label = np.array([0, 1, 2, 2, 2, 255, 1])
   h = ss.fast_hist(pred, label, 3)
@@ -370,37 +368,36 @@ def test_semseg_scheduler_and_metrics_against_reference_source(built_lib):
   assert abs(ss.precision_at_one(torch.from_numpy(pred), torch.from_numpy(label)) - 100 * 4 / 6) < 1e-4
 
 
+def sampler_stream(mod, make, n=45):
+  """n indices of make(mod), each followed by a draw of another consumer of the global torch RNG."""
+  torch.manual_seed(3)
+  s = make(mod)
+  out = []
+  for i in range(n):
+    out.append(next(s))
+    out.append(float(torch.rand(1)))  # another consumer of the RNG between two indices
+  return out
+
+
+_SAMPLER_DATA = list(range(11))
+SAMPLER_CASES = {"inf_shuffle%d" % sh: (lambda m, sh=sh: m.InfSampler(_SAMPLER_DATA, bool(sh))) for sh in (0, 1)}
+SAMPLER_CASES.update({"dist_w%d_r%d" % (w, r): (lambda m, w=w, r=r: m.DistributedInfSampler(_SAMPLER_DATA, w, r, True))
+                      for w in (2, 3, 4) for r in range(w)})
+
+
 def test_samplers_reproduce_the_reference_classes():
-  """lib/data_sampler.py against the reference's own InfSampler / DistributedInfSampler (pc/lib/data_sampler.py imports
-  only torch: executed from /root/reference where present): identical index streams AND identical positions of the
-  permutation draws in the global torch RNG stream (other consumers of that stream -- the NCE trainer's Uniform
-  draws -- sit between them)."""
-  import importlib.util
-  path = "/root/reference/pretrain/pointcontrast/lib/data_sampler.py"
-  if not os.path.isfile(path):
-    pytest.skip("/root/reference is not present on this host")
-  spec = importlib.util.spec_from_file_location("ref_sampler", path)
-  ref = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(ref)
+  """lib/data_sampler.py against what the reference's own InfSampler / DistributedInfSampler produce (pc/lib/
+  data_sampler.py, recorded in tests/golden/golden_host_ref.json by make_golden_host_ref.py): identical index streams
+  AND identical positions of the permutation draws in the global torch RNG stream (other consumers of that stream --
+  the NCE trainer's Uniform draws -- sit between them)."""
+  import json
   from pointcontrast_amd.lib import data_sampler as ds
-  data = list(range(11))
-
-  def stream(mod, make, n=45):
-    torch.manual_seed(3)
-    s = make(mod)
-    out = []
-    for i in range(n):
-      out.append(next(s))
-      out.append(float(torch.rand(1)))  # another consumer of the RNG between two indices
-    return out
-
-  for shuffle in (False, True):
-    assert stream(ref, lambda m: m.InfSampler(data, shuffle)) == stream(ds, lambda m: m.InfSampler(data, shuffle))
-  for world in (2, 3, 4):
-    for rank in range(world):
-      mk = lambda m: m.DistributedInfSampler(data, world, rank, True)
-      assert stream(ref, mk) == stream(ds, mk), (world, rank)
-      assert len(mk(ref)) == len(mk(ds))
+  with open(GOLDEN_HOST_REF) as f:
+    ref = json.load(f)["sampler"]
+  assert sorted(ref) == sorted(SAMPLER_CASES)
+  for key, make in SAMPLER_CASES.items():
+    assert sampler_stream(ds, make) == ref[key]["stream"], key
+    assert len(make(ds)) == ref[key]["len"], key
 
 
 def test_pairs_scan_host_counts_runs_and_detects_unsorted_input(built_lib):
