@@ -159,6 +159,33 @@ int pcmi_kmap_export(const pcmi_kmap_t* map, int32_t* nbr, int32_t* pair_in, int
                      pcmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Instances -- replaces ME's origin coordinates (CoordsManager::getOriginCoords) and the
+ * per-batch-index row lists behind
+ *   ME.MinkowskiGlobalPooling                      pc/model/res16unet.py:10 (import);
+ *                                                  downstream/semseg/lib/layers.py:54-90
+ *   ME.MinkowskiInstanceNorm                       pc/model/modules/common.py:22-23
+ * An instance is one batch index (column 0 of the coordinates).  Rows need not be sorted
+ * by it.  The origin key holds one row (b, 0, 0, 0) per distinct batch index, ascending,
+ * tensor stride 0; it has no hash and no kernel maps.
+ * ------------------------------------------------------------------------------------------ */
+#define PCMI_SEGMENT_CHUNK 256 /* rows per work unit of the segment reductions */
+typedef struct pcmi_segments {
+  int64_t n;                 /* rows of the key */
+  int64_t n_inst;            /* instances: distinct batch indices */
+  int64_t n_chunks;          /* chunk_offs[n_inst] */
+  const int32_t* rows;       /* [n] the key's rows grouped by instance (ascending batch index), ascending inside one */
+  const int32_t* offs;       /* [n_inst + 1] instance i holds rows[offs[i] .. offs[i+1]) */
+  const int32_t* inst;       /* [n] instance of every row */
+  const int32_t* chunk_offs; /* [n_inst + 1] instance i is split into chunks chunk_offs[i] .. chunk_offs[i+1]) of
+                              * PCMI_SEGMENT_CHUNK rows (the last one shorter) */
+} pcmi_segments_t;
+/* The origin key (built from key 0 on the first call, cached until reset).  Syncs on a miss (n_inst). */
+int pcmi_coords_origin(pcmi_coords_t* h, int* key, int64_t* n_inst, pcmi_stream_t stream);
+/* Row -> instance CSR of `key`: a 1024-bin histogram of the batch index, a scan and a stable scatter, on the device.
+ * Cached in the arena per key until reset.  Syncs on a miss (n_inst, n_chunks). */
+int pcmi_coords_segments(pcmi_coords_t* h, int key, pcmi_segments_t* out, pcmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sparse convolution -- replaces MEB.Convolution{Forward,Backward}GPU and
  * ConvolutionTranspose{Forward,Backward}GPU (pc/model/modules/common.py:117-168; 63 modules
  * in Res16UNet34C).  weight is [K, cin, cout] fp32 (K == 1: [cin, cout], map == NULL: the
@@ -238,6 +265,70 @@ int pcmi_gather_rows(const float* src, int64_t src_ld, const int64_t* idx, int64
                      float* dst, int64_t dst_ld, pcmi_stream_t stream);
 int pcmi_scatter_add_rows(const float* src, int64_t src_ld, const int64_t* idx, int64_t n, int c,
                           float* dst, int64_t dst_ld, pcmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Pooling over kernel maps (csrc/pool.hip) -- replaces MEB.{Sum,Avg}Pooling{Forward,Backward}GPU and
+ * PoolingTranspose{Forward,Backward}GPU:
+ *   ME.MinkowskiSumPooling                         pc/model/modules/common.py:203-214; pc/model/resnet.py:63
+ *   ME.MinkowskiAvgPooling                         pc/model/modules/common.py:170-186
+ *   ME.MinkowskiAvgUnpooling                       pc/model/modules/common.py:189-200
+ * map: a pcmi_kmap_get map, (k=3, s=1) on one key or (k=2, s=2) from a key to its strided key, with its pair
+ * counts on the host (M >= 0).  Any c >= 1.
+ * pool_fwd: out[j] = sum_k in[nbr[k][j]]; average != 0 divides by the number of present neighbours of j (ME's
+ *   "nonzero average": sum_pool(x) / sum_pool(mask)).  out has map.n_out rows.
+ * pool_bwd: gin (map.n_in rows) = the adjoint, in gather form: stride 1 through the mirrored offsets, stride 2 one
+ *   write per fine row from the pair lists.  ws: pcmi_pool_workspace_bytes(map.n_out) (the counts of the average).
+ * unpool_fwd: out[child] = in[parent] onto the finer key (map: fine -> coarse k2/s2, the conv_tr map; sum and
+ *   average coincide since every child has one parent); out has map.n_in rows.  unpool_bwd: the 8-way gather
+ *   gin[j] = sum_k gout[nbr[k][j]] (map.n_out rows).
+ * No float atomics: every result is reproducible bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+size_t pcmi_pool_workspace_bytes(int64_t n_out);
+int pcmi_pool_fwd(const float* in, int64_t in_ld, int c, const pcmi_kmap_t* map, int average, float* out,
+                  int64_t out_ld, pcmi_stream_t stream);
+int pcmi_pool_bwd(const float* gout, int64_t gout_ld, int c, const pcmi_kmap_t* map, int average, float* gin,
+                  int64_t gin_ld, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_unpool_fwd(const float* in, int64_t in_ld, int c, const pcmi_kmap_t* map, float* out, int64_t out_ld,
+                    pcmi_stream_t stream);
+int pcmi_unpool_bwd(const float* gout, int64_t gout_ld, int c, const pcmi_kmap_t* map, float* gin, int64_t gin_ld,
+                    pcmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-instance reductions over pcmi_segments_t (csrc/pool.hip) -- replaces
+ *   ME.MinkowskiGlobalPooling(average)             pc/model/res16unet.py:10; downstream/semseg/lib/layers.py:54-90
+ *   ME.MinkowskiBroadcast{Addition,Multiplication} downstream/semseg/lib/layers.py:54-90
+ *   ME.MinkowskiInstanceNorm                       pc/model/modules/common.py:22-23;
+ *                                                  downstream/semseg/models/modules/resnet_block.py:67-72
+ * A segment's rows are split over many workgroups (chunks of PCMI_SEGMENT_CHUNK rows, fp64 partial sums) and a second
+ * pass adds the partials of each instance in chunk order: no float atomics, reproducible bit for bit.
+ * global_pool_fwd: out [n_inst, c] = per-instance sum (average: mean) of x.  global_pool_bwd: gin[r] = gout[inst(r)]
+ *   (average: / rows of the instance).
+ * broadcast (op 0: add, 1: multiply): out[r] = x[r] op g[inst(r)], g [n_inst, c].  bwd: gx (nullable) and gg
+ *   (nullable, [n_inst, c]: the segment sum of gout, resp. of gout * x).
+ * instnorm_fwd: per instance and channel mean and biased variance (centred second pass), y = relu?((x - mean) * invstd
+ *   * weight + bias (+ residual)), weight / bias [c] shared by the instances; writes mean / invstd [n_inst, c].
+ *   instnorm_bwd: dx, dres (nullable), dweight, dbias [c] (summed over the instances in order); y (nullable) is the
+ *   forward output whose sign gives the ReLU mask.
+ * ws: pcmi_segments_workspace_bytes(seg, c).
+ * ------------------------------------------------------------------------------------------ */
+size_t pcmi_segments_workspace_bytes(const pcmi_segments_t* seg, int c);
+int pcmi_global_pool_fwd(const float* x, int64_t x_ld, int c, const pcmi_segments_t* seg, int average, float* out,
+                         int64_t out_ld, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_global_pool_bwd(const float* gout, int64_t gout_ld, int c, const pcmi_segments_t* seg, int average,
+                         float* gin, int64_t gin_ld, pcmi_stream_t stream);
+int pcmi_broadcast_fwd(const float* x, int64_t x_ld, const float* g, int64_t g_ld, int c, const pcmi_segments_t* seg,
+                       int op, float* out, int64_t out_ld, pcmi_stream_t stream);
+int pcmi_broadcast_bwd(const float* gout, int64_t gout_ld, const float* x, int64_t x_ld, const float* g, int64_t g_ld,
+                       int c, const pcmi_segments_t* seg, int op, float* gx, int64_t gx_ld, float* gg, int64_t gg_ld,
+                       void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_instnorm_fwd(const float* x, int64_t x_ld, int c, const pcmi_segments_t* seg, const float* weight,
+                      const float* bias, float eps, const float* residual, int64_t res_ld, int relu, float* y,
+                      int64_t y_ld, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes,
+                      pcmi_stream_t stream);
+int pcmi_instnorm_bwd(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y,
+                      int64_t y_ld, int c, const pcmi_segments_t* seg, const float* weight, const float* save_mean,
+                      const float* save_invstd, float* dx, int64_t dx_ld, float* dres, int64_t dres_ld,
+                      float* dweight, float* dbias, void* ws, size_t ws_bytes, pcmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Positive-pair selection of the PointInfoNCE step (pc/lib/ddp_trainer.py:400-417; csrc/pairs.hip):

@@ -41,6 +41,15 @@ class KMap(C.Structure):
 _KP = C.POINTER(KMap)
 
 
+class Segments(C.Structure):
+  """struct pcmi_segments (include/pcmi.h): the row -> instance (batch index) CSR of one key."""
+  _fields_ = [("n", c_i64), ("n_inst", c_i64), ("n_chunks", c_i64),
+              ("rows", c_vp), ("offs", c_vp), ("inst", c_vp), ("chunk_offs", c_vp)]
+
+
+_SP = C.POINTER(Segments)
+
+
 class NetTensor(C.Structure):
   """struct pcmi_net_tensor."""
   _fields_ = [("level", c_i32), ("channels", c_i32), ("parent", c_i32), ("col_off", c_i32)]
@@ -79,6 +88,8 @@ PROTOTYPES = {
     "pcmi_kernel_offsets": (C.c_int, [C.c_int, C.c_int, C.POINTER(c_i32), C.POINTER(C.c_int)]),
     "pcmi_kmap_get": (C.c_int, [c_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _KP, c_vp]),
     "pcmi_kmap_export": (C.c_int, [_KP, c_vp, c_vp, c_vp, c_vp]),
+    "pcmi_coords_origin": (C.c_int, [c_vp, C.POINTER(C.c_int), C.POINTER(c_i64), c_vp]),
+    "pcmi_coords_segments": (C.c_int, [c_vp, C.c_int, _SP, c_vp]),
     "pcmi_spconv_workspace_bytes": (c_sz, [c_i64, c_i64, C.c_int, C.c_int, C.c_int, c_i64]),
     "pcmi_spconv_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, _KP, C.c_int, c_vp, c_vp, c_i64,
                                   c_i64, c_vp, c_sz, c_vp]),
@@ -101,6 +112,21 @@ PROTOTYPES = {
     "pcmi_l2norm_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp, c_i64, c_vp]),
     "pcmi_gather_rows": (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp, c_i64, c_vp]),
     "pcmi_scatter_add_rows": (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp, c_i64, c_vp]),
+    "pcmi_pool_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_pool_fwd": (C.c_int, [c_vp, c_i64, C.c_int, _KP, C.c_int, c_vp, c_i64, c_vp]),
+    "pcmi_pool_bwd": (C.c_int, [c_vp, c_i64, C.c_int, _KP, C.c_int, c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "pcmi_unpool_fwd": (C.c_int, [c_vp, c_i64, C.c_int, _KP, c_vp, c_i64, c_vp]),
+    "pcmi_unpool_bwd": (C.c_int, [c_vp, c_i64, C.c_int, _KP, c_vp, c_i64, c_vp]),
+    "pcmi_segments_workspace_bytes": (c_sz, [_SP, C.c_int]),
+    "pcmi_global_pool_fwd": (C.c_int, [c_vp, c_i64, C.c_int, _SP, C.c_int, c_vp, c_i64, c_vp, c_sz, c_vp]),
+    "pcmi_global_pool_bwd": (C.c_int, [c_vp, c_i64, C.c_int, _SP, C.c_int, c_vp, c_i64, c_vp]),
+    "pcmi_broadcast_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.c_int, _SP, C.c_int, c_vp, c_i64, c_vp]),
+    "pcmi_broadcast_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, _SP, C.c_int, c_vp, c_i64, c_vp,
+                                     c_i64, c_vp, c_sz, c_vp]),
+    "pcmi_instnorm_fwd": (C.c_int, [c_vp, c_i64, C.c_int, _SP, c_vp, c_vp, c_f32, c_vp, c_i64, C.c_int, c_vp, c_i64,
+                                    c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_instnorm_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, _SP, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                    c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_nce_workspace_bytes": (c_sz, [c_i64, C.c_int]),
     "pcmi_nce_fwd": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_nce_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -89,6 +89,9 @@ struct Level {
   int32_t* parent = nullptr;  // valid once the next coarser level exists
   int child_key = -1;         // key of that coarser level
   int64_t split = -1;         // >= 0: rows [0, split) belong to the first segment (pcmi_coords_set_split)
+  bool has_seg = false;       // pcmi_coords_segments has built `seg` (arena-resident until reset)
+  pcmi_segments_t seg{};
+  int32_t* inst_batch = nullptr;  // [seg.n_inst] batch index of every instance
 };
 
 struct MapEntry {
@@ -119,6 +122,7 @@ struct pcmi_coords {
   hipEvent_t ev_plan = nullptr;
   bool plan_recorded = false;
   bool insert_unchecked = false;  // pcmi_coords_insert_deferred: the status words have not been read yet
+  int origin_key = -1;            // pcmi_coords_origin: the key of the (b, 0, 0, 0) rows, once built
 };
 constexpr int kMaxLevels = 16;
 constexpr int kStatusSlot = 2;  // h_pinned[2]: the two int32 status words of the insert (duplicates, out-of-range rows)
@@ -155,6 +159,7 @@ static void discard_after_bad_insert(pcmi_coords_t* h) {
   h->maps.clear();
   h->pending.clear();
   h->plan_recorded = false;
+  h->origin_key = -1;
   h->persistent.reset();
   h->scratch.reset();
 }
@@ -570,6 +575,7 @@ int pcmi_coords_reset(pcmi_coords_t* h) {
   h->defer_maps = false;
   h->plan_recorded = false;
   h->insert_unchecked = false;
+  h->origin_key = -1;
   h->persistent.reset();
   h->scratch.reset();
   return PCMI_OK;
@@ -675,6 +681,7 @@ int pcmi_coords_stride(pcmi_coords_t* h, int in_key, int stride, int* out_key, i
                        pcmi_stream_t stream) {
   PCMI_REQUIRE(h && in_key >= 0 && in_key < (int)h->levels.size(), PCMI_ERR_NOKEY, "coords_stride: unknown key %d", in_key);
   PCMI_REQUIRE(stride == 2, PCMI_ERR_UNSUPPORTED, "coords_stride: only stride 2 is on the hot path");
+  PCMI_REQUIRE(h->levels[in_key].ts > 0, PCMI_ERR_UNSUPPORTED, "coords_stride: the origin key has no strided key");
   if (h->levels[in_key].child_key >= 0) {
     const int ck = h->levels[in_key].child_key;
     if (out_key) *out_key = ck;
@@ -754,6 +761,8 @@ static int kmap_get_impl(pcmi_coords_t* h, int in_key, int out_key, int kernel_s
                "kmap_get: kernel %d / stride %d is not on the hot path", kernel_size, stride);
   PCMI_REQUIRE(region == PCMI_REGION_HYPERCUBE || region == PCMI_REGION_HYBRID, PCMI_ERR_UNSUPPORTED,
                "kmap_get: region %d not on the hot path", region);
+  PCMI_REQUIRE(h->levels[in_key].ts > 0 && h->levels[out_key].ts > 0, PCMI_ERR_UNSUPPORTED,
+               "kmap_get: the origin key has no kernel maps");
   if (kernel_size == 2) region = PCMI_REGION_HYPERCUBE;  // even kernels enumerate identically
   for (auto& e : h->maps)
     if (e.in_key == in_key && e.out_key == out_key && e.ksize == kernel_size && e.stride == stride &&
@@ -1030,6 +1039,179 @@ int pcmi_coords_plan_unet(pcmi_coords_t* h, int n_down, int first_region, int bl
   }
   PCMI_HIP_CHECK(hipEventRecord(h->ev_plan, st));
   h->plan_recorded = true;
+  return PCMI_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// instances: the row -> batch-index CSR of a key (pcmi_coords_segments) and the origin key (pcmi_coords_origin)
+//   seg_hist:    per 256-row block, a 1024-bin histogram of the batch index (LDS integer atomics), written bin-major:
+//                cnt[b * nblk + blk]
+//   scan:        exclusive scan of cnt in that order -> base[b * nblk + blk] = first position of block blk's rows of
+//                batch index b in the grouped order (ascending batch index, ascending row inside it)
+//   seg_bins:    one workgroup: instances = non-empty bins, their offsets and chunk counts
+//   seg_scatter: the stable scatter -- a row's position is its block's base plus its rank among the block's earlier
+//                rows with the same batch index
+// ---------------------------------------------------------------------------------------------
+namespace pcmi {
+
+constexpr int kSegBlock = 256;
+constexpr int kSegBins = 1024;  // the batch index has 10 bits (pack_key)
+
+__global__ __launch_bounds__(kSegBlock) void seg_hist_kernel(const int32_t* __restrict__ coords, int64_t n, int64_t nblk,
+                                                             int32_t* __restrict__ cnt) {
+  __shared__ int32_t hist[kSegBins];
+  for (int b = threadIdx.x; b < kSegBins; b += kSegBlock) hist[b] = 0;
+  __syncthreads();
+  const int64_t r = (int64_t)blockIdx.x * kSegBlock + threadIdx.x;
+  if (r < n) atomicAdd(&hist[coords[r * 4] & (kSegBins - 1)], 1);
+  __syncthreads();
+  for (int b = threadIdx.x; b < kSegBins; b += kSegBlock) cnt[(int64_t)b * nblk + blockIdx.x] = hist[b];
+}
+
+// inclusive scan of one value per thread over a kSegBins-thread workgroup
+__device__ inline int32_t seg_block_scan(int32_t v, int32_t* s) {
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+  for (int d = 1; d < kSegBins; d <<= 1) {
+    const int32_t add = t >= d ? s[t - d] : 0;
+    __syncthreads();
+    s[t] += add;
+    __syncthreads();
+  }
+  const int32_t r = s[t];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(kSegBins) void seg_bins_kernel(const int32_t* __restrict__ base, int64_t n, int64_t nblk,
+                                                            int32_t* __restrict__ inst_of_bin, int32_t* __restrict__ offs,
+                                                            int32_t* __restrict__ chunk_offs, int32_t* __restrict__ inst_batch,
+                                                            int64_t* __restrict__ totals) {
+  __shared__ int32_t s[kSegBins];
+  const int b = threadIdx.x;
+  const int32_t start = n > 0 ? base[(int64_t)b * nblk] : 0;
+  const int32_t end = b + 1 < kSegBins ? (n > 0 ? base[(int64_t)(b + 1) * nblk] : 0) : (int32_t)n;
+  const int32_t rows = end - start;
+  const int32_t flag = rows > 0 ? 1 : 0;
+  const int32_t inst_incl = seg_block_scan(flag, s);
+  const int32_t inst = inst_incl - flag;
+  const int32_t chunks = flag ? (rows + PCMI_SEGMENT_CHUNK - 1) / PCMI_SEGMENT_CHUNK : 0;
+  const int32_t chunk_incl = seg_block_scan(chunks, s);
+  inst_of_bin[b] = flag ? inst : -1;
+  if (flag) {
+    offs[inst] = start;
+    chunk_offs[inst] = chunk_incl - chunks;
+    inst_batch[inst] = b;
+  }
+  if (b == kSegBins - 1) {
+    offs[inst_incl] = (int32_t)n;
+    chunk_offs[inst_incl] = chunk_incl;
+    totals[0] = inst_incl;
+    totals[1] = chunk_incl;
+  }
+}
+
+__global__ __launch_bounds__(kSegBlock) void seg_scatter_kernel(const int32_t* __restrict__ coords, int64_t n, int64_t nblk,
+                                                                const int32_t* __restrict__ base,
+                                                                const int32_t* __restrict__ inst_of_bin,
+                                                                int32_t* __restrict__ rows, int32_t* __restrict__ inst) {
+  __shared__ int32_t sb[kSegBlock];
+  const int64_t r = (int64_t)blockIdx.x * kSegBlock + threadIdx.x;
+  const int32_t b = r < n ? (coords[r * 4] & (kSegBins - 1)) : -1;
+  sb[threadIdx.x] = b;
+  __syncthreads();
+  if (r >= n) return;
+  int32_t rank = 0;
+  for (int j = 0; j < (int)threadIdx.x; ++j) rank += sb[j] == b ? 1 : 0;
+  rows[base[(int64_t)b * nblk + blockIdx.x] + rank] = (int32_t)r;
+  inst[r] = inst_of_bin[b];
+}
+
+__global__ void origin_coords_kernel(const int32_t* __restrict__ inst_batch, int64_t n_inst, int32_t* __restrict__ coords) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_inst) reinterpret_cast<int4*>(coords)[i] = make_int4(inst_batch[i], 0, 0, 0);
+}
+
+}  // namespace pcmi
+
+extern "C" {
+
+int pcmi_coords_segments(pcmi_coords_t* h, int key, pcmi_segments_t* out, pcmi_stream_t stream) {
+  PCMI_REQUIRE(h && out, PCMI_ERR_INVALID, "coords_segments: null argument");
+  PCMI_REQUIRE(key >= 0 && key < (int)h->levels.size(), PCMI_ERR_NOKEY, "coords_segments: unknown key %d", key);
+  if (h->levels[key].has_seg) {
+    *out = h->levels[key].seg;
+    return PCMI_OK;
+  }
+  hipStream_t st = as_stream(stream);
+  h->scratch.reset();
+  const Level& L = h->levels[key];
+  const int64_t n = L.n;
+  const int64_t nblk = std::max<int64_t>(ceil_div(n, kSegBlock), 1);
+  int32_t* cnt = h->scratch.alloc_n<int32_t>(kSegBins * nblk);
+  int32_t* base = h->scratch.alloc_n<int32_t>(kSegBins * nblk);
+  int32_t* inst_of_bin = h->scratch.alloc_n<int32_t>(kSegBins);
+  int32_t* rows = h->persistent.alloc_n<int32_t>(n);
+  int32_t* inst = h->persistent.alloc_n<int32_t>(n);
+  int32_t* offs = h->persistent.alloc_n<int32_t>(kSegBins + 1);
+  int32_t* chunk_offs = h->persistent.alloc_n<int32_t>(kSegBins + 1);
+  int32_t* inst_batch = h->persistent.alloc_n<int32_t>(kSegBins);
+  if (!cnt || !base || !inst_of_bin || !rows || !inst || !offs || !chunk_offs || !inst_batch) return PCMI_ERR_HIP;
+  if (n > 0) {
+    seg_hist_kernel<<<dim3((unsigned)nblk), kSegBlock, 0, st>>>(L.coords, n, nblk, cnt);
+    PCMI_LAUNCH_CHECK();
+    int rc = exclusive_scan<false>(cnt, kSegBins * nblk, base, nullptr, h->scratch, st);
+    if (rc) return rc;
+  }
+  seg_bins_kernel<<<1, kSegBins, 0, st>>>(base, n, nblk, inst_of_bin, offs, chunk_offs, inst_batch, h->d_total);
+  PCMI_LAUNCH_CHECK();
+  if (n > 0) {
+    seg_scatter_kernel<<<dim3((unsigned)nblk), kSegBlock, 0, st>>>(L.coords, n, nblk, base, inst_of_bin, rows, inst);
+    PCMI_LAUNCH_CHECK();
+  }
+  int rc = read_back(h, h->d_total, 16, st);
+  if (rc) return rc;
+  rc = check_insert_status(h);
+  if (rc) return rc;
+  Level& Lw = h->levels[key];
+  Lw.seg.n = n;
+  Lw.seg.n_inst = h->h_pinned[0];
+  Lw.seg.n_chunks = h->h_pinned[1];
+  Lw.seg.rows = rows;
+  Lw.seg.offs = offs;
+  Lw.seg.inst = inst;
+  Lw.seg.chunk_offs = chunk_offs;
+  Lw.inst_batch = inst_batch;
+  Lw.has_seg = true;
+  *out = Lw.seg;
+  return PCMI_OK;
+}
+
+int pcmi_coords_origin(pcmi_coords_t* h, int* key, int64_t* n_inst, pcmi_stream_t stream) {
+  PCMI_REQUIRE(h && key, PCMI_ERR_INVALID, "coords_origin: null argument");
+  PCMI_REQUIRE(!h->levels.empty(), PCMI_ERR_NOKEY, "coords_origin: insert coordinates first");
+  if (h->origin_key < 0) {
+    pcmi_segments_t seg;
+    int rc = pcmi_coords_segments(h, 0, &seg, stream);
+    if (rc) return rc;
+    Level O;
+    O.ts = 0;
+    O.n = seg.n_inst;
+    O.coords = h->persistent.alloc_n<int32_t>(O.n * 4);
+    if (!O.coords) return PCMI_ERR_HIP;
+    if (O.n > 0) {
+      origin_coords_kernel<<<dim3((unsigned)ceil_div(O.n, 256)), 256, 0, as_stream(stream)>>>(h->levels[0].inst_batch, O.n,
+                                                                                              O.coords);
+      PCMI_LAUNCH_CHECK();
+    }
+    h->levels.push_back(O);
+    h->origin_key = (int)h->levels.size() - 1;
+  }
+  *key = h->origin_key;
+  if (n_inst) *n_inst = h->levels[h->origin_key].n;
   return PCMI_OK;
 }
 

@@ -420,3 +420,158 @@ def sgd_step(w, g, v, lr, momentum, weight_decay, grad_scale=1.0, dampening=0.0,
   require_cuda(w, "sgd step")
   check(lib.pcmi_sgd_step_dampened(ptr(w), ptr(g), ptr(v), w.numel(), float(lr), float(momentum), float(dampening),
                                    float(weight_decay), float(grad_scale), int(bool(first_step)), cur_stream(w.device)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pooling over kernel maps, per-instance reductions, instance norm (csrc/pool.hip); `owner` keeps the coordinate manager
+# -- and the arena behind the map / segment tables -- alive until backward
+# ---------------------------------------------------------------------------------------------------------------------
+def _packed(t):
+  """Row-major fp32 rows with a 16-byte aligned base and a leading dimension that is a multiple of 4 (else a copy)."""
+  require_cuda(t, "pooling")
+  return _c(t.float() if t.dtype != torch.float32 else t)
+
+
+class PoolFunction(Function):
+  """MinkowskiSumPooling / MinkowskiAvgPooling over a (k=3, s=1) or (k=2, s=2) map (pc/model/modules/common.py:170-214)."""
+
+  @staticmethod
+  def forward(ctx, feats, kmap, average, owner=None):
+    x = _packed(feats)
+    n, c, ld = _rows(x)
+    assert n == kmap.n_in, "pooling: %d rows for a map with %d input rows" % (n, kmap.n_in)
+    out = torch.empty((kmap.n_out, c), dtype=torch.float32, device=x.device)
+    check(lib.pcmi_pool_fwd(ptr(x), ld, c, C.byref(kmap), int(average), ptr(out), c, cur_stream(x.device)))
+    ctx.kmap, ctx.average, ctx.owner, ctx.c = kmap, int(average), owner, c
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    g = _packed(gout)
+    kmap, dev = ctx.kmap, g.device
+    gin = torch.empty((kmap.n_in, ctx.c), dtype=torch.float32, device=dev)
+    ws, wsb = ws_args(lib.pcmi_pool_workspace_bytes(kmap.n_out), dev)
+    check(lib.pcmi_pool_bwd(ptr(g), g.stride(0), ctx.c, C.byref(kmap), ctx.average, ptr(gin), ctx.c, ws, wsb,
+                            cur_stream(dev)))
+    return gin, None, None, None
+
+
+class UnpoolFunction(Function):
+  """MinkowskiAvgUnpooling / MinkowskiPoolingTranspose(2, 2): out[child] = in[parent] on the existing finer key
+  (pc/model/modules/common.py:189-200).  kmap: the fine -> coarse (k=2, s=2) map, as a transposed conv uses."""
+
+  @staticmethod
+  def forward(ctx, feats, kmap, owner=None):
+    x = _packed(feats)
+    n, c, ld = _rows(x)
+    assert n == kmap.n_out, "unpooling: %d rows for a coarse key of %d rows" % (n, kmap.n_out)
+    out = torch.empty((kmap.n_in, c), dtype=torch.float32, device=x.device)
+    check(lib.pcmi_unpool_fwd(ptr(x), ld, c, C.byref(kmap), ptr(out), c, cur_stream(x.device)))
+    ctx.kmap, ctx.owner, ctx.c = kmap, owner, c
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    g = _packed(gout)
+    kmap = ctx.kmap
+    gin = torch.empty((kmap.n_out, ctx.c), dtype=torch.float32, device=g.device)
+    check(lib.pcmi_unpool_bwd(ptr(g), g.stride(0), ctx.c, C.byref(kmap), ptr(gin), ctx.c, cur_stream(g.device)))
+    return gin, None, None
+
+
+class GlobalPoolFunction(Function):
+  """MinkowskiGlobalPooling(average): per-instance sum or mean, one output row per batch index (ascending)."""
+
+  @staticmethod
+  def forward(ctx, feats, seg, average, owner=None):
+    x = _packed(feats)
+    n, c, ld = _rows(x)
+    assert n == seg.n, "global pooling: %d rows for a key of %d rows" % (n, seg.n)
+    out = torch.empty((seg.n_inst, c), dtype=torch.float32, device=x.device)
+    ws, wsb = ws_args(lib.pcmi_segments_workspace_bytes(C.byref(seg), c), x.device)
+    check(lib.pcmi_global_pool_fwd(ptr(x), ld, c, C.byref(seg), int(average), ptr(out), c, ws, wsb, cur_stream(x.device)))
+    ctx.seg, ctx.average, ctx.owner, ctx.c = seg, int(average), owner, c
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    g = _packed(gout)
+    seg = ctx.seg
+    gin = torch.empty((seg.n, ctx.c), dtype=torch.float32, device=g.device)
+    check(lib.pcmi_global_pool_bwd(ptr(g), g.stride(0), ctx.c, C.byref(seg), ctx.average, ptr(gin), ctx.c,
+                                   cur_stream(g.device)))
+    return gin, None, None, None
+
+
+class BroadcastFunction(Function):
+  """MinkowskiBroadcast{Addition,Multiplication}: out[r] = x[r] op g[instance(r)] (op 0: add, 1: multiply)."""
+
+  @staticmethod
+  def forward(ctx, x, g, seg, op, owner=None):
+    x, g = _packed(x), _packed(g)
+    n, c, ld = _rows(x)
+    assert n == seg.n and g.shape == (seg.n_inst, c), "broadcast: shapes do not match the instances"
+    out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    check(lib.pcmi_broadcast_fwd(ptr(x), ld, ptr(g), g.stride(0), c, C.byref(seg), int(op), ptr(out), c,
+                                 cur_stream(x.device)))
+    ctx.save_for_backward(x if op == 1 else None, g if op == 1 else None)
+    ctx.seg, ctx.op, ctx.owner, ctx.c = seg, int(op), owner, c
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    x, g = ctx.saved_tensors
+    go = _packed(gout)
+    seg, c, dev = ctx.seg, ctx.c, go.device
+    gx = torch.empty((seg.n, c), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+    gg = torch.empty((seg.n_inst, c), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+    ws, wsb = ws_args(lib.pcmi_segments_workspace_bytes(C.byref(seg), c), dev)
+    check(lib.pcmi_broadcast_bwd(ptr(go), go.stride(0), ptr(x), x.stride(0) if x is not None else 0, ptr(g),
+                                 g.stride(0) if g is not None else 0, c, C.byref(seg), ctx.op, ptr(gx), c, ptr(gg), c,
+                                 ws, wsb, cur_stream(dev)))
+    return gx, gg, None, None, None
+
+
+class InstanceNormFunction(Function):
+  """MinkowskiInstanceNorm (downstream/semseg/lib/layers.py:54-90): per-instance, per-channel mean and biased variance,
+  affine weight / bias shared by the instances, optionally fused with the residual add and ReLU of the blocks."""
+
+  @staticmethod
+  def forward(ctx, x, weight, bias, seg, eps, residual, relu, owner=None):
+    x = _packed(x)
+    n, c, ld = _rows(x)
+    assert n == seg.n, "instance norm: %d rows for a key of %d rows" % (n, seg.n)
+    w, b = weight.reshape(-1).contiguous(), bias.reshape(-1).contiguous()
+    assert w.numel() == c and b.numel() == c, "instance norm: weight / bias of %d for %d channels" % (w.numel(), c)
+    res = _packed(residual) if residual is not None else None
+    assert res is None or res.shape == x.shape, "instance norm: residual %s for features %s" % (res.shape, x.shape)
+    y = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    mean = torch.empty((seg.n_inst, c), dtype=torch.float32, device=x.device)
+    invstd = torch.empty((seg.n_inst, c), dtype=torch.float32, device=x.device)
+    ws, wsb = ws_args(lib.pcmi_segments_workspace_bytes(C.byref(seg), c), x.device)
+    check(lib.pcmi_instnorm_fwd(ptr(x), ld, c, C.byref(seg), ptr(w), ptr(b), float(eps), ptr(res),
+                                res.stride(0) if res is not None else 0, int(relu), ptr(y), c, ptr(mean), ptr(invstd),
+                                ws, wsb, cur_stream(x.device)))
+    ctx.save_for_backward(x, w, mean, invstd, y if relu else None)
+    ctx.seg, ctx.owner, ctx.has_res, ctx.wshape, ctx.bshape = seg, owner, residual is not None, weight.shape, bias.shape
+    return y
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, dy):
+    x, w, mean, invstd, y = ctx.saved_tensors
+    dy = _packed(dy)
+    n, c, x_ld = _rows(x)
+    dev, seg = x.device, ctx.seg
+    dx = torch.empty((n, c), dtype=torch.float32, device=dev)
+    dres = torch.empty((n, c), dtype=torch.float32, device=dev) if ctx.has_res else None
+    dw = torch.empty(c, dtype=torch.float32, device=dev)
+    db = torch.empty(c, dtype=torch.float32, device=dev)
+    ws, wsb = ws_args(lib.pcmi_segments_workspace_bytes(C.byref(seg), c), dev)
+    check(lib.pcmi_instnorm_bwd(ptr(dy), dy.stride(0), ptr(x), x_ld, ptr(y), c, c, C.byref(seg), ptr(w), ptr(mean),
+                                ptr(invstd), ptr(dx), c, ptr(dres), c, ptr(dw), ptr(db), ws, wsb, cur_stream(dev)))
+    return dx, dw.reshape(ctx.wshape), db.reshape(ctx.bshape), None, None, dres, None, None

@@ -6,9 +6,15 @@ Symbols (exhaustive list of what pc/ imports from ME -- SURVEY.md 8b):
   CoordsManager, MinkowskiNetwork, MinkowskiConvolution,
   MinkowskiConvolutionTranspose, MinkowskiBatchNorm (.bn), MinkowskiReLU,
   KernelGenerator, RegionType, MinkowskiOps.cat, utils.sparse_quantize.
+Beyond the pre-training path, the rest of what the reference's model code reaches
+for (pc/model/modules/common.py:22-23,170-214; downstream/semseg/lib/layers.py:54-90):
+  MinkowskiSumPooling, MinkowskiAvgPooling ((k=3, s=1) and (k=2, s=2) maps),
+  MinkowskiAvgUnpooling, MinkowskiPoolingTranspose (k=2, s=2), MinkowskiGlobalPooling,
+  MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication, MinkowskiInstanceNorm.
+These run eagerly (HIP kernels of csrc/pool.hip); the native engine does not lower
+them, and tracing a model that uses one raises NotImplementedError naming it.
 Usage mirrors the reference: ``import pointcontrast_amd.minkowski as ME``.
-Anything else ME offers (pooling, instance norm, pruning ...) is outside the hot
-path and raises NotImplementedError.
+Anything else ME offers (max pooling, pruning ...) raises NotImplementedError.
 """
 import contextlib
 import ctypes as C
@@ -23,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import lib, check, KMap
+from ._lib import lib, check, KMap, Segments
 from . import functional as PF
 from .runtime import ptr, handle_pool, require_cuda
 
@@ -121,6 +127,7 @@ class CoordsManager:
     self._plan = handle_pool.plan_stream(self.device)
     self._h, prev_use = handle_pool.acquire(self.device)
     self._maps = {}
+    self._segs = {}
     self._alive = True
     with torch.cuda.device(self.device):
       if prev_use is not None:
@@ -183,6 +190,24 @@ class CoordsManager:
     k = C.c_int()
     check(lib.pcmi_coords_key_at_stride(self._h, int(tensor_stride), C.byref(k)))
     return CoordsKey(k.value, tensor_stride, self.D)
+
+  def origin_key(self):
+    """The key of one (b, 0, 0, 0) row per distinct batch index, ascending, tensor stride 0 (ME's origin coordinates)."""
+    k, n = C.c_int(), C.c_int64()
+    with torch.cuda.device(self.device):
+      check(lib.pcmi_coords_origin(self._h, C.byref(k), C.byref(n), self._st()))
+    return CoordsKey(k.value, 0, self.D)
+
+  def segments(self, key):
+    """The row -> instance (batch index) CSR of `key` (pcmi_segments_t; device tables in the arena)."""
+    kk = key.key if isinstance(key, CoordsKey) else int(key)
+    seg = self._segs.get(kk)
+    if seg is None:
+      seg = Segments()
+      with torch.cuda.device(self.device):
+        check(lib.pcmi_coords_segments(self._h, kk, C.byref(seg), self._st()))
+      self._segs[kk] = seg
+    return seg
 
   def get_coords(self, key):
     n = self.size(key)
@@ -568,22 +593,181 @@ def _sparse_quantize(coords, feats=None, labels=None, return_index=False, quanti
   return out[0] if len(out) == 1 else tuple(out)
 
 
-def _not_on_hot_path(name):
+# ---------------------------------------------------------------------------------------------------------------------
+# pooling, global pooling, broadcast, instance norm: eager only (csrc/pool.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def _eager_only(mod, x):
+  if isinstance(x, SymTensor):
+    raise NotImplementedError("%s runs eagerly only: the native engine cannot lower it" % type(mod).__name__)
+  assert isinstance(x, SparseTensor) and x.coords_man is not None, \
+      "%s: move the SparseTensor to the GPU first (.to(device))" % type(mod).__name__
 
-  class _Missing(nn.Module):
 
-    def __init__(self, *a, **k):
-      raise NotImplementedError("%s is not used by the PointContrast pre-training path and is not provided" % name)
+def _isotropic(v, what, who):
+  if isinstance(v, (list, tuple)):
+    if len(set(v[:3])) != 1:
+      raise NotImplementedError("%s: anisotropic %s %s is not supported" % (who, what, tuple(v)))
+    v = v[0]
+  return int(v)
 
-  _Missing.__name__ = name
-  return _Missing
+
+class _PoolBase(nn.Module):
+  """MinkowskiPoolingBase of ME 0.4.3: (kernel_size, stride, dilation, kernel_generator, dimension).  The maps are the
+  convolutions' own: (k=3, s=1) on the input key, (k=2, s=2) to its strided key (the key a stride-2 conv on the same
+  input gets, so MinkowskiOps.cat of the two works)."""
+  average = False
+  transpose = False
+
+  def __init__(self, kernel_size=-1, stride=1, dilation=1, kernel_generator=None, dimension=None):
+    super().__init__()
+    who = type(self).__name__
+    if dimension != 3:
+      raise NotImplementedError("%s: only D=3 is supported (got dimension=%r)" % (who, dimension))
+    if kernel_generator is not None:
+      kernel_size, stride, dilation = kernel_generator.kernel_size, kernel_generator.stride, kernel_generator.dilation
+    ks, st, dl = _isotropic(kernel_size, "kernel_size", who), _isotropic(stride, "stride", who), \
+        _isotropic(dilation, "dilation", who)
+    if dl != 1:
+      raise NotImplementedError("%s: dilation %d is not supported (the kernel maps have dilation 1)" % (who, dl))
+    ok = ((2, 2),) if self.transpose else ((3, 1), (2, 2))
+    if (ks, st) not in ok:
+      raise NotImplementedError("%s: kernel_size=%d, stride=%d is not supported; the kernel maps offer %s" % (
+          who, ks, st, " and ".join("(kernel_size=%d, stride=%d)" % p for p in ok)))
+    if kernel_generator is None:
+      kernel_generator = KernelGenerator(ks, st, dl, is_transpose=self.transpose, dimension=dimension)
+    self.kernel_generator = kernel_generator
+    self.kernel_size, self.stride, self.dilation, self.dimension = ks, st, dl, dimension
+
+  def forward(self, x):
+    _eager_only(self, x)
+    cm, in_key = x.coords_man, x.coords_key
+    region = self.kernel_generator.region_code
+    if self.transpose:
+      if in_key.tensor_stride < 2:
+        raise ValueError("%s: the input is at tensor stride %d; there is no finer key" % (type(self).__name__,
+                                                                                          in_key.tensor_stride))
+      out_key = cm.key_at_stride(in_key.tensor_stride // self.stride)
+      kmap = cm.kernel_map(out_key, in_key, self.kernel_size, self.stride, region)
+      out = PF.UnpoolFunction.apply(x.F, kmap, cm)
+    else:
+      out_key = cm.stride(in_key, self.stride) if self.stride > 1 else in_key
+      kmap = cm.kernel_map(in_key, out_key, self.kernel_size, self.stride, region)
+      out = PF.PoolFunction.apply(x.F, kmap, self.average, cm)
+    return SparseTensor(out, coords_key=out_key, coords_manager=cm)
+
+  def extra_repr(self):
+    return "kernel_size=%d, stride=%d" % (self.kernel_size, self.stride)
 
 
-MinkowskiInstanceNorm = _not_on_hot_path("MinkowskiInstanceNorm")
-MinkowskiGlobalPooling = _not_on_hot_path("MinkowskiGlobalPooling")
-MinkowskiAvgPooling = _not_on_hot_path("MinkowskiAvgPooling")
-MinkowskiAvgUnpooling = _not_on_hot_path("MinkowskiAvgUnpooling")
-MinkowskiSumPooling = _not_on_hot_path("MinkowskiSumPooling")
+class MinkowskiSumPooling(_PoolBase):
+  """ME.MinkowskiSumPooling: out[j] = sum of the present inputs in j's kernel window (pc/model/modules/common.py:203-214;
+  pc/model/resnet.py:63)."""
+  average = False
+
+
+class MinkowskiAvgPooling(_PoolBase):
+  """ME.MinkowskiAvgPooling: the sum divided by the number of PRESENT inputs of the window (ME's nonzero average;
+  pc/model/modules/common.py:170-186)."""
+  average = True
+
+
+class MinkowskiPoolingTranspose(_PoolBase):
+  """ME.MinkowskiPoolingTranspose with kernel_size=2, stride=2: out[child] = in[parent] onto the already existing finer
+  key (the key a transposed conv of the same input lands on; Appendix A5)."""
+  transpose = True
+
+
+class MinkowskiAvgUnpooling(MinkowskiPoolingTranspose):
+  """ME.MinkowskiAvgUnpooling (pc/model/modules/common.py:189-200).  Every child has exactly one parent under a
+  (k=2, s=2) map, so the average and the sum coincide: out[child] = in[parent]."""
+
+
+class MinkowskiMaxPooling(nn.Module):
+
+  def __init__(self, *a, **k):
+    raise NotImplementedError("MinkowskiMaxPooling is not provided (sum / average pooling are)")
+
+
+class MinkowskiGlobalPooling(nn.Module):
+  """ME.MinkowskiGlobalPooling(average): one row per instance (batch index), ascending, on the origin key (coordinates
+  (b, 0, 0, 0), tensor stride 0); the per-instance mean (average=True) or sum of the features."""
+
+  def __init__(self, average=True, mode=None, dimension=-1):
+    super().__init__()
+    if mode is not None and getattr(mode, "name", str(mode)) not in ("AUTO", "INDEX_SELECT", "SPARSE"):
+      raise NotImplementedError("MinkowskiGlobalPooling: mode %s is not supported" % (mode,))
+    self.average, self.dimension = bool(average), dimension
+
+  def forward(self, x):
+    _eager_only(self, x)
+    cm = x.coords_man
+    seg = cm.segments(x.coords_key)
+    out_key = cm.origin_key()
+    out = PF.GlobalPoolFunction.apply(x.F, seg, self.average, cm)
+    return SparseTensor(out, coords_key=out_key, coords_manager=cm)
+
+  def extra_repr(self):
+    return "average=%s" % self.average
+
+
+class _BroadcastBase(nn.Module):
+  op = 0
+
+  def __init__(self, dimension=-1):
+    super().__init__()
+    self.dimension = dimension
+
+  def forward(self, input, input_glob):
+    _eager_only(self, input)
+    _eager_only(self, input_glob)
+    cm = input.coords_man
+    if input_glob.coords_man is not cm or input_glob.coords_key != cm.origin_key():
+      raise ValueError("%s: the second operand must live on the origin key of the first one's coordinate manager "
+                       "(the output of MinkowskiGlobalPooling)" % type(self).__name__)
+    seg = cm.segments(input.coords_key)
+    out = PF.BroadcastFunction.apply(input.F, input_glob.F, seg, self.op, cm)
+    return SparseTensor(out, coords_key=input.coords_key, coords_manager=cm)
+
+
+class MinkowskiBroadcastAddition(_BroadcastBase):
+  """ME.MinkowskiBroadcastAddition: out[r] = x[r] + g[instance(r)] (downstream/semseg/lib/layers.py:54-90)."""
+  op = 0
+
+
+class MinkowskiBroadcastMultiplication(_BroadcastBase):
+  """ME.MinkowskiBroadcastMultiplication: out[r] = x[r] * g[instance(r)]."""
+  op = 1
+
+
+class MinkowskiInstanceNorm(nn.Module):
+  """ME.MinkowskiInstanceNorm(num_features, eps, D): per instance (batch index) and channel, mean and biased variance;
+  affine ``weight`` / ``bias`` of shape [1, C] shared by the instances; no running statistics, so train and eval agree
+  (downstream/semseg/lib/layers.py:54-90; pc/model/modules/common.py:22-23).  forward(x, residual=None, relu=False)
+  takes the fused epilogue of MinkowskiBatchNorm.forward, so the blocks use either norm unchanged."""
+
+  def __init__(self, num_features, eps=1e-5, D=-1):
+    super().__init__()
+    self.num_features, self.eps, self.D = int(num_features), float(eps), D
+    self.weight = nn.Parameter(torch.ones(1, self.num_features))
+    self.bias = nn.Parameter(torch.zeros(1, self.num_features))
+
+  def reset_parameters(self):
+    with torch.no_grad():
+      self.weight.fill_(1.0)
+      self.bias.zero_()
+
+  def forward(self, x, residual=None, relu=False):
+    _eager_only(self, x)
+    cm = x.coords_man
+    if residual is not None:
+      assert residual.coords_key == x.coords_key, "MinkowskiInstanceNorm: the residual must share the coordinates"
+    seg = cm.segments(x.coords_key)
+    y = PF.InstanceNormFunction.apply(x.F, self.weight, self.bias, seg, self.eps,
+                                      residual.F if residual is not None else None, bool(relu), cm)
+    return SparseTensor(y, coords_key=x.coords_key, coords_manager=cm)
+
+  def extra_repr(self):
+    return "%d, eps=%g" % (self.num_features, self.eps)
 
 MinkowskiOps = types.ModuleType("MinkowskiEngine.MinkowskiOps")
 MinkowskiOps.cat = cat

@@ -1,6 +1,6 @@
 """Layer factories of the pre-training models, same public names as the reference's
-pc/model/modules/common.py (ConvType, NormType, conv, conv_tr, get_norm) so model code written
-against it runs unchanged on the libpcmi-backed Minkowski surface."""
+pc/model/modules/common.py (ConvType, NormType, conv, conv_tr, avg_pool, avg_unpool, sum_pool, get_norm) so
+model code written against it runs unchanged on the libpcmi-backed Minkowski surface."""
 from enum import Enum
 
 from ... import minkowski as ME
@@ -52,7 +52,9 @@ def convert_conv_type(conv_type, kernel_size, D):
 def get_norm(norm_type, n_channels, D, bn_momentum=0.1):
   if norm_type == NormType.BATCH_NORM:
     return ME.MinkowskiBatchNorm(n_channels, momentum=bn_momentum)
-  raise ValueError("Norm type: %s not supported on the pre-training path" % (norm_type,))
+  if norm_type == NormType.SPARSE_INSTANCE_NORM:  # pc/model/modules/common.py:22-23 (eager only: not lowered)
+    return ME.MinkowskiInstanceNorm(n_channels, D=D)
+  raise ValueError("Norm type: %s not supported" % (norm_type,))
 
 
 def _make(cls, in_planes, out_planes, kernel_size, stride, dilation, bias, conv_type, D):
@@ -71,3 +73,25 @@ def conv_tr(in_planes, out_planes, kernel_size, upsample_stride=1, dilation=1, b
             conv_type=ConvType.HYPERCUBE, D=-1):
   return _make(ME.MinkowskiConvolutionTranspose, in_planes, out_planes, kernel_size, upsample_stride, dilation, bias,
                conv_type, D)
+
+
+def _pool(cls, kernel_size, stride, dilation, conv_type, D):
+  assert D > 0, "Dimension must be a positive integer"
+  region_type, axis_types, kernel_size = convert_conv_type(conv_type, kernel_size, D)
+  gen = ME.KernelGenerator(kernel_size, stride, dilation, region_type=region_type, axis_types=axis_types, dimension=D)
+  return cls(kernel_size=kernel_size, stride=stride, dilation=dilation, kernel_generator=gen, dimension=D)
+
+
+def avg_pool(kernel_size, stride=1, dilation=1, conv_type=ConvType.HYPERCUBE, in_coords_key=None, D=-1):
+  """pc/model/modules/common.py:170-186 (in_coords_key is accepted and unused, as there)."""
+  return _pool(ME.MinkowskiAvgPooling, kernel_size, stride, dilation, conv_type, D)
+
+
+def avg_unpool(kernel_size, stride=1, dilation=1, conv_type=ConvType.HYPERCUBE, D=-1):
+  """pc/model/modules/common.py:189-200."""
+  return _pool(ME.MinkowskiAvgUnpooling, kernel_size, stride, dilation, conv_type, D)
+
+
+def sum_pool(kernel_size, stride=1, dilation=1, conv_type=ConvType.HYPERCUBE, D=-1):
+  """pc/model/modules/common.py:203-214."""
+  return _pool(ME.MinkowskiSumPooling, kernel_size, stride, dilation, conv_type, D)

@@ -30,3 +30,8 @@ class BasicBlockBase(nn.Module):
 
 class BasicBlock(BasicBlockBase):
   NORM_TYPE = NormType.BATCH_NORM
+
+
+class BasicBlockIN(BasicBlockBase):
+  """BasicBlock with instance norm (downstream/semseg/models/modules/resnet_block.py:67-68): runs eagerly only."""
+  NORM_TYPE = NormType.SPARSE_INSTANCE_NORM
