@@ -219,6 +219,24 @@ int pcmi_spconv_bwd_weight(const float* in, int64_t in_ld, int64_t n_in, int cin
  * (pc/model/modules/common.py:117-168 reach them through ME.MinkowskiConvolution). */
 int pcmi_spconv_split_precision(void);
 
+/* Convolution precision mode.  PCMI_CONV_PRECISION_FP32 (the default) is the arithmetic above.  In
+ * PCMI_CONV_PRECISION_BF16 the launches the split-precision kernels take by default -- the forward / backward-data
+ * launches of spconv16x (>= 64 channels on both sides, >= 512 rows, table and unit-balanced form) and the weight
+ * gradients of wgrad_x3t (3^3 stride-1 and dense 1x1 layers, >= 8192 rows, >= 64 channels) -- round both operands to
+ * bf16 (round to nearest even) and contract them with ONE bf16 product per 32-channel chunk, fp32 accumulation
+ * (relative error of order 2^-9 per product instead of fp32 round-off).  Every other launch, and every other op, is
+ * bit-identical in both modes; parameters, activations and gradients stay fp32.  PCMI_CONV16_X3=0 is a diagnostic of
+ * the fp32 mode only: with it the forward / backward-data launches take the fp32-MFMA kernel in both modes.  The
+ * reference has no counterpart (its GEMMs are cuBLAS fp32); the switch is the analogue of torch's autocast.
+ *   pcmi_set_conv_precision: the CALLING THREAD's mode for its eager pcmi_spconv_* calls (thread-local, default fp32).
+ *   pcmi_net_set_conv_precision: the mode of every later pcmi_net_forward / pcmi_net_backward of `net`, applied for the
+ *     duration of the call (the thread's own mode is restored on return).
+ * PCMI_ERR_INVALID for any other value. */
+#define PCMI_CONV_PRECISION_FP32 0
+#define PCMI_CONV_PRECISION_BF16 1
+int pcmi_set_conv_precision(int precision);
+int pcmi_get_conv_precision(void);
+
 /* ------------------------------------------------------------------------------------------
  * Normalisation / elementwise
  *   BatchNorm1d inside ME.MinkowskiBatchNorm      pc/model/modules/common.py:19-21
@@ -495,6 +513,9 @@ int pcmi_net_backward(pcmi_net_t* net, int pass, const float* d_out, int64_t d_l
 /* Inside a pcmi_ready_fn callback: `stream` waits (device side, no host wait) for everything that produced the bucket
  * the callback announces.  PCMI_ERR_INVALID outside a backward pass that has announced a bucket. */
 int pcmi_net_stream_wait_bucket(pcmi_net_t* net, pcmi_stream_t stream);
+/* The convolution precision mode (PCMI_CONV_PRECISION_*, see pcmi_set_conv_precision) of every later forward and backward
+ * pass of `net`; a backward pass uses the mode set when it is called.  Default fp32.  PCMI_ERR_INVALID for other values. */
+int pcmi_net_set_conv_precision(pcmi_net_t* net, int precision);
 int pcmi_net_apply_running_stats(pcmi_net_t* net, int pass, pcmi_stream_t stream);
 /* Copy of one activation tensor of the last forward of `pass` (they stay in the pass's arena until its next forward)
  * into caller memory out [rows, out_ld]; rows / channels (nullable) report its shape, out == NULL only queries.  For

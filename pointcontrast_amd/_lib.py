@@ -98,6 +98,8 @@ PROTOTYPES = {
     "pcmi_spconv_bwd_weight": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, c_i64, c_i64, C.c_int, _KP, C.c_int,
                                          c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_spconv_split_precision": (C.c_int, []),
+    "pcmi_set_conv_precision": (C.c_int, [C.c_int]),
+    "pcmi_get_conv_precision": (C.c_int, []),
     "pcmi_bn_workspace_bytes": (c_sz, [c_i64, C.c_int]),
     "pcmi_bn_fwd_train": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp,
                                     c_i64, C.c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -160,6 +162,7 @@ PROTOTYPES = {
                                     c_vp]),
     "pcmi_net_apply_running_stats": (C.c_int, [c_vp, C.c_int, c_vp]),
     "pcmi_net_stream_wait_bucket": (C.c_int, [c_vp, c_vp]),
+    "pcmi_net_set_conv_precision": (C.c_int, [c_vp, C.c_int]),
     "pcmi_net_export_tensor": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(c_i64), C.POINTER(C.c_int), c_vp, c_i64, c_vp]),
     "pcmi_net_memory_bytes": (C.c_int, [c_vp, C.POINTER(c_sz)]),
     "pcmi_net_time_ops": (C.c_int, [c_vp, C.POINTER(C.c_int), C.c_int, C.c_int]),

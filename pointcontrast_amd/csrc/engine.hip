@@ -162,6 +162,7 @@ struct PassState {
   std::vector<X3Prepacked> x3_table;
   std::vector<int> x3_nts;  // slice width per (conv op, orientation) the table was built for
   const float* x3_params = nullptr;
+  int x3_terms = 0;         // bf16 terms the table was built for (3, or 1 in the bf16 conv precision mode)
   bool x3_current = false;  // the last forward of this pass packed (the packs are those of its weights)
   int x3_n_jobs = 0;
   int x3_first_op = -1;
@@ -206,6 +207,7 @@ struct pcmi_net {
   pcmi::DevBuf ws_side[kSides];
   // weight gradients of the coarse levels collected for ONE launch per run of layers (spconv_wgrad.hip: wgrad_group_*)
   pcmi::WgradGroupBuilder* wgroup = nullptr;
+  int conv_precision = PCMI_CONV_PRECISION_FP32;  // pcmi_net_set_conv_precision: the mode of this net's passes
   int64_t param_extent = 0;  // floats covered by the ops' parameters (rounded up to 4)
   // pcmi_net_time_ops: timing events around the convolution launches of selected ops INSIDE the passes (bench.py:
   // roofline.in_step_ms -- what the dominant kernel costs where it runs, next to the other streams, not stand-alone)
@@ -308,7 +310,8 @@ static size_t op_workspace(const pcmi_net_op_t& op, int64_t n_in, int64_t n_out,
 // Packs the weights of every layer the split-precision kernel can take (3^3 / 2^3 convolutions with >= 64 channels on
 // both sides), forward and backward-data orientation, in one launch on `st`, and makes the table current for this
 // thread's convolution calls.  The job table is rebuilt when the parameter buffer changes or a level crosses a size
-// class (its slice width changes).  PCMI_X3_PREPACK=0: every convolution packs its own weights in front of its launch
+// class (its slice width changes) or the conv precision mode changes (the packs of the other term count would be read
+// otherwise: x3_find_prepacked keys on it as well).  PCMI_X3_PREPACK=0: every convolution packs its own weights in front of its launch
 // (as the C-ABI entry points do).
 static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream_t st, bool split_bwd) {
   const char* pe = getenv("PCMI_X3_PREPACK");  // read per pass: the parity test runs both forms in one process
@@ -333,7 +336,8 @@ static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream
       if (tr == 0 && nts.back() >= 2 && ps.x3_first_op < 0) ps.x3_first_op = (int)oi;
     }
   }
-  if (ps.x3_params != params || nts != ps.x3_nts) {
+  const int terms = conv_terms();
+  if (ps.x3_params != params || nts != ps.x3_nts || ps.x3_terms != terms) {
     size_t slot = 0;
     std::vector<X3PackJob> jobs;
     std::vector<X3Prepacked> table;
@@ -359,11 +363,12 @@ static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream
         j.C = C;
         j.N = N;
         j.NS = 32 * NT;
+        j.terms = terms;
         j.out = (void*)bytes;  // offset for now
         j.first_item = items;
         jobs.push_back(j);
-        table.push_back({j.w, tr, NT, (const void*)bytes});
-        bytes += x3_pack_bytes(K, C, N);
+        table.push_back({j.w, tr, NT, terms, (const void*)bytes});
+        bytes += x3_pack_bytes(K, C, N);  // (the three-term size in both modes)
         items += (int64_t)K * (C / 32) * N * 4;
       }
     }
@@ -400,6 +405,7 @@ static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream
     ps.x3_n_jobs = (int)jobs.size();
     ps.x3_items = items;
     ps.x3_params = params;
+    ps.x3_terms = terms;
   }
   if (ps.x3_n_jobs == 0) {
     x3_set_prepacked(nullptr, 0);
@@ -896,6 +902,7 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
                      pcmi_stream_t stream) {
   PCMI_REQUIRE(net && coords && in_feats && params && out_feats, PCMI_ERR_INVALID, "net_forward: null argument");
   PCMI_REQUIRE(pass >= 0 && pass < (int)net->passes.size(), PCMI_ERR_INVALID, "net_forward: bad pass %d", pass);
+  const ConvPrecisionScope precision(net->conv_precision);  // the net's mode for this pass, the thread's afterwards
   hipStream_t st = as_stream(stream);
   pcmi_net& n = *net;
   PassState& ps = n.passes[pass];
@@ -1373,7 +1380,17 @@ int pcmi_net_backward(pcmi_net_t* net, int pass, const float* d_out, int64_t d_l
   job.d_out = d_out;
   job.d_ld = d_ld;
   job.st = as_stream(stream);
+  // (the weight gradients enqueued on the side stream are launched from this call too: same mode)
+  const ConvPrecisionScope precision(net->conv_precision);
   return run_backward(*net, job, params, grads, bucket_lo_host, n_buckets, ready, ready_ctx);
+}
+
+int pcmi_net_set_conv_precision(pcmi_net_t* net, int precision) {
+  PCMI_REQUIRE(net, PCMI_ERR_INVALID, "net_set_conv_precision: null net");
+  PCMI_REQUIRE(precision == PCMI_CONV_PRECISION_FP32 || precision == PCMI_CONV_PRECISION_BF16, PCMI_ERR_INVALID,
+               "net_set_conv_precision: unknown mode %d", precision);
+  net->conv_precision = precision;
+  return PCMI_OK;
 }
 
 }  // extern "C"

@@ -88,6 +88,21 @@ static inline int64_t kmap_pairs_bound(const pcmi_kmap_t& m) {
   return m.M >= 0 ? m.M : (m.stride == 1 ? (int64_t)m.K * m.n_out : m.n_in);
 }
 
+// The calling thread's convolution arithmetic (spconv.hip; pcmi_set_conv_precision, and the executor for the duration of
+// a pass): PCMI_CONV_PRECISION_FP32 or _BF16.  conv_terms(): the bf16 terms per operand element the split-precision
+// kernels (spconv16x_kernel, wgrad_x3t / x3p_kernel) use in that mode.  Every other kernel ignores it.
+int conv_precision();
+void conv_precision_set(int precision);  // precision already validated
+static inline int conv_terms() { return conv_precision() == PCMI_CONV_PRECISION_BF16 ? 1 : 3; }
+// Sets the calling thread's mode for a scope and restores the previous one.
+struct ConvPrecisionScope {
+  explicit ConvPrecisionScope(int precision) : saved(conv_precision()) { conv_precision_set(precision); }
+  ~ConvPrecisionScope() { conv_precision_set(saved); }
+  ConvPrecisionScope(const ConvPrecisionScope&) = delete;
+  ConvPrecisionScope& operator=(const ConvPrecisionScope&) = delete;
+  int saved;
+};
+
 // spconv_wgrad_x3.hip: weight gradients of the 3^3 / stride-1 convolutions, output-tile stationary on the bf16 matrix cores
 bool wgrad_x3t_eligible(const pcmi_kmap_t* map, int64_t n_in, int64_t n_out, int cin, int cout, int64_t in_ld, int64_t gout_ld);
 size_t wgrad_x3t_workspace(int64_t n_rows, int cin, int cout);

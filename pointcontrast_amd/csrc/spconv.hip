@@ -872,8 +872,13 @@ static bool conv16_x3_on() {
   return !e || atoi(e) != 0;
 }
 static bool conv16_x3(int NT, int C, int N) { return conv16_x3_on() && NT >= 2 && NT <= 4 && C >= 64 && N >= 64; }
-// resident workgroups per CU of spconv16x_kernel (LDS: 2 weight blocks of 6 KiB x NT + the 13.5 KiB offset table)
-static int x3_workgroups(int NT) { return (NT <= 3 ? 3 : 2) * num_cu() / 8 * 8; }
+
+// The calling thread's conv precision mode (include/pcmi.h: pcmi_set_conv_precision).  It decides only the term count of
+// the split-precision launches below (x3_launch) and in spconv_wgrad_x3.hip; every plan -- which kernel, slice width,
+// offset split, row blocks -- is the same in both modes.
+static thread_local int t_conv_precision = PCMI_CONV_PRECISION_FP32;
+int conv_precision() { return t_conv_precision; }
+void conv_precision_set(int precision) { t_conv_precision = precision; }
 
 template <bool WT, bool SK>
 static int launch16(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
@@ -975,7 +980,7 @@ static Plan make_plan(int64_t rows, int N, int K, bool pair, bool wide = false, 
     const char* re = getenv("PCMI_KSPLIT_RULE");
     if (C >= 64 && wide && p.RW == 4 && wgs < target && rows < 16384 && !(re && re[0] == '0') && conv16_x3(p.NT, C, N) && min16 > 0 &&
         rows >= min16) {
-      const double slots = (double)x3_workgroups(p.NT), nch = (double)(C / kKC);
+      const double slots = (double)x3_workgroups(p.NT, 3), nch = (double)(C / kKC);  // (the fp32 mode's plan in both modes)
       const double traffic = (double)rows * N * 8.0 / 3.0e6 / 2.0;  // chunk steps per partial tensor
       auto cost = [&](int ks) {
         const double w = (double)wgs * ks;
@@ -1089,7 +1094,8 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
   if (map && map->tile_pref && map->perm && p.RW == 4 && p.ksplit == 1 && sk_rows_eligible(n_rows, a.K) &&
       map->n_tiles == ceil_div(n_rows, 128) && C >= 64 && N >= 64 && conv16_enabled(n_rows, x_rows * x_ld * 4)) {
     const bool x3 = conv16_x3(p.NT, C, N);
-    const int G = x3 ? x3_workgroups(p.NT) : sk_workgroups(p.NT);
+    const int terms = conv_terms();
+    const int G = x3 ? x3_workgroups(p.NT, terms) : sk_workgroups(p.NT);  // (<= sk_workgroups_max: the partial tiles fit)
     const size_t part = sk_partial_bytes(n_rows, N, a.K);
     const size_t need = part + (x3 ? x3_pack_bytes(a.K, C, N) : 0);
     PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "spconv: workspace %zu < %zu bytes", ws_bytes, need);
@@ -1100,13 +1106,13 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
     dim3 grid((unsigned)G, (unsigned)(N / (32 * p.NT)), 1);
     int rc;
     if (x3) {
-      a.wpack = x3_find_prepacked(w, w_transposed, p.NT);  // the executor's once-per-pass pack, if there is one
+      a.wpack = x3_find_prepacked(w, w_transposed, p.NT, terms);  // the executor's once-per-pass pack, if there is one
       rc = PCMI_OK;
       if (!a.wpack) {
         a.wpack = (char*)ws + part;
-        rc = x3_pack_weights(a, p.NT, const_cast<void*>(a.wpack), st);
+        rc = x3_pack_weights(a, p.NT, const_cast<void*>(a.wpack), st, terms);
       }
-      if (rc == PCMI_OK) rc = x3_launch(p.NT, true, a, grid, st);
+      if (rc == PCMI_OK) rc = x3_launch(p.NT, true, a, grid, st, terms);
     } else
       rc = w_transposed ? launch16<true, true>(p.NT, a, grid, st) : launch16<false, true>(p.NT, a, grid, st);
     if (rc) return rc;
@@ -1117,14 +1123,15 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
     return PCMI_OK;
   }
   const bool x3 = p.RW == 4 && map && conv16_enabled(n_rows, x_rows * x_ld * 4) && conv16_x3(p.NT, C, N);
+  const int terms = conv_terms();
   const size_t split_bytes = p.ksplit > 1 ? align_up((size_t)p.ksplit * n_rows * N * sizeof(float), 256) : 0;
   if (x3) {
     PCMI_REQUIRE(ws && ws_bytes >= split_bytes + x3_pack_bytes(a.K, C, N), PCMI_ERR_WORKSPACE,
                  "spconv: workspace %zu < %zu bytes", ws_bytes, split_bytes + x3_pack_bytes(a.K, C, N));
-    a.wpack = x3_find_prepacked(w, w_transposed, p.NT);
+    a.wpack = x3_find_prepacked(w, w_transposed, p.NT, terms);
     if (!a.wpack) {
       a.wpack = (char*)ws + split_bytes;
-      const int rc_pack = x3_pack_weights(a, p.NT, const_cast<void*>(a.wpack), st);
+      const int rc_pack = x3_pack_weights(a, p.NT, const_cast<void*>(a.wpack), st, terms);
       if (rc_pack) return rc_pack;
     }
   }
@@ -1146,7 +1153,7 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
   dim3 grid((unsigned)tiles, (unsigned)(N / (32 * p.NT)), (unsigned)p.ksplit);
   int rc;
   if (x3) {
-    rc = x3_launch(p.NT, false, a, grid, st);
+    rc = x3_launch(p.NT, false, a, grid, st, terms);
   } else if (p.RW == 4 && conv16_enabled(n_rows, x_rows * x_ld * 4)) {
     rc = w_transposed ? launch16<true, false>(p.NT, a, grid, st) : launch16<false, false>(p.NT, a, grid, st);
   } else if (p.RW == 4 && (w_transposed ? launch_deep<true>(p.NT, a, grid, st) : launch_deep<false>(p.NT, a, grid, st))) {
@@ -1260,6 +1267,15 @@ int pcmi_spconv_bwd_data(const float* gout, int64_t gout_ld, int64_t n_out, int 
 }
 
 int pcmi_spconv_split_precision(void) { return conv16_x3_on() ? 1 : 0; }
+
+int pcmi_set_conv_precision(int precision) {
+  PCMI_REQUIRE(precision == PCMI_CONV_PRECISION_FP32 || precision == PCMI_CONV_PRECISION_BF16, PCMI_ERR_INVALID,
+               "set_conv_precision: unknown mode %d", precision);
+  conv_precision_set(precision);
+  return PCMI_OK;
+}
+
+int pcmi_get_conv_precision(void) { return conv_precision(); }
 
 
 }  // extern "C"

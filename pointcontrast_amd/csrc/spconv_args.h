@@ -32,17 +32,23 @@ struct ConvArgs {
   const int32_t* sk_pref;   // [n_tiles + 1] units before a tile
   int sk_tiles;
   float* sk_part;           // [gridDim.x][2][128][N] partial tiles
-  // split-precision form (spconv_x3.hip): the weights as three bf16 terms in the kernel's LDS image order
+  // split-precision form (spconv_x3.hip): the weights as three bf16 terms (one in the bf16 conv precision mode) in the
+  // kernel's LDS image order
   const void* wpack;
 };
 
 // ---- spconv_x3.hip: fp32 convolution on the bf16 matrix cores (three-term operand split) ---------------------------
-// bytes of the packed weights of one launch (all K slices, every chunk / output slice), 256-byte aligned
+// `terms`: bf16 terms per operand element -- 3 (fp32 accuracy, the default) or 1 (the bf16 conv precision mode: both
+// operands rounded to bf16, one MFMA per tile); the calling thread's mode is conv_terms() (internal.h)
+// bytes of the packed weights of one launch (all K slices, every chunk / output slice), 256-byte aligned: the three-term
+// size, an upper bound for the one-term image
 size_t x3_pack_bytes(int K, int C, int N);
 // packs B_k[c][n] = w[k * w_kstride + c * w_sc + n * w_sn] for k < K into `out` (x3_pack_bytes) for NT-wide slices
-int x3_pack_weights(const ConvArgs& a, int NT, void* out, hipStream_t st);
-// the 128-row-tile kernel itself (a.wpack set; grid as for spconv16p_kernel); NT in {2, 3, 4}
-int x3_launch(int NT, bool sk, const ConvArgs& a, dim3 grid, hipStream_t st);
+int x3_pack_weights(const ConvArgs& a, int NT, void* out, hipStream_t st, int terms);
+// the 128-row-tile kernel itself (a.wpack set, packed with the same `terms`; grid as for spconv16p_kernel); NT in {2, 3, 4}
+int x3_launch(int NT, bool sk, const ConvArgs& a, dim3 grid, hipStream_t st, int terms);
+// resident workgroups of spconv16x_kernel on the whole chip (a multiple of 8)
+int x3_workgroups(int NT, int terms);
 // output slice width (in units of 32 channels) of a table launch over `rows` output rows contracting C channels
 // (0: that launch does not take the split kernel)
 int x3_plan_nt(int64_t rows, int C, int N, int K);
@@ -57,6 +63,7 @@ struct X3PackJob {   // one (layer, orientation): B_k[c][n] = w[k * w_kstride + 
   const float* w;
   int64_t w_kstride, w_sc, w_sn;
   int K, C, N, NS;
+  int terms;           // 3 or 1 (the bf16 conv precision mode)
   void* out;           // x3_pack_bytes(K, C, N)
   int64_t first_item;  // exclusive prefix of K * (C / 32) * N * 4 over the jobs
 };
@@ -66,12 +73,13 @@ struct X3Prepacked {
   const float* w;
   int transposed;  // 0: B = W[k] (forward), 1: B = W[k]^T (backward-data)
   int NT;
+  int terms;       // 3 or 1: a pass in one conv precision mode never reads the other mode's pack
   const void* pack;
 };
 // The calling thread's table of packed weights: run_gathered uses an entry instead of packing when (weights pointer,
-// orientation, slice width) match.  Set only while the owner guarantees the packs are current (the executor: from the
+// orientation, slice width, terms) match.  Set only while the owner guarantees the packs are current (the executor: from the
 // pack launch at the top of a forward pass to the end of the matching backward); nullptr / 0 clears.
 void x3_set_prepacked(const X3Prepacked* table, int n);
-const void* x3_find_prepacked(const float* w, bool transposed, int NT);
+const void* x3_find_prepacked(const float* w, bool transposed, int NT, int terms);
 
 }  // namespace pcmi

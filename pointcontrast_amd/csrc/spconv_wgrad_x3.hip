@@ -20,6 +20,9 @@
 // The row-block partial sums leave as slabs [k][row block][cin][cout] and are added in row-block order by
 // wgrad_slab_sum_kernel (deterministic, no float atomics).  Two workgroups per CU (<= 80 KB of LDS, <= 256 registers):
 // one stages while the other multiplies.
+// wgrad_x3t_kernel takes the term count as a template argument: TERMS = 3 is the above; TERMS = 1 (the bf16 conv
+// precision mode, pcmi_set_conv_precision) stages h alone -- a third of the LDS image and of the cell writes, no residual
+// VALU work -- and issues ONE MFMA per tile.  The one-term mode always takes that kernel (wgrad_x3t_run says why).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -45,14 +48,14 @@ struct WgradTArgs {
   float* slabs;         // [K][RB][C][N]
 };
 
-template <int MTW, int NTW, int KG>
+template <int MTW, int NTW, int KG, int TERMS>
 __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
   constexpr int TR = 64, RG = TR / 8;          // rows per tile, groups of 8 rows
   constexpr int CB = 32 * MTW, NB = 32 * NTW;  // channel block of the workgroup: 2 waves x MTW (NTW) tiles of 16
   constexpr uint32_t kAbsent = 0x80000000u;
   constexpr int kRsrcFlags = 0x00020000;       // raw buffer, 32-bit data format
-  __shared__ __attribute__((aligned(16))) u32x4 s_x[3 * RG * CB];
-  __shared__ __attribute__((aligned(16))) u32x4 s_g[3 * RG * NB];
+  __shared__ __attribute__((aligned(16))) u32x4 s_x[TERMS * RG * CB];
+  __shared__ __attribute__((aligned(16))) u32x4 s_g[TERMS * RG * NB];
   __shared__ uint32_t s_xoff[KG][TR];
   __shared__ uint32_t s_goff[TR];
   __shared__ int s_any[KG];
@@ -102,12 +105,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
 #if defined(PCMI_X3_DIAG_NO_SPLIT)  // timing diagnostic (wrong results)
         h = __builtin_bit_cast(u32x4, x0); m = __builtin_bit_cast(u32x4, x1); l = h;
 #else
-        split3(x0, x1, h, m, l);
+        split_terms<TERMS>(x0, x1, h, m, l);
 #endif
         const int cell = rg_s * width + ((4 * q_s + e4) ^ rg_s);
         dst[cell] = h;
-        dst[RG * width + cell] = m;
-        dst[2 * RG * width + cell] = l;
+        if constexpr (TERMS == 3) {
+          dst[RG * width + cell] = m;
+          dst[2 * RG * width + cell] = l;
+        }
       }
     }
   };
@@ -149,13 +154,20 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
         for (int mt = 0; mt < MTW; ++mt) {
           const int cell = rgq * CB + ((16 * (wm * MTW + mt) + i) ^ rgq);
           ah[mt] = s_x[cell];
-          am[mt] = s_x[RG * CB + cell];
-          al[mt] = s_x[2 * RG * CB + cell];
+          if constexpr (TERMS == 3) {
+            am[mt] = s_x[RG * CB + cell];
+            al[mt] = s_x[2 * RG * CB + cell];
+          }
         }
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) {
           const int cell = rgq * NB + ((16 * (wn * NTW + nt) + i) ^ rgq);
-          const u32x4 bh = s_g[cell], bm = s_g[RG * NB + cell], bl = s_g[2 * RG * NB + cell];
+          const u32x4 bh = s_g[cell];
+          u32x4 bm, bl;
+          if constexpr (TERMS == 3) {
+            bm = s_g[RG * NB + cell];
+            bl = s_g[2 * RG * NB + cell];
+          }
 #if defined(PCMI_X3_DIAG_NO_MFMA)  // timing diagnostic (wrong results)
 #define PCMI_WX3_MFMA(AT, BT) asm volatile("" ::"v"(AT[mt]), "v"(BT))
 #else
@@ -167,11 +179,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
           // alternated the MTW tiles of a term: same sums, same order per accumulator, a little slower -- profiles/r04e_*)
 #pragma unroll
           for (int mt = 0; mt < MTW; ++mt) {
-            PCMI_WX3_MFMA(al, bh);
-            PCMI_WX3_MFMA(ah, bl);
-            PCMI_WX3_MFMA(am, bm);
-            PCMI_WX3_MFMA(am, bh);
-            PCMI_WX3_MFMA(ah, bm);
+            if constexpr (TERMS == 3) {
+              PCMI_WX3_MFMA(al, bh);
+              PCMI_WX3_MFMA(ah, bl);
+              PCMI_WX3_MFMA(am, bm);
+              PCMI_WX3_MFMA(am, bh);
+              PCMI_WX3_MFMA(ah, bm);
+            }
             PCMI_WX3_MFMA(ah, bh);
           }
 #undef PCMI_WX3_MFMA
@@ -647,9 +661,10 @@ size_t wgrad_x3t_workspace(int64_t n_rows, int cin, int cout) {
 }
 
 template <int MTW, int NTW>
-static void launch_x3t(const WgradTArgs& a, dim3 grid, int mode, hipStream_t st) {
-  if (mode == 1) wgrad_x3p_kernel<MTW, NTW, kWgradTKG><<<grid, 512, 0, st>>>(a);
-  else wgrad_x3t_kernel<MTW, NTW, kWgradTKG><<<grid, 256, 0, st>>>(a);
+static void launch_x3t(const WgradTArgs& a, dim3 grid, int mode, int terms, hipStream_t st) {
+  if (terms == 1) wgrad_x3t_kernel<MTW, NTW, kWgradTKG, 1><<<grid, 256, 0, st>>>(a);  // (one role: see wgrad_x3t_run)
+  else if (mode == 1) wgrad_x3p_kernel<MTW, NTW, kWgradTKG><<<grid, 512, 0, st>>>(a);
+  else wgrad_x3t_kernel<MTW, NTW, kWgradTKG, 3><<<grid, 256, 0, st>>>(a);
 }
 
 int wgrad_x3t_run(const float* in, int64_t in_ld, const float* gout, int64_t gout_ld, int64_t n_rows, int cin, int cout,
@@ -669,7 +684,11 @@ int wgrad_x3t_run(const float* in, int64_t in_ld, const float* gout, int64_t gou
   a.C = cin;
   a.N = cout;
   const int gy = cin / (32 * MTW), gz = cout / (32 * NTW);
-  const int mode = wgrad_x3p_mode();
+  const int terms = conv_terms();  // the calling thread's conv precision mode
+  // The one-term mode takes the one-role kernel: wgrad_x3p_kernel<..., 1> compiles with its producers' register sets on
+  // the stack (.private_segment_fixed_size 480 B, scratch loads and stores; the three-term form has none) and measured
+  // 1.03 against 0.44 ms for the three-term kernel on the level-1 96 -> 96 launch.
+  const int mode = terms == 1 ? 0 : wgrad_x3p_mode();
   [[maybe_unused]] const bool pc = mode == 1;
   const int kg = kWgradTKG;
   a.NG = (K + kg - 1) / kg;
@@ -684,10 +703,10 @@ int wgrad_x3t_run(const float* in, int64_t in_ld, const float* gout, int64_t gou
   a.slabs = (float*)ws;
   const dim3 grid((unsigned)(a.RB * a.NG), (unsigned)gy, (unsigned)gz);
   switch (MTW * 4 + NTW) {
-    case 3 * 4 + 3: launch_x3t<3, 3>(a, grid, mode, st); break;
-    case 3 * 4 + 2: launch_x3t<3, 2>(a, grid, mode, st); break;
-    case 2 * 4 + 3: launch_x3t<2, 3>(a, grid, mode, st); break;
-    default: launch_x3t<2, 2>(a, grid, mode, st); break;
+    case 3 * 4 + 3: launch_x3t<3, 3>(a, grid, mode, terms, st); break;
+    case 3 * 4 + 2: launch_x3t<3, 2>(a, grid, mode, terms, st); break;
+    case 2 * 4 + 3: launch_x3t<2, 3>(a, grid, mode, terms, st); break;
+    default: launch_x3t<2, 2>(a, grid, mode, terms, st); break;
   }
   PCMI_LAUNCH_CHECK();
 #if defined(PCMI_X3_DIAG_STAMP)

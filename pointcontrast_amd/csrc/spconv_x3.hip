@@ -48,7 +48,9 @@ __host__ __device__ constexpr int x3_piece(int n, int kk) { return (n >> 4) * 64
 // channel of chunk-local element e of lane quad kk (see the header)
 __host__ __device__ constexpr int x3_channel(int kk, int e) { return 4 * kk + (e & 3) + 16 * (e >> 2); }
 
-// One thread per (slice, chunk, output slice, column, lane quad): the three 16-byte pieces of that lane's B fragment.
+// One thread per (slice, chunk, output slice, column, lane quad): the TERMS 16-byte pieces of that lane's B fragment
+// (TERMS = 3: h, m, l; TERMS = 1, the bf16 conv precision mode: h alone, a block of a third of the size).
+template <int TERMS>
 __global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ w, int64_t w_kstride, int64_t w_sc, int64_t w_sn,
                                                       int K, int C, int N, int NS, u32x4* __restrict__ out) {
   const int nch = C / kKC, nns = N / NS;
@@ -71,12 +73,14 @@ __global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ 
     x1[e] = wb[(int64_t)(cc * kKC + x3_channel(kk, e + 4)) * w_sc];
   }
   u32x4 h, m, l;
-  split3(x0, x1, h, m, l);
-  u32x4* blk = out + (((int64_t)wk * nch + cc) * nns + ns) * (3 * NS * 4);
+  split_terms<TERMS>(x0, x1, h, m, l);
+  u32x4* blk = out + (((int64_t)wk * nch + cc) * nns + ns) * (TERMS * NS * 4);
   const int piece = x3_piece(nl, kk);
   blk[0 * NS * 4 + piece] = h;
-  blk[1 * NS * 4 + piece] = m;
-  blk[2 * NS * 4 + piece] = l;
+  if constexpr (TERMS == 3) {
+    blk[1 * NS * 4 + piece] = m;
+    blk[2 * NS * 4 + piece] = l;
+  }
 }
 
 // DMA: the weight block of the next step goes global -> LDS directly (buffer_load_dwordx4 ... lds: the block is a
@@ -110,10 +114,16 @@ __global__ __launch_bounds__(256) void x3_pack_many_kernel(const X3PackJob* __re
     x0[e] = wb[(int64_t)(cc * kKC + x3_channel(kk, e)) * jb.w_sc];
     x1[e] = wb[(int64_t)(cc * kKC + x3_channel(kk, e + 4)) * jb.w_sc];
   }
+  const int piece = x3_piece(nl, kk);
+  if (jb.terms == 1) {  // (uniform per job) the one-term image of the bf16 conv precision mode
+    u32x4 h;
+    split1(x0, x1, h);
+    reinterpret_cast<u32x4*>(jb.out)[(((int64_t)wk * nch + cc) * nns + ns) * (jb.NS * 4) + piece] = h;
+    return;
+  }
   u32x4 h, m, l;
   split3(x0, x1, h, m, l);
   u32x4* blk = reinterpret_cast<u32x4*>(jb.out) + (((int64_t)wk * nch + cc) * nns + ns) * (3 * jb.NS * 4);
-  const int piece = x3_piece(nl, kk);
   blk[0 * jb.NS * 4 + piece] = h;
   blk[1 * jb.NS * 4 + piece] = m;
   blk[2 * jb.NS * 4 + piece] = l;
@@ -136,13 +146,18 @@ __device__ unsigned long long g_x3c_phase[8];
 #else
 #define PCMI_X3C_PHASE(P) do {} while (0)
 #endif
-template <int NT, bool SK, bool DMA>
-__global__ __launch_bounds__(256, NT == 4 ? 2 : 3) void spconv16x_kernel(ConvArgs a) {
+// TERMS = 3: the split-precision kernel described above.  TERMS = 1 (the bf16 conv precision mode, pcmi_set_conv_precision):
+// the gathered rows and the weights rounded to bf16 (h alone), ONE MFMA per tile and row group, a weight block of a third
+// of the size; the rest of the kernel is the same code.
+template <int TERMS>
+constexpr int x3_min_waves(int NT) { return TERMS == 3 ? (NT == 4 ? 2 : 3) : (NT == 2 ? 4 : 3); }
+template <int NT, bool SK, bool DMA, int TERMS>
+__global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel(ConvArgs a) {
   constexpr int TM = 128, NS = 32 * NT, CTN = 2 * NT;  // rows per tile, output slice, 16-wide column tiles
   constexpr int KSLOTS = PCMI_MAX_KERNEL_VOLUME;
   constexpr uint32_t kAbsent = 0x80000000u;
   constexpr int kRsrcFlags = 0x00020000;  // raw buffer, 32-bit data format
-  constexpr int PIECES = 3 * NS * 4;      // 16-byte pieces of one weight block
+  constexpr int PIECES = TERMS * NS * 4;  // 16-byte pieces of one weight block
   constexpr int BLOCK_BYTES = PIECES * 16;
   constexpr int BR = (PIECES + 255) / 256;  // staging rounds of a thread
   static_assert(CTN >= 3, "the three load stages sit behind the MFMAs of column tiles 0, 1, 2");
@@ -383,8 +398,8 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 3) void spconv16x_kernel(ConvArg
       ah[0] = __builtin_bit_cast(u32x4, cur[0][0]); am[0] = __builtin_bit_cast(u32x4, cur[0][1]); al[0] = ah[0];
       ah[1] = __builtin_bit_cast(u32x4, cur[1][0]); am[1] = __builtin_bit_cast(u32x4, cur[1][1]); al[1] = ah[1];
 #else
-      if (g0) split3(cur[0][0], cur[0][1], ah[0], am[0], al[0]);
-      if (g1) split3(cur[1][0], cur[1][1], ah[1], am[1], al[1]);
+      if (g0) split_terms<TERMS>(cur[0][0], cur[0][1], ah[0], am[0], al[0]);
+      if (g1) split_terms<TERMS>(cur[1][0], cur[1][1], ah[1], am[1], al[1]);
 #endif
       PCMI_X3C_PHASE(1);  // priority + operand split
       // B fragments of column tile ct: piece (term, n = 16 ct + i, kk); a two-tile register ring, read one tile ahead
@@ -396,8 +411,10 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 3) void spconv16x_kernel(ConvArg
 #else
       if (va_cur) {
         bh[0] = sb[0 * NS * 4];
-        bm[0] = sb[1 * NS * 4];
-        bl[0] = sb[2 * NS * 4];
+        if constexpr (TERMS == 3) {
+          bm[0] = sb[1 * NS * 4];
+          bl[0] = sb[2 * NS * 4];
+        }
       }
 #endif
       __builtin_amdgcn_sched_barrier(0);
@@ -407,8 +424,10 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 3) void spconv16x_kernel(ConvArg
 #if !defined(PCMI_X3_DIAG_NO_BFRAG)
         if (va_cur && ct + 1 < CTN) {
           bh[rb ^ 1] = sb[(0 * NS + 16 * (ct + 1)) * 4];
-          bm[rb ^ 1] = sb[(1 * NS + 16 * (ct + 1)) * 4];
-          bl[rb ^ 1] = sb[(2 * NS + 16 * (ct + 1)) * 4];
+          if constexpr (TERMS == 3) {
+            bm[rb ^ 1] = sb[(1 * NS + 16 * (ct + 1)) * 4];
+            bl[rb ^ 1] = sb[(2 * NS + 16 * (ct + 1)) * 4];
+          }
         }
 #endif
         // six products per row group, the small ones first, BACK TO BACK on the group's accumulator, one group after the other
@@ -421,12 +440,14 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 3) void spconv16x_kernel(ConvArg
   acc[G][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AT[G]), __builtin_bit_cast(bf16x8, BT[rb]), \
                                                        acc[G][ct], 0, 0, 0)
 #endif
-#define PCMI_X3_SIX(G)      \
-  PCMI_X3_MFMA(G, al, bh);  \
-  PCMI_X3_MFMA(G, ah, bl);  \
-  PCMI_X3_MFMA(G, am, bm);  \
-  PCMI_X3_MFMA(G, am, bh);  \
-  PCMI_X3_MFMA(G, ah, bm);  \
+#define PCMI_X3_SIX(G)        \
+  if constexpr (TERMS == 3) { \
+    PCMI_X3_MFMA(G, al, bh);  \
+    PCMI_X3_MFMA(G, ah, bl);  \
+    PCMI_X3_MFMA(G, am, bm);  \
+    PCMI_X3_MFMA(G, am, bh);  \
+    PCMI_X3_MFMA(G, ah, bm);  \
+  }                           \
   PCMI_X3_MFMA(G, ah, bh)
         if (g0 && g1) {
           PCMI_X3_SIX(0);
@@ -512,12 +533,12 @@ __global__ __launch_bounds__(256, NT == 4 ? 2 : 3) void spconv16x_kernel(ConvArg
 #endif
 }
 
-template <bool SK, bool DMA>
+template <bool SK, bool DMA, int TERMS>
 static int launch_x3(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
   switch (NT) {
-    case 2: spconv16x_kernel<2, SK, DMA><<<grid, 256, 0, st>>>(a); break;
-    case 3: spconv16x_kernel<3, SK, DMA><<<grid, 256, 0, st>>>(a); break;
-    case 4: spconv16x_kernel<4, SK, DMA><<<grid, 256, 0, st>>>(a); break;
+    case 2: spconv16x_kernel<2, SK, DMA, TERMS><<<grid, 256, 0, st>>>(a); break;
+    case 3: spconv16x_kernel<3, SK, DMA, TERMS><<<grid, 256, 0, st>>>(a); break;
+    case 4: spconv16x_kernel<4, SK, DMA, TERMS><<<grid, 256, 0, st>>>(a); break;
     default: set_error("spconv x3: bad NT %d", NT); return PCMI_ERR_INVALID;
   }
   PCMI_LAUNCH_CHECK();
@@ -537,13 +558,20 @@ static int launch_x3(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
 
 size_t x3_pack_bytes(int K, int C, int N) { return align_up((size_t)std::max(K, 1) * C * N * 6, 256); }
 
-int x3_pack_weights(const ConvArgs& a, int NT, void* out, hipStream_t st) {
-  PCMI_REQUIRE(out && ((uintptr_t)out % 16 == 0) && a.C % kKC == 0 && a.N % (32 * NT) == 0, PCMI_ERR_INVALID,
-               "spconv x3: bad pack arguments (%d -> %d, NT %d)", a.C, a.N, NT);
+int x3_workgroups(int NT, int terms) {
+  return (terms == 1 ? x3_min_waves<1>(NT) : x3_min_waves<3>(NT)) * num_cu() / 8 * 8;
+}
+
+int x3_pack_weights(const ConvArgs& a, int NT, void* out, hipStream_t st, int terms) {
+  PCMI_REQUIRE(out && ((uintptr_t)out % 16 == 0) && a.C % kKC == 0 && a.N % (32 * NT) == 0 && (terms == 1 || terms == 3),
+               PCMI_ERR_INVALID, "spconv x3: bad pack arguments (%d -> %d, NT %d, %d terms)", a.C, a.N, NT, terms);
   // every weight slice a launch can select: wsel maps offsets to slices 0 .. K-1
   const int64_t total = (int64_t)a.K * (a.C / kKC) * a.N * 4;
-  x3_pack_kernel<<<dim3((unsigned)ceil_div(total, 256)), 256, 0, st>>>(a.w, a.w_kstride, a.w_sc, a.w_sn, a.K, a.C, a.N, 32 * NT,
-                                                                      reinterpret_cast<u32x4*>(out));
+  const dim3 grid((unsigned)ceil_div(total, 256));
+  if (terms == 1)
+    x3_pack_kernel<1><<<grid, 256, 0, st>>>(a.w, a.w_kstride, a.w_sc, a.w_sn, a.K, a.C, a.N, 32 * NT, reinterpret_cast<u32x4*>(out));
+  else
+    x3_pack_kernel<3><<<grid, 256, 0, st>>>(a.w, a.w_kstride, a.w_sc, a.w_sn, a.K, a.C, a.N, 32 * NT, reinterpret_cast<u32x4*>(out));
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
@@ -561,17 +589,21 @@ void x3_set_prepacked(const X3Prepacked* table, int n) {
   t_prepacked = table;
   t_n_prepacked = table ? n : 0;
 }
-const void* x3_find_prepacked(const float* w, bool transposed, int NT) {
+const void* x3_find_prepacked(const float* w, bool transposed, int NT, int terms) {
   for (int i = 0; i < t_n_prepacked; ++i)
-    if (t_prepacked[i].w == w && (t_prepacked[i].transposed != 0) == transposed && t_prepacked[i].NT == NT) return t_prepacked[i].pack;
+    if (t_prepacked[i].w == w && (t_prepacked[i].transposed != 0) == transposed && t_prepacked[i].NT == NT &&
+        t_prepacked[i].terms == terms)
+      return t_prepacked[i].pack;
   return nullptr;
 }
 
-int x3_launch(int NT, bool sk, const ConvArgs& a, dim3 grid, hipStream_t st) {
-  PCMI_REQUIRE(a.wpack && NT >= 2 && NT <= 4, PCMI_ERR_INVALID, "spconv x3: needs packed weights and NT in 2..4 (NT %d)", NT);
+int x3_launch(int NT, bool sk, const ConvArgs& a, dim3 grid, hipStream_t st, int terms) {
+  PCMI_REQUIRE(a.wpack && NT >= 2 && NT <= 4 && (terms == 1 || terms == 3), PCMI_ERR_INVALID,
+               "spconv x3: needs packed weights, NT in 2..4 and 1 or 3 terms (NT %d, %d terms)", NT, terms);
   // (weight blocks go global -> LDS directly; the form through staging registers -- DMA = false, 185 instead of 166
   //  VGPRs at NT = 3, 0.404 against 0.343 ms on the level-1 launch -- is kept as a template flag only)
-  return sk ? launch_x3<true, true>(NT, a, grid, st) : launch_x3<false, true>(NT, a, grid, st);
+  if (terms == 1) return sk ? launch_x3<true, true, 1>(NT, a, grid, st) : launch_x3<false, true, 1>(NT, a, grid, st);
+  return sk ? launch_x3<true, true, 3>(NT, a, grid, st) : launch_x3<false, true, 3>(NT, a, grid, st);
 }
 
 }  // namespace pcmi

@@ -41,4 +41,21 @@ __device__ __forceinline__ void split3(const v4f& x0, const v4f& x1, u32x4& h, u
   }
 }
 
+// The one-term form of the bf16 conv precision mode (pcmi_set_conv_precision): h alone, the same rounding as split3's h.
+// An element that rounds to +-inf gives +-inf products here (no residual, so no inf - inf).
+__device__ __forceinline__ void split1(const v4f& x0, const v4f& x1, u32x4& h) {
+  h[0] = cvt_pk_bf16(x0[0], x0[1]);
+  h[1] = cvt_pk_bf16(x0[2], x0[3]);
+  h[2] = cvt_pk_bf16(x1[0], x1[1]);
+  h[3] = cvt_pk_bf16(x1[2], x1[3]);
+}
+
+// TERMS = 3: split3; TERMS = 1: split1 (m and l untouched)
+template <int TERMS>
+__device__ __forceinline__ void split_terms(const v4f& x0, const v4f& x1, u32x4& h, u32x4& m, u32x4& l) {
+  static_assert(TERMS == 1 || TERMS == 3, "one or three bf16 terms");
+  if constexpr (TERMS == 3) split3(x0, x1, h, m, l);
+  else split1(x0, x1, h);
+}
+
 }  // namespace pcmi

@@ -63,7 +63,7 @@ class SegmentationTrainer:
 
   def __init__(self, num_labels, in_channels=3, model="Res16UNet34C", lr=0.1, momentum=0.9, dampening=0.1,
                weight_decay=1e-4, max_iter=60000, poly_power=0.9, ignore_label=255, bn_momentum=0.02, pretrained=None,
-               kernel_order="hybrid", device=None):
+               kernel_order="hybrid", device=None, conv_precision="fp32"):
     assert torch.cuda.is_available(), "the fine-tuning step runs on a gfx950 GPU (no CPU path)"
     self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = get_config(["net.normalize_feature=False", "opt.bn_momentum=%g" % bn_momentum])
@@ -75,7 +75,8 @@ class SegmentationTrainer:
       own.update(ck.load_state_with_same_shape(self.model, weights))
       self.model.load_state_dict(own)
     self.flat = FlatParameters(self.model.parameters())
-    self.engine = NativeEngine(self.model, self.flat, in_channels=in_channels, n_passes=1)
+    # conv_precision "bf16": the opt-in bf16 matrix-core mode of the convolutions
+    self.engine = NativeEngine(self.model, self.flat, in_channels=in_channels, n_passes=1, conv_precision=conv_precision)
     # downstream/semseg/lib/solvers.py:52-60: SGD(lr, momentum=sgd_momentum 0.9, dampening=sgd_dampening 0.1, weight_decay)
     self.optimizer = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=dampening)
     self.scheduler = PolyLR(self.optimizer, max_iter=max_iter, power=poly_power)

@@ -14,6 +14,7 @@ import torch
 from . import minkowski as ME
 from ._lib import lib, check, NetOp, NetTensor, READY_FN
 from .runtime import ptr, cur_stream, require_cuda
+from .functional import conv_precision_code
 
 OP_CONV, OP_BN, OP_L2NORM = 0, 1, 2
 
@@ -170,7 +171,10 @@ class NativeEngine:
   """model: a network of ME modules whose forward maps one SparseTensor to one SparseTensor
   (Res16UNet family).  flat: lib.distributed.FlatParameters of the same model."""
 
-  def __init__(self, model, flat, in_channels=3, n_passes=2):
+  def __init__(self, model, flat, in_channels=3, n_passes=2, conv_precision="fp32"):
+    """conv_precision: "fp32" or "bf16", the convolution precision of every forward / backward of this engine
+    (minkowski.set_conv_precision; the calling thread's own mode does not apply to the engine)."""
+    code = conv_precision_code(conv_precision)
     require_cuda(flat.w, "NativeEngine")
     self.model, self.flat, self.n_passes = model, flat, n_passes
     prog = lower_model(model, flat, in_channels)
@@ -180,9 +184,16 @@ class NativeEngine:
     self._tensors = prog["tensors"]  # {level, channels, parent, col_off} per tensor id
     self._ops = prog["ops"]  # the lowered program (dicts): which op writes which tensor (activation / relu_masks)
     self._h = create_net(prog, n_passes)
+    self.conv_precision = conv_precision
+    check(lib.pcmi_net_set_conv_precision(self._h, code))
     self._held = [None] * n_passes
     self._pair_stream = None
     self.pair_marks = None
+
+  def set_conv_precision(self, mode):
+    """Switches the convolution precision ("fp32" | "bf16") of every later forward / backward of this engine."""
+    check(lib.pcmi_net_set_conv_precision(self._h, conv_precision_code(mode)))
+    self.conv_precision = mode
 
   def __del__(self):
     try:

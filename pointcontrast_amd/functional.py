@@ -4,6 +4,7 @@ Every forward/backward below is one or a few calls into libpcmi.so on the
 current torch stream; tensors are plain fp32 row-major [rows, channels].  There is
 no torch-op fallback: a CPU tensor raises.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -24,6 +25,32 @@ def _c(t):
   if t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 and t.stride(0) >= t.shape[1]:
     return t
   return t.contiguous()
+
+
+# Convolution precision modes (include/pcmi.h: pcmi_set_conv_precision).  "bf16": the launches of the split-precision
+# kernels round both operands to bf16 and take one bf16 product per 32-channel chunk, fp32 accumulation; every other
+# launch and op is unchanged.  The mode is the calling thread's (thread-local in libpcmi).
+CONV_PRECISIONS = {"fp32": 0, "bf16": 1}
+
+
+def conv_precision_code(name):
+  if not isinstance(name, str) or name not in CONV_PRECISIONS:
+    raise ValueError("conv precision must be one of %s, got %r" % (sorted(CONV_PRECISIONS), name))
+  return CONV_PRECISIONS[name]
+
+
+@contextlib.contextmanager
+def _conv_precision_code_as(code):
+  """The calling thread's libpcmi conv precision set to `code` for the block (restored afterwards)."""
+  prev = lib.pcmi_get_conv_precision()
+  if prev == code:
+    yield
+    return
+  check(lib.pcmi_set_conv_precision(code))
+  try:
+    yield
+  finally:
+    check(lib.pcmi_set_conv_precision(prev))
 
 
 def _kmap_ref(kmap):
@@ -49,6 +76,9 @@ class SparseConvFunction(Function):
                               ptr(bias), ptr(out), cout, n_out, ws, wsb, cur_stream(feats.device)))
     ctx.save_for_backward(feats, kernel)
     ctx.kmap, ctx.transpose, ctx.has_bias = kmap, int(transpose), bias is not None
+    # autocast's rule: backward-data and weight gradient run in the forward's precision mode, whatever the mode is when
+    # (and on whichever thread) .backward() runs
+    ctx.precision = lib.pcmi_get_conv_precision()
     ctx.owner = owner  # keeps the coordinate manager (and the arena behind kmap) alive until backward
     return out
 
@@ -66,16 +96,17 @@ class SparseConvFunction(Function):
     st = cur_stream(dev)
     ws, wsb = ws_args(lib.pcmi_spconv_workspace_bytes(n_in, n_out, cin, cout, K, M), dev)
     gin = gw = gb = None
-    if ctx.needs_input_grad[0]:
-      gin = torch.empty((n_in, cin), dtype=torch.float32, device=dev)
-      check(lib.pcmi_spconv_bwd_data(ptr(gout), g_ld, n_out, cout, ptr(kernel), cin, _kmap_ref(kmap), ctx.transpose,
-                                     ptr(gin), cin, n_in, ws, wsb, st))
-    if ctx.needs_input_grad[1]:
-      gw = torch.empty_like(kernel)
-      if ctx.has_bias and ctx.needs_input_grad[2]:
-        gb = torch.empty((1, cout), dtype=torch.float32, device=dev)
-      check(lib.pcmi_spconv_bwd_weight(ptr(feats), in_ld, n_in, cin, ptr(gout), g_ld, n_out, cout, _kmap_ref(kmap),
-                                       ctx.transpose, ptr(gw), ptr(gb), ws, wsb, st))
+    with _conv_precision_code_as(ctx.precision):
+      if ctx.needs_input_grad[0]:
+        gin = torch.empty((n_in, cin), dtype=torch.float32, device=dev)
+        check(lib.pcmi_spconv_bwd_data(ptr(gout), g_ld, n_out, cout, ptr(kernel), cin, _kmap_ref(kmap), ctx.transpose,
+                                       ptr(gin), cin, n_in, ws, wsb, st))
+      if ctx.needs_input_grad[1]:
+        gw = torch.empty_like(kernel)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+          gb = torch.empty((1, cout), dtype=torch.float32, device=dev)
+        check(lib.pcmi_spconv_bwd_weight(ptr(feats), in_ld, n_in, cin, ptr(gout), g_ld, n_out, cout, _kmap_ref(kmap),
+                                         ctx.transpose, ptr(gw), ptr(gb), ws, wsb, st))
     return gin, gw, gb, None, None, None, None
 
 

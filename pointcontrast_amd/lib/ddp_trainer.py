@@ -76,6 +76,10 @@ class ContrastiveLossTrainer:
     # misc.engine: "native" = whole forward / backward as one libpcmi call each (engine.py);
     #              "autograd" = per-layer torch.autograd.Function path (same kernels)
     self.engine = None
+    # misc.conv_precision: "fp32" (default) or "bf16" -- the native engine's mode, or the autograd path's forward passes
+    # run inside ME.conv_precision (their backward follows the forward's mode)
+    self.conv_precision = config.misc.get("conv_precision", "fp32")
+    PF.conv_precision_code(self.conv_precision)  # ValueError for an unknown mode, before anything is built
     self.host_ms, self._host_t, self._host_c = {}, 0.0, 0.0
     self._prefetch_thread, self._prefetch_err = None, None
     if config.misc.get("switch_interval", None):
@@ -86,7 +90,7 @@ class ContrastiveLossTrainer:
     self._gpu_marks = []
     if config.misc.get("engine", "native") == "native":
       from ..engine import NativeEngine
-      self.engine = NativeEngine(model, self.flat, in_channels=num_feats)
+      self.engine = NativeEngine(model, self.flat, in_channels=num_feats, conv_precision=self.conv_precision)
     self.optimizer = FlatSGD(self.flat, lr=config.opt.lr, momentum=config.opt.momentum,
                              weight_decay=config.opt.weight_decay, grad_scale=self.reducer.grad_scale)
     if self.engine is not None and config.misc.get("bucket_sgd", False):
@@ -336,7 +340,8 @@ class ContrastiveLossTrainer:
       return F[:prep["n0"]], F[prep["n0"]:]
     s0, s1 = prep["s0"], prep["s1"]
     if self.engine is None:
-      return self.model(s0).F, self.model(s1).F
+      with ME.conv_precision(self.conv_precision):
+        return self.model(s0).F, self.model(s1).F
     if self.model.training and self.config.misc.get("concurrent_forward", True):
       F0, F1 = self.engine.forward_pair(s0, s1)  # two streams, same results
       F0, F1 = F0.requires_grad_(True), F1.requires_grad_(True)

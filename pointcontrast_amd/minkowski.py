@@ -15,6 +15,9 @@ These run eagerly (HIP kernels of csrc/pool.hip); the native engine does not low
 them, and tracing a model that uses one raises NotImplementedError naming it.
 Usage mirrors the reference: ``import pointcontrast_amd.minkowski as ME``.
 Anything else ME offers (max pooling, pruning ...) raises NotImplementedError.
+Beyond ME: ``set_conv_precision("fp32" | "bf16")``, ``get_conv_precision()`` and the
+context manager ``conv_precision(mode)`` -- the opt-in bf16 matrix-core mode of the
+convolutions (INTEGRATION.md, "Convolution precision").
 """
 import contextlib
 import ctypes as C
@@ -32,6 +35,26 @@ from . import _lib
 from ._lib import lib, check, KMap, Segments
 from . import functional as PF
 from .runtime import ptr, handle_pool, require_cuda
+
+
+def set_conv_precision(mode):
+  """The calling thread's convolution precision: "fp32" (default) or "bf16" -- the matrix-bound convolution launches
+  round both operands to bf16 and take one bf16 product per 32-channel chunk (fp32 accumulation); everything else is
+  unchanged.  A convolution's backward runs in the mode of its forward.  ValueError for any other mode."""
+  check(lib.pcmi_set_conv_precision(PF.conv_precision_code(mode)))
+
+
+def get_conv_precision():
+  code = lib.pcmi_get_conv_precision()
+  return next(k for k, v in PF.CONV_PRECISIONS.items() if v == code)
+
+
+@contextlib.contextmanager
+def conv_precision(mode):
+  """``with ME.conv_precision("bf16"): y = model(x)`` -- the mode for the block, the previous one restored after."""
+  code = PF.conv_precision_code(mode)
+  with PF._conv_precision_code_as(code):
+    yield
 
 
 class RegionType(Enum):
