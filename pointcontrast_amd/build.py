@@ -51,8 +51,8 @@ def sources_digest():
 
 
 def build_variant(name, extra_flags, force=False, verbose=False):
-  """An A/B build of the SAME sources with extra compiler flags: objects in csrc/_build_<name>/, library
-  pointcontrast_amd/libpcmi_<name>.so (select it with PCMI_LIB=<path>; scripts/gpu A/B runs).  Not the product build."""
+  """An A/B build of the SAME sources with extra compiler flags (e.g. optimisation passes, -mllvm options): objects in
+  csrc/_build_<name>/, library pointcontrast_amd/libpcmi_<name>.so, selected with PCMI_LIB=<path>.  Not the product build."""
   global BUILD, LIB, FLAGS
   saved = (BUILD, LIB, FLAGS)
   try:

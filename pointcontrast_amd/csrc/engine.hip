@@ -16,7 +16,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "internal.h"
@@ -59,10 +58,7 @@ static HostProfile g_prof_fwd, g_prof_bwd;
 // the loader workers).  An event created with hipEventBlockingSync still spun on this driver (measured: same CPU time),
 // so the wait polls the event and SLEEPS in between (PCMI_THROTTLE_SLEEP_US, default 50; 0 = hipEventSynchronize):
 // the GPU is a whole backward pass behind the thread at that point, 50 us of wake-up latency cost nothing.
-static unsigned host_wait_event_flags() {
-  const char* e = getenv("PCMI_BLOCKING_EVENTS");  // 0: plain events (A/B)
-  return hipEventDisableTiming | ((e && e[0] == '0') ? 0u : (unsigned)hipEventBlockingSync);
-}
+static unsigned host_wait_event_flags() { return hipEventDisableTiming | hipEventBlockingSync; }
 static int host_wait_event(hipEvent_t ev) {
   const char* e = getenv("PCMI_THROTTLE_SLEEP_US");
   const long us = e ? atol(e) : 50;
@@ -169,7 +165,7 @@ struct PassState {
   int64_t x3_items = 0;
   // The jobs are ordered forward orientations first: [0, x3_items_fwd) is packed at the top of the forward pass, on its
   // stream; the backward-data orientations [x3_items_fwd, x3_items) -- not needed before the backward pass -- are packed
-  // on the executor's side stream while the forward pass is in its coarse levels (PCMI_X3_PACK_SPLIT=0: all at the top).
+  // on the executor's side stream while the forward pass is in its coarse levels (training passes; others pack all at the top).
   int64_t x3_items_fwd = 0;
   bool x3_bwd_owed = false;          // this pass's forward still has to enqueue the backward orientations
   bool x3_bwd_pending = false;       // ... they are enqueued on the side stream and x3_bwd_packed is recorded behind them
@@ -193,18 +189,14 @@ struct pcmi_net {
   std::vector<pcmi::PassState> passes;
   // side: the weight gradients of a backward pass (off the critical path: nothing downstream reads them) at the lowest
   // stream priority, with a workspace of their own
-  // side[1] (PCMI_WGRAD_SIDE2=1, an experiment that lost: 254.4 against 260.2 pairs/s, profiles/r05a_*): the SMALL
-  // weight-gradient launches (levels under 8192 rows, strided and 1x1 layers: ~45 latency-bound launches per step that use
-  // a few dozen compute units each) on a stream of their own, beside the large level-1 launches instead of behind them
-  static constexpr int kSides = 2;
-  hipStream_t side[kSides] = {nullptr, nullptr};
-  hipEvent_t ev_main[kSides] = {nullptr, nullptr}, ev_side[kSides] = {nullptr, nullptr};
+  hipStream_t side = nullptr;
+  hipEvent_t ev_main = nullptr, ev_side = nullptr;
   // what produced the gradient bucket the running `ready` callback is about: the chain up to the bucket's last op on
   // the backward stream, and the weight gradients enqueued so far on the side stream (pcmi_net_stream_wait_bucket)
-  hipEvent_t ev_bkt_main = nullptr, ev_bkt_side[kSides] = {nullptr, nullptr};
+  hipEvent_t ev_bkt_main = nullptr, ev_bkt_side = nullptr;
   hipEvent_t ev_fwd_fork = nullptr, ev_fwd_join = nullptr, ev_fwd_pack = nullptr;  // forward pass: a block's residual branch on the side stream
-  bool bkt_valid = false, bkt_side[kSides] = {false, false};
-  pcmi::DevBuf ws_side[kSides];
+  bool bkt_valid = false, bkt_side = false;
+  pcmi::DevBuf ws_side;
   // weight gradients of the coarse levels collected for ONE launch per run of layers (spconv_wgrad.hip: wgrad_group_*)
   pcmi::WgradGroupBuilder* wgroup = nullptr;
   int conv_precision = PCMI_CONV_PRECISION_FP32;  // pcmi_net_set_conv_precision: the mode of this net's passes
@@ -250,12 +242,10 @@ struct pcmi_net {
     (void)hipDeviceSynchronize();
     timed_clear();
     pcmi::wgrad_group_destroy(wgroup);
-    for (int i = 0; i < kSides; ++i) {
-      if (side[i]) (void)hipStreamDestroy(side[i]);
-      if (ev_main[i]) (void)hipEventDestroy(ev_main[i]);
-      if (ev_side[i]) (void)hipEventDestroy(ev_side[i]);
-      if (ev_bkt_side[i]) (void)hipEventDestroy(ev_bkt_side[i]);
-    }
+    if (side) (void)hipStreamDestroy(side);
+    if (ev_main) (void)hipEventDestroy(ev_main);
+    if (ev_side) (void)hipEventDestroy(ev_side);
+    if (ev_bkt_side) (void)hipEventDestroy(ev_bkt_side);
     if (ev_bkt_main) (void)hipEventDestroy(ev_bkt_main);
     if (ev_fwd_fork) (void)hipEventDestroy(ev_fwd_fork);
     if (ev_fwd_join) (void)hipEventDestroy(ev_fwd_join);
@@ -312,8 +302,9 @@ static size_t op_workspace(const pcmi_net_op_t& op, int64_t n_in, int64_t n_out,
 // thread's convolution calls.  The job table is rebuilt when the parameter buffer changes or a level crosses a size
 // class (its slice width changes) or the conv precision mode changes (the packs of the other term count would be read
 // otherwise: x3_find_prepacked keys on it as well).  PCMI_X3_PREPACK=0: every convolution packs its own weights in front of its launch
-// (as the C-ABI entry points do).
-static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream_t st, bool split_bwd) {
+// (as the C-ABI entry points do).  A training pass packs only the forward orientations here and owes the backward-data
+// ones (x3_bwd_owed: pcmi_net_forward packs them on the side stream); any other pass packs both.
+static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream_t st, bool training) {
   const char* pe = getenv("PCMI_X3_PREPACK");  // read per pass: the parity test runs both forms in one process
   const bool enabled = !(pe && pe[0] == '0');
   ps.x3_current = false;
@@ -411,14 +402,13 @@ static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream
     x3_set_prepacked(nullptr, 0);
     return PCMI_OK;
   }
-  // (training passes only owe the backward orientations; `split`: they follow later on the side stream, x3_pack_backward)
-  const int64_t upto = split_bwd ? ps.x3_items_fwd : ps.x3_items;
+  const int64_t upto = training ? ps.x3_items_fwd : ps.x3_items;
   const int rc = x3_pack_many(reinterpret_cast<const X3PackJob*>(ps.x3_jobs_dev.p), ps.x3_n_jobs, upto, st);
   if (rc) return rc;
   // (the forward pass still OWES the backward orientations; x3_bwd_pending -- "an event to wait for exists" -- is set only
   //  once they have been enqueued and the event recorded, pcmi_net_forward: a pass that fails in between must not leave a
   //  stale event to be waited for as if the packs were those of its weights -- ADVICE round 5)
-  ps.x3_bwd_owed = split_bwd && ps.x3_items > ps.x3_items_fwd;
+  ps.x3_bwd_owed = training && ps.x3_items > ps.x3_items_fwd;
   ps.x3_current = true;
   x3_set_prepacked(ps.x3_table.data(), (int)ps.x3_table.size());
   return PCMI_OK;
@@ -466,8 +456,8 @@ static long debug_env_long(const char* name) {
   return e ? atol(e) : 0;
 }
 
-static int ensure_streams(pcmi_net& n, bool second) {
-  if (n.side[0] && (!second || n.side[1])) return PCMI_OK;
+static int ensure_streams(pcmi_net& n) {
+  if (n.side) return PCMI_OK;
   // the weight gradients are off the critical path: lowest priority, so that the chain's kernels are dispatched
   // first and the weight-gradient workgroups fill what they leave idle (same priority measured: 17.5-19.4 against
   // 16.6 ms per iteration; weight gradients on the chain's own stream: 28 ms)
@@ -476,18 +466,14 @@ static int ensure_streams(pcmi_net& n, bool second) {
   // (a stream confined to a subset of the compute units -- hipExtStreamCreateWithCUMask, so that the chain's small
   //  kernels always find free units -- was tried: such a stream cannot be non-blocking and serialises against the
   //  caller's default stream, 165 against 253 pairs/s with any mask; profiles/r03j_bench_ab_cu_mask.txt)
-  // The second side stream exists ONLY under PCMI_WGRAD_SIDE2=1.  Round 5 created it unconditionally for one GPU call
-  // (idle unless the switch was on) and the forced 1-rank reducer run went from 15.8 to 45 ms per step: with the
-  // reducer's communication stream it was one stream too many for the device's hardware queues, two of the executor's
-  // streams shared a queue and serialised (profiles/r05b_idle_second_side_stream_and_forced_reducer.txt).  Streams of
-  // a rank in the step: compute, plan, weight-gradient side, communication -- nothing else may be added casually.
-  for (int i = 0; i < (second ? pcmi_net::kSides : 1); ++i) {
-    if (n.side[i]) continue;
-    PCMI_HIP_CHECK(hipStreamCreateWithPriority(&n.side[i], hipStreamNonBlocking, least));
-    PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_main[i], hipEventDisableTiming));
-    PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_side[i], hipEventDisableTiming));
-    PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_bkt_side[i], hipEventDisableTiming));
-  }
+  // Streams of a rank in the step: compute, plan, weight-gradient side, communication -- nothing else may be added casually.
+  // Round 5 created a second, idle side stream for one GPU call and the forced 1-rank reducer run went from 15.8 to 45 ms
+  // per step: with the reducer's communication stream it was one stream too many for the device's hardware queues, two of
+  // the executor's streams shared a queue and serialised (profiles/r05b_idle_second_side_stream_and_forced_reducer.txt).
+  PCMI_HIP_CHECK(hipStreamCreateWithPriority(&n.side, hipStreamNonBlocking, least));
+  PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_main, hipEventDisableTiming));
+  PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_side, hipEventDisableTiming));
+  PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_bkt_side, hipEventDisableTiming));
   if (!n.ev_bkt_main) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_bkt_main, hipEventDisableTiming));
   return PCMI_OK;
 }
@@ -503,17 +489,11 @@ struct BackwardRun {
   pcmi_ready_fn ready;
   void* ready_ctx;
   // set by begin()
-  hipStream_t st = nullptr, wst = nullptr;  // wst: the side stream of the op being differentiated (step)
-  bool two_sides = false;
-  bool stem_on_chain = true;  // the input layer's weight gradient on the chain (see step())
-  int64_t small_rows = 0;
+  hipStream_t st = nullptr, wst = nullptr;  // wst: the stream of the weight gradient being enqueued (step)
   PassState* ps = nullptr;
   DevBuf* wws = nullptr;
-  bool pending[pcmi_net::kSides] = {false, false}, used[pcmi_net::kSides] = {false, false};
+  bool pending = false, used = false;  // weight gradients on the side stream: not yet joined / since the pass began
   float* scratch_g = nullptr;
-  size_t scratch_stride = 0;
-  int bn_seen = 0;
-  bool bn_par = false;
   std::vector<int> bucket_last;
 
   BackwardRun(pcmi_net& net, const BackwardJob& j, const float* prm, float* g, const int64_t* blo, int nb, pcmi_ready_fn r,
@@ -521,31 +501,29 @@ struct BackwardRun {
       : n(net), job(j), params(prm), grads(g), bucket_lo_host(blo), n_buckets(nb), ready(r), ready_ctx(rc) {}
 
   int join_side() {  // `st` continues only after the weight gradients enqueued so far
-    for (int q = 0; q < pcmi_net::kSides; ++q) {
-      if (!pending[q]) continue;
-      PCMI_HIP_CHECK(hipEventRecord(n.ev_side[q], n.side[q]));
-      PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_side[q], 0));
-      pending[q] = false;
-    }
+    if (!pending) return PCMI_OK;
+    PCMI_HIP_CHECK(hipEventRecord(n.ev_side, n.side));
+    PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_side, 0));
+    pending = false;
     return PCMI_OK;
   }
   // The collected weight gradients go to the side stream now: everything their operands need has been enqueued on `st`.
   int flush_group() {
     if (wgrad_group_size(n.wgroup) == 0) return PCMI_OK;
-    PCMI_HIP_CHECK(hipEventRecord(n.ev_main[0], st));
-    PCMI_HIP_CHECK(hipStreamWaitEvent(n.side[0], n.ev_main[0], 0));
-    pending[0] = used[0] = true;
+    PCMI_HIP_CHECK(hipEventRecord(n.ev_main, st));
+    PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_main, 0));
+    pending = used = true;
     int slot = -1;  // (pcmi_net_time_all: the grouped launch between two events of the current set)
     if (n.timed_keep_groups && n.timed_cur >= 0) {
       const int set = n.timed_cur % n.timed_sets;
       if (n.timed_group_n[set] < pcmi_net::kTimedGroups) slot = set * pcmi_net::kTimedGroups + n.timed_group_n[set];
     }
-    if (slot >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_group_ev[2 * slot], n.side[0]));
+    if (slot >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_group_ev[2 * slot], n.side));
     const long l0 = g_launches;
-    const int rc = wgrad_group_flush(n.wgroup, n.side[0]);
+    const int rc = wgrad_group_flush(n.wgroup, n.side);
     if (slot >= 0 && !rc) {
       n.timed_group_cnt[slot] = (int)(g_launches - l0);
-      PCMI_HIP_CHECK(hipEventRecord(n.timed_group_ev[2 * slot + 1], n.side[0]));
+      PCMI_HIP_CHECK(hipEventRecord(n.timed_group_ev[2 * slot + 1], n.side));
       ++n.timed_group_n[n.timed_cur % n.timed_sets];
     }
     return rc;
@@ -573,37 +551,18 @@ struct BackwardRun {
     }
     int rc = ps->grad.reserve(off, st);
     if (rc) return rc;
-    // per BatchNorm op its own [2 segments][dbeta, dgamma] sums: a BatchNorm whose parameter gradients are accumulated on
-    // the side stream (bn_param_accumulate) must not have its sums overwritten by the next BatchNorm of the chain
-    int n_bn = 0;
-    for (int i = 0; i < n_ops; ++i) n_bn += n.ops[i].type == PCMI_OP_BN;
-    rc = ps->small.reserve((size_t)(n_bn + 1) * 4 * max_c * sizeof(float) + 256, st);
+    // the BatchNorm parameter-gradient sums ([2 segments][dbeta, dgamma]): every BatchNorm reads and writes them on the
+    // chain's stream inside its own backward call, so one block serves them all in turn
+    rc = ps->small.reserve((size_t)4 * max_c * sizeof(float) + 256, st);
     if (rc) return rc;
     scratch_g = (float*)ps->small.p;
-    scratch_stride = 4 * (size_t)max_c;
-    bn_seen = 0;
-    {  // PCMI_BN_SMALL_PAR=1: a small BatchNorm's backward with its two segments side by side and the parameter gradients
-       // added by a kernel on the side stream.  Measured (profiles/r05h_*): 272.5 against 275.9 pairs/s with the segments one
-       // after the other inside the kernel -- 30 more launches and event pairs on the weight-gradient stream cost more than
-       // the shorter BatchNorm kernels return.  Off.
-      const char* e = getenv("PCMI_BN_SMALL_PAR");
-      bn_par = e && e[0] == '1';
-    }
-    two_sides = debug_env_long("PCMI_WGRAD_SIDE2") != 0;
-    {
-      const char* e = getenv("PCMI_STEM_WGRAD_ON_CHAIN");
-      stem_on_chain = !(e && e[0] == '0');
-    }
-    rc = ensure_streams(n, two_sides);
+    rc = ensure_streams(n);
     if (rc) return rc;
-    small_rows = 8192;  // (= the default of PCMI_WGRAD_X3T: what is under it takes the pair-list kernel)
-    for (int q = 0; q < (two_sides ? 2 : 1); ++q) {
-      rc = n.ws_side[q].reserve(ps->ws.cap, n.side[q]);
-      if (rc) return rc;
-      pending[q] = used[q] = false;
-    }
-    wst = n.side[0];
-    wws = &n.ws_side[0];
+    rc = n.ws_side.reserve(ps->ws.cap, n.side);
+    if (rc) return rc;
+    pending = used = false;
+    wst = n.side;
+    wws = &n.ws_side;
     if (!n.wgroup) n.wgroup = wgrad_group_create();
     wgrad_group_drop(n.wgroup);
     if (ps->x3_bwd_pending) {  // the backward-data weight packs of this pass were enqueued on the side stream (forward)
@@ -644,36 +603,28 @@ struct BackwardRun {
       // a coarse-level 3^3 layer: its gradient joins the open group and is launched with the others of its run (at the
       // next layer that does not fit the group, at a bucket boundary, or at the end of the pass)
       bool grouped = false;
-      // PCMI_DEBUG_SKIP_WGRAD_ROWS=<n> (timing diagnostic, WRONG gradients): the weight gradients of layers with at least n
-      // rows on both sides are not launched at all (1 = none is) -- what the chain costs without them beside it
-      // (profiles/r06a_*: the bound of moving the level-1 weight gradients out of the backward pass)
-      const long skip_rows = debug_env_long("PCMI_DEBUG_SKIP_WGRAD_ROWS");
-      const bool skip_wgrad = skip_rows > 0 && std::min(n_in, n_out) >= skip_rows && op.in != n.input_tensor;
-      if (!skip_wgrad && !two_sides && !op.transpose && op.kernel_size == 3 && op.stride == 1 && !op.has_bias && map && (n.timed_keep_groups || n.timed_slot(i) < 0)) {
-        grouped = wgrad_group_add(n.wgroup, x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, map, grads + op.w_off, 1, n.side[0]);
+      if (!op.transpose && op.kernel_size == 3 && op.stride == 1 && !op.has_bias && map && (n.timed_keep_groups || n.timed_slot(i) < 0)) {
+        grouped = wgrad_group_add(n.wgroup, x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, map, grads + op.w_off, 1, n.side);
         if (!grouped && wgrad_group_size(n.wgroup) > 0) {  // another tile shape, or the group is full: launch it, start a new one
           rc = flush_group();
           if (rc) return rc;
-          grouped = wgrad_group_add(n.wgroup, x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, map, grads + op.w_off, 1, n.side[0]);
+          grouped = wgrad_group_add(n.wgroup, x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, map, grads + op.w_off, 1, n.side);
         }
       }
-      if (!grouped && !skip_wgrad) {
-      const int sq = (two_sides && (std::min(n_in, n_out) < small_rows || op.kernel_size != 3 || op.stride != 1 ||
-                                    std::min(op.cin, op.cout) < 64)) ? 1 : 0;
+      if (!grouped) {
       // The layer that reads the network's input is the LAST op of a backward pass: nothing is left on the chain that its
       // weight gradient could run beside, the pass's join follows.  On the side stream it cost two event hand-overs
       // (chain -> side -> chain, ~10 us each in the kernel trace) for 50 us of work: it stays on the chain, with the chain's
-      // workspace.  PCMI_STEM_WGRAD_ON_CHAIN=0: on the side stream like every other weight gradient (A/B; read per pass).
-      const bool on_chain = op.in == n.input_tensor && stem_on_chain;
-      if (on_chain) {
+      // workspace.
+      if (op.in == n.input_tensor) {
         wst = st;
         wws = &ps->ws;
       } else {
-        wst = n.side[sq];
-        wws = &n.ws_side[sq];
-        PCMI_HIP_CHECK(hipEventRecord(n.ev_main[sq], st));
-        PCMI_HIP_CHECK(hipStreamWaitEvent(wst, n.ev_main[sq], 0));
-        pending[sq] = used[sq] = true;
+        wst = n.side;
+        wws = &n.ws_side;
+        PCMI_HIP_CHECK(hipEventRecord(n.ev_main, st));
+        PCMI_HIP_CHECK(hipStreamWaitEvent(wst, n.ev_main, 0));
+        pending = used = true;
       }
       const int tw = n.timed_slot(i);
       if (tw >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tw + 4], wst));
@@ -710,19 +661,11 @@ struct BackwardRun {
       const float* stats0 = (const float*)(ps->act.p + ps->stat_off[i]);
       const uint32_t* rbits = (op.relu && ps->bits_off[i] != SIZE_MAX) ? (const uint32_t*)(ps->act.p + ps->bits_off[i]) : nullptr;
       const int64_t sp = ps->split[n.tensors[op.in].level];
-      if (sp < n_in) {  // a segment = one forward call of the reference: own statistics, own sums; one launch pair
-        float* sums = scratch_g + (size_t)(++bn_seen) * scratch_stride;
-        int deferred = 0;
+      if (sp < n_in)  // a segment = one forward call of the reference: own statistics, own sums; one launch pair
         rc = bn_backward2(dy.p, dy.ld, x.p, x.ld, op.relu ? y.p : nullptr, y.ld, n_in, sp, op.cout, params + op.w_off, stats0,
-                          stats0 + op.cout, 3 * op.cout, dx.p, dx.ld, dr.p, dr.ld, pl.acc_res, sums, grads + op.w_off,
-                          grads + op.b_off, ps->ws.p, ps->ws.cap, st, (two_sides || !bn_par) ? nullptr : &deferred, rbits);
-        if (!rc && deferred) {  // the parameter gradients of this BatchNorm: on the side stream, behind the sums
-          PCMI_HIP_CHECK(hipEventRecord(n.ev_main[0], st));
-          PCMI_HIP_CHECK(hipStreamWaitEvent(n.side[0], n.ev_main[0], 0));
-          pending[0] = used[0] = true;
-          rc = bn_param_accumulate(sums, op.cout, grads + op.w_off, grads + op.b_off, n.side[0]);
-        }
-      } else
+                          stats0 + op.cout, 3 * op.cout, dx.p, dx.ld, dr.p, dr.ld, pl.acc_res, scratch_g, grads + op.w_off,
+                          grads + op.b_off, ps->ws.p, ps->ws.cap, st, rbits);
+      else
         rc = bn_backward(dy.p, dy.ld, x.p, x.ld, op.relu ? y.p : nullptr, y.ld, n_in, op.cout, params + op.w_off, stats0,
                          stats0 + op.cout, dx.p, dx.ld, dr.p, dr.ld, pl.acc_res, scratch_g, scratch_g + op.cout,
                          grads + op.w_off, grads + op.b_off, ps->ws.p, ps->ws.cap, st, rbits);
@@ -756,10 +699,8 @@ struct BackwardRun {
         rc = flush_group();  // (collected gradients may belong to this bucket: they must be on the side stream before its event)
         if (rc) return rc;
         PCMI_HIP_CHECK(hipEventRecord(n.ev_bkt_main, st));
-        for (int q = 0; q < pcmi_net::kSides; ++q) {
-          if (used[q]) PCMI_HIP_CHECK(hipEventRecord(n.ev_bkt_side[q], n.side[q]));
-          n.bkt_side[q] = used[q];
-        }
+        if (used) PCMI_HIP_CHECK(hipEventRecord(n.ev_bkt_side, n.side));
+        n.bkt_side = used;
         n.bkt_valid = true;
         ready(ready_ctx, b);
       }
@@ -891,7 +832,7 @@ int pcmi_net_export_tensor(pcmi_net_t* net, int pass, int tensor, int64_t* rows,
 
 int pcmi_net_memory_bytes(pcmi_net_t* net, size_t* bytes) {
   PCMI_REQUIRE(net && bytes, PCMI_ERR_INVALID, "net_memory_bytes: null argument");
-  size_t b = net->ws_side[0].cap + net->ws_side[1].cap;
+  size_t b = net->ws_side.cap;
   for (auto& p : net->passes) b += p.act.cap + p.ws.cap + p.grad.cap + p.small.cap + p.x3_packs.cap + p.x3_jobs_dev.cap;
   *bytes = b;
   return PCMI_OK;
@@ -1025,10 +966,6 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
     ps.x3_bwd_pending = false;
   }
   const bool train0 = (training & 1) != 0;
-  const bool pack_split = train0 && [] {  // PCMI_X3_PACK_SPLIT=0: both orientations at the top of the pass (round 4; A/B)
-    const char* e = getenv("PCMI_X3_PACK_SPLIT");
-    return !(e && e[0] == '0');
-  }();
   // PCMI_X3_PACK_SIDE (round 6, default on for training passes): the forward orientations are packed on the side stream, behind
   // everything enqueued so far, and the pass waits for them in front of the first convolution that reads a pack -- the stem and
   // the 32-channel layers of the first two levels (~0.45 ms) do not.  (Round 5 measured this at +0.3 %, inside the spread, with a
@@ -1039,17 +976,17 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
   }();
   bool pack_joined = true;
   if (pack_side) {
-    rc = ensure_streams(n, false);
+    rc = ensure_streams(n);
     if (rc) return rc;
     if (!n.ev_fwd_fork) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_fork, hipEventDisableTiming));
     if (!n.ev_fwd_pack) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_pack, hipEventDisableTiming));
     PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_fork, st));
-    PCMI_HIP_CHECK(hipStreamWaitEvent(n.side[0], n.ev_fwd_fork, 0));
-    rc = x3_prepack(n, ps, params, n.side[0], pack_split);
-    PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_pack, n.side[0]));
+    PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_fwd_fork, 0));
+    rc = x3_prepack(n, ps, params, n.side, train0);
+    PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_pack, n.side));
     pack_joined = false;
   } else {
-    rc = x3_prepack(n, ps, params, st, pack_split);
+    rc = x3_prepack(n, ps, params, st, train0);
   }
   const X3TableScope x3_scope;  // the table is this thread's only until the pass has been enqueued
   if (rc) return rc;
@@ -1073,54 +1010,11 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
         pack_bwd_at = i;
         break;
       }
-    rc = ensure_streams(n, false);
+    rc = ensure_streams(n);
     if (rc) return rc;
     if (!ps.x3_bwd_packed) PCMI_HIP_CHECK(hipEventCreateWithFlags(&ps.x3_bwd_packed, hipEventDisableTiming));
   }
   g_prof_fwd.lap(2);
-  // PCMI_DEBUG_LATE_WGRAD=<rows> (timing prototype, WRONG results; use with PCMI_DEBUG_SKIP_WGRAD_ROWS=<rows>): the weight
-  // gradients of the layers with at least <rows> rows on both sides -- which the backward pass then leaves out -- are
-  // launched HERE, on the side stream beside the forward pass, into a scratch buffer (operands: whatever the arenas hold),
-  // and the pass waits for them in front of the first such layer: the schedule of "the level-1 weight gradients of
-  // iteration i run beside the forward pass of iteration i + 1 and their layers are updated before it reaches them",
-  // without the trainer-side plumbing.  profiles/r06b_*.
-  int late_first_op = -1;
-  if (const long late_rows = debug_env_long("PCMI_DEBUG_LATE_WGRAD"); late_rows > 0 && train0 && ps.grad.p && !ps.grad_off.empty()) {
-    rc = ensure_streams(n, false);
-    if (rc) return rc;
-    static DevBuf late_scratch;
-    rc = late_scratch.reserve((size_t)27 * 256 * 256 * sizeof(float), st);
-    if (rc) return rc;
-    rc = n.ws_side[0].reserve(ps.ws.cap, n.side[0]);
-    if (rc) return rc;
-    PCMI_HIP_CHECK(hipEventRecord(n.ev_main[0], st));
-    PCMI_HIP_CHECK(hipStreamWaitEvent(n.side[0], n.ev_main[0], 0));
-    const bool late_fp32 = debug_env_long("PCMI_DEBUG_LATE_FP32") != 0;  // the pair-list fp32 kernel for them (small workgroups)
-    const char* x3t_env = getenv("PCMI_WGRAD_X3T");
-    const std::string x3t_saved = x3t_env ? x3t_env : "";
-    if (late_fp32) setenv("PCMI_WGRAD_X3T", "0", 1);
-    struct RestoreEnv {
-      bool on, had;
-      const std::string& v;
-      ~RestoreEnv() {
-        if (!on) return;
-        if (had) setenv("PCMI_WGRAD_X3T", v.c_str(), 1); else unsetenv("PCMI_WGRAD_X3T");
-      }
-    } restore{late_fp32, x3t_env != nullptr, x3t_saved};
-    for (int i = n_ops - 1; i >= 0; --i) {
-      const auto& op = n.ops[i];
-      if (op.type != PCMI_OP_CONV || op.in == n.input_tensor) continue;
-      const int64_t n_in = ps.rows[n.tensors[op.in].level], n_out = ps.rows[n.tensors[op.out].level];
-      if (std::min(n_in, n_out) < late_rows) continue;
-      late_first_op = i;
-      const View x = act_view(n, ps, op.in);
-      const View dy = grad_view(n, ps, op.out, out_feats, out_ld);
-      rc = spconv_backward_weight(x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, ps.has_map[i] ? &ps.maps[i] : nullptr,
-                                  op.transpose, (float*)late_scratch.p, nullptr, 0, n.ws_side[0].p, n.ws_side[0].cap, n.side[0]);
-      if (rc) return rc;
-    }
-    if (late_first_op >= 0) PCMI_HIP_CHECK(hipEventRecord(n.ev_side[0], n.side[0]));
-  }
   // ---- run --------------------------------------------------------------------------------------
   if (!n.timed_ops.empty()) {  // the next event set of the ring (pcmi_net_time_ops); its old records are dropped
     ++n.timed_cur;
@@ -1138,7 +1032,7 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
   std::vector<char> on_side(n_ops, 0);
   {
     const char* e = getenv("PCMI_FWD_BRANCH");
-    if (!(e && e[0] == '0') && late_first_op < 0) {
+    if (!(e && e[0] == '0')) {
       for (int i = 3; i + 2 < n_ops; ++i) {
         const auto &c = n.ops[i], &b1 = n.ops[i + 1], &b2 = n.ops[i + 2];
         if (c.type != PCMI_OP_CONV || c.kernel_size != 1 || b1.type != PCMI_OP_BN || b1.in != c.out || b1.relu || b1.in2 >= 0 ||
@@ -1160,9 +1054,9 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
   bool any_fork = false;
   for (int i = 0; i < n_ops; ++i) any_fork |= fork_at[i] >= 0;
   if (any_fork) {
-    rc = ensure_streams(n, false);
+    rc = ensure_streams(n);
     if (rc) return rc;
-    rc = n.ws_side[0].reserve(ps.ws.cap, n.side[0]);
+    rc = n.ws_side.reserve(ps.ws.cap, n.side);
     if (rc) return rc;
     if (!n.ev_fwd_fork) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_fork, hipEventDisableTiming));
     if (!n.ev_fwd_join) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_join, hipEventDisableTiming));
@@ -1219,19 +1113,18 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
   };
   for (int i = 0; i < n_ops; ++i) {
     const auto& op = n.ops[i];
-    if (i == late_first_op) PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_side[0], 0));  // (PCMI_DEBUG_LATE_WGRAD)
     if (!pack_joined && (i >= ps.x3_first_op || fork_at[i] >= 0)) {  // (a forked 1x1 layer may pack for itself on the side stream: keep it simple)
       PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_fwd_pack, 0));
       pack_joined = true;
     }
     if (fork_at[i] >= 0) {  // everything enqueued so far is the branch's input (and more): the branch starts behind it
       PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_fork, st));
-      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side[0], n.ev_fwd_fork, 0));
-      rc = run_op(fork_at[i], n.side[0], n.ws_side[0]);
+      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_fwd_fork, 0));
+      rc = run_op(fork_at[i], n.side, n.ws_side);
       if (rc) return rc;
-      rc = run_op(fork_at[i] + 1, n.side[0], n.ws_side[0]);
+      rc = run_op(fork_at[i] + 1, n.side, n.ws_side);
       if (rc) return rc;
-      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_join, n.side[0]));
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_join, n.side));
     }
     if (join_before[i] >= 0) PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_fwd_join, 0));
     if (!on_side[i]) {
@@ -1239,11 +1132,11 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
       if (rc) return rc;
     }
     if (i == pack_bwd_at) {  // the side stream starts behind this point of the pass (and behind the job table's upload)
-      PCMI_HIP_CHECK(hipEventRecord(n.ev_main[0], st));
-      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side[0], n.ev_main[0], 0));
-      rc = x3_pack_many(reinterpret_cast<const X3PackJob*>(ps.x3_jobs_dev.p), ps.x3_n_jobs, ps.x3_items, n.side[0], ps.x3_items_fwd);
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_main, st));
+      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_main, 0));
+      rc = x3_pack_many(reinterpret_cast<const X3PackJob*>(ps.x3_jobs_dev.p), ps.x3_n_jobs, ps.x3_items, n.side, ps.x3_items_fwd);
       if (rc) return rc;
-      PCMI_HIP_CHECK(hipEventRecord(ps.x3_bwd_packed, n.side[0]));
+      PCMI_HIP_CHECK(hipEventRecord(ps.x3_bwd_packed, n.side));
       ps.x3_bwd_owed = false;
       ps.x3_bwd_pending = true;
     }
@@ -1270,9 +1163,8 @@ int pcmi_net_stream_wait_bucket(pcmi_net_t* net, pcmi_stream_t stream) {
   PCMI_REQUIRE(net, PCMI_ERR_INVALID, "net_stream_wait_bucket: null argument");
   PCMI_REQUIRE(net->bkt_valid, PCMI_ERR_INVALID, "net_stream_wait_bucket: only valid inside a pcmi_ready_fn callback");
   PCMI_HIP_CHECK(hipStreamWaitEvent(as_stream(stream), net->ev_bkt_main, 0));
-  if (!debug_env_long("PCMI_DEBUG_SKIP_BUCKET_SIDE_WAIT"))
-    for (int q = 0; q < pcmi_net::kSides; ++q)
-      if (net->bkt_side[q]) PCMI_HIP_CHECK(hipStreamWaitEvent(as_stream(stream), net->ev_bkt_side[q], 0));
+  if (!debug_env_long("PCMI_DEBUG_SKIP_BUCKET_SIDE_WAIT") && net->bkt_side)
+    PCMI_HIP_CHECK(hipStreamWaitEvent(as_stream(stream), net->ev_bkt_side, 0));
   return PCMI_OK;
 }
 

@@ -20,7 +20,6 @@
 // and dk in the backward -- no finishing launches, no float atomics.  Forward + backward: 4 launches (pack + forward,
 // pack + backward) instead of 8, 88 instead of 168 us at n = 4096, c = 32; what is left is hand-over latency, not matrix
 // work (profiles/r04n_loss_block_nce_matrix_cores_and_hardest_host.txt: chunk loops 11.5 / 27 us, finish 14 / 19 us).
-// -DPCMI_NCE_DIAG_NO_LOOP / -DPCMI_NCE_DIAG_NO_FINISH compile one of the two out (timing only, wrong results).
 #include <algorithm>
 #include <cstdlib>
 
@@ -163,11 +162,7 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_x3_kernel(const u32x4* __restr
   stage_store<false, false>(s_st[0], nullptr, t, sr);
   __syncthreads();
   int buf = 0;
-#if defined(PCMI_NCE_DIAG_NO_LOOP)
-  for (int64_t b0 = cbeg; b0 < cbeg; b0 += kChunk, buf ^= 1) {
-#else
   for (int64_t b0 = cbeg; b0 < cend; b0 += kChunk, buf ^= 1) {
-#endif
     stage_load<false, false>(oth_rows, nullptr, nullptr, n, min(b0 / kChunk + 1, last_chunk), t, sr);
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise sinks the loads to their use at the end of the step)
     u32x4 ak[2][3];
@@ -225,9 +220,6 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_x3_kernel(const u32x4* __restr
   }
   // ---- the last workgroup of the row tile: merge the splits (in split order), lse, the tile's share of the loss ----
   const int splits = (int)gridDim.y;
-#if defined(PCMI_NCE_DIAG_NO_FINISH)  // timing diagnostic (no lse, no loss)
-  return;
-#endif
   if (!arrive_last(&counters[blockIdx.x], (unsigned)splits, &s_flag)) return;
   float contrib = 0.f;
   if (t < kOwn) {
@@ -303,11 +295,7 @@ __device__ __forceinline__ void nce_bwd_body(const u32x4* __restrict__ own_rows,
   stage_store<true, FOR_K>(s_st[0], s_lse[0], t, sr);
   __syncthreads();
   int buf = 0;
-#if defined(PCMI_NCE_DIAG_NO_LOOP)
-  for (int64_t b0 = cbeg; b0 < cbeg; b0 += kChunk, buf ^= 1) {
-#else
   for (int64_t b0 = cbeg; b0 < cend; b0 += kChunk, buf ^= 1) {
-#endif
     stage_load<true, FOR_K>(oth_rows, oth_cols, lse, n, min(b0 / kChunk + 1, last_chunk), t, sr);
     __builtin_amdgcn_sched_barrier(0);  // (the scheduler otherwise sinks the loads to their use at the end of the step)
     float lb[2][4];  // log2-domain lse of the other rows (side 1)
@@ -390,9 +378,6 @@ __device__ __forceinline__ void nce_bwd_body(const u32x4* __restrict__ own_rows,
 #pragma unroll
       for (int ct = 0; ct < NCT; ++ct) mine[a * 32 + 16 * ct + i] = dacc[g][ct][r];
     }
-#if defined(PCMI_NCE_DIAG_NO_FINISH)
-  return;
-#endif
   if (!arrive_last(counter, (unsigned)splits, s_flag)) return;
   // the last workgroup of the row tile: the shares in split order, four channels per thread
   constexpr int F4 = C / 4;  // float4 per row

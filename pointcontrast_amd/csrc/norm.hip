@@ -43,9 +43,9 @@ unsigned* stream_counters(hipStream_t st, size_t n) {
 }
 
 constexpr int kMaxRedBlocks = 1024;
-// up to this many row blocks the statistics kernel finishes the reduction itself (last-arriving workgroup), beyond
-// it a separate one-wave-per-channel kernel does (the serial merge of the partials would be a visible tail)
-constexpr int kFuseFinalBlocks = 256;
+// up to this many row blocks colreduce_final_kernel merges the partials, beyond it a one-wave-per-channel kernel does
+// (bn_stats_final_kernel / colsum2_final_kernel); a two-segment launch stays within it
+constexpr int kFinalMergeBlocks = 256;
 
 struct RedGeom {
   int c4;              // float4 columns
@@ -93,10 +93,8 @@ __device__ inline void chan_merge(float& n, float4& mean, float4& m2, float on, 
   n = tot;
 }
 
-// What the last-arriving workgroup of a fused statistics launch needs to finish the reduction (counter == nullptr:
-// a separate kernel does it).
+// What the merge of a statistics reduction writes (colreduce_final_kernel, bn_small_fwd_kernel).
 struct RedFinal {
-  unsigned* counter;
   // MODE 0 (BatchNorm forward statistics)
   float eps, momentum;
   float* running_mean;
@@ -109,57 +107,9 @@ struct RedFinal {
   float* out_b;
   float* acc_a;
   float* acc_b;
-  // two-segment launches (gridDim.y == 2, see colreduce_partial_kernel): floats between the segments' outputs
+  // two-segment launches (gridDim.y == 2): floats between the segments' outputs
   int out_seg_stride;
 };
-
-// The merge of the per-block partials of one statistics launch (one segment), by ONE workgroup, in a fixed order ->
-// deterministic.  Two levels, in the geometry of the main pass: thread (rl, col) folds the blocks rl, rl + rp, ... of its
-// four channels (coalesced float4 loads, independent of each other), then the c4 column threads fold the rp lanes
-// through LDS.  (A thread-per-channel loop over all blocks was one L2 latency per block: 20 us for 80 blocks.)
-// All 256 threads call; threads t < c4 return the result: MODE 0 (a, b, cnt) = (mean, M2, rows), MODE 1 (sum a, sum b).
-template <int MODE>
-__device__ __forceinline__ void colreduce_merge(const float* __restrict__ part, int nblocks, int64_t n, int rows_per_block,
-                                                int c4, int rp, int t, float4* s_a, float4* s_b, float* s_n, float4& a,
-                                                float4& b, float& cnt) {
-  const int col = t % c4, rl = t / c4;
-  const int c = c4 * 4;
-  cnt = 0.f;
-  a = make_float4(0.f, 0.f, 0.f, 0.f);  // MODE 0: running mean, MODE 1: sum a
-  b = a;                                 // MODE 0: running M2,   MODE 1: sum b
-  if (rl < rp) {
-#pragma unroll 4
-    for (int q = rl; q < nblocks; q += rp) {
-      const float4 pa = *reinterpret_cast<const float4*>(part + (int64_t)q * 2 * c + col * 4);
-      const float4 pb = *reinterpret_cast<const float4*>(part + (int64_t)q * 2 * c + c + col * 4);
-      if (MODE == 0) {
-        const int64_t b0 = (int64_t)q * rows_per_block;
-        chan_merge(cnt, a, b, (float)(min(b0 + (int64_t)rows_per_block, n) - b0), pa, pb);
-      } else {
-        a.x += pa.x; a.y += pa.y; a.z += pa.z; a.w += pa.w;
-        b.x += pb.x; b.y += pb.y; b.z += pb.z; b.w += pb.w;
-      }
-    }
-  }
-  __syncthreads();  // (the caller's earlier use of the LDS arrays)
-  s_a[t] = a;
-  s_b[t] = b;
-  s_n[t] = cnt;
-  __syncthreads();
-  if (t >= c4) return;
-  a = s_a[t];
-  b = s_b[t];
-  cnt = s_n[t];
-  for (int q = 1; q < rp; ++q) {
-    const float4 va = s_a[q * c4 + t], vb = s_b[q * c4 + t];
-    if (MODE == 0) {
-      chan_merge(cnt, a, b, s_n[q * c4 + t], va, vb);
-    } else {
-      a.x += va.x; a.y += va.y; a.z += va.z; a.w += va.w;
-      b.x += vb.x; b.y += vb.y; b.z += vb.z; b.w += vb.w;
-    }
-  }
-}
 
 // MODE 0: (mean, M2, rows) -> invstd / unbiased variance; both: what column thread t of the merging workgroup stores
 __device__ __forceinline__ float4 bn_invstd(const float4& m2, float cnt, float eps) {
@@ -201,22 +151,22 @@ __device__ __forceinline__ void colreduce_write(const RedFinal& fin, int t, cons
 // of its own with s_waitcnt vmcnt(0) in front of and behind it (hipcc -S) -- eight serialised memory round trips per batch
 // where the batch exists to make it one.  For the same reason a row past the block is no longer `ok ? load : 0` but a load
 // of the block's last row whose contribution is zeroed afterwards (v_cndmask, no branch).
+// MASK 0 is held to 8 waves per SIMD (<= 64 VGPRs): <1, 0> had that while the kernel could end in the merge of its own
+// partials (a form since removed); without it hipcc gives <1, 0> 66 VGPRs, a wave per SIMD less.
 template <int MODE, int MASK = 0>
-__global__ __launch_bounds__(256) void colreduce_partial_kernel(
+__global__ __launch_bounds__(256, MASK == 0 ? 8 : 1) void colreduce_partial_kernel(
     const float* __restrict__ x, int64_t x_ld, const float* __restrict__ dy, int64_t dy_ld,
     const float* __restrict__ ymask, int64_t y_ld, const float* __restrict__ mean,
     const float* __restrict__ invstd, int64_t n, int c4, int rp, int rows_per_block,
-    float* __restrict__ part /* [nblocks][2][c] */, RedFinal fin, int64_t seg_split = 0, int in_seg_stride = 0,
+    float* __restrict__ part /* [nblocks][2][c] */, int64_t seg_split = 0, int in_seg_stride = 0,
     int64_t part_seg_stride = 0, const uint32_t* __restrict__ bits = nullptr /* MODE 1: the ReLU pattern, see relu_bits */) {
   __shared__ float4 s_a[256];
   __shared__ float4 s_b[256];
-  __shared__ unsigned s_last;
   const int t = threadIdx.x;
   const int col = t % c4, rl = t / c4;
   const int c = c4 * 4;
   // gridDim.y == 2: the rows [0, seg_split) and [seg_split, n) are two independent reductions (the two point clouds
-  // of a pair in one sparse tensor: BatchNorm statistics per cloud) in ONE launch, each with its own partials,
-  // arrival counter and outputs
+  // of a pair in one sparse tensor: BatchNorm statistics per cloud) in ONE launch, each with its own partials
   int64_t base = 0;
   if (gridDim.y > 1) {
     const int sg = blockIdx.y;
@@ -226,18 +176,6 @@ __global__ __launch_bounds__(256) void colreduce_partial_kernel(
     if (MODE == 1) {
       mean += sg * in_seg_stride;
       invstd += sg * in_seg_stride;
-    }
-    if (fin.counter) {
-      fin.counter += sg;
-      const int os = sg * fin.out_seg_stride;
-      if (MODE == 0) {
-        fin.save_mean += os;
-        fin.save_invstd += os;
-        if (fin.save_unbiased) fin.save_unbiased += os;
-      } else {
-        fin.out_a += os;
-        fin.out_b += os;
-      }
     }
     if ((int64_t)blockIdx.x * rows_per_block >= n) return;  // the shorter segment has fewer row blocks
   }
@@ -321,14 +259,6 @@ __global__ __launch_bounds__(256) void colreduce_partial_kernel(
       reinterpret_cast<float4*>(p0 + c)[t] = sb;
     }
   }
-  // ---- fused final: the last workgroup to arrive merges the per-block partials (colreduce_merge) ----
-  if (fin.counter == nullptr) return;
-  const int nblocks = (int)((n + rows_per_block - 1) / rows_per_block);  // (= gridDim.x for a one-segment launch)
-  if (!arrive_last(fin.counter, (unsigned)nblocks, &s_last)) return;
-  __shared__ float s_n[256];
-  float cnt;
-  colreduce_merge<MODE>(part, nblocks, n, rows_per_block, c4, rp, t, s_a, s_b, s_n, a, b, cnt);
-  if (t < c4) colreduce_write<MODE>(fin, t, a, b, cnt);
 }
 
 // The backward sums of colreduce_partial_kernel<1> within 48 registers and 4 KiB of LDS, for large activations.
@@ -735,8 +665,6 @@ struct BnSmallBwd {
 // The segments of a two-segment tensor are handled ONE AFTER THE OTHER by the same workgroup: the parameter gradients
 // are (acc + sums of segment 0) + sums of segment 1, in that order -- what two consecutive one-segment calls accumulate
 // (and what bn_bwd_apply_kernel does) -- without a hand-over between workgroups.
-// gridDim.y == 2 (a two-segment tensor whose parameter gradients somebody else accumulates from `sum_g / sum_gx` --
-// a.acc_g == nullptr, bn_param_acc_kernel): one workgroup per segment, side by side.
 template <int RPT, int THREADS>
 __global__ __launch_bounds__(THREADS) void bn_small_bwd_kernel(BnSmallBwd a) {
   __shared__ float4 s_w[16][kSmallCG];
@@ -745,7 +673,6 @@ __global__ __launch_bounds__(THREADS) void bn_small_bwd_kernel(BnSmallBwd a) {
   const int col4 = blockIdx.x * kSmallCG + cg;
   const int cb = blockIdx.x * (4 * kSmallCG);
   const int n_seg = a.split < a.n ? 2 : 1;
-  const int sg_first = gridDim.y > 1 ? (int)blockIdx.y : 0, sg_end = gridDim.y > 1 ? (int)blockIdx.y + 1 : n_seg;
   const float4 ga = reinterpret_cast<const float4*>(a.gamma)[col4];
   float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), pb = pa;
   if (a.acc_g && rl == 0) {
@@ -757,7 +684,7 @@ __global__ __launch_bounds__(THREADS) void bn_small_bwd_kernel(BnSmallBwd a) {
   const uint32_t lane_b = (uint32_t)cg * 16u;
   const bool masked = a.ymask != nullptr, has_res = a.dres != nullptr, bitmask = a.bits != nullptr;
 #pragma unroll 1
-  for (int sg = sg_first; sg < sg_end; ++sg) {
+  for (int sg = 0; sg < n_seg; ++sg) {
     const int64_t base = sg ? a.split : 0;
     const int ns = (int)(n_seg > 1 ? (sg ? a.n - a.split : a.split) : a.n);
     const float4 mu = reinterpret_cast<const float4*>(a.mean + sg * a.stat_stride)[col4];
@@ -833,23 +760,6 @@ __global__ __launch_bounds__(THREADS) void bn_small_bwd_kernel(BnSmallBwd a) {
     reinterpret_cast<float4*>(a.acc_g)[col4] = pa;
     reinterpret_cast<float4*>(a.acc_gx)[col4] = pb;
   }
-}
-
-// acc += sums of segment 0, then += sums of segment 1 (the order of two consecutive one-segment calls): the parameter
-// gradients of a BatchNorm whose backward ran its two segments side by side.  One thread per four channels.
-__global__ void bn_param_acc_kernel(float* __restrict__ acc_g, float* __restrict__ acc_gx, const float* __restrict__ sum_g,
-                                    const float* __restrict__ sum_gx, int sum_stride, int c4, int n_seg) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= c4) return;
-  float4 a = reinterpret_cast<float4*>(acc_g)[t], b = reinterpret_cast<float4*>(acc_gx)[t];
-  for (int sg = 0; sg < n_seg; ++sg) {
-    const float4 u = reinterpret_cast<const float4*>(sum_g + sg * sum_stride)[t];
-    const float4 v = reinterpret_cast<const float4*>(sum_gx + sg * sum_stride)[t];
-    a = make_float4(a.x + u.x, a.y + u.y, a.z + u.z, a.w + u.w);
-    b = make_float4(b.x + v.x, b.y + v.y, b.z + v.z, b.w + v.w);
-  }
-  reinterpret_cast<float4*>(acc_g)[t] = a;
-  reinterpret_cast<float4*>(acc_gx)[t] = b;
 }
 
 // y = relu?( (x - mean) * (invstd * gamma) + beta (+ residual) )
@@ -1034,8 +944,6 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ a
   *reinterpret_cast<float4*>(out + r * out_ld + sub * 4) = o;
 }
 
-// PCMI_BN_FUSED_FINAL=1: the statistics launch merges its own partials (last-arriving workgroup) instead of leaving
-// them to colreduce_final_kernel -- the round-1..3 form, kept for the A/B (see colreduce_final_kernel)
 // PCMI_BN_LEAN_ROWS: from this many rows the backward statistics take the 48-register form of colreduce_partial_kernel
 // (0 = never).  Read per call (A/B in one process).  Same row blocks and the same partial layout, but NOT the same
 // summation order inside a block: the lean kernel has 256 / (c / 2) row lanes where the wide one has 256 / (c / 4), so the
@@ -1047,10 +955,6 @@ static int64_t bn_lean_rows() {
   return e ? (int64_t)atoll(e) : (int64_t)65536;
 }
 
-static bool bn_apply_buf_ok(int64_t n, int64_t a, int64_t b, int64_t c_, int64_t d, int64_t e) {  // every tensor of n rows < 2 GiB
-  const int64_t ld = std::max(std::max(std::max(a, b), std::max(c_, d)), e);
-  return n * ld * 4 <= 0x7FFFFF00ll;
-}
 static bool bn_lean_eligible(int64_t n, int c, int64_t x_ld, int64_t dy_ld, int64_t y_ld) {
   const int64_t lean = bn_lean_rows();
   const int64_t ld = std::max(std::max(x_ld, dy_ld), y_ld);
@@ -1104,21 +1008,12 @@ static int bn_small_forward(const float* x, int64_t x_ld, int64_t n, int64_t spl
   return PCMI_OK;
 }
 
-static int bn_small_backward(const BnSmallBwd& a, int c, hipStream_t st, bool parallel_segments = false) {
-  const bool two = a.split < a.n;
-  const int64_t longest = two ? std::max(a.split, a.n - a.split) : a.n;
-  const dim3 grid((unsigned)(c / (4 * kSmallCG)), (two && parallel_segments) ? 2u : 1u);
+static int bn_small_backward(const BnSmallBwd& a, int c, hipStream_t st) {
+  const int64_t longest = a.split < a.n ? std::max(a.split, a.n - a.split) : a.n;
+  const dim3 grid((unsigned)(c / (4 * kSmallCG)));
   PCMI_BN_SMALL_DISPATCH(bn_small_bwd_kernel, a, grid, longest, st);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
-}
-
-static bool fuse_final_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("PCMI_BN_FUSED_FINAL");
-    return e && e[0] == '1';
-  }();
-  return on;
 }
 
 static int check_rows(const char* who, const void* p, int64_t ld, int c) {
@@ -1138,7 +1033,7 @@ static int check_rows(const char* who, const void* p, int64_t ld, int c) {
   } while (0)
 #define PCMI_BN_BWD_APPLY_CASE(M, D, GRID, ST, ...) \
   case (M) * 3 + (D): bn_bwd_apply_kernel<M, D><<<(GRID), 256, 0, (ST)>>>(__VA_ARGS__); break
-#define PCMI_BN_BWD_APPLY_LAUNCH(GRID, ST, MASK, DRESMODE, BUF, ...)                     \
+#define PCMI_BN_BWD_APPLY_LAUNCH(GRID, ST, MASK, DRESMODE, ...)                          \
   switch ((MASK) * 3 + (DRESMODE)) {                                                      \
     PCMI_BN_BWD_APPLY_CASE(0, 0, GRID, ST, __VA_ARGS__);                                  \
     PCMI_BN_BWD_APPLY_CASE(0, 1, GRID, ST, __VA_ARGS__);                                  \
@@ -1203,7 +1098,7 @@ int bn_forward_train(const float* x, int64_t x_ld, int64_t n, int c, const float
   float* part = (float*)ws;
   RedFinal fin;
   memset(&fin, 0, sizeof(fin));
-  const bool small = g.nblocks <= kFuseFinalBlocks, fuse = small && fuse_final_enabled();
+  const bool small = g.nblocks <= kFinalMergeBlocks;
   fin.eps = eps;
   fin.momentum = momentum;
   fin.running_mean = running_mean;
@@ -1212,14 +1107,10 @@ int bn_forward_train(const float* x, int64_t x_ld, int64_t n, int c, const float
   fin.save_invstd = save_invstd;
   fin.save_unbiased = save_unbiased;
   if (bn_small_eligible(n, c)) return bn_small_forward(x, x_ld, n, n, c, gamma, beta, residual, res_ld, relu, y, y_ld, fin, st, relu_bits);
-  if (fuse) {  // statistics + their final merge in ONE launch (last-arriving workgroup), then the apply pass
-    fin.counter = stream_counters(st, 1);
-    if (!fin.counter) return PCMI_ERR_HIP;
-  }
   colreduce_partial_kernel<0><<<g.nblocks, 256, 0, st>>>(x, x_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, n, g.c4, g.rp,
-                                                        g.rows_per_block, part, fin);
+                                                        g.rows_per_block, part);
   PCMI_LAUNCH_CHECK();
-  if (small && !fuse) {
+  if (small) {
     colreduce_final_kernel<0><<<(unsigned)ceil_div(g.c4, kFinalCols), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, 0, 0);
     PCMI_LAUNCH_CHECK();
   }
@@ -1235,8 +1126,8 @@ int bn_forward_train(const float* x, int64_t x_ld, int64_t n, int c, const float
   return PCMI_OK;
 }
 
-// Two-segment BatchNorm forward (rows [0, split) and [split, n): own statistics each) in two launches: statistics of
-// both segments (gridDim.y = 2, fused final), then one apply pass.  save_*: [2][3c] blocks (mean, invstd, unbiased)
+// Two-segment BatchNorm forward (rows [0, split) and [split, n): own statistics each) in three launches: statistics of
+// both segments (gridDim.y = 2), their merge, then one apply pass.  save_*: [2][3c] blocks (mean, invstd, unbiased)
 // `stat_stride` floats apart; the running estimates are the caller's business (BnRunningUpdate with mean2).
 int bn_forward_train2(const float* x, int64_t x_ld, int64_t n, int64_t split, int c, const float* gamma, const float* beta,
                       float eps, const float* residual, int64_t res_ld, int relu, float* y, int64_t y_ld, float* save_mean,
@@ -1253,40 +1144,27 @@ int bn_forward_train2(const float* x, int64_t x_ld, int64_t n, int64_t split, in
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(n, c), PCMI_ERR_WORKSPACE, "bn_fwd_train2: workspace too small");
   const int64_t longest = std::max(split, n - split);
   RedGeom g = red_geom(longest, c);
-  if (g.nblocks > kFuseFinalBlocks) {  // at most kFuseFinalBlocks row blocks per segment: the final merge stays fused
-    g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFuseFinalBlocks), g.rp) * g.rp);
+  if (g.nblocks > kFinalMergeBlocks) {  // at most kFinalMergeBlocks row blocks per segment: colreduce_final_kernel merges them
+    g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFinalMergeBlocks), g.rp) * g.rp);
     g.nblocks = (int)ceil_div(longest, g.rows_per_block);
   }
   float* part = (float*)ws;
   RedFinal fin;
   memset(&fin, 0, sizeof(fin));
-  const bool fuse = fuse_final_enabled();
-  if (fuse) {
-    fin.counter = stream_counters(st, 2);
-    if (!fin.counter) return PCMI_ERR_HIP;
-  }
   fin.eps = eps;
   fin.save_mean = save_mean;
   fin.save_invstd = save_invstd;
   fin.save_unbiased = save_unbiased;
   fin.out_seg_stride = stat_stride;
-  if (bn_small_eligible(longest, c)) {
-    fin.counter = nullptr;
+  if (bn_small_eligible(longest, c))
     return bn_small_forward(x, x_ld, n, split, c, gamma, beta, residual, res_ld, relu, y, y_ld, fin, st, relu_bits);
-  }
   const int64_t part_seg = (int64_t)g.nblocks * 2 * c;
-#if defined(PCMI_BN_DIAG_SKIP_SMALL_STATS)  // timing diagnostic (wrong results): as if the producer had left the partials behind
-  if (longest >= PCMI_BN_DIAG_SKIP_SMALL_STATS)
-#endif
   colreduce_partial_kernel<0><<<dim3((unsigned)g.nblocks, 2), 256, 0, st>>>(x, x_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, n,
-                                                                           g.c4, g.rp, g.rows_per_block, part, fin, split, 0,
-                                                                           part_seg);
+                                                                           g.c4, g.rp, g.rows_per_block, part, split, 0, part_seg);
   PCMI_LAUNCH_CHECK();
-  if (!fuse) {
-    colreduce_final_kernel<0><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), 2), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, split,
-                                                                                              part_seg);
-    PCMI_LAUNCH_CHECK();
-  }
+  colreduce_final_kernel<0><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), 2), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, split,
+                                                                                            part_seg);
+  PCMI_LAUNCH_CHECK();
   PCMI_BN_APPLY_LAUNCH(stream_grid(n * g.c4), st, residual, relu_bits, x, x_ld, n, g.c4, gamma, beta, save_mean, save_invstd, eps, 0,
                        residual, res_ld, relu, y, y_ld, split, stat_stride / 4, relu_bits);
   PCMI_LAUNCH_CHECK();
@@ -1298,7 +1176,7 @@ int bn_forward_train2(const float* x, int64_t x_ld, int64_t n, int64_t split, in
 int bn_backward2(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y, int64_t y_ld, int64_t n,
                  int64_t split, int c, const float* gamma, const float* save_mean, const float* save_invstd, int stat_stride,
                  float* dx, int64_t dx_ld, float* dres, int64_t dres_ld, int dres_accumulate, float* sums, float* acc_dgamma,
-                 float* acc_dbeta, void* ws, size_t ws_bytes, hipStream_t st, int* deferred_acc, const uint32_t* relu_bits) {
+                 float* acc_dbeta, void* ws, size_t ws_bytes, hipStream_t st, const uint32_t* relu_bits) {
   if (c % 32 != 0) relu_bits = nullptr;
   if (relu_bits) relu_mask_y = nullptr;  // the pattern comes from the bits: y is not read
   const int bits_ld = c / 32;
@@ -1315,43 +1193,30 @@ int bn_backward2(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, c
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(n, c), PCMI_ERR_WORKSPACE, "bn_bwd2: workspace too small");
   const int64_t longest = std::max(split, n - split);
   RedGeom g = red_geom(longest, c);
-  if (g.nblocks > kFuseFinalBlocks) {
-    g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFuseFinalBlocks), g.rp) * g.rp);
+  if (g.nblocks > kFinalMergeBlocks) {
+    g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFinalMergeBlocks), g.rp) * g.rp);
     g.nblocks = (int)ceil_div(longest, g.rows_per_block);
   }
   float* part = (float*)ws;
   RedFinal fin;
   memset(&fin, 0, sizeof(fin));
-  // deferred_acc (nullable): the caller can add the two segments' sums to the parameter gradients itself
-  // (bn_param_accumulate, on any stream ordered behind this call) -- then the segments run side by side, and the one-launch
-  // form pays up to the forward threshold; else one workgroup walks them in order and accumulates.
-  if (deferred_acc) *deferred_acc = 0;
-  if (bn_small_eligible(longest, c, deferred_acc == nullptr)) {
+  if (bn_small_eligible(longest, c, true)) {  // (one workgroup walks the two segments in order and accumulates)
     BnSmallBwd a;
     a.dy = dy; a.dy_ld = dy_ld; a.x = x; a.x_ld = x_ld; a.ymask = relu_mask_y; a.y_ld = y_ld; a.n = n; a.split = split;
     a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd; a.stat_stride = stat_stride;
     a.dx = dx; a.dx_ld = dx_ld; a.dres = dres; a.dres_ld = dres_ld; a.dres_accumulate = dres_accumulate;
     a.sum_g = sums; a.sum_gx = sums + c; a.sum_stride = 2 * c;
-    a.acc_g = deferred_acc ? nullptr : acc_dbeta;
-    a.acc_gx = deferred_acc ? nullptr : acc_dgamma;
+    a.acc_g = acc_dbeta;
+    a.acc_gx = acc_dgamma;
     a.bits = reinterpret_cast<const uint16_t*>(relu_bits);
-    if (deferred_acc) *deferred_acc = 1;
-    return bn_small_backward(a, c, st, deferred_acc != nullptr);
+    return bn_small_backward(a, c, st);
   }
   // (the 48-register kernel finds a row's bit words through x's own offsets: with the bits it needs x_ld == c)
   const bool lean = bn_lean_eligible(n, c, x_ld, dy_ld, relu_mask_y ? y_ld : 0) && (!relu_bits || x_ld == c);
-  const bool fuse = fuse_final_enabled() && !lean;  // (the lean statistics kernel never merges: it has no registers for it)
-  if (fuse) {
-    fin.counter = stream_counters(st, 2);
-    if (!fin.counter) return PCMI_ERR_HIP;
-  }
   fin.out_a = sums;      // dbeta of a segment
   fin.out_b = sums + c;  // dgamma
   fin.out_seg_stride = 2 * c;
   const int64_t part_seg = (int64_t)g.nblocks * 2 * c;
-#if defined(PCMI_BN_DIAG_SKIP_SMALL_STATS_BWD)
-  if (longest >= PCMI_BN_DIAG_SKIP_SMALL_STATS_BWD)
-#endif
   if (lean && relu_bits)
     bn_bwd_stats_lean_kernel<2><<<dim3((unsigned)g.nblocks, 2), 256, 0, st>>>(x, x_ld, dy, dy_ld, reinterpret_cast<const float*>(relu_bits),
                                                                              bits_ld, save_mean, save_invstd, n, c, g.rows_per_block, part,
@@ -1366,26 +1231,15 @@ int bn_backward2(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, c
                                                                              part_seg);
   else
     PCMI_BN_BWD_PARTIAL_LAUNCH(dim3((unsigned)g.nblocks, 2), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), x, x_ld, dy, dy_ld, relu_mask_y,
-                               y_ld, save_mean, save_invstd, n, g.c4, g.rp, g.rows_per_block, part, fin, split, stat_stride, part_seg,
+                               y_ld, save_mean, save_invstd, n, g.c4, g.rp, g.rows_per_block, part, split, stat_stride, part_seg,
                                relu_bits);
   PCMI_LAUNCH_CHECK();
-  if (!fuse) {
-    colreduce_final_kernel<1><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), 2), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, split,
-                                                                                              part_seg);
-    PCMI_LAUNCH_CHECK();
-  }
-  PCMI_BN_BWD_APPLY_LAUNCH(stream_grid(n * g.c4), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), dres ? (dres_accumulate ? 2 : 1) : 0,
-                           bn_apply_buf_ok(n, dy_ld, x_ld, relu_mask_y ? y_ld : 0, dx_ld, dres ? dres_ld : 0), dy, dy_ld, x, x_ld,
-                           relu_mask_y, y_ld, n, g.c4, gamma, save_mean, save_invstd, sums, sums + c, dx, dx_ld, dres, dres_ld,
-                           dres_accumulate, split, stat_stride / 4, 2 * c / 4, acc_dbeta, acc_dgamma, relu_bits);
+  colreduce_final_kernel<1><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), 2), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, split,
+                                                                                            part_seg);
   PCMI_LAUNCH_CHECK();
-  return PCMI_OK;
-}
-
-// (acc_dbeta, acc_dgamma) += the sums bn_backward2 left in `sums` ([2][2c]: dbeta, dgamma per segment) with *deferred_acc == 1
-int bn_param_accumulate(const float* sums, int c, float* acc_dgamma, float* acc_dbeta, hipStream_t st) {
-  PCMI_REQUIRE(sums && acc_dgamma && acc_dbeta && c % 4 == 0, PCMI_ERR_INVALID, "bn_param_accumulate: bad argument");
-  bn_param_acc_kernel<<<(unsigned)ceil_div(c / 4, 64), 64, 0, st>>>(acc_dbeta, acc_dgamma, sums, sums + c, 2 * c, c / 4, 2);
+  PCMI_BN_BWD_APPLY_LAUNCH(stream_grid(n * g.c4), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), dres ? (dres_accumulate ? 2 : 1) : 0,
+                           dy, dy_ld, x, x_ld, relu_mask_y, y_ld, n, g.c4, gamma, save_mean, save_invstd, sums, sums + c, dx, dx_ld, dres, dres_ld,
+                           dres_accumulate, split, stat_stride / 4, 2 * c / 4, acc_dbeta, acc_dgamma, relu_bits);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
@@ -1467,15 +1321,11 @@ int bn_backward(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, co
   }
   // (the 48-register kernel finds a row's bit words through x's own offsets: with the bits it needs x_ld == c)
   const bool lean = bn_lean_eligible(n, c, x_ld, dy_ld, relu_mask_y ? y_ld : 0) && (!relu_bits || x_ld == c);
-  const bool small = g.nblocks <= kFuseFinalBlocks, fuse = small && fuse_final_enabled() && !lean;
+  const bool small = g.nblocks <= kFinalMergeBlocks;
   fin.out_a = dbeta;
   fin.out_b = dgamma;
   fin.acc_a = acc_dbeta;
   fin.acc_b = acc_dgamma;
-  if (fuse) {
-    fin.counter = stream_counters(st, 1);
-    if (!fin.counter) return PCMI_ERR_HIP;
-  }
   if (lean && relu_bits)
     bn_bwd_stats_lean_kernel<2><<<g.nblocks, 256, 0, st>>>(x, x_ld, dy, dy_ld, reinterpret_cast<const float*>(relu_bits), bits_ld,
                                                           save_mean, save_invstd, n, c, g.rows_per_block, part, 0, 0, 0);
@@ -1487,9 +1337,9 @@ int bn_backward(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, co
                                                           g.rows_per_block, part, 0, 0, 0);
   else
     PCMI_BN_BWD_PARTIAL_LAUNCH(g.nblocks, st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), x, x_ld, dy, dy_ld, relu_mask_y, y_ld, save_mean,
-                               save_invstd, n, g.c4, g.rp, g.rows_per_block, part, fin, (int64_t)0, 0, (int64_t)0, relu_bits);
+                               save_invstd, n, g.c4, g.rp, g.rows_per_block, part, (int64_t)0, 0, (int64_t)0, relu_bits);
   PCMI_LAUNCH_CHECK();
-  if (small && !fuse) {
+  if (small) {
     colreduce_final_kernel<1><<<(unsigned)ceil_div(g.c4, kFinalCols), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, 0, 0);
     PCMI_LAUNCH_CHECK();
   }
@@ -1498,8 +1348,7 @@ int bn_backward(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, co
     PCMI_LAUNCH_CHECK();
   }
   PCMI_BN_BWD_APPLY_LAUNCH(stream_grid(n * g.c4), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), dres ? (dres_accumulate ? 2 : 1) : 0,
-                           bn_apply_buf_ok(n, dy_ld, x_ld, relu_mask_y ? y_ld : 0, dx_ld, dres ? dres_ld : 0), dy, dy_ld, x, x_ld,
-                           relu_mask_y, y_ld, n, g.c4, gamma, save_mean, save_invstd, dbeta, dgamma, dx, dx_ld, dres, dres_ld,
+                           dy, dy_ld, x, x_ld, relu_mask_y, y_ld, n, g.c4, gamma, save_mean, save_invstd, dbeta, dgamma, dx, dx_ld, dres, dres_ld,
                            dres_accumulate, INT64_MAX, 0, 0, (float*)nullptr, (float*)nullptr, relu_bits);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;

@@ -341,12 +341,8 @@ __global__ __launch_bounds__(256, KC > 32 ? 2 : 3) void spconv_mfma_kernel(ConvA
 // per step) serves both row groups.  LDB = NS + 4 keeps those reads bank-conflict free (4 LDB = 16 mod 32).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // waves per SIMD the 16-row kernel is compiled for: 4 for NT <= 3 (128 VGPRs, 2-5 dwords of scratch outside the
-// MFMA loop) -- measured 3-5 % faster than 3 waves on the level-1 / level-2 convs (scripts/kbench.py); build with
-// -DPCMI_CONV16_W4=0 (PCMI_EXTRA_HIPCC_FLAGS) for the 3-wave form
-#ifndef PCMI_CONV16_W4
-#define PCMI_CONV16_W4 1
-#endif
-__host__ __device__ constexpr int kConv16Waves(int nt) { return (PCMI_CONV16_W4 && nt <= 3) ? 4 : 3; }
+// MFMA loop) -- measured 3-5 % faster than 3 waves on the level-1 / level-2 convs (scripts/kbench.py)
+__host__ __device__ constexpr int kConv16Waves(int nt) { return nt <= 3 ? 4 : 3; }
 
 // ---- the kernel (software-pipelined; round 2's unpipelined form -- same operands, bit-identical results -- is gone) ----
 // Per-wave cycle accounting of the unpipelined form (profiles/r02_stall_attribution.txt): a wave spent
@@ -835,43 +831,50 @@ static int launch_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
 
 constexpr int kStreamKDefaultMinTiles = 256;  // unit-balanced launch from 256 tiles (32768 rows); PCMI_SPCONV_STREAMK=0 turns it off
 
-// PCMI_SPCONV_STREAMK: minimum number of 128-row tiles for the unit-balanced launch (0 = never).
-static int64_t sk_min_tiles() {  // read per call: the parity test compares both launches in one process
+// The switches of the convolution plans, read from the environment once per convolution call and per workspace query
+// (not once per process: the parity tests compare both settings in one process) and handed to everything that plans.
+//   PCMI_SPCONV_STREAMK  minimum number of 128-row tiles for the unit-balanced launch (0 = never)
+//   PCMI_CONV16          the 16-row kernels take the 128-row tiles of levels with at least this many rows (0 = never,
+//                        1 = always).  Default 512 since round 3: with the weights of every layer packed for its level's
+//                        slice width ahead of the launches (x3_plan_nt), the split-precision kernel also wins on the
+//                        coarse levels -- 240 -> 247 pairs/s at 2048, 249 at 512 (profiles/r03e_bench_ab_*.txt); round
+//                        2's 8192 was measured with the fp32 form, which lost below it.
+//   PCMI_CONV16_X3       the split-precision form (spconv_x3.hip: fp32 operands as three bf16 terms on the bf16 matrix
+//                        cores) takes the matrix-bound launches of the 16-row kernel (>= 64 channels on both sides);
+//                        0: the fp32-MFMA kernel
+struct ConvEnv {
+  int64_t sk_min_tiles, conv16_min_rows;
+  bool x3_on;
+};
+static ConvEnv conv_env() {
+  ConvEnv env;
   const char* e = getenv("PCMI_SPCONV_STREAMK");
-  return e ? (int64_t)atoll(e) : (int64_t)kStreamKDefaultMinTiles;
+  env.sk_min_tiles = e ? (int64_t)atoll(e) : (int64_t)kStreamKDefaultMinTiles;
+  e = getenv("PCMI_CONV16");
+  env.conv16_min_rows = e ? atoll(e) : 512;
+  e = getenv("PCMI_CONV16_X3");
+  env.x3_on = !e || atoi(e) != 0;
+  return env;
 }
+
 // resident workgroups of the unit-balanced launch (3 or 4 waves per SIMD, see kConv16Waves), multiple of 8
 static int sk_workgroups(int NT = 4) { return kConv16Waves(NT) * num_cu() / 8 * 8; }
 static int sk_workgroups_max() { return 4 * num_cu() / 8 * 8; }
-static bool sk_rows_eligible(int64_t rows, int K) {
-  const int64_t mt = sk_min_tiles();
+static bool sk_rows_eligible(const ConvEnv& env, int64_t rows, int K) {
+  const int64_t mt = env.sk_min_tiles;
   return K > 1 && mt > 0 && rows >= 4096 /* kSortRowsMin: such maps carry tile units */ && ceil_div(rows, 128) >= mt;
 }
-static size_t sk_partial_bytes(int64_t rows, int N, int K) {
-  return sk_rows_eligible(rows, K) ? (size_t)sk_workgroups_max() * 2 * 128 * N * sizeof(float) : 0;
+static size_t sk_partial_bytes(const ConvEnv& env, int64_t rows, int N, int K) {
+  return sk_rows_eligible(env, rows, K) ? (size_t)sk_workgroups_max() * 2 * 128 * N * sizeof(float) : 0;
 }
 
-// The 16-row kernels take the 128-row tiles of levels with at least PCMI_CONV16 rows (0 = never, 1 = always).  Default
-// 512 since round 3: with the weights of every layer packed for its level's slice width ahead of the launches
-// (x3_plan_nt), the split-precision kernel also wins on the coarse levels -- 240 -> 247 pairs/s at 2048, 249 at 512
-// (profiles/r03e_bench_ab_*.txt); round 2's 8192 was measured with the fp32 form, which lost below it.
-static int64_t conv16_min_rows() {
-  const char* e = getenv("PCMI_CONV16");
-  return e ? atoll(e) : 512;
-}
-static bool conv16_enabled(int64_t n_rows, int64_t x_bytes) {
-  const int64_t min_rows = conv16_min_rows();
+static bool conv16_enabled(const ConvEnv& env, int64_t n_rows, int64_t x_bytes) {
+  const int64_t min_rows = env.conv16_min_rows;
   // the pipelined form addresses the gathered operand with 32-bit byte offsets (absent = 2^31)
   return min_rows > 0 && n_rows >= min_rows && x_bytes <= 0x7FFFFF00ll;
 }
 
-// The split-precision form (spconv_x3.hip: fp32 operands as three bf16 terms on the bf16 matrix cores) takes the
-// matrix-bound launches of the 16-row kernel (>= 64 channels on both sides); PCMI_CONV16_X3=0: the fp32-MFMA kernel.
-static bool conv16_x3_on() {
-  const char* e = getenv("PCMI_CONV16_X3");
-  return !e || atoi(e) != 0;
-}
-static bool conv16_x3(int NT, int C, int N) { return conv16_x3_on() && NT >= 2 && NT <= 4 && C >= 64 && N >= 64; }
+static bool conv16_x3(const ConvEnv& env, int NT, int C, int N) { return env.x3_on && NT >= 2 && NT <= 4 && C >= 64 && N >= 64; }
 
 // The calling thread's conv precision mode (include/pcmi.h: pcmi_set_conv_precision).  It decides only the term count of
 // the split-precision launches below (x3_launch) and in spconv_wgrad_x3.hip; every plan -- which kernel, slice width,
@@ -945,7 +948,7 @@ constexpr int kMaxKSplit = 27;
 // wide: the contraction has >= 64 channels (with N >= 64 the launch can take the split-precision kernel, whose slices
 // are at least 64 wide)
 // C: the contraction size when the caller knows it (0: the round-2 rule alone)
-static Plan make_plan(int64_t rows, int N, int K, bool pair, bool wide = false, int C = 0) {
+static Plan make_plan(const ConvEnv& env, int64_t rows, int N, int K, bool pair, bool wide = false, int C = 0) {
   Plan p;
   const int nt_all = N / 32;
   p.NT = nt_all % 4 == 0 ? 4 : (nt_all % 3 == 0 ? 3 : (nt_all % 2 == 0 ? 2 : 1));
@@ -954,9 +957,9 @@ static Plan make_plan(int64_t rows, int N, int K, bool pair, bool wide = false, 
   if (p.RW == 1 && p.NT > 2) p.NT = (nt_all % 2 == 0) ? 2 : 1;  // the cross-wave reduction lives in LDS
   // small levels: narrow output slices partition the weights (no extra weight traffic) and multiply the
   // number of resident workgroups; the re-gathered rows are L2-resident at these sizes
-  const int64_t min16 = conv16_min_rows();
+  const int64_t min16 = env.conv16_min_rows;
   if (rows < 2048)
-    p.NT = (wide && !pair && K > 1 && N >= 64 && nt_all % 2 == 0 && conv16_x3_on() && min16 > 0 && rows >= min16 && p.RW == 4) ? 2 : 1;
+    p.NT = (wide && !pair && K > 1 && N >= 64 && nt_all % 2 == 0 && env.x3_on && min16 > 0 && rows >= min16 && p.RW == 4) ? 2 : 1;
   else if (rows < 8192 && p.NT > 2)
     p.NT = (nt_all % 2 == 0) ? 2 : 1;
   if (!pair && K > 1) {
@@ -976,10 +979,7 @@ static Plan make_plan(int64_t rows, int N, int K, bool pair, bool wide = false, 
     // when it beats the rule above by 10 % of its own estimate, and only under 16384 rows: on the stride-2 level it picks
     // ksplit 2, which measured equal in the forward pass and 20 % SLOWER in the backward pass, beside the weight-gradient
     // stream (profiles/r06d_*: 632 workgroups of 42 steps leave nothing for the other stream to slip into).
-    // PCMI_KSPLIT_RULE=0: the rule above alone (read per call).
-    const char* re = getenv("PCMI_KSPLIT_RULE");
-    if (C >= 64 && wide && p.RW == 4 && wgs < target && rows < 16384 && !(re && re[0] == '0') && conv16_x3(p.NT, C, N) && min16 > 0 &&
-        rows >= min16) {
+    if (C >= 64 && wide && p.RW == 4 && wgs < target && rows < 16384 && conv16_x3(env, p.NT, C, N) && min16 > 0 && rows >= min16) {
       const double slots = (double)x3_workgroups(p.NT, 3), nch = (double)(C / kKC);  // (the fp32 mode's plan in both modes)
       const double traffic = (double)rows * N * 8.0 / 3.0e6 / 2.0;  // chunk steps per partial tensor
       auto cost = [&](int ks) {
@@ -998,21 +998,22 @@ static Plan make_plan(int64_t rows, int N, int K, bool pair, bool wide = false, 
   return p;
 }
 
-static size_t partial_bytes(int64_t rows, int N, int K) {
+static size_t partial_bytes(const ConvEnv& env, int64_t rows, int N, int K) {
   if (K <= 1 || rows <= 0 || N % 32 != 0) return 0;
-  int ks = std::max(make_plan(rows, N, K, false, false).ksplit, make_plan(rows, N, K, false, true).ksplit);
-  for (int C = 64; C <= 512; C += 32) ks = std::max(ks, make_plan(rows, N, K, false, true, C).ksplit);  // (any contraction size)
+  int ks = std::max(make_plan(env, rows, N, K, false, false).ksplit, make_plan(env, rows, N, K, false, true).ksplit);
+  for (int C = 64; C <= 512; C += 32) ks = std::max(ks, make_plan(env, rows, N, K, false, true, C).ksplit);  // (any contraction size)
   return ks > 1 ? (size_t)ks * rows * N * sizeof(float) : 0;
 }
 
 // Output slice width (units of 32 channels) of the table launch over `rows` output rows if it takes the split-precision
 // kernel, else 0: what the executor packs the weights for ahead of the launches (engine.hip: x3_prepack).
 int x3_plan_nt(int64_t rows, int C, int N, int K) {
-  if (C % 32 != 0 || N % 32 != 0 || C < 64 || N < 64 || K <= 1 || !conv16_x3_on()) return 0;
-  const Plan p = make_plan(rows, N, K, false, true);
-  const int64_t min16 = conv16_min_rows();
+  const ConvEnv env = conv_env();
+  if (C % 32 != 0 || N % 32 != 0 || C < 64 || N < 64 || K <= 1 || !env.x3_on) return 0;
+  const Plan p = make_plan(env, rows, N, K, false, true);
+  const int64_t min16 = env.conv16_min_rows;
   if (p.RW != 4 || min16 <= 0 || rows < min16) return 0;
-  return conv16_x3(p.NT, C, N) ? p.NT : 0;
+  return conv16_x3(env, p.NT, C, N) ? p.NT : 0;
 }
 
 // One gathered GEMM:  out[rows, N] = sum_k x[idx_k(rows)] @ B_k
@@ -1026,6 +1027,7 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
   PCMI_REQUIRE(x_ld % 4 == 0 && out_ld >= N && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0),
                PCMI_ERR_INVALID, "spconv: operands must be 16-byte aligned with ld %% 4 == 0");
   if (n_rows == 0) return PCMI_OK;
+  const ConvEnv env = conv_env();
   ConvArgs a;
   a.x = x;
   a.x_ld = x_ld;
@@ -1063,7 +1065,7 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
     a.pair_src = swap_pairs ? map->pair_in : map->pair_out;
     a.pair_dst = swap_pairs ? map->pair_out : map->pair_in;
     a.offs = map->offs;
-    Plan p = make_plan(n_rows, N, a.K, true);
+    Plan p = make_plan(env, n_rows, N, a.K, true);
     const int TM = 32 * p.RW;
     // tiles of all offsets: exact when the map's counts are on the host, else their bound (every pair is one fine row
     // and every offset adds at most one ragged tile); a workgroup past the last tile leaves at once
@@ -1084,19 +1086,19 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
   }
   // 32 -> 32 channels: all weight slices resident in LDS, a wave per 16-row group (spconv32r.hip)
   if (conv32r_eligible(a, x_rows * x_ld * 4)) return conv32r_launch(w_transposed, a, st);
-  Plan p = make_plan(n_rows, N, a.K, false, C >= 64, C);
+  Plan p = make_plan(env, n_rows, N, a.K, false, C >= 64, C);
   // (32-channel convs are HBM/latency-bound: the partial tiles cost them more than the balance gains -- measured)
   // (the unit-balanced launch exists for the 16-row kernels: an operand of >= 2 GiB, which they cannot address, takes the
   //  whole-tile launch of spconv_mfma_kernel below)
   // (Round 6 measured this launch also on the levels that split their offsets over blockIdx.z -- ksplit > 1: the stride-2 level
   //  of the bench batch, 316 tiles, neutral; the stride-4 level as well, 78 tiles cut into 3-10 pieces each, 0.5 ms per step
   //  SLOWER: profiles/r06a_wgrad_stream_cost_and_sk_mid_ab.txt.  The offset split + split_reduce_kernel stays there.)
-  if (map && map->tile_pref && map->perm && p.RW == 4 && p.ksplit == 1 && sk_rows_eligible(n_rows, a.K) &&
-      map->n_tiles == ceil_div(n_rows, 128) && C >= 64 && N >= 64 && conv16_enabled(n_rows, x_rows * x_ld * 4)) {
-    const bool x3 = conv16_x3(p.NT, C, N);
+  if (map && map->tile_pref && map->perm && p.RW == 4 && p.ksplit == 1 && sk_rows_eligible(env, n_rows, a.K) &&
+      map->n_tiles == ceil_div(n_rows, 128) && C >= 64 && N >= 64 && conv16_enabled(env, n_rows, x_rows * x_ld * 4)) {
+    const bool x3 = conv16_x3(env, p.NT, C, N);
     const int terms = conv_terms();
     const int G = x3 ? x3_workgroups(p.NT, terms) : sk_workgroups(p.NT);  // (<= sk_workgroups_max: the partial tiles fit)
-    const size_t part = sk_partial_bytes(n_rows, N, a.K);
+    const size_t part = sk_partial_bytes(env, n_rows, N, a.K);
     const size_t need = part + (x3 ? x3_pack_bytes(a.K, C, N) : 0);
     PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "spconv: workspace %zu < %zu bytes", ws_bytes, need);
     a.sk_mask = map->tile_mask;
@@ -1122,7 +1124,7 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
     PCMI_LAUNCH_CHECK();
     return PCMI_OK;
   }
-  const bool x3 = p.RW == 4 && map && conv16_enabled(n_rows, x_rows * x_ld * 4) && conv16_x3(p.NT, C, N);
+  const bool x3 = p.RW == 4 && map && conv16_enabled(env, n_rows, x_rows * x_ld * 4) && conv16_x3(env, p.NT, C, N);
   const int terms = conv_terms();
   const size_t split_bytes = p.ksplit > 1 ? align_up((size_t)p.ksplit * n_rows * N * sizeof(float), 256) : 0;
   if (x3) {
@@ -1154,7 +1156,7 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
   int rc;
   if (x3) {
     rc = x3_launch(p.NT, false, a, grid, st, terms);
-  } else if (p.RW == 4 && conv16_enabled(n_rows, x_rows * x_ld * 4)) {
+  } else if (p.RW == 4 && conv16_enabled(env, n_rows, x_rows * x_ld * 4)) {
     rc = w_transposed ? launch16<true, false>(p.NT, a, grid, st) : launch16<false, false>(p.NT, a, grid, st);
   } else if (p.RW == 4 && (w_transposed ? launch_deep<true>(p.NT, a, grid, st) : launch_deep<false>(p.NT, a, grid, st))) {
     rc = PCMI_OK;
@@ -1172,8 +1174,9 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
 }
 
 size_t spconv_fwd_bwd_workspace(int64_t n_in, int64_t n_out, int cin, int cout, int K) {
-  const size_t ks = std::max(partial_bytes(n_out, cout, K), partial_bytes(n_in, cin, K));
-  const size_t sk = n_in == n_out ? std::max(sk_partial_bytes(n_out, cout, K), sk_partial_bytes(n_in, cin, K)) : 0;
+  const ConvEnv env = conv_env();
+  const size_t ks = std::max(partial_bytes(env, n_out, cout, K), partial_bytes(env, n_in, cin, K));
+  const size_t sk = n_in == n_out ? std::max(sk_partial_bytes(env, n_out, cout, K), sk_partial_bytes(env, n_in, cin, K)) : 0;
   // the packed weights of the split-precision form sit behind the partial tiles (whether or not it is switched on:
   // <= 10.6 MB for the widest layer)
   const size_t pack = (K > 1 && cin % 32 == 0 && cout % 32 == 0) ? x3_pack_bytes(K, cin, cout) : 0;
@@ -1266,7 +1269,7 @@ int pcmi_spconv_bwd_data(const float* gout, int64_t gout_ld, int64_t n_out, int 
                               ws_bytes, as_stream(stream));
 }
 
-int pcmi_spconv_split_precision(void) { return conv16_x3_on() ? 1 : 0; }
+int pcmi_spconv_split_precision(void) { return conv_env().x3_on ? 1 : 0; }
 
 int pcmi_set_conv_precision(int precision) {
   PCMI_REQUIRE(precision == PCMI_CONV_PRECISION_FP32 || precision == PCMI_CONV_PRECISION_BF16, PCMI_ERR_INVALID,

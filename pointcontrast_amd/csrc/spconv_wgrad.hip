@@ -1040,17 +1040,10 @@ int spconv_backward_weight_m32(const float* in, int64_t in_ld, int64_t n_in, int
   if (!transpose && !gbias && wgrad_x3t_eligible(map, n_in, n_out, cin, cout, in_ld, gout_ld) && in_ld % 4 == 0 &&
       gout_ld % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)gout % 16 == 0)
     return wgrad_x3t_run(in, in_ld, gout, gout_ld, n_out, cin, cout, map, gweight, accumulate, ws, ws_bytes, st);
-  // PCMI_STEM_WGRAD_MFMA=0: the pair-list form of the stem's gradient (A/B); read per call
-  const bool stem_mfma = [] {
-    const char* e = getenv("PCMI_STEM_WGRAD_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  if (stem_mfma && cin == 3 && K == 27 && map && map->nbr && !transpose && map->stride == 1 && n_in == n_out && cout % 32 == 0 &&
-      !gbias) {
+  // the stem's gradient on the matrix cores; the shapes it refuses take the pair-list form (stem_wgrad_kernel, below)
+  if (cin == 3 && K == 27 && map && map->nbr && !transpose && map->stride == 1 && n_in == n_out && cout % 32 == 0 && !gbias) {
     const int64_t n_blocks = ceil_div(n_out, 64);
-    int slabs_max = kStemSlabs;
-    if (const char* e = getenv("PCMI_STEM_SLABS")) slabs_max = std::max(1, std::min(kStemSlabs, atoi(e)));  // (tuning; <= the workspace's 512)
-    const int n_wg = (int)std::min<int64_t>(slabs_max, n_blocks);
+    const int n_wg = (int)std::min<int64_t>(kStemSlabs, n_blocks);
     PCMI_REQUIRE(ws && ws_bytes >= (size_t)n_wg * K * per_k * sizeof(float), PCMI_ERR_WORKSPACE,
                  "spconv_bwd_weight (stem): workspace %zu < %zu bytes", ws_bytes, (size_t)n_wg * K * per_k * sizeof(float));
     stem_wgrad_mfma_kernel<3, 27><<<dim3((unsigned)n_wg, (unsigned)(cout / 32)), 256, 0, st>>>(in, in_ld, gout, gout_ld, map->nbr, n_out,

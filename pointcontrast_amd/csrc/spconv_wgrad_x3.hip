@@ -93,20 +93,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
       const uint32_t col = (uint32_t)(ch0 + 4 * q_s) * 4u;
 #pragma unroll
       for (int e = 0; e < 8; ++e)  // an absent row has an offset >= 2^31: out of range, the load returns zeros
-#if defined(PCMI_X3_DIAG_NO_GATHER)  // timing diagnostic (wrong results): every row out of range = no memory traffic
-        v[e] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, kAbsent + (offs[8 * rg_s + e] & 0u) + col, 0, 0));
-#else
         v[e] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, offs[8 * rg_s + e] + col, 0, 0));
-#endif
 #pragma unroll
       for (int e4 = 0; e4 < 4; ++e4) {
         const v4f x0 = {v[0][e4], v[1][e4], v[2][e4], v[3][e4]}, x1 = {v[4][e4], v[5][e4], v[6][e4], v[7][e4]};
         u32x4 h, m, l;
-#if defined(PCMI_X3_DIAG_NO_SPLIT)  // timing diagnostic (wrong results)
-        h = __builtin_bit_cast(u32x4, x0); m = __builtin_bit_cast(u32x4, x1); l = h;
-#else
         split_terms<TERMS>(x0, x1, h, m, l);
-#endif
         const int cell = rg_s * width + ((4 * q_s + e4) ^ rg_s);
         dst[cell] = h;
         if constexpr (TERMS == 3) {
@@ -168,13 +160,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
             bm = s_g[RG * NB + cell];
             bl = s_g[2 * RG * NB + cell];
           }
-#if defined(PCMI_X3_DIAG_NO_MFMA)  // timing diagnostic (wrong results)
-#define PCMI_WX3_MFMA(AT, BT) asm volatile("" ::"v"(AT[mt]), "v"(BT))
-#else
 #define PCMI_WX3_MFMA(AT, BT)                                                                                              \
   acc[s][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AT[mt]), __builtin_bit_cast(bf16x8, BT), \
                                                            acc[s][mt][nt], 0, 0, 0)
-#endif
           // six products per tile, the small ones first, back to back on the tile's accumulator, tile after tile (round 3
           // alternated the MTW tiles of a term: same sums, same order per accumulator, a little slower -- profiles/r04e_*)
 #pragma unroll
@@ -231,34 +219,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
 //           consumers: multiply slot q if present      all: barrier
 // Same cells, same fragment reads, same six products in the same order per accumulator, same slabs as wgrad_x3t_kernel: the
 // results are bit-identical to it for the same row-block count.
-#if defined(PCMI_X3_DIAG_STAMP)  // timing diagnostic: shader-clock stamps around every per-slot barrier of workgroup 0 (one consumer, one producer wave)
-__device__ unsigned long long g_x3p_stamp[2][2 * 1024];
-#define PCMI_X3P_BARRIER(Q, ROLE)                                                                                  \
-  do {                                                                                                             \
-    const unsigned long long t_in = __builtin_readcyclecounter();                                                  \
-    __syncthreads();                                                                                               \
-    const unsigned long long t_out = __builtin_readcyclecounter();                                                 \
-    if (blockIdx.x == 17 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0 && (wave == 0 || wave == 4) && (Q) < 1024) { \
-      g_x3p_stamp[ROLE][2 * (Q)] = t_in;                                                                           \
-      g_x3p_stamp[ROLE][2 * (Q) + 1] = t_out;                                                                      \
-    }                                                                                                              \
-  } while (0)
-__device__ unsigned long long g_x3p_phase[4];  // producer wave 4 of that workgroup: cycles in (gather issue | X conversion + writes | G / tables | barrier)
-#define PCMI_X3P_PHASE(P)                                          \
-  do {                                                             \
-    __builtin_amdgcn_sched_barrier(0);                             \
-    const unsigned long long t_ph = __builtin_readcyclecounter();  \
-    __builtin_amdgcn_sched_barrier(0);                             \
-    ph_sum[((P) + 3) & 3] += t_ph - ph_last;                       \
-    ph_last = t_ph;                                                \
-  } while (0)
-#elif defined(PCMI_X3_DIAG_NO_BARRIER)  // timing diagnostic (racy)
-#define PCMI_X3P_BARRIER(Q, ROLE) do {} while (0)
-#define PCMI_X3P_PHASE(P) do {} while (0)
-#else
-#define PCMI_X3P_BARRIER(Q, ROLE) __syncthreads()
-#define PCMI_X3P_PHASE(P) do {} while (0)
-#endif
 template <int MTW, int NTW, int KG>
 __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
   static_assert(KG % 2 == 0 && KG >= 2 && KG <= 4, "slot parity = offset parity; one producer wave per offset slot");
@@ -286,9 +246,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
   const uint32_t xld = (uint32_t)(a.x_ld * 4), gld = (uint32_t)(a.g_ld * 4);
 
   if (producer) {
-#if defined(PCMI_X3P_PRIO_P)  // A/B: wave priority of the staging waves
-    __builtin_amdgcn_s_setprio(PCMI_X3P_PRIO_P);
-#endif
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, 0x7FFFFFFF, kRsrcFlags);
     const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.g), 0, 0x7FFFFFFF, kRsrcFlags);
     const int pt = t - 256;
@@ -332,18 +289,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
     const int rg_s = pt & 7, q_s = pt >> 3;
     auto issue = [&](auto& v, const __amdgpu_buffer_rsrc_t& rsrc, const uint32_t* offs, int ch0, auto wtag, auto e0tag, auto e1tag) {
       constexpr int W = decltype(wtag)::value, CPT = W / 32, E0 = decltype(e0tag)::value, E1 = decltype(e1tag)::value;
-#if defined(PCMI_X3_DIAG_NO_GATHER)  // timing diagnostic (wrong results): every row out of range = no memory traffic
-      const uint32_t col = kAbsent;
-#else
       const uint32_t col = (uint32_t)(ch0 + CPT * q_s) * 4u;
-#endif
 #pragma unroll
       for (int e = E0; e < E1; ++e) {  // an absent row has an offset >= 2^31: out of range, the load returns zeros
-#if defined(PCMI_X3_DIAG_NO_GATHER)
-        const uint32_t o = (offs[8 * rg_s + e] & 0xFFFFu) | col;
-#else
         const uint32_t o = offs[8 * rg_s + e] + col;
-#endif
         if constexpr (CPT == 3) {
           const auto t3 = __builtin_amdgcn_raw_buffer_load_b96(rsrc, o, 0, 0);
           static_assert(sizeof(t3) >= 12, "b96");
@@ -361,19 +310,11 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
       for (int ec = EC0; ec < (EC1 < CPT ? EC1 : CPT); ++ec) {
         const v4f x0 = {v[0].f[ec], v[1].f[ec], v[2].f[ec], v[3].f[ec]}, x1 = {v[4].f[ec], v[5].f[ec], v[6].f[ec], v[7].f[ec]};
         u32x4 h, m, l;
-#if defined(PCMI_X3_DIAG_NO_SPLIT)  // timing diagnostic (wrong results)
-        h = __builtin_bit_cast(u32x4, x0); m = __builtin_bit_cast(u32x4, x1); l = h;
-#else
         split3(x0, x1, h, m, l);
-#endif
-#if defined(PCMI_X3_DIAG_NO_LDSW)  // timing diagnostic (wrong results): the packed cells are not written
-        asm volatile("" ::"v"(h), "v"(m), "v"(l));
-#else
         const int cell = rg_s * W + ((CPT * q_s + ec) ^ rg_s);
         dst[cell] = h;
         dst[RG * W + cell] = m;
         dst[2 * RG * W + cell] = l;
-#endif
       }
     };
     struct Row { float f[3]; };  // the (2 or 3) channels of one gathered row
@@ -414,44 +355,30 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
     issue(rgv, gr, s_goff[1], n0, kWG, k0, k8);  // G rows of the second tile (converted in step 1)
     __syncthreads();  // (B1) slot 0 and the G rows of the first tile are staged
 #define PCMI_X3P_SET(j) ((j) == 0 ? r0 : ((j) == 1 ? r1 : ((j) == 2 ? r2 : r3)))
-#if defined(PCMI_X3_DIAG_STAMP)
-    unsigned long long ph_sum[4] = {0, 0, 0, 0}, ph_last = __builtin_readcyclecounter();
-#endif
     for (int tl = 0; tl < nt_tiles; ++tl) {
 #pragma unroll
       for (int sx = 0; sx < KG; ++sx) {
-        PCMI_X3P_PHASE(0);
         if (sx == 0) table_issue(tl + 2);
         {  // rows of slot q + 3 into the register set slot q - 1 has left (converted two steps ago)
           const int s3 = (sx + 3) % KG, tl3 = tl + (sx + 3) / KG;
           issue(PCMI_X3P_SET(s3), xr, s_xoff[tl3 % 3][s3], c0, kWX, k0, k8);
         }
-        PCMI_X3P_PHASE(1);
         // slot q + 1 (requested two steps ago): convert and write into the X buffer the consumers are not reading.
         // (Round 6 measured the order of the two: the 8 requests of a wave take ~780 of a step's 2830 cycles -- four waves'
         //  gathers queue on the CU's one address unit -- and neither the conversion first nor a channel's conversion behind
         //  every few requests hides that: 0.491 / 0.436 against 0.435 ms per level-1 launch, profiles/r06pq_*.)
         finish(s_x[(sx + 1) & 1], PCMI_X3P_SET((sx + 1) % KG), kWX, k0, k8);
-        PCMI_X3P_PHASE(2);
         if (sx == 1) finish(s_g[(tl + 1) & 1], rgv, kWG, k0, k8);
         if (sx == KG - 2) table_commit(tl + 2);  // (first read one step on: a barrier away)
         if (sx == KG - 1) issue(rgv, gr, s_goff[(tl + 2) % 3], n0, kWG, k0, k8);  // (its table: written one step ago)
-        PCMI_X3P_PHASE(3);
-        PCMI_X3P_BARRIER(tl * KG + sx, 1);
+        __syncthreads();
       }
     }
-#if defined(PCMI_X3_DIAG_STAMP)
-    if (blockIdx.x == 17 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0 && wave == 4)
-      for (int e = 0; e < 4; ++e) g_x3p_phase[e] = ph_sum[e];
-#endif
 #undef PCMI_X3P_SET
     return;
   }
 
   // ---- consumers: waves 0-3, 2 x 2 over the [CB x NB] block, MTW x NTW tiles of 16 x 16 each ---------------------------
-#if defined(PCMI_X3P_PRIO_C)  // A/B: wave priority of the multiplying waves
-  __builtin_amdgcn_s_setprio(PCMI_X3P_PRIO_C);
-#endif
   const int i = lane & 15, kk = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
   f32x4 acc[KG][MTW][NTW];
@@ -478,13 +405,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
         u32x4 bh[2], bm[2], bl[2];
         auto read_a = [&](int step) {
           const int rgq = 4 * step + kk;  // the 8 rows this lane quad contracts in this MFMA
-#if defined(PCMI_X3_DIAG_NO_FRAG)  // timing diagnostic (wrong results): no fragment reads from LDS
-          if (step >= 0) {
-#pragma unroll
-            for (int mt = 0; mt < MTW; ++mt) asm volatile("" : "+v"(ah[mt]), "+v"(am[mt]), "+v"(al[mt]));
-            return;
-          }
-#endif
 #pragma unroll
           for (int mt = 0; mt < MTW; ++mt) {
             const int cell = rgq * CB + ((16 * (wm * MTW + mt) + i) ^ rgq);
@@ -495,12 +415,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
         };
         auto read_b = [&](int step, int nt, int slot) {
           const int rgq = 4 * step + kk;
-#if defined(PCMI_X3_DIAG_NO_FRAG)
-          if (step >= 0) {
-            asm volatile("" : "+v"(bh[slot]), "+v"(bm[slot]), "+v"(bl[slot]));
-            return;
-          }
-#endif
           const int cell = rgq * NB + ((16 * (wn * NTW + nt) + i) ^ rgq);
           bh[slot] = sg[cell];
           bm[slot] = sg[RG * NB + cell];
@@ -515,13 +429,9 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
           const int step = it / NTW, nt = it % NTW, slot = it & 1;
           if (it + 1 < STEPS * NTW) read_b((it + 1) / NTW, (it + 1) % NTW, slot ^ 1);
           __builtin_amdgcn_sched_barrier(0);
-#if defined(PCMI_X3_DIAG_NO_MFMA)  // timing diagnostic (wrong results)
-#define PCMI_WX3P_MFMA(AT, BT) asm volatile("" ::"v"(AT[mt]), "v"(BT[slot]))
-#else
 #define PCMI_WX3P_MFMA(AT, BT)                                                                                                      \
   acc[sx][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AT[mt]), __builtin_bit_cast(bf16x8, BT[slot]), \
                                                             acc[sx][mt][nt], 0, 0, 0)
-#endif
 #pragma unroll
           for (int mt = 0; mt < MTW; ++mt) {
             PCMI_WX3P_MFMA(al, bh);
@@ -530,9 +440,6 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
             PCMI_WX3P_MFMA(am, bh);
             PCMI_WX3P_MFMA(ah, bm);
             PCMI_WX3P_MFMA(ah, bh);
-#if defined(PCMI_X3_DIAG_B2B)  // A/B: the six products of an accumulator back to back (the compiler interleaves the three)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
           }
 #undef PCMI_WX3P_MFMA
           __builtin_amdgcn_sched_barrier(0);
@@ -542,7 +449,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
           }
         }
       }
-      PCMI_X3P_BARRIER(tl * KG + sx, 0);
+      __syncthreads();
     }
   }
   // ---- slabs: D[row = 4 kk + r][col = i] of every 16x16 tile; row = input channel, col = output channel ------------
@@ -563,7 +470,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
   }
 }
 
-// Round 6 measured where a slot of wgrad_x3p_kernel goes (shader-clock stamps, -DPCMI_X3_DIAG_STAMP, profiles/r06l_*): at level 1,
+// Round 6 measured where a slot of wgrad_x3p_kernel goes (shader-clock stamps, profiles/r06l_*): at level 1,
 // 96 -> 96, a slot lasts 3400 cycles of which the consumers multiply for 2050 (108 MFMAs = 1836) and WAIT for 1360; the four
 // producer waves need 3300 -- 750 to read the offsets and issue 8 gathers, 1860 to convert 24 elements per lane (132 VALU
 // operations) and write 9 cells, 440 for their share of the G rows and the tables.  The kernel is bound by the producers' VALU
@@ -709,30 +616,6 @@ int wgrad_x3t_run(const float* in, int64_t in_ld, const float* gout, int64_t gou
     default: launch_x3t<2, 2>(a, grid, mode, terms, st); break;
   }
   PCMI_LAUNCH_CHECK();
-#if defined(PCMI_X3_DIAG_STAMP)
-  if (pc) {
-    static unsigned long long h[2][2048];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_x3p_stamp), sizeof(h));
-    const int nq = std::min(1024, a.tiles_per_rb * kWgradTKG);
-    double work[2] = {0, 0}, wait[2] = {0, 0};
-    int cnt = 0;
-    for (int q = 8; q + 8 < nq; ++q, ++cnt)
-      for (int r = 0; r < 2; ++r) {
-        work[r] += (double)(h[r][2 * q] - h[r][2 * q - 1]);
-        wait[r] += (double)(h[r][2 * q + 1] - h[r][2 * q]);
-      }
-    unsigned long long php[4];
-    (void)hipMemcpyFromSymbol(php, HIP_SYMBOL(g_x3p_phase), sizeof(php));
-    const double nsl = (double)a.tiles_per_rb * kWgradTKG;
-    fprintf(stderr, "x3p phases: C %d rows %lld | per slot: table + gather issue %.0f | X convert+write %.0f | G/tables %.0f | barrier %.0f\n", cin, (long long)n_rows,
-            php[0] / nsl, php[1] / nsl, php[2] / nsl, php[3] / nsl);
-    if (cnt > 0)
-      fprintf(stderr, "x3p stamp: rows %lld C %d N %d K %d | slots %d | consumer work %.0f wait %.0f | producer work %.0f wait %.0f | slot %.0f cycles\n",
-              (long long)n_rows, cin, cout, K, cnt, work[0] / cnt, wait[0] / cnt, work[1] / cnt, wait[1] / cnt,
-              (double)(h[0][2 * (nq - 9)] - h[0][2 * 8]) / (nq - 17));
-  }
-#endif
   const int64_t per_k = (int64_t)cin * cout;
   wgrad_slab_sum_kernel<<<dim3((unsigned)ceil_div(per_k, 32), (unsigned)K), 256, 0, st>>>(a.slabs, a.RB, per_k, gweight, accumulate);
   PCMI_LAUNCH_CHECK();

@@ -129,23 +129,9 @@ __global__ __launch_bounds__(256) void x3_pack_many_kernel(const X3PackJob* __re
   blk[2 * jb.NS * 4 + piece] = l;
 }
 
-// -DPCMI_X3_DIAG_NO_{GATHER,DMA,SPLIT,BFRAG,MFMA,BARRIER}: timing diagnostics -- one component compiled out, wrong results, for
-// stand-alone timing only (pointcontrast_amd.build.build_variant + PCMI_LIB; profiles/r04e_kernel_component_removal.txt
-// is what they showed: no single component bounds the kernel, and it is NOT memory latency -- requesting the gathers, or
-// gathers and weight blocks, two steps ahead changed nothing: profiles/r04b_*, r04f_*).
-#if defined(PCMI_X3_DIAG_STAMP)  // timing diagnostic: shader-clock totals of one wave's phases (workgroup 17, wave 0)
-__device__ unsigned long long g_x3c_phase[8];
-#define PCMI_X3C_PHASE(P)                                          \
-  do {                                                             \
-    __builtin_amdgcn_sched_barrier(0);                             \
-    const unsigned long long t_ph = __builtin_readcyclecounter();  \
-    __builtin_amdgcn_sched_barrier(0);                             \
-    ph_sum[P] += t_ph - ph_last;                                   \
-    ph_last = t_ph;                                                \
-  } while (0)
-#else
-#define PCMI_X3C_PHASE(P) do {} while (0)
-#endif
+// Timed with one component compiled out at a time (gathers, weight staging, split, fragment reads, MFMAs, barrier;
+// profiles/r04e_kernel_component_removal.txt): no single component bounds the kernel, and it is NOT memory latency --
+// requesting the gathers, or gathers and weight blocks, two steps ahead changed nothing: profiles/r04b_*, r04f_*.
 // TERMS = 3: the split-precision kernel described above.  TERMS = 1 (the bf16 conv precision mode, pcmi_set_conv_precision):
 // the gathered rows and the weights rounded to bf16 (h alone), ONE MFMA per tile and row group, a weight block of a third
 // of the size; the rest of the kernel is the same code.
@@ -205,9 +191,6 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
   const uint32_t ld_bytes = (uint32_t)(a.x_ld * 4);
   const int sk_total = SK ? sk_u1 - sk_u : 0;
   int sk_done = 0, prio_qtr = -1;
-#if defined(PCMI_X3_DIAG_STAMP)
-  unsigned long long ph_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_last = __builtin_readcyclecounter();
-#endif
   for (;;) {  // one pass per tile piece (exactly one when !SK)
   bool sk_whole = true;
   int sk_next_u = 0, sk_c0 = 0, sk_steps = 0;
@@ -347,9 +330,7 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
     l_voff[1] = *reinterpret_cast<const uint32_t*>(row + 64);
     const uint32_t soff = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wofs + (uint32_t)lc * chunk_bytes));
     if constexpr (DMA) {
-#if !defined(PCMI_X3_DIAG_NO_DMA)  // timing diagnostic (wrong results): the weight blocks are never staged
       if (live) dma_b(nbuf, soff);
-#endif
     } else {
 #pragma unroll
       for (int q = 0; q < BR; ++q)
@@ -360,11 +341,7 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
     const uint32_t v0 = live ? l_voff[0] : kAbsent, v1 = live ? l_voff[1] : kAbsent;
     const int va = (__any(v0 != kAbsent) ? 1 : 0) | (__any(v1 != kAbsent) ? 2 : 0);
     const uint32_t soff = (uint32_t)__builtin_amdgcn_readfirstlane(lc * (kKC * 4));
-#if defined(PCMI_X3_DIAG_NO_GATHER)  // timing diagnostic (wrong results): every gather out of range = no memory traffic
-    const uint32_t o0 = kAbsent, o1 = kAbsent;
-#else
     const uint32_t o0 = v0 + 16 * kk, o1 = v1 + 16 * kk;  // absent stays out of range
-#endif
     dst[0][0] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xr, o0, soff, 0));
     dst[1][0] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xr, o1, soff, 0));
     dst[0][1] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xr, o0 + 64, soff, 0));
@@ -379,7 +356,6 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
     store_b(0);
     __syncthreads();  // (DMA: the barrier's fence waits for the block to have landed)
     auto do_step = [&](int step, v4f (&cur)[2][2], int va_cur, v4f (&nxt)[2][2], int& va_nxt) {
-      PCMI_X3C_PHASE(0);  // everything between two steps (tile prologue / epilogue, table build)
       const bool more = step + 1 < nsteps;
       if constexpr (SK) {  // issue priority falls with the workgroup's progress through its share (spconv16p_kernel)
         const int qtr = __builtin_amdgcn_readfirstlane(((sk_done + step) * 4) / max(sk_total, 1));
@@ -394,21 +370,11 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
       const bool g0 = (va_cur & 1) != 0, g1 = (va_cur & 2) != 0;
       // the gathered rows of this step as three bf16 terms
       u32x4 ah[2], am[2], al[2];
-#if defined(PCMI_X3_DIAG_NO_SPLIT)  // timing diagnostic (wrong results): no operand split, the raw bits stand in for the terms
-      ah[0] = __builtin_bit_cast(u32x4, cur[0][0]); am[0] = __builtin_bit_cast(u32x4, cur[0][1]); al[0] = ah[0];
-      ah[1] = __builtin_bit_cast(u32x4, cur[1][0]); am[1] = __builtin_bit_cast(u32x4, cur[1][1]); al[1] = ah[1];
-#else
       if (g0) split_terms<TERMS>(cur[0][0], cur[0][1], ah[0], am[0], al[0]);
       if (g1) split_terms<TERMS>(cur[1][0], cur[1][1], ah[1], am[1], al[1]);
-#endif
-      PCMI_X3C_PHASE(1);  // priority + operand split
       // B fragments of column tile ct: piece (term, n = 16 ct + i, kk); a two-tile register ring, read one tile ahead
       const u32x4* sb = &s_b[step & 1][kk * 16 + i];  // x3_piece(16 ct + i, kk) = 64 ct + this
       u32x4 bh[2], bm[2], bl[2];
-#if defined(PCMI_X3_DIAG_NO_BFRAG)  // timing diagnostic (wrong results): no fragment reads from LDS, a register stands in
-      bh[0] = bm[0] = bl[0] = bh[1] = bm[1] = bl[1] = ah[0];
-      (void)sb;
-#else
       if (va_cur) {
         bh[0] = sb[0 * NS * 4];
         if constexpr (TERMS == 3) {
@@ -416,12 +382,10 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
           bl[0] = sb[2 * NS * 4];
         }
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ct = 0; ct < CTN; ++ct) {
         const int rb = ct & 1;
-#if !defined(PCMI_X3_DIAG_NO_BFRAG)
         if (va_cur && ct + 1 < CTN) {
           bh[rb ^ 1] = sb[(0 * NS + 16 * (ct + 1)) * 4];
           if constexpr (TERMS == 3) {
@@ -429,17 +393,12 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
             bl[rb ^ 1] = sb[(2 * NS + 16 * (ct + 1)) * 4];
           }
         }
-#endif
         // six products per row group, the small ones first, BACK TO BACK on the group's accumulator, one group after the other
         // (round 3 alternated the two groups' accumulators: the same sums in the same order per accumulator, 0.6 % slower
         // in the step -- profiles/r04e_kernel_component_removal.txt); one wave-uniform branch per column tile, not per MFMA
-#if defined(PCMI_X3_DIAG_NO_MFMA)  // timing diagnostic (wrong results): the operands are kept alive, the products are not issued
-#define PCMI_X3_MFMA(G, AT, BT) asm volatile("" ::"v"(AT[G]), "v"(BT[rb]))
-#else
 #define PCMI_X3_MFMA(G, AT, BT)                                                                                             \
   acc[G][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AT[G]), __builtin_bit_cast(bf16x8, BT[rb]), \
                                                        acc[G][ct], 0, 0, 0)
-#endif
 #define PCMI_X3_SIX(G)        \
   if constexpr (TERMS == 3) { \
     PCMI_X3_MFMA(G, al, bh);  \
@@ -465,17 +424,8 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
         if (ct == 2) va_nxt = stage_a(nxt, more);
         __builtin_amdgcn_sched_barrier(0);
       }
-      PCMI_X3C_PHASE(2);  // fragment reads, MFMAs, next step's requests
-#if defined(PCMI_X3_DIAG_STAMP)
-      if (va_cur) ph_sum[4] += 1; else ph_sum[5] += 1;
-#endif
       if (more) store_b((step + 1) & 1);
-#if defined(PCMI_X3_DIAG_NO_BARRIER)  // timing diagnostic (racy): the waves of a workgroup never meet
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#else
       __syncthreads();
-#endif
-      PCMI_X3C_PHASE(3);  // barrier
     };
     for (int step = 0; step < nsteps; step += 2) {
       do_step(step, a0, va0, a1, va1);
@@ -527,10 +477,6 @@ __global__ __launch_bounds__(256, x3_min_waves<TERMS>(NT)) void spconv16x_kernel
     __syncthreads();  // s_off / s_orow / the staging area are rewritten by the next piece
   }
   }  // for (;;)
-#if defined(PCMI_X3_DIAG_STAMP)
-  if (blockIdx.x == 17 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
-    for (int e = 0; e < 8; ++e) g_x3c_phase[e] = ph_sum[e];
-#endif
 }
 
 template <bool SK, bool DMA, int TERMS>
@@ -542,17 +488,6 @@ static int launch_x3(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
     default: set_error("spconv x3: bad NT %d", NT); return PCMI_ERR_INVALID;
   }
   PCMI_LAUNCH_CHECK();
-#if defined(PCMI_X3_DIAG_STAMP)
-  {
-    unsigned long long h[8];
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_x3c_phase), sizeof(h));
-    const double ns = (double)(h[4] + h[5]);
-    if (ns > 0)
-      fprintf(stderr, "x3c phases: NT %d sk %d C %d rows %lld grid %u,%u,%u | steps %.0f (%.0f absent) | per step: split %.0f | reads + MFMAs + requests %.0f | barrier %.0f | between steps %.0f\n",
-              NT, SK ? 1 : 0, a.C, (long long)a.n_rows, grid.x, grid.y, grid.z, ns, (double)h[5], h[1] / ns, h[2] / ns, h[3] / ns, h[0] / ns);
-  }
-#endif
   return PCMI_OK;
 }
 
