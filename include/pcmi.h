@@ -431,6 +431,39 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
                       double radius, int32_t* pairs, int64_t pairs_capacity, int64_t* n_pairs_host, void* ws,
                       size_t ws_bytes, pcmi_stream_t stream);
 
+/* ---- pre-training pair corpus (csrc/corpus.hip) -----------------------------------------------------------------
+ * The geometric part of the reference's offline preprocessing ("dp/" = pretrain/data_preprocess/scannet_pair/ of the
+ * reference), one scene of F frames at a time.  Each call syncs (it returns counts or checks ranges);
+ * pcmi_corpus_overlap_counts enqueues its count kernel after its range check, so counts are ready in stream order.
+ * Rows of a frame are contiguous: offsets [F+1] (device) / offsets_host [F+1] delimit them.
+ * pcmi_corpus_backproject = dp/point_cloud_extractor.py:43-75: depth uint16 [F, H, W] (millimetres), poses fp64
+ *   [F, 4, 4] camera-to-world, intrinsic_host = the 4x4 intrinsic_depth.txt row-major (fx, fy, cx, cy, bx, by read
+ *   from it as the reference does).  Pixels with depth 0 are dropped; the rest keep row-major pixel order:
+ *   d = depth / depth_shift, X = ((u - cx) d) / fx + bx, Y = ((v - cy) d) / fy + by, Z = d,
+ *   w_r = ((X P[r,0] + Y P[r,1]) + Z P[r,2]) + P[r,3], every operation rounded on its own (no FMA).
+ *   points: fp64 [F*H*W, 3] capacity; nan_count [F] = points of the frame with a NaN coordinate.
+ * pcmi_corpus_voxel_centroids = open3d voxel_down_sample (dp/compute_full_overlapping.py:15-26) of every frame:
+ *   origin = per-frame min bound - voxel/2, voxel = floor((p - origin) / voxel_size); centroid = sequential sum of the
+ *   voxel's points in ascending order / count; rows ordered by first occurrence.  centroids: fp64 [n, 3] capacity,
+ *   voxel_offsets / voxel_offsets_host [F+1] delimit the frames' centroids.  At most 2^29 points.
+ * pcmi_corpus_overlap_counts = the ordered-pair query loop of dp/compute_full_overlapping.py:63-73 for all pairs at
+ *   once: counts [F, F] int32 (device, row-major, written whole), counts[i*F + j] = #{q in frame j : some p in frame i
+ *   with ((ex ex + ey ey) + ez ez) <= radius^2, e = q - p} (pcmi_match_radius's test) for i != j; the diagonal is 0.
+ * PCMI_ERR_RANGE: a point outside +-2^20 cells (voxels of its frame, or radius-sized cells of the overlap grid). */
+size_t pcmi_corpus_backproject_workspace_bytes(int64_t n_frames, int64_t height, int64_t width);
+int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width,
+                            const double* intrinsic_host, const double* poses, double depth_shift, double* points,
+                            int64_t* offsets, int32_t* nan_count, int64_t* offsets_host, void* ws, size_t ws_bytes,
+                            pcmi_stream_t stream);
+size_t pcmi_corpus_voxel_centroids_workspace_bytes(int64_t n_points, int64_t n_frames);
+int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, const int64_t* offsets_host,
+                                int64_t n_frames, double voxel_size, double* centroids, int64_t* voxel_offsets,
+                                int64_t* voxel_offsets_host, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_corpus_overlap_workspace_bytes(int64_t n_points, int64_t n_frames);
+int pcmi_corpus_overlap_counts(const double* centroids, const int64_t* offsets, const int64_t* offsets_host,
+                               int64_t n_frames, double radius, int32_t* counts, void* ws, size_t ws_bytes,
+                               pcmi_stream_t stream);
+
 /* Softmax cross-entropy over the rows of logits [n, c] with an ignore label -- the loss of the downstream semantic
  * segmentation fine-tuning that reuses this backbone with out_channels = number of classes
  * (downstream/semseg/lib/train.py:64,124: nn.CrossEntropyLoss(ignore_index=config.ignore_label)).

@@ -146,6 +146,14 @@ PROTOTYPES = {
     "pcmi_match_radius_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcmi_match_radius": (C.c_int, [c_vp, c_i64, C.POINTER(C.c_double), c_vp, c_i64, C.c_double, c_vp, c_i64,
                                     C.POINTER(c_i64), c_vp, c_sz, c_vp]),
+    "pcmi_corpus_backproject_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pcmi_corpus_backproject": (C.c_int, [c_vp, c_i64, c_i64, c_i64, C.POINTER(C.c_double), c_vp, C.c_double, c_vp, c_vp,
+                                          c_vp, C.POINTER(c_i64), c_vp, c_sz, c_vp]),
+    "pcmi_corpus_voxel_centroids_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_corpus_voxel_centroids": (C.c_int, [c_vp, c_vp, C.POINTER(c_i64), c_i64, C.c_double, c_vp, c_vp, C.POINTER(c_i64),
+                                              c_vp, c_sz, c_vp]),
+    "pcmi_corpus_overlap_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_corpus_overlap_counts": (C.c_int, [c_vp, c_vp, C.POINTER(c_i64), c_i64, C.c_double, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

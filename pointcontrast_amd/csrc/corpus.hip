@@ -1,0 +1,560 @@
+// Pre-training pair corpus on the device: the geometric part of the reference's offline ScanNet preprocessing
+// (pretrain/data_preprocess/scannet_pair/), which turns exported depth frames into the 'pcd' npz files and the
+// `fileA fileB overlap` list that ScanNetMatchPairDataset reads --
+//   * point_cloud_extractor.py:43-75   back-projection of every depth image to world space
+//       -> pcmi_corpus_backproject: all frames of a scene in one launch sequence, compacted in row-major pixel order;
+//   * compute_full_overlapping.py:15-26,29-31   open3d voxel_down_sample of every frame
+//       -> pcmi_corpus_voxel_centroids: per-frame min bound, a per-frame hash of voxel indices, a stable sort of the
+//          points by voxel and an ordered sequential sum per voxel;
+//   * compute_full_overlapping.py:63-73   one KD-tree radius query per point for every ORDERED pair of frames, in Python
+//       -> pcmi_corpus_overlap_counts: one hash grid of r-sized cells over the centroids of all frames; every query point
+//          walks its 27 cells once per block of 64 frames and sets one bit per frame it meets; the bits are summed per
+//          workgroup in LDS and land in the integer matrix C with one integer atomic per (workgroup, frame).
+// Everything is integer or exactly-rounded fp64 work with a fixed order (explicit round-to-nearest operations, no FMA
+// contraction, IEEE division), so the outputs are bit-identical to the numpy restatement in tests/pair_corpus_ref.py.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+
+#include "common.h"
+#include "internal.h"
+
+// hipcc contracts a * b + c into an FMA by default, and __dmul_rn / __dadd_rn are plain operators in a system header
+// where this file's pragma does not reach: the operators are written here, under the pragma, so that every product
+// and sum is rounded on its own
+#pragma clang fp contract(off)
+
+namespace pcmi {
+namespace corpus {
+
+constexpr int kBias = 1 << 20;  // |cell index| < 2^20 per axis (the loader's range, csrc/loader.hip)
+constexpr int kThreads = 256;
+constexpr int kMinChunk = 4096;  // points per workgroup of the min-bound partials
+
+__device__ inline double mul_rn(double a, double b) { return a * b; }
+__device__ inline double add_rn(double a, double b) { return a + b; }
+__device__ inline double div_rn(double a, double b) { return a / b; }
+
+// floor(v) as a cell index, or false when it is not strictly inside +-2^20 (NaN included)
+__device__ inline bool cell_of(double v, int64_t* c) {
+  const double f = floor(v);
+  if (!(f > -(double)kBias && f < (double)kBias)) return false;
+  *c = (int64_t)f;
+  return true;
+}
+__device__ inline uint64_t cell_key(int64_t x, int64_t y, int64_t z) {
+  return ((uint64_t)(x + kBias) << 42) | ((uint64_t)(y + kBias) << 21) | (uint64_t)(z + kBias);
+}
+__device__ inline bool cell_ok(int64_t x, int64_t y, int64_t z) {
+  return x > -kBias && x < kBias && y > -kBias && y < kBias && z > -kBias && z < kBias;
+}
+// open addressing, linear probing; the tables are sized >= 2x their keys, so a probe always meets an empty slot
+__device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t base, uint32_t mask, uint64_t key) {
+  uint32_t slot = hash_key(key) & mask;
+  while (true) {
+    const unsigned long long prev =
+        atomicCAS((unsigned long long*)&keys[base + slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
+    if (prev == kEmptyKey || prev == key) return base + slot;
+    slot = (slot + 1) & mask;
+  }
+}
+__device__ inline int64_t find_slot(const uint64_t* keys, uint32_t mask, uint64_t key) {
+  uint32_t slot = hash_key(key) & mask;
+  while (true) {
+    const uint64_t k = keys[slot];
+    if (k == key) return slot;
+    if (k == kEmptyKey) return -1;
+    slot = (slot + 1) & mask;
+  }
+}
+__host__ __device__ inline uint32_t pow2_at_least(int64_t n) {
+  uint32_t c = 64;
+  while ((int64_t)c < n) c <<= 1;
+  return c;
+}
+
+// ---- back-projection ---------------------------------------------------------------------------------------------
+struct Intrinsic {
+  double fx, fy, cx, cy, bx, by;
+};
+
+__global__ void bp_flag_kernel(const uint16_t* __restrict__ depth, int64_t n, int32_t* __restrict__ flags) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) flags[k] = depth[k] != 0 ? 1 : 0;
+}
+
+// d = depth / shift; X = ((u - cx) * d) / fx + bx; Y = ((v - cy) * d) / fy + by; Z = d;
+// w_r = ((X P[r,0] + Y P[r,1]) + Z P[r,2]) + P[r,3]   (point_cloud_extractor.py:58-71, our fixed order)
+__global__ void bp_points_kernel(const uint16_t* __restrict__ depth, int64_t n_frames, int64_t height, int64_t width,
+                                 Intrinsic K, const double* __restrict__ poses, double shift, const int32_t* __restrict__ pos,
+                                 double* __restrict__ points, int32_t* __restrict__ nan_count) {
+  const int64_t hw = height * width;
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_frames * hw) return;
+  const uint16_t raw = depth[k];
+  if (raw == 0) return;
+  const int64_t f = k / hw, pix = k - f * hw;
+  const double u = (double)(pix % width), v = (double)(pix / width);
+  const double d = div_rn((double)raw, shift);
+  const double X = add_rn(div_rn(mul_rn(add_rn(u, -K.cx), d), K.fx), K.bx);
+  const double Y = add_rn(div_rn(mul_rn(add_rn(v, -K.cy), d), K.fy), K.by);
+  const double* P = poses + 16 * f;
+  double* o = points + 3 * (int64_t)pos[k];
+  bool nan = false;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double w = add_rn(add_rn(add_rn(mul_rn(X, P[4 * r]), mul_rn(Y, P[4 * r + 1])), mul_rn(d, P[4 * r + 2])), P[4 * r + 3]);
+    nan |= isnan(w);
+    o[r] = w;
+  }
+  if (nan) atomicAdd(&nan_count[f], 1);
+}
+
+// offsets[f] = first output row of frame f (f < F), offsets[F] = total
+__global__ void bp_offsets_kernel(const int32_t* __restrict__ flags, const int32_t* __restrict__ pos, int64_t n_frames,
+                                  int64_t hw, int64_t* __restrict__ offsets) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f < n_frames) offsets[f] = pos[f * hw];
+  if (f == n_frames) offsets[f] = (int64_t)pos[n_frames * hw - 1] + flags[n_frames * hw - 1];
+}
+
+// ---- voxel centroids ---------------------------------------------------------------------------------------------
+// partial[f][c] = per-axis minimum of chunk c of frame f (grid: chunks x frames)
+__global__ void vc_min_partial_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offsets, int64_t n_chunks,
+                                      double* __restrict__ partial) {
+  const int64_t f = blockIdx.y, c = blockIdx.x;
+  const int64_t b = offsets[f] + c * kMinChunk, e = min(offsets[f + 1], b + kMinChunk);
+  double m[3] = {INFINITY, INFINITY, INFINITY};
+  for (int64_t i = b + threadIdx.x; i < e; i += blockDim.x)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) m[a] = fmin(m[a], pts[3 * i + a]);
+  __shared__ double red[3][kThreads];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = m[a];
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = fmin(red[a][threadIdx.x], red[a][threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) partial[3 * (f * n_chunks + c) + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// origin[f] = min_bound - 0.5 voxel; one workgroup per frame.  Also lays out the per-frame hash tables (thread 0 of the
+// workgroup of frame 0: a serial prefix over the frames, a few hundred at most).
+__global__ void vc_origin_kernel(const double* __restrict__ partial, int64_t n_chunks, double half_voxel,
+                                 const int64_t* __restrict__ offsets, int64_t n_frames, double* __restrict__ origin,
+                                 uint32_t* __restrict__ tbase, uint32_t* __restrict__ tmask) {
+  const int64_t f = blockIdx.x;
+  double m[3] = {INFINITY, INFINITY, INFINITY};
+  for (int64_t c = threadIdx.x; c < n_chunks; c += blockDim.x)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) m[a] = fmin(m[a], partial[3 * (f * n_chunks + c) + a]);
+  __shared__ double red[3][kThreads];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = m[a];
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = fmin(red[a][threadIdx.x], red[a][threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) origin[3 * f + threadIdx.x] = add_rn(red[threadIdx.x][0], -half_voxel);
+  if (f == 0 && threadIdx.x == 0) {
+    uint32_t base = 0;
+    for (int64_t g = 0; g < n_frames; ++g) {
+      const uint32_t cap = pow2_at_least(2 * (offsets[g + 1] - offsets[g]));
+      tbase[g] = base;
+      tmask[g] = cap - 1;
+      base += cap;
+    }
+  }
+}
+
+// voxel index floor((p - origin) / voxel) per axis; first[slot] = smallest point index of the voxel (grid: chunks x frames)
+__global__ void vc_insert_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offsets,
+                                 const double* __restrict__ origin, double voxel, const uint32_t* __restrict__ tbase,
+                                 const uint32_t* __restrict__ tmask, uint64_t* keys, int32_t* first, uint32_t* __restrict__ slot_of,
+                                 int32_t* err) {
+  const int64_t f = blockIdx.y;
+  const int64_t b = offsets[f], e = offsets[f + 1];
+  for (int64_t i = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t c[3];
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok &= cell_of(div_rn(add_rn(pts[3 * i + a], -origin[3 * f + a]), voxel), &c[a]);
+    if (!ok) {
+      atomicAdd(err, 1);
+      slot_of[i] = 0xffffffffu;
+      continue;
+    }
+    const uint32_t slot = claim_slot(keys, tbase[f], tmask[f], cell_key(c[0], c[1], c[2]));
+    atomicMin(&first[slot], (int32_t)i);
+    slot_of[i] = slot;
+  }
+}
+
+__global__ void vc_flag_kernel(int64_t n, const int32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
+                               int32_t* __restrict__ flags, int32_t* __restrict__ iota) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  flags[i] = first[slot_of[i]] == (int32_t)i ? 1 : 0;
+  iota[i] = (int32_t)i;
+}
+
+// vid[i] = output row of the voxel of point i (= number of first occurrences before the voxel's first point)
+__global__ void vc_vid_kernel(int64_t n, const int32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
+                              const int32_t* __restrict__ pos, int32_t* __restrict__ vid) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) vid[i] = pos[first[slot_of[i]]];
+}
+
+__global__ void vc_voxel_offsets_kernel(const int32_t* __restrict__ pos, const int64_t* __restrict__ offsets, int64_t n_frames,
+                                        int64_t n, int64_t n_vox, int64_t* __restrict__ voxel_offsets) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f <= n_frames) voxel_offsets[f] = offsets[f] < n ? (int64_t)pos[offsets[f]] : n_vox;
+}
+
+// start[v] = first row of voxel v in the stably sorted order; start[n_vox] = n
+__global__ void vc_starts_kernel(const int32_t* __restrict__ sorted_vid, int64_t n, int64_t n_vox, int32_t* __restrict__ start) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  if (k == 0 || sorted_vid[k] != sorted_vid[k - 1]) start[sorted_vid[k]] = (int32_t)k;
+  if (k == n - 1) start[n_vox] = (int32_t)n;
+}
+
+// centroid = (((0 + p_a) + p_b) + ...) / count over the voxel's points in ascending index order (the stable sort kept it)
+__global__ void vc_centroid_kernel(const double* __restrict__ pts, const int32_t* __restrict__ sorted_idx,
+                                   const int32_t* __restrict__ start, int64_t n_vox, double* __restrict__ centroids) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_vox) return;
+  const int32_t b = start[v], e = start[v + 1];
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  int32_t k = b;
+  for (; k + 4 <= e; k += 4) {  // loads issued ahead of the dependent additions, which stay in order
+    double q[4][3];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = sorted_idx[k + u];
+      q[u][0] = pts[3 * i];
+      q[u][1] = pts[3 * i + 1];
+      q[u][2] = pts[3 * i + 2];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      s0 = add_rn(s0, q[u][0]);
+      s1 = add_rn(s1, q[u][1]);
+      s2 = add_rn(s2, q[u][2]);
+    }
+  }
+  for (; k < e; ++k) {
+    const int64_t i = sorted_idx[k];
+    s0 = add_rn(s0, pts[3 * i]);
+    s1 = add_rn(s1, pts[3 * i + 1]);
+    s2 = add_rn(s2, pts[3 * i + 2]);
+  }
+  const double cnt = (double)(e - b);
+  centroids[3 * v] = div_rn(s0, cnt);
+  centroids[3 * v + 1] = div_rn(s1, cnt);
+  centroids[3 * v + 2] = div_rn(s2, cnt);
+}
+
+// ---- all-pairs overlap counts ------------------------------------------------------------------------------------
+__global__ void ov_insert_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offsets, double radius,
+                                 uint64_t* keys, int32_t* head, uint32_t mask, int32_t* __restrict__ next,
+                                 int32_t* __restrict__ frame_of, int32_t* err) {
+  const int64_t f = blockIdx.y;
+  const int64_t b = offsets[f], e = offsets[f + 1];
+  for (int64_t i = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
+    frame_of[i] = (int32_t)f;
+    int64_t c[3];
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok &= cell_of(div_rn(pts[3 * i + a], radius), &c[a]);
+    if (!ok) {
+      atomicAdd(err, 1);
+      next[i] = -1;
+      continue;
+    }
+    const uint32_t slot = claim_slot(keys, 0, mask, cell_key(c[0], c[1], c[2]));
+    next[i] = atomicExch(&head[slot], (int32_t)i);
+  }
+}
+
+// grid: (chunks of the query frame, query frame j, block t of 64 source frames).  Every query point q of frame j walks
+// the 27 cells around it once, sets bit (i - 64 t) for every source frame i of the block that holds a point p with
+// ((ex ex + ey ey) + ez ez) <= r r, e = q - p (pcmi_match_radius's test), and adds its bits to the workgroup's 64
+// LDS counters; the workgroup then adds them to C[i, j] (one global integer atomic per frame of the block).
+__global__ void __launch_bounds__(kThreads) ov_count_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offsets,
+                                                            int64_t n_frames, double radius, const uint64_t* __restrict__ keys,
+                                                            const int32_t* __restrict__ head, uint32_t mask,
+                                                            const int32_t* __restrict__ next,
+                                                            const int32_t* __restrict__ frame_of, int32_t* __restrict__ counts) {
+  __shared__ int32_t acc[64];
+  const int64_t j = blockIdx.y, t0 = (int64_t)blockIdx.z * 64;
+  if (threadIdx.x < 64) acc[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t b = offsets[j], e = offsets[j + 1];
+  const int64_t q_i = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t bits = 0;
+  if (q_i < e) {
+    const double q[3] = {pts[3 * q_i], pts[3 * q_i + 1], pts[3 * q_i + 2]};
+    const double r2 = mul_rn(radius, radius);
+    int64_t c[3];
+    // a query outside the grid's range met no cell: ov_insert_kernel counted it as an error already
+    if (cell_of(div_rn(q[0], radius), &c[0]) && cell_of(div_rn(q[1], radius), &c[1]) && cell_of(div_rn(q[2], radius), &c[2])) {
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) {
+            if (!cell_ok(c[0] + dx, c[1] + dy, c[2] + dz)) continue;
+            const int64_t slot = find_slot(keys, mask, cell_key(c[0] + dx, c[1] + dy, c[2] + dz));
+            if (slot < 0) continue;
+            for (int32_t p = head[slot]; p >= 0; p = next[p]) {
+              const int64_t bit = (int64_t)frame_of[p] - t0;
+              if (bit < 0 || bit >= 64 || ((bits >> bit) & 1ull)) continue;
+              const double ex = add_rn(q[0], -pts[3 * p]), ey = add_rn(q[1], -pts[3 * p + 1]), ez = add_rn(q[2], -pts[3 * p + 2]);
+              const double d2 = add_rn(add_rn(mul_rn(ex, ex), mul_rn(ey, ey)), mul_rn(ez, ez));
+              if (d2 <= r2) bits |= 1ull << bit;
+            }
+          }
+    }
+    if (j >= t0 && j < t0 + 64) bits &= ~(1ull << (j - t0));  // C[j, j] is not an overlap
+  }
+  while (bits) {
+    const int bit = __builtin_ctzll(bits);
+    bits &= bits - 1;
+    atomicAdd(&acc[bit], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x < 64 && t0 + threadIdx.x < n_frames && acc[threadIdx.x] != 0)
+    atomicAdd(&counts[(t0 + threadIdx.x) * n_frames + j], acc[threadIdx.x]);
+}
+
+struct Carve {
+  char* p;
+  size_t left;
+  void* take(size_t bytes) {
+    const size_t b = align_up(bytes, 256);
+    if (b > left) return nullptr;
+    void* r = p;
+    p += b;
+    left -= b;
+    return r;
+  }
+};
+
+static size_t scan_bytes(int64_t n) {
+  size_t b = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)std::max<int64_t>(n, 1));
+  return b;
+}
+static size_t sort_bytes(int64_t n) {
+  size_t b = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr,
+                                           (int32_t*)nullptr, (int)std::max<int64_t>(n, 1));
+  return b;
+}
+static int64_t max_frame(const int64_t* offsets_host, int64_t n_frames) {
+  int64_t m = 0;
+  for (int64_t f = 0; f < n_frames; ++f) m = std::max(m, offsets_host[f + 1] - offsets_host[f]);
+  return m;
+}
+static bool offsets_ok(const int64_t* offsets_host, int64_t n_frames) {
+  if (offsets_host[0] != 0) return false;
+  for (int64_t f = 0; f < n_frames; ++f)
+    if (offsets_host[f + 1] < offsets_host[f]) return false;
+  return true;
+}
+// slots of the per-frame voxel tables: sum over frames of pow2 >= 2 n_f (min 64) <= 4 n + 64 F
+static int64_t vc_table_slots(int64_t n, int64_t n_frames) { return 4 * n + 64 * n_frames; }
+
+}  // namespace corpus
+}  // namespace pcmi
+
+using namespace pcmi;
+using namespace pcmi::corpus;
+
+extern "C" {
+
+size_t pcmi_corpus_backproject_workspace_bytes(int64_t n_frames, int64_t height, int64_t width) {
+  const int64_t n = std::max<int64_t>(n_frames * height * width, 1);
+  return 2 * align_up((size_t)n * 4, 256) + align_up(scan_bytes(n), 256) + 1024;
+}
+
+int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width, const double* intrinsic_host,
+                            const double* poses, double depth_shift, double* points, int64_t* offsets, int32_t* nan_count,
+                            int64_t* offsets_host, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
+  PCMI_REQUIRE(n_frames > 0 && height > 0 && width > 0 && n_frames * height * width < (1ll << 31) && intrinsic_host && depth &&
+                   poses && points && offsets && nan_count && offsets_host && depth_shift > 0,
+               PCMI_ERR_INVALID, "corpus_backproject: bad argument (%lld frames of %lld x %lld)", (long long)n_frames,
+               (long long)height, (long long)width);
+  const int64_t hw = height * width, n = n_frames * hw;
+  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_backproject_workspace_bytes(n_frames, height, width), PCMI_ERR_WORKSPACE,
+               "corpus_backproject: workspace too small");
+  hipStream_t st = as_stream(stream);
+  Carve cv{(char*)ws, ws_bytes};
+  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
+  size_t tb = scan_bytes(n);
+  void* temp = cv.take(tb);
+  PCMI_REQUIRE(flags && pos && temp, PCMI_ERR_WORKSPACE, "corpus_backproject: workspace too small");
+  const double* A = intrinsic_host;  // 4x4 row-major (intrinsic_depth.txt)
+  const Intrinsic K{A[0], A[5], A[2], A[6], A[3], A[7]};
+  PCMI_HIP_CHECK(hipMemsetAsync(nan_count, 0, (size_t)n_frames * 4, st));
+  const unsigned gn = (unsigned)ceil_div(n, kThreads);
+  bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, flags);
+  PCMI_LAUNCH_CHECK();
+  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, flags, pos, (int)n, st));
+  bp_points_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, poses, depth_shift, pos, points, nan_count);
+  PCMI_LAUNCH_CHECK();
+  bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(flags, pos, n_frames, hw, offsets);
+  PCMI_LAUNCH_CHECK();
+  PCMI_HIP_CHECK(hipMemcpyAsync(offsets_host, offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  return PCMI_OK;
+}
+
+size_t pcmi_corpus_voxel_centroids_workspace_bytes(int64_t n_points, int64_t n_frames) {
+  const int64_t n = std::max<int64_t>(n_points, 1), F = std::max<int64_t>(n_frames, 1);
+  const int64_t chunks = ceil_div(n, kMinChunk) + F;  // bound on sum over frames of ceil(n_f / kMinChunk)
+  const size_t slots = (size_t)vc_table_slots(n, F);
+  return align_up(slots * 8, 256) + align_up(slots * 4, 256) + 7 * align_up((size_t)n * 4, 256) +
+         align_up((size_t)(n + 1) * 4, 256) + align_up((size_t)F * chunks * 24, 256) + align_up((size_t)F * 24, 256) +
+         2 * align_up((size_t)F * 4, 256) + align_up(std::max(scan_bytes(n), sort_bytes(n)), 256) + 256 + 1024;
+}
+
+int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, const int64_t* offsets_host, int64_t n_frames,
+                                double voxel_size, double* centroids, int64_t* voxel_offsets, int64_t* voxel_offsets_host,
+                                void* ws, size_t ws_bytes, pcmi_stream_t stream) {
+  PCMI_REQUIRE(n_frames > 0 && n_frames < 65536 && offsets && offsets_host && centroids && voxel_offsets && voxel_offsets_host && voxel_size > 0,
+               PCMI_ERR_INVALID, "corpus_voxel_centroids: bad argument");
+  PCMI_REQUIRE(offsets_ok(offsets_host, n_frames), PCMI_ERR_INVALID, "corpus_voxel_centroids: offsets must start at 0 and ascend");
+  const int64_t n = offsets_host[n_frames];
+  PCMI_REQUIRE(n < (1ll << 29) && (n == 0 || points), PCMI_ERR_INVALID,
+               "corpus_voxel_centroids: %lld points (at most 2^29 per call)", (long long)n);
+  hipStream_t st = as_stream(stream);
+  if (n == 0) {
+    for (int64_t f = 0; f <= n_frames; ++f) voxel_offsets_host[f] = 0;
+    PCMI_HIP_CHECK(hipMemsetAsync(voxel_offsets, 0, (size_t)(n_frames + 1) * 8, st));
+    return PCMI_OK;
+  }
+  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_voxel_centroids_workspace_bytes(n, n_frames), PCMI_ERR_WORKSPACE,
+               "corpus_voxel_centroids: workspace too small");
+  const int64_t mf = max_frame(offsets_host, n_frames), n_chunks = std::max<int64_t>(ceil_div(mf, kMinChunk), 1);
+  const size_t slots = (size_t)vc_table_slots(n, n_frames);
+  Carve cv{(char*)ws, ws_bytes};
+  uint64_t* keys = (uint64_t*)cv.take(slots * 8);
+  int32_t* first = (int32_t*)cv.take(slots * 4);
+  uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
+  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* vid = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* iota = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* svid = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* sidx = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* start = (int32_t*)cv.take((size_t)(n + 1) * 4);
+  double* partial = (double*)cv.take((size_t)n_frames * n_chunks * 24);
+  double* origin = (double*)cv.take((size_t)n_frames * 24);
+  uint32_t* tbase = (uint32_t*)cv.take((size_t)n_frames * 4);
+  uint32_t* tmask = (uint32_t*)cv.take((size_t)n_frames * 4);
+  int32_t* err = (int32_t*)cv.take(256);
+  size_t tb = std::max(scan_bytes(n), sort_bytes(n));
+  void* temp = cv.take(tb);
+  PCMI_REQUIRE(keys && first && slot_of && flags && pos && vid && iota && svid && sidx && start && partial && origin && tbase &&
+                   tmask && err && temp,
+               PCMI_ERR_WORKSPACE, "corpus_voxel_centroids: workspace too small");
+  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, slots * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(first, 0x7f, slots * 4, st));  // 0x7f7f7f7f > any point index
+  PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
+  vc_min_partial_kernel<<<dim3((unsigned)n_chunks, (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, n_chunks, partial);
+  PCMI_LAUNCH_CHECK();
+  vc_origin_kernel<<<(unsigned)n_frames, kThreads, 0, st>>>(partial, n_chunks, 0.5 * voxel_size, offsets, n_frames, origin,
+                                                             tbase, tmask);
+  PCMI_LAUNCH_CHECK();
+  const unsigned gx = (unsigned)std::min<int64_t>(ceil_div(mf, kThreads), 1024), gn = (unsigned)ceil_div(n, kThreads);
+  vc_insert_kernel<<<dim3(std::max(gx, 1u), (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, origin, voxel_size, tbase,
+                                                                                    tmask, keys, first, slot_of, err);
+  PCMI_LAUNCH_CHECK();
+  int32_t herr = 0;
+  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  PCMI_REQUIRE(herr == 0, PCMI_ERR_RANGE,
+               "corpus_voxel_centroids: %d points fall outside 2^20 voxels of their frame's min bound (or are not finite)", herr);
+  vc_flag_kernel<<<gn, kThreads, 0, st>>>(n, first, slot_of, flags, iota);
+  PCMI_LAUNCH_CHECK();
+  size_t tb2 = tb;
+  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, flags, pos, (int)n, st));
+  int32_t last[2] = {0, 0};
+  PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], flags + n - 1, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&last[1], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  const int64_t n_vox = (int64_t)last[0] + last[1];
+  vc_vid_kernel<<<gn, kThreads, 0, st>>>(n, first, slot_of, pos, vid);
+  PCMI_LAUNCH_CHECK();
+  vc_voxel_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(pos, offsets, n_frames, n, n_vox,
+                                                                                          voxel_offsets);
+  PCMI_LAUNCH_CHECK();
+  int end_bit = 1;
+  while ((1ll << end_bit) < n_vox) ++end_bit;
+  tb2 = tb;  // stable LSD radix sort: the points of a voxel keep ascending index order
+  PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, tb2, vid, svid, iota, sidx, (int)n, 0, end_bit, st));
+  vc_starts_kernel<<<gn, kThreads, 0, st>>>(svid, n, n_vox, start);
+  PCMI_LAUNCH_CHECK();
+  vc_centroid_kernel<<<(unsigned)ceil_div(n_vox, kThreads), kThreads, 0, st>>>(points, sidx, start, n_vox, centroids);
+  PCMI_LAUNCH_CHECK();
+  PCMI_HIP_CHECK(hipMemcpyAsync(voxel_offsets_host, voxel_offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  return PCMI_OK;
+}
+
+size_t pcmi_corpus_overlap_workspace_bytes(int64_t n_points, int64_t n_frames) {
+  (void)n_frames;
+  const int64_t n = std::max<int64_t>(n_points, 1);
+  const size_t cap = pow2_at_least(2 * n);
+  return align_up(cap * 8, 256) + align_up(cap * 4, 256) + 2 * align_up((size_t)n * 4, 256) + 256 + 1024;
+}
+
+int pcmi_corpus_overlap_counts(const double* centroids, const int64_t* offsets, const int64_t* offsets_host, int64_t n_frames,
+                               double radius, int32_t* counts, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
+  PCMI_REQUIRE(n_frames > 0 && n_frames < 65536 && offsets && offsets_host && counts && radius > 0, PCMI_ERR_INVALID,
+               "corpus_overlap_counts: bad argument");
+  PCMI_REQUIRE(offsets_ok(offsets_host, n_frames), PCMI_ERR_INVALID, "corpus_overlap_counts: offsets must start at 0 and ascend");
+  const int64_t n = offsets_host[n_frames];
+  PCMI_REQUIRE(n < (1ll << 30) && (n == 0 || centroids), PCMI_ERR_INVALID,
+               "corpus_overlap_counts: %lld points (at most 2^30 per call)", (long long)n);
+  hipStream_t st = as_stream(stream);
+  PCMI_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n_frames * n_frames * 4, st));
+  if (n == 0) return PCMI_OK;
+  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_overlap_workspace_bytes(n, n_frames), PCMI_ERR_WORKSPACE,
+               "corpus_overlap_counts: workspace too small");
+  const uint32_t cap = pow2_at_least(2 * n);
+  Carve cv{(char*)ws, ws_bytes};
+  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
+  int32_t* head = (int32_t*)cv.take((size_t)cap * 4);
+  int32_t* next = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* frame_of = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* err = (int32_t*)cv.take(256);
+  PCMI_REQUIRE(keys && head && next && frame_of && err, PCMI_ERR_WORKSPACE, "corpus_overlap_counts: workspace too small");
+  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(head, 0xff, (size_t)cap * 4, st));  // -1
+  PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
+  const int64_t mf = max_frame(offsets_host, n_frames);
+  const unsigned gx = (unsigned)std::max<int64_t>(ceil_div(mf, kThreads), 1);
+  ov_insert_kernel<<<dim3(std::min(gx, 1024u), (unsigned)n_frames), kThreads, 0, st>>>(centroids, offsets, radius, keys, head,
+                                                                                      cap - 1, next, frame_of, err);
+  PCMI_LAUNCH_CHECK();
+  int32_t herr = 0;
+  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  PCMI_REQUIRE(herr == 0, PCMI_ERR_RANGE,
+               "corpus_overlap_counts: %d points fall outside +-2^20 cells of size %g (or are not finite)", herr, radius);
+  const unsigned tiles = (unsigned)ceil_div(n_frames, 64);
+  ov_count_kernel<<<dim3(gx, (unsigned)n_frames, tiles), kThreads, 0, st>>>(centroids, offsets, n_frames, radius, keys, head,
+                                                                           cap - 1, next, frame_of, counts);
+  PCMI_LAUNCH_CHECK();
+  return PCMI_OK;
+}
+
+}  // extern "C"
