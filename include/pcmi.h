@@ -196,6 +196,10 @@ int pcmi_coords_segments(pcmi_coords_t* h, int key, pcmi_segments_t* out, pcmi_s
  *   bwd_data   gin[i]  = sum_k gout[j] @ W[k]^T
  *   bwd_weight gW[k]   = sum_pairs in[i]^T gout[j]
  * All three overwrite their outputs (no accumulate) and are deterministic (no float atomics).
+ * out_ld / gin_ld may exceed the width (the output as a column slice of a wider buffer): the columns outside the slice
+ * are left untouched.  Feature matrices -- inputs and outputs -- start 16-byte aligned with a leading dimension that is a
+ * multiple of 4 (PCMI_ERR_INVALID otherwise); ws holds at least pcmi_spconv_workspace_bytes() bytes for the same shape
+ * (PCMI_ERR_WORKSPACE otherwise).  A refused call enqueues nothing.  tests/test_gpu_c_contract.py holds all of this.
  * ------------------------------------------------------------------------------------------ */
 size_t pcmi_spconv_workspace_bytes(int64_t n_in, int64_t n_out, int cin, int cout, int K,
                                    int64_t M);

@@ -1024,7 +1024,9 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
                         hipStream_t st) {
   PCMI_REQUIRE(C % 32 == 0 && N % 32 == 0, PCMI_ERR_UNSUPPORTED,
                "spconv: channels (%d -> %d) must be multiples of 32 on the MFMA path", C, N);
-  PCMI_REQUIRE(x_ld % 4 == 0 && out_ld >= N && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0),
+  // (the reductions behind a split launch -- sk_fixup_kernel, split_reduce_kernel -- store the output rows as float4)
+  PCMI_REQUIRE(x_ld % 4 == 0 && out_ld >= N && out_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) &&
+                   ((uintptr_t)out % 16 == 0),
                PCMI_ERR_INVALID, "spconv: operands must be 16-byte aligned with ld %% 4 == 0");
   if (n_rows == 0) return PCMI_OK;
   const ConvEnv env = conv_env();

@@ -1062,12 +1062,13 @@ int spconv_backward_weight_m32(const float* in, int64_t in_ld, int64_t n_in, int
                               &NT, &nchunks);
     if (rc) return rc;
   }
-  if (a.mode != kSlabs && map && !accumulate)  // an offset without pairs gets no workgroup: its slice must read zero
-    PCMI_HIP_CHECK(hipMemsetAsync(gweight, 0, sizeof(float) * K * per_k, st));
+  // (checked before anything is enqueued: a refused call writes nothing; the column sums start at the next 256 bytes)
   const size_t slab_bytes = a.mode == kDirect ? 0 : (size_t)nchunks * per_k * sizeof(float);
   const size_t bias_bytes = gbias ? (size_t)1024 * cout * sizeof(float) : 0;
-  PCMI_REQUIRE(ws && ws_bytes >= slab_bytes + bias_bytes, PCMI_ERR_WORKSPACE,
-               "spconv_bwd_weight: workspace %zu < %zu bytes", ws_bytes, slab_bytes + bias_bytes);
+  const size_t ws_need = gbias ? align_up(slab_bytes, 256) + bias_bytes : slab_bytes;
+  PCMI_REQUIRE(ws && ws_bytes >= ws_need, PCMI_ERR_WORKSPACE, "spconv_bwd_weight: workspace %zu < %zu bytes", ws_bytes, ws_need);
+  if (a.mode != kSlabs && map && !accumulate)  // an offset without pairs gets no workgroup: its slice must read zero
+    PCMI_HIP_CHECK(hipMemsetAsync(gweight, 0, sizeof(float) * K * per_k, st));
   a.slabs = (float*)ws;
   const int64_t grid_x = nchunks;
   if (stem) {
