@@ -468,6 +468,69 @@ int pcmi_corpus_overlap_counts(const double* centroids, const int64_t* offsets, 
                                int64_t n_frames, double radius, int32_t* counts, void* ws, size_t ws_bytes,
                                pcmi_stream_t stream);
 
+/* ---- PointNet++ point-set ops (csrc/pointset.hip) -----------------------------------------------------------------
+ * What the reference's detection fine-tuning ("vn/" = downstream/votenet_det_new/ of the reference) reaches through its
+ * one native extension, vn/models/backbone/pointnet2/pointnet2_utils.py.  fp32 data, int32 indices; feature tensors are
+ * channel-first and contiguous, as the reference's: [B, C, N].  A "cloud" is one batch element.  Every squared distance is
+ * ((dx dx) + (dy dy)) + (dz dz), each operation rounded on its own, so index outputs are reproducible in float32 on the
+ * host (tests/pointset_ref.py).  No float atomics: every result is reproducible bit for bit.  A refused call enqueues nothing.
+ *
+ * pcmi_fps = furthest_point_sample (pointnet2_utils.py:51-80; called per scene at vn/models/backbone_module.py:166-169 and
+ *   from the set-abstraction modules).  Clouds: dense -- offs == NULL, rows == NULL, cloud i = xyz[i * max_cloud ..), and
+ *   n_points == n_clouds * max_cloud -- or segments of xyz [n_points, 3]: offs [n_clouds + 1] (device), point p of cloud i
+ *   is xyz[rows[offs[i] + p]], or xyz[offs[i] + p] with rows == NULL (pcmi_segments_t's rows / offs); max_cloud is then an
+ *   upper bound of any cloud's size known to the host (n_points if nothing better is): it only selects which size tiers are
+ *   launched, and no host synchronisation is needed.  One launch covers the whole batch (one workgroup per cloud).
+ *   Semantics: the running minimum of every point starts at 1e10; pick 0 is point 0; for each later pick every point with
+ *   x^2 + y^2 + z^2 > 1e-3 (the reference's padding convention; others are never updated nor chosen) lowers its minimum by
+ *   its squared distance to the previous pick, and the pick is the point with the largest minimum, the LOWEST index among
+ *   equals (the reference's tie order depends on its block size), index 0 if no point qualifies.  m > n repeats picks.
+ *   out [n_clouds, m]: positions within the cloud, -1 for an empty cloud (or one beyond max_cloud or n_points);
+ *   out_rows (nullable, [n_clouds, m]): the same picks as rows of xyz (rows[offs[i] + pick] / offs[i] + pick), -1 likewise.
+ *   ws: pcmi_fps_workspace_bytes(n_points, max_cloud, rows != NULL) -- a compacted copy of the coordinates when there is a
+ *   row list, and the running minima when max_cloud > 8192 (smaller clouds keep coordinates and minima in registers);
+ *   0 bytes (ws may be NULL) for a dense batch of at most 8192 points per cloud.
+ * pcmi_ball_query = ball_query (pointnet2_utils.py:260-291; vn/models/proposal_module.py:93 through QueryAndGroup):
+ *   idx [B, np, nsample] = the first nsample points of xyz [B, n, 3], in ascending index, with d^2 < radius * radius (the
+ *   product in fp32) of centre new_xyz [B, np, 3]; unfilled slots repeat the first hit, no hit: zeros.  No workspace.
+ * pcmi_three_nn = three_nn (pointnet2_utils.py:120-149; the feature-propagation modules): for every unknown [B, n, 3] the
+ *   three nearest of known [B, m, 3], scanning in ascending index with strict <, so the lower index wins a tie; dist2
+ *   [B, n, 3] holds SQUARED distances (the caller takes the root, as the reference's Python does), idx [B, n, 3].
+ *   m < 3: PCMI_ERR_INVALID.  No workspace.
+ * Gathers, forward (gather_operation :83-117, grouping_operation :209-257, three_interpolate :152-206):
+ *   gather_points   out [B, C, m]      = feat [B, C, N] at idx [B, m]
+ *   group_points    out [B, C, np, ns] = feat [B, C, N] at idx [B, np, ns]
+ *   three_interpolate out [B, C, n]    = (w0 f0 + w1 f1) + w2 f2, f_k = feat [B, C, M] at idx [B, n, 3], weight [B, n, 3]
+ * and backward: gfeat [B, C, N] (resp. M), written whole, = the scatter-add of gout over idx, computed in gather form --
+ *   inverse lists from an integer count, a scan and a stable radix placement by flat source position, every target summed in
+ *   ascending source position (the reference uses float atomics) -- ws: pcmi_pointset_scatter_workspace_bytes(number of
+ *   indices = B m / B np ns / 3 B n, number of targets = B N / B M).
+ * validate != 0: the indices are checked on the device first and the call SYNCS; an index outside [0, N) returns
+ *   PCMI_ERR_RANGE with nothing else launched.  validate == 0 (indices this library produced, or a backward pass whose
+ *   forward validated them): no synchronisation; an index outside the range is still never dereferenced -- it reads as 0 in
+ *   the forward passes and is dropped by the backward ones. */
+size_t pcmi_fps_workspace_bytes(int64_t n_points, int64_t max_cloud, int with_rows);
+int pcmi_fps(const float* xyz, int64_t n_points, const int32_t* rows, const int32_t* offs, int64_t n_clouds,
+             int64_t max_cloud, int64_t m, int32_t* out, int32_t* out_rows, void* ws, size_t ws_bytes,
+             pcmi_stream_t stream);
+int pcmi_ball_query(const float* xyz, const float* new_xyz, int64_t B, int64_t n, int64_t np, float radius, int nsample,
+                    int32_t* idx, pcmi_stream_t stream);
+int pcmi_three_nn(const float* unknown, const float* known, int64_t B, int64_t n, int64_t m, float* dist2, int32_t* idx,
+                  pcmi_stream_t stream);
+size_t pcmi_pointset_scatter_workspace_bytes(int64_t n_idx, int64_t n_targets);
+int pcmi_gather_points_fwd(const float* feat, const int32_t* idx, int64_t B, int C, int64_t N, int64_t m, float* out,
+                           int validate, pcmi_stream_t stream);
+int pcmi_gather_points_bwd(const float* gout, const int32_t* idx, int64_t B, int C, int64_t N, int64_t m, float* gfeat,
+                           int validate, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_group_points_fwd(const float* feat, const int32_t* idx, int64_t B, int C, int64_t N, int64_t np, int64_t ns,
+                          float* out, int validate, pcmi_stream_t stream);
+int pcmi_group_points_bwd(const float* gout, const int32_t* idx, int64_t B, int C, int64_t N, int64_t np, int64_t ns,
+                          float* gfeat, int validate, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_three_interpolate_fwd(const float* feat, const int32_t* idx, const float* weight, int64_t B, int C, int64_t M,
+                               int64_t n, float* out, int validate, pcmi_stream_t stream);
+int pcmi_three_interpolate_bwd(const float* gout, const int32_t* idx, const float* weight, int64_t B, int C, int64_t M,
+                               int64_t n, float* gfeat, int validate, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+
 /* Softmax cross-entropy over the rows of logits [n, c] with an ignore label -- the loss of the downstream semantic
  * segmentation fine-tuning that reuses this backbone with out_channels = number of classes
  * (downstream/semseg/lib/train.py:64,124: nn.CrossEntropyLoss(ignore_index=config.ignore_label)).

@@ -154,6 +154,18 @@ PROTOTYPES = {
                                               c_vp, c_sz, c_vp]),
     "pcmi_corpus_overlap_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcmi_corpus_overlap_counts": (C.c_int, [c_vp, c_vp, C.POINTER(c_i64), c_i64, C.c_double, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_fps_workspace_bytes": (c_sz, [c_i64, c_i64, C.c_int]),
+    "pcmi_fps": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_ball_query": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, C.c_int, c_vp, c_vp]),
+    "pcmi_three_nn": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pcmi_pointset_scatter_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_gather_points_fwd": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp]),
+    "pcmi_gather_points_bwd": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp, c_sz, c_vp]),
+    "pcmi_group_points_fwd": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp]),
+    "pcmi_group_points_bwd": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_sz, c_vp]),
+    "pcmi_three_interpolate_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp]),
+    "pcmi_three_interpolate_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp, c_sz,
+                                             c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

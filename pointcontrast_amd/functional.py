@@ -606,3 +606,190 @@ class InstanceNormFunction(Function):
     check(lib.pcmi_instnorm_bwd(ptr(dy), dy.stride(0), ptr(x), x_ld, ptr(y), c, c, C.byref(seg), ptr(w), ptr(mean),
                                 ptr(invstd), ptr(dx), c, ptr(dres), c, ptr(dw), ptr(db), ws, wsb, cur_stream(dev)))
     return dx, dw.reshape(ctx.wshape), db.reshape(ctx.bshape), None, None, dres, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PointNet++ point-set ops (csrc/pointset.hip) -- the reference's pointnet2 extension
+# (downstream/votenet_det_new/models/backbone/pointnet2/pointnet2_utils.py).  Channel-first fp32 features [B, C, N],
+# int32 indices, as there.  The forward passes validate their indices on the device (an index outside the range raises
+# PcmiError instead of faulting); the backward passes reuse the validated indices without a host synchronisation.
+# ---------------------------------------------------------------------------------------------------------------------
+def _f32c(t, who):
+  require_cuda(t, who)
+  return (t if t.dtype == torch.float32 else t.float()).contiguous()
+
+
+def _i32c(t, device):
+  return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def furthest_point_sample_segments(xyz, offs, rows, n_clouds, max_cloud, npoint):
+  """One furthest-point-sampling launch over the segments of xyz [N, 3]: offs / rows are device pointers (ints or
+  ctypes void pointers; pcmi_segments_t's tables, rows may be None), max_cloud an upper bound of any cloud's size.
+  Returns (positions within the cloud, rows of xyz), both int32 [n_clouds, npoint]; -1 for an empty cloud.  No host sync."""
+  xyz = _f32c(xyz, "furthest point sampling")
+  assert xyz.dim() == 2 and xyz.shape[1] == 3, "xyz must be [N, 3]"
+  N, dev = xyz.shape[0], xyz.device
+  out = torch.empty((n_clouds, npoint), dtype=torch.int32, device=dev)
+  out_rows = torch.empty((n_clouds, npoint), dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_fps_workspace_bytes(N, max_cloud, int(rows is not None)), dev)
+  check(lib.pcmi_fps(ptr(xyz), N, rows, offs, n_clouds, max_cloud, npoint, ptr(out), ptr(out_rows), ws, wsb, cur_stream(dev)))
+  return out, out_rows
+
+
+class FurthestPointSampleFunction(Function):
+  """furthest_point_sample(xyz [B, N, 3], npoint) -> int32 [B, npoint] (pointnet2_utils.py:51-80); not differentiable."""
+
+  @staticmethod
+  def forward(ctx, xyz, npoint):
+    xyz = _f32c(xyz, "furthest point sampling")
+    assert xyz.dim() == 3 and xyz.shape[2] == 3, "xyz must be [B, N, 3]"
+    B, N, _ = xyz.shape
+    out = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device)
+    ws, wsb = ws_args(lib.pcmi_fps_workspace_bytes(B * N, N, 0), xyz.device)
+    check(lib.pcmi_fps(ptr(xyz), B * N, None, None, B, N, int(npoint), ptr(out), None, ws, wsb, cur_stream(xyz.device)))
+    ctx.mark_non_differentiable(out)
+    return out
+
+  @staticmethod
+  def backward(ctx, a=None):
+    return None, None
+
+
+class BallQueryFunction(Function):
+  """ball_query(radius, nsample, xyz [B, N, 3], new_xyz [B, npoint, 3]) -> int32 [B, npoint, nsample]
+  (pointnet2_utils.py:260-291); not differentiable."""
+
+  @staticmethod
+  def forward(ctx, radius, nsample, xyz, new_xyz):
+    xyz, new_xyz = _f32c(xyz, "ball query"), _f32c(new_xyz, "ball query")
+    assert xyz.dim() == 3 and new_xyz.dim() == 3 and xyz.shape[2] == 3 and new_xyz.shape[2] == 3 and \
+        xyz.shape[0] == new_xyz.shape[0], "ball query: xyz [B, N, 3], new_xyz [B, npoint, 3]"
+    B, N, _ = xyz.shape
+    npoint = new_xyz.shape[1]
+    idx = torch.empty((B, npoint, int(nsample)), dtype=torch.int32, device=xyz.device)
+    check(lib.pcmi_ball_query(ptr(xyz), ptr(new_xyz), B, N, npoint, float(radius), int(nsample), ptr(idx),
+                              cur_stream(xyz.device)))
+    ctx.mark_non_differentiable(idx)
+    return idx
+
+  @staticmethod
+  def backward(ctx, a=None):
+    return None, None, None, None
+
+
+def three_nn_squared(unknown, known):
+  """(squared distances fp32 [B, n, 3], indices int32 [B, n, 3]) of the three nearest known points (pcmi_three_nn)."""
+  unknown, known = _f32c(unknown, "three_nn"), _f32c(known, "three_nn")
+  assert unknown.dim() == 3 and known.dim() == 3 and unknown.shape[2] == 3 and known.shape[2] == 3 and \
+      unknown.shape[0] == known.shape[0], "three_nn: unknown [B, n, 3], known [B, m, 3]"
+  B, n, _ = unknown.shape
+  d2 = torch.empty((B, n, 3), dtype=torch.float32, device=unknown.device)
+  idx = torch.empty((B, n, 3), dtype=torch.int32, device=unknown.device)
+  check(lib.pcmi_three_nn(ptr(unknown), ptr(known), B, n, known.shape[1], ptr(d2), ptr(idx), cur_stream(unknown.device)))
+  return d2, idx
+
+
+class ThreeNNFunction(Function):
+  """three_nn(unknown [B, n, 3], known [B, m, 3]) -> (l2 distances [B, n, 3], int32 indices [B, n, 3])
+  (pointnet2_utils.py:120-149); not differentiable."""
+
+  @staticmethod
+  def forward(ctx, unknown, known):
+    d2, idx = three_nn_squared(unknown, known)
+    dist = torch.sqrt(d2)
+    ctx.mark_non_differentiable(dist, idx)
+    return dist, idx
+
+  @staticmethod
+  def backward(ctx, a=None, b=None):
+    return None, None
+
+
+class GatherOperationFunction(Function):
+  """gather_operation(features [B, C, N], idx [B, npoint]) -> [B, C, npoint] (pointnet2_utils.py:83-117)."""
+
+  @staticmethod
+  def forward(ctx, features, idx):
+    f = _f32c(features, "gather_operation")
+    idx = _i32c(idx, f.device)
+    assert f.dim() == 3 and idx.dim() == 2 and idx.shape[0] == f.shape[0], "gather_operation: features [B, C, N], idx [B, npoint]"
+    B, Cc, N = f.shape
+    m = idx.shape[1]
+    out = torch.empty((B, Cc, m), dtype=torch.float32, device=f.device)
+    check(lib.pcmi_gather_points_fwd(ptr(f), ptr(idx), B, Cc, N, m, ptr(out), 1, cur_stream(f.device)))
+    ctx.save_for_backward(idx)
+    ctx.shape = (B, Cc, N, m)
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    (idx,) = ctx.saved_tensors
+    B, Cc, N, m = ctx.shape
+    g = _f32c(gout, "gather_operation")
+    gf = torch.empty((B, Cc, N), dtype=torch.float32, device=g.device)
+    ws, wsb = ws_args(lib.pcmi_pointset_scatter_workspace_bytes(B * m, B * N), g.device)
+    check(lib.pcmi_gather_points_bwd(ptr(g), ptr(idx), B, Cc, N, m, ptr(gf), 0, ws, wsb, cur_stream(g.device)))
+    return gf, None
+
+
+class GroupingOperationFunction(Function):
+  """grouping_operation(features [B, C, N], idx [B, npoint, nsample]) -> [B, C, npoint, nsample]
+  (pointnet2_utils.py:209-257)."""
+
+  @staticmethod
+  def forward(ctx, features, idx):
+    f = _f32c(features, "grouping_operation")
+    idx = _i32c(idx, f.device)
+    assert f.dim() == 3 and idx.dim() == 3 and idx.shape[0] == f.shape[0], \
+        "grouping_operation: features [B, C, N], idx [B, npoint, nsample]"
+    B, Cc, N = f.shape
+    _, npoint, ns = idx.shape
+    out = torch.empty((B, Cc, npoint, ns), dtype=torch.float32, device=f.device)
+    check(lib.pcmi_group_points_fwd(ptr(f), ptr(idx), B, Cc, N, npoint, ns, ptr(out), 1, cur_stream(f.device)))
+    ctx.save_for_backward(idx)
+    ctx.shape = (B, Cc, N, npoint, ns)
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    (idx,) = ctx.saved_tensors
+    B, Cc, N, npoint, ns = ctx.shape
+    g = _f32c(gout, "grouping_operation")
+    gf = torch.empty((B, Cc, N), dtype=torch.float32, device=g.device)
+    ws, wsb = ws_args(lib.pcmi_pointset_scatter_workspace_bytes(B * npoint * ns, B * N), g.device)
+    check(lib.pcmi_group_points_bwd(ptr(g), ptr(idx), B, Cc, N, npoint, ns, ptr(gf), 0, ws, wsb, cur_stream(g.device)))
+    return gf, None
+
+
+class ThreeInterpolateFunction(Function):
+  """three_interpolate(features [B, c, m], idx [B, n, 3], weight [B, n, 3]) -> [B, c, n] (pointnet2_utils.py:152-206);
+  differentiable in the features only, as the reference."""
+
+  @staticmethod
+  def forward(ctx, features, idx, weight):
+    f = _f32c(features, "three_interpolate")
+    idx = _i32c(idx, f.device)
+    w = _f32c(weight, "three_interpolate")
+    assert f.dim() == 3 and idx.dim() == 3 and idx.shape[2] == 3 and w.shape == idx.shape and idx.shape[0] == f.shape[0], \
+        "three_interpolate: features [B, c, m], idx / weight [B, n, 3]"
+    B, Cc, M = f.shape
+    n = idx.shape[1]
+    out = torch.empty((B, Cc, n), dtype=torch.float32, device=f.device)
+    check(lib.pcmi_three_interpolate_fwd(ptr(f), ptr(idx), ptr(w), B, Cc, M, n, ptr(out), 1, cur_stream(f.device)))
+    ctx.save_for_backward(idx, w)
+    ctx.shape = (B, Cc, M, n)
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    idx, w = ctx.saved_tensors
+    B, Cc, M, n = ctx.shape
+    g = _f32c(gout, "three_interpolate")
+    gf = torch.empty((B, Cc, M), dtype=torch.float32, device=g.device)
+    ws, wsb = ws_args(lib.pcmi_pointset_scatter_workspace_bytes(B * n * 3, B * M), g.device)
+    check(lib.pcmi_three_interpolate_bwd(ptr(g), ptr(idx), ptr(w), B, Cc, M, n, ptr(gf), 0, ws, wsb, cur_stream(g.device)))
+    return gf, None, None
