@@ -531,6 +531,68 @@ int pcmi_three_interpolate_fwd(const float* feat, const int32_t* idx, const floa
 int pcmi_three_interpolate_bwd(const float* gout, const int32_t* idx, const float* weight, int64_t B, int C, int64_t M,
                                int64_t n, float* gfeat, int validate, void* ws, size_t ws_bytes, pcmi_stream_t stream);
 
+/* ---- VoteNet detection head (csrc/detect.hip) ------------------------------------------------------------------------
+ * The matching of the detection loss and the decoding of the predictions ("vn/" as above).  fp32 data, int32 indices,
+ * contiguous tensors.  Every operation of a distance is rounded on its own in fp32, in the order written here, so the
+ * argmins are reproducible in float32 on the host (tests/votenet_ref.py).  No float atomics: every result is reproducible
+ * bit for bit.  A refused call enqueues nothing.
+ *
+ * pcmi_nn_distance_fwd = one direction of nn_distance (vn/lib/utils/nn_distance.py:34-61; called at
+ *   vn/models/loss_helper.py:59 -- votes against ground-truth votes, B num_seed batches of vote_factor x 3 points --, :84
+ *   and :133): dist [B, N] / idx [B, N] = min / argmin over the M points b [B, M, 3] of the distance to a [B, N, 3], without
+ *   the [B, N, M] tensor the reference materialises (the other direction is the same call with a and b swapped).
+ *   mode 0: ((dx dx) + (dy dy)) + (dz dz); 1: (|dx| + |dy|) + |dz|; 2 (l1smooth): (h(dx) + h(dy)) + h(dz),
+ *   h(x) = 0.5 (q q) + delta (|x| - q), q = min(|x|, delta).  The LOWEST index wins a tie (torch.min's tie order depends
+ *   on its backend).  N, M >= 1.  One launch for any B: rows of the flat [B N] list per thread while M <= 32 (thousands of
+ *   tiny batches, several per wave), else a workgroup per 256 rows with b streamed through LDS.  No workspace.
+ * pcmi_nn_distance_bwd: gpc1 [B, N, 3] and gpc2 [B, M, 3] (written whole) from gdist1 [B, N] and gdist2 [B, M] -- what
+ *   autograd derives from the two torch.min of :59-60: every distance routes its gradient to its argmin pair, with
+ *   d'(x) = 2 x / sign(x) (0 at 0) / clamp(x, -delta, delta) per component.  idx1 [B, N] indexes pc2, idx2 [B, M] indexes
+ *   pc1 (the forward's outputs).  A point's gradient is its own term plus the terms of every point of the other cloud whose
+ *   nearest neighbour it is, added in ascending index of the other cloud (gather form): a direct scan of the other cloud's
+ *   indices up to 1024 points, the inverse lists of the point-set ops beyond.  An index outside its cloud is never
+ *   dereferenced.  ws: pcmi_nn_distance_bwd_workspace_bytes(B, N, M) -- 0 (ws may be NULL) while both clouds have at most
+ *   1024 points.
+ * pcmi_box_decode = the decoding loop of parse_predictions (vn/models/ap_helper.py:57-83, :102-103: B K calls of
+ *   class2angle / class2size / get_3d_box with a .cpu() each): one thread per proposal of center [B, K, 3], heading_scores /
+ *   heading_residuals [B, K, H], size_scores [B, K, S], size_residuals [B, K, S, 3], sem_cls_scores [B, K, Cls],
+ *   objectness_scores [B, K, 2], mean_size_arr [S, 3].  heading_class / size_class / sem_cls [B, K]: argmax, the lowest index
+ *   of equal scores as torch.argmax.  box_params [B, K, 7]: the centre in upright-camera coordinates (x, -z, y), the size
+ *   (l, w, h) = mean_size_arr[size_class] + residual, the heading angle = class 2 pi / H + residual, minus 2 pi if above pi
+ *   (vn/lib/datasets/sunrgbd/model_util_sunrgbd.py:67-75), 0 with zero_heading != 0 (the axis-aligned boxes of
+ *   vn/lib/datasets/scannet/model_util_scannet.py:45-49).  corners [B, K, 8, 3] in get_3d_box's order
+ *   (vn/lib/utils/box_util.py:210-225), minmax [B, K, 6] = (min x, y, z, max x, y, z) over the corners, obj_prob [B, K] =
+ *   softmax(objectness)[1], sem_cls_probs [B, K, Cls] = softmax(sem_cls_scores).
+ * pcmi_box_point_counts = the remove_empty_box loop (ap_helper.py:88-99: B K Delaunay triangulations with find_simplex over
+ *   every point of the scene): counts [B, K] (int32, written whole) = points of points [B, N, point_ld >= 3] (upright-depth
+ *   x, y, z in the first three columns) inside box_params' boxes -- rotated into the box's frame, every |coordinate| <= half
+ *   the size, faces included (the triangulation's answer on a face depends on its tolerance).  Integer atomics only.
+ * pcmi_box_nms = nms_2d_faster / nms_3d_faster / nms_3d_faster_samecls (vn/lib/utils/nms.py:44-155; ap_helper.py:104-162),
+ *   mode 0 / 1 / 2, one workgroup per scene: the boxes with counts >= min_points (counts == NULL: all) are ranked by
+ *   obj_prob descending, equal scores by ascending index (numpy's argsort leaves ties unspecified); in rank order a box
+ *   that is still alive is kept and clears every later box it suppresses: overlap o > nms_iou in fp32 (a NaN overlap
+ *   suppresses nothing), o = inter / (area_i + area_j - inter), or inter / area_j with old_type != 0, on minmax's camera
+ *   x / z rectangle (mode 0) or the whole box (1, 2), in mode 2 only between boxes of the same sem_cls (nullable otherwise).
+ *   pred_mask [B, K] (int32, written whole): 1 for a kept box.  K <= 1024 (the K x K suppression bits live in LDS, 128 KiB
+ *   at 1024): PCMI_ERR_UNSUPPORTED beyond. */
+int pcmi_nn_distance_fwd(const float* a, const float* b, int64_t B, int64_t N, int64_t M, int mode, float delta,
+                         float* dist, int32_t* idx, pcmi_stream_t stream);
+size_t pcmi_nn_distance_bwd_workspace_bytes(int64_t B, int64_t N, int64_t M);
+int pcmi_nn_distance_bwd(const float* pc1, const float* pc2, const int32_t* idx1, const int32_t* idx2,
+                         const float* gdist1, const float* gdist2, int64_t B, int64_t N, int64_t M, int mode,
+                         float delta, float* gpc1, float* gpc2, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_box_decode(const float* center, const float* heading_scores, const float* heading_residuals,
+                    const float* size_scores, const float* size_residuals, const float* sem_cls_scores,
+                    const float* objectness_scores, const float* mean_size_arr, int64_t B, int64_t K, int H, int S,
+                    int Cls, int zero_heading, int32_t* heading_class, int32_t* size_class, int32_t* sem_cls,
+                    float* box_params, float* corners, float* minmax, float* obj_prob, float* sem_cls_probs,
+                    pcmi_stream_t stream);
+int pcmi_box_point_counts(const float* points, int64_t point_ld, const float* box_params, int64_t B, int64_t N,
+                          int64_t K, int32_t* counts, pcmi_stream_t stream);
+int pcmi_box_nms(const float* minmax, const float* obj_prob, const int32_t* sem_cls, const int32_t* counts,
+                 int min_points, int64_t B, int64_t K, int mode, int old_type, float nms_iou, int32_t* pred_mask,
+                 pcmi_stream_t stream);
+
 /* Softmax cross-entropy over the rows of logits [n, c] with an ignore label -- the loss of the downstream semantic
  * segmentation fine-tuning that reuses this backbone with out_channels = number of classes
  * (downstream/semseg/lib/train.py:64,124: nn.CrossEntropyLoss(ignore_index=config.ignore_label)).

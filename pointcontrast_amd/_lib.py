@@ -166,6 +166,13 @@ PROTOTYPES = {
     "pcmi_three_interpolate_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp]),
     "pcmi_three_interpolate_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp, c_sz,
                                              c_vp]),
+    "pcmi_nn_distance_fwd": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_vp, c_vp]),
+    "pcmi_nn_distance_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pcmi_nn_distance_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_vp,
+                                       c_vp, c_sz, c_vp]),
+    "pcmi_box_decode": (C.c_int, [c_vp] * 8 + [c_i64, c_i64, C.c_int, C.c_int, C.c_int, C.c_int] + [c_vp] * 8 + [c_vp]),
+    "pcmi_box_point_counts": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "pcmi_box_nms": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, C.c_int, C.c_int, c_f32, c_vp, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

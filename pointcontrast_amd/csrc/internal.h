@@ -121,6 +121,14 @@ int tile_units(const uint32_t* sorted_key, int K, int64_t n, uint32_t* tile_mask
 // rows of the contiguous tile range one XCD processes (tile swizzle of the conv kernel, 128-row tiles)
 static inline int64_t xcd_chunk_rows(int64_t n) { return ceil_div(ceil_div(n, 128), 8) * 128; }
 
+// pointset.hip: the inverse lists of an index tensor idx [B, L] with targets in [0, N) -- integer count, scan and a stable
+// radix placement by flat source position: the sources p = b L + l of target (b, t) are pos[start[b N + t] ..
+// start[b N + t + 1]) in ascending p; an index outside the range is dropped.  B L and B N in [1, 2^31 - 1); start / pos
+// point into ws (inverse_lists_workspace bytes) and stay valid until it is reused.  No synchronisation.
+size_t inverse_lists_workspace(int64_t n_idx, int64_t n_targets);
+int inverse_lists(const char* who, const int32_t* idx, int64_t B, int64_t L, int64_t N, void* ws, size_t ws_bytes,
+                  const int32_t** start, const int32_t** pos, hipStream_t st);
+
 // n zero-initialised arrival counters (common.h: arrive_last) for launches on `st`: one pool per stream -- launches
 // on a stream are serialised and every kernel leaves its counters at zero.  nullptr on allocation failure.
 unsigned* stream_counters(hipStream_t st, size_t n);

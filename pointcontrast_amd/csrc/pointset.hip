@@ -467,18 +467,11 @@ static size_t scatter_workspace(int64_t n_idx, int64_t n_targets) {
          align_up(std::max(scan_bytes(n_targets + 1), sort_bytes(n_idx)), 256) + 256;
 }
 
-// idx: [B, L] targets in [0, N); gout: [B, C, L / div]; weight (nullable): [B, L]; gin: [B, C, N], written whole
-static int scatter_bwd(const char* who, const float* gout, const int32_t* idx, const float* weight, int need_weight, int64_t B, int C,
-                       int64_t N, int64_t L, int div, float* gin, int validate, void* ws, size_t ws_bytes, hipStream_t st) {
-  PCMI_REQUIRE(B >= 0 && C >= 0 && N >= 0 && L >= 0 && grid_ok(B, C) && B * L < (1ll << 31) && B * N < (1ll << 31) - 1, PCMI_ERR_INVALID,
-               "%s: bad shape (B %lld, C %d, N %lld, %lld indices per cloud)", who, (long long)B, C, (long long)N, (long long)L);
-  if (B == 0 || C == 0 || N == 0) return PCMI_OK;
-  PCMI_REQUIRE(gin && (L == 0 || (gout && idx && (!need_weight || weight))), PCMI_ERR_INVALID, "%s: null pointer", who);
+// The inverse lists of idx [B, L] (targets in [0, N)): the flat source positions p = b L + l of target (b, t) are
+// pos[start[b N + t] .. start[b N + t + 1]), in ascending p.  n_idx = B L > 0, n_targets = B N > 0; both < 2^31 - 1.
+static int build_inverse_lists(const char* who, const int32_t* idx, int64_t B, int64_t L, int64_t N, int validate, void* ws,
+                               size_t ws_bytes, const int32_t** start_out, const int32_t** pos_out, hipStream_t st) {
   const int64_t n_idx = B * L, n_targets = B * N;
-  if (n_idx == 0) {
-    PCMI_HIP_CHECK(hipMemsetAsync(gin, 0, (size_t)B * C * N * 4, st));
-    return PCMI_OK;
-  }
   PCMI_REQUIRE(ws && ws_bytes >= scatter_workspace(n_idx, n_targets), PCMI_ERR_WORKSPACE, "%s: workspace too small", who);
   Carve cv{(char*)ws, ws_bytes};
   int32_t* keys = (int32_t*)cv.take((size_t)n_idx * 4);
@@ -512,6 +505,25 @@ static int scatter_bwd(const char* who, const float* gout, const int32_t* idx, c
   // a stable sort of (key, flat position): the sources of a target end up in ascending position
   stb = tb;
   PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, stb, keys, keys_sorted, iota, pos, (int)n_idx, 0, bits, st));
+  *start_out = start;
+  *pos_out = pos;
+  return PCMI_OK;
+}
+
+// idx: [B, L] targets in [0, N); gout: [B, C, L / div]; weight (nullable): [B, L]; gin: [B, C, N], written whole
+static int scatter_bwd(const char* who, const float* gout, const int32_t* idx, const float* weight, int need_weight, int64_t B, int C,
+                       int64_t N, int64_t L, int div, float* gin, int validate, void* ws, size_t ws_bytes, hipStream_t st) {
+  PCMI_REQUIRE(B >= 0 && C >= 0 && N >= 0 && L >= 0 && grid_ok(B, C) && B * L < (1ll << 31) && B * N < (1ll << 31) - 1, PCMI_ERR_INVALID,
+               "%s: bad shape (B %lld, C %d, N %lld, %lld indices per cloud)", who, (long long)B, C, (long long)N, (long long)L);
+  if (B == 0 || C == 0 || N == 0) return PCMI_OK;
+  PCMI_REQUIRE(gin && (L == 0 || (gout && idx && (!need_weight || weight))), PCMI_ERR_INVALID, "%s: null pointer", who);
+  if (B * L == 0) {
+    PCMI_HIP_CHECK(hipMemsetAsync(gin, 0, (size_t)B * C * N * 4, st));
+    return PCMI_OK;
+  }
+  const int32_t *start = nullptr, *pos = nullptr;
+  const int rc = build_inverse_lists(who, idx, B, L, N, validate, ws, ws_bytes, &start, &pos, st);
+  if (rc != PCMI_OK) return rc;
   scatter_accumulate_kernel<<<dim3((unsigned)ceil_div(N, 256), (unsigned)C, (unsigned)B), 256, 0, st>>>(gout, weight, start, pos, C, N, L,
                                                                                                       div, gin);
   PCMI_LAUNCH_CHECK();
@@ -519,6 +531,12 @@ static int scatter_bwd(const char* who, const float* gout, const int32_t* idx, c
 }
 
 }  // namespace pointset
+
+size_t inverse_lists_workspace(int64_t n_idx, int64_t n_targets) { return pointset::scatter_workspace(n_idx, n_targets); }
+int inverse_lists(const char* who, const int32_t* idx, int64_t B, int64_t L, int64_t N, void* ws, size_t ws_bytes,
+                  const int32_t** start, const int32_t** pos, hipStream_t st) {
+  return pointset::build_inverse_lists(who, idx, B, L, N, 0, ws, ws_bytes, start, pos, st);
+}
 }  // namespace pcmi
 
 using namespace pcmi;

@@ -793,3 +793,96 @@ class ThreeInterpolateFunction(Function):
     ws, wsb = ws_args(lib.pcmi_pointset_scatter_workspace_bytes(B * n * 3, B * M), g.device)
     check(lib.pcmi_three_interpolate_bwd(ptr(g), ptr(idx), ptr(w), B, Cc, M, n, ptr(gf), 0, ws, wsb, cur_stream(g.device)))
     return gf, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# VoteNet detection head (csrc/detect.hip): the matching of the loss (downstream/votenet_det_new/lib/utils/nn_distance.py)
+# and the decoding of the predictions (models/ap_helper.py parse_predictions).
+# ---------------------------------------------------------------------------------------------------------------------
+NN_DISTANCE_MODES = {"l2": 0, "l1": 1, "huber": 2}
+
+
+class NNDistanceFunction(Function):
+  """nn_distance(pc1 [B, N, 3], pc2 [B, M, 3]) -> (dist1 [B, N], idx1 int64 [B, N], dist2 [B, M], idx2 int64 [B, M])
+  (nn_distance.py:34-61): two pcmi_nn_distance_fwd launches; the backward pass routes both distance gradients to their
+  argmin pairs in one pcmi_nn_distance_bwd.  The lowest index wins a tie.  The indices are not differentiable."""
+
+  @staticmethod
+  def forward(ctx, pc1, pc2, mode, delta):
+    a, b = _f32c(pc1, "nn_distance"), _f32c(pc2, "nn_distance")
+    B, N, _ = a.shape
+    M = b.shape[1]
+    dev = a.device
+    dist1 = torch.empty((B, N), dtype=torch.float32, device=dev)
+    dist2 = torch.empty((B, M), dtype=torch.float32, device=dev)
+    idx1 = torch.empty((B, N), dtype=torch.int32, device=dev)
+    idx2 = torch.empty((B, M), dtype=torch.int32, device=dev)
+    st = cur_stream(dev)
+    check(lib.pcmi_nn_distance_fwd(ptr(a), ptr(b), B, N, M, mode, delta, ptr(dist1), ptr(idx1), st))
+    check(lib.pcmi_nn_distance_fwd(ptr(b), ptr(a), B, M, N, mode, delta, ptr(dist2), ptr(idx2), st))
+    ctx.save_for_backward(a, b, idx1, idx2)
+    ctx.args = (B, N, M, mode, delta)
+    i1, i2 = idx1.long(), idx2.long()
+    ctx.mark_non_differentiable(i1, i2)
+    return dist1, i1, dist2, i2
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, g1, _gi1, g2, _gi2):
+    a, b, idx1, idx2 = ctx.saved_tensors
+    B, N, M, mode, delta = ctx.args
+    g1, g2 = _f32c(g1, "nn_distance"), _f32c(g2, "nn_distance")
+    ga, gb = torch.empty_like(a), torch.empty_like(b)
+    ws, wsb = ws_args(lib.pcmi_nn_distance_bwd_workspace_bytes(B, N, M), a.device)
+    check(lib.pcmi_nn_distance_bwd(ptr(a), ptr(b), ptr(idx1), ptr(idx2), ptr(g1), ptr(g2), B, N, M, mode, delta, ptr(ga), ptr(gb),
+                                   ws, wsb, cur_stream(a.device)))
+    return ga, gb, None, None
+
+
+def box_decode(center, heading_scores, heading_residuals, size_scores, size_residuals, sem_cls_scores, objectness_scores,
+               mean_size_arr, zero_heading, with_counts_of=None, nms=None, min_points=5):
+  """pcmi_box_decode, then (with_counts_of = point_clouds [B, N, >= 3]) pcmi_box_point_counts and (nms = (mode, old_type,
+  nms_iou)) pcmi_box_nms over the boxes holding at least min_points points (all of them without counts).  Returns a dict of device
+  tensors: heading_class / size_class / sem_cls (int32 [B, K]), box_params [B, K, 7], corners [B, K, 8, 3], minmax [B, K, 6],
+  obj_prob [B, K], sem_cls_probs [B, K, Cls], counts (int32 [B, K] or None), pred_mask (int32 [B, K] or None), and `packed`:
+  the one float32 buffer that corners, obj_prob, sem_cls_probs, sem_cls and pred_mask are views of, in this order (the int32
+  ones bit-cast), so that a single copy reads all of them back.  No host synchronisation."""
+  who = "box_decode"
+  ts = [_f32c(t, who) for t in (center, heading_scores, heading_residuals, size_scores, size_residuals, sem_cls_scores,
+                               objectness_scores, mean_size_arr)]
+  c, hs, hr, ss, sr, sem, obj, msa = ts
+  assert c.dim() == 3 and c.shape[2] == 3, "box_decode: center [B, K, 3]"
+  B, K, _ = c.shape
+  H, S, Cls = hs.shape[2], ss.shape[2], sem.shape[2]
+  assert hs.shape == (B, K, H) and hr.shape == (B, K, H) and ss.shape == (B, K, S) and sr.shape == (B, K, S, 3) and \
+      sem.shape == (B, K, Cls) and obj.shape == (B, K, 2) and msa.shape == (S, 3), "box_decode: inconsistent shapes"
+  dev = c.device
+  n = B * K
+  packed = torch.empty(n * (24 + 1 + Cls + 2), dtype=torch.float32, device=dev)
+  o = 0
+  corners = packed[o:o + n * 24].view(B, K, 8, 3); o += n * 24
+  obj_prob = packed[o:o + n].view(B, K); o += n
+  sem_probs = packed[o:o + n * Cls].view(B, K, Cls); o += n * Cls
+  sem_cls = packed[o:o + n].view(torch.int32).view(B, K); o += n
+  pred_mask = packed[o:o + n].view(torch.int32).view(B, K)
+  heading_class = torch.empty((B, K), dtype=torch.int32, device=dev)
+  size_class = torch.empty((B, K), dtype=torch.int32, device=dev)
+  params = torch.empty((B, K, 7), dtype=torch.float32, device=dev)
+  minmax = torch.empty((B, K, 6), dtype=torch.float32, device=dev)
+  st = cur_stream(dev)
+  check(lib.pcmi_box_decode(ptr(c), ptr(hs), ptr(hr), ptr(ss), ptr(sr), ptr(sem), ptr(obj), ptr(msa), B, K, H, S, Cls,
+                            int(bool(zero_heading)), ptr(heading_class), ptr(size_class), ptr(sem_cls), ptr(params), ptr(corners),
+                            ptr(minmax), ptr(obj_prob), ptr(sem_probs), st))
+  counts = None
+  if with_counts_of is not None:
+    pts = _f32c(with_counts_of, who)
+    assert pts.dim() == 3 and pts.shape[0] == B and pts.shape[2] >= 3, "box_decode: point_clouds [B, N, >= 3]"
+    counts = torch.empty((B, K), dtype=torch.int32, device=dev)
+    check(lib.pcmi_box_point_counts(ptr(pts), pts.shape[2], ptr(params), B, pts.shape[1], K, ptr(counts), st))
+  if nms is not None:
+    mode, old_type, nms_iou = nms
+    check(lib.pcmi_box_nms(ptr(minmax), ptr(obj_prob), ptr(sem_cls), ptr(counts), int(min_points), B, K, int(mode), int(bool(old_type)),
+                           float(nms_iou), ptr(pred_mask), st))
+  return dict(heading_class=heading_class, size_class=size_class, sem_cls=sem_cls, box_params=params, corners=corners, minmax=minmax,
+              obj_prob=obj_prob, sem_cls_probs=sem_probs, counts=counts, pred_mask=pred_mask if nms is not None else None,
+              packed=packed)

@@ -1,0 +1,173 @@
+"""tests/votenet_ref.py (the host restatement the GPU tests of the detection head compare against) pinned to the reference's
+own functions: directly where the reference tree is present, and everywhere through tests/golden/golden_votenet.npz, which
+holds what those functions returned.  loss_helper.get_loss itself calls .cuda() and cannot run without a device: its
+restatement is checked by reading, its nn_distance / huber_loss parts against the reference's functions here."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import make_golden_votenet as mk  # noqa: E402
+import votenet_ref as R  # noqa: E402
+
+G = np.load(mk.PATH)
+needs_reference = pytest.mark.skipif(not mk.reference_available(), reason="the reference tree is not present on this host")
+KW = {"l2": {}, "l1": dict(l1=True), "huber": dict(l1smooth=True, delta=0.75)}
+
+
+@needs_reference
+def test_golden_fixture_is_what_the_reference_functions_produce():
+  new = mk.generate()
+  assert set(new) == set(G.files)
+  for k in G.files:
+    assert new[k].dtype == G[k].dtype and np.array_equal(new[k], G[k]), k
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+def test_nn_distance_matches_the_fixture(mode):
+  d1, i1, d2, i2 = R.nn_distance(torch.from_numpy(G["nn_pc1"]), torch.from_numpy(G["nn_pc2"]), **KW[mode])
+  assert d1.dtype == torch.float64 and i1.dtype == torch.int64
+  assert np.array_equal(i1.numpy(), G["nn_%s_idx1" % mode]) and np.array_equal(i2.numpy(), G["nn_%s_idx2" % mode])
+  np.testing.assert_allclose(d1.numpy(), G["nn_%s_dist1" % mode], rtol=1e-5, atol=1e-6)
+  np.testing.assert_allclose(d2.numpy(), G["nn_%s_dist2" % mode], rtol=1e-5, atol=1e-6)
+
+
+@needs_reference
+@pytest.mark.parametrize("mode", R.MODES)
+@pytest.mark.parametrize("shape", [(1, 1, 1), (2, 63, 65), (3, 65, 1), (50, 3, 3)])
+def test_nn_distance_matches_the_reference_function(mode, shape):
+  nd, _, _ = mk.import_reference()
+  rng = np.random.RandomState(sum(shape))
+  B, N, M = shape
+  p1 = torch.from_numpy(rng.uniform(-2, 2, (B, N, 3)).astype(np.float32))
+  p2 = torch.from_numpy(rng.uniform(-2, 2, (B, M, 3)).astype(np.float32))
+  want = nd.nn_distance(p1, p2, **KW[mode])
+  got = R.nn_distance(p1, p2, **KW[mode])
+  # random float32 coordinates: no two candidates tie, so torch's argmin is the float32 rule's
+  assert torch.equal(got[1], want[1]) and torch.equal(got[3], want[3])
+  np.testing.assert_allclose(got[0].numpy(), want[0].numpy(), rtol=1e-5, atol=1e-6)
+  np.testing.assert_allclose(got[2].numpy(), want[2].numpy(), rtol=1e-5, atol=1e-6)
+  # the gradient through the restatement's gathers is the gradient through the reference's two torch.min
+  a, b = p1.double().requires_grad_(), p2.double().requires_grad_()
+  d1, _, d2, _ = nd.nn_distance(a, b, **KW[mode])
+  w1, w2 = torch.from_numpy(rng.rand(B, N)), torch.from_numpy(rng.rand(B, M))
+  ((d1 * w1).sum() + (d2 * w2).sum()).backward()
+  a2, b2 = p1.double().requires_grad_(), p2.double().requires_grad_()
+  e1, e2 = R.nn_distance_at(a2, b2, got[1], got[3], "huber" if mode == "huber" else mode, KW[mode].get("delta", 1.0))
+  ((e1 * w1).sum() + (e2 * w2).sum()).backward()
+  np.testing.assert_allclose(a2.grad.numpy(), a.grad.numpy(), rtol=1e-9, atol=1e-12)
+  np.testing.assert_allclose(b2.grad.numpy(), b.grad.numpy(), rtol=1e-9, atol=1e-12)
+
+
+def test_ties_take_the_lowest_index():
+  rng = np.random.RandomState(5)
+  p2 = np.tile(rng.uniform(-1, 1, (1, 9, 3)).astype(np.float32), (1, 4, 1))  # every point four times
+  p1 = rng.uniform(-1, 1, (1, 20, 3)).astype(np.float32)
+  for mode in R.MODES:
+    i1, _ = R.nn_indices(p1, p2, mode)
+    assert (i1 < 9).all()
+
+
+def test_huber_matches_the_fixture():
+  got = R.huber(torch.from_numpy(G["huber_in"]).double(), 0.75).numpy()
+  np.testing.assert_allclose(got, G["huber_out"], rtol=1e-6, atol=1e-7)
+  from pointcontrast_amd.downstream import votenet
+  assert np.array_equal(votenet.huber_loss(torch.from_numpy(G["huber_in"]), 0.75).numpy(), G["huber_out"])
+
+
+def test_corners_match_get_3d_box():
+  got = R.corners_of(G["box_size"], G["box_angle"], G["box_center"])
+  np.testing.assert_allclose(got, G["box_corners"], rtol=0, atol=1e-12)
+  from pointcontrast_amd.downstream import votenet
+  for k in range(6):
+    np.testing.assert_allclose(votenet.box_corners(G["box_size"][k], G["box_angle"][k], G["box_center"][k]), G["box_corners"][k],
+                               rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("old", [0, 1])
+@pytest.mark.parametrize("name,mode", [("2d", 0), ("3d", 1), ("3dcls", 2)])
+def test_nms_matches_the_fixture(name, mode, old):
+  K = G["nms_boxes"].shape[0]
+  mask, gap = R.nms(G["nms_boxes"], G["nms_score"], G["nms_cls"], np.ones(K, bool), mode, bool(old), mk.NMS_IOU)
+  assert np.array_equal(mask, G["nms_%s_old%d" % (name, old)])
+  assert 0 < mask.sum() < K, "the fixture must suppress some boxes and keep some"
+  assert gap > 1e-6
+
+
+@needs_reference
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_nms_matches_the_reference_functions_with_empty_boxes(seed):
+  _, _, nm = mk.import_reference()
+  rng = np.random.RandomState(seed)
+  K = 40
+  b = mk.clustered_boxes(rng, K, 6)
+  b[3, 3:] = b[3, :3]  # a zero-volume box
+  s = rng.permutation(K) / K + 0.01
+  c = rng.randint(0, 3, K).astype(np.float64)
+  ne = rng.rand(K) > 0.2
+  nz = np.where(ne)[0]
+  for old in (False, True):
+    with np.errstate(invalid="ignore", divide="ignore"):
+      picks = (nm.nms_2d_faster(np.stack([b[ne, 0], b[ne, 2], b[ne, 3], b[ne, 5], s[ne]], 1), 0.25, old),
+               nm.nms_3d_faster(np.concatenate([b[ne], s[ne, None]], 1), 0.25, old),
+               nm.nms_3d_faster_samecls(np.concatenate([b[ne], s[ne, None], c[ne, None]], 1), 0.25, old))
+    for mode, pick in enumerate(picks):
+      want = np.zeros(K, np.int64)
+      want[nz[np.asarray(pick, np.int64)]] = 1
+      got, _ = R.nms(b, s, c, ne, mode, old, 0.25)
+      assert np.array_equal(got, want), (mode, old)
+
+
+def test_nms_equal_scores_go_to_the_lower_index():
+  b = np.array([[0, 0, 0, 1, 1, 1], [0.1, 0, 0, 1.1, 1, 1]], np.float64)
+  mask, _ = R.nms(b, np.array([0.5, 0.5]), np.zeros(2), np.ones(2, bool), 1, False, 0.25)
+  assert mask.tolist() == [1, 0]
+
+
+def test_point_counts_match_delaunay():
+  """extract_pc_in_box3d of the reference is in_hull: scipy.spatial.Delaunay(corners).find_simplex(points) >= 0, on the
+  box flipped to upright-depth coordinates; written out here because its module needs cv2."""
+  from scipy.spatial import Delaunay
+  rng = np.random.RandomState(11)
+  K, N = 12, 3000
+  params = np.concatenate([rng.uniform(-1, 1, (K, 3)), rng.uniform(0.3, 1.5, (K, 3)), rng.uniform(-np.pi, np.pi, (K, 1))], 1)
+  params[0, 6] = 0.0
+  pts = rng.uniform(-2, 2, (N, 3)).astype(np.float32)
+  counts, face = R.box_point_counts(pts, params)
+  assert face.min() > 1e-7, "a point on a face: the triangulation's answer would depend on its tolerance"
+  corners = R.corners_of(params[:, 3:6], params[:, 6], params[:, 0:3])  # camera
+  depth = np.stack([corners[..., 0], corners[..., 2], -corners[..., 1]], -1)
+  for k in range(K):
+    want = int((Delaunay(depth[k]).find_simplex(pts.astype(np.float64)) >= 0).sum())
+    assert counts[k] == want, (k, counts[k], want)
+  assert counts.max() >= 5 and counts.min() < 5
+
+
+def test_parse_predictions_matches_the_fixture():
+  arrays = {k[3:]: G[k] for k in G.files if k.startswith("pp_") and k not in ("pp_corners", "pp_obj_prob", "pp_pred_mask", "pp_mean_size_arr")}
+  out, mask, stats = R.parse_predictions(arrays, G["pp_mean_size_arr"], 4, False, False, 1, False, mk.NMS_IOU, 0.05, False)
+  assert np.array_equal(mask, G["pp_pred_mask"]) and 0 < mask.sum() < mask.size
+  assert stats["min_iou_gap"] > 1e-4
+  dec = R.box_decode(arrays["center"], arrays["heading_scores"], arrays["heading_residuals"], arrays["size_scores"],
+                     arrays["size_residuals"], arrays["sem_cls_scores"], arrays["objectness_scores"], G["pp_mean_size_arr"], False)
+  np.testing.assert_allclose(dec["corners"], G["pp_corners"], rtol=0, atol=1e-9)
+  np.testing.assert_allclose(dec["obj_prob"], G["pp_obj_prob"], rtol=1e-6)
+  for (c, corners, score, j) in out[0]:
+    assert mask[0, j] == 1 and score > 0.05
+
+
+def test_get_loss_runs_and_is_differentiable():
+  sys.path.insert(0, HERE)
+  import votenet_fixtures as VF
+  ep, cfg = VF.loss_inputs(B=2, num_points=64, num_seed=16, K=8, K2=3, H=4, S=3, Cls=3, seed=0)
+  ep64 = VF.to_float64(ep, requires_grad=True)
+  out = R.get_loss(ep64, cfg.num_heading_bin, cfg.mean_size_arr)
+  out["loss"].backward()
+  assert torch.isfinite(out["loss"]) and all(ep64[k].grad is not None and torch.isfinite(ep64[k].grad).all() for k in VF.PREDICTED)
+  assert out["loss"].item() == pytest.approx(10 * (out["vote_loss"] + 0.5 * out["objectness_loss"] + out["box_loss"] +
+                                                   0.1 * out["sem_cls_loss"]).item())
