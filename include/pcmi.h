@@ -551,7 +551,7 @@ int pcmi_three_interpolate_bwd(const float* gout, const int32_t* idx, const floa
  *   pc1 (the forward's outputs).  A point's gradient is its own term plus the terms of every point of the other cloud whose
  *   nearest neighbour it is, added in ascending index of the other cloud (gather form): a direct scan of the other cloud's
  *   indices up to 1024 points, the inverse lists of the point-set ops beyond.  An index outside its cloud is never
- *   dereferenced.  ws: pcmi_nn_distance_bwd_workspace_bytes(B, N, M) -- 0 (ws may be NULL) while both clouds have at most
+ *   dereferenced: its term is dropped from both gradients, in every form (no error code, no synchronisation).  ws: pcmi_nn_distance_bwd_workspace_bytes(B, N, M) -- 0 (ws may be NULL) while both clouds have at most
  *   1024 points.
  * pcmi_box_decode = the decoding loop of parse_predictions (vn/models/ap_helper.py:57-83, :102-103: B K calls of
  *   class2angle / class2size / get_3d_box with a .cpu() each): one thread per proposal of center [B, K, 3], heading_scores /

@@ -51,6 +51,9 @@ def _p(t):
 
 # ---- 1. nn_distance forward ---------------------------------------------------------------------------------------------------
 FWD_SHAPES = [(1, 1, 1), (2, 63, 65), (2, 64, 64), (3, 65, 1), (2, 256, 64), (1, 1000, 1025), (8192, 1, 3), (8192, 3, 3), (5000, 3, 1)]
+# the dispatch of nn_fwd_mode (flat kernel if M <= kSmallOther = 32 or B > 65535, else LDS tiles of kTile = 1024 points):
+# B > 65535 with M > kSmallOther (the flat kernel walking a large other cloud), the kSmallOther edge, exactly one full kTile
+FWD_SHAPES += [(65536, 1, 33), (65536, 2, 40), (3, 70, 32), (3, 70, 33), (2, 300, 1024)]
 
 
 def _clouds(shape, seed):
@@ -114,6 +117,10 @@ def test_nn_distance_refuses_other_shapes():
 # (1, 300, 7): many pc1 points share a nearest pc2 point; (1, 1100, 1030): both directions take the inverse lists (a cloud
 # of more than 1024 points); (2, 65, 64): the LDS scan; (8192, 3, 3): the flat kernel
 BWD_SHAPES = [(2, 65, 64), (8192, 3, 3), (1, 300, 7), (1, 1100, 1030)]
+# the two directions in DIFFERENT forms of nn_bwd_dir (flat scan: other cloud <= kSmallOther = 32; LDS scan: <= kTile = 1024 and
+# B <= 65535; else inverse lists, the second direction reusing the first one's workspace in stream order): small + lists,
+# scan + lists, lists + scan, small + scan and scan + scan on the kSmallOther edge, lists forced by B > 65535 + small
+BWD_SHAPES += [(2, 5, 1100), (1, 1024, 1025), (1, 1025, 1024), (3, 70, 32), (3, 70, 33), (65536, 1, 33)]
 
 
 def _backward(p1, p2, g1, g2, mode):
@@ -278,10 +285,12 @@ def test_box_point_counts(K):
 
 # ---- 6. NMS -----------------------------------------------------------------------------------------------------------------------
 NMS_IOU = 0.25
-# seeds drawn on the host until every compared overlap is >= 1e-4 from NMS_IOU.  At 1024 boxes about a million overlaps are
+# seeds drawn on the host until every compared overlap is >= 1e-4 from NMS_IOU.  From 1023 boxes about a million overlaps are
 # compared and random boxes always put one closer than that, so there the boxes are unit cubes on a lattice of step 0.35 in
 # x and z around their cluster's centre: every overlap is one of a few known values, none within 0.01 of NMS_IOU.
-NMS_SEEDS = {1: 0, 2: 0, 64: 0, 65: 0, 256: 4, 1024: 0}
+# 257: the first K on the 1024-thread template (K <= 256 takes the 256-thread one), whose rows of suppression bits have 16
+# words instead of 4; 1023: the last K below kNmsMaxK = 1024.
+NMS_SEEDS = {1: 0, 2: 0, 64: 0, 65: 0, 256: 4, 257: 4, 1023: 0, 1024: 0}
 
 
 def nms_case(K, seed):
@@ -290,7 +299,7 @@ def nms_case(K, seed):
   rng = np.random.RandomState(1000 * seed + K)
   mm = np.zeros((3, K, 6), np.float32)
   for b in range(3):
-    if K >= 1024:
+    if K >= 1023:
       n_cl = K // 6
       cl = rng.randint(0, n_cl, K)
       c = np.stack([5.0 * (cl % 16) + 0.35 * rng.randint(0, 3, K), np.zeros(K), 5.0 * (cl // 16) + 0.35 * rng.randint(0, 3, K)], 1)
@@ -326,6 +335,11 @@ def test_box_nms(K):
   from pointcontrast_amd._lib import lib, check
   (mm, score, cls, counts), want, gap = nms_expected(K, NMS_SEEDS[K])
   assert gap >= 1e-4, "an overlap %.3g from nms_iou: float32 could decide differently" % gap
+  if K == 257:
+    # scene 2 has no empty box, so its lowest-scored box holds rank 256: the first bit of the fifth word of the mask.  It is
+    # suppressed -- by a kept box of a rank below 256, since nothing else precedes it -- so the word edge is crossed
+    last = sorted(range(K), key=lambda i: (-float(score[2][i]), i))[-1]
+    assert (counts[2] >= 5).all() and all(w[2][last] == 0 for w in want.values()), "no suppression crosses rank 256"
   dmm, dscore, dcls, dcounts = _dev(mm), _dev(score), _dev(cls), _dev(counts)
   for (mode, old), w in want.items():
     assert w[1].sum() == 0 and (K < 64 or 0 < w[0].sum() < (counts[0] >= 5).sum()), "the case must suppress some boxes"

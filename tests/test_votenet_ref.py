@@ -171,3 +171,24 @@ def test_get_loss_runs_and_is_differentiable():
   assert torch.isfinite(out["loss"]) and all(ep64[k].grad is not None and torch.isfinite(ep64[k].grad).all() for k in VF.PREDICTED)
   assert out["loss"].item() == pytest.approx(10 * (out["vote_loss"] + 0.5 * out["objectness_loss"] + out["box_loss"] +
                                                    0.1 * out["sem_cls_loss"]).item())
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+def test_nn_backward_f32_is_the_float64_gradient_with_out_of_range_terms_dropped(mode):
+  rng = np.random.RandomState(5)
+  B, N, M = 3, 40, 9  # long lists: about four pc1 points per pc2 point
+  p1, p2 = rng.uniform(-2, 2, (B, N, 3)).astype(np.float32), rng.uniform(-2, 2, (B, M, 3)).astype(np.float32)
+  delta = KW[mode].get("delta", 1.0)
+  i1, i2 = R.nn_indices(p1, p2, mode, delta)
+  g1, g2 = rng.normal(0, 1, (B, N)).astype(np.float32), rng.normal(0, 1, (B, M)).astype(np.float32)
+  bad1, bad2 = i1.copy(), i2.copy()
+  bad1[0, 3], bad1[1, 7], bad2[2, 4], bad2[0, 0] = -1, M, -1, N
+  for idx1, idx2 in ((i1, i2), (bad1, bad2)):
+    ok1, ok2 = (idx1 >= 0) & (idx1 < M), (idx2 >= 0) & (idx2 < N)
+    a, b = torch.from_numpy(p1).double().requires_grad_(), torch.from_numpy(p2).double().requires_grad_()
+    e1, e2 = R.nn_distance_at(a, b, np.where(ok1, idx1, 0), np.where(ok2, idx2, 0), mode, delta)
+    torch.autograd.backward([e1, e2], [torch.from_numpy(g1 * ok1).double(), torch.from_numpy(g2 * ok2).double()])
+    ga, gb = R.nn_backward_f32(p1, p2, idx1, idx2, g1, g2, mode, delta)
+    assert ga.dtype == np.float32 and gb.dtype == np.float32
+    np.testing.assert_allclose(ga, a.grad.numpy(), rtol=0, atol=1e-5 * float(a.grad.abs().max()))
+    np.testing.assert_allclose(gb, b.grad.numpy(), rtol=0, atol=1e-5 * float(b.grad.abs().max()))

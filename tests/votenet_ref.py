@@ -80,6 +80,47 @@ def nn_distance(pc1, pc2, l1smooth=False, delta=1.0, l1=False):
   return d1, torch.from_numpy(idx1), d2, torch.from_numpy(idx2)
 
 
+def _dcomp32(x, mode, delta):
+  """The derivative of _comp32 in float32: 2 x / sign(x) / clamp(x, -delta, delta)."""
+  if mode == "l2":
+    return np.float32(2) * x
+  if mode == "l1":
+    return np.sign(x).astype(np.float32)
+  d = np.float32(delta)
+  return np.minimum(np.maximum(x, -d), d)
+
+
+def nn_backward_f32(pc1, pc2, idx1, idx2, g1, g2, mode="l2", delta=1.0):
+  """(gpc1 [B, N, 3], gpc2 [B, M, 3]) in float32 in the ORDER include/pcmi.h promises for pcmi_nn_distance_bwd: a point's own
+  term first, then the term of every point of the other cloud whose nearest neighbour it is, in ascending index of the other
+  cloud, every operation rounded on its own (g * d'(a - o), then the add).  An index outside its cloud drops its term.  What a
+  kernel that sums in another order misses by a few last bits, and a float64 comparison at 1e-4 cannot see."""
+  p1, p2 = np.asarray(pc1, np.float32), np.asarray(pc2, np.float32)
+
+  def one_cloud(a, o, idx_a, idx_o, g_a, g_o):
+    B, N, _ = a.shape
+    M = o.shape[1]
+    af, of = a.reshape(B * N, 3), o.reshape(B * M, 3)
+    ia, io = np.asarray(idx_a, np.int64).reshape(B * N), np.asarray(idx_o, np.int64).reshape(B * M)
+    ga_, go_ = np.asarray(g_a, np.float32).reshape(B * N), np.asarray(g_o, np.float32).reshape(B * M)
+    out = np.zeros((B * N, 3), np.float32)
+    rows = np.nonzero((ia >= 0) & (ia < M))[0]
+    out[rows] = out[rows] + ga_[rows, None] * _dcomp32(af[rows] - of[(rows // N) * M + ia[rows]], mode, delta)
+    src = np.nonzero((io >= 0) & (io < N))[0]  # flat positions b M + j, ascending
+    tgt = (src // M) * N + io[src]
+    order = np.argsort(tgt, kind="stable")     # grouped by target, ascending j within a target
+    src, tgt = src[order], tgt[order]
+    first = np.searchsorted(tgt, tgt, side="left")
+    rank = np.arange(len(tgt)) - first
+    for k in range(int(rank.max()) + 1 if len(rank) else 0):  # the k-th source of every target: one add each
+      s, t = src[rank == k], tgt[rank == k]
+      out[t] = out[t] + go_[s, None] * _dcomp32(af[t] - of[s], mode, delta)
+    assert out.dtype == np.float32
+    return out.reshape(B, N, 3)
+
+  return one_cloud(p1, p2, idx1, idx2, g1, g2), one_cloud(p2, p1, idx2, idx1, g2, g1)
+
+
 # ---- get_loss -----------------------------------------------------------------------------------------------------------------
 def _masked_mean(v, w):
   return (v * w).sum() / (w.sum() + 1e-6)
