@@ -593,6 +593,53 @@ int pcmi_box_nms(const float* minmax, const float* obj_prob, const int32_t* sem_
                  int min_points, int64_t B, int64_t K, int mode, int old_type, float nms_iou, int32_t* pred_mask,
                  pcmi_stream_t stream);
 
+/* ---- detection scoring (csrc/evaldet.hip) ------------------------------------------------------------------------------
+ * The last step of the detection evaluation loop (vn/lib/test.py:44,76-92): what APCalculator (vn/models/ap_helper.py:223-276)
+ * computes through eval_det_multiprocessing / eval_det_cls / voc_ap (vn/lib/utils/eval_det.py) with get_iou_obb.  Overlaps
+ * are fp32 (every operation rounded on its own, in the order of the reference's expressions), counts are integers, recall /
+ * precision / AP are fp64 on those integers.  The only atomic is an integer minimum: every output is reproducible bit for
+ * bit.  Contiguous tensors, everything on the caller's stream, no synchronisation.  A refused call enqueues nothing.
+ *
+ * pcmi_box3d_iou = box3d_iou (vn/lib/utils/box_util.py:92-117, called per box pair at eval_det.py:136): corners1 [n, 8, 3],
+ *   corners2 [m, 8, 3] in get_3d_box's corner order (what pcmi_box_decode writes) -> iou3d [n, m] and, if not NULL, iou2d
+ *   [n, m].  The bird's-eye-view rectangles are corners 3, 2, 1, 0 as (x, z); rect1 is clipped by the edges of rect2 with the
+ *   reference's Sutherland-Hodgman walk (same vertex order, same strict inside test, same intersection formula) after both
+ *   are moved so that corner 3 of box 1 is the origin (absolute coordinates would cancel in fp32); the area of the result is
+ *   its shoelace sum (= the reference's hull area, the polygon being convex).  Vertical overlap max(0, min(c1[0].y, c2[0].y)
+ *   - max(c1[4].y, c2[4].y)); volumes |c0 c1| |c1 c2| |c0 c4| (box3d_vol).  Rectangles that are disjoint or merely touch give
+ *   exactly 0 (the reference's clipping returns None).  One thread per pair, the polygons (at most 8 vertices) in registers.
+ * pcmi_det_match = the inner loop of eval_det_cls (eval_det.py:126-139) for a whole batch and every class at once: per
+ *   scene, pred_corners [B, K, 8, 3] against gt_corners [B, G, 8, 3] with gt_cls [B, G] (int32) and gt_mask [B, G] (int32,
+ *   0: no box; a class outside [0, Cls) is no box either).  best_iou [B, K, Cls] = the largest overlap of box k with the
+ *   scene's boxes of class c, best_gt [B, K, Cls] (int32) = its index, the LOWEST among equal overlaps (the reference's strict
+ *   >); -inf and -1 where the scene has no box of the class.  Neither the confidence order nor the threshold enters, so one
+ *   match serves every threshold; entry [b, k, c] serves per_class_proposal (all Cls entries of a box) and the plain mode
+ *   (entry sem_cls[b, k] only).  The [K, G] overlaps of a scene are computed once (tiles of 32 boxes in LDS) and reduced per
+ *   class.  K <= 1024 (as pcmi_box_nms) and G <= 256: PCMI_ERR_UNSUPPORTED beyond; B <= 65535.
+ * pcmi_det_ap = eval_det.py:142-159 and voc_ap (:24-55) for Cls classes and n_thresholds <= 16 thresholds from one match.
+ *   The nd detections are listed class by class, in descending confidence within a class: class c holds the positions
+ *   [cls_offs[c], cls_offs[c + 1]) (device int32 [Cls + 1]; positions outside every range are ignored).  best_iou [nd] and
+ *   gt_id [nd] (int32: the detection's best box as an index into the n_gt ground-truth boxes of the whole evaluation, -1 for
+ *   none) come from pcmi_det_match; npos [Cls] (device int32) counts the ground-truth boxes of a class.  thresholds is a HOST
+ *   array.  Per threshold t: a detection with (double)best_iou > t bids its position for its box (integer atomic min); the
+ *   winner is the true positive, every other detection a false positive.  Then inclusive counts, rec = tp / npos, prec =
+ *   tp / max(tp + fp, 2^-52), the precision envelope (running maximum from the end) and ap = the sum over the detections
+ *   where recall changes of (rec_i - rec_{i-1}) envelope_i, or with use_07_metric != 0 the 11-point form: sum over k = 0..10
+ *   of (the largest prec where rec >= k * 0.1, else 0) / 11.  ap [T, Cls], last_rec [T, Cls] (rec of the class's last
+ *   detection; 0 for a class without detections, whose ap is 0 too); a class without ground truth has rec = 0 / 0 = NaN and
+ *   ap NaN (0 in the 11-point form), as the reference.  Optional (nullable) rec / prec (double) and tp_flag (int32), each
+ *   [T, nd] in the list's order.  One workgroup per (class, threshold) walks its detections in blocks of 1024 with a carry, so
+ *   a class may hold any number of them.  ws: pcmi_det_ap_workspace_bytes(nd, n_gt, n_thresholds). */
+int pcmi_box3d_iou(const float* corners1, const float* corners2, int64_t n, int64_t m, float* iou3d, float* iou2d,
+                   pcmi_stream_t stream);
+int pcmi_det_match(const float* pred_corners, const float* gt_corners, const int32_t* gt_cls, const int32_t* gt_mask,
+                   int64_t B, int64_t K, int64_t G, int Cls, int32_t* best_gt, float* best_iou, pcmi_stream_t stream);
+size_t pcmi_det_ap_workspace_bytes(int64_t nd, int64_t n_gt, int n_thresholds);
+int pcmi_det_ap(const float* best_iou, const int32_t* gt_id, const int32_t* cls_offs, const int32_t* npos, int64_t nd,
+                int64_t n_gt, int Cls, const double* thresholds, int n_thresholds, int use_07_metric, double* ap,
+                double* last_rec, double* rec, double* prec, int32_t* tp_flag, void* ws, size_t ws_bytes,
+                pcmi_stream_t stream);
+
 /* Softmax cross-entropy over the rows of logits [n, c] with an ignore label -- the loss of the downstream semantic
  * segmentation fine-tuning that reuses this backbone with out_channels = number of classes
  * (downstream/semseg/lib/train.py:64,124: nn.CrossEntropyLoss(ignore_index=config.ignore_label)).

@@ -173,6 +173,11 @@ PROTOTYPES = {
     "pcmi_box_decode": (C.c_int, [c_vp] * 8 + [c_i64, c_i64, C.c_int, C.c_int, C.c_int, C.c_int] + [c_vp] * 8 + [c_vp]),
     "pcmi_box_point_counts": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "pcmi_box_nms": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, C.c_int, C.c_int, c_f32, c_vp, c_vp]),
+    "pcmi_box3d_iou": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pcmi_det_match": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_vp, c_vp, c_vp]),
+    "pcmi_det_ap_workspace_bytes": (c_sz, [c_i64, c_i64, C.c_int]),
+    "pcmi_det_ap": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, c_vp, c_vp,
+                              c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -280,3 +280,219 @@ def parse_groundtruths(end_points, config_dict):
     batch_gt_map_cls.append(cur)
   end_points["batch_gt_map_cls"] = batch_gt_map_cls
   return batch_gt_map_cls
+
+
+# ---- the scoring ----------------------------------------------------------------------------------------------------
+def ground_truth_boxes(end_points, config_dict, heading=None):
+  """The device half of parse_groundtruths: (corners float32 [B, K2, 8, 3] in upright-camera coordinates and get_3d_box's
+  corner order, class int64 [B, K2], mask bool [B, K2]) from the label tensors, with decode_predictions' heading modes.  The
+  corners are computed in float64, as parse_groundtruths does on the host, and rounded once.  A handful of torch ops on
+  [B, K2] tensors; nothing is read back."""
+  dc = config_dict["dataset_config"]
+  if heading is None:
+    heading = heading_mode(dc)
+  if heading not in ("bins", "zero"):
+    raise ValueError('heading must be "bins" or "zero", got %r' % (heading,))
+  center = end_points["center_label"]
+  PF.require_cuda(center, "ground_truth_boxes")
+  dev = center.device
+  c = center[:, :, 0:3].detach().double()
+  cx, cy, cz = c[..., 0], -c[..., 2], c[..., 1]
+  size_class = end_points["size_class_label"].long()
+  size = (_mean_size(dc, dev)[size_class] + end_points["size_residual_label"].detach().float()).double()  # class2size's float32 sum
+  if heading == "zero":
+    angle = torch.zeros_like(cx)
+  else:
+    angle = end_points["heading_class_label"].double() * (2 * math.pi / float(dc.num_heading_bin)) + \
+        end_points["heading_residual_label"].detach().double()
+    angle = torch.where(angle > math.pi, angle - 2 * math.pi, angle)
+  sign = _constant("corner_signs", dev, lambda: torch.tensor([[1, 1, -1, -1, 1, 1, -1, -1], [1, 1, 1, 1, -1, -1, -1, -1],
+                                                              [1, -1, -1, 1, 1, -1, -1, 1]], dtype=torch.float64))
+  x = sign[0] * (size[..., 0:1] / 2)
+  y = sign[1] * (size[..., 2:3] / 2)
+  z = sign[2] * (size[..., 1:2] / 2)
+  co, si = torch.cos(angle)[..., None], torch.sin(angle)[..., None]
+  corners = torch.stack([co * x + si * z + cx[..., None], y + cy[..., None], -si * x + co * z + cz[..., None]], dim=-1)
+  return corners.float(), end_points["sem_cls_label"].long(), end_points["box_label_mask"] == 1
+
+
+class APCalculator(object):
+  """APCalculator of the reference (models/ap_helper.py:223-276) on the device: the oriented overlaps, the matching and the
+  precision / recall curves are libpcmi's (pcmi_det_match, pcmi_det_ap); the confidence ordering is a stable torch.sort.
+
+  step() takes the host lists of parse_predictions / parse_groundtruths, step_decoded() the device tensors of
+  decode_predictions and the labels; both run the match at once and keep device records, and only compute_metrics() reads
+  anything back.  ap_iou_thresh may be a sequence: compute_metrics() then returns {threshold: dict}, all scored from the one
+  match.  Differences from the reference: equal confidences keep accumulation order; overlaps are float32; a class with
+  ground truth and no prediction scores AP 0 and recall 0 (eval_det raises KeyError, eval_det_multiprocessing misaligns the
+  classes); corners must be in get_3d_box's order."""
+
+  def __init__(self, ap_iou_thresh=0.25, class2type_map=None, device=None):
+    self.ap_iou_thresh = ap_iou_thresh
+    self.class2type_map = class2type_map
+    self.device = None if device is None else torch.device(device)  # None: the current device at the first use
+    self.reset()
+
+  def reset(self):
+    self._dense = {}    # class id -> dense index, in order of first appearance
+    self._records = []  # (score float64 [n], dense class int64 [n], gt id int64 [n], overlap float32 [n])
+    self._npos = []     # int64 [dense classes at the time]
+    self._n_gt = 0      # ground-truth slots handed out so far
+    self.scan_cnt = 0
+
+  def _device(self):
+    if self.device is None:
+      self.device = torch.device("cuda", torch.cuda.current_device())
+    return self.device
+
+  # -- accumulation --
+  def _register(self, ids):
+    for i in ids:
+      if i not in self._dense:
+        self._dense[i] = len(self._dense)
+
+  def _append(self, score, cls, best_gt, best_iou, gt_base, gt_cls, gt_mask, n_slots):
+    """best_gt / best_iou [n]: the match entry of every detection; gt_base [n]: the first slot of its scene's boxes."""
+    gid = torch.where(best_gt >= 0, best_gt.long() + gt_base, torch.full_like(gt_base, -1))
+    self._records.append((score, cls, gid, best_iou))
+    n_cls = len(self._dense)
+    hit = (gt_cls.reshape(-1, 1) == torch.arange(n_cls, device=gt_cls.device)) & gt_mask.reshape(-1, 1)
+    self._npos.append(hit.sum(0))
+    self._n_gt += n_slots
+
+  def step(self, batch_pred_map_cls, batch_gt_map_cls):
+    """Accumulates one batch: lists over the scenes of (class, corners [8, 3], score) and of (class, corners [8, 3]).  One
+    upload of the padded arrays, one match.  A scene with more than 1024 detections is matched in rows of 1024."""
+    bsize = len(batch_pred_map_cls)
+    assert bsize == len(batch_gt_map_cls)
+    self.scan_cnt += bsize
+    self._register(c for scene in batch_pred_map_cls for c, _, _ in scene)
+    self._register(c for scene in batch_gt_map_cls for c, _ in scene)
+    if not self._dense:
+      return
+    G = max(max((len(s) for s in batch_gt_map_cls), default=0), 1)
+    KM = PF.DET_MATCH_MAX_K
+    rows = []  # (scene, first detection, detections)
+    for i, scene in enumerate(batch_pred_map_cls):
+      for s in range(0, len(scene), KM):
+        rows.append((i, s, min(KM, len(scene) - s)))
+    gt_c = np.zeros((bsize, G, 8, 3), np.float32)
+    gt_k = np.zeros((bsize, G), np.int64)
+    gt_m = np.zeros((bsize, G), bool)
+    for i, scene in enumerate(batch_gt_map_cls):
+      for j, (c, box) in enumerate(scene):
+        gt_c[i, j], gt_k[i, j], gt_m[i, j] = box, self._dense[c], True
+    K = max(max((r[2] for r in rows), default=0), 1)
+    R = max(len(rows), 1)
+    pr_c = np.zeros((R, K, 8, 3), np.float32)
+    row_scene = np.zeros(R, np.int64)
+    n_det = sum(r[2] for r in rows)
+    score, cls, at_row, at_k = np.zeros(n_det, np.float64), np.zeros(n_det, np.int64), np.zeros(n_det, np.int64), np.zeros(n_det, np.int64)
+    o = 0
+    for r, (i, s, n) in enumerate(rows):
+      row_scene[r] = i
+      for k in range(n):
+        c, box, sc = batch_pred_map_cls[i][s + k]
+        pr_c[r, k] = box
+        score[o], cls[o], at_row[o], at_k[o] = sc, self._dense[c], r, k
+        o += 1
+    dev = self._device()
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    gt_cls, gt_mask, rs = up(gt_k), up(gt_m), up(row_scene)
+    best_gt, best_iou = PF.det_match(up(pr_c), up(gt_c)[rs], gt_cls[rs], gt_mask[rs], len(self._dense))
+    cls_d, row_d, k_d = up(cls), up(at_row), up(at_k)
+    self._append(up(score), cls_d, best_gt[row_d, k_d, cls_d], best_iou[row_d, k_d, cls_d], self._n_gt + rs[row_d] * G,
+                 gt_cls, gt_mask, bsize * G)
+
+  def step_decoded(self, decoded, end_points, config_dict, heading=None):
+    """Accumulates one batch from decode_predictions' dict and the label tensors: pred_mask, conf_thresh and
+    per_class_proposal are applied on the device (a box that is not kept stays in the record as a detection of no class),
+    the match runs at once.  No device-to-host copy and no synchronisation."""
+    dc = config_dict["dataset_config"]
+    num_class = int(dc.num_class)
+    corners, obj_prob = decoded["corners"], decoded["obj_prob"]
+    B, K = obj_prob.shape
+    dev = obj_prob.device
+    self.scan_cnt += B
+    self._register(range(num_class))
+    ids = tuple(self._dense[c] for c in range(num_class))
+    lut = _constant(("dense_classes", ids), dev, lambda: torch.tensor(ids, dtype=torch.int64))
+    gt_corners, gt_cls, gt_mask = ground_truth_boxes(end_points, config_dict, heading)
+    gt_mask = gt_mask & (gt_cls >= 0) & (gt_cls < num_class)
+    gt_cls = lut[gt_cls.clamp(0, num_class - 1)]
+    G = gt_cls.shape[1]
+    best_gt, best_iou = PF.det_match(corners, gt_corners, gt_cls, gt_mask, len(self._dense))
+    keep = obj_prob > config_dict["conf_thresh"]
+    if decoded.get("pred_mask") is not None:
+      keep = keep & (decoded["pred_mask"] == 1)
+    if config_dict["per_class_proposal"]:
+      score = (decoded["sem_cls_probs"] * obj_prob.unsqueeze(-1)).double()  # the float32 product, as parse_predictions
+      cls = lut.expand(B, K, num_class)
+      keep = keep.unsqueeze(-1).expand(B, K, num_class)
+      pick = cls
+    else:
+      score = obj_prob.double()
+      cls = lut[decoded["sem_cls"].long()]
+      pick = cls.unsqueeze(-1)
+    bg = torch.gather(best_gt, 2, pick).reshape(B, K, -1)
+    bo = torch.gather(best_iou, 2, pick).reshape(B, K, -1)
+    cls = torch.where(keep, cls, torch.full_like(cls, _NO_CLASS)).reshape(B, K, -1)
+    bg = torch.where(keep.reshape(B, K, -1), bg, torch.full_like(bg, -1))
+    base = (self._n_gt + torch.arange(B, device=dev) * G).reshape(B, 1, 1).expand_as(bg)
+    self._append(score.reshape(-1), cls.reshape(-1), bg.reshape(-1), bo.reshape(-1), base.reshape(-1), gt_cls, gt_mask, B * G)
+
+  # -- scoring --
+  def evaluate(self, thresholds=None, use_07_metric=False, curves=False):
+    """Scores what has been accumulated: a dict with class_ids (the original ids in dense order), and device tensors ap /
+    last_rec [T, classes], nd / npos [classes] and, with curves, rec / prec / tp [T, nd] with order (the detection of every
+    position, as an index into the accumulation order) and cls_offs.  No synchronisation."""
+    if thresholds is None:
+      thresholds = self._thresholds()
+    n_cls = max(len(self._dense), 1)
+    dev = self._device()
+    if self._records:
+      score, cls, gid, iou = (torch.cat([r[k] for r in self._records]) for k in range(4))
+      npos = torch.stack([F.pad(n, (0, n_cls - n.shape[0])) for n in self._npos]).sum(0)
+    else:
+      score, cls, gid = torch.zeros(0, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), \
+          torch.zeros(0, dtype=torch.int64, device=dev)
+      iou, npos = torch.zeros(0, dtype=torch.float32, device=dev), torch.zeros(n_cls, dtype=torch.int64, device=dev)
+    # descending confidence, then class: both sorts are stable, so equal confidences keep accumulation order
+    by_score = torch.sort(score, descending=True, stable=True)[1]
+    cls_sorted, by_cls = torch.sort(cls[by_score], stable=True)
+    order = by_score[by_cls]
+    offs = torch.searchsorted(cls_sorted, torch.arange(n_cls + 1, device=cls.device))
+    out = PF.det_ap(iou[order], gid[order], offs, npos, self._n_gt, list(thresholds), use_07_metric, curves)
+    out.update(class_ids=sorted(self._dense, key=self._dense.get), nd=offs[1:] - offs[:-1], npos=npos, order=order, cls_offs=offs)
+    return out
+
+  def _thresholds(self):
+    t = self.ap_iou_thresh
+    return [float(x) for x in t] if isinstance(t, (list, tuple, np.ndarray)) else [float(t)]
+
+  def compute_metrics(self):
+    """The reference's dict -- '<name> Average Precision', 'mAP', '<name> Recall', 'AR' over the classes that have a
+    detection or a ground-truth box -- or, for a sequence of thresholds, {threshold: dict}.  The one read-back."""
+    thr = self._thresholds()
+    res = self.evaluate(thr)
+    host = torch.cat([res["ap"].reshape(-1), res["last_rec"].reshape(-1), res["nd"].double(), res["npos"].double()]).cpu().numpy()
+    n_cls, T = res["npos"].shape[0], len(thr)
+    ap, rec = host[:T * n_cls].reshape(T, n_cls), host[T * n_cls:2 * T * n_cls].reshape(T, n_cls)
+    nd, npos = host[2 * T * n_cls:2 * T * n_cls + n_cls], host[2 * T * n_cls + n_cls:]
+    seen = [(cid, d) for d, cid in enumerate(res["class_ids"]) if nd[d] > 0 or npos[d] > 0]
+    seen.sort(key=lambda e: e[0])
+    out = {}
+    for t in range(T):
+      ret = {}
+      name = lambda cid: self.class2type_map[cid] if self.class2type_map else str(cid)  # noqa: E731
+      for cid, d in seen:
+        ret["%s Average Precision" % name(cid)] = ap[t, d]
+      ret["mAP"] = np.mean([ap[t, d] for _, d in seen]) if seen else float("nan")
+      for cid, d in seen:
+        ret["%s Recall" % name(cid)] = rec[t, d]
+      ret["AR"] = np.mean([rec[t, d] for _, d in seen]) if seen else float("nan")
+      out[thr[t]] = ret
+    return out if isinstance(self.ap_iou_thresh, (list, tuple, np.ndarray)) else out[thr[0]]
+
+
+_NO_CLASS = 1 << 30  # the class of a detection that was not kept: sorted behind every class, scored by none

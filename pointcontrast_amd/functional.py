@@ -886,3 +886,66 @@ def box_decode(center, heading_scores, heading_residuals, size_scores, size_resi
   return dict(heading_class=heading_class, size_class=size_class, sem_cls=sem_cls, box_params=params, corners=corners, minmax=minmax,
               obj_prob=obj_prob, sem_cls_probs=sem_probs, counts=counts, pred_mask=pred_mask if nms is not None else None,
               packed=packed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Detection scoring (csrc/evaldet.hip): box3d_iou of downstream/votenet_det_new/lib/utils/box_util.py and eval_det_cls /
+# voc_ap of lib/utils/eval_det.py.
+# ---------------------------------------------------------------------------------------------------------------------
+DET_MATCH_MAX_K = 1024  # kMatchMaxK / kMatchMaxG of evaldet.hip
+DET_MATCH_MAX_G = 256
+DET_AP_MAX_THRESHOLDS = 16
+
+
+def box3d_iou(corners1, corners2, with_2d=True):
+  """corners1 [n, 8, 3], corners2 [m, 8, 3] in get_3d_box's corner order -> (iou3d [n, m], iou2d [n, m] or None): the oriented
+  overlap of every pair (pcmi_box3d_iou), float32, one launch."""
+  a, b = _f32c(corners1, "box3d_iou"), _f32c(corners2, "box3d_iou")
+  assert a.dim() == 3 and b.dim() == 3 and a.shape[1:] == (8, 3) and b.shape[1:] == (8, 3), "box3d_iou: corners [n, 8, 3] and [m, 8, 3]"
+  n, m = a.shape[0], b.shape[0]
+  iou3d = torch.empty((n, m), dtype=torch.float32, device=a.device)
+  iou2d = torch.empty((n, m), dtype=torch.float32, device=a.device) if with_2d else None
+  check(lib.pcmi_box3d_iou(ptr(a), ptr(b), n, m, ptr(iou3d), ptr(iou2d), cur_stream(a.device)))
+  return iou3d, iou2d
+
+
+def det_match(pred_corners, gt_corners, gt_cls, gt_mask, num_class):
+  """pred_corners [B, K, 8, 3], gt_corners [B, G, 8, 3], gt_cls [B, G], gt_mask [B, G] (nonzero: a box) -> (best_gt int32
+  [B, K, num_class], best_iou float32 [B, K, num_class]): per predicted box and class the scene's ground-truth box of that
+  class it overlaps most (the lowest index of equal overlaps; -1 / -inf without one).  pcmi_det_match, one launch."""
+  p, g = _f32c(pred_corners, "det_match"), _f32c(gt_corners, "det_match")
+  assert p.dim() == 4 and g.dim() == 4 and p.shape[2:] == (8, 3) and g.shape[2:] == (8, 3) and p.shape[0] == g.shape[0], \
+      "det_match: pred_corners [B, K, 8, 3], gt_corners [B, G, 8, 3]"
+  B, K, G = p.shape[0], p.shape[1], g.shape[1]
+  assert gt_cls.shape == (B, G) and gt_mask.shape == (B, G), "det_match: gt_cls / gt_mask [B, G]"
+  cls = _i32c(gt_cls, p.device)
+  mask = (gt_mask.to(p.device) != 0).to(torch.int32).contiguous()
+  best_gt = torch.empty((B, K, int(num_class)), dtype=torch.int32, device=p.device)
+  best_iou = torch.empty((B, K, int(num_class)), dtype=torch.float32, device=p.device)
+  check(lib.pcmi_det_match(ptr(p), ptr(g), ptr(cls), ptr(mask), B, K, G, int(num_class), ptr(best_gt), ptr(best_iou),
+                           cur_stream(p.device)))
+  return best_gt, best_iou
+
+
+def det_ap(best_iou, gt_id, cls_offs, npos, n_gt, thresholds, use_07_metric=False, curves=False):
+  """pcmi_det_ap.  best_iou float32 [nd] / gt_id int32 [nd]: the detections class by class in descending confidence, class c at
+  [cls_offs[c], cls_offs[c + 1]) (int32 [Cls + 1]); npos int32 [Cls]; n_gt: ground-truth boxes gt_id indexes; thresholds: a
+  sequence of floats (host).  Returns a dict of device tensors: ap, last_rec (float64 [T, Cls]) and, with curves, rec, prec
+  (float64 [T, nd]) and tp (int32 [T, nd]).  No host synchronisation."""
+  iou = _f32c(best_iou, "det_ap").reshape(-1)
+  dev = iou.device
+  gid, offs, np_ = _i32c(gt_id, dev).reshape(-1), _i32c(cls_offs, dev), _i32c(npos, dev)
+  nd, Cls, T = iou.shape[0], np_.shape[0], len(thresholds)
+  assert gid.shape[0] == nd and offs.shape == (Cls + 1,), "det_ap: gt_id [nd], cls_offs [Cls + 1], npos [Cls]"
+  thr = (C.c_double * max(T, 1))(*[float(t) for t in thresholds])
+  ap = torch.empty((T, Cls), dtype=torch.float64, device=dev)
+  last_rec = torch.empty((T, Cls), dtype=torch.float64, device=dev)
+  rec = prec = tp = None
+  if curves:
+    rec = torch.empty((T, nd), dtype=torch.float64, device=dev)
+    prec = torch.empty((T, nd), dtype=torch.float64, device=dev)
+    tp = torch.empty((T, nd), dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_det_ap_workspace_bytes(nd, int(n_gt), T), dev)
+  check(lib.pcmi_det_ap(ptr(iou), ptr(gid), ptr(offs), ptr(np_), nd, int(n_gt), Cls, thr, T, int(bool(use_07_metric)), ptr(ap),
+                        ptr(last_rec), ptr(rec), ptr(prec), ptr(tp), ws, wsb, cur_stream(dev)))
+  return dict(ap=ap, last_rec=last_rec, rec=rec, prec=prec, tp=tp)
