@@ -653,6 +653,46 @@ int pcmi_softmax_ce_bwd(const float* logits, int64_t ld, int64_t n, int c, const
                         int ignore_label, const float* out2, const float* gloss, float* dlogits,
                         int64_t d_ld, pcmi_stream_t stream);
 
+/* ---- segmentation validation (csrc/segeval.hip) -----------------------------------------------------------------------
+ * What the validation loop of the segmentation fine-tuning (downstream/semseg/lib/test.py:62-196) computes per batch on the
+ * host, with nothing read back.  1 <= c <= 64 classes (the workgroup's private confusion matrix is 16 KB of LDS at 64):
+ * PCMI_ERR_INVALID beyond; n < 2^31 - 256.  Everything on the caller's stream, no synchronisation; a refused call enqueues
+ * nothing.  The only atomics are integer adds and every float64 sum has a fixed order: all outputs are reproducible bit for
+ * bit.
+ *
+ * pcmi_seg_eval_rows = lib/test.py:119,137-140,143 with precision_at_one and fast_hist of lib/utils.py:117-133, one pass over
+ *   logits [n, c] (fp32 rows with leading dimension ld >= c, so a column slice of a wider buffer) and labels [n] (int32):
+ *   pred [n] (int32) = the arg-max of the row (get_prediction), the LOWEST class among equal logits.
+ *   prob_t [c, n] (nullable) = softmax of the row, CLASS-major -- the layout the per-class sort reads contiguously.  exp and the
+ *     quotient are fp32, the row's sum of exponentials is fp64 over the classes in ascending order: a row's probabilities
+ *     depend on that row's logits only (equal rows give bit-equal probabilities, wherever they stand).
+ *   hist [c, c] (int64) += the confusion matrix: a row counts iff 0 <= label < c, at hist[label, pred] (fast_hist).
+ *   batch4 [4] (fp64) = sum of logsumexp(x) - x[label] over the counted rows (label != ignore_label), their number, the
+ *     number of those with pred == label, and n.  A label that is neither a class nor ignore_label makes the sum NaN, as
+ *     pcmi_softmax_ce_fwd.  Workgroup partials merged in workgroup order by the last workgroup to arrive.
+ *   totals3 [3] (fp64, nullable) += n * sum / counted, n * (100 * correct / counted), n: the two AverageMeters of
+ *     lib/test.py:138-139 (weighted by num_sample = n, ignored rows included) and their common count.  A batch without a
+ *     counted row adds nothing to any of the three (the reference's meters would turn NaN for good).
+ *   n == 0 enqueues nothing and leaves every output as it is.  ws: pcmi_seg_eval_rows_workspace_bytes(n), 8-byte aligned.
+ * pcmi_seg_ap = average_precision(prob, target) of lib/test.py:55-59,144 (label_binarize + sklearn's
+ *   average_precision_score(average=None)) for every class of one batch.  sorted_prob [c, n] (fp32) = every class's scores in
+ *   descending order and order [c, n] (int64) = the row of each sorted element -- what torch.sort(prob_t, 1, descending=True)
+ *   returns; labels [n] (int32).  For class k the positives are the rows with label == k; every other row, ignored and
+ *   out-of-range labels included, is a negative (label_binarize gives it a zero row).  With tp = the positives among the
+ *   first `rank` elements, at the LAST element of every run of equal scores: P = tp / rank, R = tp / npos, and
+ *   ap [k] = sum (R - R_prev) P in fp64.  The order inside a run of equal scores does not matter (the sort need not be stable).
+ *   A class without a positive row gets NaN (the reference's scikit-learn; np.nanmean(aps, 0) of lib/test.py:149 relies on
+ *   it).  ap_sum [c] (fp64) += ap and ap_cnt [c] (int64) += 1 where ap is not NaN (both nullable): nanmean's numerator and
+ *   denominator.  One workgroup per class walks its list in blocks of 4096 with a carry, so n may be anything; n == 0 gives
+ *   NaN everywhere.  ws: pcmi_seg_ap_workspace_bytes(c) (the positives per class), 4-byte aligned. */
+size_t pcmi_seg_eval_rows_workspace_bytes(int64_t n);
+int pcmi_seg_eval_rows(const float* logits, int64_t ld, int64_t n, int c, const int32_t* labels, int ignore_label,
+                       int32_t* pred, float* prob_t, int64_t* hist, double* batch4, double* totals3, void* ws,
+                       size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_seg_ap_workspace_bytes(int c);
+int pcmi_seg_ap(const float* sorted_prob, const int64_t* order, const int32_t* labels, int64_t n, int c, double* ap,
+                double* ap_sum, int64_t* ap_cnt, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+
 int pcmi_sgd_step(float* w, const float* g, float* v, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, pcmi_stream_t stream);
 /* The same with torch's dampening (the downstream fine-tuning's optimiser: SGD(lr, sgd_momentum, dampening =

@@ -178,6 +178,10 @@ PROTOTYPES = {
     "pcmi_det_ap_workspace_bytes": (c_sz, [c_i64, c_i64, C.c_int]),
     "pcmi_det_ap": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, c_vp, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_seg_eval_rows_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_seg_eval_rows": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_seg_ap_workspace_bytes": (c_sz, [C.c_int]),
+    "pcmi_seg_ap": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -8,9 +8,13 @@ What the reference's downstream/semseg does per iteration (downstream/semseg/lib
   loss       nn.CrossEntropyLoss(ignore_index=ignore_label) on model(x).F (train.py:64,124) -> pcmi_softmax_ce_fwd/bwd
   optimiser  SGD(lr, sgd_momentum, dampening, weight_decay) + PolyLR (lib/solvers.py:27-31,50-59,75-76) -> FlatSGD + PolyLR
   metrics    precision_at_one (lib/utils.py:117-128), fast_hist / per_class_iu -> mIoU (:131-138)
-Datasets, augmentation, validation loop, tensorboard and checkpoint bookkeeping of the downstream trainer are outside
-the hot path and not provided.
+  validation test() of lib/test.py:62-196 per batch -- loss, precision@1, confusion matrix, per-class average precision ->
+             SegmentationEvaluator (pcmi_seg_eval_rows, pcmi_seg_ap), SegmentationTrainer.validate
+Datasets, augmentation, the transfer of predictions onto the original point cloud, tensorboard and checkpoint bookkeeping
+of the downstream trainer are outside the hot path and not provided.
 """
+import warnings
+
 import numpy as np
 import torch
 from torch.optim.lr_scheduler import LambdaLR
@@ -56,6 +60,68 @@ def per_class_iu(hist):
   """Intersection over union per class; mIoU = nanmean (lib/utils.py:136-138)."""
   with np.errstate(divide="ignore", invalid="ignore"):
     return np.diag(hist) / (hist.sum(1) + hist.sum(0) - np.diag(hist))
+
+
+class SegmentationEvaluator:
+  """The accumulators of the reference's validation loop (test() of downstream/semseg/lib/test.py:62-196) on the device.
+
+  step(logits, target) adds one batch: cross-entropy and precision@1 into the two AverageMeters (weighted by the number of
+  rows, ignored ones included), fast_hist into the confusion matrix (pcmi_seg_eval_rows), and the per-class average precision
+  of the softmax scores into nanmean's sum and count (torch.sort per class + pcmi_seg_ap).  Nothing is read back until
+  compute_metrics().  Differences from the reference: arg-max ties go to the lowest class; a class without
+  a positive row in a batch scores NaN there whatever scikit-learn is installed; a batch without a counted row adds nothing
+  to the loss and score averages; the ranking uses float32 probabilities."""
+
+  def __init__(self, num_labels, ignore_label=255, device=None):
+    self.num_labels, self.ignore_label = int(num_labels), int(ignore_label)
+    self.device = None if device is None else torch.device(device)  # None: the current device at the first use
+    self.reset()
+
+  def reset(self):
+    self.hist = self.totals = self.ap_sum = self.ap_cnt = None
+    self.batches = 0
+
+  def _state(self):
+    if self.hist is None:
+      if self.device is None:
+        self.device = torch.device("cuda", torch.cuda.current_device())
+      c, dev = self.num_labels, self.device
+      self.hist = torch.zeros((c, c), dtype=torch.int64, device=dev)
+      self.totals = torch.zeros(3, dtype=torch.float64, device=dev)  # sum n loss, sum n score, sum n
+      self.ap_sum = torch.zeros(c, dtype=torch.float64, device=dev)
+      self.ap_cnt = torch.zeros(c, dtype=torch.int64, device=dev)
+
+  def step(self, logits, target):
+    """logits [n, num_labels] on the device, target [n] (a host tensor or array is copied once).  No synchronisation."""
+    assert logits.dim() == 2 and logits.shape[1] == self.num_labels, "logits [n, num_labels]"
+    if logits.shape[0] == 0:
+      return
+    self._state()
+    tgt = torch.as_tensor(target).reshape(-1).to(device=self.device, dtype=torch.int32)
+    out = PF.seg_eval_rows(logits, tgt, self.ignore_label, hist=self.hist, totals=self.totals)
+    PF.seg_average_precision(out["prob_t"], tgt, self.ap_sum, self.ap_cnt)
+    self.batches += 1
+
+  def compute_metrics(self):
+    """One read-back.  loss / score: the AverageMeters' averages; ious, acc, ap_class (per class, in %), their nanmeans mIoU,
+    mAcc, mAP, and hist -- the values test() logs and returns."""
+    c = self.num_labels
+    if self.hist is None:
+      flat = np.zeros(3 + 2 * c + c * c)
+    else:  # (every count is far below 2^53: float64 carries it exactly)
+      flat = torch.cat([self.totals, self.ap_sum, self.ap_cnt.double(), self.hist.reshape(-1).double()]).cpu().numpy()
+    totals, ap_sum, ap_cnt = flat[:3], flat[3:3 + c], flat[3 + c:3 + 2 * c]
+    hist = np.rint(flat[3 + 2 * c:]).astype(np.int64).reshape(c, c)
+    ious = per_class_iu(hist) * 100.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+      acc = np.diag(hist) / hist.sum(1) * 100.0
+      ap_class = ap_sum / ap_cnt * 100.0
+    with warnings.catch_warnings():  # a class that never occurred: nanmean of nothing but NaN
+      warnings.simplefilter("ignore", category=RuntimeWarning)
+      means = dict(mIoU=float(np.nanmean(ious)), mAP=float(np.nanmean(ap_class)), mAcc=float(np.nanmean(acc)))
+    n = totals[2]
+    return dict(loss=float(totals[0] / n) if n > 0 else 0.0, score=float(totals[1] / n) if n > 0 else 0.0, ious=ious,
+                ap_class=ap_class, acc=acc, hist=hist, **means)
 
 
 class SegmentationTrainer:
@@ -113,3 +179,15 @@ class SegmentationTrainer:
     hist = fast_hist(pred, np.asarray(target), self.num_labels)
     ious = per_class_iu(hist) * 100.0
     return float(np.nanmean(ious)), ious, hist
+
+  @torch.no_grad()
+  def validate(self, batches):
+    """test() of downstream/semseg/lib/test.py:62-196 over an iterable of (coords, feats, target): eval mode, one forward
+    and one SegmentationEvaluator.step per batch, one read-back at the end.  Returns the reference's (loss average, score
+    average, mAP, mIoU); the evaluator with every other metric stays on self.evaluator."""
+    self.model.eval()
+    self.evaluator = SegmentationEvaluator(self.num_labels, self.ignore_label, self.device)
+    for coords, feats, target in batches:
+      self.evaluator.step(self.forward(coords, feats, training=False), target)
+    m = self.evaluator.compute_metrics()
+    return m["loss"], m["score"], m["mAP"], m["mIoU"]

@@ -949,3 +949,68 @@ def det_ap(best_iou, gt_id, cls_offs, npos, n_gt, thresholds, use_07_metric=Fals
   check(lib.pcmi_det_ap(ptr(iou), ptr(gid), ptr(offs), ptr(np_), nd, int(n_gt), Cls, thr, T, int(bool(use_07_metric)), ptr(ap),
                         ptr(last_rec), ptr(rec), ptr(prec), ptr(tp), ws, wsb, cur_stream(dev)))
   return dict(ap=ap, last_rec=last_rec, rec=rec, prec=prec, tp=tp)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Segmentation validation (csrc/segeval.hip): the per-batch work of downstream/semseg/lib/test.py:119,137-145.
+# ---------------------------------------------------------------------------------------------------------------------
+SEG_EVAL_MAX_CLASSES = 64  # kMaxClasses of segeval.hip
+
+
+def seg_eval_rows(logits, target, ignore_label, hist=None, want_prob=True, totals=None):
+  """pcmi_seg_eval_rows.  logits float32 [n, c] (rows may be a column slice), target [n] -> a dict of device tensors: pred
+  int32 [n] (arg-max, the lowest class of equal logits), prob_t float32 [c, n] (class-major softmax; None without want_prob),
+  hist int64 [c, c] (the confusion matrix ADDED to the one passed in, a fresh one otherwise) and batch float64 [4] = (sum of the
+  counted rows' losses, counted rows, correct among them, n).  totals float64 [3] (optional) accumulates the reference's two
+  AverageMeters and their count.  No host synchronisation."""
+  require_cuda(logits, "seg_eval_rows")
+  x = logits if (logits.stride(1) == 1 and logits.dtype == torch.float32) else logits.float().contiguous()
+  assert x.dim() == 2 and x.shape[1] >= 1, "seg_eval_rows: logits [n, c]"
+  n, c = x.shape
+  dev = x.device
+  lb = _i32c(target, dev).reshape(-1)
+  assert lb.shape[0] == n, "seg_eval_rows: target [n]"
+  if hist is None:
+    hist = torch.zeros((c, c), dtype=torch.int64, device=dev)
+  assert hist.shape == (c, c) and hist.dtype == torch.int64 and hist.is_contiguous() and hist.device == dev, \
+      "seg_eval_rows: hist int64 [c, c] on the logits' device"
+  assert totals is None or (totals.shape == (3,) and totals.dtype == torch.float64 and totals.device == dev), \
+      "seg_eval_rows: totals float64 [3] on the logits' device"
+  pred = torch.empty(n, dtype=torch.int32, device=dev)
+  prob_t = torch.empty((c, n), dtype=torch.float32, device=dev) if want_prob else None
+  batch = torch.zeros(4, dtype=torch.float64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_seg_eval_rows_workspace_bytes(n), dev)
+  check(lib.pcmi_seg_eval_rows(ptr(x), x.stride(0) if n else c, n, c, ptr(lb), int(ignore_label), ptr(pred), ptr(prob_t), ptr(hist),
+                               ptr(batch), ptr(totals), ws, wsb, cur_stream(dev)))
+  return dict(pred=pred, prob_t=prob_t, hist=hist, batch=batch)
+
+
+def seg_average_precision(prob_t, target, ap_sum=None, ap_cnt=None):
+  """average_precision(prob, target) of downstream/semseg/lib/test.py:55-59 for class-major scores prob_t float32 [c, n] and
+  target [n]: a torch.sort per class on the device, then pcmi_seg_ap.  Returns ap float64 [c] on the device (NaN for a class
+  without a positive row); ap_sum float64 [c] / ap_cnt int64 [c] (optional) accumulate the values that are not NaN.  No host
+  synchronisation."""
+  p = _f32c(prob_t, "seg_average_precision")
+  assert p.dim() == 2, "seg_average_precision: prob_t [c, n]"
+  c, n = p.shape
+  dev = p.device
+  lb = _i32c(target, dev).reshape(-1)
+  assert lb.shape[0] == n, "seg_average_precision: target [n]"
+  assert ap_sum is None or (ap_sum.shape == (c,) and ap_sum.dtype == torch.float64 and ap_sum.device == dev), "ap_sum float64 [c]"
+  assert ap_cnt is None or (ap_cnt.shape == (c,) and ap_cnt.dtype == torch.int64 and ap_cnt.device == dev), "ap_cnt int64 [c]"
+  sorted_prob, order = torch.sort(p, dim=1, descending=True)
+  return seg_ap_sorted(sorted_prob, order, lb, ap_sum, ap_cnt)
+
+
+def seg_ap_sorted(sorted_prob, order, target, ap_sum=None, ap_cnt=None):
+  """pcmi_seg_ap on scores that are sorted already: sorted_prob float32 [c, n] descending along n, order int64 [c, n] the row
+  of each sorted element, target int32 [n]."""
+  s, o = _f32c(sorted_prob, "seg_ap"), order.to(torch.int64).contiguous()
+  c, n = s.shape
+  dev = s.device
+  lb = _i32c(target, dev).reshape(-1)
+  assert o.shape == (c, n) and o.device == dev and lb.shape[0] == n, "seg_ap: sorted_prob / order [c, n], target [n]"
+  ap = torch.empty(c, dtype=torch.float64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_seg_ap_workspace_bytes(c), dev)
+  check(lib.pcmi_seg_ap(ptr(s), ptr(o), ptr(lb), n, c, ptr(ap), ptr(ap_sum), ptr(ap_cnt), ws, wsb, cur_stream(dev)))
+  return ap
