@@ -693,6 +693,57 @@ size_t pcmi_seg_ap_workspace_bytes(int c);
 int pcmi_seg_ap(const float* sorted_prob, const int64_t* order, const int32_t* labels, int64_t n, int c, double* ap,
                 double* ap_sum, int64_t* ap_cnt, void* ws, size_t ws_bytes, pcmi_stream_t stream);
 
+/* ---- evaluation on the original point cloud (csrc/nearest.hip) ----------------------------------------------------------
+ * What the segmentation test loop does after the forward pass to score the ORIGINAL vertices of a scan (downstream/semseg/
+ * lib/test.py:85-93,122-123,190-192): save_predictions (lib/utils.py:304-344) writes the voxel centres in world coordinates
+ * with their predictions, dataset.test_pointcloud (lib/datasets/scannet.py:131-171, stanford.py:41-72) builds a scipy KD-tree
+ * over them per room, queries it for every vertex and accumulates fast_hist on the host.  Here: three calls, float64
+ * throughout, every product and sum rounded on its own in the stated order (no FMA contraction), integer atomics only -- every
+ * output is defined by the formulas below bit for bit.  Contiguous tensors, everything on the caller's stream, no
+ * synchronisation; a refused call enqueues nothing.
+ *
+ * pcmi_voxel_centers = lib/utils.py:322-327: coords [n, 4] (int32, batch index FIRST: b, x, y, z), inv_T_host = B x 16 HOST
+ *   doubles, the row-major inverse of each scene's voxelizer matrix (rigid_transformation; the caller inverts it) -> centers
+ *   [n, 3] (fp64) = inv_T[b] (x + 0.5, y + 0.5, z + 0.5, 1): per output coordinate ((X m0 + Y m1) + Z m2) + m3, the order
+ *   csrc/corpus.hip documents.  Whether a row's batch index lies in [0, B) cannot be known without reading the coordinates
+ *   back: such a row gets NaN in all three columns and the call succeeds.  The matrices travel as kernel arguments, 32 scenes
+ *   per launch.  n < 2^31 - 256; n == 0 enqueues nothing.
+ * pcmi_nearest_point = KDTree(pred[:, :3], leafsize=500).query(query_xyz) (scannet.py:154-155), for a batch of scenes: ref
+ *   [m, 3] and query [n, 3] (fp64), scene b holding the rows [ref_offs[b], ref_offs[b + 1]) and [query_offs[b],
+ *   query_offs[b + 1]) (DEVICE int64 [B + 1], ascending; ref_offs is clamped to [0, m]).  A query searches the references of
+ *   its own scene only.  idx [n] (int32) = the GLOBAL row of ref that minimises d2 = (dx dx + dy dy) + dz dz with d = q - r,
+ *   every operation rounded in fp64, the LOWEST row among equal d2 (a KD-tree's choice among them is arbitrary); dist2 [n]
+ *   (fp64, nullable) = that d2.  This rule defines the result for every input: it equals a brute-force scan.
+ *     - a scene without references, or a query row outside [query_offs[0], query_offs[B]): idx -1, dist2 +inf
+ *     - a query row with a non-finite coordinate: idx -1, dist2 NaN
+ *     - a reference row with a non-finite coordinate is never chosen (a scene of nothing else: idx -1, dist2 +inf)
+ *   The references are binned into cubic cells of side `cell` (open-addressing table keyed by scene and cell, records of a
+ *   cell contiguous); one lane per query walks the Chebyshev rings around its cell and stops once its best d2 is strictly
+ *   below (r cell)^2 (1 - 2^-30), a bound no reference outside the searched cube can reach (justified in the source).
+ *   Queries undecided after radius 3 are listed, and a second launch scans their scene's whole segment, one workgroup per
+ *   query, with a min-reduction on (d2, row).  The grid only accelerates: neither `cell` nor the ring cap changes an output.
+ *   A cell index needs |floor(x / cell)| < 2^17 - 8 per axis.  A finite reference outside that range is not binned, and EVERY
+ *   query of its scene takes the whole-segment scan; so does a query whose own cell is outside it: slower, never different.
+ *   cell > 0 and finite (PCMI_ERR_INVALID otherwise), unless cell_dev (nullable, DEVICE double [1]) is given, which then
+ *   replaces it -- a cell size derived from the data on the device, without reading it back; a cell_dev value that is not
+ *   positive and finite sends every query to the scan.  fallback_count [1] (device int64, nullable) += the queries the second
+ *   launch scanned.  1 <= B <= 1024; n < 2^31; m <= 2^29 (PCMI_ERR_UNSUPPORTED beyond: the table has 2 m slots).  n == 0
+ *   enqueues nothing.  ws: pcmi_nearest_point_workspace_bytes(m, n, B), 16-byte aligned.
+ * pcmi_seg_hist = fast_hist(pred[idx], label) of scannet.py:156,168 (lib/utils.py:131-133): pred [m] (int32), idx [n] (int32,
+ *   NULL = identity), labels [n] (int32), 1 <= c <= 64 as pcmi_seg_eval_rows (the same workgroup-private matrix in LDS, flushed
+ *   with integer atomics).  hist [c, c] (int64) += 1 at [label, pred[idx]] for the rows with 0 <= label < c, 0 <= idx < m and
+ *   0 <= pred[idx] < c.  point_pred [n] (int32, nullable) = pred[idx], -1 where idx is outside [0, m) -- the per-vertex labels
+ *   the reference writes to <room>.txt; missing [1] (int64, nullable) += the rows with idx outside [0, m).  n == 0 enqueues
+ *   nothing. */
+int pcmi_voxel_centers(const int32_t* coords, int64_t n, const double* inv_T_host, int64_t B, double* centers,
+                       pcmi_stream_t stream);
+size_t pcmi_nearest_point_workspace_bytes(int64_t m, int64_t n, int64_t B);
+int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, const double* query, const int64_t* query_offs,
+                       int64_t n, int64_t B, double cell, const double* cell_dev, int32_t* idx, double* dist2,
+                       int64_t* fallback_count, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_seg_hist(const int32_t* pred, int64_t m, const int32_t* idx, const int32_t* labels, int64_t n, int c, int64_t* hist,
+                  int32_t* point_pred, int64_t* missing, pcmi_stream_t stream);
+
 int pcmi_sgd_step(float* w, const float* g, float* v, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, pcmi_stream_t stream);
 /* The same with torch's dampening (the downstream fine-tuning's optimiser: SGD(lr, sgd_momentum, dampening =

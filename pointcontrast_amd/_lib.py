@@ -182,6 +182,11 @@ PROTOTYPES = {
     "pcmi_seg_eval_rows": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_seg_ap_workspace_bytes": (c_sz, [C.c_int]),
     "pcmi_seg_ap": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_voxel_centers": (C.c_int, [c_vp, c_i64, C.POINTER(C.c_double), c_i64, c_vp, c_vp]),
+    "pcmi_nearest_point_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pcmi_nearest_point": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                     c_vp]),
+    "pcmi_seg_hist": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -10,8 +10,12 @@ What the reference's downstream/semseg does per iteration (downstream/semseg/lib
   metrics    precision_at_one (lib/utils.py:117-128), fast_hist / per_class_iu -> mIoU (:131-138)
   validation test() of lib/test.py:62-196 per batch -- loss, precision@1, confusion matrix, per-class average precision ->
              SegmentationEvaluator (pcmi_seg_eval_rows, pcmi_seg_ap), SegmentationTrainer.validate
-Datasets, augmentation, the transfer of predictions onto the original point cloud, tensorboard and checkpoint bookkeeping
-of the downstream trainer are outside the hot path and not provided.
+  full eval  save_predictions + dataset.test_pointcloud (lib/utils.py:304-344, lib/datasets/scannet.py:131-171): the voxel
+             predictions carried onto the ORIGINAL vertices of the scan through the nearest voxel centre, and their mIoU ->
+             PointCloudEvaluator (pcmi_voxel_centers, pcmi_nearest_point, pcmi_seg_hist),
+             SegmentationTrainer.test_original_pointcloud
+Datasets, augmentation, PLY / txt files and colour maps, tensorboard and checkpoint bookkeeping of the downstream trainer are
+outside the hot path and not provided.
 """
 import warnings
 
@@ -124,6 +128,96 @@ class SegmentationEvaluator:
                 ap_class=ap_class, acc=acc, hist=hist, **means)
 
 
+class PointCloudEvaluator:
+  """mIoU on the ORIGINAL point cloud, on the device: what the reference does between save_predictions (downstream/semseg/
+  lib/utils.py:304-344) and dataset.test_pointcloud (lib/datasets/scannet.py:131-171, stanford.py:41-72) through .npy files,
+  a scipy KD-tree per room and fast_hist on the host.
+
+  step(coords, pred, transformation, points, point_labels, point_offsets) adds one batch of scenes -- or one PIECE of them:
+  a room that was evaluated in pieces (the Stanford rooms) is scored by one call per piece, each with the vertices that belong
+  to the piece, or by one call with the pieces' voxels concatenated into one segment.  Nothing is read back until
+  compute_metrics().  Differences from the reference: equidistant voxel centres go to the lowest row (the
+  KD-tree's choice is arbitrary), a scene without voxels and a vertex with a non-finite coordinate get the prediction -1 and
+  are counted in `missing` instead of raising."""
+
+  def __init__(self, num_labels, ignore_label=255, label_map=None, device=None):
+    self.num_labels, self.ignore_label = int(num_labels), int(ignore_label)
+    self.device = None if device is None else torch.device(device)  # None: the current device at the first use
+    # label_map: raw dataset id -> class (a dict, or a sequence indexed by the raw id); ids it does not contain -> ignore_label
+    self._lut_host = None
+    if label_map is not None:
+      if isinstance(label_map, dict):
+        lut = np.full(max([int(k) for k in label_map] + [0]) + 1, self.ignore_label, dtype=np.int64)
+        for k, v in label_map.items():
+          if int(k) >= 0:
+            lut[int(k)] = int(v)
+      else:
+        lut = np.asarray(label_map, dtype=np.int64).reshape(-1)
+      self._lut_host = lut
+    self._lut = None
+    self.reset()
+
+  def reset(self):
+    self.hist = self.missing = None
+    self.batches = 0
+
+  def _state(self):
+    if self.device is None:
+      self.device = torch.device("cuda", torch.cuda.current_device())
+    if self.hist is None:
+      self.hist = torch.zeros((self.num_labels, self.num_labels), dtype=torch.int64, device=self.device)
+      self.missing = torch.zeros(1, dtype=torch.int64, device=self.device)
+    if self._lut is None and self._lut_host is not None:
+      self._lut = torch.from_numpy(self._lut_host).to(self.device)
+
+  def map_labels(self, raw):
+    """Raw dataset labels -> classes through label_map (a device gather); ignored rows become -1, which no class equals."""
+    lb = torch.as_tensor(np.asarray(raw) if not torch.is_tensor(raw) else raw).reshape(-1).to(self.device).long()
+    if self._lut is not None:
+      inside = (lb >= 0) & (lb < self._lut.shape[0])
+      lb = torch.where(inside, self._lut[lb.clamp(0, self._lut.shape[0] - 1)], torch.full_like(lb, self.ignore_label))
+    return torch.where(lb == self.ignore_label, torch.full_like(lb, -1), lb).to(torch.int32)
+
+  def step(self, coords, pred, transformation, points, point_labels, point_offsets):
+    """coords int32 [nv, 4] (b, x, y, z) and pred [nv] (the voxels' predicted classes) on the device; transformation [B, 16]:
+    the voxelizer matrices as the loader returns them (host); points float64 [n, 3]: the original vertices, scene b at rows
+    [point_offsets[b], point_offsets[b + 1]); point_labels [n]: raw dataset labels.  Returns the predicted class per vertex
+    (int32 [n] on the device, -1 where there is none) -- what the reference writes to <room>.txt.  No synchronisation."""
+    self._state()
+    dev = self.device
+    T = np.asarray(transformation.cpu() if torch.is_tensor(transformation) else transformation, dtype=np.float64)
+    T = T[:, :16] if T.ndim == 2 else T.reshape(-1, 16)
+    B = T.shape[0]
+    c = torch.as_tensor(coords).to(dev).to(torch.int32)
+    # the voxels scene by scene (a stable sort by batch index: rows of a scene keep their order), and the scenes' offsets
+    order = torch.sort(c[:, 0], stable=True)[1]
+    c, vp = c[order].contiguous(), torch.as_tensor(pred).reshape(-1).to(dev).to(torch.int32)[order]
+    ref_offs = torch.searchsorted(c[:, 0].contiguous(), torch.arange(B + 1, dtype=torch.int32, device=dev)).to(torch.int64)
+    centers = PF.voxel_centers(c, T)
+    # two voxels: the world-space voxel edge is the length of a column of the inverse's linear part (host arithmetic)
+    edge = float(max(np.linalg.norm(np.linalg.inv(T.reshape(-1, 4, 4))[:, :3, 0], axis=1).max(), 0.0))
+    cell = 2.0 * edge if np.isfinite(edge) and edge > 0 else None
+    pts = torch.as_tensor(points)
+    assert pts.dtype == torch.float64, "points: float64 [n, 3] (the original vertices, unrounded)"
+    idx = PF.nearest_point(centers, ref_offs, pts.to(dev), point_offsets, cell=cell)
+    out = PF.seg_hist(vp, idx, self.map_labels(point_labels), self.num_labels, hist=self.hist, missing=self.missing)
+    self.batches += 1
+    return out["point_pred"]
+
+  def compute_metrics(self):
+    """One read-back.  ious and acc per class in %, their nanmeans mIoU and mAcc (scannet.py:169-170), hist, and missing: the
+    vertices that received no prediction."""
+    c = self.num_labels
+    flat = np.zeros(c * c + 1, dtype=np.int64) if self.hist is None else torch.cat([self.hist.reshape(-1), self.missing]).cpu().numpy()
+    hist = flat[:c * c].reshape(c, c)
+    ious = per_class_iu(hist) * 100.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+      acc = np.diag(hist) / hist.sum(1) * 100.0
+    with warnings.catch_warnings():  # a class that never occurred: nanmean of nothing but NaN
+      warnings.simplefilter("ignore", category=RuntimeWarning)
+      return dict(ious=ious, mIoU=float(np.nanmean(ious)), acc=acc, mAcc=float(np.nanmean(acc)), hist=hist, missing=int(flat[-1]))
+
+
 class SegmentationTrainer:
   """One process per GPU; `train_iter(coords, feats, target)` = forward, cross-entropy, backward, SGD + PolyLR step."""
 
@@ -191,3 +285,27 @@ class SegmentationTrainer:
       self.evaluator.step(self.forward(coords, feats, training=False), target)
     m = self.evaluator.compute_metrics()
     return m["loss"], m["score"], m["mAP"], m["mIoU"]
+
+  @torch.no_grad()
+  def test_original_pointcloud(self, batches, label_map=None):
+    """The full-resolution evaluation of downstream/semseg/lib/test.py:85-93,122-123,190-192 over an iterable of (coords,
+    feats, transformation, points, point_labels): eval mode, one forward per batch, the voxels' arg-max carried onto the
+    original vertices by PointCloudEvaluator.step, one read-back at the end.  points / point_labels: one array per scene of the
+    batch (a list), or a single array for a batch of one scene.  Returns (mIoU, ious); the evaluator stays on
+    self.pointcloud_evaluator and the per-vertex predictions of every batch (device tensors) on self.pointcloud_predictions."""
+    self.model.eval()
+    self.pointcloud_evaluator = PointCloudEvaluator(self.num_labels, self.ignore_label, label_map, self.device)
+    self.pointcloud_predictions = []
+    for coords, feats, transformation, points, point_labels in batches:
+      if isinstance(points, (list, tuple)):
+        sizes = [len(p) for p in points]
+        points = torch.cat([torch.as_tensor(p).reshape(-1, 3) for p in points])
+        point_labels = torch.cat([torch.as_tensor(np.asarray(l)).reshape(-1) for l in point_labels])
+      else:
+        sizes = [len(points)]
+      offsets = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64)
+      pred = self.forward(coords, feats, training=False).max(1)[1]
+      self.pointcloud_predictions.append(
+          self.pointcloud_evaluator.step(coords, pred, transformation, points, point_labels, offsets))
+    m = self.pointcloud_evaluator.compute_metrics()
+    return m["mIoU"], m["ious"]

@@ -1014,3 +1014,103 @@ def seg_ap_sorted(sorted_prob, order, target, ap_sum=None, ap_cnt=None):
   ws, wsb = ws_args(lib.pcmi_seg_ap_workspace_bytes(c), dev)
   check(lib.pcmi_seg_ap(ptr(s), ptr(o), ptr(lb), n, c, ptr(ap), ptr(ap_sum), ptr(ap_cnt), ws, wsb, cur_stream(dev)))
   return ap
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Evaluation on the original point cloud (csrc/nearest.hip): save_predictions + dataset.test_pointcloud of the reference
+# (downstream/semseg/lib/utils.py:304-344, lib/datasets/scannet.py:131-171).  None of these is differentiable.
+# ---------------------------------------------------------------------------------------------------------------------
+def _f64c(t, device, who):
+  t = torch.as_tensor(t)
+  assert t.dtype == torch.float64, "%s: float64 (the evaluation geometry is not rounded to float32)" % who
+  return t.to(device).contiguous()
+
+
+def _offsets(offsets, device):
+  return torch.as_tensor(offsets).to(device=device, dtype=torch.int64).contiguous()
+
+
+def voxel_centers(coords, transformation):
+  """pcmi_voxel_centers.  coords int32 [n, 4] on the device in (b, x, y, z) order; transformation: the [B, 16] (or [B, 4, 4])
+  voxelizer matrices as the loader returns them, on the HOST -- each is inverted here in float64 (np.linalg.inv,
+  lib/utils.py:325-327).  Returns centers float64 [n, 3] = inv(T[b]) (x + 0.5, y + 0.5, z + 0.5, 1); a row whose batch index is
+  outside [0, B) is NaN.  No synchronisation."""
+  import numpy as np
+  require_cuda(coords, "voxel_centers")
+  assert coords.dim() == 2 and coords.shape[1] == 4, "voxel_centers: coords [n, 4]"
+  c = coords.to(torch.int32).contiguous()
+  T = np.asarray(transformation.cpu() if torch.is_tensor(transformation) else transformation, dtype=np.float64)
+  T = (T[:, :16] if T.ndim == 2 else T.reshape(-1, 16)).reshape(-1, 4, 4)  # (transformation[i, :16], lib/utils.py:325)
+  inv = np.ascontiguousarray(np.linalg.inv(T)).reshape(-1)
+  B = T.shape[0]
+  assert B >= 1, "voxel_centers: at least one transformation"
+  out = torch.empty((c.shape[0], 3), dtype=torch.float64, device=c.device)
+  check(lib.pcmi_voxel_centers(ptr(c), c.shape[0], inv.ctypes.data_as(C.POINTER(C.c_double)), B, ptr(out), cur_stream(c.device)))
+  return out
+
+
+def default_cell(ref, n_scenes):
+  """The cell size nearest_point uses when it is given none, as a device tensor float64 [1] (nothing is read back): twice the
+  spacing of m / B points spread over a square of the references' largest extent L -- 2 L / sqrt(m / B).  Voxel centres of
+  a scan lie on surfaces, for which this is about two voxels; at least L 2^-15, so that every cell index fits the grid key.
+  It is a guess that only costs time: the result does not depend on the cell size."""
+  m = ref.shape[0]
+  if m == 0:
+    return torch.ones(1, dtype=torch.float64, device=ref.device)
+  r = torch.nan_to_num(ref, nan=0.0, posinf=0.0, neginf=0.0)
+  L = (r.amax(0) - r.amin(0)).amax()
+  cell = torch.clamp(2.0 * L / (max(m / max(int(n_scenes), 1), 1.0) ** 0.5), min=L * 2.0 ** -15)
+  return torch.where(cell > 0, cell, torch.ones_like(cell)).reshape(1)
+
+
+def nearest_point(ref, ref_offsets, query, query_offsets, cell=None, return_dist2=False, fallback_count=None):
+  """pcmi_nearest_point: the exact nearest reference row of every query row, scene by scene.  ref float64 [m, 3] with
+  ref_offsets [B + 1], query float64 [n, 3] with query_offsets [B + 1] (ascending row offsets of the scenes).  Returns idx
+  int32 [n], the GLOBAL row of ref minimising (dx dx + dy dy) + dz dz in float64, the lowest row among equal distances; -1 for
+  a scene without references and for a non-finite query row; with return_dist2 also dist2 float64 [n] (+inf / NaN there).
+  cell: the side of the binning cells -- 2 x voxel_size for voxel centres; None: default_cell(ref, B), computed on the
+  device.  It changes the time only, never the result.  fallback_count int64 [1] (optional) += the queries that needed the
+  whole-segment scan.  No host synchronisation."""
+  require_cuda(query, "nearest_point")
+  dev = query.device
+  q, r = _f64c(query, dev, "nearest_point"), _f64c(ref, dev, "nearest_point")
+  ro, qo = _offsets(ref_offsets, dev), _offsets(query_offsets, dev)
+  assert q.dim() == 2 and q.shape[1] == 3 and r.dim() == 2 and r.shape[1] == 3, "nearest_point: ref [m, 3], query [n, 3]"
+  assert ro.dim() == 1 and ro.shape == qo.shape and ro.shape[0] >= 2, "nearest_point: offsets [B + 1]"
+  m, n, B = r.shape[0], q.shape[0], ro.shape[0] - 1
+  cell_dev = None
+  if cell is None:
+    cell_dev, cell = default_cell(r, B), 0.0
+  elif torch.is_tensor(cell):
+    cell_dev, cell = cell.to(device=dev, dtype=torch.float64).reshape(1).contiguous(), 0.0
+  assert fallback_count is None or (fallback_count.dtype == torch.int64 and fallback_count.numel() == 1 and
+                                    fallback_count.device == dev), "nearest_point: fallback_count int64 [1]"
+  idx = torch.empty(n, dtype=torch.int32, device=dev)
+  dist2 = torch.empty(n, dtype=torch.float64, device=dev) if return_dist2 else None
+  ws, wsb = ws_args(lib.pcmi_nearest_point_workspace_bytes(m, n, B), dev)
+  check(lib.pcmi_nearest_point(ptr(r), ptr(ro), m, ptr(q), ptr(qo), n, B, float(cell), ptr(cell_dev), ptr(idx), ptr(dist2),
+                               ptr(fallback_count), ws, wsb, cur_stream(dev)))
+  return (idx, dist2) if return_dist2 else idx
+
+
+def seg_hist(pred, idx, labels, num_labels, hist=None, missing=None, want_point_pred=True):
+  """pcmi_seg_hist: fast_hist(pred[idx], labels) on the device.  pred [m], idx int32 [n] (None: identity), labels [n] -> a dict
+  of device tensors: hist int64 [c, c] (ADDED to the one passed in, a fresh one otherwise) counting the rows with 0 <= label
+  < c, 0 <= idx < m and 0 <= pred[idx] < c at [label, pred[idx]]; point_pred int32 [n] = pred[idx], -1 where idx is outside
+  [0, m) (None without want_point_pred); missing int64 [1] += the number of such rows.  No host synchronisation."""
+  require_cuda(pred, "seg_hist")
+  dev = pred.device
+  p, lb = _i32c(pred, dev).reshape(-1), _i32c(labels, dev).reshape(-1)
+  ix = None if idx is None else _i32c(idx, dev).reshape(-1)
+  m, n, c = p.shape[0], lb.shape[0], int(num_labels)
+  assert ix is None or ix.shape[0] == n, "seg_hist: idx [n], labels [n]"
+  if hist is None:
+    hist = torch.zeros((c, c), dtype=torch.int64, device=dev)
+  assert hist.shape == (c, c) and hist.dtype == torch.int64 and hist.is_contiguous() and hist.device == dev, \
+      "seg_hist: hist int64 [c, c] on pred's device"
+  if missing is None:
+    missing = torch.zeros(1, dtype=torch.int64, device=dev)
+  assert missing.dtype == torch.int64 and missing.numel() == 1 and missing.device == dev, "seg_hist: missing int64 [1]"
+  point_pred = torch.empty(n, dtype=torch.int32, device=dev) if want_point_pred else None
+  check(lib.pcmi_seg_hist(ptr(p), m, ptr(ix), ptr(lb), n, c, ptr(hist), ptr(point_pred), ptr(missing), cur_stream(dev)))
+  return dict(hist=hist, point_pred=point_pred, missing=missing)
