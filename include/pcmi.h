@@ -744,6 +744,101 @@ int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, co
 int pcmi_seg_hist(const int32_t* pred, int64_t m, const int32_t* idx, const int32_t* labels, int64_t n, int c, int64_t* hist,
                   int32_t* point_pred, int64_t* missing, pcmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The input of segmentation fine-tuning for a batch of scans (csrc/semseg_input.hip) -- what the reference runs per scan on
+ * the host in downstream/semseg/lib/dataset.py:289-298: Voxelizer.voxelize (lib/voxelizer.py:81-148) with
+ * ME.utils.sparse_quantize(coords, feats, labels, ignore_label), then RandomHorizontalFlip, ChromaticAutoContrast,
+ * ChromaticTranslation and ChromaticJitter (lib/transforms.py), feats / 255 - 0.5 (lib/train.py:114-115) and the label map
+ * (dataset.py:297-298).  Every random quantity is an INPUT.  Scene b of B holds the rows [offsets[b], offsets[b + 1]) (DEVICE
+ * int64 [B + 1], ascending, empty scenes allowed; a row outside [offsets[0], offsets[B]) belongs to no scene and is dropped).
+ * 1 <= B <= 1023, row counts < 2^31 - 256.  fp64 arithmetic, every product and sum rounded on its own in the stated order (no
+ * FMA contraction); integer atomics only; the same bits from run to run.  Contiguous tensors, everything on the caller's
+ * stream, no synchronisation; a refused call enqueues nothing.  Data-dependent errors are ORed into flags [B] (device int32,
+ * one word per scene, zeroed by the CALLER so that the calls of a batch share it):
+ *   PCMI_SEG_FLAG_RANGE  a point of the scene is not finite, or a voxel coordinate is not inside +-2^20 (pcmi_seg_transform)
+ *   PCMI_SEG_FLAG_SPAN   a voxel coordinate minus the scene's minimum is outside [0, 2^18)           (pcmi_seg_quantize)
+ *   PCMI_SEG_FLAG_ELASTIC a scene's noise grid does not fit the capacity block; the scene is not distorted  (pcmi_elastic_blur)
+ * The offending rows are dropped.
+ *
+ * pcmi_seg_transform = voxelizer.py:81-142.  xyz [n, 3] (fp64); mats [B, 16] (DEVICE fp64, row-major 4 x 4: M_r M_v, or M_v
+ *   alone without augmentation, voxelizer.py:128-132; the caller builds it).  Clip (voxelizer.py:81-111), if clip_mode != 0,
+ *   per scene from the bounding box (mn, mx) of its finite points: size = mx - mn; center = (mn + size 0.5) + ratio size with
+ *   ratio = trans_ratio [B, 3] (DEVICE fp64, NULL = 0).  clip_mode 1 (numeric bound L = clip_host[0]): nothing is clipped if
+ *   max(size) < L, else a point is kept iff -L + center <= p < L + center on every axis; clip_mode 2 (clip_host = 6 HOST
+ *   doubles, (lo, hi) per axis): kept iff lo + center <= p < hi + center.  A kept point gets
+ *   vox [n, 3] (int32) = floor(((x m0 + y m1) + z m2) + m3) per matrix row, keep [n] (uint8) = 1; every other row vox 0,
+ *   keep 0.  scene_min [B, 3] (int32) = the minimum of vox over the scene's kept rows, 0 for a scene without one (the
+ *   reference raises there); aligned [B, 16] (fp64) = M_t M with M_t the translation by -scene_min (voxelizer.py:138-141):
+ *   aligned[r][c] = M[r][c] + (-min_r) M[3][c] for r < 3, row 3 copied.  ws: pcmi_seg_transform_workspace_bytes(B), 16-byte
+ *   aligned.
+ * pcmi_seg_quantize = ME.utils.sparse_quantize(coords - min, feats, labels, ignore_label) for the whole batch (the label rule
+ *   as MinkowskiEngine 0.4.3 implements it).  vox [n, 3] (int32), keep [n] (uint8, NULL = all), labels [n] (int32, nullable
+ *   together with out_labels), scene_min [B, 3] (NULL = 0).  Two kept rows of a scene are the same voxel iff their vox are
+ *   equal (open-addressing table keyed by common.h's pack_key(scene, x - min, y - min, z - min), 2 n slots).  A voxel is
+ *   represented by its FIRST row, the lowest; its label is that row's label if every row of the voxel carries the same one,
+ *   else ignore_label.  The M voxels leave in ascending order of their first row -- scenes in order, and within a scene the
+ *   order of first occurrence (the reference's order is that of a hash-map walk and unspecified): coords [M, 4] (int32; b,
+ *   x - min_x, y - min_y, z - min_z), index [M] (int64, the first row), out_labels [M] (int32); the three arrays hold n rows.
+ *   counts [B + 1] (DEVICE int64) = the voxels per scene, then M.  n <= 2^29 (PCMI_ERR_UNSUPPORTED beyond).  n == 0 zeroes
+ *   counts.  ws: pcmi_seg_quantize_workspace_bytes(n), 16-byte aligned.
+ * pcmi_seg_color_augment: one pass over the m voxel rows.  coords [m, 4] (int32, in place; the scene is column 0, a row
+ *   whose scene is outside [0, B) is not augmented), source colours feats_src [n_src, 3] (fp32) read at index [m] (int64,
+ *   NULL = the row itself; a row outside [0, n_src) reads 0), labels [m] (int32, nullable, in place), params [B, 12] (DEVICE
+ *   fp64, NULL = no augmentation): flip x, y, z (non-zero = on) | auto-contrast on, blend | translation on, tr r, g, b |
+ *   jitter on, std 255 | unused.  In the reference's order (the input_transform of lib/datasets/scannet.py), per channel in fp64 on
+ *   f = the fp32 colour widened:
+ *     flip      coords[a] = max_a - coords[a], max_a over the scene's rows                            (transforms.py:173-179)
+ *     contrast  (lo, hi) = the channel's extremes over the scene's rows; if hi > lo: scale = 255 / (hi - lo),
+ *               f = (1 - blend) f + blend ((f - lo) scale); a channel with hi == lo is left as it is (the reference
+ *               divides by zero there)                                                                 (transforms.py:45-61)
+ *     translate f = min(max(tr + f, 0), 255)                                                          (transforms.py:32-36)
+ *     jitter    f = min(max(normal (std 255) + f, 0), 255), normals [m, 3] (fp32, widened; NULL = off) (transforms.py:69-74)
+ *     normalize != 0: f = f / 255 - 0.5                                                                (train.py:114-115)
+ *   feats_out [m, 3] (fp32) = f rounded once.  lut [lut_n] (int32, nullable): labels = lut[label] for 0 <= label < lut_n,
+ *   ignore_label otherwise (dataset.py:249-259,297-298).  m == 0 enqueues nothing.
+ *   ws: pcmi_seg_color_augment_workspace_bytes(B), 16-byte aligned.
+ * pcmi_elastic_blur + pcmi_elastic_apply = ONE (granularity g, magnitude) stage of ElasticDistortion (transforms.py:187-217) for
+ *   the batch, on the raw points before pcmi_seg_transform; the caller chains the stages, and the second reads the extents the
+ *   first left in xyz.  noise [B, cx, cy, cz, 3] (fp32, standard normals, changed in place): scene b's volume [dx, dy, dz, 3]
+ *   sits in the corner of its capacity block and is addressed with the capacity strides; 3 <= cx, cy, cz <= 4096 and
+ *   B cx cy cz 3 < 2^31.  blur: per scene (mn, mx) = the box of its finite points, grid_min [B, 3] (fp64) = mn, dims =
+ *   ((mx - mn) // g) + 3 with numpy's floor division of doubles (the quotient of a - fmod(a, g), floored, plus 1 if it lies more
+ *   than 0.5 above its floor); grid_dims [B, 4] (int32) = dx, dy, dz, on.  on = 1 iff active[b] != 0 (DEVICE int32 [B], NULL =
+ *   all), the scene has a finite point and dims <= capacity on every axis; an active scene that does not fit gets
+ *   PCMI_SEG_FLAG_ELASTIC (its dims are written as 0) and is left undistorted.  Then two rounds of a 3-tap box filter along
+ *   x, y, z with zero padding at the DIMS: out = fp32(((v[i-1] w + v[i] w) + v[i+1] w)) in fp64 with w = fp32(1/3) widened, one
+ *   rounding per pass.  Elements outside the dims and the volumes of scenes that are not on keep their values.
+ *   ws: pcmi_elastic_blur_workspace_bytes(B, cx, cy, cz), 16-byte aligned.
+ *   apply: for every row of a scene that is on, per axis the nodes of np.linspace(start, stop, d): start = mn - g, stop = mn +
+ *   g (d - 2), step = (stop - start) / (d - 1), node_i = i step + start, node_{d-1} = stop.  A coordinate outside [start, stop]
+ *   (or NaN) on any axis adds 0.  Else the interval k with node_k <= p < node_{k+1} (p == stop: k = d - 2, scipy's rule), t = (p -
+ *   node_k) / (node_{k+1} - node_k), and value = the sum over the 8 corners -- x slowest, the low node first -- of noise[corner]
+ *   ((wx wy) wz) with w = 1 - t at the low node and t at the high one, accumulated from 0 in that order; xyz [n, 3] (fp64, in
+ *   place) = p + value magnitude. */
+#define PCMI_SEG_FLAG_RANGE 1
+#define PCMI_SEG_FLAG_SPAN 2
+#define PCMI_SEG_FLAG_ELASTIC 4
+size_t pcmi_elastic_blur_workspace_bytes(int64_t B, int cx, int cy, int cz);
+int pcmi_elastic_blur(const double* xyz, const int64_t* offsets, int64_t n, int64_t B, double granularity, const int32_t* active,
+                      float* noise, int cx, int cy, int cz, int32_t* grid_dims, double* grid_min, int32_t* flags, void* ws,
+                      size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_elastic_apply(double* xyz, const int64_t* offsets, int64_t n, int64_t B, double granularity, double magnitude,
+                       const float* noise, int cx, int cy, int cz, const int32_t* grid_dims, const double* grid_min,
+                       pcmi_stream_t stream);
+size_t pcmi_seg_transform_workspace_bytes(int64_t B);
+int pcmi_seg_transform(const double* xyz, const int64_t* offsets, int64_t n, int64_t B, const double* mats, int clip_mode,
+                       const double* clip_host, const double* trans_ratio, int32_t* vox, uint8_t* keep, int32_t* scene_min,
+                       double* aligned, int32_t* flags, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_seg_quantize_workspace_bytes(int64_t n);
+int pcmi_seg_quantize(const int32_t* vox, const uint8_t* keep, const int32_t* labels, const int64_t* offsets,
+                      const int32_t* scene_min, int64_t n, int64_t B, int32_t ignore_label, int32_t* coords, int64_t* index,
+                      int32_t* out_labels, int64_t* counts, int32_t* flags, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_seg_color_augment_workspace_bytes(int64_t B);
+int pcmi_seg_color_augment(const float* feats_src, int64_t n_src, const int64_t* index, int32_t* coords, int32_t* labels,
+                           int64_t m, int64_t B, const double* params, const float* normals, int normalize, const int32_t* lut,
+                           int64_t lut_n, int32_t ignore_label, float* feats_out, void* ws, size_t ws_bytes,
+                           pcmi_stream_t stream);
+
 int pcmi_sgd_step(float* w, const float* g, float* v, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, pcmi_stream_t stream);
 /* The same with torch's dampening (the downstream fine-tuning's optimiser: SGD(lr, sgd_momentum, dampening =

@@ -187,6 +187,20 @@ PROTOTYPES = {
     "pcmi_nearest_point": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                                      c_vp]),
     "pcmi_seg_hist": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp]),
+    "pcmi_elastic_blur_workspace_bytes": (c_sz, [c_i64, C.c_int, C.c_int, C.c_int]),
+    "pcmi_elastic_blur": (C.c_int, [c_vp, c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_vp,
+                                    c_vp, c_sz, c_vp]),
+    "pcmi_elastic_apply": (C.c_int, [c_vp, c_vp, c_i64, c_i64, C.c_double, C.c_double, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_vp,
+                                     c_vp]),
+    "pcmi_seg_transform_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_seg_transform": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, C.c_int, C.POINTER(C.c_double), c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_seg_quantize_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_seg_quantize": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                    c_vp]),
+    "pcmi_seg_color_augment_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_seg_color_augment": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, C.c_int, c_vp, c_i64, c_i32,
+                                         c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

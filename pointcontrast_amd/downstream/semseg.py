@@ -14,8 +14,12 @@ What the reference's downstream/semseg does per iteration (downstream/semseg/lib
              predictions carried onto the ORIGINAL vertices of the scan through the nearest voxel centre, and their mIoU ->
              PointCloudEvaluator (pcmi_voxel_centers, pcmi_nearest_point, pcmi_seg_hist),
              SegmentationTrainer.test_original_pointcloud
-Datasets, augmentation, PLY / txt files and colour maps, tensorboard and checkpoint bookkeeping of the downstream trainer are
-outside the hot path and not provided.
+  input      Voxelizer.voxelize + sparse_quantize with labels, flip and the chromatic transforms, colour normalisation, label
+             map and collation (lib/dataset.py:289-298, lib/voxelizer.py, lib/transforms.py) for a batch of raw scans ->
+             SegmentationInputPipeline (pcmi_seg_transform, pcmi_seg_quantize, pcmi_seg_color_augment),
+             SegmentationTrainer.train_iter_scenes; every random draw is data (AugmentationDraws)
+Dataset classes, the elastic distortion and random dropout, PLY / txt files and colour maps, tensorboard and checkpoint
+bookkeeping of the downstream trainer are not provided.
 """
 import warnings
 
@@ -223,7 +227,7 @@ class SegmentationTrainer:
 
   def __init__(self, num_labels, in_channels=3, model="Res16UNet34C", lr=0.1, momentum=0.9, dampening=0.1,
                weight_decay=1e-4, max_iter=60000, poly_power=0.9, ignore_label=255, bn_momentum=0.02, pretrained=None,
-               kernel_order="hybrid", device=None, conv_precision="fp32"):
+               kernel_order="hybrid", device=None, conv_precision="fp32", input_pipeline=None):
     assert torch.cuda.is_available(), "the fine-tuning step runs on a gfx950 GPU (no CPU path)"
     self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = get_config(["net.normalize_feature=False", "opt.bn_momentum=%g" % bn_momentum])
@@ -241,6 +245,7 @@ class SegmentationTrainer:
     self.optimizer = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=dampening)
     self.scheduler = PolyLR(self.optimizer, max_iter=max_iter, power=poly_power)
     self.ignore_label, self.num_labels, self.curr_iter = ignore_label, num_labels, 0
+    self.input_pipeline = input_pipeline  # a SegmentationInputPipeline, for train_iter_scenes
 
   def forward(self, coords, feats, training=True):
     st = ME.SparseTensor(feats, coords=coords).to(self.device)
@@ -309,3 +314,228 @@ class SegmentationTrainer:
           self.pointcloud_evaluator.step(coords, pred, transformation, points, point_labels, offsets))
     m = self.pointcloud_evaluator.compute_metrics()
     return m["mIoU"], m["ious"]
+
+  def train_iter_scenes(self, scenes, draws=None, limit_numpoints=0):
+    """One iteration from raw scans: self.input_pipeline (a SegmentationInputPipeline, the constructor's argument) on (scenes,
+    draws, limit_numpoints), then train_iter on its device tensors (the coordinates never visit the host).  The result
+    carries the batch's `transformation` too."""
+    assert self.input_pipeline is not None, "construct the trainer with input_pipeline=SegmentationInputPipeline(aug, device)"
+    coords, feats, target, transformation = self.input_pipeline(scenes, draws, limit_numpoints)
+    out = self.train_iter(coords, feats, target)
+    out["transformation"] = transformation
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The input side on the device (csrc/semseg_input.hip): what dataset.py:289-298 of the reference runs per scan on the host.
+# ---------------------------------------------------------------------------------------------------------------------
+_SCANNET_VALID = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39)
+
+
+def make_label_map(num_labels, ignore_labels, ignore_label=255):
+  """The lookup table of dataset.py:249-259: raw label -> its rank among the labels that are not ignored; the ignored ones,
+  and (in pcmi_seg_color_augment) every label outside the table, -> ignore_label."""
+  lut, used = np.full(num_labels, ignore_label, dtype=np.int32), 0
+  for l in range(num_labels):
+    if l not in ignore_labels:
+      lut[l], used = used, used + 1
+  return lut
+
+
+class SegmentationAugmentation:
+  """The dataset constants of the reference's VoxelizationDataset subclasses and of config/default.yaml:86-90."""
+
+  def __init__(self, voxel_size=0.05, clip_bound=None, scale_bound=(0.9, 1.1),
+               rotation_bound=((-np.pi / 6, np.pi / 6), (-np.pi, np.pi), (-np.pi / 6, np.pi / 6)),
+               translation_ratio_bound=((-0.2, 0.2), (-0.05, 0.05), (-0.2, 0.2)), rotation_axis="z", ignore_label=255,
+               label_map=None, color_trans_ratio=0.10, color_jitter_std=0.05, normalize_color=True, augment=True,
+               elastic_params=None, dropout_ratio=0.2):
+    self.voxel_size, self.clip_bound, self.scale_bound = float(voxel_size), clip_bound, scale_bound
+    self.rotation_bound, self.translation_ratio_bound = rotation_bound, translation_ratio_bound
+    self.rotation_axis, self.ignore_label = rotation_axis, int(ignore_label)
+    self.label_map = None if label_map is None else np.asarray(label_map, dtype=np.int32)
+    self.color_trans_ratio, self.color_jitter_std = float(color_trans_ratio), float(color_jitter_std)
+    self.normalize_color, self.augment = bool(normalize_color), bool(augment)
+    # ((granularity, magnitude), ...) of ElasticDistortion in the units of the raw points, or None; RandomDropout's ratio
+    self.elastic_params, self.dropout_ratio = elastic_params, float(dropout_ratio)
+
+  def replace(self, **kw):
+    new = SegmentationAugmentation.__new__(SegmentationAugmentation)
+    new.__dict__.update(self.__dict__)
+    new.__dict__.update(kw)
+    return new
+
+  @property
+  def horizontal_axes(self):
+    return [a for a in range(3) if a != "xyz".index(self.rotation_axis.lower())]
+
+
+_SCANNET = dict(clip_bound=None, rotation_bound=((-np.pi / 64, np.pi / 64), (-np.pi / 64, np.pi / 64), (-np.pi, np.pi)),
+                translation_ratio_bound=((-0.2, 0.2), (-0.2, 0.2), (0, 0)), rotation_axis="z",
+                label_map=make_label_map(41, set(range(41)) - set(_SCANNET_VALID)),
+                elastic_params=((0.2, 0.4), (0.8, 1.6)))  # ELASTIC_DISTORT_PARAMS, scannet.py:76
+# lib/datasets/scannet.py:68-78,176 and lib/datasets/stanford.py:98-106 (the training phase: Stanford clips at 4 m)
+SCANNET_2CM = SegmentationAugmentation(voxel_size=0.02, **_SCANNET)
+SCANNET_5CM = SegmentationAugmentation(voxel_size=0.05, **_SCANNET)
+STANFORD_5CM = SegmentationAugmentation(
+    voxel_size=0.05, clip_bound=4, rotation_bound=((-np.pi / 32, np.pi / 32), (-np.pi / 32, np.pi / 32), (-np.pi, np.pi)),
+    translation_ratio_bound=((-0.2, 0.2), (-0.2, 0.2), (-0.05, 0.05)), rotation_axis="z", label_map=make_label_map(14, {10}))
+
+
+def axis_rotation(axis, theta):
+  """The rotation by theta about coordinate axis `axis`: M(axis, theta) of lib/voxelizer.py:14-15 in closed form."""
+  c, s = np.cos(theta), np.sin(theta)
+  i, j = (axis + 1) % 3, (axis + 2) % 3
+  R = np.eye(3)
+  R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+  return R
+
+
+class AugmentationDraws:
+  """Every random quantity of one batch, as data.  Host, per scene: mats [B, 4, 4] (M_r M_v of voxelizer.py:49-79,128-132),
+  trans_ratio [B, 3], flip [B] of (fx, fy, fz) or None, contrast [B] of the blend factor or None, translation [B] of (r, g, b)
+  in colour units or None, jitter_std [B] of std or None, elastic_on [B] and dropout_on [B] of booleans or None.  Device:
+  normals float32 [rows, 3] for the jitter and dropout_keys float32 [rows], both read by VOXEL row (rows >= the number of
+  voxels; the number of points always suffices); elastic_noise: per stage of aug.elastic_params one float32 [B, cx, cy, cz, 3]
+  block of standard normals (the pipeline smooths a copy, so the draws can be used again)."""
+
+  # the largest |value| a blurred grid of float32 normals can take: the filter's weights sum to at most 1, and a float32 normal
+  # drawn from 24 uniform bits stays below sqrt(2 * 24 * ln 2) = 5.77
+  NOISE_BOUND = 6.0
+
+  def __init__(self, mats, trans_ratio=None, flip=None, contrast=None, translation=None, jitter_std=None, normals=None,
+               elastic_on=None, elastic_noise=None, dropout_on=None, dropout_keys=None):
+    self.mats = np.asarray(mats, dtype=np.float64).reshape(-1, 4, 4)
+    B = len(self.mats)
+    self.trans_ratio = np.zeros((B, 3)) if trans_ratio is None else np.asarray(trans_ratio, dtype=np.float64).reshape(B, 3)
+    self.flip, self.contrast, self.translation, self.jitter_std, self.normals = flip, contrast, translation, jitter_std, normals
+    self.elastic_on, self.elastic_noise, self.dropout_on, self.dropout_keys = elastic_on, elastic_noise, dropout_on, dropout_keys
+
+  @staticmethod
+  def identity(aug, n_scenes):
+    """No augmentation: the validation path (M_v alone)."""
+    M = np.eye(4)
+    np.fill_diagonal(M[:3, :3], 1 / aug.voxel_size)
+    return AugmentationDraws(np.repeat(M[None], n_scenes, 0))
+
+  @staticmethod
+  def sample(aug, scenes, rng, generator=None, device=None):
+    """Draws with the reference's probabilities (transforms.py: flip 0.95 then 0.5 per horizontal axis, auto-contrast 0.2,
+    translation 0.95, jitter 0.95, elastic distortion 0.95, dropout aug.dropout_ratio) -- the scalars from rng (numpy.random.RandomState), the normals from `generator` (a
+    torch.Generator of `device`).  The streams are not numpy's of the reference; the distributions are.  The capacity of a
+    stage's noise blocks comes from the scenes' raw bounding boxes (host arithmetic on the arrays as loaded) widened by what
+    the earlier stages can add, NOISE_BOUND * magnitude on either side."""
+    B = len(scenes)
+    mats, ratio, flip, contrast, translation, jitter, elastic_on, dropout_on = [], [], [], [], [], [], [], []
+    for _ in range(B):
+      rots = [axis_rotation(a, rng.uniform(*bound) if bound is not None else 0.0) for a, bound in enumerate(aug.rotation_bound)]
+      order = rng.permutation(3)  # "use random order" (voxelizer.py:67-69)
+      M_r, M_v = np.eye(4), np.eye(4)
+      M_r[:3, :3] = rots[order[0]] @ rots[order[1]] @ rots[order[2]]
+      np.fill_diagonal(M_v[:3, :3], 1 / aug.voxel_size * rng.uniform(*aug.scale_bound))
+      mats.append(M_r @ M_v)
+      ratio.append([rng.uniform(*bound) for bound in aug.translation_ratio_bound])
+      f = [False] * 3
+      if rng.random_sample() < 0.95:
+        for a in aug.horizontal_axes:
+          f[a] = bool(rng.random_sample() < 0.5)
+      flip.append(tuple(f))
+      contrast.append(float(rng.random_sample()) if rng.random_sample() < 0.2 else None)
+      translation.append((rng.random_sample(3) - 0.5) * 255 * 2 * aug.color_trans_ratio if rng.random_sample() < 0.95 else None)
+      jitter.append(aug.color_jitter_std if rng.random_sample() < 0.95 else None)
+      elastic_on.append(bool(rng.random_sample() < 0.95))
+      dropout_on.append(bool(rng.random_sample() < aug.dropout_ratio))
+    rows = sum(len(s[0]) for s in scenes)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    normals = torch.randn((rows, 3), dtype=torch.float32, device=dev, generator=generator)
+    keys = torch.rand(rows, dtype=torch.float32, device=dev, generator=generator)
+    noise = None
+    if aug.elastic_params:
+      extent = np.max([np.ptp(np.asarray(s[0], dtype=np.float64).reshape(-1, 3), axis=0) if len(s[0]) else np.zeros(3)
+                       for s in scenes], axis=0)
+      noise, grown = [], 0.0
+      for g, mag in aug.elastic_params:
+        cap = [int((e + grown) // g) + 4 for e in extent]  # dims = extent // g + 3, and one more against round-off
+        noise.append(torch.randn((B, cap[0], cap[1], cap[2], 3), dtype=torch.float32, device=dev, generator=generator))
+        grown += 2 * AugmentationDraws.NOISE_BOUND * mag
+    return AugmentationDraws(mats, ratio, flip, contrast, translation, jitter, normals, elastic_on, noise, dropout_on, keys)
+
+
+class SegmentationInputPipeline:
+  """scenes -> (coords, feats, target, transformation) on the device: pcmi_seg_transform, pcmi_seg_quantize, ONE read-back
+  (counts, flags), pcmi_seg_color_augment.  Differences from the reference: rows leave in the order of first
+  occurrence, scenes in order; colour arithmetic in float64 with one rounding; a channel with hi == lo is not contrasted."""
+
+  def __init__(self, aug, device=None):
+    self.aug = aug
+    self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    self.last_scene_min = None  # int64 [B, 3]: the voxel minima of the last batch, from its read-back
+    self._lut = None if aug.label_map is None else torch.from_numpy(aug.label_map).to(self.device)
+
+  def __call__(self, scenes, draws=None, limit_numpoints=0):
+    """scenes: a list of (xyz float64 [n, 3], feats [n, 3] in 0..255, labels [n]).  draws None: AugmentationDraws.identity
+    (requires aug.augment False).  Returns coords int32 [M, 4], feats float32 [M, 3], target int32 [M], transformation float64
+    [B', 16]; limit_numpoints > 0 keeps the leading scenes whose voxels fit (cfl_collate_fn, transforms.py:251-283)."""
+    aug, dev, B = self.aug, self.device, len(scenes)
+    assert B >= 1, "at least one scene"
+    if draws is None:
+      assert not aug.augment, "an augmenting pipeline needs its draws (AugmentationDraws.sample)"
+      draws = AugmentationDraws.identity(aug, B)
+    assert len(draws.mats) == B, "one set of draws per scene"
+    sizes = [len(s[0]) for s in scenes]
+    offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64)
+    for s in scenes:
+      assert torch.as_tensor(s[0]).dtype == torch.float64, "xyz: float64 [n, 3]"
+    xyz = torch.cat([torch.as_tensor(s[0]).reshape(-1, 3) for s in scenes]).to(dev)
+    feats = torch.cat([torch.as_tensor(s[1]).reshape(-1, 3).float() for s in scenes]).to(dev)
+    labels = torch.cat([torch.as_tensor(np.asarray(s[2])).reshape(-1).to(torch.int32) for s in scenes]).to(dev)
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    if draws.elastic_noise is not None:  # the stages chain on the device: each reads the extents the one before left in xyz
+      assert aug.elastic_params and len(draws.elastic_noise) == len(aug.elastic_params), "one noise block per elastic stage"
+      offs_dev = offs.to(dev)
+      active = None if draws.elastic_on is None else torch.tensor([int(bool(v)) for v in draws.elastic_on], dtype=torch.int32)
+      for (g, mag), noise in zip(aug.elastic_params, draws.elastic_noise):
+        noise = noise.clone()  # smoothed in place
+        grid = PF.elastic_blur(xyz, offs_dev, g, noise, active, flags)
+        PF.elastic_apply(xyz, offs_dev, g, mag, noise, grid)
+    t = PF.seg_transform(xyz, offs, torch.from_numpy(draws.mats.reshape(B, 16)), aug.clip_bound,
+                         torch.from_numpy(draws.trans_ratio) if aug.clip_bound is not None else None, flags=flags)
+    q = PF.seg_quantize(t["vox"], offs, labels, t["keep"], t["scene_min"], aug.ignore_label, flags=flags)
+    # the batch's one read-back: counts [B + 1], flags [B], per-scene minima [3 B]
+    host = torch.cat([q["counts"], flags.to(torch.int64), t["scene_min"].reshape(-1).to(torch.int64)]).cpu().numpy()
+    msg = PF.seg_flags_message(host[B + 1:2 * B + 1])
+    if msg:
+      raise ValueError(msg)
+    self.last_scene_min = host[2 * B + 1:].reshape(B, 3)
+    counts = [int(c) for c in host[:B]]
+    coords, index, target = q["coords"], q["index"], q["labels"]
+    if draws.dropout_on is not None and any(draws.dropout_on):
+      # RandomDropout on the voxel rows (transforms.py:153-158): the int(m (1 - ratio)) rows of the scene with the smallest keys,
+      # in row order (a stable sort of the keys, then a sort of the winners); the counts are already on the host
+      assert draws.dropout_keys is not None, "dropout needs its keys"
+      kept, start = [], 0
+      for b in range(B):
+        rows = torch.arange(start, start + counts[b], device=dev)
+        if draws.dropout_on[b]:
+          k = int(counts[b] * (1 - aug.dropout_ratio))
+          order = torch.sort(draws.dropout_keys[start:start + counts[b]], stable=True).indices[:k]
+          rows = rows[torch.sort(order).values]
+        kept.append(rows)
+        start += counts[b]
+        counts[b] = len(rows)
+      kept = torch.cat(kept)
+      coords, index, target = coords[kept].contiguous(), index[kept].contiguous(), target[kept].contiguous()
+    nb, total = B, 0
+    for b in range(B):  # cfl_collate_fn: stop before the scene that would exceed the limit
+      if limit_numpoints and total + counts[b] > limit_numpoints:
+        nb = b
+        break
+      total += counts[b]
+    coords, index, target = coords[:total], index[:total], target[:total]
+    params = None
+    if any(x is not None for x in (draws.flip, draws.contrast, draws.translation, draws.jitter_std)):
+      params = torch.from_numpy(PF.seg_color_params(B, draws.flip, draws.contrast, draws.translation, draws.jitter_std)[:max(nb, 1)])
+    normals = None if draws.normals is None else draws.normals[:total]
+    out = PF.seg_color_augment(feats, coords, max(nb, 1), index, target, params, normals, aug.normalize_color,
+                               self._lut, aug.ignore_label)
+    return coords, out, target, t["aligned"][:nb]

@@ -1114,3 +1114,172 @@ def seg_hist(pred, idx, labels, num_labels, hist=None, missing=None, want_point_
   point_pred = torch.empty(n, dtype=torch.int32, device=dev) if want_point_pred else None
   check(lib.pcmi_seg_hist(ptr(p), m, ptr(ix), ptr(lb), n, c, ptr(hist), ptr(point_pred), ptr(missing), cur_stream(dev)))
   return dict(hist=hist, point_pred=point_pred, missing=missing)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The input of segmentation fine-tuning (csrc/semseg_input.hip): Voxelizer.voxelize with sparse_quantize and the voxel-space
+# augmentations of the reference (downstream/semseg/lib/voxelizer.py, lib/transforms.py) for a batch of scans.  None of these
+# is differentiable and none synchronises; errors arrive in `flags` (int32 [B], SEG_FLAG_* bits per scene).
+# ---------------------------------------------------------------------------------------------------------------------
+SEG_FLAG_RANGE, SEG_FLAG_SPAN, SEG_FLAG_ELASTIC = 1, 2, 4
+SEG_FLAG_NAMES = {SEG_FLAG_RANGE: "a point is not finite or its voxel coordinate is outside +-2^20",
+                  SEG_FLAG_SPAN: "a voxel coordinate lies 2^18 or more above the scene's minimum",
+                  SEG_FLAG_ELASTIC: "the elastic noise grid does not fit its capacity block"}
+
+
+def seg_flags_message(flags_host):
+  """The exception text for a read-back flags array (None if no bit is set): every flagged scene with its causes."""
+  bad = ["scene %d: %s" % (b, "; ".join(t for bit, t in SEG_FLAG_NAMES.items() if int(f) & bit) or "flag %d" % int(f))
+         for b, f in enumerate(flags_host) if int(f)]
+  return "segmentation input: " + " | ".join(bad) if bad else None
+
+
+def _seg_flags(flags, B, dev):
+  if flags is None:
+    return torch.zeros(B, dtype=torch.int32, device=dev)
+  assert flags.dtype == torch.int32 and flags.shape == (B,) and flags.device == dev and flags.is_contiguous(), "flags: int32 [B]"
+  return flags
+
+
+def _elastic_args(xyz, offsets, noise, what):
+  require_cuda(xyz, what)
+  dev = xyz.device
+  assert xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous(), \
+      what + ": xyz float64 [n, 3], contiguous (changed in place)"
+  offs = _offsets(offsets, dev)
+  B = offs.shape[0] - 1
+  assert noise.dtype == torch.float32 and noise.dim() == 5 and noise.shape[0] == B and noise.shape[4] == 3 and \
+      noise.is_contiguous() and noise.device == dev, what + ": noise float32 [B, cx, cy, cz, 3] on xyz's device, contiguous"
+  return dev, offs, B
+
+
+def elastic_blur(xyz, offsets, granularity, noise, active=None, flags=None):
+  """pcmi_elastic_blur: the noise grids of one elastic stage from the scenes' current extents, smoothed IN PLACE in noise
+  float32 [B, cx, cy, cz, 3] (each scene's [dx, dy, dz, 3] volume in the corner of its capacity block).  active int32 [B]
+  (None: all).  Returns a dict: grid_dims int32 [B, 4] (dx, dy, dz, on), grid_min float64 [B, 3], flags int32 [B]."""
+  dev, offs, B = _elastic_args(xyz, offsets, noise, "elastic_blur")
+  act = None if active is None else _i32c(torch.as_tensor(active), dev).reshape(-1)
+  assert act is None or act.shape[0] == B, "elastic_blur: active [B]"
+  flags = _seg_flags(flags, B, dev)
+  cx, cy, cz = (int(v) for v in noise.shape[1:4])
+  grid_dims = torch.empty((B, 4), dtype=torch.int32, device=dev)
+  grid_min = torch.empty((B, 3), dtype=torch.float64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_elastic_blur_workspace_bytes(B, cx, cy, cz), dev)
+  check(lib.pcmi_elastic_blur(ptr(xyz), ptr(offs), xyz.shape[0], B, float(granularity), ptr(act), ptr(noise), cx, cy, cz,
+                              ptr(grid_dims), ptr(grid_min), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(grid_dims=grid_dims, grid_min=grid_min, flags=flags)
+
+
+def elastic_apply(xyz, offsets, granularity, magnitude, noise, grid):
+  """pcmi_elastic_apply: xyz += trilinear(noise)(xyz) * magnitude IN PLACE for the scenes that elastic_blur switched on
+  (grid: its result)."""
+  dev, offs, B = _elastic_args(xyz, offsets, noise, "elastic_apply")
+  cx, cy, cz = (int(v) for v in noise.shape[1:4])
+  check(lib.pcmi_elastic_apply(ptr(xyz), ptr(offs), xyz.shape[0], B, float(granularity), float(magnitude), ptr(noise), cx, cy, cz,
+                               ptr(grid["grid_dims"]), ptr(grid["grid_min"]), cur_stream(dev)))
+  return xyz
+
+
+def seg_transform(xyz, offsets, mats, clip_bound=None, trans_ratio=None, flags=None):
+  """pcmi_seg_transform.  xyz float64 [n, 3] and offsets [B + 1] (the scenes' row offsets), mats float64 [B, 16] or [B, 4, 4]
+  (host or device).  clip_bound: None, a number, or ((lo, hi),) * 3 as Voxelizer.clip_bound; trans_ratio float64 [B, 3]
+  (None: 0).  Returns a dict of device tensors: vox int32 [n, 3], keep uint8 [n], scene_min int32 [B, 3], aligned float64
+  [B, 16] and flags int32 [B] (ORed into the one passed in)."""
+  require_cuda(xyz, "seg_transform")
+  dev = xyz.device
+  x, offs = _f64c(xyz, dev, "seg_transform"), _offsets(offsets, dev)
+  assert x.dim() == 2 and x.shape[1] == 3 and offs.dim() == 1 and offs.shape[0] >= 2, "seg_transform: xyz [n, 3], offsets [B + 1]"
+  n, B = x.shape[0], offs.shape[0] - 1
+  M = _f64c(mats, dev, "seg_transform").reshape(-1, 16)
+  assert M.shape[0] == B, "seg_transform: one matrix per scene"
+  tr = None if trans_ratio is None else _f64c(trans_ratio, dev, "seg_transform").reshape(-1, 3)
+  assert tr is None or tr.shape[0] == B, "seg_transform: trans_ratio [B, 3]"
+  if clip_bound is None:
+    mode, lim = 0, (C.c_double * 6)()
+  elif isinstance(clip_bound, (int, float)):
+    mode, lim = 1, (C.c_double * 6)(float(clip_bound))
+  else:
+    mode, lim = 2, (C.c_double * 6)(*[float(v) for pair in clip_bound for v in pair])
+  flags = _seg_flags(flags, B, dev)
+  vox = torch.empty((n, 3), dtype=torch.int32, device=dev)
+  keep = torch.empty(n, dtype=torch.uint8, device=dev)
+  scene_min = torch.empty((B, 3), dtype=torch.int32, device=dev)
+  aligned = torch.empty((B, 16), dtype=torch.float64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_seg_transform_workspace_bytes(B), dev)
+  check(lib.pcmi_seg_transform(ptr(x), ptr(offs), n, B, ptr(M), mode, lim, ptr(tr), ptr(vox), ptr(keep), ptr(scene_min),
+                               ptr(aligned), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(vox=vox, keep=keep, scene_min=scene_min, aligned=aligned, flags=flags)
+
+
+def seg_quantize(vox, offsets, labels=None, keep=None, scene_min=None, ignore_label=255, flags=None):
+  """pcmi_seg_quantize: ME.utils.sparse_quantize with labels for a batch.  vox int32 [n, 3], offsets [B + 1], labels [n],
+  keep uint8 [n] (None: all), scene_min int32 [B, 3] (None: 0).  Returns a dict of device tensors whose first counts[B] rows
+  are valid -- coords int32 [n, 4] (b, x - min, ...), index int64 [n], labels int32 [n] (None without labels) -- and counts
+  int64 [B + 1] (voxels per scene, then their sum), flags int32 [B].  Nothing is read back: slice after reading counts."""
+  require_cuda(vox, "seg_quantize")
+  dev = vox.device
+  v, offs = _i32c(vox, dev), _offsets(offsets, dev)
+  assert v.dim() == 2 and v.shape[1] == 3 and offs.dim() == 1 and offs.shape[0] >= 2, "seg_quantize: vox [n, 3], offsets [B + 1]"
+  n, B = v.shape[0], offs.shape[0] - 1
+  lb = None if labels is None else _i32c(labels, dev).reshape(-1)
+  kp = None if keep is None else keep.to(device=dev, dtype=torch.uint8).contiguous()
+  mn = None if scene_min is None else _i32c(scene_min, dev).reshape(-1, 3)
+  assert (lb is None or lb.shape[0] == n) and (kp is None or kp.shape == (n,)) and (mn is None or mn.shape[0] == B), \
+      "seg_quantize: labels [n], keep [n], scene_min [B, 3]"
+  flags = _seg_flags(flags, B, dev)
+  coords = torch.empty((n, 4), dtype=torch.int32, device=dev)
+  index = torch.empty(n, dtype=torch.int64, device=dev)
+  out_labels = None if lb is None else torch.empty(n, dtype=torch.int32, device=dev)
+  counts = torch.empty(B + 1, dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_seg_quantize_workspace_bytes(n), dev)
+  check(lib.pcmi_seg_quantize(ptr(v), ptr(kp), ptr(lb), ptr(offs), ptr(mn), n, B, int(ignore_label), ptr(coords), ptr(index),
+                              ptr(out_labels), ptr(counts), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(coords=coords, index=index, labels=out_labels, counts=counts, flags=flags)
+
+
+def seg_color_params(B, flip=None, contrast=None, translation=None, jitter_std=None):
+  """The [B, 12] float64 parameter block of seg_color_augment on the host (numpy).  Per scene (each a length-B sequence, an
+  entry None = that transform is off): flip (fx, fy, fz) booleans; contrast = the blend factor; translation = (tr_r, tr_g,
+  tr_b), already scaled to colour units; jitter_std = std (the noise is normal * std * 255)."""
+  import numpy as np
+  P = np.zeros((B, 12), dtype=np.float64)
+  for b in range(B):
+    if flip is not None and flip[b] is not None:
+      P[b, 0:3] = [1.0 if f else 0.0 for f in flip[b]]
+    if contrast is not None and contrast[b] is not None:
+      P[b, 3], P[b, 4] = 1.0, float(contrast[b])
+    if translation is not None and translation[b] is not None:
+      P[b, 5], P[b, 6:9] = 1.0, np.asarray(translation[b], dtype=np.float64).reshape(3)
+    if jitter_std is not None and jitter_std[b] is not None:
+      P[b, 9], P[b, 10] = 1.0, float(jitter_std[b]) * 255
+  return P
+
+
+def seg_color_augment(feats_src, coords, n_scenes, index=None, labels=None, params=None, normals=None, normalize=False,
+                      label_lut=None, ignore_label=255):
+  """pcmi_seg_color_augment over the m voxel rows.  feats_src float32 [n_src, 3], read at index int64 [m] (None: the row
+  itself); coords int32 [m, 4] and labels int32 [m] are changed IN PLACE (flip; label map) and must be contiguous device
+  tensors; params float64 [B, 12] (seg_color_params; None: no augmentation); normals float32 [m, 3]; label_lut int32 [L].
+  Returns feats float32 [m, 3]."""
+  require_cuda(coords, "seg_color_augment")
+  dev = coords.device
+  assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4 and coords.is_contiguous(), \
+      "seg_color_augment: coords int32 [m, 4], contiguous (changed in place)"
+  assert labels is None or (labels.dtype == torch.int32 and labels.is_contiguous() and labels.device == dev and
+                            labels.shape == (coords.shape[0],)), "seg_color_augment: labels int32 [m] on the device (changed in place)"
+  m, B = coords.shape[0], int(n_scenes)
+  src = _f32c(torch.as_tensor(feats_src).to(dev), "seg_color_augment")
+  assert src.dim() == 2 and src.shape[1] == 3, "seg_color_augment: feats_src [n_src, 3]"
+  ix = None if index is None else index.to(device=dev, dtype=torch.int64).contiguous()
+  assert ix is None or ix.shape == (m,), "seg_color_augment: index [m]"
+  P = None if params is None else _f64c(params, dev, "seg_color_augment").reshape(-1, 12)
+  assert P is None or P.shape[0] == B, "seg_color_augment: params [B, 12]"
+  nm = None if normals is None else _f32c(normals.to(dev), "seg_color_augment")
+  assert nm is None or nm.shape == (m, 3), "seg_color_augment: normals [m, 3]"
+  lut = None if label_lut is None else _i32c(torch.as_tensor(label_lut), dev).reshape(-1)
+  out = torch.empty((m, 3), dtype=torch.float32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_seg_color_augment_workspace_bytes(B), dev)
+  check(lib.pcmi_seg_color_augment(ptr(src), src.shape[0], ptr(ix), ptr(coords), ptr(labels), m, B, ptr(P), ptr(nm),
+                                   1 if normalize else 0, ptr(lut), 0 if lut is None else lut.shape[0], int(ignore_label),
+                                   ptr(out), ws, wsb, cur_stream(dev)))
+  return out
