@@ -63,7 +63,9 @@ int pcmi_device_info(int* n_cu, char* arch_host, int arch_len);
  *   ME.SparseTensor(feats, coords=...)             pc/lib/ddp_trainer.py:290-297,392-398
  *   strided coordinates of every stride-2 conv     pc/model/res16unet.py:58-64,75-81,92-98,109-115
  * Coordinates are int32 rows (batch, x, y, z), batch index FIRST
- * (pc/lib/ddp_data_loaders.py:68-76); |x|,|y|,|z| < 2^17, 0 <= batch < 1023.
+ * (pc/lib/ddp_data_loaders.py:68-76); |x|,|y|,|z| < 2^17, 0 <= batch < 1023 for the inserted rows
+ * (PCMI_ERR_RANGE otherwise).  Strided levels may hold -2^17 = floor(-(2^17 - 1) / ts) * ts: its key
+ * field is 0, a valid key, and kernel maps find such rows and their neighbours like any other.
  * Key 0 is the inserted set (tensor stride 1); row i of a feature matrix belongs to
  * row i of its key's coordinates.
  * ------------------------------------------------------------------------------------------ */
@@ -386,11 +388,15 @@ int pcmi_nce_bwd(const float* q, const float* k, const float* lse, int64_t n, in
 /* ------------------------------------------------------------------------------------------
  * Hardest-contrastive block (pc/lib/ddp_trainer.py:182-238)
  *   pdist_argmin: dmin[p] = min_s sqrt(|a_p - b_s|^2 + 1e-7), amin[p] = first arg min
- *                 (replaces pdist :182-184 + .min(1) :218-219; no [P,S,C] temporary)
+ *                 (replaces pdist :182-184 + .min(1) :218-219; no [P,S,C] temporary).
+ *                 torch.min's order: a NaN distance is below every number, so a row with one has
+ *                 dmin = NaN and amin = its first NaN position; exact ties and rows whose distances
+ *                 are all +inf go to the lowest index.  0 <= amin[p] < s always.
  *   keyset: device hash set of int64 keys a + b*M (replaces _hash :39-51 + np.isin :231-234)
  *   hardest_loss: pos = mean(relu(|a-b|^2 - pos_thresh)); neg = (mean_masked(relu(nt-D01)^2)
  *                 + mean_masked(relu(nt-D10)^2)) / 2 (fwd), and the gradients w.r.t. the four
- *                 gathered matrices (bwd).
+ *                 gathered matrices (bwd).  relu is F.relu: a NaN feature or mined distance makes
+ *                 the loss it enters NaN (it is not dropped by the hinge).
  * ------------------------------------------------------------------------------------------ */
 int pcmi_pdist_argmin(const float* a, int64_t p, const float* b, int64_t s, int c, float* dmin,
                       int32_t* amin, pcmi_stream_t stream);
@@ -426,7 +432,10 @@ size_t pcmi_hardest_workspace_bytes(int64_t p);
  * pcmi_match_radius = get_matching_indices (pc/lib/ddp_data_loaders.py:36-49): all (i, j) with
  *   |R src_i + t - dst_j| <= radius, rigid3x4_host = [R | t] row-major (12 host doubles); pairs [*n_pairs, 2] sorted by
  *   (i, j).  pairs == NULL: only counts.  PCMI_ERR_WORKSPACE if pairs_capacity is too small (*n_pairs_host = needed).
- * Both synchronise the stream (they return counts) and are bit-exact against oracle/loader_ref.py. */
+ * Both synchronise the stream (they return counts) and are bit-exact against oracle/loader_ref.py.
+ * PCMI_ERR_RANGE: a voxel / cell index outside +-(2^20 - 1), more than 96 matches of one source point, or a
+ *   NON-FINITE point (NaN, +-inf) in xyz, in dst or in R src_i + t -- tested before the float -> integer conversion,
+ *   which is undefined for them; oracle/loader_ref.py raises for the same inputs. */
 size_t pcmi_voxelize_workspace_bytes(int64_t n);
 int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* first_index, int32_t* coords,
                   int64_t* n_unique_host, void* ws, size_t ws_bytes, pcmi_stream_t stream);

@@ -11,7 +11,15 @@
 import numpy as np
 
 
+def _require_finite(x, who):
+  """A NaN or an infinity has no voxel / cell: floor -> integer is undefined for it.  The device kernels refuse such a
+  point (PCMI_ERR_RANGE, include/pcmi.h); the restatement raises."""
+  if not np.isfinite(x).all():
+    raise ValueError("%s: non-finite point" % who)
+
+
 def sparse_quantize_index(xyz, voxel_size):
+  _require_finite(np.asarray(xyz, dtype=np.float64), "sparse_quantize_index")
   q = np.floor(np.asarray(xyz, dtype=np.float64) / np.float64(voxel_size)).astype(np.int64)
   if len(q) == 0:
     return np.zeros(0, np.int64)
@@ -27,8 +35,9 @@ def apply_rigid(trans, xyz):
   T = np.asarray(trans, dtype=np.float64)
   p = np.asarray(xyz, dtype=np.float64)
   out = np.empty_like(p)
-  for r in range(3):
-    out[:, r] = ((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3]
+  with np.errstate(invalid="ignore", over="ignore"):  # (a non-finite result is match_radius's to refuse)
+    for r in range(3):
+      out[:, r] = ((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3]
   return out
 
 
@@ -38,6 +47,8 @@ def match_radius(xyz0, trans, xyz1, radius):
   dst = np.asarray(xyz1, dtype=np.float64)
   if len(src) == 0 or len(dst) == 0:
     return np.zeros((0, 2), np.int64)
+  _require_finite(src, "match_radius (source, transformed)")
+  _require_finite(dst, "match_radius (target)")
   r = np.float64(radius)
   r2 = r * r
   cell = np.floor(dst / r).astype(np.int64)

@@ -419,8 +419,9 @@ __global__ __launch_bounds__(256) void kmap_k3_kernel(const int32_t* __restrict_
     if (c.x >= 0) {
       const int x = c.y + offs.o[k][0] * ts, y = c.z + offs.o[k][1] * ts,
                 z = c.w + offs.o[k][2] * ts;
-      if (x > -kCoordBias && x < kCoordBias && y > -kCoordBias && y < kCoordBias &&
-          z > -kCoordBias && z < kCoordBias)
+      // (>= : a strided level may hold -2^17 = floor_div(-(2^17 - 1), ts) * ts, whose key field is 0 -- a valid key)
+      if (x >= -kCoordBias && x < kCoordBias && y >= -kCoordBias && y < kCoordBias &&
+          z >= -kCoordBias && z < kCoordBias)
         v = table_lookup(keys, vals, mask, pack_key(c.x, x, y, z));
     }
     s_nbr[k][r] = v;

@@ -26,6 +26,9 @@ __device__ inline uint64_t cell_key(int64_t x, int64_t y, int64_t z) {
 __device__ inline bool cell_ok(int64_t x, int64_t y, int64_t z) {
   return x > -kCellBias && x < kCellBias && y > -kCellBias && y < kCellBias && z > -kCellBias && z < kCellBias;
 }
+// floor(v / cell) as an integer is defined only for a finite point: a NaN or an infinity is refused before the conversion
+// (PCMI_ERR_RANGE, as a point outside +-2^20 cells), whatever the hardware's conversion would have made of it
+__device__ inline bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // slot of `key` (claimed if absent): open addressing, linear probing
 __device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t mask, uint64_t key) {
@@ -51,9 +54,10 @@ __global__ void vox_insert_kernel(const double* __restrict__ xyz, int64_t n, dou
                                   uint32_t mask, uint32_t* slot_of, int32_t* err) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int64_t x = (int64_t)floor(xyz[3 * i] / voxel), y = (int64_t)floor(xyz[3 * i + 1] / voxel),
-                z = (int64_t)floor(xyz[3 * i + 2] / voxel);
-  if (!cell_ok(x, y, z)) {
+  const bool fin = finite3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+  const int64_t x = fin ? (int64_t)floor(xyz[3 * i] / voxel) : 0, y = fin ? (int64_t)floor(xyz[3 * i + 1] / voxel) : 0,
+                z = fin ? (int64_t)floor(xyz[3 * i + 2] / voxel) : 0;
+  if (!fin || !cell_ok(x, y, z)) {
     atomicAdd(err, 1);
     slot_of[i] = 0xffffffffu;
     return;
@@ -100,9 +104,10 @@ __global__ void grid_insert_kernel(const double* __restrict__ dst, int64_t n1, d
                                    uint32_t mask, int32_t* __restrict__ next, int32_t* err) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n1) return;
-  const int64_t x = (int64_t)floor(dst[3 * j] / radius), y = (int64_t)floor(dst[3 * j + 1] / radius),
-                z = (int64_t)floor(dst[3 * j + 2] / radius);
-  if (!cell_ok(x, y, z)) {
+  const bool fin = finite3(dst[3 * j], dst[3 * j + 1], dst[3 * j + 2]);
+  const int64_t x = fin ? (int64_t)floor(dst[3 * j] / radius) : 0, y = fin ? (int64_t)floor(dst[3 * j + 1] / radius) : 0,
+                z = fin ? (int64_t)floor(dst[3 * j + 2] / radius) : 0;
+  if (!fin || !cell_ok(x, y, z)) {
     atomicAdd(err, 1);
     next[j] = -1;
     return;
@@ -122,6 +127,13 @@ __global__ void match_kernel(const double* __restrict__ src, int64_t n0, Rigid T
   const double p[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
   double q[3];
   apply_rigid(T, p, q);
+  if (!finite3(q[0], q[1], q[2])) {  // a non-finite source point, or one the transform made non-finite
+    if (!FILL) {
+      atomicAdd(err, 1);
+      count[i] = 0;
+    }
+    return;
+  }
   const int64_t cx = (int64_t)floor(q[0] / radius), cy = (int64_t)floor(q[1] / radius), cz = (int64_t)floor(q[2] / radius);
   const double r2 = mul_rn(radius, radius);
   int32_t found[kMaxMatches];
@@ -234,7 +246,7 @@ int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* firs
   PCMI_HIP_CHECK(hipMemcpyAsync(&host[1], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipMemcpyAsync(&host[2], err, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
-  PCMI_REQUIRE(host[2] == 0, PCMI_ERR_RANGE, "voxelize: %d points fall outside +-2^20 voxels", host[2]);
+  PCMI_REQUIRE(host[2] == 0, PCMI_ERR_RANGE, "voxelize: %d points are not finite or fall outside +-2^20 voxels", host[2]);
   *n_unique_host = (int64_t)host[0] + host[1];
   vox_compact_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, flags, pos, first_index, coords);
   PCMI_LAUNCH_CHECK();
@@ -285,7 +297,7 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   PCMI_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   PCMI_REQUIRE(herr == 0, PCMI_ERR_RANGE,
-               "match_radius: %d points outside +-2^20 cells or with more than %d matches (is the radius far above the voxel size?)",
+               "match_radius: %d points not finite, outside +-2^20 cells or with more than %d matches (is the radius far above the voxel size?)",
                herr, kMaxMatches);
   *n_pairs_host = last[0] + last[1];
   if (!pairs || *n_pairs_host == 0) return PCMI_OK;  // count-only call

@@ -270,6 +270,15 @@ __device__ inline void load_rows_dmajor(const float* __restrict__ m, int64_t n, 
   }
 }
 
+// torch.min's order of (value, index) candidates: NaN is below every number, and among equals -- two NaNs, an exact tie,
+// +inf against the +inf a row starts from -- the lower index is first.  So amin is always a column of b (a row of
+// distances that are all +inf mines column 0, a row with a NaN distance its first NaN) and dmin is NaN where torch's is.
+__device__ inline bool argmin_before(float v, int32_t i, float bv, int32_t bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v < bv || (v == bv && i < bi);
+}
+
 template <int C, int TR, int TS>
 __global__ __launch_bounds__(256) void pdist_argmin_kernel(const float* __restrict__ a, int64_t p,
                                                            const float* __restrict__ b, int64_t s,
@@ -315,7 +324,8 @@ __global__ __launch_bounds__(256) void pdist_argmin_kernel(const float* __restri
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int64_t col = c0 + tc * 4 + j;
-        if (col < s && acc[i][j] < best[i]) {
+        // a thread's columns only grow: strictly smaller, or the first NaN (unordered against a number; a NaN it holds stays)
+        if (col < s && !(acc[i][j] >= best[i]) && best[i] == best[i]) {
           best[i] = acc[i][j];
           bidx[i] = (int32_t)col;
         }
@@ -327,7 +337,7 @@ __global__ __launch_bounds__(256) void pdist_argmin_kernel(const float* __restri
     for (int d = 1; d < LPR; d <<= 1) {
       const float ob = __shfl_xor(best[i], d, 64);
       const int32_t oi = __shfl_xor(bidx[i], d, 64);
-      if (ob < best[i] || (ob == best[i] && oi < bidx[i])) {
+      if (argmin_before(ob, oi, best[i], bidx[i])) {
         best[i] = ob;
         bidx[i] = oi;
       }
@@ -335,7 +345,7 @@ __global__ __launch_bounds__(256) void pdist_argmin_kernel(const float* __restri
     const int64_t row = r0 + tr * 4 + i;
     if (row < p && tc == 0) {
       dmin[row] = sqrtf(best[i] + 1e-7f);
-      amin[row] = bidx[i];
+      amin[row] = bidx[i] == 0x7fffffff ? 0 : bidx[i];  // nothing below the +inf it started from, no NaN: all +inf, the first is 0
     }
   }
 }
@@ -377,6 +387,9 @@ __global__ void keyset_mask_kernel(const uint64_t* __restrict__ keys, uint32_t m
 // ---- hardest-contrastive loss values + gradients ------------------------------------------------------
 // stats[0] = sum relu(|a-b|^2 - pt); [1] = sum_mask0 relu(nt - d01)^2; [2] = count mask0;
 // [3] = sum_mask1 relu(nt - d10)^2; [4] = count mask1
+// F.relu: a NaN stays a NaN (fmaxf would return the other operand, and a diverged run would report a finite loss)
+__device__ inline float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }
+
 __global__ __launch_bounds__(256) void hardest_stats_kernel(const float* __restrict__ f0, const float* __restrict__ f1,
                                                             int64_t p, int c, const float* __restrict__ d01,
                                                             const uint8_t* __restrict__ m0,
@@ -392,14 +405,14 @@ __global__ __launch_bounds__(256) void hardest_stats_kernel(const float* __restr
       const float df = f0[i * c + d] - f1[i * c + d];
       d2 = fmaf(df, df, d2);
     }
-    v[0] = fmaxf(d2 - pt, 0.f);
+    v[0] = relu_keep_nan(d2 - pt);
     if (m0[i]) {
-      const float h = fmaxf(nt - d01[i], 0.f);
+      const float h = relu_keep_nan(nt - d01[i]);
       v[1] = h * h;
       v[2] = 1.f;
     }
     if (m1[i]) {
-      const float h = fmaxf(nt - d10[i], 0.f);
+      const float h = relu_keep_nan(nt - d10[i]);
       v[3] = h * h;
       v[4] = 1.f;
     }
@@ -899,7 +912,8 @@ size_t pcmi_keyset_bytes(int64_t n_keys) {
 }
 
 int pcmi_keyset_build(const int32_t* pairs, int64_t n, int64_t M, void* set, size_t set_bytes, pcmi_stream_t stream) {
-  PCMI_REQUIRE(pairs && set && set_bytes >= pcmi_keyset_bytes(n), PCMI_ERR_WORKSPACE, "keyset_build: set buffer too small");
+  PCMI_REQUIRE((pairs || n == 0) && n >= 0, PCMI_ERR_INVALID, "keyset_build: bad argument");
+  PCMI_REQUIRE(set && set_bytes >= pcmi_keyset_bytes(n), PCMI_ERR_WORKSPACE, "keyset_build: set buffer too small");
   hipStream_t st = as_stream(stream);
   const uint32_t cap = keyset_cap(set_bytes);
   PCMI_HIP_CHECK(hipMemsetAsync(set, 0xFF, (size_t)cap * sizeof(uint64_t), st));

@@ -124,7 +124,7 @@ size_t pcmi_pair_select_workspace_bytes(int64_t n_pairs) {
 
 int pcmi_pair_select(const int32_t* pairs, int64_t n_pairs, int64_t n_unique, const float* uniform, const int64_t* sampled,
                      int64_t n_sel, int64_t* q_idx, int64_t* k_idx, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
-  PCMI_REQUIRE(pairs && uniform && q_idx && k_idx && n_pairs > 0 && n_pairs < (1ll << 31) && n_unique > 0 && n_sel >= 0, PCMI_ERR_INVALID,
+  PCMI_REQUIRE(pairs && uniform && ((q_idx && k_idx) || n_sel == 0) && n_pairs > 0 && n_pairs < (1ll << 31) && n_unique > 0 && n_sel >= 0, PCMI_ERR_INVALID,
                "pair_select: bad argument");
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_pair_select_workspace_bytes(n_pairs), PCMI_ERR_WORKSPACE, "pair_select: workspace too small");
   if (n_sel == 0) return PCMI_OK;
