@@ -848,6 +848,128 @@ int pcmi_seg_color_augment(const float* feats_src, int64_t n_src, const int64_t*
                            int64_t lut_n, int32_t ignore_label, float* feats_out, void* ws, size_t ws_bytes,
                            pcmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The input of VoteNet detection fine-tuning for a batch of scans (csrc/detect_input.hip) -- what the reference runs per scan on
+ * the host in downstream/votenet_det_new: ScannetDetectionDataset.__getitem__
+ * (lib/datasets/scannet/scannet_detection_dataset.py:60-172), SunrgbdDetectionVotesDataset.__getitem__
+ * (lib/datasets/sunrgbd/sunrgbd_detection_dataset.py:68-212), and VoxelizationDataset.__getitem__ with collate_fn
+ * (models/backbone/sparseconv/voxelized_dataset.py:33-65), for the sparse-backbone recipe: xyz only (no colour, no height).
+ * Every random quantity is an INPUT.  Scene b of B holds the raw rows [offsets[b], offsets[b + 1]) (DEVICE int64 [B + 1]) and
+ * yields exactly num_points = P output rows, [b P, (b + 1) P) of every [B, P, ...] output.  1 <= B <= 1023, P >= 1, B P <= 2^29,
+ * n < 2^31 - 256.  Every product and sum below is rounded on its own, in the stated order and precision (no FMA contraction);
+ * integer atomics only; the same bits from run to run.  Contiguous tensors, everything on the caller's stream, no
+ * synchronisation; a refused call enqueues nothing.  Pointers to fp64 and int64 data are 8-byte aligned, the others 4-byte
+ * (PCMI_ERR_INVALID otherwise).  Data-dependent errors are ORed into flags [B] (device int32, one word per scene, zeroed by
+ * the CALLER so that the calls of a batch share it):
+ *   PCMI_DET_FLAG_RANGE    a chosen point or a live box is not finite, or a voxel coordinate is not inside +-2^20
+ *   PCMI_DET_FLAG_SPAN     a voxel coordinate minus the scene's minimum is outside [0, 2^18) (= PCMI_SEG_FLAG_SPAN, which the
+ *                          shared pcmi_seg_quantize sets)
+ *   PCMI_DET_FLAG_CHOICE   a choice is outside [0, n_b) (every choice of an empty scene is), or the scene's offsets are not
+ *                          0 <= offsets[b] <= offsets[b + 1] <= n
+ *   PCMI_DET_FLAG_INSTANCE an instance id is outside [0, PCMI_DET_MAX_INSTANCES) and is not -1
+ *   PCMI_DET_FLAG_LABEL    a live box's label id has no class in label_to_class, or its class is outside [0, n_class)
+ *   PCMI_DET_FLAG_BOXES    n_boxes[b] is outside [0, PCMI_DET_MAX_NUM_OBJ]; the scene then has no box
+ * Common inputs: choices [B, P] (int32, the row WITHIN the scene; repeats allowed -- the reference's random_sampling with
+ * replacement, pc_util.py:35-43); augment (0: no flip, rotation or scale is applied and flip, rot, rot_angle, scale may be
+ * NULL, the reference's augment=False); flip [B, 2] (int32: flip x, flip y; non-zero = on); rot [B, 9] (fp64, row-major R =
+ * rotz(rot_angle), built by the caller with numpy's cos and sin so that both sides use the same bits); scale [B] (fp64; 1
+ * for ScanNet).
+ *
+ * pcmi_det_sample_transform = scannet_detection_dataset.py:103-108,115-128 and sunrgbd_detection_dataset.py:104-106,120,
+ *   139-141,193 for the points.  xyz [n, 3] is fp32, as the arrays on disk are.  Per output row, p = xyz[offsets[b] + choice]:
+ *     flip      x = -x, y = -y (exact)
+ *     rotate    p R^T in fp64 on the widened coordinates: r_i = (x R[i][0] + y R[i][1]) + z R[i][2], rounded to fp32 ONCE -- the
+ *               reference assigns np.dot's float64 result into the float32 array.  (np.dot's own order of the three terms is
+ *               the BLAS's; it can move the fp32 rounding by one step.)  An identity R returns the inputs, a -0.0 as +0.0.
+ *     scale     fp32(fp64(r_i) scale): `point_cloud[:,0:3] *= scale_ratio` multiplies a float32 array by a float64 array in
+ *               place -- numpy computes in float64 and rounds the product to float32 (sunrgbd_detection_dataset.py:138-141).
+ *   point_clouds [B, P, 3] (fp32).  Optional payloads gathered with the same choice: instance, semantic [n] (int32) ->
+ *   out_instance, out_semantic [B, P] (a payload and its output are NULL together).  A row whose choice is out of range
+ *   (PCMI_DET_FLAG_CHOICE) or whose point is not finite (PCMI_DET_FLAG_RANGE) is DROPPED: its point is 0, its payloads -1,
+ *   which pcmi_det_votes_from_instances passes over silently, so it never gets a vote.
+ * pcmi_det_votes_transform = the same for SUN RGB-D, with the stored votes [n, 10] (fp64 -- sunrgbd_data.py writes
+ *   np.zeros((N, 10)): the mask, then three votes) carried along (sunrgbd_detection_dataset.py:109,115-125,144-146,194-195,
+ *   208-209).  In fp64, per vote v with (x, y, z) the FLIPPED point widened: flip v_x = -v_x, v_y = -v_y; e = p + v per
+ *   coordinate; end_i = (e_x R[i][0] + e_y R[i][1]) + e_z R[i][2]; v_i = end_i - fp64(fp32(r_i)) -- the rotated point AFTER
+ *   its rounding to fp32, BEFORE the scale; v_i = v_i scale; vote_label [B, P, 9] (fp32) = v rounded once;
+ *   vote_label_mask [B, P] (int64) = column 0 truncated (astype).  augment == 0: the votes are only rounded to fp32.  A
+ *   dropped row has vote 0 and mask 0.
+ * pcmi_det_votes_from_instances = scannet_detection_dataset.py:137-148 on the sampled, augmented points: point_clouds
+ *   [B, P, 3] (fp32), instance, semantic [B, P] (int32).  Per scene and instance id, (mn, mx) = the bounding box of the
+ *   instance's rows and first = its lowest row (the reference's ind[0]).  If semantic[first] is one of valid_sem [n_valid]
+ *   (int32, n_valid <= 1024; the reference's nyu40ids), every row of the instance gets vote = fp32(0.5 fp32(mn + mx)) - x,
+ *   all in fp32 as in the reference, and mask 1; every other row vote 0, mask 0.  An instance id decides nothing by itself:
+ *   id 0 is left out only because its semantic label is not valid.  vote_label [B, P, 9] (fp32, the vote three times),
+ *   vote_label_mask [B, P] (int64).  The extremes are integer atomic minima and maxima of the order-preserving image of
+ *   the float (-0.0 sorts below +0.0, where numpy may return either zero: only the SIGN of a zero vote can differ), in an
+ *   LDS table per workgroup of 2048 rows, merged into the table in ws.  PCMI_DET_MAX_INSTANCES = 1024: 7 words per id, 28
+ *   KiB of the 64 KiB of LDS a workgroup may declare, which leaves two workgroups per CU room beside it.  Id -1 (a dropped
+ *   row) gets no vote; another id outside the range, PCMI_DET_FLAG_INSTANCE and no vote; a non-finite point,
+ *   PCMI_DET_FLAG_RANGE and no vote.  ws: pcmi_det_votes_from_instances_workspace_bytes(B), 16-byte aligned.
+ * pcmi_det_box_labels: one thread per slot of boxes [B, 64, 8] (fp64; cx, cy, cz, then ScanNet: dx, dy, dz, unused, label id --
+ *   SUN RGB-D: HALF sizes l, w, h, heading, class), of which the first n_boxes[b] (DEVICE int32 [B]) are live; in fp64, each
+ *   output rounded once to its dtype.
+ *   mode PCMI_DET_SCANNET (scannet_detection_dataset.py:110-129,150-167, model_util_scannet.py:70-91): on ALL 64 slots, live
+ *     or padded (zero): flip cx = -1 cx, cy = -1 cy (a padded zero becomes -0.0, as in the reference); rotate_aligned_boxes: c
+ *     = ((cx R[i][0] + cy R[i][1]) + cz R[i][2]); with hx = dx / 2, hy = dy / 2 and the corners (-hx, -hy), (hx, -hy), (hx,
+ *     hy), (-hx, hy): X = (u R[0][0] + v R[0][1]) + 0 R[0][2], Y = (u R[1][0] + v R[1][1]) + 0 R[1][2]; dx = 2 max X, dy = 2 max
+ *     Y, dz kept.  center_label = c.  Live slots: class = label_to_class[label id] (int32 [n_lut], -1 = none; the reference's
+ *     nyu40id2class), size_class = sem_cls = class, size_residual = size - mean_size[class] (fp64 [n_class, 3]); heading 0.
+ *   mode PCMI_DET_SUNRGBD (sunrgbd_detection_dataset.py:107-108,121-122,142-143,151-191, model_util_sunrgbd.py:38-65,
+ *     sunrgbd_utils.py:226-236): live slots only, the padded ones stay +0.  flip cx = -1 cx, heading = pi - heading (flip y
+ *     does not touch a SUN RGB-D box: the reference has none); c = p R^T as above; heading = heading - rot_angle[b] (fp64 [B]);
+ *     c = c scale, (l, w, h) = (l, w, h) scale.  angle2class with Python's float %: a % m = fmod(a, m), plus m if that is
+ *     negative -- the result takes the divisor's sign, a zero result is +0: ang = heading % 2pi; per = 2pi / num_heading_bin;
+ *     shifted = (ang + per / 2) % 2pi; class = trunc(shifted / per); residual = shifted - (class per + per / 2).  size_class =
+ *     sem_cls = the box's class; size_residual = (l, w, h) 2 - mean_size[class].  center_label = ((min + max) / 2) per axis
+ *     over the eight corners of my_compute_box_3d: with (co, si) = heading_cs [B, 64, 2] (fp64: cos and sin of -1 heading, the
+ *     FINAL heading, from the caller's numpy -- the device's cos is not numpy's) and corner offsets x = (-l, l, l, -l, -l, l,
+ *     l, -l), y = (w, w, -w, -w, w, w, -w, -w), z = (h, h, h, h, -h, -h, -h, -h): X = ((co x + (-si) y) + 0 z) + cx, Y = ((si x
+ *     + co y) + 0 z) + cy, Z = ((0 x + 0 y) + 1 z) + cz.
+ *   Outputs [B, 64(, 3)]: center_label, size_residual_label (fp32 [.., 3]), heading_class_label, size_class_label,
+ *   sem_cls_label (int64), heading_residual_label, box_label_mask (fp32; 1 for a live slot).  A live box that is not finite
+ *   counts as a slot of zeros with mask 1 -- class 0, no residual, no heading (PCMI_DET_FLAG_RANGE); one without a class gets
+ *   class 0 and zero residuals (PCMI_DET_FLAG_LABEL).
+ * pcmi_det_voxelize = voxelized_dataset.py:37-63 for the batch.  vox = floor(p / fp32(voxel_size)) in fp32 -- numpy divides a
+ *   float32 array by a Python float in float32 -- as int32; a row outside +-2^20 (or NaN) is dropped with
+ *   PCMI_DET_FLAG_RANGE.  Then pcmi_seg_quantize on (vox, offsets b P, the scenes' minima) without labels, and the minimum is
+ *   added back: voxel_coords [M, 4] (int32: b, x, y, z), voxel_inds [M] (int32: the voxel's FIRST row, minus b P), voxel_feats
+ *   [M, 3] (fp32 ones); the three arrays hold B P rows, of which the first M = counts[B] are written; counts [B + 1] (DEVICE
+ *   int64) = the voxels per scene, then M.  Scenes in order; within a scene the order of first occurrence (the reference's
+ *   is that of a hash-map walk and unspecified).  ws: pcmi_det_voxelize_workspace_bytes(B, P), 16-byte aligned. */
+#define PCMI_DET_FLAG_RANGE 1
+#define PCMI_DET_FLAG_SPAN 2
+#define PCMI_DET_FLAG_CHOICE 4
+#define PCMI_DET_FLAG_INSTANCE 8
+#define PCMI_DET_FLAG_LABEL 16
+#define PCMI_DET_FLAG_BOXES 32
+#define PCMI_DET_MAX_INSTANCES 1024
+#define PCMI_DET_MAX_NUM_OBJ 64
+#define PCMI_DET_SCANNET 0
+#define PCMI_DET_SUNRGBD 1
+int pcmi_det_sample_transform(const float* xyz, const int64_t* offsets, int64_t n, int64_t B, int64_t num_points,
+                              const int32_t* choices, int augment, const int32_t* flip, const double* rot, const double* scale,
+                              const int32_t* instance, const int32_t* semantic, float* point_clouds, int32_t* out_instance,
+                              int32_t* out_semantic, int32_t* flags, pcmi_stream_t stream);
+int pcmi_det_votes_transform(const float* xyz, const double* votes, const int64_t* offsets, int64_t n, int64_t B,
+                             int64_t num_points, const int32_t* choices, int augment, const int32_t* flip, const double* rot,
+                             const double* scale, float* point_clouds, float* vote_label, int64_t* vote_label_mask,
+                             int32_t* flags, pcmi_stream_t stream);
+size_t pcmi_det_votes_from_instances_workspace_bytes(int64_t B);
+int pcmi_det_votes_from_instances(const float* point_clouds, const int32_t* instance, const int32_t* semantic, int64_t B,
+                                  int64_t num_points, const int32_t* valid_sem, int n_valid, float* vote_label,
+                                  int64_t* vote_label_mask, int32_t* flags, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_det_box_labels(const double* boxes, const int32_t* n_boxes, int64_t B, int mode, int augment, const int32_t* flip,
+                        const double* rot, const double* rot_angle, const double* scale, const double* heading_cs,
+                        const int32_t* label_to_class, int n_lut, const double* mean_size, int n_class, int num_heading_bin,
+                        float* center_label, int64_t* heading_class_label, float* heading_residual_label,
+                        int64_t* size_class_label, float* size_residual_label, int64_t* sem_cls_label, float* box_label_mask,
+                        int32_t* flags, pcmi_stream_t stream);
+size_t pcmi_det_voxelize_workspace_bytes(int64_t B, int64_t num_points);
+int pcmi_det_voxelize(const float* point_clouds, int64_t B, int64_t num_points, double voxel_size, int32_t* voxel_coords,
+                      int32_t* voxel_inds, float* voxel_feats, int64_t* counts, int32_t* flags, void* ws, size_t ws_bytes,
+                      pcmi_stream_t stream);
+
 int pcmi_sgd_step(float* w, const float* g, float* v, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, pcmi_stream_t stream);
 /* The same with torch's dampening (the downstream fine-tuning's optimiser: SGD(lr, sgd_momentum, dampening =

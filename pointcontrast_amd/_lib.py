@@ -201,6 +201,16 @@ PROTOTYPES = {
     "pcmi_seg_color_augment_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_seg_color_augment": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, C.c_int, c_vp, c_i64, c_i32,
                                          c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_det_sample_transform": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp]),
+    "pcmi_det_votes_transform": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp]),
+    "pcmi_det_votes_from_instances_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_det_votes_from_instances": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_det_box_labels": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_vp, C.c_int,
+                                      C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pcmi_det_voxelize_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_det_voxelize": (C.c_int, [c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

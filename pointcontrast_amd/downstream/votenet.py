@@ -496,3 +496,175 @@ class APCalculator(object):
 
 
 _NO_CLASS = 1 << 30  # the class of a detection that was not kept: sorted behind every class, scored by none
+
+
+# ---- the input side: raw scans -> the batch dict, on the device (csrc/detect_input.hip) --------------------------------------------
+MAX_NUM_OBJ = PF.DET_MAX_NUM_OBJ
+SCANNET_NYU40IDS = (3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39)  # model_util_scannet.py:25
+DET_ROT_RANGE = {"scannet": np.pi / 18, "sunrgbd": np.pi / 3}  # the full width of the rotation draw: +-5 and +-30 degrees
+
+
+def rotz(t):
+  """pc_util.rotz of the reference: the rotation about z from numpy's cos and sin (the kernels take the matrix as data)."""
+  c, s = np.cos(t), np.sin(t)
+  return np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]], dtype=np.float64)
+
+
+class DetectionDraws:
+  """Every random quantity of one detection batch, on the host: choices int32 [B, num_points] (the row within the scene),
+  flip_x, flip_y bool [B], rot_angle float64 [B], scale float64 [B]; augment False = the reference's augment=False (only
+  the choice is applied)."""
+
+  def __init__(self, choices, flip_x=None, flip_y=None, rot_angle=None, scale=None, augment=True):
+    self.choices = np.ascontiguousarray(choices, dtype=np.int32)
+    B = self.choices.shape[0]
+    self.flip_x = np.zeros(B, bool) if flip_x is None else np.asarray(flip_x, dtype=bool)
+    self.flip_y = np.zeros(B, bool) if flip_y is None else np.asarray(flip_y, dtype=bool)
+    self.rot_angle = np.zeros(B, np.float64) if rot_angle is None else np.asarray(rot_angle, dtype=np.float64)
+    self.scale = np.ones(B, np.float64) if scale is None else np.asarray(scale, dtype=np.float64)
+    self.augment = bool(augment)
+
+  @staticmethod
+  def sample(sizes, num_points, dataset, generator=None, augment=True):
+    """Draws by the reference's distributions (scannet_detection_dataset.py:103-104,115-126, sunrgbd_detection_dataset.py:
+    104-112,139,193, pc_util.py:35-43): a choice of num_points rows without replacement where the scan has at least that many,
+    with replacement otherwise; flips with probability 1/2 (u > 0.5; no y flip for SUN RGB-D); the angle u w - w / 2 with w =
+    pi / 18 (ScanNet) or pi / 3 (SUN RGB-D); the scale u 0.3 + 0.85 for SUN RGB-D only.  generator: a numpy Generator or a
+    seed; the same seed gives the same draws.  augment False: identity draws apart from the choice."""
+    assert dataset in DET_ROT_RANGE, "dataset: 'scannet' or 'sunrgbd'"
+    rng = generator if isinstance(generator, np.random.Generator) else np.random.default_rng(generator)
+    B, w = len(sizes), DET_ROT_RANGE[dataset]
+    choices = np.zeros((B, num_points), np.int32)
+    d = DetectionDraws(choices, augment=augment)
+    for b, n in enumerate(sizes):
+      if n > 0:
+        choices[b] = rng.choice(int(n), num_points, replace=int(n) < num_points)
+      if not augment:
+        continue
+      d.flip_x[b] = rng.random() > 0.5
+      if dataset == "scannet":
+        d.flip_y[b] = rng.random() > 0.5
+      d.rot_angle[b] = (rng.random() * w) - w / 2
+      if dataset == "sunrgbd":
+        d.scale[b] = rng.random() * 0.3 + 0.85
+    return d
+
+  def rot(self):
+    """float64 [B, 9]: rotz(rot_angle) per scene."""
+    return np.stack([rotz(t).reshape(9) for t in self.rot_angle])
+
+  def flip(self):
+    return np.stack([self.flip_x, self.flip_y], 1).astype(np.int32)
+
+
+def _upload(arrays, device):
+  """ONE host -> device copy for a dict of numpy arrays: they are packed, 16-byte aligned, into one byte buffer; returns the
+  dict of device tensors, views of the copy."""
+  spans, total = {}, 0
+  for k, a in arrays.items():
+    a = np.ascontiguousarray(a)
+    arrays[k] = a
+    spans[k] = (total, a.nbytes)
+    total += (a.nbytes + 15) // 16 * 16
+  host = np.zeros(max(total, 16), np.uint8)
+  for k, a in arrays.items():
+    o, nb = spans[k]
+    host[o:o + nb] = a.reshape(-1).view(np.uint8)
+  dev = torch.from_numpy(host).to(device)
+  out = {}
+  for k, a in arrays.items():
+    o, nb = spans[k]
+    out[k] = dev[o:o + nb].view(getattr(torch, a.dtype.name)).reshape(a.shape)
+  return out
+
+
+class DetectionInputPipeline:
+  """Raw scans -> the batch dict of the reference's detection fine-tuning (VoxelizationDataset over ScannetDetectionDataset or
+  SunrgbdDetectionVotesDataset, then collate_fn) as device tensors: ONE upload, pcmi_det_sample_transform /
+  pcmi_det_votes_transform, pcmi_det_votes_from_instances, pcmi_det_box_labels, pcmi_det_voxelize, ONE read-back (the flags
+  and the voxel counts).  The sparse-backbone recipe: xyz only, no colour and no height column.  Differences from the reference
+  (INTEGRATION.md B2): voxel rows leave in the order of first occurrence; the choices are data; a flagged scene raises."""
+
+  def __init__(self, dataset, num_points, voxel_size, device=None, valid_sem=None, label_to_class=None, mean_size_arr=None,
+               num_heading_bin=None):
+    assert dataset in PF.DET_MODES, "dataset: 'scannet' or 'sunrgbd'"
+    assert mean_size_arr is not None, "mean_size_arr [n_class, 3]: the dataset config's mean sizes"
+    self.dataset, self.num_points, self.voxel_size = dataset, int(num_points), float(voxel_size)
+    self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    self.num_heading_bin = int(num_heading_bin) if num_heading_bin is not None else (1 if dataset == "scannet" else 12)
+    ids = SCANNET_NYU40IDS if valid_sem is None else [int(v) for v in valid_sem]
+    if label_to_class is None:  # nyu40id2class: the position of the id in nyu40ids
+      label_to_class = np.full(max(ids) + 1, -1, np.int32)
+      label_to_class[np.asarray(ids)] = np.arange(len(ids))
+    const = _upload(dict(valid_sem=np.asarray(ids, dtype=np.int32), label_to_class=np.asarray(label_to_class, dtype=np.int32),
+                         mean_size=np.asarray(mean_size_arr, dtype=np.float64).reshape(-1, 3)), self.device)
+    self._valid, self._lut, self._mean = const["valid_sem"], const["label_to_class"], const["mean_size"]
+
+  def host_inputs(self, scenes, draws):
+    """The numpy arrays that one batch uploads (what tests feed the restatement with)."""
+    B, scannet = len(scenes), self.dataset == "scannet"
+    sizes = [len(s[0]) for s in scenes]
+    for s in scenes:
+      assert np.asarray(s[0]).dtype == np.float32, "points: float32 [n, 3], as the arrays on disk are"
+    a = dict(offsets=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
+             xyz=np.concatenate([np.asarray(s[0], dtype=np.float32).reshape(-1, 3) for s in scenes]),
+             choices=draws.choices)
+    boxes = np.zeros((B, MAX_NUM_OBJ, 8), np.float64)
+    n_boxes = np.zeros(B, np.int32)
+    for b, s in enumerate(scenes):
+      bx = np.asarray(s[3] if scannet else s[1], dtype=np.float64)
+      k = bx.shape[0]
+      assert k <= MAX_NUM_OBJ, "scene %d: %d boxes, at most %d" % (b, k, MAX_NUM_OBJ)
+      n_boxes[b] = k
+      if k and scannet:
+        boxes[b, :k, 0:6], boxes[b, :k, 7] = bx[:, 0:6], bx[:, -1]
+      elif k:
+        boxes[b, :k] = bx[:, 0:8]
+    a["boxes"], a["n_boxes"] = boxes, n_boxes
+    if scannet:
+      a["instance"] = np.concatenate([np.asarray(s[1]).reshape(-1) for s in scenes]).astype(np.int32)
+      a["semantic"] = np.concatenate([np.asarray(s[2]).reshape(-1) for s in scenes]).astype(np.int32)
+    else:
+      a["votes"] = np.concatenate([np.asarray(s[2], dtype=np.float64).reshape(-1, 10) for s in scenes])
+      h = boxes[:, :, 6].copy()  # the final heading, as pcmi_det_box_labels computes it; its cos and sin are numpy's
+      if draws.augment:
+        h = np.where(draws.flip_x[:, None], np.pi - h, h) - draws.rot_angle[:, None]
+      h = np.where((np.arange(MAX_NUM_OBJ)[None] < n_boxes[:, None]) & np.isfinite(h), h, 0.0)
+      a["heading_cs"] = np.stack([np.cos(-1 * h), np.sin(-1 * h)], -1)
+    if draws.augment:
+      a.update(flip=draws.flip(), rot=draws.rot(), rot_angle=draws.rot_angle, scale=draws.scale)
+    return a
+
+  def __call__(self, scenes, draws=None):
+    """scenes: a list of raw scans -- ScanNet (vertices float32 [n, 3], instance_labels [n], semantic_labels [n],
+    instance_bboxes [k, 7]), SUN RGB-D (points float32 [n, 3], bboxes [k, 8], point_votes float64 [n, 10]).  draws: a
+    DetectionDraws; None draws with DetectionDraws.sample(augment=False) from a fresh generator.  Returns the batch dict as
+    device tensors: point_clouds, center_label, heading_class_label, heading_residual_label, size_class_label,
+    size_residual_label, sem_cls_label, box_label_mask, vote_label, vote_label_mask, voxel_coords int32 [M, 4], voxel_inds int32
+    [M], voxel_feats float32 [M, 3]."""
+    B, dev, P = len(scenes), self.device, self.num_points
+    assert B >= 1, "at least one scene"
+    if draws is None:
+      draws = DetectionDraws.sample([len(s[0]) for s in scenes], P, self.dataset, augment=False)
+    assert draws.choices.shape == (B, P), "draws: choices [B, num_points]"
+    d = _upload(self.host_inputs(scenes, draws), dev)
+    aug = dict(augment=draws.augment, flip=d.get("flip"), rot=d.get("rot"), scale=d.get("scale"))
+    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+    if self.dataset == "scannet":
+      s = PF.det_sample_transform(d["xyz"], d["offsets"], d["choices"], instance=d["instance"], semantic=d["semantic"], flags=flags, **aug)
+      v = PF.det_votes_from_instances(s["point_clouds"], s["out_instance"], s["out_semantic"], self._valid, flags=flags)
+    else:
+      s = v = PF.det_votes_transform(d["xyz"], d["votes"], d["offsets"], d["choices"], flags=flags, **aug)
+    out = PF.det_box_labels(d["boxes"], d["n_boxes"], self.dataset, self._mean, rot_angle=d.get("rot_angle"), heading_cs=d.get("heading_cs"),
+                            label_to_class=self._lut if self.dataset == "scannet" else None, num_heading_bin=self.num_heading_bin,
+                            flags=flags, **aug)
+    x = PF.det_voxelize(s["point_clouds"], self.voxel_size, flags=flags)
+    host = torch.cat([x["counts"], flags.to(torch.int64)]).cpu().numpy()  # the batch's one read-back
+    msg = PF.det_flags_message(host[B + 1:])
+    if msg:
+      raise ValueError(msg)
+    M = int(host[B])
+    del out["flags"]
+    out.update(point_clouds=s["point_clouds"], vote_label=v["vote_label"], vote_label_mask=v["vote_label_mask"],
+               voxel_coords=x["voxel_coords"][:M], voxel_inds=x["voxel_inds"][:M], voxel_feats=x["voxel_feats"][:M])
+    return out

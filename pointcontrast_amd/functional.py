@@ -1283,3 +1283,167 @@ def seg_color_augment(feats_src, coords, n_scenes, index=None, labels=None, para
                                    1 if normalize else 0, ptr(lut), 0 if lut is None else lut.shape[0], int(ignore_label),
                                    ptr(out), ws, wsb, cur_stream(dev)))
   return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The input of detection fine-tuning (csrc/detect_input.hip): what ScannetDetectionDataset / SunrgbdDetectionVotesDataset
+# __getitem__ and VoxelizationDataset + collate_fn of the reference (downstream/votenet_det_new) do per scan on the host, for a
+# batch.  None of these is differentiable and none synchronises; errors arrive in `flags` (int32 [B], DET_FLAG_* bits per scene).
+# ---------------------------------------------------------------------------------------------------------------------
+DET_FLAG_RANGE, DET_FLAG_SPAN, DET_FLAG_CHOICE, DET_FLAG_INSTANCE, DET_FLAG_LABEL, DET_FLAG_BOXES = 1, 2, 4, 8, 16, 32
+DET_FLAG_NAMES = {DET_FLAG_RANGE: "a chosen point or a box is not finite, or a voxel coordinate is outside +-2^20",
+                  DET_FLAG_SPAN: "a voxel coordinate lies 2^18 or more above the scene's minimum",
+                  DET_FLAG_CHOICE: "a choice is outside the scene's rows",
+                  DET_FLAG_INSTANCE: "an instance id is outside [0, 1024)",
+                  DET_FLAG_LABEL: "a box's label has no class",
+                  DET_FLAG_BOXES: "the number of boxes is outside [0, 64]"}
+DET_MAX_INSTANCES = 1024  # PCMI_DET_MAX_INSTANCES
+DET_MAX_NUM_OBJ = 64      # PCMI_DET_MAX_NUM_OBJ, the reference's MAX_NUM_OBJ
+DET_MODES = {"scannet": 0, "sunrgbd": 1}
+
+
+def det_flags_message(flags_host):
+  """The exception text for a read-back flags array (None if no bit is set): every flagged scene with its causes."""
+  bad = ["scene %d: %s" % (b, "; ".join(t for bit, t in DET_FLAG_NAMES.items() if int(f) & bit) or "flag %d" % int(f))
+         for b, f in enumerate(flags_host) if int(f)]
+  return "detection input: " + " | ".join(bad) if bad else None
+
+
+def _det_draws(dev, B, augment, flip, rot, scale, who):
+  if not augment:
+    return None, None, None
+  fl = _i32c(torch.as_tensor(flip), dev).reshape(-1, 2)
+  R = _f64c(rot, dev, who).reshape(-1, 9)
+  sc = _f64c(scale, dev, who).reshape(-1)
+  assert fl.shape[0] == B and R.shape[0] == B and sc.shape[0] == B, who + ": flip [B, 2], rot [B, 9], scale [B]"
+  return fl, R, sc
+
+
+def _det_sample_args(xyz, offsets, choices, who):
+  require_cuda(xyz, who)
+  dev = xyz.device
+  x, offs = _f32c(xyz, who), _offsets(offsets, dev)
+  ch = _i32c(torch.as_tensor(choices), dev)
+  assert x.dim() == 2 and x.shape[1] == 3 and offs.dim() == 1 and offs.shape[0] >= 2, who + ": xyz [n, 3], offsets [B + 1]"
+  B = offs.shape[0] - 1
+  assert ch.dim() == 2 and ch.shape[0] == B and ch.shape[1] >= 1, who + ": choices [B, num_points]"
+  return dev, x, offs, ch, B, ch.shape[1]
+
+
+def det_sample_transform(xyz, offsets, choices, augment=True, flip=None, rot=None, scale=None, instance=None, semantic=None,
+                         flags=None):
+  """pcmi_det_sample_transform.  xyz float32 [n, 3], offsets [B + 1], choices int32 [B, P] (rows within the scene); with
+  augment: flip [B, 2], rot float64 [B, 9], scale float64 [B].  instance, semantic int32 [n] (optional payloads).  Returns a
+  dict of device tensors: point_clouds float32 [B, P, 3], out_instance / out_semantic int32 [B, P] (None without the
+  payload), flags int32 [B]."""
+  dev, x, offs, ch, B, P = _det_sample_args(xyz, offsets, choices, "det_sample_transform")
+  fl, R, sc = _det_draws(dev, B, augment, flip, rot, scale, "det_sample_transform")
+  ins = None if instance is None else _i32c(torch.as_tensor(instance), dev).reshape(-1)
+  sem = None if semantic is None else _i32c(torch.as_tensor(semantic), dev).reshape(-1)
+  assert (ins is None or ins.shape[0] == x.shape[0]) and (sem is None or sem.shape[0] == x.shape[0]), \
+      "det_sample_transform: instance [n], semantic [n]"
+  flags = _seg_flags(flags, B, dev)
+  pc = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
+  oi = None if ins is None else torch.empty((B, P), dtype=torch.int32, device=dev)
+  os_ = None if sem is None else torch.empty((B, P), dtype=torch.int32, device=dev)
+  check(lib.pcmi_det_sample_transform(ptr(x), ptr(offs), x.shape[0], B, P, ptr(ch), 1 if augment else 0, ptr(fl), ptr(R), ptr(sc),
+                                      ptr(ins), ptr(sem), ptr(pc), ptr(oi), ptr(os_), ptr(flags), cur_stream(dev)))
+  return dict(point_clouds=pc, out_instance=oi, out_semantic=os_, flags=flags)
+
+
+def det_votes_transform(xyz, votes, offsets, choices, augment=True, flip=None, rot=None, scale=None, flags=None):
+  """pcmi_det_votes_transform: det_sample_transform with the stored votes float64 [n, 10] of SUN RGB-D carried along.  Returns
+  point_clouds float32 [B, P, 3], vote_label float32 [B, P, 9], vote_label_mask int64 [B, P], flags."""
+  dev, x, offs, ch, B, P = _det_sample_args(xyz, offsets, choices, "det_votes_transform")
+  v = _f64c(votes, dev, "det_votes_transform")
+  assert v.shape == (x.shape[0], 10), "det_votes_transform: votes float64 [n, 10]"
+  fl, R, sc = _det_draws(dev, B, augment, flip, rot, scale, "det_votes_transform")
+  flags = _seg_flags(flags, B, dev)
+  pc = torch.empty((B, P, 3), dtype=torch.float32, device=dev)
+  vl = torch.empty((B, P, 9), dtype=torch.float32, device=dev)
+  vm = torch.empty((B, P), dtype=torch.int64, device=dev)
+  check(lib.pcmi_det_votes_transform(ptr(x), ptr(v), ptr(offs), x.shape[0], B, P, ptr(ch), 1 if augment else 0, ptr(fl), ptr(R),
+                                     ptr(sc), ptr(pc), ptr(vl), ptr(vm), ptr(flags), cur_stream(dev)))
+  return dict(point_clouds=pc, vote_label=vl, vote_label_mask=vm, flags=flags)
+
+
+def det_votes_from_instances(point_clouds, instance, semantic, valid_sem, flags=None):
+  """pcmi_det_votes_from_instances.  point_clouds float32 [B, P, 3], instance and semantic int32 [B, P], valid_sem int32
+  [n_valid].  Returns vote_label float32 [B, P, 9], vote_label_mask int64 [B, P], flags int32 [B]."""
+  require_cuda(point_clouds, "det_votes_from_instances")
+  dev = point_clouds.device
+  pc = _f32c(point_clouds, "det_votes_from_instances")
+  assert pc.dim() == 3 and pc.shape[2] == 3 and pc.shape[1] >= 1, "det_votes_from_instances: point_clouds [B, P, 3]"
+  B, P = pc.shape[0], pc.shape[1]
+  ins, sem = _i32c(torch.as_tensor(instance), dev).reshape(-1), _i32c(torch.as_tensor(semantic), dev).reshape(-1)
+  assert ins.shape[0] == B * P and sem.shape[0] == B * P, "det_votes_from_instances: instance [B, P], semantic [B, P]"
+  vs = _i32c(torch.as_tensor(valid_sem), dev).reshape(-1)
+  flags = _seg_flags(flags, B, dev)
+  vl = torch.empty((B, P, 9), dtype=torch.float32, device=dev)
+  vm = torch.empty((B, P), dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_det_votes_from_instances_workspace_bytes(B), dev)
+  check(lib.pcmi_det_votes_from_instances(ptr(pc), ptr(ins), ptr(sem), B, P, ptr(vs), vs.shape[0], ptr(vl), ptr(vm), ptr(flags), ws,
+                                          wsb, cur_stream(dev)))
+  return dict(vote_label=vl, vote_label_mask=vm, flags=flags)
+
+
+def det_box_labels(boxes, n_boxes, dataset, mean_size, augment=True, flip=None, rot=None, rot_angle=None, scale=None,
+                   heading_cs=None, label_to_class=None, num_heading_bin=1, flags=None):
+  """pcmi_det_box_labels.  boxes float64 [B, 64, 8] on the device, n_boxes int32 [B], dataset "scannet" or "sunrgbd", mean_size
+  float64 [n_class, 3]; with augment: flip [B, 2], rot [B, 9], and for SUN RGB-D rot_angle [B], scale [B]; heading_cs float64
+  [B, 64, 2] (SUN RGB-D: cos and sin of -1 * the final heading); label_to_class int32 [n_lut] (ScanNet).  Returns the
+  reference's label keys as device tensors [B, 64(, 3)], and flags."""
+  require_cuda(boxes, "det_box_labels")
+  dev = boxes.device
+  bx = _f64c(boxes, dev, "det_box_labels")
+  assert bx.dim() == 3 and bx.shape[1:] == (DET_MAX_NUM_OBJ, 8), "det_box_labels: boxes [B, 64, 8]"
+  B, mode = bx.shape[0], DET_MODES[dataset]
+  nb = _i32c(torch.as_tensor(n_boxes), dev).reshape(-1)
+  ms = _f64c(mean_size, dev, "det_box_labels").reshape(-1, 3)
+  assert nb.shape[0] == B and ms.shape[0] >= 1, "det_box_labels: n_boxes [B], mean_size [n_class, 3]"
+  fl = R = ra = sc = None
+  if augment:
+    fl, R = _i32c(torch.as_tensor(flip), dev).reshape(-1, 2), _f64c(rot, dev, "det_box_labels").reshape(-1, 9)
+    assert fl.shape[0] == B and R.shape[0] == B, "det_box_labels: flip [B, 2], rot [B, 9]"
+    if mode == 1:
+      ra, sc = _f64c(rot_angle, dev, "det_box_labels").reshape(-1), _f64c(scale, dev, "det_box_labels").reshape(-1)
+      assert ra.shape[0] == B and sc.shape[0] == B, "det_box_labels: rot_angle [B], scale [B]"
+  cs = None if heading_cs is None else _f64c(heading_cs, dev, "det_box_labels")
+  assert cs is None or cs.shape == (B, DET_MAX_NUM_OBJ, 2), "det_box_labels: heading_cs [B, 64, 2]"
+  lut = None if label_to_class is None else _i32c(torch.as_tensor(label_to_class), dev).reshape(-1)
+  flags = _seg_flags(flags, B, dev)
+  K = DET_MAX_NUM_OBJ
+  out = dict(center_label=torch.empty((B, K, 3), dtype=torch.float32, device=dev),
+             heading_class_label=torch.empty((B, K), dtype=torch.int64, device=dev),
+             heading_residual_label=torch.empty((B, K), dtype=torch.float32, device=dev),
+             size_class_label=torch.empty((B, K), dtype=torch.int64, device=dev),
+             size_residual_label=torch.empty((B, K, 3), dtype=torch.float32, device=dev),
+             sem_cls_label=torch.empty((B, K), dtype=torch.int64, device=dev),
+             box_label_mask=torch.empty((B, K), dtype=torch.float32, device=dev), flags=flags)
+  check(lib.pcmi_det_box_labels(ptr(bx), ptr(nb), B, mode, 1 if augment else 0, ptr(fl), ptr(R), ptr(ra), ptr(sc), ptr(cs), ptr(lut),
+                                0 if lut is None else lut.shape[0], ptr(ms), ms.shape[0], int(num_heading_bin), ptr(out["center_label"]),
+                                ptr(out["heading_class_label"]), ptr(out["heading_residual_label"]), ptr(out["size_class_label"]),
+                                ptr(out["size_residual_label"]), ptr(out["sem_cls_label"]), ptr(out["box_label_mask"]), ptr(flags),
+                                cur_stream(dev)))
+  return out
+
+
+def det_voxelize(point_clouds, voxel_size, flags=None):
+  """pcmi_det_voxelize.  point_clouds float32 [B, P, 3].  Returns a dict of device tensors whose first counts[B] rows are valid
+  -- voxel_coords int32 [B P, 4] (b, x, y, z), voxel_inds int32 [B P] (the voxel's first row within its scene), voxel_feats
+  float32 [B P, 3] (ones) -- and counts int64 [B + 1] (voxels per scene, then their sum), flags int32 [B].  Nothing is read
+  back: slice after reading counts."""
+  require_cuda(point_clouds, "det_voxelize")
+  dev = point_clouds.device
+  pc = _f32c(point_clouds, "det_voxelize")
+  assert pc.dim() == 3 and pc.shape[2] == 3 and pc.shape[1] >= 1, "det_voxelize: point_clouds [B, P, 3]"
+  B, P = pc.shape[0], pc.shape[1]
+  flags = _seg_flags(flags, B, dev)
+  coords = torch.empty((B * P, 4), dtype=torch.int32, device=dev)
+  inds = torch.empty(B * P, dtype=torch.int32, device=dev)
+  feats = torch.empty((B * P, 3), dtype=torch.float32, device=dev)
+  counts = torch.empty(B + 1, dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_det_voxelize_workspace_bytes(B, P), dev)
+  check(lib.pcmi_det_voxelize(ptr(pc), B, P, float(voxel_size), ptr(coords), ptr(inds), ptr(feats), ptr(counts), ptr(flags), ws, wsb,
+                              cur_stream(dev)))
+  return dict(voxel_coords=coords, voxel_inds=inds, voxel_feats=feats, counts=counts, flags=flags)
