@@ -661,14 +661,15 @@ struct BackwardRun {
       const float* stats0 = (const float*)(ps->act.p + ps->stat_off[i]);
       const uint32_t* rbits = (op.relu && ps->bits_off[i] != SIZE_MAX) ? (const uint32_t*)(ps->act.p + ps->bits_off[i]) : nullptr;
       const int64_t sp = ps->split[n.tensors[op.in].level];
-      if (sp < n_in)  // a segment = one forward call of the reference: own statistics, own sums; one launch pair
-        rc = bn_backward2(dy.p, dy.ld, x.p, x.ld, op.relu ? y.p : nullptr, y.ld, n_in, sp, op.cout, params + op.w_off, stats0,
-                          stats0 + op.cout, 3 * op.cout, dx.p, dx.ld, dr.p, dr.ld, pl.acc_res, scratch_g, grads + op.w_off,
-                          grads + op.b_off, ps->ws.p, ps->ws.cap, st, rbits);
-      else
-        rc = bn_backward(dy.p, dy.ld, x.p, x.ld, op.relu ? y.p : nullptr, y.ld, n_in, op.cout, params + op.w_off, stats0,
-                         stats0 + op.cout, dx.p, dx.ld, dr.p, dr.ld, pl.acc_res, scratch_g, scratch_g + op.cout,
-                         grads + op.w_off, grads + op.b_off, ps->ws.p, ps->ws.cap, st, rbits);
+      // a segment = one forward call of the reference: own statistics, own sums; one set of launches for both
+      BnBackwardArgs a;
+      memset(&a, 0, sizeof(a));
+      a.dy = dy.p; a.dy_ld = dy.ld; a.x = x.p; a.x_ld = x.ld; a.relu_mask_y = op.relu ? y.p : nullptr; a.y_ld = y.ld;
+      a.n = n_in; a.split = sp; a.c = op.cout; a.gamma = params + op.w_off;
+      a.save_mean = stats0; a.save_invstd = stats0 + op.cout; a.stat_stride = 3 * op.cout;
+      a.dx = dx.p; a.dx_ld = dx.ld; a.dres = dr.p; a.dres_ld = dr.ld; a.dres_accumulate = pl.acc_res;
+      a.sums = scratch_g; a.acc_dgamma = grads + op.w_off; a.acc_dbeta = grads + op.b_off; a.relu_bits = rbits;
+      rc = bn_backward(a, ps->ws.p, ps->ws.cap, st);
       if (tb >= 0 && !rc) {
         PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tb + 3], st));
         n.timed_hit[tb] |= 2;
@@ -1080,22 +1081,23 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
         uint32_t* rbits = ps.bits_off[i] != SIZE_MAX ? (uint32_t*)(ps.act.p + ps.bits_off[i]) : nullptr;
         if (train) {
           const int64_t sp = ps.split[n.tensors[op.in].level];
+          // two segments: both in one statistics launch + one apply launch.  The running estimates go through the table
+          // then (segment 0, then segment 1), as they do when this pass defers them or another level has two segments.
+          const bool two = sp < n_in, tab = two || defer || two_seg;
           float* stats1 = stats0 + 3 * op.cout;
-          if (sp < n_in) {  // both segments in one statistics launch + one apply launch; running estimates via the table
-            rc = bn_forward_train2(x.p, x.ld, n_in, sp, op.cout, params + op.w_off, params + op.b_off, op.eps, r.p, r.ld, op.relu,
-                                   y.p, y.ld, stats0, stats0 + op.cout, stats0 + 2 * op.cout, 3 * op.cout, w.p, w.cap, sq, rbits);
-            if (op.running_mean)
-              ps.upd_host[ps.upd_n++] = {op.running_mean, op.running_var, stats0, stats0 + 2 * op.cout, op.cout, op.momentum,
-                                         stats1, stats1 + 2 * op.cout};
-          } else {
-            const bool tab = defer || two_seg;
-            rc = bn_forward_train(x.p, x.ld, n_in, op.cout, params + op.w_off, params + op.b_off,
-                                  tab ? nullptr : op.running_mean, tab ? nullptr : op.running_var, op.momentum, op.eps, r.p,
-                                  r.ld, op.relu, y.p, y.ld, stats0, stats0 + op.cout, stats0 + 2 * op.cout, w.p, w.cap, sq, rbits);
-            if (tab && op.running_mean)
-              ps.upd_host[ps.upd_n++] = {op.running_mean, op.running_var, stats0, stats0 + 2 * op.cout, op.cout, op.momentum,
-                                         nullptr, nullptr};
-          }
+          BnTrainForward a;
+          memset(&a, 0, sizeof(a));
+          a.x = x.p; a.x_ld = x.ld; a.residual = r.p; a.res_ld = r.ld; a.y = y.p; a.y_ld = y.ld;
+          a.n = n_in; a.split = sp; a.c = op.cout; a.gamma = params + op.w_off; a.beta = params + op.b_off;
+          a.eps = op.eps; a.relu = op.relu;
+          a.save_mean = stats0; a.save_invstd = stats0 + op.cout; a.save_unbiased = stats0 + 2 * op.cout;
+          a.stat_stride = 3 * op.cout;
+          a.running_mean = tab ? nullptr : op.running_mean; a.running_var = tab ? nullptr : op.running_var;
+          a.momentum = op.momentum; a.relu_bits = rbits;
+          rc = bn_forward_train(a, w.p, w.cap, sq);
+          if (tab && op.running_mean)
+            ps.upd_host[ps.upd_n++] = {op.running_mean, op.running_var, stats0, stats0 + 2 * op.cout, op.cout, op.momentum,
+                                       two ? stats1 : nullptr, two ? stats1 + 2 * op.cout : nullptr};
         } else {
           rc = pcmi_bn_fwd_eval(x.p, x.ld, n_in, op.cout, params + op.w_off, params + op.b_off, op.running_mean,
                                 op.running_var, op.eps, r.p, r.ld, op.relu, y.p, y.ld, (void*)sq);

@@ -38,19 +38,59 @@ bool wgrad_group_add(WgradGroupBuilder* b, const float* in, int64_t in_ld, int64
                      hipStream_t st);
 int wgrad_group_flush(WgradGroupBuilder* b, hipStream_t st);
 
-int bn_backward(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y, int64_t y_ld,
-                int64_t n, int c, const float* gamma, const float* save_mean, const float* save_invstd, float* dx,
-                int64_t dx_ld, float* dres, int64_t dres_ld, int dres_accumulate, float* dgamma, float* dbeta,
-                float* acc_dgamma, float* acc_dbeta, void* ws, size_t ws_bytes, hipStream_t st,
-                const uint32_t* relu_bits = nullptr);
+// ---- BatchNorm (norm.hip): ONE training-forward and ONE backward entry point for one- and two-segment row sets ----------
+// Rows [0, split) and [split, n) are two segments with their own statistics (the two clouds of a pair in one sparse tensor);
+// split == n: one segment.  The kernels are the same either way (gridDim.y, seg_split and the *_stride arguments); what
+// differs between the two forms is decided in norm.hip (bn_path and the numbered notes (1)-(5) beside it):
+//   (1) row blocks: red_geom(n), the wide final kernels beyond kFinalMergeBlocks | red_geom(longest segment) re-cut to
+//       <= kFinalMergeBlocks blocks, always colreduce_final_kernel;
+//   (2) parameter gradients are accumulated (acc_*) in the merge | in the apply launch;
+//   (3) running estimates: updated by the merge when the pointers are given | never (BnRunningUpdate with mean2);
+//   (4) the lean backward statistics are chosen by the TOTAL row count in both forms;
+//   (5) statistics / sums of the second segment lie stat_stride / 2 c floats behind the first's | strides 0.
 // relu_bits (nullable, norm.hip "relu_bits"): the ReLU pattern of a fused BatchNorm(+residual)+ReLU output as one bit per
-// element, [rows][c / 32] words, c a multiple of 32 -- written by the forward functions when relu != 0, read by the backward
-// ones INSTEAD of relu_mask_y (which may then be null)
+// element, [rows][c / 32] words, c a multiple of 32 -- written by the forward when relu != 0, read by the backward INSTEAD
+// of relu_mask_y (which may then be null).
+struct BnTrainForward {
+  const float* x; int64_t x_ld;
+  const float* residual; int64_t res_ld;  // nullable
+  float* y; int64_t y_ld;
+  int64_t n, split;
+  int c;
+  const float* gamma; const float* beta;
+  float eps;
+  int relu;
+  float* save_mean; float* save_invstd;
+  float* save_unbiased;  // nullable
+  int stat_stride;       // two segments: floats from a save_* block of segment 0 to that of segment 1
+  // one segment only, nullable: updated in place.  Null with save_unbiased set: the executor applies the update later, in
+  // program order, with bn_running_update (two passes forwarded concurrently, and every two-segment pass).
+  float* running_mean; float* running_var;
+  float momentum;
+  uint32_t* relu_bits;   // nullable
+};
+int bn_forward_train(const BnTrainForward& a, void* ws, size_t ws_bytes, hipStream_t st);
 
-int bn_forward_train(const float* x, int64_t x_ld, int64_t n, int c, const float* gamma, const float* beta,
-                     float* running_mean, float* running_var, float momentum, float eps, const float* residual,
-                     int64_t res_ld, int relu, float* y, int64_t y_ld, float* save_mean, float* save_invstd,
-                     float* save_unbiased, void* ws, size_t ws_bytes, hipStream_t st, uint32_t* relu_bits = nullptr);
+struct BnBackwardArgs {
+  const float* dy; int64_t dy_ld;
+  const float* x; int64_t x_ld;
+  const float* relu_mask_y; int64_t y_ld;  // nullable: no ReLU (or relu_bits)
+  int64_t n, split;
+  int c;
+  const float* gamma; const float* save_mean; const float* save_invstd;
+  int stat_stride;  // as in the forward
+  float* dx; int64_t dx_ld;
+  float* dres; int64_t dres_ld;  // nullable: gradient of the residual, stored or (dres_accumulate) added to
+  int dres_accumulate;
+  // this call's sums (scratch, overwritten): EITHER dgamma and dbeta, c floats each (one segment: the C ABI), OR `sums`,
+  // 2 c floats per segment, laid out inside: [dgamma | dbeta] for one segment, [segment][dbeta | dgamma] for two
+  float* dgamma; float* dbeta;
+  float* sums;
+  float* acc_dgamma; float* acc_dbeta;  // nullable: += the sums (segment 0, then segment 1)
+  const uint32_t* relu_bits;            // nullable
+};
+int bn_backward(const BnBackwardArgs& a, void* ws, size_t ws_bytes, hipStream_t st);
+
 // deferred running-estimate update of one BatchNorm layer: running = (1 - momentum) * running + momentum * batch
 struct BnRunningUpdate {
   float* running_mean;
@@ -62,14 +102,6 @@ struct BnRunningUpdate {
   const float* mean2;      // nullable: statistics of the second segment of a two-segment pass, applied after the first
   const float* unbiased2;
 };
-int bn_forward_train2(const float* x, int64_t x_ld, int64_t n, int64_t split, int c, const float* gamma, const float* beta,
-                      float eps, const float* residual, int64_t res_ld, int relu, float* y, int64_t y_ld, float* save_mean,
-                      float* save_invstd, float* save_unbiased, int stat_stride, void* ws, size_t ws_bytes, hipStream_t st,
-                      uint32_t* relu_bits = nullptr);
-int bn_backward2(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y, int64_t y_ld, int64_t n,
-                 int64_t split, int c, const float* gamma, const float* save_mean, const float* save_invstd, int stat_stride,
-                 float* dx, int64_t dx_ld, float* dres, int64_t dres_ld, int dres_accumulate, float* sums, float* acc_dgamma,
-                 float* acc_dbeta, void* ws, size_t ws_bytes, hipStream_t st, const uint32_t* relu_bits = nullptr);
 int bn_running_update(const BnRunningUpdate* table_dev, int n_entries, hipStream_t st);
 
 // coords.hip: a cached map as it is -- M == -1 / offs_host unset when pcmi_coords_plan_unet built it and nobody has asked

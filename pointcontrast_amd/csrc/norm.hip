@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 
@@ -158,8 +159,8 @@ __global__ __launch_bounds__(256, MASK == 0 ? 8 : 1) void colreduce_partial_kern
     const float* __restrict__ x, int64_t x_ld, const float* __restrict__ dy, int64_t dy_ld,
     const float* __restrict__ ymask, int64_t y_ld, const float* __restrict__ mean,
     const float* __restrict__ invstd, int64_t n, int c4, int rp, int rows_per_block,
-    float* __restrict__ part /* [nblocks][2][c] */, int64_t seg_split = 0, int in_seg_stride = 0,
-    int64_t part_seg_stride = 0, const uint32_t* __restrict__ bits = nullptr /* MODE 1: the ReLU pattern, see relu_bits */) {
+    float* __restrict__ part /* [nblocks][2][c] */, int64_t seg_split, int in_seg_stride,
+    int64_t part_seg_stride, const uint32_t* __restrict__ bits /* MODE 1: the ReLU pattern, see relu_bits */) {
   __shared__ float4 s_a[256];
   __shared__ float4 s_b[256];
   const int t = threadIdx.x;
@@ -774,8 +775,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
                                                        const float* __restrict__ invstd_or_var, float eps,
                                                        int use_var, const float* __restrict__ res,
                                                        int64_t res_ld, int relu, float* __restrict__ y,
-                                                       int64_t y_ld, int64_t seg_split = INT64_MAX, int seg_stride4 = 0,
-                                                       uint32_t* __restrict__ bits = nullptr /* relu_bits, c4 % 8 == 0 */) {
+                                                       int64_t y_ld, int64_t seg_split, int seg_stride4,
+                                                       uint32_t* __restrict__ bits /* relu_bits, c4 % 8 == 0 */) {
   const int64_t total = n * c4;
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
     const int64_t r = idx / c4;
@@ -829,8 +830,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float* __restrict__ ymask, int64_t y_ld, int64_t n, int c4, const float* __restrict__ gamma,
     const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ sum_g,
     const float* __restrict__ sum_gx, float* __restrict__ dx, int64_t dx_ld, float* __restrict__ dres,
-    int64_t dres_ld, int dres_accumulate, int64_t seg_split = INT64_MAX, int stat_stride4 = 0, int sum_stride4 = 0,
-    float* __restrict__ acc_g = nullptr, float* __restrict__ acc_gx = nullptr, const uint32_t* __restrict__ bits = nullptr) {
+    int64_t dres_ld, int dres_accumulate, int64_t seg_split, int stat_stride4, int sum_stride4,
+    float* __restrict__ acc_g, float* __restrict__ acc_gx, const uint32_t* __restrict__ bits) {
   const int64_t total = n * c4;
   const bool two = seg_split < n;
   const float inv_n0 = 1.0f / (float)(two ? seg_split : n), inv_n1 = two ? 1.0f / (float)(n - seg_split) : 0.f;
@@ -944,6 +945,22 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ a
   *reinterpret_cast<float4*>(out + r * out_ld + sub * 4) = o;
 }
 
+__global__ __launch_bounds__(256) void bn_running_update_kernel(const BnRunningUpdate* __restrict__ tab) {
+  const BnRunningUpdate u = tab[blockIdx.x];
+  for (int ch = threadIdx.x; ch < u.c; ch += 256) {
+    float rm = (1.f - u.momentum) * u.running_mean[ch] + u.momentum * u.mean[ch];
+    float rv = (1.f - u.momentum) * u.running_var[ch] + u.momentum * u.unbiased[ch];
+    if (u.mean2) {  // second segment of the same layer: the second of two forward calls
+      rm = (1.f - u.momentum) * rm + u.momentum * u.mean2[ch];
+      rv = (1.f - u.momentum) * rv + u.momentum * u.unbiased2[ch];
+    }
+    u.running_mean[ch] = rm;
+    u.running_var[ch] = rv;
+  }
+}
+
+// ================================================ host side ================================================================
+
 // PCMI_BN_LEAN_ROWS: from this many rows the backward statistics take the 48-register form of colreduce_partial_kernel
 // (0 = never).  Read per call (A/B in one process).  Same row blocks and the same partial layout, but NOT the same
 // summation order inside a block: the lean kernel has 256 / (c / 2) row lanes where the wide one has 256 / (c / 4), so the
@@ -974,8 +991,56 @@ static int64_t bn_small_rows(bool backward) {
   const int64_t v = e ? (int64_t)atoll(e) : (int64_t)(backward ? 768 : 1536);
   return std::min<int64_t>(v, 128 * kSmallMaxRPT);
 }
-static bool bn_small_eligible(int64_t longest_segment, int c, bool backward = false) {
+static bool bn_small_eligible(int64_t longest_segment, int c, bool backward) {
   return longest_segment > 0 && longest_segment <= bn_small_rows(backward) && c % (4 * kSmallCG) == 0;
+}
+
+// The launches of one BatchNorm call, forward (bwd == nullptr) or backward, decided in ONE place.  The kernels treat one
+// and two segments alike; the numbered notes are the places where the two forms differ in what they compute with.
+struct BnPath {
+  enum Form { kOneLaunch, kMergeFinal, kWideFinal };  // bn_small_*_kernel | partials + colreduce_final_kernel | partials +
+  Form form;                                          // bn_stats_final_kernel / colsum2_final_kernel
+  bool two;             // rows [0, split) and [split, n) with their own statistics
+  bool lean;            // backward statistics by bn_bwd_stats_lean_kernel
+  RedGeom g;            // row blocks of the partial launch (per segment)
+  unsigned grid_y;      // segments
+  int64_t part_seg;     // floats from the first segment's partials to the second's
+  int64_t red_split;    // seg_split of the reduction kernels (0 for one segment: they look at gridDim.y) ...
+  int64_t apply_split;  // ... and of the apply kernels (INT64_MAX: every row is of segment 0)
+  int mask;             // MASK / MASKED: 0 no ReLU, 1 the pattern from y (fp32), 2 from relu_bits
+  int dres;             // DRES: 0 no residual gradient, 1 store, 2 accumulate
+};
+
+static BnPath bn_path(int64_t n, int64_t split, int c, const BnBackwardArgs* bwd) {
+  BnPath p;
+  p.two = split < n;
+  p.grid_y = p.two ? 2u : 1u;
+  p.red_split = p.two ? split : 0;
+  p.apply_split = p.two ? split : INT64_MAX;
+  const int64_t longest = p.two ? std::max(split, n - split) : n;
+  // (1) Row-block geometry.  One segment: red_geom(n), and beyond kFinalMergeBlocks blocks the one-wave-per-channel kernels
+  // merge the partials.  Two segments: the blocks of the LONGEST segment for both, re-cut to at most kFinalMergeBlocks, so
+  // that colreduce_final_kernel always merges them (the wide kernels know no segments).
+  p.g = red_geom(longest, c);
+  if (p.two && p.g.nblocks > kFinalMergeBlocks) {
+    p.g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFinalMergeBlocks), p.g.rp) * p.g.rp);
+    p.g.nblocks = (int)ceil_div(longest, p.g.rows_per_block);
+  }
+  p.part_seg = p.two ? (int64_t)p.g.nblocks * 2 * c : 0;
+  p.form = bn_small_eligible(longest, c, bwd != nullptr) ? BnPath::kOneLaunch
+           : p.g.nblocks <= kFinalMergeBlocks           ? BnPath::kMergeFinal
+                                                        : BnPath::kWideFinal;
+  p.lean = false;
+  p.mask = p.dres = 0;
+  if (bwd) {
+    p.mask = bwd->relu_bits ? 2 : (bwd->relu_mask_y ? 1 : 0);
+    p.dres = bwd->dres ? (bwd->dres_accumulate ? 2 : 1) : 0;
+    // (4) Lean eligibility looks at the TOTAL row count, not the longest segment, in both forms.
+    // (the 48-register kernel finds a row's bit words through x's own offsets: with the bits it needs x_ld == c)
+    p.lean = p.form != BnPath::kOneLaunch && bn_lean_eligible(n, c, bwd->x_ld, bwd->dy_ld, bwd->relu_mask_y ? bwd->y_ld : 0) &&
+             (!bwd->relu_bits || bwd->x_ld == c);
+  }
+  return p;
 }
 
 #define PCMI_BN_SMALL_DISPATCH(KERNEL, ARGS, GRID, LONGEST, ST)                                   \
@@ -993,21 +1058,16 @@ static bool bn_small_eligible(int64_t longest_segment, int c, bool backward = fa
     }                                                                                             \
   } while (0)
 
-static int bn_small_forward(const float* x, int64_t x_ld, int64_t n, int64_t split, int c, const float* gamma, const float* beta,
-                            const float* residual, int64_t res_ld, int relu, float* y, int64_t y_ld, const RedFinal& fin,
-                            hipStream_t st, uint32_t* relu_bits = nullptr) {
-  BnSmallFwd a;
-  a.x = x; a.x_ld = x_ld; a.res = residual; a.res_ld = res_ld; a.y = y; a.y_ld = y_ld;
-  a.n = n; a.split = split; a.gamma = gamma; a.beta = beta; a.relu = relu; a.fin = fin;
-  a.bits = reinterpret_cast<uint16_t*>(relu_bits);
-  const bool two = split < n;
-  const int64_t longest = two ? std::max(split, n - split) : n;
+static int bn_small_forward(const BnSmallFwd& a, int c, hipStream_t st) {
+  const bool two = a.split < a.n;
+  const int64_t longest = two ? std::max(a.split, a.n - a.split) : a.n;
   const dim3 grid((unsigned)(c / (4 * kSmallCG)), two ? 2u : 1u);
   PCMI_BN_SMALL_DISPATCH(bn_small_fwd_kernel, a, grid, longest, st);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
 
+// (one workgroup walks the two segments in order and accumulates)
 static int bn_small_backward(const BnSmallBwd& a, int c, hipStream_t st) {
   const int64_t longest = a.split < a.n ? std::max(a.split, a.n - a.split) : a.n;
   const dim3 grid((unsigned)(c / (4 * kSmallCG)));
@@ -1019,6 +1079,24 @@ static int bn_small_backward(const BnSmallBwd& a, int c, hipStream_t st) {
 static int check_rows(const char* who, const void* p, int64_t ld, int c) {
   PCMI_REQUIRE(p && c > 0 && c % 4 == 0 && c <= 1024 && ld % 4 == 0 && ld >= c && (uintptr_t)p % 16 == 0, PCMI_ERR_INVALID,
                "%s: needs 16-byte aligned rows, c %% 4 == 0, c <= 1024 (c=%d ld=%lld)", who, c, (long long)ld);
+  return PCMI_OK;
+}
+
+// check_rows of every row operand of a call, in order; a nullable one is skipped when null
+struct RowsArg {
+  const char* name;
+  const void* p;
+  int64_t ld;
+  bool nullable;
+};
+static int check_rows_all(const char* who, int c, std::initializer_list<RowsArg> rows) {
+  for (const RowsArg& r : rows) {
+    if (r.nullable && !r.p) continue;
+    char what[64];
+    snprintf(what, sizeof(what), "%s(%s)", who, r.name);
+    const int rc = check_rows(what, r.p, r.ld, c);
+    if (rc) return rc;
+  }
   return PCMI_OK;
 }
 
@@ -1052,9 +1130,151 @@ static int check_rows(const char* who, const void* p, int64_t ld, int c) {
     else if (m_ == 1) colreduce_partial_kernel<1, 1><<<(GRID), 256, 0, (ST)>>>(__VA_ARGS__);            \
     else colreduce_partial_kernel<1, 0><<<(GRID), 256, 0, (ST)>>>(__VA_ARGS__);                         \
   } while (0)
+#define PCMI_BN_BWD_LEAN_LAUNCH(GRID, ST, MASK, ...)                                                    \
+  do {                                                                                                  \
+    const int m_ = (MASK);                                                                              \
+    if (m_ == 2) bn_bwd_stats_lean_kernel<2><<<(GRID), 256, 0, (ST)>>>(__VA_ARGS__);                    \
+    else if (m_ == 1) bn_bwd_stats_lean_kernel<1><<<(GRID), 256, 0, (ST)>>>(__VA_ARGS__);               \
+    else bn_bwd_stats_lean_kernel<0><<<(GRID), 256, 0, (ST)>>>(__VA_ARGS__);                            \
+  } while (0)
 
 static unsigned stream_grid(int64_t total) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 256 * 8));
+}
+
+// Training forward of one or two row segments (internal.h: BnTrainForward): statistics of every segment in one launch
+// (gridDim.y), their merge, one apply pass -- or all of it in one launch (BnPath::kOneLaunch).
+int bn_forward_train(const BnTrainForward& a, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int c = a.c;
+  uint32_t* const relu_bits = (a.relu && c % 32 == 0) ? a.relu_bits : nullptr;
+  const int rc = check_rows_all("bn_fwd_train", c, {{"x", a.x, a.x_ld, false}, {"y", a.y, a.y_ld, false},
+                                                    {"residual", a.residual, a.res_ld, true}});
+  if (rc) return rc;
+  PCMI_REQUIRE(a.gamma && a.beta && a.save_mean && a.save_invstd && a.n > 0 && a.split > 0 && a.split <= a.n &&
+                   a.stat_stride % 4 == 0 && (a.split == a.n || (!a.running_mean && !a.running_var)),
+               PCMI_ERR_INVALID, "bn_fwd_train: bad argument");
+  PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(a.n, c), PCMI_ERR_WORKSPACE, "bn_fwd_train: workspace too small");
+  const BnPath p = bn_path(a.n, a.split, c, nullptr);
+  const RedGeom& g = p.g;
+  // (5) Statistics layout: the save_* block of the second segment lies stat_stride floats behind the first's.
+  const int stat_stride = p.two ? a.stat_stride : 0;
+  float* part = (float*)ws;
+  RedFinal fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.eps = a.eps;
+  fin.save_mean = a.save_mean;
+  fin.save_invstd = a.save_invstd;
+  fin.save_unbiased = a.save_unbiased;
+  fin.out_seg_stride = stat_stride;
+  // (3) Running estimates.  One segment: the merge updates them where the pointers are given.  Two segments: never here --
+  // the update of segment 1 follows that of segment 0, which is the caller's BnRunningUpdate entry with mean2 / unbiased2.
+  if (!p.two) {
+    fin.momentum = a.momentum;
+    fin.running_mean = a.running_mean;
+    fin.running_var = a.running_var;
+  }
+  if (p.form == BnPath::kOneLaunch) {
+    BnSmallFwd s;
+    s.x = a.x; s.x_ld = a.x_ld; s.res = a.residual; s.res_ld = a.res_ld; s.y = a.y; s.y_ld = a.y_ld;
+    s.n = a.n; s.split = a.split; s.gamma = a.gamma; s.beta = a.beta; s.relu = a.relu; s.fin = fin;
+    s.bits = reinterpret_cast<uint16_t*>(relu_bits);
+    return bn_small_forward(s, c, st);
+  }
+  colreduce_partial_kernel<0><<<dim3((unsigned)g.nblocks, p.grid_y), 256, 0, st>>>(
+      a.x, a.x_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, a.n, g.c4, g.rp, g.rows_per_block, part, p.red_split, 0, p.part_seg,
+      nullptr);
+  PCMI_LAUNCH_CHECK();
+  if (p.form == BnPath::kMergeFinal)
+    colreduce_final_kernel<0><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), p.grid_y), 256, 0, st>>>(
+        part, a.n, g.c4, g.rows_per_block, fin, p.red_split, p.part_seg);
+  else
+    bn_stats_final_kernel<<<dim3((unsigned)ceil_div(c, 4)), 256, 0, st>>>(part, g.nblocks, a.n, c, g.rows_per_block, a.eps,
+                                                                         a.momentum, a.running_mean, a.running_var, a.save_mean,
+                                                                         a.save_invstd, a.save_unbiased);
+  PCMI_LAUNCH_CHECK();
+  PCMI_BN_APPLY_LAUNCH(stream_grid(a.n * g.c4), st, a.residual, relu_bits, a.x, a.x_ld, a.n, g.c4, a.gamma, a.beta, a.save_mean,
+                       a.save_invstd, a.eps, 0, a.residual, a.res_ld, a.relu, a.y, a.y_ld, p.apply_split, stat_stride / 4, relu_bits);
+  PCMI_LAUNCH_CHECK();
+  return PCMI_OK;
+}
+
+// Backward of one or two row segments (internal.h: BnBackwardArgs): the sums of every segment in one launch, their merge,
+// one apply pass -- or one launch for all of it.
+int bn_backward(const BnBackwardArgs& args, void* ws, size_t ws_bytes, hipStream_t st) {
+  BnBackwardArgs a = args;
+  const int c = a.c;
+  if (c % 32 != 0) a.relu_bits = nullptr;
+  if (a.relu_bits) a.relu_mask_y = nullptr;  // the pattern comes from the bits: y is not read
+  const int rc = check_rows_all("bn_bwd", c, {{"dy", a.dy, a.dy_ld, false}, {"x", a.x, a.x_ld, false}, {"dx", a.dx, a.dx_ld, false},
+                                              {"y", a.relu_mask_y, a.y_ld, true}, {"dres", a.dres, a.dres_ld, true}});
+  if (rc) return rc;
+  const bool two = a.split < a.n;
+  // (5) Sums layout.  The caller's own dgamma / dbeta (one segment), or inside `sums`: [dgamma | dbeta] for one segment,
+  // [segment][dbeta | dgamma] for two -- the second segment's pair sum_stride = 2 c floats behind the first's, as its
+  // statistics lie stat_stride floats behind.
+  float* const dbeta = a.sums ? (two ? a.sums : a.sums + c) : a.dbeta;
+  float* const dgamma = a.sums ? (two ? a.sums + c : a.sums) : a.dgamma;
+  const int stat_stride = two ? a.stat_stride : 0, sum_stride = two ? 2 * c : 0;
+  PCMI_REQUIRE(a.gamma && a.save_mean && a.save_invstd && dgamma && dbeta && (a.sums || !two) && a.n > 0 && a.split > 0 &&
+                   a.split <= a.n && a.stat_stride % 4 == 0,
+               PCMI_ERR_INVALID, "bn_bwd: bad argument");
+  PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(a.n, c), PCMI_ERR_WORKSPACE, "bn_bwd: workspace too small");
+  const BnPath p = bn_path(a.n, a.split, c, &a);
+  const RedGeom& g = p.g;
+  if (p.form == BnPath::kOneLaunch) {  // (2): the kernel adds segment 0, then segment 1, to acc_*
+    BnSmallBwd s;
+    s.dy = a.dy; s.dy_ld = a.dy_ld; s.x = a.x; s.x_ld = a.x_ld; s.ymask = a.relu_mask_y; s.y_ld = a.y_ld; s.n = a.n; s.split = a.split;
+    s.gamma = a.gamma; s.mean = a.save_mean; s.invstd = a.save_invstd; s.stat_stride = stat_stride;
+    s.dx = a.dx; s.dx_ld = a.dx_ld; s.dres = a.dres; s.dres_ld = a.dres_ld; s.dres_accumulate = a.dres_accumulate;
+    s.sum_g = dbeta; s.sum_gx = dgamma; s.sum_stride = sum_stride; s.acc_g = a.acc_dbeta; s.acc_gx = a.acc_dgamma;
+    s.bits = reinterpret_cast<const uint16_t*>(a.relu_bits);
+    return bn_small_backward(s, c, st);
+  }
+  // (2) Where the parameter gradients are accumulated.  One segment: in the merge (fin.acc_* / colsum2_final_kernel), and
+  // the apply launch gets none.  Two segments: in the apply launch, which adds segment 0 and then segment 1 (sum_stride
+  // apart) -- the merge of a segment cannot order itself behind the other's.
+  float* const merge_acc_dbeta = p.two ? nullptr : a.acc_dbeta;
+  float* const merge_acc_dgamma = p.two ? nullptr : a.acc_dgamma;
+  float* const apply_acc_dbeta = p.two ? a.acc_dbeta : nullptr;
+  float* const apply_acc_dgamma = p.two ? a.acc_dgamma : nullptr;
+  float* part = (float*)ws;
+  RedFinal fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.out_a = dbeta;
+  fin.out_b = dgamma;
+  fin.acc_a = merge_acc_dbeta;
+  fin.acc_b = merge_acc_dgamma;
+  fin.out_seg_stride = sum_stride;
+  const dim3 red_grid((unsigned)g.nblocks, p.grid_y);
+  if (p.lean) {  // (the bit tensor travels as `ymask`, its words per row as y_ld)
+    const float* const mask_p = a.relu_bits ? reinterpret_cast<const float*>(a.relu_bits) : a.relu_mask_y;
+    const int64_t mask_ld = a.relu_bits ? c / 32 : (a.relu_mask_y ? a.y_ld : 0);
+    PCMI_BN_BWD_LEAN_LAUNCH(red_grid, st, p.mask, a.x, a.x_ld, a.dy, a.dy_ld, mask_p, mask_ld, a.save_mean, a.save_invstd, a.n, c,
+                            g.rows_per_block, part, p.red_split, stat_stride, p.part_seg);
+  } else {
+    PCMI_BN_BWD_PARTIAL_LAUNCH(red_grid, st, p.mask, a.x, a.x_ld, a.dy, a.dy_ld, a.relu_mask_y, a.y_ld, a.save_mean, a.save_invstd,
+                               a.n, g.c4, g.rp, g.rows_per_block, part, p.red_split, stat_stride, p.part_seg, a.relu_bits);
+  }
+  PCMI_LAUNCH_CHECK();
+  if (p.form == BnPath::kMergeFinal)
+    colreduce_final_kernel<1><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), p.grid_y), 256, 0, st>>>(
+        part, a.n, g.c4, g.rows_per_block, fin, p.red_split, p.part_seg);
+  else
+    colsum2_final_kernel<<<dim3((unsigned)ceil_div(c, 4)), 256, 0, st>>>(part, g.nblocks, c, dbeta, dgamma, merge_acc_dbeta,
+                                                                        merge_acc_dgamma);
+  PCMI_LAUNCH_CHECK();
+  PCMI_BN_BWD_APPLY_LAUNCH(stream_grid(a.n * g.c4), st, p.mask, p.dres, a.dy, a.dy_ld, a.x, a.x_ld, a.relu_mask_y, a.y_ld, a.n, g.c4,
+                           a.gamma, a.save_mean, a.save_invstd, dbeta, dgamma, a.dx, a.dx_ld, a.dres, a.dres_ld, a.dres_accumulate,
+                           p.apply_split, stat_stride / 4, sum_stride / 4, apply_acc_dbeta, apply_acc_dgamma, a.relu_bits);
+  PCMI_LAUNCH_CHECK();
+  return PCMI_OK;
+}
+
+int bn_running_update(const BnRunningUpdate* table_dev, int n_entries, hipStream_t st) {
+  if (n_entries <= 0) return PCMI_OK;
+  bn_running_update_kernel<<<n_entries, 256, 0, st>>>(table_dev);
+  PCMI_LAUNCH_CHECK();
+  return PCMI_OK;
 }
 
 }  // namespace pcmi
@@ -1072,203 +1292,14 @@ int pcmi_bn_fwd_train(const float* x, int64_t x_ld, int64_t n, int c, const floa
                       float* running_mean, float* running_var, float momentum, float eps, const float* residual,
                       int64_t res_ld, int relu, float* y, int64_t y_ld, float* save_mean, float* save_invstd,
                       void* ws, size_t ws_bytes, pcmi_stream_t stream) {
-  return pcmi::bn_forward_train(x, x_ld, n, c, gamma, beta, running_mean, running_var, momentum, eps, residual, res_ld, relu, y,
-                                y_ld, save_mean, save_invstd, nullptr, ws, ws_bytes, as_stream(stream));
+  BnTrainForward a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.x_ld = x_ld; a.residual = residual; a.res_ld = res_ld; a.y = y; a.y_ld = y_ld;
+  a.n = a.split = n; a.c = c; a.gamma = gamma; a.beta = beta; a.eps = eps; a.relu = relu;
+  a.save_mean = save_mean; a.save_invstd = save_invstd;
+  a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum;
+  return bn_forward_train(a, ws, ws_bytes, as_stream(stream));
 }
-
-}  // extern "C"
-
-namespace pcmi {
-
-// running_mean / running_var may be null (no update) and save_unbiased non-null: the executor then applies the
-// running-estimate update later, in program order, with bn_running_update (two passes forwarded concurrently).
-int bn_forward_train(const float* x, int64_t x_ld, int64_t n, int c, const float* gamma, const float* beta,
-                     float* running_mean, float* running_var, float momentum, float eps, const float* residual,
-                     int64_t res_ld, int relu, float* y, int64_t y_ld, float* save_mean, float* save_invstd,
-                     float* save_unbiased, void* ws, size_t ws_bytes, hipStream_t st, uint32_t* relu_bits) {
-  if (!relu || c % 32 != 0) relu_bits = nullptr;
-  int rc = check_rows("bn_fwd_train(x)", x, x_ld, c);
-  if (rc) return rc;
-  rc = check_rows("bn_fwd_train(y)", y, y_ld, c);
-  if (rc) return rc;
-  if (residual && (rc = check_rows("bn_fwd_train(residual)", residual, res_ld, c))) return rc;
-  PCMI_REQUIRE(gamma && beta && save_mean && save_invstd && n > 0 && c <= 1024, PCMI_ERR_INVALID, "bn_fwd_train: bad argument");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(n, c), PCMI_ERR_WORKSPACE, "bn_fwd_train: workspace too small");
-  const RedGeom g = red_geom(n, c);
-  float* part = (float*)ws;
-  RedFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  const bool small = g.nblocks <= kFinalMergeBlocks;
-  fin.eps = eps;
-  fin.momentum = momentum;
-  fin.running_mean = running_mean;
-  fin.running_var = running_var;
-  fin.save_mean = save_mean;
-  fin.save_invstd = save_invstd;
-  fin.save_unbiased = save_unbiased;
-  if (bn_small_eligible(n, c)) return bn_small_forward(x, x_ld, n, n, c, gamma, beta, residual, res_ld, relu, y, y_ld, fin, st, relu_bits);
-  colreduce_partial_kernel<0><<<g.nblocks, 256, 0, st>>>(x, x_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, n, g.c4, g.rp,
-                                                        g.rows_per_block, part);
-  PCMI_LAUNCH_CHECK();
-  if (small) {
-    colreduce_final_kernel<0><<<(unsigned)ceil_div(g.c4, kFinalCols), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, 0, 0);
-    PCMI_LAUNCH_CHECK();
-  }
-  if (!small) {
-    bn_stats_final_kernel<<<dim3((unsigned)ceil_div(c, 4)), 256, 0, st>>>(part, g.nblocks, n, c, g.rows_per_block, eps, momentum,
-                                                                         running_mean, running_var, save_mean, save_invstd,
-                                                                         save_unbiased);
-    PCMI_LAUNCH_CHECK();
-  }
-  PCMI_BN_APPLY_LAUNCH(stream_grid(n * g.c4), st, residual, relu_bits, x, x_ld, n, g.c4, gamma, beta, save_mean, save_invstd, eps, 0,
-                       residual, res_ld, relu, y, y_ld, INT64_MAX, 0, relu_bits);
-  PCMI_LAUNCH_CHECK();
-  return PCMI_OK;
-}
-
-// Two-segment BatchNorm forward (rows [0, split) and [split, n): own statistics each) in three launches: statistics of
-// both segments (gridDim.y = 2), their merge, then one apply pass.  save_*: [2][3c] blocks (mean, invstd, unbiased)
-// `stat_stride` floats apart; the running estimates are the caller's business (BnRunningUpdate with mean2).
-int bn_forward_train2(const float* x, int64_t x_ld, int64_t n, int64_t split, int c, const float* gamma, const float* beta,
-                      float eps, const float* residual, int64_t res_ld, int relu, float* y, int64_t y_ld, float* save_mean,
-                      float* save_invstd, float* save_unbiased, int stat_stride, void* ws, size_t ws_bytes, hipStream_t st,
-                      uint32_t* relu_bits) {
-  if (!relu || c % 32 != 0) relu_bits = nullptr;
-  int rc = check_rows("bn_fwd_train2(x)", x, x_ld, c);
-  if (rc) return rc;
-  rc = check_rows("bn_fwd_train2(y)", y, y_ld, c);
-  if (rc) return rc;
-  if (residual && (rc = check_rows("bn_fwd_train2(residual)", residual, res_ld, c))) return rc;
-  PCMI_REQUIRE(gamma && beta && save_mean && save_invstd && split > 0 && split < n && stat_stride % 4 == 0, PCMI_ERR_INVALID,
-               "bn_fwd_train2: bad argument");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(n, c), PCMI_ERR_WORKSPACE, "bn_fwd_train2: workspace too small");
-  const int64_t longest = std::max(split, n - split);
-  RedGeom g = red_geom(longest, c);
-  if (g.nblocks > kFinalMergeBlocks) {  // at most kFinalMergeBlocks row blocks per segment: colreduce_final_kernel merges them
-    g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFinalMergeBlocks), g.rp) * g.rp);
-    g.nblocks = (int)ceil_div(longest, g.rows_per_block);
-  }
-  float* part = (float*)ws;
-  RedFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.eps = eps;
-  fin.save_mean = save_mean;
-  fin.save_invstd = save_invstd;
-  fin.save_unbiased = save_unbiased;
-  fin.out_seg_stride = stat_stride;
-  if (bn_small_eligible(longest, c))
-    return bn_small_forward(x, x_ld, n, split, c, gamma, beta, residual, res_ld, relu, y, y_ld, fin, st, relu_bits);
-  const int64_t part_seg = (int64_t)g.nblocks * 2 * c;
-  colreduce_partial_kernel<0><<<dim3((unsigned)g.nblocks, 2), 256, 0, st>>>(x, x_ld, nullptr, 0, nullptr, 0, nullptr, nullptr, n,
-                                                                           g.c4, g.rp, g.rows_per_block, part, split, 0, part_seg);
-  PCMI_LAUNCH_CHECK();
-  colreduce_final_kernel<0><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), 2), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, split,
-                                                                                            part_seg);
-  PCMI_LAUNCH_CHECK();
-  PCMI_BN_APPLY_LAUNCH(stream_grid(n * g.c4), st, residual, relu_bits, x, x_ld, n, g.c4, gamma, beta, save_mean, save_invstd, eps, 0,
-                       residual, res_ld, relu, y, y_ld, split, stat_stride / 4, relu_bits);
-  PCMI_LAUNCH_CHECK();
-  return PCMI_OK;
-}
-
-// Two-segment BatchNorm backward.  sums: [2][2c] scratch (dbeta, dgamma per segment); acc_*: parameter gradients
-// (+= segment 0, then += segment 1).
-int bn_backward2(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y, int64_t y_ld, int64_t n,
-                 int64_t split, int c, const float* gamma, const float* save_mean, const float* save_invstd, int stat_stride,
-                 float* dx, int64_t dx_ld, float* dres, int64_t dres_ld, int dres_accumulate, float* sums, float* acc_dgamma,
-                 float* acc_dbeta, void* ws, size_t ws_bytes, hipStream_t st, const uint32_t* relu_bits) {
-  if (c % 32 != 0) relu_bits = nullptr;
-  if (relu_bits) relu_mask_y = nullptr;  // the pattern comes from the bits: y is not read
-  const int bits_ld = c / 32;
-  int rc = check_rows("bn_bwd2(dy)", dy, dy_ld, c);
-  if (rc) return rc;
-  rc = check_rows("bn_bwd2(x)", x, x_ld, c);
-  if (rc) return rc;
-  rc = check_rows("bn_bwd2(dx)", dx, dx_ld, c);
-  if (rc) return rc;
-  if (relu_mask_y && (rc = check_rows("bn_bwd2(y)", relu_mask_y, y_ld, c))) return rc;
-  if (dres && (rc = check_rows("bn_bwd2(dres)", dres, dres_ld, c))) return rc;
-  PCMI_REQUIRE(gamma && save_mean && save_invstd && sums && split > 0 && split < n && stat_stride % 4 == 0, PCMI_ERR_INVALID,
-               "bn_bwd2: bad argument");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(n, c), PCMI_ERR_WORKSPACE, "bn_bwd2: workspace too small");
-  const int64_t longest = std::max(split, n - split);
-  RedGeom g = red_geom(longest, c);
-  if (g.nblocks > kFinalMergeBlocks) {
-    g.rows_per_block = (int)(ceil_div(ceil_div(longest, kFinalMergeBlocks), g.rp) * g.rp);
-    g.nblocks = (int)ceil_div(longest, g.rows_per_block);
-  }
-  float* part = (float*)ws;
-  RedFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  if (bn_small_eligible(longest, c, true)) {  // (one workgroup walks the two segments in order and accumulates)
-    BnSmallBwd a;
-    a.dy = dy; a.dy_ld = dy_ld; a.x = x; a.x_ld = x_ld; a.ymask = relu_mask_y; a.y_ld = y_ld; a.n = n; a.split = split;
-    a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd; a.stat_stride = stat_stride;
-    a.dx = dx; a.dx_ld = dx_ld; a.dres = dres; a.dres_ld = dres_ld; a.dres_accumulate = dres_accumulate;
-    a.sum_g = sums; a.sum_gx = sums + c; a.sum_stride = 2 * c;
-    a.acc_g = acc_dbeta;
-    a.acc_gx = acc_dgamma;
-    a.bits = reinterpret_cast<const uint16_t*>(relu_bits);
-    return bn_small_backward(a, c, st);
-  }
-  // (the 48-register kernel finds a row's bit words through x's own offsets: with the bits it needs x_ld == c)
-  const bool lean = bn_lean_eligible(n, c, x_ld, dy_ld, relu_mask_y ? y_ld : 0) && (!relu_bits || x_ld == c);
-  fin.out_a = sums;      // dbeta of a segment
-  fin.out_b = sums + c;  // dgamma
-  fin.out_seg_stride = 2 * c;
-  const int64_t part_seg = (int64_t)g.nblocks * 2 * c;
-  if (lean && relu_bits)
-    bn_bwd_stats_lean_kernel<2><<<dim3((unsigned)g.nblocks, 2), 256, 0, st>>>(x, x_ld, dy, dy_ld, reinterpret_cast<const float*>(relu_bits),
-                                                                             bits_ld, save_mean, save_invstd, n, c, g.rows_per_block, part,
-                                                                             split, stat_stride, part_seg);
-  else if (lean && relu_mask_y)
-    bn_bwd_stats_lean_kernel<1><<<dim3((unsigned)g.nblocks, 2), 256, 0, st>>>(x, x_ld, dy, dy_ld, relu_mask_y, y_ld, save_mean,
-                                                                             save_invstd, n, c, g.rows_per_block, part, split,
-                                                                             stat_stride, part_seg);
-  else if (lean)
-    bn_bwd_stats_lean_kernel<0><<<dim3((unsigned)g.nblocks, 2), 256, 0, st>>>(x, x_ld, dy, dy_ld, nullptr, 0, save_mean, save_invstd,
-                                                                             n, c, g.rows_per_block, part, split, stat_stride,
-                                                                             part_seg);
-  else
-    PCMI_BN_BWD_PARTIAL_LAUNCH(dim3((unsigned)g.nblocks, 2), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), x, x_ld, dy, dy_ld, relu_mask_y,
-                               y_ld, save_mean, save_invstd, n, g.c4, g.rp, g.rows_per_block, part, split, stat_stride, part_seg,
-                               relu_bits);
-  PCMI_LAUNCH_CHECK();
-  colreduce_final_kernel<1><<<dim3((unsigned)ceil_div(g.c4, kFinalCols), 2), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, split,
-                                                                                            part_seg);
-  PCMI_LAUNCH_CHECK();
-  PCMI_BN_BWD_APPLY_LAUNCH(stream_grid(n * g.c4), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), dres ? (dres_accumulate ? 2 : 1) : 0,
-                           dy, dy_ld, x, x_ld, relu_mask_y, y_ld, n, g.c4, gamma, save_mean, save_invstd, sums, sums + c, dx, dx_ld, dres, dres_ld,
-                           dres_accumulate, split, stat_stride / 4, 2 * c / 4, acc_dbeta, acc_dgamma, relu_bits);
-  PCMI_LAUNCH_CHECK();
-  return PCMI_OK;
-}
-
-__global__ __launch_bounds__(256) void bn_running_update_kernel(const BnRunningUpdate* __restrict__ tab) {
-  const BnRunningUpdate u = tab[blockIdx.x];
-  for (int ch = threadIdx.x; ch < u.c; ch += 256) {
-    float rm = (1.f - u.momentum) * u.running_mean[ch] + u.momentum * u.mean[ch];
-    float rv = (1.f - u.momentum) * u.running_var[ch] + u.momentum * u.unbiased[ch];
-    if (u.mean2) {  // second segment of the same layer: the second of two forward calls
-      rm = (1.f - u.momentum) * rm + u.momentum * u.mean2[ch];
-      rv = (1.f - u.momentum) * rv + u.momentum * u.unbiased2[ch];
-    }
-    u.running_mean[ch] = rm;
-    u.running_var[ch] = rv;
-  }
-}
-
-int bn_running_update(const BnRunningUpdate* table_dev, int n_entries, hipStream_t st) {
-  if (n_entries <= 0) return PCMI_OK;
-  bn_running_update_kernel<<<n_entries, 256, 0, st>>>(table_dev);
-  PCMI_LAUNCH_CHECK();
-  return PCMI_OK;
-}
-
-}  // namespace pcmi
-
-extern "C" {
-
 
 int pcmi_bn_fwd_eval(const float* x, int64_t x_ld, int64_t n, int c, const float* gamma, const float* beta,
                      const float* running_mean, const float* running_var, float eps, const float* residual,
@@ -1285,85 +1316,16 @@ int pcmi_bn_fwd_eval(const float* x, int64_t x_ld, int64_t n, int c, const float
   return PCMI_OK;
 }
 
-}  // extern "C"
-
-namespace pcmi {
-// dgamma / dbeta: this call's sums (scratch, overwritten); acc_dgamma / acc_dbeta (nullable): += the same sums.
-int bn_backward(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y, int64_t y_ld,
-                int64_t n, int c, const float* gamma, const float* save_mean, const float* save_invstd, float* dx,
-                int64_t dx_ld, float* dres, int64_t dres_ld, int dres_accumulate, float* dgamma, float* dbeta,
-                float* acc_dgamma, float* acc_dbeta, void* ws, size_t ws_bytes, hipStream_t st, const uint32_t* relu_bits) {
-  if (c % 32 != 0) relu_bits = nullptr;
-  if (relu_bits) relu_mask_y = nullptr;
-  const int bits_ld = c / 32;
-  int rc = check_rows("bn_bwd(dy)", dy, dy_ld, c);
-  if (rc) return rc;
-  rc = check_rows("bn_bwd(x)", x, x_ld, c);
-  if (rc) return rc;
-  rc = check_rows("bn_bwd(dx)", dx, dx_ld, c);
-  if (rc) return rc;
-  if (relu_mask_y && (rc = check_rows("bn_bwd(y)", relu_mask_y, y_ld, c))) return rc;
-  if (dres && (rc = check_rows("bn_bwd(dres)", dres, dres_ld, c))) return rc;
-  PCMI_REQUIRE(gamma && save_mean && save_invstd && dgamma && dbeta && n > 0, PCMI_ERR_INVALID, "bn_bwd: bad argument");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_bn_workspace_bytes(n, c), PCMI_ERR_WORKSPACE, "bn_bwd: workspace too small");
-  const RedGeom g = red_geom(n, c);
-  float* part = (float*)ws;
-  RedFinal fin;
-  memset(&fin, 0, sizeof(fin));
-  if (bn_small_eligible(n, c, true)) {
-    BnSmallBwd a;
-    a.dy = dy; a.dy_ld = dy_ld; a.x = x; a.x_ld = x_ld; a.ymask = relu_mask_y; a.y_ld = y_ld; a.n = n; a.split = n;
-    a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd; a.stat_stride = 0;
-    a.dx = dx; a.dx_ld = dx_ld; a.dres = dres; a.dres_ld = dres_ld; a.dres_accumulate = dres_accumulate;
-    a.sum_g = dbeta; a.sum_gx = dgamma; a.sum_stride = 0; a.acc_g = acc_dbeta; a.acc_gx = acc_dgamma;
-    a.bits = reinterpret_cast<const uint16_t*>(relu_bits);
-    return bn_small_backward(a, c, st);
-  }
-  // (the 48-register kernel finds a row's bit words through x's own offsets: with the bits it needs x_ld == c)
-  const bool lean = bn_lean_eligible(n, c, x_ld, dy_ld, relu_mask_y ? y_ld : 0) && (!relu_bits || x_ld == c);
-  const bool small = g.nblocks <= kFinalMergeBlocks;
-  fin.out_a = dbeta;
-  fin.out_b = dgamma;
-  fin.acc_a = acc_dbeta;
-  fin.acc_b = acc_dgamma;
-  if (lean && relu_bits)
-    bn_bwd_stats_lean_kernel<2><<<g.nblocks, 256, 0, st>>>(x, x_ld, dy, dy_ld, reinterpret_cast<const float*>(relu_bits), bits_ld,
-                                                          save_mean, save_invstd, n, c, g.rows_per_block, part, 0, 0, 0);
-  else if (lean && relu_mask_y)
-    bn_bwd_stats_lean_kernel<1><<<g.nblocks, 256, 0, st>>>(x, x_ld, dy, dy_ld, relu_mask_y, y_ld, save_mean, save_invstd, n, c,
-                                                          g.rows_per_block, part, 0, 0, 0);
-  else if (lean)
-    bn_bwd_stats_lean_kernel<0><<<g.nblocks, 256, 0, st>>>(x, x_ld, dy, dy_ld, nullptr, 0, save_mean, save_invstd, n, c,
-                                                          g.rows_per_block, part, 0, 0, 0);
-  else
-    PCMI_BN_BWD_PARTIAL_LAUNCH(g.nblocks, st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), x, x_ld, dy, dy_ld, relu_mask_y, y_ld, save_mean,
-                               save_invstd, n, g.c4, g.rp, g.rows_per_block, part, (int64_t)0, 0, (int64_t)0, relu_bits);
-  PCMI_LAUNCH_CHECK();
-  if (small) {
-    colreduce_final_kernel<1><<<(unsigned)ceil_div(g.c4, kFinalCols), 256, 0, st>>>(part, n, g.c4, g.rows_per_block, fin, 0, 0);
-    PCMI_LAUNCH_CHECK();
-  }
-  if (!small) {
-    colsum2_final_kernel<<<dim3((unsigned)ceil_div(c, 4)), 256, 0, st>>>(part, g.nblocks, c, dbeta, dgamma, acc_dbeta, acc_dgamma);
-    PCMI_LAUNCH_CHECK();
-  }
-  PCMI_BN_BWD_APPLY_LAUNCH(stream_grid(n * g.c4), st, relu_bits ? 2 : (relu_mask_y ? 1 : 0), dres ? (dres_accumulate ? 2 : 1) : 0,
-                           dy, dy_ld, x, x_ld, relu_mask_y, y_ld, n, g.c4, gamma, save_mean, save_invstd, dbeta, dgamma, dx, dx_ld, dres, dres_ld,
-                           dres_accumulate, INT64_MAX, 0, 0, (float*)nullptr, (float*)nullptr, relu_bits);
-  PCMI_LAUNCH_CHECK();
-  return PCMI_OK;
-}
-
-}  // namespace pcmi
-
-extern "C" {
-
 int pcmi_bn_bwd(const float* dy, int64_t dy_ld, const float* x, int64_t x_ld, const float* relu_mask_y, int64_t y_ld,
                 int64_t n, int c, const float* gamma, const float* save_mean, const float* save_invstd, float* dx,
                 int64_t dx_ld, float* dres, int64_t dres_ld, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
                 pcmi_stream_t stream) {
-  return bn_backward(dy, dy_ld, x, x_ld, relu_mask_y, y_ld, n, c, gamma, save_mean, save_invstd, dx, dx_ld, dres, dres_ld, 0,
-                     dgamma, dbeta, nullptr, nullptr, ws, ws_bytes, as_stream(stream));
+  BnBackwardArgs a;
+  memset(&a, 0, sizeof(a));
+  a.dy = dy; a.dy_ld = dy_ld; a.x = x; a.x_ld = x_ld; a.relu_mask_y = relu_mask_y; a.y_ld = y_ld;
+  a.n = a.split = n; a.c = c; a.gamma = gamma; a.save_mean = save_mean; a.save_invstd = save_invstd;
+  a.dx = dx; a.dx_ld = dx_ld; a.dres = dres; a.dres_ld = dres_ld; a.dgamma = dgamma; a.dbeta = dbeta;
+  return bn_backward(a, ws, ws_bytes, as_stream(stream));
 }
 
 int pcmi_relu_fwd(const float* x, int64_t x_ld, int64_t n, int c, float* y, int64_t y_ld, pcmi_stream_t stream) {
