@@ -540,6 +540,65 @@ int pcmi_three_interpolate_fwd(const float* feat, const int32_t* idx, const floa
 int pcmi_three_interpolate_bwd(const float* gout, const int32_t* idx, const float* weight, int64_t B, int C, int64_t M,
                                int64_t n, float* gfeat, int validate, void* ws, size_t ws_bytes, pcmi_stream_t stream);
 
+/* ---- VoteNet head on row-major activations (csrc/votehead.hip) ---------------------------------------------------------
+ * What turns the backbone's seed features into votes and proposals ("vn/" as above: vn/models/voting_module.py,
+ * vn/models/proposal_module.py with PointnetSAModuleVotes, vn/models/votenet.py:120-121) and the optimiser step of
+ * vn/lib/train.py.  Every activation is fp32 [rows, ld] with the FEATURE columns first, the geometric columns behind them
+ * and zero columns up to ld (a multiple of 4; the dense GEMM wants a multiple of 32), so the 1x1 convolution
+ * (pcmi_spconv_* with map == NULL) and pcmi_bn_* work on them as they are, with no transposes.  Tensors are contiguous
+ * fp32 / int32 apart from the leading dimensions given.  A refused call enqueues nothing.  No float atomics: every result is
+ * the same bits from run to run.  Workspace sizes come from the *_workspace_bytes query.
+ *
+ * pcmi_group_rows_fwd = QueryAndGroup(use_xyz, normalize_xyz) (pointnet2_utils.py:294-351) written straight into rows:
+ *   xyz [B, n, 3], centre [B, np, 3], feat [B n, C] (feat_ld), idx [B, np, ns] from pcmi_ball_query;
+ *   out [B np ns, out_ld]: out[r, 0:C] = feat[b n + idx[r]], out[r, C + k] = (xyz[b, idx[r], k] - centre[b, q, k]) /
+ *   radius_div -- a subtraction, then a division, each rounded on its own (radius_div 1.0: no normalisation) -- and zeros
+ *   up to out_ld.  out_ld >= C + 3 and a multiple of 4, out 16-byte aligned, else PCMI_ERR_INVALID.  One wave copies one
+ *   row: 16-byte accesses where C % 4 == 0 (and feat is 16-byte aligned with feat_ld % 4 == 0), 4-byte accesses otherwise.
+ *   An index outside [0, n) is never dereferenced: its whole row is zero.  validate as for the point-set gathers above
+ *   (!= 0: checked on the device first, the call SYNCS, PCMI_ERR_RANGE with nothing else launched).
+ * pcmi_group_rows_bwd: gout [B np ns, gout_ld] -> gfeat [B n, C] (gfeat_ld), gxyz [B, n, 3], gcentre [B, np, 3], each
+ *   written whole.  gfeat / gxyz: every point sums the rows that gathered it in ascending row, in gather form over the
+ *   inverse lists of csrc/pointset.hip (ws: pcmi_group_rows_bwd_workspace_bytes); gcentre = minus the ascending sum over
+ *   the group's ns rows; the geometric gradients are divided by radius_div element by element before they are summed.
+ *   A row whose index is outside [0, n) is dropped from all three.  No synchronisation.
+ * pcmi_rows_maxpool_fwd: out [R, C] (out_ld) = the maximum over the ns consecutive rows of x [R ns, C] (x_ld), arg [R, C]
+ *   uint8 (contiguous) = the row within the window that holds it.  The LOWEST row wins among equal values (ball-query
+ *   padding repeats rows and ReLU leaves all-zero columns: ties are the common case); a NaN in the window is the result
+ *   and the lowest NaN row the argument.  1 <= ns <= 256, else PCMI_ERR_UNSUPPORTED.
+ * pcmi_rows_maxpool_bwd: gx [R ns, C] (gx_ld), written whole: gout [R, C] at the argument row, zero elsewhere.
+ * pcmi_vote_fwd = the tail of VotingModule.forward (voting_module.py:52-66) and the feature normalisation of
+ *   votenet.py:120-121 in one pass.  net [R, vf Wb] (net_ld): block v of a row holds C residual features, then 3 offsets
+ *   (Wb >= C + 3, a multiple of 4; the head uses C + 3 rounded up to 32).  vote_xyz [R vf, 3] = seed_xyz [R, 3] + offset,
+ *   vote_feat [R vf, C] (vote_feat_ld) = u / ||u||_2 with u = seed_feat [R, C] (seed_feat_ld) + residual, norm [R vf] =
+ *   ||u||_2.  No epsilon, as in the reference: a zero row gives the reference's NaN and is not trapped.  The norm is
+ *   reduced in a fixed order (per lane in ascending column, then an xor butterfly over the wave).
+ * pcmi_vote_bwd: gu = (gy - y (y . gy)) / ||u|| with y = vote_feat, gy = g_vote_feat; g_net [R, vf Wb] (g_net_ld) = gu,
+ *   then g_vote_xyz, then zeros in every block; g_seed_feat [R, C] and g_seed_xyz [R, 3] = the sums over v in ascending v.
+ * pcmi_adam_step = torch.optim.Adam's single-tensor step (amsgrad off, L2 weight decay) on flat buffers, step number t >= 1:
+ *   g' = g + wd w; m = b1 m + (1 - b1) g'; v = b2 v + (1 - b2) g'^2; denom = sqrt(v) / sqrt(1 - b2^t) + eps;
+ *   w -= (lr / (1 - b1^t)) (m / denom).  The bias corrections are computed in double on the host, as torch does; g is not
+ *   modified.  16-byte accesses when all four buffers are 16-byte aligned. */
+int pcmi_group_rows_fwd(const float* xyz, const float* centre, const float* feat, int64_t feat_ld, const int32_t* idx,
+                        int64_t B, int64_t n, int64_t np, int64_t ns, int C, float radius_div, float* out, int64_t out_ld,
+                        int validate, pcmi_stream_t stream);
+size_t pcmi_group_rows_bwd_workspace_bytes(int64_t B, int64_t n, int64_t np, int64_t ns);
+int pcmi_group_rows_bwd(const float* gout, int64_t gout_ld, const int32_t* idx, int64_t B, int64_t n, int64_t np, int64_t ns,
+                        int C, float radius_div, float* gfeat, int64_t gfeat_ld, float* gxyz, float* gcentre, void* ws,
+                        size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_rows_maxpool_fwd(const float* x, int64_t x_ld, int64_t R, int ns, int C, float* out, int64_t out_ld, uint8_t* arg,
+                          pcmi_stream_t stream);
+int pcmi_rows_maxpool_bwd(const float* gout, int64_t gout_ld, const uint8_t* arg, int64_t R, int ns, int C, float* gx,
+                          int64_t gx_ld, pcmi_stream_t stream);
+int pcmi_vote_fwd(const float* net, int64_t net_ld, const float* seed_xyz, const float* seed_feat, int64_t seed_feat_ld,
+                  int64_t R, int vf, int C, int Wb, float* vote_xyz, float* vote_feat, int64_t vote_feat_ld, float* norm,
+                  pcmi_stream_t stream);
+int pcmi_vote_bwd(const float* g_vote_feat, int64_t g_vote_feat_ld, const float* g_vote_xyz, const float* vote_feat,
+                  int64_t vote_feat_ld, const float* norm, int64_t R, int vf, int C, int Wb, float* g_net, int64_t g_net_ld,
+                  float* g_seed_feat, int64_t g_seed_feat_ld, float* g_seed_xyz, pcmi_stream_t stream);
+int pcmi_adam_step(float* w, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, int64_t t, pcmi_stream_t stream);
+
 /* ---- VoteNet detection head (csrc/detect.hip) ------------------------------------------------------------------------
  * The matching of the detection loss and the decoding of the predictions ("vn/" as above).  fp32 data, int32 indices,
  * contiguous tensors.  Every operation of a distance is rounded on its own in fp32, in the order written here, so the
@@ -1043,6 +1102,10 @@ int pcmi_net_stream_wait_bucket(pcmi_net_t* net, pcmi_stream_t stream);
  * pass of `net`; a backward pass uses the mode set when it is called.  Default fp32.  PCMI_ERR_INVALID for other values. */
 int pcmi_net_set_conv_precision(pcmi_net_t* net, int precision);
 int pcmi_net_apply_running_stats(pcmi_net_t* net, int pass, pcmi_stream_t stream);
+/* The momentum of every BatchNorm op of `net` for later training forwards (the detection fine-tuning's BNMomentumScheduler,
+ * vn/lib/train.py: a new value per epoch); a net that never calls it keeps the momenta it was created with.  Passes already
+ * enqueued are not affected.  PCMI_ERR_INVALID outside [0, 1]. */
+int pcmi_net_set_bn_momentum(pcmi_net_t* net, float momentum);
 /* Copy of one activation tensor of the last forward of `pass` (they stay in the pass's arena until its next forward)
  * into caller memory out [rows, out_ld]; rows / channels (nullable) report its shape, out == NULL only queries.  For
  * inspection and for tests that hand the device's ReLU patterns to the oracle (the reference has no counterpart: its

@@ -166,6 +166,17 @@ PROTOTYPES = {
     "pcmi_three_interpolate_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp]),
     "pcmi_three_interpolate_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, c_vp, C.c_int, c_vp, c_sz,
                                              c_vp]),
+    "pcmi_group_rows_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_i64, C.c_int,
+                                      c_vp]),
+    "pcmi_group_rows_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "pcmi_group_rows_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                      c_sz, c_vp]),
+    "pcmi_rows_maxpool_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_i64, c_vp, c_vp]),
+    "pcmi_rows_maxpool_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_i64, c_vp]),
+    "pcmi_vote_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "pcmi_vote_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, C.c_int, c_vp, c_i64, c_vp, c_i64,
+                                c_vp, c_vp]),
+    "pcmi_adam_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
     "pcmi_nn_distance_fwd": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_vp, c_vp]),
     "pcmi_nn_distance_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "pcmi_nn_distance_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_vp,
@@ -227,6 +238,7 @@ PROTOTYPES = {
                                     c_vp]),
     "pcmi_net_apply_running_stats": (C.c_int, [c_vp, C.c_int, c_vp]),
     "pcmi_net_stream_wait_bucket": (C.c_int, [c_vp, c_vp]),
+    "pcmi_net_set_bn_momentum": (C.c_int, [c_vp, c_f32]),
     "pcmi_net_set_conv_precision": (C.c_int, [c_vp, C.c_int]),
     "pcmi_net_export_tensor": (C.c_int, [c_vp, C.c_int, C.c_int, C.POINTER(c_i64), C.POINTER(C.c_int), c_vp, c_i64, c_vp]),
     "pcmi_net_memory_bytes": (C.c_int, [c_vp, C.POINTER(c_sz)]),

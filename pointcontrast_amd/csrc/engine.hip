@@ -1287,4 +1287,14 @@ int pcmi_net_set_conv_precision(pcmi_net_t* net, int precision) {
   return PCMI_OK;
 }
 
+int pcmi_net_set_bn_momentum(pcmi_net_t* net, float momentum) {
+  PCMI_REQUIRE(net, PCMI_ERR_INVALID, "net_set_bn_momentum: null net");
+  PCMI_REQUIRE(momentum >= 0.f && momentum <= 1.f, PCMI_ERR_INVALID, "net_set_bn_momentum: momentum %g outside [0, 1]", (double)momentum);
+  // read by the training forward when it enqueues a BatchNorm (or files its deferred running-estimate update): passes already
+  // enqueued keep the value they were enqueued with
+  for (pcmi_net_op_t& op : net->ops)
+    if (op.type == PCMI_OP_BN) op.momentum = momentum;
+  return PCMI_OK;
+}
+
 }  // extern "C"

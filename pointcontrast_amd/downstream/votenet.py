@@ -5,7 +5,11 @@ The seed sampling of the detection fine-tuning's sparse backbone: what SparseCon
 (downstream/votenet_det_new/models/backbone_module.py:159-177) does after the network -- there a Python loop over the
 scenes with boolean masks and one furthest_point_sample call each, here one segmented launch over the coordinate manager's
 row -> scene tables.  The modules behind it (set abstraction, feature propagation, proposal) take their ops from
-pointcontrast_amd.pointnet2_utils."""
+pointcontrast_amd.pointnet2_utils.
+
+The network and the training step (models/voting_module.py, proposal_module.py, votenet.py with the sparse backbone, lib/train.py)
+are at the end of the file: VotingModule, ProposalModule, VoteNet on row-major activations (csrc/votehead.hip) and
+DetectionTrainer."""
 import ctypes as C
 import math
 
@@ -668,3 +672,494 @@ class DetectionInputPipeline:
     out.update(point_clouds=s["point_clouds"], vote_label=v["vote_label"], vote_label_mask=v["vote_label_mask"],
                voxel_coords=x["voxel_coords"][:M], voxel_inds=x["voxel_inds"][:M], voxel_feats=x["voxel_feats"][:M])
     return out
+
+
+# ---- the network: voting, vote aggregation, proposals (csrc/votehead.hip) ----------------------------------------------------
+# Every head activation is a row-major fp32 matrix [rows, ld] (rows = B num_seed, B num_seed vote_factor, B num_proposal
+# nsample or B num_proposal): feature columns first, geometric columns behind them, zero columns up to a multiple of 32 -- the
+# layout the dense GEMM (SparseConvFunction with kmap None) and the fused BatchNorm + ReLU already work on, so nothing is
+# ever transposed.  Parameters are stored in the GEMM's layout, [Cin_pad, Cout_pad], transposed, zero-padded and with the
+# columns permuted to "features, then xyz"; state_dict() / load_state_dict() speak the reference's names and shapes.
+VOTE_AGGREGATION_RADIUS = 0.3
+VOTE_AGGREGATION_NSAMPLE = 16
+VOTE_AGGREGATION_MLP = (128, 128, 128)
+
+
+def features_then_xyz(C, blocks=1, block_width=None):
+  """Native column of every reference channel of `blocks` groups of (3 geometric + C feature) channels: the reference puts
+  xyz first, the rows put the C features first and xyz behind them; block b starts at column b * block_width."""
+  width = C + 3 if block_width is None else block_width
+  one = torch.cat([torch.arange(C, C + 3), torch.arange(0, C)])
+  return torch.cat([one + b * width for b in range(blocks)])
+
+
+def to_native_weight(ref, in_map, out_map, cin_pad, cout_pad):
+  """A reference convolution weight [Cout, Cin, 1(, 1)] in the GEMM's layout [cin_pad, cout_pad]: native[in_map[j],
+  out_map[i]] = ref[i, j], zeros elsewhere."""
+  ref2 = ref.reshape(ref.shape[0], ref.shape[1])
+  out = torch.zeros((cin_pad, cout_pad), dtype=ref.dtype, device=ref.device)
+  out[in_map.to(ref.device).unsqueeze(1), out_map.to(ref.device).unsqueeze(0)] = ref2.t()
+  return out
+
+
+def to_reference_weight(native, in_map, out_map, ref_shape):
+  native = native.reshape(native.shape[-2], native.shape[-1])
+  return native[in_map.to(native.device).unsqueeze(1), out_map.to(native.device).unsqueeze(0)].t().reshape(ref_shape).contiguous()
+
+
+class RowConv(torch.nn.Module):
+  """A 1x1 convolution (the reference's Conv1d / Conv2d with kernel size 1) on rows: y [rows, cout_pad] = x [rows, cin_pad]
+  W + b through the dense GEMM.  in_map / out_map: the native column of every reference input / output channel (None:
+  the identity).  Padded weights and biases start at zero and receive exactly zero gradient -- their input columns are zero
+  and so are the gradients of their output columns -- so they stay zero.  The state dict holds the reference's tensors."""
+
+  def __init__(self, cin, cout, bias=True, in_map=None, out_map=None, cin_pad=None, cout_pad=None, conv_dims=1):
+    super().__init__()
+    self.cin, self.cout = int(cin), int(cout)
+    self.cin_pad = int(cin_pad) if cin_pad is not None else PF.pad_width(cin)
+    self.cout_pad = int(cout_pad) if cout_pad is not None else PF.pad_width(cout)
+    self.register_buffer("in_map", torch.arange(cin) if in_map is None else in_map.clone(), persistent=False)
+    self.register_buffer("out_map", torch.arange(cout) if out_map is None else out_map.clone(), persistent=False)
+    self.ref_shape = (self.cout, self.cin) + (1,) * conv_dims
+    ref = torch.empty(self.ref_shape)
+    torch.nn.init.kaiming_uniform_(ref, a=math.sqrt(5))  # Conv1d / Conv2d's own initialisation
+    self.weight = torch.nn.Parameter(to_native_weight(ref, self.in_map, self.out_map, self.cin_pad, self.cout_pad))
+    self.bias = None
+    if bias:
+      bound = 1.0 / math.sqrt(self.cin)
+      b = torch.zeros((1, self.cout_pad))
+      b[0, self.out_map] = torch.empty(self.cout).uniform_(-bound, bound)
+      self.bias = torch.nn.Parameter(b)
+
+  def forward(self, x):
+    assert x.dim() == 2 and x.shape[1] == self.cin_pad, "RowConv: expected rows of width %d, got %s" % (self.cin_pad, tuple(x.shape))
+    return PF.SparseConvFunction.apply(x, self.weight, self.bias, None, False, x.shape[0])
+
+  def reference_tensors(self):
+    out = {"weight": to_reference_weight(self.weight.detach(), self.in_map, self.out_map, self.ref_shape)}
+    if self.bias is not None:
+      out["bias"] = self.bias.detach()[0, self.out_map].contiguous()
+    return out
+
+  def _save_to_state_dict(self, destination, prefix, keep_vars):
+    for k, v in self.reference_tensors().items():
+      destination[prefix + k] = v
+
+  def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+    for k, param in (("weight", self.weight), ("bias", self.bias)):
+      key = prefix + k
+      if param is None:
+        if key in state_dict and strict:
+          unexpected_keys.append(key)
+        continue
+      if key not in state_dict:
+        if strict:
+          missing_keys.append(key)
+        continue
+      v = state_dict[key]
+      want = self.ref_shape if k == "weight" else (self.cout,)
+      if tuple(v.shape) != tuple(want):
+        error_msgs.append("size mismatch for %s: the reference's shape is %s, got %s" % (key, tuple(want), tuple(v.shape)))
+        continue
+      with torch.no_grad():
+        v = v.to(device=param.device, dtype=param.dtype)
+        if k == "weight":
+          param.copy_(to_native_weight(v, self.in_map, self.out_map, self.cin_pad, self.cout_pad))
+        else:
+          param.zero_()
+          param[0, self.out_map] = v
+
+
+class RowBatchNorm(torch.nn.BatchNorm1d):
+  """BatchNorm1d / BatchNorm2d of the reference over rows [rows, C], fused with the ReLU behind it (pcmi_bn_*).  A
+  BatchNorm1d by type, so that whatever sets `.momentum` on the reference's model (BNMomentumScheduler) finds it."""
+
+  def __init__(self, num_features):
+    super().__init__(num_features)
+    self._untracked = 0
+    self.register_state_dict_pre_hook(RowBatchNorm._flush_tracked)
+
+  @staticmethod
+  def _flush_tracked(module, prefix, keep_vars):
+    if module._untracked:
+      with torch.no_grad():
+        module.num_batches_tracked += module._untracked
+      module._untracked = 0
+
+  def forward(self, x, relu=True):
+    if self.training:
+      self._untracked += 1
+      return PF.BatchNormFunction.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps,
+                                        None, relu)
+    return PF.batch_norm_eval(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, None, relu)
+
+
+class VotingModule(torch.nn.Module):
+  """models/voting_module.py on rows: (seed_xyz [B, S, 3], seed rows [B S, C]) -> (vote_xyz [B S vf, 3], vote rows [B S vf, C]),
+  the vote features already L2-normalised (models/votenet.py:120-121; pcmi_vote_fwd does both)."""
+
+  def __init__(self, vote_factor, seed_feature_dim):
+    super().__init__()
+    self.vote_factor, self.in_dim = int(vote_factor), int(seed_feature_dim)
+    C = self.in_dim
+    assert C % 32 == 0, "the seed feature width must be a multiple of 32 (the dense GEMM's granularity)"
+    self.block_width = PF.pad_width(C + 3)
+    self.conv1, self.conv2 = RowConv(C, C), RowConv(C, C)
+    self.conv3 = RowConv(C, (3 + C) * self.vote_factor, out_map=features_then_xyz(C, self.vote_factor, self.block_width),
+                         cout_pad=self.vote_factor * self.block_width)
+    self.bn1, self.bn2 = RowBatchNorm(C), RowBatchNorm(C)
+
+  def forward(self, seed_xyz, seed_rows):
+    net = self.bn1(self.conv1(seed_rows))
+    net = self.bn2(self.conv2(net))
+    net = self.conv3(net)
+    return PF.VoteFunction.apply(net, seed_xyz.reshape(-1, 3), seed_rows, self.vote_factor)
+
+
+class _ConvBN(torch.nn.Module):
+  """One layer of the reference's SharedMLP: `conv` (no bias) and `bn.bn`, named as there."""
+
+  def __init__(self, cin, cout, in_map=None):
+    super().__init__()
+    self.conv = RowConv(cin, cout, bias=False, in_map=in_map, conv_dims=2)
+    self.bn = torch.nn.Module()
+    self.bn.bn = RowBatchNorm(cout)
+
+  def forward(self, x):
+    return self.bn.bn(self.conv(x))
+
+
+class VoteAggregation(torch.nn.Module):
+  """PointnetSAModuleVotes(npoint, radius 0.3, nsample 16, mlp [C, 128, 128, 128], use_xyz, normalize_xyz) on rows: the
+  sampled votes' neighbourhoods written straight into rows (pcmi_group_rows_fwd), three GEMM + BatchNorm + ReLU layers, and the
+  maximum over nsample (pcmi_rows_maxpool_fwd)."""
+
+  def __init__(self, npoint, seed_feat_dim, radius=VOTE_AGGREGATION_RADIUS, nsample=VOTE_AGGREGATION_NSAMPLE, mlp=VOTE_AGGREGATION_MLP):
+    super().__init__()
+    self.npoint, self.radius, self.nsample, self.C = int(npoint), float(radius), int(nsample), int(seed_feat_dim)
+    self.mlp_module = torch.nn.Module()
+    cin = self.C + 3
+    for i, cout in enumerate(mlp):
+      self.mlp_module.add_module("layer%d" % i, _ConvBN(cin, cout, in_map=features_then_xyz(self.C) if i == 0 else None))
+      cin = cout
+    self.n_layers = len(mlp)
+
+  def forward(self, xyz, rows, inds):
+    """xyz [B, K, 3], rows [B K, C], inds int32 [B, npoint] -> (new_xyz [B, npoint, 3], pooled rows [B npoint, 128], idx)."""
+    B, K, _ = xyz.shape
+    flat = (inds.to(torch.int64) + torch.arange(B, device=inds.device, dtype=torch.int64).unsqueeze(1) * K).reshape(-1)
+    # through the row gather, so that the gradient of the centres flows back into the votes as a deterministic scatter-add
+    xyz4 = F.pad(xyz.reshape(B * K, 3), (0, 1))
+    new_xyz = PF.GatherRowsFunction.apply(xyz4, flat)[:, :3].reshape(B, self.npoint, 3)
+    idx = PF.BallQueryFunction.apply(self.radius, self.nsample, xyz.detach(), new_xyz.detach())
+    x = PF.GroupRowsFunction.apply(xyz, new_xyz, rows, idx, self.radius, PF.pad_width(self.C + 3), False)
+    for i in range(self.n_layers):
+      x = getattr(self.mlp_module, "layer%d" % i)(x)
+    return new_xyz, PF.RowsMaxPoolFunction.apply(x, self.nsample), idx
+
+
+def decode_scores(net, end_points, num_class, num_heading_bin, num_size_cluster, mean_size_arr):
+  """decode_scores of models/proposal_module.py:18-44 on net [B, num_proposal, 2 + 3 + 2 NH + 4 NS + num_class] (the
+  reference's net_transposed): views of the rows under the reference's keys."""
+  B, P = net.shape[0], net.shape[1]
+  H, S = num_heading_bin, num_size_cluster
+  end_points["objectness_scores"] = net[:, :, 0:2]
+  end_points["center"] = end_points["aggregated_vote_xyz"] + net[:, :, 2:5]
+  end_points["heading_scores"] = net[:, :, 5:5 + H]
+  end_points["heading_residuals_normalized"] = net[:, :, 5 + H:5 + 2 * H]
+  end_points["heading_residuals"] = end_points["heading_residuals_normalized"] * (np.pi / H)
+  end_points["size_scores"] = net[:, :, 5 + 2 * H:5 + 2 * H + S]
+  end_points["size_residuals_normalized"] = net[:, :, 5 + 2 * H + S:5 + 2 * H + 4 * S].reshape(B, P, S, 3)
+  arr = np.ascontiguousarray(np.asarray(mean_size_arr, dtype=np.float32))
+  msa = _constant(("mean_size", arr.shape, arr.tobytes()), net.device, lambda: torch.from_numpy(arr.copy()))
+  end_points["size_residuals"] = end_points["size_residuals_normalized"] * msa.reshape(1, 1, S, 3)
+  end_points["sem_cls_scores"] = net[:, :, 5 + 2 * H + 4 * S:]
+  return end_points
+
+
+PROPOSAL_SAMPLINGS = ("vote_fps", "seed_fps", "random")
+
+
+class ProposalModule(torch.nn.Module):
+  """models/proposal_module.py on rows.  sampling: "vote_fps" (furthest point sampling of the votes), "seed_fps" (of the
+  seeds; the picks index the votes, as in the reference) or "random" (uniform over the seeds -- or the caller's
+  sample_inds: the draw is data)."""
+
+  def __init__(self, num_class, num_heading_bin, num_size_cluster, mean_size_arr, num_proposal, sampling, seed_feat_dim=256):
+    super().__init__()
+    if sampling not in PROPOSAL_SAMPLINGS:
+      raise ValueError("Unknown sampling strategy: %r (one of %s)" % (sampling, ", ".join(PROPOSAL_SAMPLINGS)))
+    self.num_class, self.num_heading_bin, self.num_size_cluster = int(num_class), int(num_heading_bin), int(num_size_cluster)
+    self.mean_size_arr = np.asarray(mean_size_arr, np.float32)
+    assert self.mean_size_arr.shape == (self.num_size_cluster, 3)
+    self.num_proposal, self.sampling, self.seed_feat_dim = int(num_proposal), sampling, int(seed_feat_dim)
+    self.num_outputs = 2 + 3 + self.num_heading_bin * 2 + self.num_size_cluster * 4 + self.num_class
+    self.vote_aggregation = VoteAggregation(self.num_proposal, self.seed_feat_dim)
+    self.conv1, self.conv2, self.conv3 = RowConv(128, 128), RowConv(128, 128), RowConv(128, self.num_outputs)
+    self.bn1, self.bn2 = RowBatchNorm(128), RowBatchNorm(128)
+
+  def forward(self, xyz, rows, end_points, sample_inds=None, generator=None):
+    """xyz [B, K, 3] and rows [B K, C]: the votes.  sample_inds (int [B, num_proposal], optional): the sampled votes."""
+    B = xyz.shape[0]
+    if sample_inds is None:
+      if self.sampling == "vote_fps":
+        sample_inds = PF.FurthestPointSampleFunction.apply(xyz.detach(), self.num_proposal)
+      elif self.sampling == "seed_fps":
+        sample_inds = PF.FurthestPointSampleFunction.apply(end_points["seed_xyz"].detach(), self.num_proposal)
+      else:
+        num_seed = end_points["seed_xyz"].shape[1]
+        sample_inds = torch.randint(0, num_seed, (B, self.num_proposal), dtype=torch.int32, device=xyz.device, generator=generator)
+    sample_inds = sample_inds.to(device=xyz.device, dtype=torch.int32)
+    assert tuple(sample_inds.shape) == (B, self.num_proposal), "sample_inds: [B, num_proposal]"
+    new_xyz, pooled, idx = self.vote_aggregation(xyz, rows, sample_inds)
+    end_points["aggregated_vote_xyz"] = new_xyz
+    end_points["aggregated_vote_inds"] = sample_inds
+    self.last_idx = idx  # the ball query's neighbourhoods of the last forward, for inspection (not one of the reference's keys)
+    net = self.bn1(self.conv1(pooled))
+    net = self.bn2(self.conv2(net))
+    net = self.conv3(net)[:, :self.num_outputs].reshape(B, self.num_proposal, self.num_outputs)
+    return decode_scores(net, end_points, self.num_class, self.num_heading_bin, self.num_size_cluster, self.mean_size_arr)
+
+
+class SparseConvBackbone(torch.nn.Module):
+  """models/backbone_module.py:134-180: Res16UNet34C (3 -> output_feature_dim, no feature normalisation) and the seed
+  sampling behind it (sample_seeds)."""
+
+  def __init__(self, input_feature_dim=3, output_feature_dim=256, num_seed=1024, model="Res16UNet34C", bn_momentum=0.02):
+    super().__init__()
+    from ..lib.config import get_config
+    from ..model import load_model
+    cfg = get_config(["net.normalize_feature=False", "net.conv1_kernel_size=3", "opt.bn_momentum=%g" % bn_momentum])
+    self.net = load_model(model)(input_feature_dim, output_feature_dim, cfg, D=3)
+    self.num_seed = int(num_seed)
+
+
+class VoteNet(torch.nn.Module):
+  """models/votenet.py with the sparse backbone.  forward(inputs) takes the input pipeline's batch dict (point_clouds,
+  voxel_coords, voxel_feats, voxel_inds) and returns end_points with the reference's keys, shapes and dtypes, as [B, K, ...]
+  views of the rows (vote_features and seed_features as [B, C, K] views); get_loss and decode_predictions consume it
+  unchanged.  The "pointnet2" backbone is not provided."""
+
+  def __init__(self, num_class, num_heading_bin, num_size_cluster, mean_size_arr, input_feature_dim=0, num_proposal=128,
+               vote_factor=1, sampling="vote_fps", backbone="sparseconv", num_seed=1024, seed_feature_dim=256):
+    super().__init__()
+    if backbone != "sparseconv":
+      raise NotImplementedError("VoteNet: only the sparse backbone is provided (backbone=%r)" % (backbone,))
+    mean_size_arr = np.asarray(mean_size_arr, np.float32)
+    assert mean_size_arr.shape[0] == num_size_cluster
+    self.num_class, self.num_heading_bin, self.num_size_cluster, self.mean_size_arr = num_class, num_heading_bin, num_size_cluster, mean_size_arr
+    self.input_feature_dim, self.num_proposal, self.vote_factor, self.sampling = input_feature_dim, num_proposal, vote_factor, sampling
+    self.backbone_net = SparseConvBackbone(input_feature_dim + 3, seed_feature_dim, num_seed)
+    self.vgen = VotingModule(vote_factor, seed_feature_dim)
+    self.pnet = ProposalModule(num_class, num_heading_bin, num_size_cluster, mean_size_arr, num_proposal, sampling,
+                               seed_feat_dim=seed_feature_dim)
+
+  def head_parameters(self):
+    return list(self.vgen.parameters()) + list(self.pnet.parameters())
+
+  def forward_head(self, seed_xyz, seed_rows, seed_inds=None, sample_inds=None):
+    """The head on seed_xyz [B, S, 3] and seed rows [B S, C]: everything behind the backbone."""
+    B, S, _ = seed_xyz.shape
+    C = seed_rows.shape[1]
+    end_points = {"seed_xyz": seed_xyz, "seed_features": seed_rows.reshape(B, S, C).transpose(1, 2)}
+    if seed_inds is not None:
+      end_points["seed_inds"] = seed_inds
+    vote_xyz, vote_rows = self.vgen(seed_xyz, seed_rows)
+    K = S * self.vote_factor
+    vote_xyz = vote_xyz.reshape(B, K, 3)
+    end_points["vote_xyz"] = vote_xyz
+    end_points["vote_features"] = vote_rows.reshape(B, K, C).transpose(1, 2)
+    return self.pnet(vote_xyz, vote_rows, end_points, sample_inds=sample_inds)
+
+  def forward(self, inputs, sparse_out=None):
+    """sparse_out: the backbone's output SparseTensor when something else ran the backbone (DetectionTrainer: the native
+    executor); None runs self.backbone_net.net eagerly."""
+    from .. import minkowski as ME
+    points = inputs["point_clouds"]
+    dev = self.vgen.conv1.weight.device
+    if sparse_out is None:
+      st = ME.SparseTensor(inputs["voxel_feats"].float(), coords=inputs["voxel_coords"].int()).to(dev)
+      sparse_out = self.backbone_net.net(st)
+    fp2_xyz, fp2_features, fp2_inds = sample_seeds(sparse_out, points[:, :, 0:3], inputs["voxel_inds"], self.backbone_net.num_seed)
+    B, C, S = fp2_features.shape
+    seed_rows = fp2_features.transpose(1, 2).reshape(B * S, C)
+    return self.forward_head(fp2_xyz, seed_rows, fp2_inds, inputs.get("sample_inds"))
+
+
+class BNMomentumScheduler:
+  """BNMomentumScheduler of the reference (pytorch_utils.py:271-296): step(epoch) sets the momentum bn_lambda(epoch) on
+  every BatchNorm of `model` -- the head's RowBatchNorm and the backbone's MinkowskiBatchNorm containers are BatchNorm1d --
+  and, through `engine` (a NativeEngine, optional), on the executor's program, which holds its own copy."""
+
+  def __init__(self, model, bn_lambda, last_epoch=-1, engine=None):
+    if not isinstance(model, torch.nn.Module):
+      raise RuntimeError("Class '%s' is not a PyTorch nn Module" % type(model).__name__)
+    self.model, self.lmbd, self.engine = model, bn_lambda, engine
+    self.step(last_epoch + 1)
+    self.last_epoch = last_epoch
+
+  def step(self, epoch=None):
+    if epoch is None:
+      epoch = self.last_epoch + 1
+    self.last_epoch = epoch
+    momentum = float(self.lmbd(epoch))
+    for m in self.model.modules():
+      if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d, torch.nn.BatchNorm3d)):
+        m.momentum = momentum
+    if self.engine is not None:
+      self.engine.set_bn_momentum(momentum)
+    return momentum
+
+
+def detection_lr(epoch, learning_rate=1e-3, lr_decay_steps=(80, 120, 160), lr_decay_rates=(0.1, 0.1, 0.1)):
+  """get_current_lr of lib/train.py:44-50."""
+  lr = learning_rate
+  for step, rate in zip(lr_decay_steps, lr_decay_rates):
+    if epoch >= step:
+      lr *= rate
+  return lr
+
+
+def detection_bn_momentum(epoch, init=0.5, decay_rate=0.5, decay_step=20, floor=0.001):
+  """bn_lbmd of lib/train.py:184-188."""
+  return max(init * decay_rate ** int(epoch / decay_step), floor)
+
+
+LOSS_TERMS = ("loss", "vote_loss", "objectness_loss", "box_loss", "sem_cls_loss", "center_loss", "heading_cls_loss",
+              "heading_reg_loss", "size_cls_loss", "size_reg_loss", "obj_acc", "pos_ratio", "neg_ratio")
+
+
+class DetectionTrainer:
+  """One process, one GPU (the reference's detection fine-tuning is single-GPU): `train_iter(batch)` = forward, get_loss,
+  backward, Adam step (lib/train.py train_one_epoch's body).  The backbone (Res16UNet34C, 3 -> 256) runs under
+  NativeEngine(n_passes=1), the head eagerly through autograd; one FlatParameters covers both.  start_epoch(epoch) applies
+  the epoch's learning rate and BatchNorm momentum.  Mirrors SegmentationTrainer."""
+
+  def __init__(self, dataset_config, num_proposal=256, vote_factor=1, sampling="vote_fps", num_seed=1024, input_feature_dim=0,
+               seed_feature_dim=256, lr=1e-3, weight_decay=0.0, lr_decay_steps=(80, 120, 160), lr_decay_rates=(0.1, 0.1, 0.1),
+               bn_decay_step=20, bn_decay_rate=0.5, pretrained=None, kernel_order="hybrid", device=None, conv_precision="fp32",
+               input_pipeline=None):
+    from ..engine import NativeEngine
+    from ..lib import checkpoint as ck
+    from ..lib.distributed import FlatParameters
+    from ..lib.solver import FlatAdam
+    assert torch.cuda.is_available(), "the fine-tuning step runs on a gfx950 GPU (no CPU path)"
+    self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    self.config = dataset_config
+    self.model = VoteNet(dataset_config.num_class, dataset_config.num_heading_bin, dataset_config.num_size_cluster,
+                         dataset_config.mean_size_arr, input_feature_dim=input_feature_dim, num_proposal=num_proposal,
+                         vote_factor=vote_factor, sampling=sampling, num_seed=num_seed, seed_feature_dim=seed_feature_dim).to(self.device)
+    backbone = self.model.backbone_net.net
+    self.kernel_order = kernel_order
+    if pretrained is not None:  # a pre-training checkpoint: every backbone tensor whose name and shape match
+      state = torch.load(pretrained, map_location="cpu", weights_only=False) if isinstance(pretrained, str) else pretrained
+      weights = ck.convert_kernel_order(backbone, ck.strip_prefixes(state.get("state_dict", state)), kernel_order)
+      own = backbone.state_dict()
+      own.update(ck.load_state_with_same_shape(backbone, weights))
+      backbone.load_state_dict(own)
+    # the backbone's parameters first: the executor's program addresses them by their offsets in the flat buffer
+    self.flat = FlatParameters(list(backbone.parameters()) + self.model.head_parameters())
+    self.engine = NativeEngine(backbone, self.flat, in_channels=input_feature_dim + 3, n_passes=1, conv_precision=conv_precision)
+    self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay)
+    self.base_lr, self.lr_decay_steps, self.lr_decay_rates = lr, tuple(lr_decay_steps), tuple(lr_decay_rates)
+    self.bn_scheduler = BNMomentumScheduler(self.model, lambda e: detection_bn_momentum(e, decay_rate=bn_decay_rate, decay_step=bn_decay_step),
+                                            engine=self.engine)
+    self.input_pipeline = input_pipeline  # a DetectionInputPipeline, for train_iter_scenes
+    self.epoch, self.curr_iter = 0, 0
+    self.start_epoch(0)
+
+  def start_epoch(self, epoch):
+    """The epoch's learning rate (adjust_learning_rate) and BatchNorm momentum (bnm_scheduler.step) of lib/train.py:56-59."""
+    self.epoch = int(epoch)
+    lr = detection_lr(epoch, self.base_lr, self.lr_decay_steps, self.lr_decay_rates)
+    for g in self.optimizer.param_groups:
+      g["lr"] = lr
+    return lr, self.bn_scheduler.step(epoch)
+
+  def _to_device(self, batch):
+    return {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+  def forward(self, batch, training=True):
+    """batch: the input pipeline's dict, on the device.  Returns (end_points with the batch's labels merged in, the
+    backbone's output features -- a leaf whose .grad the backward pass hands to the executor)."""
+    from .. import minkowski as ME
+    st = ME.SparseTensor(batch["voxel_feats"].float(), coords=batch["voxel_coords"].int()).to(self.device)
+    feats = self.engine.forward(0, st, training=training)
+    if training:
+      feats.requires_grad_(True)
+    sparse_out = ME.SparseTensor(feats, coords_key=st.coords_key, coords_manager=st.coords_man)
+    end_points = self.model(batch, sparse_out=sparse_out)
+    for k, v in batch.items():
+      if k not in end_points:
+        end_points[k] = v
+    return end_points, feats
+
+  def train_iter(self, batch):
+    """Forward, get_loss, backward through the head and then the executor, Adam step.  Returns the loss terms as device
+    tensors; nothing synchronises."""
+    self.model.train()
+    self.optimizer.zero_grad()
+    batch = self._to_device(batch)
+    end_points, feats = self.forward(batch, training=True)
+    loss, end_points = get_loss(end_points, self.config)
+    loss.backward()
+    self.engine.backward(0, feats.grad)
+    self.optimizer.step()
+    self.curr_iter += 1
+    return {k: end_points[k].detach() for k in LOSS_TERMS if k in end_points}
+
+  def train_iter_scenes(self, scenes, draws=None):
+    """One iteration from raw scans through self.input_pipeline (a DetectionInputPipeline, the constructor's argument)."""
+    assert self.input_pipeline is not None, "construct the trainer with input_pipeline=DetectionInputPipeline(...)"
+    return self.train_iter(self.input_pipeline(scenes, draws))
+
+  @torch.no_grad()
+  def evaluate(self, batches, config_dict, ap_iou_thresh=(0.25, 0.5)):
+    """evaluate_one_epoch of lib/train.py over an iterable of batch dicts: eval-mode forward (running BatchNorm estimates),
+    the loss, decode_predictions and APCalculator.step_decoded per batch -- one match scores every threshold -- and ONE
+    read-back, in compute_metrics().  Returns the APCalculator's dict ({threshold: metrics} for a sequence of thresholds);
+    the calculator stays on self.ap_calculator, the mean loss terms (device tensors) on self.eval_losses."""
+    self.model.eval()
+    thresholds = list(ap_iou_thresh) if isinstance(ap_iou_thresh, (list, tuple, np.ndarray)) else ap_iou_thresh
+    self.ap_calculator = APCalculator(thresholds, getattr(self.config, "class2type", None), device=self.device)
+    sums, n = {}, 0
+    for batch in batches:
+      batch = self._to_device(batch)
+      end_points, _ = self.forward(batch, training=False)
+      _, end_points = get_loss(end_points, self.config)
+      for k in LOSS_TERMS:
+        if k in end_points:
+          sums[k] = sums.get(k, 0) + end_points[k].detach()
+      n += 1
+      self.ap_calculator.step_decoded(decode_predictions(end_points, config_dict), end_points, config_dict)
+    self.eval_losses = {k: v / max(n, 1) for k, v in sums.items()}
+    return self.ap_calculator.compute_metrics()
+
+  def state_dict(self):
+    """The reference's checkpoint form (lib/train.py: epoch, optimizer_state_dict, model_state_dict under the reference's
+    names and shapes); the backbone's kernels in the file enumeration given by kernel_order."""
+    from ..lib import checkpoint as ck
+    sd = self.model.state_dict()
+    prefix = "backbone_net.net."
+    inner = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    inner = ck.convert_kernel_order(self.model.backbone_net.net, inner, self.kernel_order, inverse=True)
+    for k, v in inner.items():
+      sd[prefix + k] = v
+    return {"epoch": self.epoch, "optimizer_state_dict": self.optimizer.state_dict(), "model_state_dict": sd}
+
+  def load_state_dict(self, state, load_optimizer=True):
+    """A checkpoint of state_dict(), or of the reference (its model_state_dict loads; its Adam state does not: the
+    parameters differ in layout, so pass load_optimizer=False)."""
+    from ..lib import checkpoint as ck
+    sd = dict(state.get("model_state_dict", state.get("state_dict", state)))
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    prefix = "backbone_net.net."
+    inner = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+    inner = ck.convert_kernel_order(self.model.backbone_net.net, inner, self.kernel_order)
+    for k, v in inner.items():
+      sd[prefix + k] = v
+    self.model.load_state_dict(sd)
+    if load_optimizer and "optimizer_state_dict" in state:
+      self.optimizer.load_state_dict(state["optimizer_state_dict"])
+    if "epoch" in state:
+      self.start_epoch(int(state["epoch"]))

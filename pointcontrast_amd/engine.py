@@ -195,6 +195,13 @@ class NativeEngine:
     check(lib.pcmi_net_set_conv_precision(self._h, conv_precision_code(mode)))
     self.conv_precision = mode
 
+  def set_bn_momentum(self, momentum):
+    """The momentum of every BatchNorm of the program for later training forwards (it is baked into the program when
+    the model is traced), and the modules' `.momentum` with it (the eager path and state inspection)."""
+    check(lib.pcmi_net_set_bn_momentum(self._h, float(momentum)))
+    for m in self._bn_modules:
+      m.bn.momentum = float(momentum)
+
   def __del__(self):
     try:
       if getattr(self, "_h", None):

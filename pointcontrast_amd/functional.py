@@ -1447,3 +1447,134 @@ def det_voxelize(point_clouds, voxel_size, flags=None):
   check(lib.pcmi_det_voxelize(ptr(pc), B, P, float(voxel_size), ptr(coords), ptr(inds), ptr(feats), ptr(counts), ptr(flags), ws, wsb,
                               cur_stream(dev)))
   return dict(voxel_coords=coords, voxel_inds=inds, voxel_feats=feats, counts=counts, flags=flags)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# VoteNet head on row-major activations (csrc/votehead.hip): fp32 rows [rows, ld], feature columns first, geometric columns
+# behind them, zero columns up to ld.  As with the point-set ops, the forward pass validates the indices on the device and
+# the backward pass reuses them without a host synchronisation.
+# ---------------------------------------------------------------------------------------------------------------------
+def pad_width(c, multiple=32):
+  """c rounded up to the next multiple (the dense GEMM's channel granularity)."""
+  return (int(c) + multiple - 1) // multiple * multiple
+
+
+class GroupRowsFunction(Function):
+  """QueryAndGroup(use_xyz=True, normalize_xyz) as rows: (xyz [B, n, 3], centre [B, np, 3], feat [B n, C] or None,
+  idx int32 [B, np, ns], radius_div, out_ld) -> [B np ns, out_ld] = features, (xyz - centre) / radius_div, zeros."""
+
+  @staticmethod
+  def forward(ctx, xyz, centre, feat, idx, radius_div, out_ld, validate=True):
+    xyz, centre = _f32c(xyz, "group_rows"), _f32c(centre, "group_rows")
+    dev = xyz.device
+    idx = _i32c(idx, dev)
+    assert xyz.dim() == 3 and centre.dim() == 3 and idx.dim() == 3 and xyz.shape[2] == 3 and centre.shape[2] == 3 and \
+        idx.shape[:2] == centre.shape[:2] and xyz.shape[0] == centre.shape[0], \
+        "group_rows: xyz [B, n, 3], centre [B, np, 3], idx [B, np, ns]"
+    B, n, _ = xyz.shape
+    _, npoint, ns = idx.shape
+    if feat is not None:
+      feat = _c(feat if feat.dtype == torch.float32 else feat.float())
+      assert feat.dim() == 2 and feat.shape[0] == B * n, "group_rows: feat [B n, C]"
+    Cc = feat.shape[1] if feat is not None else 0
+    out = torch.empty((B * npoint * ns, int(out_ld)), dtype=torch.float32, device=dev)
+    check(lib.pcmi_group_rows_fwd(ptr(xyz), ptr(centre), ptr(feat) if Cc else None, feat.stride(0) if Cc else 0, ptr(idx), B, n,
+                                  npoint, ns, Cc, float(radius_div), ptr(out), int(out_ld), int(bool(validate)), cur_stream(dev)))
+    ctx.save_for_backward(idx)
+    ctx.shape, ctx.radius_div, ctx.has_feat = (B, n, npoint, ns, Cc), float(radius_div), feat is not None
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    (idx,) = ctx.saved_tensors
+    B, n, npoint, ns, Cc = ctx.shape
+    g = _c(gout)
+    dev = g.device
+    gfeat = torch.empty((B * n, Cc), dtype=torch.float32, device=dev) if ctx.has_feat else None
+    gxyz = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    gcentre = torch.empty((B, npoint, 3), dtype=torch.float32, device=dev)
+    ws, wsb = ws_args(lib.pcmi_group_rows_bwd_workspace_bytes(B, n, npoint, ns), dev)
+    check(lib.pcmi_group_rows_bwd(ptr(g), g.stride(0), ptr(idx), B, n, npoint, ns, Cc, ctx.radius_div,
+                                  ptr(gfeat) if Cc else None, Cc, ptr(gxyz), ptr(gcentre), ws, wsb, cur_stream(dev)))
+    return gxyz, gcentre, gfeat, None, None, None, None
+
+
+def rows_maxpool(x, ns):
+  """(out [R, C], arg uint8 [R, C]) of x [R ns, C]: the maximum over every ns consecutive rows and the row within the window
+  that holds it -- the lowest among equals, the lowest NaN if there is one (pcmi_rows_maxpool_fwd)."""
+  require_cuda(x, "rows_maxpool")
+  x = _c(x)
+  rows, c, ld = _rows(x)
+  assert ns >= 1 and rows % ns == 0, "rows_maxpool: %d rows are not windows of %d" % (rows, ns)
+  R = rows // ns
+  out = torch.empty((R, c), dtype=torch.float32, device=x.device)
+  arg = torch.empty((R, c), dtype=torch.uint8, device=x.device)
+  check(lib.pcmi_rows_maxpool_fwd(ptr(x), ld, R, int(ns), c, ptr(out), c, ptr(arg), cur_stream(x.device)))
+  return out, arg
+
+
+class RowsMaxPoolFunction(Function):
+  """max_pool2d over nsample (pointnet2_modules.py:255-257) on rows: x [R ns, C] -> [R, C]."""
+
+  @staticmethod
+  def forward(ctx, x, ns):
+    out, arg = rows_maxpool(x, ns)
+    ctx.save_for_backward(arg)
+    ctx.ns = int(ns)
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    (arg,) = ctx.saved_tensors
+    g = _c(gout)
+    R, c = arg.shape
+    gx = torch.empty((R * ctx.ns, c), dtype=torch.float32, device=g.device)
+    check(lib.pcmi_rows_maxpool_bwd(ptr(g), g.stride(0), ptr(arg), R, ctx.ns, c, ptr(gx), c, cur_stream(g.device)))
+    return gx, None
+
+
+class VoteFunction(Function):
+  """The tail of VotingModule.forward and the feature normalisation of votenet.py:120-121: (net [R, vf Wb], seed_xyz [R, 3],
+  seed_feat [R, C], vote_factor) -> (vote_xyz [R vf, 3], vote_feat [R vf, C]); block v of a row of net holds C residual
+  features, then 3 offsets, then zeros."""
+
+  @staticmethod
+  def forward(ctx, net, seed_xyz, seed_feat, vote_factor):
+    require_cuda(net, "vote")
+    net, seed_feat = _c(net), _c(seed_feat)
+    seed_xyz = _f32c(seed_xyz, "vote").reshape(-1, 3)
+    R, width, net_ld = _rows(net)
+    vf, Cc = int(vote_factor), seed_feat.shape[1]
+    assert width % vf == 0 and seed_feat.shape[0] == R and seed_xyz.shape[0] == R, "vote: net [R, vf Wb], seed_xyz [R, 3], seed_feat [R, C]"
+    Wb, dev = width // vf, net.device
+    vote_xyz = torch.empty((R * vf, 3), dtype=torch.float32, device=dev)
+    vote_feat = torch.empty((R * vf, Cc), dtype=torch.float32, device=dev)
+    norm = torch.empty(R * vf, dtype=torch.float32, device=dev)
+    check(lib.pcmi_vote_fwd(ptr(net), net_ld, ptr(seed_xyz), ptr(seed_feat), seed_feat.stride(0), R, vf, Cc, Wb, ptr(vote_xyz),
+                            ptr(vote_feat), Cc, ptr(norm), cur_stream(dev)))
+    ctx.save_for_backward(vote_feat, norm)
+    ctx.shape = (R, vf, Cc, Wb)
+    return vote_xyz, vote_feat
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, g_xyz, g_feat):
+    vote_feat, norm = ctx.saved_tensors
+    R, vf, Cc, Wb = ctx.shape
+    dev = vote_feat.device
+    g_xyz, g_feat = _f32c(g_xyz, "vote"), _c(g_feat)
+    g_net = torch.empty((R, vf * Wb), dtype=torch.float32, device=dev)
+    g_sf = torch.empty((R, Cc), dtype=torch.float32, device=dev)
+    g_sx = torch.empty((R, 3), dtype=torch.float32, device=dev)
+    check(lib.pcmi_vote_bwd(ptr(g_feat), g_feat.stride(0), ptr(g_xyz), ptr(vote_feat), Cc, ptr(norm), R, vf, Cc, Wb, ptr(g_net),
+                            vf * Wb, ptr(g_sf), Cc, ptr(g_sx), cur_stream(dev)))
+    return g_net, g_sx, g_sf, None
+
+
+def adam_step(w, g, m, v, lr, betas, eps, weight_decay, step):
+  """torch.optim.Adam's step number `step` (>= 1) on flat buffers (pcmi_adam_step): amsgrad off, L2 weight decay."""
+  require_cuda(w, "adam step")
+  check(lib.pcmi_adam_step(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                           float(weight_decay), int(step), cur_stream(w.device)))
