@@ -599,6 +599,57 @@ int pcmi_vote_bwd(const float* g_vote_feat, int64_t g_vote_feat_ld, const float*
 int pcmi_adam_step(float* w, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int64_t t, pcmi_stream_t stream);
 
+/* ---- PointNet++ backbone on rows (csrc/rowspool.hip) -------------------------------------------------------------------
+ * The two row kernels that vn/models/backbone_module.py's Pointnet2Backbone needs beyond the head's: the last SharedMLP
+ * layer's BatchNorm + ReLU fused with the max over nsample behind it (pointnet2_modules.py:251-257), and
+ * PointnetFPModule's three_interpolate + concatenation written straight into rows (:394-409).  Layout and conventions as
+ * for the head above; no float atomics, every result is the same bits from run to run; a refused call enqueues nothing.
+ *
+ * pcmi_bn_maxpool_fwd_train: x [R ns, C] (x_ld) -> out [R, C] (out_ld), arg [R, C] uint8 (contiguous), save_mean and
+ *   save_invstd [C].  Batch statistics over all n = R ns rows with pcmi_bn_fwd_train's conventions (biased variance for the
+ *   normalisation, unbiased for the running estimate -- the biased one when n == 1 --, running = (1 - momentum) running +
+ *   momentum batch; running_mean / running_var both NULL: no update), from fp64 (sum x, sum x^2) partials per row chunk
+ *   merged in a fixed order.  Then ONE pass computes y = relu((x - mean) * (invstd * gamma) + beta) per element, each
+ *   operation rounded on its own, and writes the maximum over every ns consecutive rows and the row that holds it; y is
+ *   never stored.  The decision rule is pcmi_rows_maxpool_fwd's on y: rows in ascending order, strict >, so the LOWEST row
+ *   wins among equals and a column that is <= 0 in the whole window gives (0, row 0); a NaN y is the result and the lowest
+ *   NaN row the argument.  The maximum is over y, not x: a negative gamma reverses the order.
+ *   1 <= ns <= 256, else PCMI_ERR_UNSUPPORTED; ws of pcmi_bn_maxpool_workspace_bytes(R, ns, C), else PCMI_ERR_WORKSPACE.
+ *   16-byte accesses when C % 4 == 0, the leading dimensions are multiples of 4 and x / out are 16-byte aligned (arg 4-byte
+ *   aligned), 4-byte accesses otherwise.
+ * pcmi_bn_maxpool_fwd_eval: the same pass on the running estimates, invstd = 1 / sqrt(running_var + eps); arg may be NULL;
+ *   no workspace.
+ * pcmi_bn_maxpool_bwd: gout [R, C], x, out, arg, gamma, save_mean, save_invstd -> dx [R ns, C] (dx_ld) written whole,
+ *   dgamma, dbeta [C].  g(r, c) = gout where out > 0, else 0, and sits at row r ns + arg; xhat = (x - mean) * invstd;
+ *   dbeta = sum_r g, dgamma = sum_r g xhat at that row (fp64 partials over the R pooled rows, fixed order),
+ *   dx_i = (gamma invstd) ((g_i - dbeta / n) - xhat_i dgamma / n).  An arg outside [0, ns) is read as 0.
+ * pcmi_interp_rows_fwd: known [B m, C2] (known_ld), idx int32 / weight fp32 [B, n, 3], skip [B n, C1] (skip_ld; NULL with
+ *   C1 == 0) -> out [B n, out_ld]: out[b n + i, 0:C2] = ((w0 f0) + (w1 f1)) + (w2 f2) with f_k = known[b m + idx_k], every
+ *   operation rounded on its own; columns C2 .. C2 + C1 a copy of skip; zeros up to out_ld >= C2 + C1.  One wave per row.
+ *   validate != 0: the indices are checked on the device first, the call SYNCS, PCMI_ERR_RANGE with nothing else launched;
+ *   validate == 0: an index outside [0, m) is never dereferenced and reads as 0.
+ * pcmi_interp_rows_bwd: gout [B n, >= C2] (gout_ld) -> gknown [B m, C2] (gknown_ld), written whole: every known point sums
+ *   weight * gout over the (row, k) slots that named it, in ascending slot, in gather form over the inverse lists of
+ *   csrc/pointset.hip (ws: pcmi_interp_rows_bwd_workspace_bytes); an index outside [0, m) is dropped.  The gradient of skip
+ *   is the view gout[:, C2:C2 + C1].  No synchronisation. */
+size_t pcmi_bn_maxpool_workspace_bytes(int64_t R, int ns, int c);
+int pcmi_bn_maxpool_fwd_train(const float* x, int64_t x_ld, int64_t R, int ns, int C, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var, float momentum, float eps, float* out, int64_t out_ld,
+                              uint8_t* arg, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_bn_maxpool_fwd_eval(const float* x, int64_t x_ld, int64_t R, int ns, int C, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps, float* out, int64_t out_ld,
+                             uint8_t* arg, pcmi_stream_t stream);
+int pcmi_bn_maxpool_bwd(const float* gout, int64_t gout_ld, const float* x, int64_t x_ld, const float* out, int64_t out_ld,
+                        const uint8_t* arg, int64_t R, int ns, int C, const float* gamma, const float* save_mean,
+                        const float* save_invstd, float* dx, int64_t dx_ld, float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                        pcmi_stream_t stream);
+int pcmi_interp_rows_fwd(const float* known, int64_t known_ld, const int32_t* idx, const float* weight, const float* skip,
+                         int64_t skip_ld, int64_t B, int64_t m, int64_t n, int C2, int C1, float* out, int64_t out_ld, int validate,
+                         pcmi_stream_t stream);
+size_t pcmi_interp_rows_bwd_workspace_bytes(int64_t B, int64_t m, int64_t n);
+int pcmi_interp_rows_bwd(const float* gout, int64_t gout_ld, const int32_t* idx, const float* weight, int64_t B, int64_t m,
+                         int64_t n, int C2, float* gknown, int64_t gknown_ld, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+
 /* ---- VoteNet detection head (csrc/detect.hip) ------------------------------------------------------------------------
  * The matching of the detection loss and the decoding of the predictions ("vn/" as above).  fp32 data, int32 indices,
  * contiguous tensors.  Every operation of a distance is rounded on its own in fp32, in the order written here, so the

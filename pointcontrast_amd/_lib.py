@@ -177,6 +177,17 @@ PROTOTYPES = {
     "pcmi_vote_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, C.c_int, c_vp, c_i64, c_vp, c_i64,
                                 c_vp, c_vp]),
     "pcmi_adam_step": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_vp]),
+    "pcmi_bn_maxpool_workspace_bytes": (c_sz, [c_i64, C.c_int, C.c_int]),
+    "pcmi_bn_maxpool_fwd_train": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_i64,
+                                            c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_bn_maxpool_fwd_eval": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp,
+                                           c_vp]),
+    "pcmi_bn_maxpool_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp,
+                                      c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_interp_rows_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_i64,
+                                       C.c_int, c_vp]),
+    "pcmi_interp_rows_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pcmi_interp_rows_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_vp, c_i64, c_vp, c_sz, c_vp]),
     "pcmi_nn_distance_fwd": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_vp, c_vp]),
     "pcmi_nn_distance_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "pcmi_nn_distance_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, C.c_int, c_f32, c_vp, c_vp,

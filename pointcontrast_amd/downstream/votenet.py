@@ -793,6 +793,18 @@ class RowBatchNorm(torch.nn.BatchNorm1d):
                                         None, relu)
     return PF.batch_norm_eval(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, None, relu)
 
+  def forward_maxpool(self, x, ns, return_arg=False):
+    """BatchNorm + ReLU + the maximum over every ns consecutive rows in one pass (pcmi_bn_maxpool_*): x [R ns, C] -> [R, C],
+    the same statistics, running estimates and decision rule as rows_maxpool(forward(x)); the full output is never stored.
+    return_arg: also the uint8 rows [R, C] that hold the maxima."""
+    if self.training:
+      self._untracked += 1
+      out, arg = PF.BatchNormMaxPoolFunction.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum,
+                                                   self.eps, ns)
+    else:
+      out, arg = PF.batch_norm_maxpool_eval(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, ns, want_arg=True)
+    return (out, arg) if return_arg else out
+
 
 class VotingModule(torch.nn.Module):
   """models/voting_module.py on rows: (seed_xyz [B, S, 3], seed rows [B S, C]) -> (vote_xyz [B S vf, 3], vote rows [B S vf, C]),
@@ -856,6 +868,152 @@ class VoteAggregation(torch.nn.Module):
     for i in range(self.n_layers):
       x = getattr(self.mlp_module, "layer%d" % i)(x)
     return new_xyz, PF.RowsMaxPoolFunction.apply(x, self.nsample), idx
+
+
+# ---- the PointNet++ backbone on rows (csrc/rowspool.hip beside votehead.hip and pointset.hip) ---------------------------------
+POINTNET2_NPOINTS = (2048, 1024, 512, 256)
+POINTNET2_RADII = (0.2, 0.4, 0.8, 1.2)
+POINTNET2_NSAMPLES = (64, 32, 16, 16)
+POINTNET2_SA_MLPS = ((64, 64, 128), (128, 128, 256), (128, 128, 256), (128, 128, 256))  # behind each level's input width
+POINTNET2_FP_MLPS = ((256, 256), (256, 256))
+
+
+def _check_widths(who, widths):
+  for w in widths:
+    if w % 32:
+      raise ValueError("%s: layer width %d is not a multiple of 32 (the dense GEMM's granularity)" % (who, w))
+
+
+class PointnetSAModuleVotes(torch.nn.Module):
+  """PointnetSAModuleVotes(npoint, radius, nsample, mlp, use_xyz=True, normalize_xyz) of the reference on rows: furthest point
+  sampling, the ball query, the neighbourhoods written straight into rows (pcmi_group_rows_fwd), the SharedMLP as GEMM +
+  BatchNorm + ReLU layers, and the last layer's BatchNorm + ReLU fused with the maximum over nsample (pcmi_bn_maxpool_*).
+  mlp = [C, c1, ..., cL] WITHOUT the three coordinate channels, as the reference's argument; c1 .. cL multiples of 32.
+  fused_pool=False keeps the composition RowBatchNorm -> RowsMaxPoolFunction (A/B measurements and tests)."""
+
+  def __init__(self, *, mlp, npoint, radius, nsample, use_xyz=True, normalize_xyz=True, fused_pool=True):
+    super().__init__()
+    if not use_xyz:
+      raise NotImplementedError("PointnetSAModuleVotes on rows: use_xyz=False is not provided")
+    self.npoint, self.radius, self.nsample, self.C = int(npoint), float(radius), int(nsample), int(mlp[0])
+    self.normalize_xyz, self.fused_pool = bool(normalize_xyz), bool(fused_pool)
+    _check_widths("PointnetSAModuleVotes", mlp[1:])
+    self.mlp_module = torch.nn.Module()
+    cin = self.C + 3
+    for i, cout in enumerate(mlp[1:]):
+      self.mlp_module.add_module("layer%d" % i, _ConvBN(cin, cout, in_map=features_then_xyz(self.C) if i == 0 else None))
+      cin = cout
+    self.n_layers = len(mlp) - 1
+    # the last forward's picks, neighbourhoods and (fused pool) pooling rows, for inspection
+    self.last_inds = self.last_idx = self.last_arg = None
+
+  def forward(self, xyz, rows=None, inds=None):
+    """xyz [B, N, 3], rows [B N, C] (None with C == 0), inds int [B, npoint] or None -> (new_xyz [B, npoint, 3], pooled rows
+    [B npoint, cL], inds int32 [B, npoint])."""
+    B = xyz.shape[0]
+    if inds is None:
+      inds = PF.FurthestPointSampleFunction.apply(xyz.detach(), self.npoint)
+    inds = inds.to(device=xyz.device, dtype=torch.int32)
+    assert tuple(inds.shape) == (B, self.npoint), "inds: [B, npoint]"
+    new_xyz = torch.gather(xyz, 1, inds.to(torch.int64).unsqueeze(-1).expand(B, self.npoint, 3))
+    idx = PF.BallQueryFunction.apply(self.radius, self.nsample, xyz.detach(), new_xyz.detach())
+    x = PF.GroupRowsFunction.apply(xyz, new_xyz, rows if self.C else None, idx, self.radius if self.normalize_xyz else 1.0,
+                                   PF.pad_width(self.C + 3), False)
+    for i in range(self.n_layers - 1):
+      x = getattr(self.mlp_module, "layer%d" % i)(x)
+    last = getattr(self.mlp_module, "layer%d" % (self.n_layers - 1))
+    self.last_inds, self.last_idx = inds, idx
+    if self.fused_pool:
+      pooled, self.last_arg = last.bn.bn.forward_maxpool(last.conv(x), self.nsample, return_arg=True)
+    else:
+      pooled, self.last_arg = PF.RowsMaxPoolFunction.apply(last(x), self.nsample), None
+    return new_xyz, pooled, inds
+
+
+class PointnetFPModule(torch.nn.Module):
+  """PointnetFPModule(mlp) of the reference on rows: the three nearest known points (pcmi_three_nn), the reference's weights
+  1 / (dist + 1e-8) normalised over the three, the interpolation and the concatenation with the unknown points' own features
+  written into rows in one pass (pcmi_interp_rows_fwd), then the SharedMLP.  mlp = [C2 + C1, c1, ..., cL]."""
+
+  def __init__(self, *, mlp):
+    super().__init__()
+    _check_widths("PointnetFPModule", mlp[1:])
+    self.cin = int(mlp[0])
+    self.mlp = torch.nn.Module()
+    cin = self.cin
+    for i, cout in enumerate(mlp[1:]):
+      self.mlp.add_module("layer%d" % i, _ConvBN(cin, cout))
+      cin = cout
+    self.n_layers = len(mlp) - 1
+    self.last_idx = None
+
+  def forward(self, unknown, known, unknown_rows, known_rows):
+    """unknown [B, n, 3], known [B, m, 3], unknown_rows [B n, C1] or None, known_rows [B m, C2] -> rows [B n, cL]."""
+    dist, idx = PF.ThreeNNFunction.apply(unknown.detach(), known.detach())
+    dist_recip = 1.0 / (dist + 1e-8)
+    weight = dist_recip / torch.sum(dist_recip, dim=2, keepdim=True)
+    C1 = unknown_rows.shape[1] if unknown_rows is not None else 0
+    assert known_rows.shape[1] + C1 == self.cin, "PointnetFPModule: %d + %d feature columns, the first layer takes %d" % (
+        known_rows.shape[1], C1, self.cin)
+    self.last_idx = idx
+    x = PF.InterpRowsFunction.apply(known_rows, idx, weight, unknown_rows, PF.pad_width(self.cin), False)
+    for i in range(self.n_layers):
+      x = getattr(self.mlp, "layer%d" % i)(x)
+    return x
+
+
+class Pointnet2Backbone(torch.nn.Module):
+  """models/backbone_module.py Pointnet2Backbone on rows: four set-abstraction levels and two feature propagations; the
+  defaults are the reference's numbers.  forward(pointcloud [B, N, 3 + input_feature_dim]) returns the reference's end_points:
+  saK_xyz [B, npoint, 3], saK_features [B, C, npoint] (views of the rows), sa1_inds, sa2_inds, fp2_inds (int32), fp2_xyz and
+  fp2_features [B, 256, 1024].  Differences from the reference: fp2_inds = sa1_inds taken at sa2_inds --
+  the reference's sa1_inds[:, :num_seed] wherever its comment "this fps_inds is just 0, 1, ..., 1023" holds, and the seeds'
+  true points where it does not; ties of the sampling and of the pooling go to the lowest index / row."""
+
+  def __init__(self, input_feature_dim=0, npoints=POINTNET2_NPOINTS, radii=POINTNET2_RADII, nsamples=POINTNET2_NSAMPLES,
+               sa_mlps=None, fp_mlps=None, fused_pool=True):
+    super().__init__()
+    F_ = int(input_feature_dim)
+    if sa_mlps is None:
+      cins = (F_,) + tuple(m[-1] for m in POINTNET2_SA_MLPS[:-1])
+      sa_mlps = tuple((c,) + tuple(m) for c, m in zip(cins, POINTNET2_SA_MLPS))
+    if fp_mlps is None:
+      fp_mlps = ((sa_mlps[3][-1] + sa_mlps[2][-1],) + POINTNET2_FP_MLPS[0], (POINTNET2_FP_MLPS[0][-1] + sa_mlps[1][-1],) + POINTNET2_FP_MLPS[1])
+    assert len(sa_mlps) == 4 and len(fp_mlps) == 2 and len(npoints) == 4 and len(radii) == 4 and len(nsamples) == 4
+    assert sa_mlps[0][0] == F_, "the first level takes the input's %d feature columns" % F_
+    self.input_feature_dim = F_
+    for k in range(4):
+      self.add_module("sa%d" % (k + 1), PointnetSAModuleVotes(npoint=npoints[k], radius=radii[k], nsample=nsamples[k], mlp=list(sa_mlps[k]),
+                                                             use_xyz=True, normalize_xyz=True, fused_pool=fused_pool))
+    self.fp1 = PointnetFPModule(mlp=list(fp_mlps[0]))
+    self.fp2 = PointnetFPModule(mlp=list(fp_mlps[1]))
+    self.num_seed, self.out_dim = int(npoints[1]), int(fp_mlps[1][-1])
+
+  def forward(self, pointcloud, end_points=None):
+    if not end_points:
+      end_points = {}
+    PF.require_cuda(pointcloud, "Pointnet2Backbone")
+    assert pointcloud.dim() == 3 and pointcloud.shape[2] == 3 + self.input_feature_dim, \
+        "pointcloud: [B, N, 3 + %d], got %s" % (self.input_feature_dim, tuple(pointcloud.shape))
+    B, N, W = pointcloud.shape
+    pointcloud = pointcloud.float()
+    xyz = pointcloud[..., 0:3].contiguous()
+    rows = pointcloud.reshape(B * N, W)[:, 3:] if W > 3 else None
+    saved = {}
+    for k in (1, 2, 3, 4):
+      xyz, rows, inds = getattr(self, "sa%d" % k)(xyz, rows)
+      saved[k] = (xyz, rows)
+      end_points["sa%d_xyz" % k] = xyz
+      end_points["sa%d_features" % k] = rows.reshape(B, xyz.shape[1], rows.shape[1]).transpose(1, 2)
+      if k <= 2:
+        end_points["sa%d_inds" % k] = inds
+    rows = self.fp1(saved[3][0], saved[4][0], saved[3][1], saved[4][1])
+    rows = self.fp2(saved[2][0], saved[3][0], saved[2][1], rows)
+    S = saved[2][0].shape[1]
+    end_points["fp2_features"] = rows.reshape(B, S, rows.shape[1]).transpose(1, 2)
+    end_points["fp2_xyz"] = saved[2][0]
+    end_points["fp2_inds"] = torch.gather(end_points["sa1_inds"], 1, end_points["sa2_inds"].to(torch.int64))
+    return end_points
 
 
 def decode_scores(net, end_points, num_class, num_heading_bin, num_size_cluster, mean_size_arr):
@@ -935,21 +1093,29 @@ class SparseConvBackbone(torch.nn.Module):
 
 
 class VoteNet(torch.nn.Module):
-  """models/votenet.py with the sparse backbone.  forward(inputs) takes the input pipeline's batch dict (point_clouds,
-  voxel_coords, voxel_feats, voxel_inds) and returns end_points with the reference's keys, shapes and dtypes, as [B, K, ...]
-  views of the rows (vote_features and seed_features as [B, C, K] views); get_loss and decode_predictions consume it
-  unchanged.  The "pointnet2" backbone is not provided."""
+  """models/votenet.py.  backbone="sparseconv": forward(inputs) takes the input pipeline's batch dict (point_clouds,
+  voxel_coords, voxel_feats, voxel_inds); backbone="pointnet2" (the reference's default, Pointnet2Backbone on rows): it needs
+  only point_clouds [B, N, 3 + input_feature_dim], and the backbone's end_points (saK_*, fp2_*) are returned too.  Either way
+  the result is end_points with the reference's keys, shapes and dtypes, as [B, K, ...] views of the rows (vote_features and
+  seed_features as [B, C, K] views); get_loss and decode_predictions consume it unchanged."""
 
   def __init__(self, num_class, num_heading_bin, num_size_cluster, mean_size_arr, input_feature_dim=0, num_proposal=128,
                vote_factor=1, sampling="vote_fps", backbone="sparseconv", num_seed=1024, seed_feature_dim=256):
     super().__init__()
-    if backbone != "sparseconv":
-      raise NotImplementedError("VoteNet: only the sparse backbone is provided (backbone=%r)" % (backbone,))
+    if backbone not in ("sparseconv", "pointnet2"):
+      raise NotImplementedError("VoteNet: backbone is 'sparseconv' or 'pointnet2' (backbone=%r)" % (backbone,))
     mean_size_arr = np.asarray(mean_size_arr, np.float32)
     assert mean_size_arr.shape[0] == num_size_cluster
     self.num_class, self.num_heading_bin, self.num_size_cluster, self.mean_size_arr = num_class, num_heading_bin, num_size_cluster, mean_size_arr
     self.input_feature_dim, self.num_proposal, self.vote_factor, self.sampling = input_feature_dim, num_proposal, vote_factor, sampling
-    self.backbone_net = SparseConvBackbone(input_feature_dim + 3, seed_feature_dim, num_seed)
+    self.backbone = backbone
+    if backbone == "pointnet2":
+      self.backbone_net = Pointnet2Backbone(input_feature_dim=input_feature_dim)
+      if (self.backbone_net.num_seed, self.backbone_net.out_dim) != (num_seed, seed_feature_dim):
+        raise ValueError("VoteNet: the pointnet2 backbone gives %d seeds of %d features (num_seed=%r, seed_feature_dim=%r)" % (
+            self.backbone_net.num_seed, self.backbone_net.out_dim, num_seed, seed_feature_dim))
+    else:
+      self.backbone_net = SparseConvBackbone(input_feature_dim + 3, seed_feature_dim, num_seed)
     self.vgen = VotingModule(vote_factor, seed_feature_dim)
     self.pnet = ProposalModule(num_class, num_heading_bin, num_size_cluster, mean_size_arr, num_proposal, sampling,
                                seed_feat_dim=seed_feature_dim)
@@ -974,9 +1140,15 @@ class VoteNet(torch.nn.Module):
   def forward(self, inputs, sparse_out=None):
     """sparse_out: the backbone's output SparseTensor when something else ran the backbone (DetectionTrainer: the native
     executor); None runs self.backbone_net.net eagerly."""
-    from .. import minkowski as ME
     points = inputs["point_clouds"]
     dev = self.vgen.conv1.weight.device
+    if self.backbone == "pointnet2":
+      end_points = self.backbone_net(points.to(dev))
+      B, C, S = end_points["fp2_features"].shape
+      seed_rows = end_points["fp2_features"].transpose(1, 2).reshape(B * S, C)  # the rows themselves: the view of a view
+      end_points.update(self.forward_head(end_points["fp2_xyz"], seed_rows, end_points["fp2_inds"], inputs.get("sample_inds")))
+      return end_points
+    from .. import minkowski as ME
     if sparse_out is None:
       st = ME.SparseTensor(inputs["voxel_feats"].float(), coords=inputs["voxel_coords"].int()).to(dev)
       sparse_out = self.backbone_net.net(st)
@@ -1033,24 +1205,47 @@ class DetectionTrainer:
   """One process, one GPU (the reference's detection fine-tuning is single-GPU): `train_iter(batch)` = forward, get_loss,
   backward, Adam step (lib/train.py train_one_epoch's body).  The backbone (Res16UNet34C, 3 -> 256) runs under
   NativeEngine(n_passes=1), the head eagerly through autograd; one FlatParameters covers both.  start_epoch(epoch) applies
-  the epoch's learning rate and BatchNorm momentum.  Mirrors SegmentationTrainer."""
+  the epoch's learning rate and BatchNorm momentum.  Mirrors SegmentationTrainer.
+
+  backbone="pointnet2" (the from-scratch VoteNet baseline): no executor -- the whole model goes through autograd, all of its
+  parameters lie in the one FlatParameters, FlatAdam and the schedules are the same; the batch needs only point_clouds
+  [B, N, 3 + input_feature_dim] beside the labels; state_dict / load_state_dict hold no sparse kernels to convert; pretrained=
+  is refused (a pre-training checkpoint holds a sparse backbone)."""
 
   def __init__(self, dataset_config, num_proposal=256, vote_factor=1, sampling="vote_fps", num_seed=1024, input_feature_dim=0,
                seed_feature_dim=256, lr=1e-3, weight_decay=0.0, lr_decay_steps=(80, 120, 160), lr_decay_rates=(0.1, 0.1, 0.1),
                bn_decay_step=20, bn_decay_rate=0.5, pretrained=None, kernel_order="hybrid", device=None, conv_precision="fp32",
-               input_pipeline=None):
-    from ..engine import NativeEngine
-    from ..lib import checkpoint as ck
+               input_pipeline=None, backbone="sparseconv"):
     from ..lib.distributed import FlatParameters
     from ..lib.solver import FlatAdam
     assert torch.cuda.is_available(), "the fine-tuning step runs on a gfx950 GPU (no CPU path)"
     self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    self.config = dataset_config
+    self.config, self.backbone = dataset_config, backbone
+    if backbone == "pointnet2" and pretrained is not None:
+      raise ValueError("DetectionTrainer: pretrained= holds a sparse backbone; the pointnet2 backbone trains from scratch "
+                       "(load a VoteNet checkpoint with load_state_dict)")
     self.model = VoteNet(dataset_config.num_class, dataset_config.num_heading_bin, dataset_config.num_size_cluster,
                          dataset_config.mean_size_arr, input_feature_dim=input_feature_dim, num_proposal=num_proposal,
-                         vote_factor=vote_factor, sampling=sampling, num_seed=num_seed, seed_feature_dim=seed_feature_dim).to(self.device)
-    backbone = self.model.backbone_net.net
+                         vote_factor=vote_factor, sampling=sampling, num_seed=num_seed, seed_feature_dim=seed_feature_dim,
+                         backbone=backbone).to(self.device)
     self.kernel_order = kernel_order
+    if backbone == "pointnet2":
+      self.flat, self.engine = FlatParameters(list(self.model.parameters())), None
+    else:
+      self._init_sparse_backbone(pretrained, kernel_order, input_feature_dim, conv_precision)
+    self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay)
+    self.base_lr, self.lr_decay_steps, self.lr_decay_rates = lr, tuple(lr_decay_steps), tuple(lr_decay_rates)
+    self.bn_scheduler = BNMomentumScheduler(self.model, lambda e: detection_bn_momentum(e, decay_rate=bn_decay_rate, decay_step=bn_decay_step),
+                                            engine=self.engine)
+    self.input_pipeline = input_pipeline  # a DetectionInputPipeline, for train_iter_scenes
+    self.epoch, self.curr_iter = 0, 0
+    self.start_epoch(0)
+
+  def _init_sparse_backbone(self, pretrained, kernel_order, input_feature_dim, conv_precision):
+    from ..engine import NativeEngine
+    from ..lib import checkpoint as ck
+    from ..lib.distributed import FlatParameters
+    backbone = self.model.backbone_net.net
     if pretrained is not None:  # a pre-training checkpoint: every backbone tensor whose name and shape match
       state = torch.load(pretrained, map_location="cpu", weights_only=False) if isinstance(pretrained, str) else pretrained
       weights = ck.convert_kernel_order(backbone, ck.strip_prefixes(state.get("state_dict", state)), kernel_order)
@@ -1060,13 +1255,6 @@ class DetectionTrainer:
     # the backbone's parameters first: the executor's program addresses them by their offsets in the flat buffer
     self.flat = FlatParameters(list(backbone.parameters()) + self.model.head_parameters())
     self.engine = NativeEngine(backbone, self.flat, in_channels=input_feature_dim + 3, n_passes=1, conv_precision=conv_precision)
-    self.optimizer = FlatAdam(self.flat, lr=lr, weight_decay=weight_decay)
-    self.base_lr, self.lr_decay_steps, self.lr_decay_rates = lr, tuple(lr_decay_steps), tuple(lr_decay_rates)
-    self.bn_scheduler = BNMomentumScheduler(self.model, lambda e: detection_bn_momentum(e, decay_rate=bn_decay_rate, decay_step=bn_decay_step),
-                                            engine=self.engine)
-    self.input_pipeline = input_pipeline  # a DetectionInputPipeline, for train_iter_scenes
-    self.epoch, self.curr_iter = 0, 0
-    self.start_epoch(0)
 
   def start_epoch(self, epoch):
     """The epoch's learning rate (adjust_learning_rate) and BatchNorm momentum (bnm_scheduler.step) of lib/train.py:56-59."""
@@ -1081,8 +1269,15 @@ class DetectionTrainer:
 
   def forward(self, batch, training=True):
     """batch: the input pipeline's dict, on the device.  Returns (end_points with the batch's labels merged in, the
-    backbone's output features -- a leaf whose .grad the backward pass hands to the executor)."""
+    backbone's output features -- a leaf whose .grad the backward pass hands to the executor; None with the pointnet2
+    backbone, which autograd covers)."""
     from .. import minkowski as ME
+    if self.engine is None:
+      end_points = self.model(batch)
+      for k, v in batch.items():
+        if k not in end_points:
+          end_points[k] = v
+      return end_points, None
     st = ME.SparseTensor(batch["voxel_feats"].float(), coords=batch["voxel_coords"].int()).to(self.device)
     feats = self.engine.forward(0, st, training=training)
     if training:
@@ -1103,7 +1298,8 @@ class DetectionTrainer:
     end_points, feats = self.forward(batch, training=True)
     loss, end_points = get_loss(end_points, self.config)
     loss.backward()
-    self.engine.backward(0, feats.grad)
+    if self.engine is not None:
+      self.engine.backward(0, feats.grad)
     self.optimizer.step()
     self.curr_iter += 1
     return {k: end_points[k].detach() for k in LOSS_TERMS if k in end_points}
@@ -1140,11 +1336,12 @@ class DetectionTrainer:
     names and shapes); the backbone's kernels in the file enumeration given by kernel_order."""
     from ..lib import checkpoint as ck
     sd = self.model.state_dict()
-    prefix = "backbone_net.net."
-    inner = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-    inner = ck.convert_kernel_order(self.model.backbone_net.net, inner, self.kernel_order, inverse=True)
-    for k, v in inner.items():
-      sd[prefix + k] = v
+    if self.engine is not None:
+      prefix = "backbone_net.net."
+      inner = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+      inner = ck.convert_kernel_order(self.model.backbone_net.net, inner, self.kernel_order, inverse=True)
+      for k, v in inner.items():
+        sd[prefix + k] = v
     return {"epoch": self.epoch, "optimizer_state_dict": self.optimizer.state_dict(), "model_state_dict": sd}
 
   def load_state_dict(self, state, load_optimizer=True):
@@ -1153,11 +1350,12 @@ class DetectionTrainer:
     from ..lib import checkpoint as ck
     sd = dict(state.get("model_state_dict", state.get("state_dict", state)))
     sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-    prefix = "backbone_net.net."
-    inner = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-    inner = ck.convert_kernel_order(self.model.backbone_net.net, inner, self.kernel_order)
-    for k, v in inner.items():
-      sd[prefix + k] = v
+    if self.engine is not None:
+      prefix = "backbone_net.net."
+      inner = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+      inner = ck.convert_kernel_order(self.model.backbone_net.net, inner, self.kernel_order)
+      for k, v in inner.items():
+        sd[prefix + k] = v
     self.model.load_state_dict(sd)
     if load_optimizer and "optimizer_state_dict" in state:
       self.optimizer.load_state_dict(state["optimizer_state_dict"])

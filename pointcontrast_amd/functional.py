@@ -1535,6 +1535,107 @@ class RowsMaxPoolFunction(Function):
     return gx, None
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The PointNet++ backbone on rows (csrc/rowspool.hip): BatchNorm + ReLU + max over nsample in one pass, and the feature
+# propagation's interpolation + concatenation written into rows.
+# ---------------------------------------------------------------------------------------------------------------------
+def _maxpool_rows(x, ns, who):
+  require_cuda(x, who)
+  x = _c(x)
+  rows, c, ld = _rows(x)
+  assert ns >= 1 and rows % ns == 0, "%s: %d rows are not windows of %d" % (who, rows, ns)
+  return x, rows // int(ns), c, ld
+
+
+class BatchNormMaxPoolFunction(Function):
+  """rows_maxpool(bn_relu(x), ns) without the intermediate: (x [R ns, C], gamma, beta, running_mean, running_var, momentum,
+  eps, ns) -> (out [R, C], arg uint8 [R, C]) with training-mode statistics over all R ns rows (pcmi_bn_maxpool_fwd_train /
+  _bwd).  Keeps x, the pooled output and the argument rows for the backward pass."""
+
+  @staticmethod
+  def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, ns):
+    x, R, c, x_ld = _maxpool_rows(x, ns, "bn_maxpool")
+    dev = x.device
+    out = torch.empty((R, c), dtype=torch.float32, device=dev)
+    arg = torch.empty((R, c), dtype=torch.uint8, device=dev)
+    mean = torch.empty(c, dtype=torch.float32, device=dev)
+    invstd = torch.empty(c, dtype=torch.float32, device=dev)
+    ws, wsb = ws_args(lib.pcmi_bn_maxpool_workspace_bytes(R, int(ns), c), dev)
+    check(lib.pcmi_bn_maxpool_fwd_train(ptr(x), x_ld, R, int(ns), c, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+                                        float(momentum), float(eps), ptr(out), c, ptr(arg), ptr(mean), ptr(invstd), ws, wsb,
+                                        cur_stream(dev)))
+    ctx.save_for_backward(x, gamma, mean, invstd, out, arg)
+    ctx.mark_non_differentiable(arg)
+    ctx.ns = int(ns)
+    return out, arg
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout, garg=None):
+    x, gamma, mean, invstd, out, arg = ctx.saved_tensors
+    g = _c(gout)
+    n, c, x_ld = _rows(x)
+    R, dev = out.shape[0], x.device
+    dx = torch.empty((n, c), dtype=torch.float32, device=dev)
+    dgamma = torch.empty(c, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(c, dtype=torch.float32, device=dev)
+    ws, wsb = ws_args(lib.pcmi_bn_maxpool_workspace_bytes(R, ctx.ns, c), dev)
+    check(lib.pcmi_bn_maxpool_bwd(ptr(g), g.stride(0), ptr(x), x_ld, ptr(out), c, ptr(arg), R, ctx.ns, c, ptr(gamma), ptr(mean),
+                                  ptr(invstd), ptr(dx), c, ptr(dgamma), ptr(dbeta), ws, wsb, cur_stream(dev)))
+    return dx, dgamma, dbeta, None, None, None, None, None
+
+
+def batch_norm_maxpool_eval(x, gamma, beta, running_mean, running_var, eps, ns, want_arg=False):
+  """The eval form of BatchNormMaxPoolFunction: the same pass on the running estimates (pcmi_bn_maxpool_fwd_eval); no
+  gradient.  want_arg: also return the uint8 argument rows."""
+  x, R, c, x_ld = _maxpool_rows(x, ns, "bn_maxpool (eval)")
+  out = torch.empty((R, c), dtype=torch.float32, device=x.device)
+  arg = torch.empty((R, c), dtype=torch.uint8, device=x.device) if want_arg else None
+  check(lib.pcmi_bn_maxpool_fwd_eval(ptr(x), x_ld, R, int(ns), c, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+                                     float(eps), ptr(out), c, ptr(arg), cur_stream(x.device)))
+  return (out, arg) if want_arg else out
+
+
+class InterpRowsFunction(Function):
+  """three_interpolate + the concatenation of PointnetFPModule.forward as rows: (known [B m, C2], idx int32 [B, n, 3],
+  weight [B, n, 3], skip [B n, C1] or None, out_ld) -> [B n, out_ld] = interpolated features, skip features, zeros.
+  Differentiable in known and skip (the weights carry no gradient, as in the reference)."""
+
+  @staticmethod
+  def forward(ctx, known, idx, weight, skip, out_ld, validate=True):
+    require_cuda(known, "interp_rows")
+    known = _c(known if known.dtype == torch.float32 else known.float())
+    dev = known.device
+    idx, w = _i32c(idx, dev), _f32c(weight, "interp_rows")
+    assert known.dim() == 2 and idx.dim() == 3 and idx.shape[2] == 3 and w.shape == idx.shape and known.shape[0] % idx.shape[0] == 0, \
+        "interp_rows: known [B m, C2], idx / weight [B, n, 3]"
+    B, n, _ = idx.shape
+    m, C2 = known.shape[0] // B, known.shape[1]
+    C1 = 0
+    if skip is not None:
+      skip = _c(skip if skip.dtype == torch.float32 else skip.float())
+      assert skip.dim() == 2 and skip.shape[0] == B * n, "interp_rows: skip [B n, C1]"
+      C1 = skip.shape[1]
+    out = torch.empty((B * n, int(out_ld)), dtype=torch.float32, device=dev)
+    check(lib.pcmi_interp_rows_fwd(ptr(known), known.stride(0), ptr(idx), ptr(w), ptr(skip) if C1 else None, skip.stride(0) if C1 else 0,
+                                   B, m, n, C2, C1, ptr(out), int(out_ld), int(bool(validate)), cur_stream(dev)))
+    ctx.save_for_backward(idx, w)
+    ctx.shape, ctx.has_skip = (B, m, n, C2, C1), skip is not None
+    return out
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gout):
+    idx, w = ctx.saved_tensors
+    B, m, n, C2, C1 = ctx.shape
+    g = _c(gout)
+    dev = g.device
+    gknown = torch.empty((B * m, C2), dtype=torch.float32, device=dev)
+    ws, wsb = ws_args(lib.pcmi_interp_rows_bwd_workspace_bytes(B, m, n), dev)
+    check(lib.pcmi_interp_rows_bwd(ptr(g), g.stride(0), ptr(idx), ptr(w), B, m, n, C2, ptr(gknown), C2, ws, wsb, cur_stream(dev)))
+    return gknown, None, None, (g[:, C2:C2 + C1] if ctx.has_skip else None), None, None
+
+
 class VoteFunction(Function):
   """The tail of VotingModule.forward and the feature normalisation of votenet.py:120-121: (net [R, vf Wb], seed_xyz [R, 3],
   seed_feat [R, C], vote_factor) -> (vote_xyz [R vf, 3], vote_feat [R vf, C]); block v of a row of net holds C residual
