@@ -49,7 +49,14 @@ struct HostProfile {
     fprintf(stderr, "\n");
   }
 };
-static HostProfile g_prof_fwd, g_prof_bwd;
+static HostProfile g_prof_fwd;
+
+// A/B switches of the executor that default to on: unset, or anything that does not start with '0'.  Read per pass (the
+// parity tests run both forms in one process).
+static bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
+}
 
 // Host-side waits of the executor.  The wait in front of a forward pass for the previous pass's BatchNorm table is
 // what keeps the enqueueing thread one pass ahead of the GPU, i.e. the thread sits in it for about half of every
@@ -107,9 +114,17 @@ struct DevBuf {
   }
 };
 
+// What pcmi_net_create derives from the static program for op i (the per-network facts are members of pcmi_net).
+enum MapForm { kMapNone, kMapSame, kMapDown, kMapUp };
 struct OpPlan {
   int acc_in = 0;   // gradient w.r.t. `in` accumulates (a previous op already wrote that range)
   int acc_res = 0;  // gradient w.r.t. `in2` (BN residual) accumulates
+  int li = 0, lo = 0;       // level of `in` / `out`
+  int map_form = kMapNone;  // a convolution with kernel_size > 1: its kernel map stays on li, goes li -> li + 1, or is that of li - 1 -> li
+  // the residual branch of a block on the side stream (plan_branches)
+  int fork_at = -1;      // in front of this op, ops fork_at and fork_at + 1 are enqueued on the side stream
+  int join_before = -1;  // this op waits for the branch whose first op is join_before
+  char on_side = 0;      // enqueued by a fork, not in program order
 };
 
 struct PassState {
@@ -140,15 +155,13 @@ struct PassState {
   std::vector<size_t> tensor_off;  // byte offset of every root tensor in `act`
   std::vector<size_t> stat_off;    // per op: BN save_mean/save_invstd (2*C floats) or L2 norms
   std::vector<size_t> bits_off;    // per op: the ReLU pattern of a BN(+residual)+ReLU output, one bit per element (norm.hip: relu_bits); SIZE_MAX = none
-  std::vector<pcmi_kmap_t> maps;   // per op
-  std::vector<char> has_map;
+  std::vector<pcmi_kmap_t> maps;   // per op (those with a map_form in the plan)
   std::vector<int64_t> rows;       // per level
   std::vector<int64_t> split;      // per level: rows of the first segment (= rows when the pass has one segment)
   const float* in_feats = nullptr;
   int64_t in_ld = 0;
   float* out_feats = nullptr;
   int64_t out_ld = 0;
-  pcmi_coords_t* coords = nullptr;
   bool valid = false;
   // split-precision convolutions: the weights of every eligible layer, both orientations, packed by ONE launch at the
   // top of this pass's forward (x3_prepack) instead of one pack launch in front of every convolution.  Per PASS, not
@@ -186,6 +199,10 @@ struct pcmi_net {
   std::vector<pcmi_net_op_t> ops;
   std::vector<pcmi::OpPlan> plan;
   int input_tensor = -1, output_tensor = -1, n_levels = 0;
+  // static facts of the forward pass (plan_forward)
+  std::vector<int> roots;           // the tensors that own arena storage: no slice, not the network's input or output
+  int n_bn = 0, pack_bwd_at = 0;    // BatchNorm ops; the op behind which a training pass packs the backward-data weights
+  bool any_fork = false;            // some op has a fork_at
   std::vector<pcmi::PassState> passes;
   // side: the weight gradients of a backward pass (off the critical path: nothing downstream reads them) at the lowest
   // stream priority, with a workspace of their own
@@ -243,13 +260,8 @@ struct pcmi_net {
     timed_clear();
     pcmi::wgrad_group_destroy(wgroup);
     if (side) (void)hipStreamDestroy(side);
-    if (ev_main) (void)hipEventDestroy(ev_main);
-    if (ev_side) (void)hipEventDestroy(ev_side);
-    if (ev_bkt_side) (void)hipEventDestroy(ev_bkt_side);
-    if (ev_bkt_main) (void)hipEventDestroy(ev_bkt_main);
-    if (ev_fwd_fork) (void)hipEventDestroy(ev_fwd_fork);
-    if (ev_fwd_join) (void)hipEventDestroy(ev_fwd_join);
-    if (ev_fwd_pack) (void)hipEventDestroy(ev_fwd_pack);
+    for (hipEvent_t e : {ev_main, ev_side, ev_bkt_side, ev_bkt_main, ev_fwd_fork, ev_fwd_join, ev_fwd_pack})
+      if (e) (void)hipEventDestroy(e);
   }
 };
 
@@ -266,6 +278,33 @@ static int col_of(const pcmi_net& n, int t) {
     t = n.tensors[t].parent;
   }
   return c;
+}
+
+// Lays the root tensors out one behind the other at 256-byte granularity for a pass with `rows` per level (activations
+// in the forward pass, their gradients in the backward pass); returns the bytes they take.
+static size_t layout_roots(const pcmi_net& n, const std::vector<int64_t>& rows, std::vector<size_t>& off) {
+  off.assign(n.tensors.size(), 0);
+  size_t end = 0;
+  for (int t : n.roots) {
+    off[t] = end;
+    end += align_up((size_t)rows[n.tensors[t].level] * n.tensors[t].channels * sizeof(float), 256);
+  }
+  return end;
+}
+
+// call() as one timed call of op `op` on `st` (pcmi_net_time_ops): an event on either side of it and its kernel launches.
+// kind: 0 forward, 1 backward-data, 2 weight gradient.  A call that fails leaves its hit bit clear.
+template <class Call>
+static int timed(pcmi_net& n, int op, int kind, hipStream_t st, Call&& call) {
+  const int slot = n.timed_slot(op);
+  if (slot >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * slot + 2 * kind], st));
+  const long l0 = g_launches;
+  const int rc = call();
+  if (rc || slot < 0) return rc;
+  PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * slot + 2 * kind + 1], st));
+  n.timed_hit[slot] |= (char)(1 << kind);
+  n.timed_cnt[3 * slot + kind] = (int)(g_launches - l0);
+  return PCMI_OK;
 }
 
 struct View {
@@ -303,10 +342,9 @@ static size_t op_workspace(const pcmi_net_op_t& op, int64_t n_in, int64_t n_out,
 // class (its slice width changes) or the conv precision mode changes (the packs of the other term count would be read
 // otherwise: x3_find_prepacked keys on it as well).  PCMI_X3_PREPACK=0: every convolution packs its own weights in front of its launch
 // (as the C-ABI entry points do).  A training pass packs only the forward orientations here and owes the backward-data
-// ones (x3_bwd_owed: pcmi_net_forward packs them on the side stream); any other pass packs both.
+// ones (x3_bwd_owed: ForwardRun::step packs them on the side stream); any other pass packs both.
 static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream_t st, bool training) {
-  const char* pe = getenv("PCMI_X3_PREPACK");  // read per pass: the parity test runs both forms in one process
-  const bool enabled = !(pe && pe[0] == '0');
+  const bool enabled = env_on("PCMI_X3_PREPACK");
   ps.x3_current = false;
   ps.x3_bwd_pending = false;
   ps.x3_bwd_owed = false;
@@ -406,7 +444,7 @@ static int x3_prepack(pcmi_net& n, PassState& ps, const float* params, hipStream
   const int rc = x3_pack_many(reinterpret_cast<const X3PackJob*>(ps.x3_jobs_dev.p), ps.x3_n_jobs, upto, st);
   if (rc) return rc;
   // (the forward pass still OWES the backward orientations; x3_bwd_pending -- "an event to wait for exists" -- is set only
-  //  once they have been enqueued and the event recorded, pcmi_net_forward: a pass that fails in between must not leave a
+  //  once they have been enqueued and the event recorded, ForwardRun::step: a pass that fails in between must not leave a
   //  stale event to be waited for as if the packs were those of its weights -- ADVICE round 5)
   ps.x3_bwd_owed = training && ps.x3_items > ps.x3_items_fwd;
   ps.x3_current = true;
@@ -435,13 +473,6 @@ struct X3TableScope {
 // two-chain form that ran the backward passes of the two clouds next to each other -- bit-identical, 111 against 174
 // pairs/s, a queueing effect of five concurrently active streams; the pair as ONE two-segment pass replaced it and the
 // code is gone.)
-struct BackwardJob {
-  int pass = 0;
-  const float* d_out = nullptr;
-  int64_t d_ld = 0;
-  hipStream_t st = nullptr;
-};
-
 // Test hooks of the bucket hand-over (tests/test_gpu_bucket_sync.py; read per call, never set in production):
 //   PCMI_DEBUG_SIDE_DELAY_US=<n>        the weight-gradient stream starts every backward pass n microseconds late (a spin
 //                                       kernel at its head), so that it trails the chain by far more than it ever does
@@ -481,7 +512,10 @@ static int ensure_streams(pcmi_net& n) {
 // One pass's backward: op by op in reverse, the chain on `st`, the weight gradients on the side stream.
 struct BackwardRun {
   pcmi_net& n;
-  BackwardJob job;
+  int pass;
+  const float* d_out;
+  int64_t d_ld;
+  hipStream_t st;
   const float* params;
   float* grads;
   const int64_t* bucket_lo_host;
@@ -489,16 +523,12 @@ struct BackwardRun {
   pcmi_ready_fn ready;
   void* ready_ctx;
   // set by begin()
-  hipStream_t st = nullptr, wst = nullptr;  // wst: the stream of the weight gradient being enqueued (step)
+  hipStream_t wst = nullptr;  // the stream of the weight gradient being enqueued (step)
   PassState* ps = nullptr;
   DevBuf* wws = nullptr;
   bool pending = false, used = false;  // weight gradients on the side stream: not yet joined / since the pass began
   float* scratch_g = nullptr;
   std::vector<int> bucket_last;
-
-  BackwardRun(pcmi_net& net, const BackwardJob& j, const float* prm, float* g, const int64_t* blo, int nb, pcmi_ready_fn r,
-              void* rc)
-      : n(net), job(j), params(prm), grads(g), bucket_lo_host(blo), n_buckets(nb), ready(r), ready_ctx(rc) {}
 
   int join_side() {  // `st` continues only after the weight gradients enqueued so far
     if (!pending) return PCMI_OK;
@@ -536,21 +566,13 @@ struct BackwardRun {
   }
 
   int begin() {
-    st = job.st;
-    ps = &n.passes[job.pass];
-    const int n_ops = (int)n.ops.size(), n_t = (int)n.tensors.size();
+    ps = &n.passes[pass];
+    const int n_ops = (int)n.ops.size();
     if (n_buckets < 0 || !bucket_lo_host) n_buckets = 0;
-    ps->grad_off.assign(n_t, 0);
-    size_t off = 0;
-    int max_c = 4;
-    for (int t = 0; t < n_t; ++t) {
-      max_c = std::max(max_c, n.tensors[t].channels);
-      if (n.tensors[t].parent >= 0 || t == n.input_tensor || t == n.output_tensor) continue;
-      ps->grad_off[t] = off;
-      off += align_up((size_t)ps->rows[n.tensors[t].level] * n.tensors[t].channels * sizeof(float), 256);
-    }
-    int rc = ps->grad.reserve(off, st);
+    int rc = ps->grad.reserve(layout_roots(n, ps->rows, ps->grad_off), st);
     if (rc) return rc;
+    int max_c = 4;
+    for (const pcmi_net_tensor_t& T : n.tensors) max_c = std::max(max_c, T.channels);
     // the BatchNorm parameter-gradient sums ([2 segments][dbeta, dgamma]): every BatchNorm reads and writes them on the
     // chain's stream inside its own backward call, so one block serves them all in turn
     rc = ps->small.reserve((size_t)4 * max_c * sizeof(float) + 256, st);
@@ -586,16 +608,14 @@ struct BackwardRun {
   }
 
   int step(int i) {  // differentiate op i (called for i = n_ops - 1 ... 0)
-    const float* d_out = job.d_out;
-    const int64_t d_ld = job.d_ld;
     const auto& op = n.ops[i];
     const OpPlan& pl = n.plan[i];
     const View x = act_view(n, *ps, op.in), y = act_view(n, *ps, op.out);
     const View dy = grad_view(n, *ps, op.out, d_out, d_ld);
-    const int64_t n_in = ps->rows[n.tensors[op.in].level], n_out = ps->rows[n.tensors[op.out].level];
+    const int64_t n_in = ps->rows[pl.li], n_out = ps->rows[pl.lo];
     int rc = PCMI_OK;
     if (op.type == PCMI_OP_CONV) {
-      const pcmi_kmap_t* map = ps->has_map[i] ? &ps->maps[i] : nullptr;
+      const pcmi_kmap_t* map = pl.map_form != kMapNone ? &ps->maps[i] : nullptr;
       // dy is complete at this point of `st` (all its consumers were differentiated before)
       // (weight gradients of the largest layers ON the chain instead of the side stream -- they cannot share a CU with the
       //  chain's kernels anyway, two of their workgroups fill register file and LDS -- were measured: 16.47 against 15.85 ms
@@ -626,35 +646,20 @@ struct BackwardRun {
         PCMI_HIP_CHECK(hipStreamWaitEvent(wst, n.ev_main, 0));
         pending = used = true;
       }
-      const int tw = n.timed_slot(i);
-      if (tw >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tw + 4], wst));
-      const long lw0 = g_launches;
-      rc = spconv_backward_weight(x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, map, op.transpose, grads + op.w_off,
-                                  op.has_bias ? grads + op.b_off : nullptr, 1, wws->p, wws->cap, wst);
+      rc = timed(n, i, 2, wst, [&] {
+        return spconv_backward_weight(x.p, x.ld, n_in, op.cin, dy.p, dy.ld, n_out, op.cout, map, op.transpose, grads + op.w_off,
+                                      op.has_bias ? grads + op.b_off : nullptr, 1, wws->p, wws->cap, wst);
+      });
       if (rc) return rc;
-      if (tw >= 0) {
-        PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tw + 5], wst));
-        n.timed_hit[tw] |= 4;
-        n.timed_cnt[3 * tw + 2] = (int)(g_launches - lw0);
-      }
       }  // !grouped
       if (op.in != n.input_tensor) {
         const View dx = grad_view(n, *ps, op.in, d_out, d_ld);
-        const int tq = n.timed_slot(i);
-        if (tq >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tq + 2], st));
-        const long lb0 = g_launches;
-        rc = spconv_backward_data(dy.p, dy.ld, n_out, op.cout, params + op.w_off, op.cin, map, op.transpose, dx.p, dx.ld,
-                                  n_in, pl.acc_in, ps->ws.p, ps->ws.cap, st);
-        if (tq >= 0 && !rc) {
-          PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tq + 3], st));
-          n.timed_hit[tq] |= 2;
-          n.timed_cnt[3 * tq + 1] = (int)(g_launches - lb0);
-        }
+        rc = timed(n, i, 1, st, [&] {
+          return spconv_backward_data(dy.p, dy.ld, n_out, op.cout, params + op.w_off, op.cin, map, op.transpose, dx.p, dx.ld, n_in,
+                                      pl.acc_in, ps->ws.p, ps->ws.cap, st);
+        });
       }
     } else if (op.type == PCMI_OP_BN) {
-      const int tb = n.timed_slot(i);
-      if (tb >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tb + 2], st));
-      const long lb0 = g_launches;
       const View dx = grad_view(n, *ps, op.in, d_out, d_ld);
       View dr = {nullptr, 0};
       if (op.in2 >= 0) dr = grad_view(n, *ps, op.in2, d_out, d_ld);
@@ -669,24 +674,13 @@ struct BackwardRun {
       a.save_mean = stats0; a.save_invstd = stats0 + op.cout; a.stat_stride = 3 * op.cout;
       a.dx = dx.p; a.dx_ld = dx.ld; a.dres = dr.p; a.dres_ld = dr.ld; a.dres_accumulate = pl.acc_res;
       a.sums = scratch_g; a.acc_dgamma = grads + op.w_off; a.acc_dbeta = grads + op.b_off; a.relu_bits = rbits;
-      rc = bn_backward(a, ps->ws.p, ps->ws.cap, st);
-      if (tb >= 0 && !rc) {
-        PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tb + 3], st));
-        n.timed_hit[tb] |= 2;
-        n.timed_cnt[3 * tb + 1] = (int)(g_launches - lb0);
-      }
+      rc = timed(n, i, 1, st, [&] { return bn_backward(a, ps->ws.p, ps->ws.cap, st); });
     } else {
       const View dx = grad_view(n, *ps, op.in, d_out, d_ld);
-      const int tl = n.timed_slot(i);
-      if (tl >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tl + 2], st));
-      const long ll0 = g_launches;
-      rc = pcmi_l2norm_bwd(dy.p, dy.ld, y.p, y.ld, (const float*)(ps->act.p + ps->stat_off[i]), n_in, op.cout, dx.p, dx.ld,
-                           (pcmi_stream_t)st);
-      if (tl >= 0 && !rc) {
-        PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tl + 3], st));
-        n.timed_hit[tl] |= 2;
-        n.timed_cnt[3 * tl + 1] = (int)(g_launches - ll0);
-      }
+      rc = timed(n, i, 1, st, [&] {
+        return pcmi_l2norm_bwd(dy.p, dy.ld, y.p, y.ld, (const float*)(ps->act.p + ps->stat_off[i]), n_in, op.cout, dx.p, dx.ld,
+                               (pcmi_stream_t)st);
+      });
     }
     if (rc) return rc;
     // A bucket is final once this op's kernels have run -- on `st` AND, for the weight gradients, on the side stream.
@@ -719,14 +713,312 @@ struct BackwardRun {
   }
 };
 
-static int run_backward(pcmi_net& n, const BackwardJob& job, const float* params, float* grads,
-                        const int64_t* bucket_lo_host, int n_buckets, pcmi_ready_fn ready, void* ready_ctx) {
-  const X3TableScope x3_scope(n.passes[job.pass], params);
-  BackwardRun r(n, job, params, grads, bucket_lo_host, n_buckets, ready, ready_ctx);
-  int rc = r.begin();
-  for (int i = (int)n.ops.size() - 1; i >= 0 && !rc; --i) rc = r.step(i);
-  return rc ? rc : r.end();
+// ---- forward ------------------------------------------------------------------------------------------
+// What the forward pass needs of the program alone (pcmi_net_create): levels and kernel-map form per op -- a malformed
+// program is refused here, before any pass --, where the backward-data weights are packed, the tensors that own storage
+// and the residual branches.
+static int plan_forward(pcmi_net& n) {
+  static const char* const kLevels[] = {"", "stride-1 conv across levels", "strided conv must go one level down",
+                                        "transposed conv must go one level up"};
+  const int n_ops = (int)n.ops.size();
+  n.pack_bwd_at = -1;
+  for (int i = 0; i < n_ops; ++i) {
+    const auto& op = n.ops[i];
+    OpPlan& pl = n.plan[i];
+    pl.li = n.tensors[op.in].level;
+    pl.lo = n.tensors[op.out].level;
+    if (op.type == PCMI_OP_CONV && op.kernel_size > 1) {
+      pl.map_form = op.transpose ? kMapUp : (op.stride == 1 ? kMapSame : kMapDown);
+      PCMI_REQUIRE(pl.lo == pl.li + (pl.map_form == kMapDown) - (pl.map_form == kMapUp), PCMI_ERR_INVALID, "net: op %d: %s", i,
+                   kLevels[pl.map_form]);
+    }
+    n.n_bn += op.type == PCMI_OP_BN;
+    if (pl.lo >= 2 && n.pack_bwd_at < 0) n.pack_bwd_at = i;
+  }
+  if (n.pack_bwd_at < 0) n.pack_bwd_at = n_ops - 1;
+  for (int t = 0; t < (int)n.tensors.size(); ++t)
+    if (n.tensors[t].parent < 0 && t != n.input_tensor && t != n.output_tensor) n.roots.push_back(t);
+  // ---- the residual branch of a block beside its main path (round 6) ------------------------------------------------------
+  // A BasicBlock whose channel count changes computes its residual with a 1x1 convolution + BatchNorm of the block's INPUT
+  // (pc/model/resnet.py: downsample); the traced program lists the two behind conv1 / bn1 / conv2 although they depend on
+  // nothing the main path computes.  They go to the side stream -- idle during a forward pass but for the weight packs -- as
+  // soon as the block's input is complete, with the side workspace, and the BatchNorm that adds the residual waits for them.
+  // Same kernels on the same operands: bit-identical results (tests/test_gpu_timing.py).  PCMI_FWD_BRANCH=0: in program order.
+  for (int i = 3; i + 2 < n_ops; ++i) {
+    const auto &c = n.ops[i], &b1 = n.ops[i + 1], &b2 = n.ops[i + 2];
+    if (c.type != PCMI_OP_CONV || c.kernel_size != 1 || b1.type != PCMI_OP_BN || b1.in != c.out || b1.relu || b1.in2 >= 0 ||
+        b2.type != PCMI_OP_BN || b2.in2 != b1.out)
+      continue;
+    int s0 = -1;  // the first of the three ops in front that reads the block's input: the branch forks in front of it
+    for (int q = i - 3; q < i; ++q)
+      if (n.ops[q].in == c.in && !n.plan[q].on_side) {
+        s0 = q;
+        break;
+      }
+    if (s0 < 0 || n.plan[s0].fork_at >= 0) continue;  // (a fork point is used once)
+    n.plan[s0].fork_at = i;
+    n.plan[i].on_side = n.plan[i + 1].on_side = 1;
+    n.plan[i + 2].join_before = i;
+    n.any_fork = true;
+  }
+  return PCMI_OK;
 }
+
+// One pass's forward: begin() sizes the pass, lays its arena out and packs the weights, step(i) enqueues op i
+// (i = 0 ... n_ops - 1) where the static plan puts it, end() hands the BatchNorm running estimates on.
+struct ForwardRun {
+  pcmi_net& n;
+  PassState& ps;
+  pcmi_coords_t* coords;
+  const float *in_feats, *params;
+  float* out_feats;
+  int64_t in_ld, out_ld, n_rows;
+  hipStream_t st;
+  bool train, defer;
+  // set by begin()
+  bool two_seg = false;     // a two-segment pass updates the running estimates through the table as well (segment 0, then 1)
+  bool pack_joined = true;  // `st` has waited for the forward weight packs (or they were packed on `st`)
+  bool branch = false;      // the residual branches of the plan go to the side stream
+  int pack_bwd_at = -1;     // the op behind which this pass packs the backward-data weights, if it owes them
+
+  int begin() {
+    const int n_ops = (int)n.ops.size();
+    const pcmi_stream_t stream = (pcmi_stream_t)st;
+    g_prof_fwd.start();
+    // the coordinate plan may have been enqueued on another stream without a host synchronisation behind it
+    int rc = coords_wait_plan(coords, st);
+    if (rc) return rc;
+    // ---- level sizes (cache hits once the coordinate plan exists) ------------------------------------
+    std::vector<int> keys(n.n_levels, 0);
+    ps.rows.assign(n.n_levels, 0);
+    int64_t n0 = 0;
+    rc = pcmi_coords_size(coords, 0, &n0, nullptr);
+    if (rc) return rc;
+    PCMI_REQUIRE(n0 == n_rows, PCMI_ERR_INVALID, "net_forward: %lld feature rows but %lld coordinates", (long long)n_rows,
+                 (long long)n0);
+    ps.rows[0] = n0;
+    for (int l = 1; l < n.n_levels; ++l) {
+      rc = pcmi_coords_stride(coords, keys[l - 1], 2, &keys[l], &ps.rows[l], stream);
+      if (rc) return rc;
+    }
+    // two-segment batch (pcmi_coords_set_split): BatchNorm normalises every segment with its own statistics, as two
+    // forward calls of the reference would
+    ps.split.assign(n.n_levels, 0);
+    for (int l = 0; l < n.n_levels; ++l) {
+      int64_t sp = -1;
+      rc = pcmi_coords_split(coords, keys[l], &sp);
+      if (rc) return rc;
+      ps.split[l] = (sp <= 0 || sp >= ps.rows[l]) ? ps.rows[l] : sp;
+      two_seg |= train && ps.split[l] < ps.rows[l];
+    }
+    g_prof_fwd.lap(0);
+    // ---- maps, arena layout, workspace --------------------------------------------------------------
+    ps.maps.resize(n_ops);
+    size_t ws_need = 0;
+    for (int i = 0; i < n_ops; ++i) {
+      const auto& op = n.ops[i];
+      const OpPlan& pl = n.plan[i];
+      int64_t M = ps.rows[pl.li];
+      if (pl.map_form != kMapNone) {  // (a transposed convolution reads the map of the strided one it undoes)
+        const bool up = pl.map_form == kMapUp;
+        rc = kmap_get_nosync(coords, keys[up ? pl.lo : pl.li], keys[up ? pl.li : pl.lo], op.kernel_size, op.stride, op.region,
+                             &ps.maps[i], stream);
+        if (rc) return rc;
+        M = kmap_pairs_bound(ps.maps[i]);
+      }
+      ws_need = std::max(ws_need, op_workspace(op, ps.rows[pl.li], ps.rows[pl.lo], M));
+    }
+    g_prof_fwd.lap(1);
+    size_t off = layout_roots(n, ps.rows, ps.tensor_off);
+    ps.stat_off.assign(n_ops, 0);
+    ps.bits_off.assign(n_ops, SIZE_MAX);
+    // PCMI_BN_RELU_BITS=0: the backward BatchNorm kernels read the ReLU pattern from the fp32 output again (A/B)
+    const bool relu_bits_on = train && env_on("PCMI_BN_RELU_BITS");
+    for (int i = 0; i < n_ops; ++i) {
+      const auto& op = n.ops[i];
+      const int64_t n_in = ps.rows[n.plan[i].li];
+      ps.stat_off[i] = off;
+      if (op.type == PCMI_OP_BN) off += align_up((size_t)2 * 3 * op.cout * sizeof(float), 256);  // per segment: mean, invstd, unbiased var
+      if (op.type == PCMI_OP_L2NORM) off += align_up((size_t)n_in * sizeof(float), 256);
+      if (op.type == PCMI_OP_BN && op.relu && op.cout % 32 == 0 && relu_bits_on) {
+        ps.bits_off[i] = off;
+        off += align_up((size_t)n_in * (op.cout / 32) * sizeof(uint32_t), 256);
+      }
+    }
+    rc = ps.act.reserve(off, st);
+    if (rc) return rc;
+    rc = ps.ws.reserve(ws_need + 256, st);
+    if (rc) return rc;
+    ps.upd_n = 0;
+    if (defer || two_seg) {
+      if (n.n_bn > ps.upd_cap) {
+        PCMI_HIP_CHECK(hipDeviceSynchronize());
+        if (ps.upd_host) PCMI_HIP_CHECK(hipHostFree(ps.upd_host));
+        if (ps.upd_dev) PCMI_HIP_CHECK(hipFree(ps.upd_dev));
+        ps.upd_host = ps.upd_dev = nullptr;
+        PCMI_HIP_CHECK(hipHostMalloc((void**)&ps.upd_host, sizeof(BnRunningUpdate) * n.n_bn, hipHostMallocDefault));
+        PCMI_HIP_CHECK(hipMalloc((void**)&ps.upd_dev, sizeof(BnRunningUpdate) * n.n_bn));
+        ps.upd_cap = n.n_bn;
+      }
+      // (this wait is also what keeps the enqueueing thread ONE pass ahead of the GPU: host_wait_event sleeps in it)
+      if (!ps.upd_copied) PCMI_HIP_CHECK(hipEventCreateWithFlags(&ps.upd_copied, host_wait_event_flags()));
+      rc = host_wait_event(ps.upd_copied);  // the previous table has left the pinned buffer
+      if (rc) return rc;
+    }
+    ps.in_feats = in_feats;
+    ps.in_ld = in_ld;
+    ps.out_feats = out_feats;
+    ps.out_ld = out_ld;
+    if (ps.x3_bwd_pending && ps.x3_bwd_packed) {
+      // a training forward of this pass that was never differentiated: its side-stream pack may still be reading the job
+      // table / writing the packs this pass is about to rebuild
+      PCMI_HIP_CHECK(hipStreamWaitEvent(st, ps.x3_bwd_packed, 0));
+      ps.x3_bwd_pending = false;
+    }
+    // PCMI_X3_PACK_SIDE (round 6, default on for training passes): the forward orientations are packed on the side stream, behind
+    // everything enqueued so far, and the pass waits for them in front of the first convolution that reads a pack -- the stem and
+    // the 32-channel layers of the first two levels (~0.45 ms) do not.  (A first side-stream pack, joined in front of the first
+    // convolution that needs it, was measured at 237.7 against 238.3 pairs/s in line -- profiles/r03c_bench_ab.txt -- and removed;
+    // round 5 measured +0.3 %, inside the spread, with a join in front of the first convolution of ANY kind; round 6 brought it
+    // back in this form, beside the residual branches on the same stream.)  Otherwise the pass packs on its own stream.
+    if (train && env_on("PCMI_X3_PACK_SIDE")) {
+      rc = ensure_streams(n);
+      if (rc) return rc;
+      if (!n.ev_fwd_fork) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_fork, hipEventDisableTiming));
+      if (!n.ev_fwd_pack) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_pack, hipEventDisableTiming));
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_fork, st));
+      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_fwd_fork, 0));
+      rc = x3_prepack(n, ps, params, n.side, train);
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_pack, n.side));
+      pack_joined = false;
+    } else {
+      rc = x3_prepack(n, ps, params, st, train);
+    }
+    if (rc) return rc;
+    // where the backward-data orientations are packed: behind the first op of the third level (the pass is in its
+    // latency-bound coarse phase from there on and the side stream is idle during a forward pass) -- or behind the last op
+    if (ps.x3_bwd_owed) {
+      pack_bwd_at = n.pack_bwd_at;
+      rc = ensure_streams(n);
+      if (rc) return rc;
+      if (!ps.x3_bwd_packed) PCMI_HIP_CHECK(hipEventCreateWithFlags(&ps.x3_bwd_packed, hipEventDisableTiming));
+    }
+    g_prof_fwd.lap(2);
+    if (!n.timed_ops.empty()) {  // the next event set of the ring (pcmi_net_time_ops); its old records are dropped
+      ++n.timed_cur;
+      const size_t per = n.timed_ops.size(), base = (size_t)(n.timed_cur % n.timed_sets) * per;
+      for (size_t q = 0; q < per; ++q) n.timed_hit[base + q] = 0;
+      if (n.timed_keep_groups) n.timed_group_n[n.timed_cur % n.timed_sets] = 0;
+    }
+    branch = n.any_fork && env_on("PCMI_FWD_BRANCH");
+    if (branch) {
+      rc = ensure_streams(n);
+      if (rc) return rc;
+      rc = n.ws_side.reserve(ps.ws.cap, n.side);
+      if (rc) return rc;
+      if (!n.ev_fwd_fork) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_fork, hipEventDisableTiming));
+      if (!n.ev_fwd_join) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_join, hipEventDisableTiming));
+    }
+    return PCMI_OK;
+  }
+
+  int enqueue(int i, hipStream_t sq, DevBuf& w) {  // op i on `sq` with workspace `w`
+    return timed(n, i, 0, sq, [&] { return launch(i, sq, w); });
+  }
+  int launch(int i, hipStream_t sq, DevBuf& w) {
+    const auto& op = n.ops[i];
+    const View x = act_view(n, ps, op.in), y = act_view(n, ps, op.out);
+    const int64_t n_in = ps.rows[n.plan[i].li], n_out = ps.rows[n.plan[i].lo];
+    int rc = PCMI_OK;
+    if (op.type == PCMI_OP_CONV) {
+      rc = spconv_forward(x.p, x.ld, n_in, op.cin, params + op.w_off, op.cout, n.plan[i].map_form != kMapNone ? &ps.maps[i] : nullptr,
+                          op.transpose, op.has_bias ? params + op.b_off : nullptr, y.p, y.ld, n_out, 0, w.p, w.cap, sq);
+    } else if (op.type == PCMI_OP_BN) {
+      View r = {nullptr, 0};
+      if (op.in2 >= 0) r = act_view(n, ps, op.in2);
+      float* stats0 = (float*)(ps.act.p + ps.stat_off[i]);
+      uint32_t* rbits = ps.bits_off[i] != SIZE_MAX ? (uint32_t*)(ps.act.p + ps.bits_off[i]) : nullptr;
+      if (train) {
+        const int64_t sp = ps.split[n.plan[i].li];
+        // two segments: both in one statistics launch + one apply launch.  The running estimates go through the table
+        // then (segment 0, then segment 1), as they do when this pass defers them or another level has two segments.
+        const bool two = sp < n_in, tab = two || defer || two_seg;
+        float* stats1 = stats0 + 3 * op.cout;
+        BnTrainForward a;
+        memset(&a, 0, sizeof(a));
+        a.x = x.p; a.x_ld = x.ld; a.residual = r.p; a.res_ld = r.ld; a.y = y.p; a.y_ld = y.ld;
+        a.n = n_in; a.split = sp; a.c = op.cout; a.gamma = params + op.w_off; a.beta = params + op.b_off;
+        a.eps = op.eps; a.relu = op.relu;
+        a.save_mean = stats0; a.save_invstd = stats0 + op.cout; a.save_unbiased = stats0 + 2 * op.cout;
+        a.stat_stride = 3 * op.cout;
+        a.running_mean = tab ? nullptr : op.running_mean; a.running_var = tab ? nullptr : op.running_var;
+        a.momentum = op.momentum; a.relu_bits = rbits;
+        rc = bn_forward_train(a, w.p, w.cap, sq);
+        if (tab && op.running_mean)
+          ps.upd_host[ps.upd_n++] = {op.running_mean, op.running_var, stats0, stats0 + 2 * op.cout, op.cout, op.momentum,
+                                     two ? stats1 : nullptr, two ? stats1 + 2 * op.cout : nullptr};
+      } else {
+        rc = pcmi_bn_fwd_eval(x.p, x.ld, n_in, op.cout, params + op.w_off, params + op.b_off, op.running_mean,
+                              op.running_var, op.eps, r.p, r.ld, op.relu, y.p, y.ld, (void*)sq);
+      }
+    } else {
+      rc = pcmi_l2norm_fwd(x.p, x.ld, n_in, op.cout, y.p, y.ld, (float*)(ps.act.p + ps.stat_off[i]), (void*)sq);
+    }
+    return rc;
+  }
+
+  int step(int i) {
+    const auto& op = n.ops[i];
+    const OpPlan& pl = n.plan[i];
+    const int fork = branch ? pl.fork_at : -1;
+    int rc = PCMI_OK;
+    if (!pack_joined && (i >= ps.x3_first_op || fork >= 0)) {  // (a forked 1x1 layer may pack for itself on the side stream: keep it simple)
+      PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_fwd_pack, 0));
+      pack_joined = true;
+    }
+    if (fork >= 0) {  // everything enqueued so far is the branch's input (and more): the branch starts behind it
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_fork, st));
+      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_fwd_fork, 0));
+      for (int q = fork; q <= fork + 1; ++q) {
+        rc = enqueue(q, n.side, n.ws_side);
+        if (rc) return rc;
+      }
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_join, n.side));
+    }
+    if (branch && pl.join_before >= 0) PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_fwd_join, 0));
+    if (!(branch && pl.on_side)) {
+      rc = enqueue(i, st, ps.ws);
+      if (rc) return rc;
+    }
+    if (i == pack_bwd_at) {  // the side stream starts behind this point of the pass (and behind the job table's upload)
+      PCMI_HIP_CHECK(hipEventRecord(n.ev_main, st));
+      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_main, 0));
+      rc = x3_pack_many(reinterpret_cast<const X3PackJob*>(ps.x3_jobs_dev.p), ps.x3_n_jobs, ps.x3_items, n.side, ps.x3_items_fwd);
+      if (rc) return rc;
+      PCMI_HIP_CHECK(hipEventRecord(ps.x3_bwd_packed, n.side));
+      ps.x3_bwd_owed = false;
+      ps.x3_bwd_pending = true;
+    }
+    g_prof_fwd.lap(op.type == PCMI_OP_CONV ? 3 : (op.type == PCMI_OP_BN ? 4 : 5));
+    return PCMI_OK;
+  }
+
+  int end() {
+    if ((defer || two_seg) && ps.upd_n > 0) {
+      PCMI_HIP_CHECK(hipMemcpyAsync(ps.upd_dev, ps.upd_host, sizeof(BnRunningUpdate) * ps.upd_n, hipMemcpyHostToDevice, st));
+      PCMI_HIP_CHECK(hipEventRecord(ps.upd_copied, st));
+      if (!defer) {  // two-segment pass without a deferral request: apply now, in layer order
+        const int rc = bn_running_update(ps.upd_dev, ps.upd_n, st);
+        if (rc) return rc;
+        ps.upd_n = 0;
+      }
+    }
+    g_prof_fwd.lap(6);
+    static const char* const kFwdNames[] = {"levels", "maps", "layout+reserve", "conv", "bn", "l2norm", "tail"};
+    g_prof_fwd.report("net_forward", kFwdNames, 7);
+    return PCMI_OK;
+  }
+};
 
 }  // namespace pcmi
 
@@ -803,6 +1095,10 @@ int pcmi_net_create(const pcmi_net_tensor_t* tensors, int n_tensors, const pcmi_
     }
   }
   n->param_extent = (n->param_extent + 3) / 4 * 4;
+  if (const int rc = plan_forward(*n)) {
+    delete n;
+    return rc;
+  }
   *out = n;
   return PCMI_OK;
 }
@@ -845,320 +1141,20 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
   PCMI_REQUIRE(net && coords && in_feats && params && out_feats, PCMI_ERR_INVALID, "net_forward: null argument");
   PCMI_REQUIRE(pass >= 0 && pass < (int)net->passes.size(), PCMI_ERR_INVALID, "net_forward: bad pass %d", pass);
   const ConvPrecisionScope precision(net->conv_precision);  // the net's mode for this pass, the thread's afterwards
-  hipStream_t st = as_stream(stream);
-  pcmi_net& n = *net;
-  PassState& ps = n.passes[pass];
+  const X3TableScope x3_scope;  // the table of packed weights is this thread's only until the pass has been enqueued
+  PassState& ps = net->passes[pass];
   ps.valid = false;
-  const int n_ops = (int)n.ops.size(), n_t = (int)n.tensors.size();
-  g_prof_fwd.start();
-  // the coordinate plan may have been enqueued on another stream without a host synchronisation behind it
-  int rc = coords_wait_plan(coords, st);
-  if (rc) return rc;
-  // ---- level sizes (cache hits once the coordinate plan exists) ------------------------------------
-  std::vector<int> keys(n.n_levels, 0);
-  ps.rows.assign(n.n_levels, 0);
-  int64_t n0 = 0;
-  rc = pcmi_coords_size(coords, 0, &n0, nullptr);
-  if (rc) return rc;
-  PCMI_REQUIRE(n0 == n_rows, PCMI_ERR_INVALID, "net_forward: %lld feature rows but %lld coordinates", (long long)n_rows,
-               (long long)n0);
-  ps.rows[0] = n0;
-  for (int l = 1; l < n.n_levels; ++l) {
-    rc = pcmi_coords_stride(coords, keys[l - 1], 2, &keys[l], &ps.rows[l], stream);
-    if (rc) return rc;
-  }
-  // two-segment batch (pcmi_coords_set_split): BatchNorm normalises every segment with its own statistics, as two
-  // forward calls of the reference would
-  ps.split.assign(n.n_levels, 0);
-  for (int l = 0; l < n.n_levels; ++l) {
-    int64_t sp = -1;
-    rc = pcmi_coords_split(coords, keys[l], &sp);
-    if (rc) return rc;
-    ps.split[l] = (sp <= 0 || sp >= ps.rows[l]) ? ps.rows[l] : sp;
-  }
-  g_prof_fwd.lap(0);
-  // ---- maps, arena layout, workspace --------------------------------------------------------------
-  ps.maps.resize(n_ops);
-  ps.has_map.assign(n_ops, 0);
-  size_t ws_need = 0;
-  for (int i = 0; i < n_ops; ++i) {
-    const auto& op = n.ops[i];
-    const int li = n.tensors[op.in].level, lo = n.tensors[op.out].level;
-    int64_t M = ps.rows[li];
-    if (op.type == PCMI_OP_CONV && op.kernel_size > 1) {
-      if (!op.transpose && op.stride == 1) {
-        PCMI_REQUIRE(li == lo, PCMI_ERR_INVALID, "net: op %d: stride-1 conv across levels", i);
-        rc = kmap_get_nosync(coords, keys[li], keys[li], op.kernel_size, 1, op.region, &ps.maps[i], stream);
-      } else if (!op.transpose) {
-        PCMI_REQUIRE(lo == li + 1, PCMI_ERR_INVALID, "net: op %d: strided conv must go one level down", i);
-        rc = kmap_get_nosync(coords, keys[li], keys[lo], op.kernel_size, op.stride, op.region, &ps.maps[i], stream);
-      } else {
-        PCMI_REQUIRE(lo == li - 1, PCMI_ERR_INVALID, "net: op %d: transposed conv must go one level up", i);
-        rc = kmap_get_nosync(coords, keys[lo], keys[li], op.kernel_size, op.stride, op.region, &ps.maps[i], stream);
-      }
-      if (rc) return rc;
-      ps.has_map[i] = 1;
-      M = kmap_pairs_bound(ps.maps[i]);
-    }
-    ws_need = std::max(ws_need, op_workspace(op, ps.rows[li], ps.rows[lo], M));
-  }
-  g_prof_fwd.lap(1);
-  ps.tensor_off.assign(n_t, 0);
-  size_t off = 0;
-  for (int t = 0; t < n_t; ++t) {
-    if (n.tensors[t].parent >= 0 || t == n.input_tensor || t == n.output_tensor) continue;
-    ps.tensor_off[t] = off;
-    off += align_up((size_t)ps.rows[n.tensors[t].level] * n.tensors[t].channels * sizeof(float), 256);
-  }
-  ps.stat_off.assign(n_ops, 0);
-  ps.bits_off.assign(n_ops, SIZE_MAX);
-  // PCMI_BN_RELU_BITS=0: the backward BatchNorm kernels read the ReLU pattern from the fp32 output again (A/B; read per pass)
-  const bool relu_bits_on = [] {
-    const char* e = getenv("PCMI_BN_RELU_BITS");
-    return !(e && e[0] == '0');
-  }();
-  for (int i = 0; i < n_ops; ++i) {
-    const auto& op = n.ops[i];
-    ps.stat_off[i] = off;
-    if (op.type == PCMI_OP_BN) off += align_up((size_t)2 * 3 * op.cout * sizeof(float), 256);  // per segment: mean, invstd, unbiased var
-    if (op.type == PCMI_OP_L2NORM) off += align_up((size_t)ps.rows[n.tensors[op.in].level] * sizeof(float), 256);
-    if (op.type == PCMI_OP_BN && op.relu && op.cout % 32 == 0 && relu_bits_on && (training & 1)) {
-      ps.bits_off[i] = off;
-      off += align_up((size_t)ps.rows[n.tensors[op.in].level] * (op.cout / 32) * sizeof(uint32_t), 256);
-    }
-  }
-  rc = ps.act.reserve(off, st);
-  if (rc) return rc;
-  rc = ps.ws.reserve(ws_need + 256, st);
-  if (rc) return rc;
   const bool train = (training & 1) != 0, defer = train && (training & PCMI_NET_DEFER_RUNNING_STATS) != 0;
-  bool two_seg = false;  // a two-segment pass updates the running estimates through the table as well (segment 0, then 1)
-  for (int l = 0; l < n.n_levels; ++l) two_seg |= ps.split[l] < ps.rows[l];
-  two_seg &= train;
-  ps.upd_n = 0;
-  if (defer || two_seg) {
-    int n_bn = 0;
-    for (int i = 0; i < n_ops; ++i) n_bn += n.ops[i].type == PCMI_OP_BN;
-    if (n_bn > ps.upd_cap) {
-      PCMI_HIP_CHECK(hipDeviceSynchronize());
-      if (ps.upd_host) PCMI_HIP_CHECK(hipHostFree(ps.upd_host));
-      if (ps.upd_dev) PCMI_HIP_CHECK(hipFree(ps.upd_dev));
-      ps.upd_host = ps.upd_dev = nullptr;
-      PCMI_HIP_CHECK(hipHostMalloc((void**)&ps.upd_host, sizeof(BnRunningUpdate) * n_bn, hipHostMallocDefault));
-      PCMI_HIP_CHECK(hipMalloc((void**)&ps.upd_dev, sizeof(BnRunningUpdate) * n_bn));
-      ps.upd_cap = n_bn;
-    }
-    // (this wait is also what keeps the enqueueing thread ONE pass ahead of the GPU: host_wait_event sleeps in it)
-    if (!ps.upd_copied) PCMI_HIP_CHECK(hipEventCreateWithFlags(&ps.upd_copied, host_wait_event_flags()));
-    rc = host_wait_event(ps.upd_copied);  // the previous table has left the pinned buffer
-    if (rc) return rc;
-  }
-  ps.in_feats = in_feats;
-  ps.in_ld = in_ld;
-  ps.out_feats = out_feats;
-  ps.out_ld = out_ld;
-  ps.coords = coords;
-  // (the pack on a side stream, joined in front of the first convolution that needs it, was measured: 237.7 against
-  //  238.3 pairs/s in line -- profiles/r03c_bench_ab.txt -- and is gone)
-  if (ps.x3_bwd_pending && ps.x3_bwd_packed) {
-    // a training forward of this pass that was never differentiated: its side-stream pack may still be reading the job
-    // table / writing the packs this pass is about to rebuild
-    PCMI_HIP_CHECK(hipStreamWaitEvent(st, ps.x3_bwd_packed, 0));
-    ps.x3_bwd_pending = false;
-  }
-  const bool train0 = (training & 1) != 0;
-  // PCMI_X3_PACK_SIDE (round 6, default on for training passes): the forward orientations are packed on the side stream, behind
-  // everything enqueued so far, and the pass waits for them in front of the first convolution that reads a pack -- the stem and
-  // the 32-channel layers of the first two levels (~0.45 ms) do not.  (Round 5 measured this at +0.3 %, inside the spread, with a
-  // join in front of the first convolution of ANY kind; the residual branches above use the same stream.)
-  const bool pack_side = train0 && [] {
-    const char* e = getenv("PCMI_X3_PACK_SIDE");
-    return !(e && e[0] == '0');
-  }();
-  bool pack_joined = true;
-  if (pack_side) {
-    rc = ensure_streams(n);
-    if (rc) return rc;
-    if (!n.ev_fwd_fork) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_fork, hipEventDisableTiming));
-    if (!n.ev_fwd_pack) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_pack, hipEventDisableTiming));
-    PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_fork, st));
-    PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_fwd_fork, 0));
-    rc = x3_prepack(n, ps, params, n.side, train0);
-    PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_pack, n.side));
-    pack_joined = false;
-  } else {
-    rc = x3_prepack(n, ps, params, st, train0);
-  }
-  const X3TableScope x3_scope;  // the table is this thread's only until the pass has been enqueued
-  if (rc) return rc;
-  // where the backward-data orientations are packed: behind the first op of the third level (the pass is in its
-  // latency-bound coarse phase from there on and the side stream is idle during a forward pass) -- or behind the last op
-  // an error return from here on leaves no table behind that a later pass could mistake for this one's packs
-  struct X3FailGuard {
-    PassState& ps;
-    bool armed = true;
-    ~X3FailGuard() {
-      // (x3_bwd_pending stays: it is true only if THIS pass recorded the event, and the next forward of the pass must still
-      //  wait for that side-stream pack before it rebuilds the job table)
-      if (armed) ps.x3_current = ps.x3_bwd_owed = false;
-    }
-  } x3_guard{ps};
-  int pack_bwd_at = -1;
-  if (ps.x3_bwd_owed) {
-    pack_bwd_at = n_ops - 1;
-    for (int i = 0; i < n_ops; ++i)
-      if (n.tensors[n.ops[i].out].level >= 2) {
-        pack_bwd_at = i;
-        break;
-      }
-    rc = ensure_streams(n);
-    if (rc) return rc;
-    if (!ps.x3_bwd_packed) PCMI_HIP_CHECK(hipEventCreateWithFlags(&ps.x3_bwd_packed, hipEventDisableTiming));
-  }
-  g_prof_fwd.lap(2);
-  // ---- run --------------------------------------------------------------------------------------
-  if (!n.timed_ops.empty()) {  // the next event set of the ring (pcmi_net_time_ops); its old records are dropped
-    ++n.timed_cur;
-    const size_t per = n.timed_ops.size(), base = (size_t)(n.timed_cur % n.timed_sets) * per;
-    for (size_t q = 0; q < per; ++q) n.timed_hit[base + q] = 0;
-    if (n.timed_keep_groups) n.timed_group_n[n.timed_cur % n.timed_sets] = 0;
-  }
-  // ---- the residual branch of a block beside its main path (round 6) ------------------------------------------------------
-  // A BasicBlock whose channel count changes computes its residual with a 1x1 convolution + BatchNorm of the block's INPUT
-  // (pc/model/resnet.py: downsample); the traced program lists the two behind conv1 / bn1 / conv2 although they depend on
-  // nothing the main path computes.  They go to the side stream -- idle during a forward pass but for the weight packs -- as
-  // soon as the block's input is complete, with the side workspace, and the BatchNorm that adds the residual waits for them.
-  // Same kernels on the same operands: bit-identical results (tests/test_gpu_timing.py).  PCMI_FWD_BRANCH=0: in program order.
-  std::vector<int> fork_at(n_ops, -1), join_before(n_ops, -1);
-  std::vector<char> on_side(n_ops, 0);
-  {
-    const char* e = getenv("PCMI_FWD_BRANCH");
-    if (!(e && e[0] == '0')) {
-      for (int i = 3; i + 2 < n_ops; ++i) {
-        const auto &c = n.ops[i], &b1 = n.ops[i + 1], &b2 = n.ops[i + 2];
-        if (c.type != PCMI_OP_CONV || c.kernel_size != 1 || b1.type != PCMI_OP_BN || b1.in != c.out || b1.relu || b1.in2 >= 0 ||
-            b2.type != PCMI_OP_BN || b2.in2 != b1.out)
-          continue;
-        int s0 = -1;
-        for (int q = i - 3; q < i; ++q)
-          if (n.ops[q].in == c.in && !on_side[q]) {
-            s0 = q;
-            break;
-          }
-        if (s0 < 0 || fork_at[s0] >= 0) continue;
-        fork_at[s0] = i;
-        on_side[i] = on_side[i + 1] = 1;
-        join_before[i + 2] = i;
-      }
-    }
-  }
-  bool any_fork = false;
-  for (int i = 0; i < n_ops; ++i) any_fork |= fork_at[i] >= 0;
-  if (any_fork) {
-    rc = ensure_streams(n);
-    if (rc) return rc;
-    rc = n.ws_side.reserve(ps.ws.cap, n.side);
-    if (rc) return rc;
-    if (!n.ev_fwd_fork) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_fork, hipEventDisableTiming));
-    if (!n.ev_fwd_join) PCMI_HIP_CHECK(hipEventCreateWithFlags(&n.ev_fwd_join, hipEventDisableTiming));
-  }
-  auto run_op = [&](int i, hipStream_t sq, DevBuf& w) -> int {
-    const auto& op = n.ops[i];
-    const View x = act_view(n, ps, op.in), y = act_view(n, ps, op.out);
-    const int64_t n_in = ps.rows[n.tensors[op.in].level], n_out = ps.rows[n.tensors[op.out].level];
-    int rc = PCMI_OK;
-      const int tq = n.timed_slot(i);
-      if (tq >= 0) PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tq + 0], sq));
-      const long lf0 = g_launches;
-      if (op.type == PCMI_OP_CONV) {
-        rc = spconv_forward(x.p, x.ld, n_in, op.cin, params + op.w_off, op.cout, ps.has_map[i] ? &ps.maps[i] : nullptr,
-                            op.transpose, op.has_bias ? params + op.b_off : nullptr, y.p, y.ld, n_out, 0, w.p, w.cap,
-                            sq);
-      } else if (op.type == PCMI_OP_BN) {
-        View r = {nullptr, 0};
-        if (op.in2 >= 0) r = act_view(n, ps, op.in2);
-        float* stats0 = (float*)(ps.act.p + ps.stat_off[i]);
-        uint32_t* rbits = ps.bits_off[i] != SIZE_MAX ? (uint32_t*)(ps.act.p + ps.bits_off[i]) : nullptr;
-        if (train) {
-          const int64_t sp = ps.split[n.tensors[op.in].level];
-          // two segments: both in one statistics launch + one apply launch.  The running estimates go through the table
-          // then (segment 0, then segment 1), as they do when this pass defers them or another level has two segments.
-          const bool two = sp < n_in, tab = two || defer || two_seg;
-          float* stats1 = stats0 + 3 * op.cout;
-          BnTrainForward a;
-          memset(&a, 0, sizeof(a));
-          a.x = x.p; a.x_ld = x.ld; a.residual = r.p; a.res_ld = r.ld; a.y = y.p; a.y_ld = y.ld;
-          a.n = n_in; a.split = sp; a.c = op.cout; a.gamma = params + op.w_off; a.beta = params + op.b_off;
-          a.eps = op.eps; a.relu = op.relu;
-          a.save_mean = stats0; a.save_invstd = stats0 + op.cout; a.save_unbiased = stats0 + 2 * op.cout;
-          a.stat_stride = 3 * op.cout;
-          a.running_mean = tab ? nullptr : op.running_mean; a.running_var = tab ? nullptr : op.running_var;
-          a.momentum = op.momentum; a.relu_bits = rbits;
-          rc = bn_forward_train(a, w.p, w.cap, sq);
-          if (tab && op.running_mean)
-            ps.upd_host[ps.upd_n++] = {op.running_mean, op.running_var, stats0, stats0 + 2 * op.cout, op.cout, op.momentum,
-                                       two ? stats1 : nullptr, two ? stats1 + 2 * op.cout : nullptr};
-        } else {
-          rc = pcmi_bn_fwd_eval(x.p, x.ld, n_in, op.cout, params + op.w_off, params + op.b_off, op.running_mean,
-                                op.running_var, op.eps, r.p, r.ld, op.relu, y.p, y.ld, (void*)sq);
-        }
-      } else {
-        rc = pcmi_l2norm_fwd(x.p, x.ld, n_in, op.cout, y.p, y.ld, (float*)(ps.act.p + ps.stat_off[i]), (void*)sq);
-      }
-      if (rc) return rc;
-      if (tq >= 0) {
-        PCMI_HIP_CHECK(hipEventRecord(n.timed_ev[pcmi_net::kTimedEv * tq + 1], sq));
-        n.timed_hit[tq] |= 1;
-        n.timed_cnt[3 * tq + 0] = (int)(g_launches - lf0);
-      }
-    return PCMI_OK;
-  };
-  for (int i = 0; i < n_ops; ++i) {
-    const auto& op = n.ops[i];
-    if (!pack_joined && (i >= ps.x3_first_op || fork_at[i] >= 0)) {  // (a forked 1x1 layer may pack for itself on the side stream: keep it simple)
-      PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_fwd_pack, 0));
-      pack_joined = true;
-    }
-    if (fork_at[i] >= 0) {  // everything enqueued so far is the branch's input (and more): the branch starts behind it
-      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_fork, st));
-      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_fwd_fork, 0));
-      rc = run_op(fork_at[i], n.side, n.ws_side);
-      if (rc) return rc;
-      rc = run_op(fork_at[i] + 1, n.side, n.ws_side);
-      if (rc) return rc;
-      PCMI_HIP_CHECK(hipEventRecord(n.ev_fwd_join, n.side));
-    }
-    if (join_before[i] >= 0) PCMI_HIP_CHECK(hipStreamWaitEvent(st, n.ev_fwd_join, 0));
-    if (!on_side[i]) {
-      rc = run_op(i, st, ps.ws);
-      if (rc) return rc;
-    }
-    if (i == pack_bwd_at) {  // the side stream starts behind this point of the pass (and behind the job table's upload)
-      PCMI_HIP_CHECK(hipEventRecord(n.ev_main, st));
-      PCMI_HIP_CHECK(hipStreamWaitEvent(n.side, n.ev_main, 0));
-      rc = x3_pack_many(reinterpret_cast<const X3PackJob*>(ps.x3_jobs_dev.p), ps.x3_n_jobs, ps.x3_items, n.side, ps.x3_items_fwd);
-      if (rc) return rc;
-      PCMI_HIP_CHECK(hipEventRecord(ps.x3_bwd_packed, n.side));
-      ps.x3_bwd_owed = false;
-      ps.x3_bwd_pending = true;
-    }
-    g_prof_fwd.lap(op.type == PCMI_OP_CONV ? 3 : (op.type == PCMI_OP_BN ? 4 : 5));
-  }
-  if ((defer || two_seg) && ps.upd_n > 0) {
-    PCMI_HIP_CHECK(hipMemcpyAsync(ps.upd_dev, ps.upd_host, sizeof(BnRunningUpdate) * ps.upd_n, hipMemcpyHostToDevice, st));
-    PCMI_HIP_CHECK(hipEventRecord(ps.upd_copied, st));
-    if (!defer) {  // two-segment pass without a deferral request: apply now, in layer order
-      rc = bn_running_update(ps.upd_dev, ps.upd_n, st);
-      if (rc) return rc;
-      ps.upd_n = 0;
-    }
-  }
-  g_prof_fwd.lap(6);
-  static const char* const kFwdNames[] = {"levels", "maps", "layout+reserve", "conv", "bn", "l2norm", "tail"};
-  g_prof_fwd.report("net_forward", kFwdNames, 7);
-  ps.valid = train;
-  x3_guard.armed = false;
-  return PCMI_OK;
+  ForwardRun r{*net, ps, coords, in_feats, params, out_feats, in_ld, out_ld, n_rows, as_stream(stream), train, defer};
+  int rc = r.begin();
+  for (int i = 0; i < (int)net->ops.size() && !rc; ++i) rc = r.step(i);
+  if (!rc) rc = r.end();
+  // an error return leaves no table behind that a later pass could mistake for this one's packs
+  // (x3_bwd_pending stays: it is true only if THIS pass recorded the event, and the next forward of the pass must still
+  //  wait for that side-stream pack before it rebuilds the job table)
+  if (rc) ps.x3_current = ps.x3_bwd_owed = false;
+  else ps.valid = train;
+  return rc;
 }
 
 int pcmi_net_stream_wait_bucket(pcmi_net_t* net, pcmi_stream_t stream) {
@@ -1269,14 +1265,13 @@ int pcmi_net_backward(pcmi_net_t* net, int pass, const float* d_out, int64_t d_l
   PCMI_REQUIRE(net && d_out && params && grads, PCMI_ERR_INVALID, "net_backward: null argument");
   PCMI_REQUIRE(pass >= 0 && pass < (int)net->passes.size() && net->passes[pass].valid, PCMI_ERR_INVALID,
                "net_backward: pass %d has no training-mode forward to differentiate", pass);
-  BackwardJob job;
-  job.pass = pass;
-  job.d_out = d_out;
-  job.d_ld = d_ld;
-  job.st = as_stream(stream);
   // (the weight gradients enqueued on the side stream are launched from this call too: same mode)
   const ConvPrecisionScope precision(net->conv_precision);
-  return run_backward(*net, job, params, grads, bucket_lo_host, n_buckets, ready, ready_ctx);
+  const X3TableScope x3_scope(net->passes[pass], params);
+  BackwardRun r{*net, pass, d_out, d_ld, as_stream(stream), params, grads, bucket_lo_host, n_buckets, ready, ready_ctx};
+  int rc = r.begin();
+  for (int i = (int)net->ops.size() - 1; i >= 0 && !rc; --i) rc = r.step(i);
+  return rc ? rc : r.end();
 }
 
 int pcmi_net_set_conv_precision(pcmi_net_t* net, int precision) {

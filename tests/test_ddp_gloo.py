@@ -77,7 +77,7 @@ def test_grad_reducer_world2_gloo():
 
 def _engine_worker(rank, world, port, q):
   """The REAL GradReducer driven through NativeEngine._ready_args by a CPU stand-in for pcmi_net_backward's bucket
-  logic (csrc/engine.hip::run_backward: a bucket is final after the lowest-index op that owns parameters of it; the
+  logic (csrc/engine.hip::BackwardRun::begin: a bucket is final after the lowest-index op that owns parameters of it; the
   executor reports it by its position in the ASCENDING list of bucket offsets)."""
   os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
   from pointcontrast_amd.engine import NativeEngine, lower_model

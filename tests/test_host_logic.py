@@ -164,6 +164,45 @@ def test_model_lowers_to_a_valid_network_program(built_lib):
     assert len(set(offs)) == n_conv and offs[0] == 0
 
 
+def test_net_create_refuses_convolutions_across_the_wrong_levels(built_lib):
+  """The level rules of a convolution with a kernel map (stride 1 stays on its level, a strided one goes one level down,
+  a transposed one goes one level up) are checked when the network is created, not in its first forward pass: the
+  lowered Res16UNet14 program with ONE convolution's output tensor moved to another level is refused with
+  PCMI_ERR_INVALID and the op named; the unmodified program is accepted."""
+  from pointcontrast_amd._lib import NetTensor, PcmiError, lib, check
+  from pointcontrast_amd.engine import create_net, lower_model
+  from pointcontrast_amd.lib.config import get_config
+  from pointcontrast_amd.lib.distributed import FlatParameters
+  from pointcontrast_amd.model import load_model
+  model = load_model("Res16UNet14")(3, 32, get_config([]), D=3)
+  prog = lower_model(model, FlatParameters(model.parameters()))
+  check(lib.pcmi_net_destroy(create_net(prog)))
+  tensors, ops = prog["tensors"], prog["ops"]
+
+  def conv_where(pred):  # the first such convolution whose output is a tensor of its own (moving it moves no other op's levels)
+    for i, o in enumerate(ops):
+      if o["type"] == 0 and o.get("kernel_size", 0) > 1 and pred(o) and tensors[o["out"]]["parent"] < 0 and o["out"] != prog["output"] \
+          and not any(t["parent"] == o["out"] for t in tensors):
+        return i, o
+    raise AssertionError("the program has no such convolution")
+
+  cases = [  # (which convolution, the level its output is moved to, the message)
+      (lambda o: not o.get("transpose", 0) and o.get("stride", 1) == 1 and o.get("kernel_size", 0) == 3, lambda li: li + 1,
+       "stride-1 conv across levels"),
+      (lambda o: not o.get("transpose", 0) and o.get("stride", 1) == 2, lambda li: li + 2, "strided conv must go one level down"),
+      (lambda o: o.get("transpose", 0), lambda li: li, "transposed conv must go one level up"),
+  ]
+  for pred, move, message in cases:
+    i, o = conv_where(pred)
+    T = (NetTensor * len(tensors))()
+    ctypes.memmove(T, prog["T"], ctypes.sizeof(T))
+    T[o["out"]].level = move(tensors[o["in_"]]["level"])
+    with pytest.raises(PcmiError) as err:
+      h = create_net(dict(prog, T=T))
+      lib.pcmi_net_destroy(h)
+    assert str(err.value) == "libpcmi error -1: net: op %d: %s" % (i, message), str(err.value)  # -1: PCMI_ERR_INVALID
+
+
 def test_checkpoint_layout_interoperates_with_reference_format(built_lib, tmp_path):
   """a checkpoint in the reference's layout ({state_dict, optimizer, scheduler, curr_iter, config},
   pc/lib/ddp_trainer.py:113-133) whose state_dict uses the reference's parameter names (restated by the oracle
