@@ -95,11 +95,14 @@ def _dev(t):
 
 
 class _Maps:
-  """One coordinate manager over the first n rows of the fixed voxel set, its maps and their exported pair lists."""
+  """One coordinate manager over the first n rows of the fixed voxel set (or over a given int32 [n, 4] coordinate
+  array), its maps and their exported pair lists."""
 
-  def __init__(self, n, base="mid"):
+  def __init__(self, n, base="mid", coords=None):
     import pointcontrast_amd.minkowski as me
-    self.cm = me.CoordsManager(torch.from_numpy(coords_with_rows(n, base)).to(DEV))
+    coords = coords_with_rows(n, base) if coords is None else np.ascontiguousarray(coords)
+    assert len(coords) == n
+    self.cm = me.CoordsManager(torch.from_numpy(coords).to(DEV))
     self.key0 = self.cm.key(0)
     self.n = n
     self._exp = {}
