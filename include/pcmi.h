@@ -1080,6 +1080,54 @@ int pcmi_det_voxelize(const float* point_clouds, int64_t B, int64_t num_points, 
                       int32_t* voxel_inds, float* voxel_feats, int64_t* counts, int32_t* flags, void* ws, size_t ws_bytes,
                       pcmi_stream_t stream);
 
+/* ---- The feature columns of the detection input (csrc/detect_features.hip): height above the floor, normalised colour -------
+ * What the reference adds per scan on the host with use_height / use_color (downstream/votenet_det_new); nothing here
+ * synchronises or reads back.  One more flag bit, set per scene in the same flags [B] as above:
+ *   PCMI_DET_FLAG_FEATURE  the scene is empty (or its offsets are not 0 <= offsets[b] <= offsets[b + 1] <= n) or holds a
+ *                          non-finite value where a quantile is asked for; or a chosen row's raw colour or raw z is not finite
+ *
+ * pcmi_segment_quantile = np.percentile(point_cloud[:, 2], 0.99) (scannet_detection_dataset.py:91,
+ *   sunrgbd_detection_dataset.py:98) for every scene of a batch.  values[i stride] (fp32) is element i -- the z column of xyz
+ *   [n, 3] is read in place with values = xyz + 2, stride = 3 (1 <= stride <= 65536); offsets [B + 1] (DEVICE int64) delimit
+ *   the scenes; q in [0, 100].  For a scene of m values, numpy's method="linear" on its own terms, in fp64, every operation
+ *   rounded on its own:  v = (m - 1) (q / 100);  k = floor(v);  g = v - k;  lo = the k-th smallest value (from 0), hi = the
+ *   min(k + 1, m - 1)-th smallest;  out[b] = lo + (hi - lo) g  (fp64 [B]).  lo and hi are EXACT order statistics, the values a
+ *   full sort would put at those ranks; a zero (lo, hi or out) is returned as +0.  out_stats [B, 2] (fp32; may be NULL) = lo, hi.
+ *   numpy's own float32 path rounds hi - lo, the product and the sum to fp32 and so differs by up to 3 fp32 ulps of
+ *   max(|lo|, |hi|).  An empty scene or one that holds a NaN or an infinity: PCMI_DET_FLAG_FEATURE, out = 0, out_stats = 0.
+ *   A radix select, eight bits a pass, over the order-preserving integer image of the floats (-0.0 sorts below +0.0):
+ *   histograms in LDS with integer atomics.  One launch with one workgroup per scene serves every scene of up to 16384
+ *   values; when n > 16384 four launches (one a pass) of one workgroup per 8192 values and a closing launch serve the larger
+ *   scenes, merging into ws with integer additions and one integer minimum -- the same bits from run to run.
+ *   B <= 1023 and n < 2^29, PCMI_ERR_RANGE beyond.  ws: pcmi_segment_quantile_workspace_bytes(B), 16-byte aligned.
+ * pcmi_det_point_features writes the final point_clouds [B, P, 3 + C] (fp32) in the reference's column order: xyz -- copied
+ *   from point_clouds_xyz [B, P, 3], the output of pcmi_det_sample_transform / pcmi_det_votes_transform --, then rgb if rgb
+ *   [n, 3] (fp32, raw) is given, then the height if floor_height [B] (DEVICE fp64, e.g. out of pcmi_segment_quantile) is
+ *   given; C = 1, 3 or 4 (both NULL: PCMI_ERR_INVALID).  Row (b, p) reads raw row offsets[b] + choices[b, p]; xyz [n, 3] is
+ *   the raw scan (only z is read, only with floor_height).
+ *     height  fp32(fp64(z) - floor_height[b]); mode PCMI_DET_SUNRGBD with augment: then fp32(fp64(height) scale[b])
+ *             (sunrgbd_detection_dataset.py:147-148: a float32 column times a float64 scalar in place, which numpy >= 2
+ *             computes in float64).  ScanNet's flips and rotation about z leave it alone.  The reference subtracts numpy's
+ *             float32 percentile in float32: one more fp32 rounding beside the quantile's bound.
+ *     colour  PCMI_DET_SCANNET: fp32((fp64(rgb) - MEAN) / 256), MEAN = (109.8, 97.2, 83.8) (scannet_detection_dataset.py:24,
+ *             88); no augmentation.  PCMI_DET_SUNRGBD: c = fp32(fp64(rgb) - 0.5) (sunrgbd_detection_dataset.py:38,95); with
+ *             augment, in fp64 (:129-136): x = c + 0.5; x = x color_gain[b, j]; x = x + color_shift[b, j]; x = x +
+ *             color_jitter[b, p]; x = min(max(x, 0), 1); x = x * (color_keep[b, p] != 0); out = fp32(x - 0.5).  color_gain,
+ *             color_shift [B, 3], color_jitter [B, P] (fp64), color_keep [B, P] (uint8) may each be NULL: 1, 0, 0, 1.  The
+ *             reference draws jitter and keep per RAW point before sampling; here they are per CHOSEN point.
+ *   A row whose choice is out of range (PCMI_DET_FLAG_CHOICE) has feature columns 0; a non-finite raw colour, or a
+ *   non-finite raw z with floor_height, sets PCMI_DET_FLAG_FEATURE and leaves those columns 0.  scale [B] (fp64) is read only
+ *   for the augmented SUN RGB-D height. */
+#define PCMI_DET_FLAG_FEATURE 64
+size_t pcmi_segment_quantile_workspace_bytes(int64_t B);
+int pcmi_segment_quantile(const float* values, int64_t stride, const int64_t* offsets, int64_t n, int64_t B, double q,
+                          double* out, float* out_stats, int32_t* flags, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_det_point_features(const float* point_clouds_xyz, const float* xyz, const float* rgb, const int64_t* offsets, int64_t n,
+                            int64_t B, int64_t num_points, const int32_t* choices, const double* floor_height, int mode,
+                            int augment, const double* scale, const double* color_gain, const double* color_shift,
+                            const double* color_jitter, const uint8_t* color_keep, float* out, int32_t* flags,
+                            pcmi_stream_t stream);
+
 int pcmi_sgd_step(float* w, const float* g, float* v, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, pcmi_stream_t stream);
 /* The same with torch's dampening (the downstream fine-tuning's optimiser: SGD(lr, sgd_momentum, dampening =

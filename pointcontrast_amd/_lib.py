@@ -233,6 +233,10 @@ PROTOTYPES = {
                                       C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pcmi_det_voxelize_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcmi_det_voxelize": (C.c_int, [c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_segment_quantile_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_segment_quantile": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_det_point_features": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, C.c_int, C.c_int, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pcmi_softmax_ce_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_softmax_ce_fwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_softmax_ce_bwd": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp]),

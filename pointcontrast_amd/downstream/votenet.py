@@ -517,9 +517,12 @@ def rotz(t):
 class DetectionDraws:
   """Every random quantity of one detection batch, on the host: choices int32 [B, num_points] (the row within the scene),
   flip_x, flip_y bool [B], rot_angle float64 [B], scale float64 [B]; augment False = the reference's augment=False (only
-  the choice is applied)."""
+  the choice is applied).  The colour augmentation of SUN RGB-D (use_color): color_gain, color_shift float64 [B, 3],
+  color_jitter float64 [B, num_points], color_keep bool [B, num_points] -- per CHOSEN point, where the reference draws per raw
+  point before it samples; each None = the identity (1, 0, 0, keep)."""
 
-  def __init__(self, choices, flip_x=None, flip_y=None, rot_angle=None, scale=None, augment=True):
+  def __init__(self, choices, flip_x=None, flip_y=None, rot_angle=None, scale=None, augment=True, color_gain=None, color_shift=None,
+               color_jitter=None, color_keep=None):
     self.choices = np.ascontiguousarray(choices, dtype=np.int32)
     B = self.choices.shape[0]
     self.flip_x = np.zeros(B, bool) if flip_x is None else np.asarray(flip_x, dtype=bool)
@@ -527,14 +530,22 @@ class DetectionDraws:
     self.rot_angle = np.zeros(B, np.float64) if rot_angle is None else np.asarray(rot_angle, dtype=np.float64)
     self.scale = np.ones(B, np.float64) if scale is None else np.asarray(scale, dtype=np.float64)
     self.augment = bool(augment)
+    P = self.choices.shape[1]
+    self.color_gain = None if color_gain is None else np.asarray(color_gain, dtype=np.float64).reshape(B, 3)
+    self.color_shift = None if color_shift is None else np.asarray(color_shift, dtype=np.float64).reshape(B, 3)
+    self.color_jitter = None if color_jitter is None else np.asarray(color_jitter, dtype=np.float64).reshape(B, P)
+    self.color_keep = None if color_keep is None else np.asarray(color_keep, dtype=bool).reshape(B, P)
 
   @staticmethod
-  def sample(sizes, num_points, dataset, generator=None, augment=True):
+  def sample(sizes, num_points, dataset, generator=None, augment=True, color=False):
     """Draws by the reference's distributions (scannet_detection_dataset.py:103-104,115-126, sunrgbd_detection_dataset.py:
     104-112,139,193, pc_util.py:35-43): a choice of num_points rows without replacement where the scan has at least that many,
     with replacement otherwise; flips with probability 1/2 (u > 0.5; no y flip for SUN RGB-D); the angle u w - w / 2 with w =
     pi / 18 (ScanNet) or pi / 3 (SUN RGB-D); the scale u 0.3 + 0.85 for SUN RGB-D only.  generator: a numpy Generator or a
-    seed; the same seed gives the same draws.  augment False: identity draws apart from the choice."""
+    seed; the same seed gives the same draws.  augment False: identity draws apart from the choice.  color (SUN RGB-D with
+    augment; sunrgbd_detection_dataset.py:130-135): gain 1 + 0.4 u - 0.2 and shift 0.1 u - 0.05 per scene and channel, jitter
+    0.05 u - 0.025 and keep u > 0.3 per chosen point -- taken from the generator AFTER every draw above, so that a seed gives
+    the same choices, flips, angles and scales with and without it."""
     assert dataset in DET_ROT_RANGE, "dataset: 'scannet' or 'sunrgbd'"
     rng = generator if isinstance(generator, np.random.Generator) else np.random.default_rng(generator)
     B, w = len(sizes), DET_ROT_RANGE[dataset]
@@ -551,6 +562,11 @@ class DetectionDraws:
       d.rot_angle[b] = (rng.random() * w) - w / 2
       if dataset == "sunrgbd":
         d.scale[b] = rng.random() * 0.3 + 0.85
+    if color and augment and dataset == "sunrgbd":
+      d.color_gain = 1 + 0.4 * rng.random((B, 3)) - 0.2
+      d.color_shift = 0.1 * rng.random((B, 3)) - 0.05
+      d.color_jitter = 0.05 * rng.random((B, num_points)) - 0.025
+      d.color_keep = rng.random((B, num_points)) > 0.3
     return d
 
   def rot(self):
@@ -586,14 +602,19 @@ class DetectionInputPipeline:
   """Raw scans -> the batch dict of the reference's detection fine-tuning (VoxelizationDataset over ScannetDetectionDataset or
   SunrgbdDetectionVotesDataset, then collate_fn) as device tensors: ONE upload, pcmi_det_sample_transform /
   pcmi_det_votes_transform, pcmi_det_votes_from_instances, pcmi_det_box_labels, pcmi_det_voxelize, ONE read-back (the flags
-  and the voxel counts).  The sparse-backbone recipe: xyz only, no colour and no height column.  Differences from the reference
-  (INTEGRATION.md B2): voxel rows leave in the order of first occurrence; the choices are data; a flagged scene raises."""
+  and the voxel counts).  use_height / use_color (the reference's dataset options) widen point_clouds to [B, P, 3 + C] --
+  xyz, then rgb, then the height above the floor, feature_dim = C -- with pcmi_segment_quantile over every scan's z and
+  pcmi_det_point_features; votes, box labels and voxels are computed from xyz as without them.  Differences from the reference
+  (INTEGRATION.md B2): voxel rows leave in the order of first occurrence; the choices are data; a flagged scene raises; the
+  colour jitter and dropout are drawn per chosen point."""
 
   def __init__(self, dataset, num_points, voxel_size, device=None, valid_sem=None, label_to_class=None, mean_size_arr=None,
-               num_heading_bin=None):
+               num_heading_bin=None, use_height=False, use_color=False):
     assert dataset in PF.DET_MODES, "dataset: 'scannet' or 'sunrgbd'"
     assert mean_size_arr is not None, "mean_size_arr [n_class, 3]: the dataset config's mean sizes"
     self.dataset, self.num_points, self.voxel_size = dataset, int(num_points), float(voxel_size)
+    self.use_height, self.use_color = bool(use_height), bool(use_color)
+    self.feature_dim = (3 if self.use_color else 0) + (1 if self.use_height else 0)
     self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     self.num_heading_bin = int(num_heading_bin) if num_heading_bin is not None else (1 if dataset == "scannet" else 12)
     ids = SCANNET_NYU40IDS if valid_sem is None else [int(v) for v in valid_sem]
@@ -608,11 +629,22 @@ class DetectionInputPipeline:
     """The numpy arrays that one batch uploads (what tests feed the restatement with)."""
     B, scannet = len(scenes), self.dataset == "scannet"
     sizes = [len(s[0]) for s in scenes]
+    width = 6 if self.use_color else 3
     for s in scenes:
-      assert np.asarray(s[0]).dtype == np.float32, "points: float32 [n, 3], as the arrays on disk are"
+      p = np.asarray(s[0])
+      assert p.dtype == np.float32 and p.ndim == 2 and p.shape[1] == width, \
+          "points: float32 [n, %d], as the arrays on disk are%s" % (width, " (xyz, then rgb: use_color)" if self.use_color else "")
     a = dict(offsets=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
-             xyz=np.concatenate([np.asarray(s[0], dtype=np.float32).reshape(-1, 3) for s in scenes]),
+             xyz=np.concatenate([np.asarray(s[0], dtype=np.float32)[:, 0:3] for s in scenes]),
              choices=draws.choices)
+    if self.use_color:
+      a["rgb"] = np.concatenate([np.asarray(s[0], dtype=np.float32)[:, 3:6] for s in scenes])
+      if draws.augment and not scannet:
+        for k in ("color_gain", "color_shift", "color_jitter"):
+          if getattr(draws, k) is not None:
+            a[k] = getattr(draws, k)
+        if draws.color_keep is not None:
+          a["color_keep"] = draws.color_keep.astype(np.uint8)
     boxes = np.zeros((B, MAX_NUM_OBJ, 8), np.float64)
     n_boxes = np.zeros(B, np.int32)
     for b, s in enumerate(scenes):
@@ -641,7 +673,8 @@ class DetectionInputPipeline:
 
   def __call__(self, scenes, draws=None):
     """scenes: a list of raw scans -- ScanNet (vertices float32 [n, 3], instance_labels [n], semantic_labels [n],
-    instance_bboxes [k, 7]), SUN RGB-D (points float32 [n, 3], bboxes [k, 8], point_votes float64 [n, 10]).  draws: a
+    instance_bboxes [k, 7]), SUN RGB-D (points float32 [n, 3], bboxes [k, 8], point_votes float64 [n, 10]); with use_color
+    the vertices / points are [n, 6]: xyz, then the raw rgb (0..255 for ScanNet, 0..1 for SUN RGB-D).  draws: a
     DetectionDraws; None draws with DetectionDraws.sample(augment=False) from a fresh generator.  Returns the batch dict as
     device tensors: point_clouds, center_label, heading_class_label, heading_residual_label, size_class_label,
     size_residual_label, sem_cls_label, box_label_mask, vote_label, vote_label_mask, voxel_coords int32 [M, 4], voxel_inds int32
@@ -663,13 +696,20 @@ class DetectionInputPipeline:
                             label_to_class=self._lut if self.dataset == "scannet" else None, num_heading_bin=self.num_heading_bin,
                             flags=flags, **aug)
     x = PF.det_voxelize(s["point_clouds"], self.voxel_size, flags=flags)
+    point_clouds = s["point_clouds"]
+    if self.feature_dim:
+      floor = PF.segment_quantile(d["xyz"], d["offsets"], 0.99, column=2, flags=flags)["quantile"] if self.use_height else None
+      point_clouds, _ = PF.det_point_features(point_clouds, d["xyz"], d["offsets"], d["choices"], self.dataset, rgb=d.get("rgb"),
+                                              floor_height=floor, augment=draws.augment, scale=d.get("scale"),
+                                              color_gain=d.get("color_gain"), color_shift=d.get("color_shift"),
+                                              color_jitter=d.get("color_jitter"), color_keep=d.get("color_keep"), flags=flags)
     host = torch.cat([x["counts"], flags.to(torch.int64)]).cpu().numpy()  # the batch's one read-back
     msg = PF.det_flags_message(host[B + 1:])
     if msg:
       raise ValueError(msg)
     M = int(host[B])
     del out["flags"]
-    out.update(point_clouds=s["point_clouds"], vote_label=v["vote_label"], vote_label_mask=v["vote_label_mask"],
+    out.update(point_clouds=point_clouds, vote_label=v["vote_label"], vote_label_mask=v["vote_label_mask"],
                voxel_coords=x["voxel_coords"][:M], voxel_inds=x["voxel_inds"][:M], voxel_feats=x["voxel_feats"][:M])
     return out
 
@@ -1238,6 +1278,9 @@ class DetectionTrainer:
     self.bn_scheduler = BNMomentumScheduler(self.model, lambda e: detection_bn_momentum(e, decay_rate=bn_decay_rate, decay_step=bn_decay_step),
                                             engine=self.engine)
     self.input_pipeline = input_pipeline  # a DetectionInputPipeline, for train_iter_scenes
+    if backbone == "pointnet2" and input_pipeline is not None and getattr(input_pipeline, "feature_dim", 0) != input_feature_dim:
+      raise ValueError("DetectionTrainer: the input pipeline makes %d feature columns (use_height, use_color) and the pointnet2 backbone "
+                       "takes input_feature_dim=%d" % (getattr(input_pipeline, "feature_dim", 0), input_feature_dim))
     self.epoch, self.curr_iter = 0, 0
     self.start_epoch(0)
 

@@ -1291,12 +1291,14 @@ def seg_color_augment(feats_src, coords, n_scenes, index=None, labels=None, para
 # batch.  None of these is differentiable and none synchronises; errors arrive in `flags` (int32 [B], DET_FLAG_* bits per scene).
 # ---------------------------------------------------------------------------------------------------------------------
 DET_FLAG_RANGE, DET_FLAG_SPAN, DET_FLAG_CHOICE, DET_FLAG_INSTANCE, DET_FLAG_LABEL, DET_FLAG_BOXES = 1, 2, 4, 8, 16, 32
+DET_FLAG_FEATURE = 64
 DET_FLAG_NAMES = {DET_FLAG_RANGE: "a chosen point or a box is not finite, or a voxel coordinate is outside +-2^20",
                   DET_FLAG_SPAN: "a voxel coordinate lies 2^18 or more above the scene's minimum",
                   DET_FLAG_CHOICE: "a choice is outside the scene's rows",
                   DET_FLAG_INSTANCE: "an instance id is outside [0, 1024)",
                   DET_FLAG_LABEL: "a box's label has no class",
-                  DET_FLAG_BOXES: "the number of boxes is outside [0, 64]"}
+                  DET_FLAG_BOXES: "the number of boxes is outside [0, 64]",
+                  DET_FLAG_FEATURE: "the scan is empty or holds a non-finite z (no floor height), or a chosen colour or z is not finite"}
 DET_MAX_INSTANCES = 1024  # PCMI_DET_MAX_INSTANCES
 DET_MAX_NUM_OBJ = 64      # PCMI_DET_MAX_NUM_OBJ, the reference's MAX_NUM_OBJ
 DET_MODES = {"scannet": 0, "sunrgbd": 1}
@@ -1447,6 +1449,73 @@ def det_voxelize(point_clouds, voxel_size, flags=None):
   check(lib.pcmi_det_voxelize(ptr(pc), B, P, float(voxel_size), ptr(coords), ptr(inds), ptr(feats), ptr(counts), ptr(flags), ws, wsb,
                               cur_stream(dev)))
   return dict(voxel_coords=coords, voxel_inds=inds, voxel_feats=feats, counts=counts, flags=flags)
+
+
+def segment_quantile(values, offsets, q, column=None, flags=None, return_stats=False):
+  """pcmi_segment_quantile: numpy's percentile (method "linear") of every scene of a batch, exact order statistics, no
+  synchronisation.  values float32 [n] -- or [n, w] with column = the column to read in place (xyz [n, 3], column 2: the z
+  of every vertex); offsets [B + 1]; q in [0, 100].  Returns a dict of device tensors: quantile float64 [B], stats float32
+  [B, 2] (the two order statistics lo, hi; None unless return_stats), flags int32 [B] (DET_FLAG_FEATURE for an empty scene or
+  one with a non-finite value, whose quantile is 0)."""
+  require_cuda(values, "segment_quantile")
+  dev = values.device
+  v, offs = _f32c(values, "segment_quantile"), _offsets(offsets, dev)
+  assert offs.dim() == 1 and offs.shape[0] >= 2, "segment_quantile: offsets [B + 1]"
+  if column is None:
+    assert v.dim() == 1, "segment_quantile: values [n], or [n, w] with column"
+    stride, first = 1, 0
+  else:
+    assert v.dim() == 2 and 0 <= int(column) < v.shape[1], "segment_quantile: values [n, w] and 0 <= column < w"
+    stride, first = v.shape[1], int(column)
+  n, B = v.shape[0], offs.shape[0] - 1
+  flags = _seg_flags(flags, B, dev)
+  out = torch.empty(B, dtype=torch.float64, device=dev)
+  stats = torch.empty((B, 2), dtype=torch.float32, device=dev) if return_stats else None
+  ws, wsb = ws_args(lib.pcmi_segment_quantile_workspace_bytes(B), dev)
+  base = C.c_void_p(v.data_ptr() + 4 * first) if n else None
+  check(lib.pcmi_segment_quantile(base, stride, ptr(offs), n, B, float(q), ptr(out), ptr(stats), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(quantile=out, stats=stats, flags=flags)
+
+
+def det_point_features(point_clouds, xyz, offsets, choices, dataset, rgb=None, floor_height=None, augment=False, scale=None,
+                       color_gain=None, color_shift=None, color_jitter=None, color_keep=None, flags=None):
+  """pcmi_det_point_features: the final point_clouds float32 [B, P, 3 + C] -- xyz, then rgb, then height.  point_clouds float32
+  [B, P, 3] (det_sample_transform / det_votes_transform); xyz float32 [n, 3], the raw scans; offsets [B + 1]; choices int32
+  [B, P]; dataset "scannet" or "sunrgbd"; rgb float32 [n, 3] (raw colours; None: no colour columns); floor_height float64 [B]
+  on the device (segment_quantile's; None: no height column).  With augment and "sunrgbd": scale float64 [B] (the height),
+  color_gain, color_shift float64 [B, 3], color_jitter float64 [B, P], color_keep bool / uint8 [B, P] (each None = identity).
+  Returns (point_clouds [B, P, 3 + C], flags int32 [B])."""
+  require_cuda(point_clouds, "det_point_features")
+  dev = point_clouds.device
+  pc, x, offs = _f32c(point_clouds, "det_point_features"), _f32c(xyz, "det_point_features"), _offsets(offsets, dev)
+  ch = _i32c(torch.as_tensor(choices), dev)
+  assert pc.dim() == 3 and pc.shape[2] == 3 and x.dim() == 2 and x.shape[1] == 3, "det_point_features: point_clouds [B, P, 3], xyz [n, 3]"
+  B, P, n = pc.shape[0], pc.shape[1], x.shape[0]
+  assert offs.shape == (B + 1,) and ch.shape == (B, P), "det_point_features: offsets [B + 1], choices [B, P]"
+  assert rgb is not None or floor_height is not None, "det_point_features: rgb, floor_height or both"
+  col = None if rgb is None else _f32c(rgb, "det_point_features")
+  assert col is None or col.shape == (n, 3), "det_point_features: rgb [n, 3]"
+  fh = None if floor_height is None else _f64c(floor_height, dev, "det_point_features").reshape(-1)
+  assert fh is None or fh.shape[0] == B, "det_point_features: floor_height [B]"
+  mode = DET_MODES[dataset]
+  sc = gain = shift = jit = keep = None
+  if augment and mode == 1:
+    if fh is not None:
+      sc = _f64c(scale, dev, "det_point_features").reshape(-1)
+      assert sc.shape[0] == B, "det_point_features: scale [B]"
+    if col is not None:
+      gain = None if color_gain is None else _f64c(color_gain, dev, "det_point_features").reshape(-1, 3)
+      shift = None if color_shift is None else _f64c(color_shift, dev, "det_point_features").reshape(-1, 3)
+      jit = None if color_jitter is None else _f64c(color_jitter, dev, "det_point_features")
+      keep = None if color_keep is None else torch.as_tensor(color_keep).to(device=dev, dtype=torch.uint8).contiguous()
+      assert (gain is None or gain.shape[0] == B) and (shift is None or shift.shape[0] == B) and (jit is None or jit.shape == (B, P)) and \
+          (keep is None or keep.shape == (B, P)), "det_point_features: color_gain, color_shift [B, 3], color_jitter, color_keep [B, P]"
+  flags = _seg_flags(flags, B, dev)
+  Cf = (0 if col is None else 3) + (0 if fh is None else 1)
+  out = torch.empty((B, P, 3 + Cf), dtype=torch.float32, device=dev)
+  check(lib.pcmi_det_point_features(ptr(pc), ptr(x), ptr(col), ptr(offs), n, B, P, ptr(ch), ptr(fh), mode, 1 if augment else 0, ptr(sc),
+                                    ptr(gain), ptr(shift), ptr(jit), ptr(keep), ptr(out), ptr(flags), cur_stream(dev)))
+  return out, flags
 
 
 # ---------------------------------------------------------------------------------------------------------------------

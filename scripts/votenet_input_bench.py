@@ -7,10 +7,13 @@ voxels, sampled draws.
   * the whole DetectionInputPipeline.__call__ from host arrays, upload and read-back included: wall clock with a synchronise;
   * the host path it replaces, one scan after another as a DataLoader worker would: the numpy restatement
     tests/detect_input_ref.py (which loops over instances, box slots and voxel rows in Python as the reference's __getitem__
-    does), wall clock.
+    does), wall clock (--host-repeats 0 leaves it out).
+--height and --color add the feature columns (csrc/detect_features.hip; DetectionInputPipeline(use_height, use_color)): the
+device time of pcmi_segment_quantile over every room's z (all of its launches), of pcmi_det_point_features, and the same work
+in numpy on the host -- np.percentile per scan, then the gathers and the colour arithmetic; the whole call then includes them.
 One JSON line per measurement.
 
-  python scripts/votenet_input_bench.py [--scenes 32] [--points 40000] [--warmup 3] [--repeats 15] [--out FILE]
+  python scripts/votenet_input_bench.py [--scenes 32] [--points 40000] [--vertices 50000 150000] [--height] [--color] [--warmup 3] [--repeats 15] [--out FILE]
 """
 import argparse
 import json
@@ -93,6 +96,10 @@ def main():
   ap.add_argument("--warmup", type=int, default=3)
   ap.add_argument("--repeats", type=int, default=15)
   ap.add_argument("--host-repeats", type=int, default=2)
+  ap.add_argument("--vertices", type=int, nargs=2, default=[50000, 150000], metavar=("LO", "HI"),
+                  help="vertices per room, drawn from [LO, HI]; rooms of up to 16384 take pcmi_segment_quantile's one-workgroup launch")
+  ap.add_argument("--height", action="store_true", help="the height column: DetectionInputPipeline(use_height=True)")
+  ap.add_argument("--color", action="store_true", help="the colour columns: DetectionInputPipeline(use_color=True), vertices [n, 6]")
   ap.add_argument("--out", default=None)
   args = ap.parse_args()
   import detect_input_ref as dr
@@ -101,11 +108,15 @@ def main():
   dev = torch.device("cuda:0")
   B, P, vs = args.scenes, args.points, args.voxel_size
   rng = np.random.RandomState(0)
-  scenes = [make_room(rng, int(rng.randint(50000, 150001))) for _ in range(B)]
+  scenes = [make_room(rng, int(rng.randint(args.vertices[0], args.vertices[1] + 1))) for _ in range(B)]
   sizes = [len(s[0]) for s in scenes]
+  scenes_xyz = scenes
+  if args.color:  # vertices [n, 6]: xyz, then rgb in 0..255 as the ScanNet arrays hold it
+    crng = np.random.RandomState(1)
+    scenes = [(np.concatenate([s[0], crng.randint(0, 256, (len(s[0]), 3)).astype(np.float32)], 1),) + s[1:] for s in scenes]
   mean = rng.uniform(0.3, 1.5, (18, 3))
   draws = votenet.DetectionDraws.sample(sizes, P, "scannet", 1)
-  pipe = votenet.DetectionInputPipeline("scannet", P, vs, dev, mean_size_arr=mean)
+  pipe = votenet.DetectionInputPipeline("scannet", P, vs, dev, mean_size_arr=mean, use_height=args.height, use_color=args.color)
   results = []
 
   def emit(name, **kw):
@@ -131,15 +142,38 @@ def main():
                    args.warmup, args.repeats))
   emit("stage_voxelize", **device_ms(lambda: PF.det_voxelize(s["point_clouds"], vs), args.warmup, args.repeats),
        voxels=int(PF.det_voxelize(s["point_clouds"], vs)["counts"][B]))
-  emit("pipeline_call", **wall_ms(lambda: pipe(scenes, draws), args.warmup, args.repeats))
+  if args.height or args.color:
+    def quantile():
+      return PF.segment_quantile(d["xyz"], d["offsets"], 0.99, column=2)["quantile"]
+
+    if args.height:
+      emit("stage_segment_quantile", **device_ms(quantile, args.warmup, args.repeats))
+    floor = quantile() if args.height else None
+    emit("stage_point_features", columns=pipe.feature_dim,
+         **device_ms(lambda: PF.det_point_features(s["point_clouds"], d["xyz"], d["offsets"], d["choices"], "scannet", rgb=d.get("rgb"),
+                                                   floor_height=floor, augment=True), args.warmup, args.repeats))
+
+    def host_features():  # the reference's lines per scan: the percentile over every vertex, then the columns of the chosen rows
+      for b, sc in enumerate(scenes):
+        v, cols = sc[0], []
+        c = draws.choices[b]
+        if args.color:
+          cols.append(((v[c, 3:6] - np.array([109.8, 97.2, 83.8])) / 256.0).astype(np.float32))
+        if args.height:
+          cols.append((v[c, 2] - np.percentile(v[:, 2], 0.99))[:, None])
+        np.concatenate(cols, 1)
+
+    emit("host_numpy_feature_columns", columns=pipe.feature_dim, **wall_ms(host_features, 1, max(args.host_repeats, 3), sync=False))
+  emit("pipeline_call", feature_columns=pipe.feature_dim, **wall_ms(lambda: pipe(scenes, draws), args.warmup, args.repeats))
   lut = dr.nyu40id_table(NYU)
 
   def host_batch():
-    for b, sc in enumerate(scenes):
+    for b, sc in enumerate(scenes_xyz):
       dr.batch("scannet", [sc], draws.choices[b:b + 1], True, draws.flip()[b:b + 1], draws.rot_angle[b:b + 1], draws.scale[b:b + 1], vs,
                valid_sem=NYU, label_to_class=lut, mean_size=mean)
 
-  emit("host_numpy_restatement_batch", **wall_ms(host_batch, 0, args.host_repeats, sync=False))
+  if args.host_repeats > 0:
+    emit("host_numpy_restatement_batch", **wall_ms(host_batch, 0, args.host_repeats, sync=False))
   if args.out:
     with open(args.out, "w") as f:
       for r in results:
