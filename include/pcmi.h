@@ -225,6 +225,37 @@ int pcmi_spconv_bwd_weight(const float* in, int64_t in_ld, int64_t n_in, int cin
  * (pc/model/modules/common.py:117-168 reach them through ME.MinkowskiConvolution). */
 int pcmi_spconv_split_precision(void);
 
+/* What one forward / backward-data launch over `rows` output rows will do (csrc/spconv_plan.h: plan_conv, the function
+ * the launch itself executes): host code only -- no device memory touched, nothing enqueued, usable without a GPU (the
+ * plan then counts the MI355X's 256 compute units).  It reads the environment as a convolution call does.
+ *   x_bytes  size of the gathered operand (its rows x leading dimension x 4): from 2 GiB on the kernels that address it
+ *            with 32-bit offsets are out
+ *   C, N     contraction size and output channels (multiples of 32): cin -> cout in the forward, cout -> cin in the
+ *            backward-data launch
+ *   K        offsets of the map (1 without one)
+ *   form     how the launch gathers, PCMI_CONV_FORM_*:  NONE no map (dense 1x1);  TABLE the neighbour table (forward of
+ *            a strided map, both directions of a stride-1 map);  TABLE_UNITS the table of a map that carries the sorted
+ *            order and tile units for these rows (perm, nbr_perm, tile_pref, n_tiles == ceil(rows / 128));  PAIRS the
+ *            pair lists (backward-data of a strided map, forward of its transposed convolution)
+ * Out (each nullable):  kernel PCMI_CONV_KERNEL_*;  rows_per_wave: the row tile is 32 x this (0 for spconv32r);  slice: the
+ * output slice of a workgroup is 32 x this channels (0 for spconv32r);  ksplit: offset ranges summed through partial
+ * tensors in the workspace (1 = none);  ws_bytes: the smallest workspace the call accepts (at most
+ * pcmi_spconv_workspace_bytes() of the convolution).  PCMI_ERR_INVALID for a shape no launch has. */
+#define PCMI_CONV_FORM_NONE 0
+#define PCMI_CONV_FORM_TABLE 1
+#define PCMI_CONV_FORM_TABLE_UNITS 2
+#define PCMI_CONV_FORM_PAIRS 3
+#define PCMI_CONV_KERNEL_PAIR 0      /* pair tiles (spconv_mfma_kernel, PAIR) */
+#define PCMI_CONV_KERNEL_32R 1       /* spconv32r_kernel: 32 -> 32 channels, weights resident in LDS */
+#define PCMI_CONV_KERNEL_UNITS_16 2  /* unit-balanced 16-row fp32 (spconv16p_kernel, SK) + sk_fixup_kernel */
+#define PCMI_CONV_KERNEL_UNITS_X3 3  /* unit-balanced split-precision (spconv16x_kernel, SK) + sk_fixup_kernel */
+#define PCMI_CONV_KERNEL_TABLE_X3 4  /* table split-precision (spconv16x_kernel) */
+#define PCMI_CONV_KERNEL_TABLE_16 5  /* table 16-row fp32 (spconv16p_kernel) */
+#define PCMI_CONV_KERNEL_DEEP 6      /* 128-row tiles in 64-channel chunks (spconv_mfma_kernel, KC 64) */
+#define PCMI_CONV_KERNEL_PLAIN 7     /* 128 / 64 / 32-row tiles (spconv_mfma_kernel) */
+int pcmi_spconv_plan(int64_t rows, int64_t x_bytes, int C, int N, int K, int form, int* kernel, int* rows_per_wave,
+                     int* slice, int* ksplit, size_t* ws_bytes);
+
 /* Convolution precision mode.  PCMI_CONV_PRECISION_FP32 (the default) is the arithmetic above.  In
  * PCMI_CONV_PRECISION_BF16 the launches the split-precision kernels take by default -- the forward / backward-data
  * launches of spconv16x (>= 64 channels on both sides, >= 512 rows, table and unit-balanced form) and the weight

@@ -35,6 +35,7 @@
 #include "common.h"
 #include "internal.h"
 #include "spconv_args.h"
+#include "spconv_plan.h"
 
 namespace pcmi {
 
@@ -829,52 +830,8 @@ static int launch_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
   return PCMI_OK;
 }
 
-constexpr int kStreamKDefaultMinTiles = 256;  // unit-balanced launch from 256 tiles (32768 rows); PCMI_SPCONV_STREAMK=0 turns it off
-
-// The switches of the convolution plans, read from the environment once per convolution call and per workspace query
-// (not once per process: the parity tests compare both settings in one process) and handed to everything that plans.
-//   PCMI_SPCONV_STREAMK  minimum number of 128-row tiles for the unit-balanced launch (0 = never)
-//   PCMI_CONV16          the 16-row kernels take the 128-row tiles of levels with at least this many rows (0 = never,
-//                        1 = always).  Default 512 since round 3: with the weights of every layer packed for its level's
-//                        slice width ahead of the launches (x3_plan_nt), the split-precision kernel also wins on the
-//                        coarse levels -- 240 -> 247 pairs/s at 2048, 249 at 512 (profiles/r03e_bench_ab_*.txt); round
-//                        2's 8192 was measured with the fp32 form, which lost below it.
-//   PCMI_CONV16_X3       the split-precision form (spconv_x3.hip: fp32 operands as three bf16 terms on the bf16 matrix
-//                        cores) takes the matrix-bound launches of the 16-row kernel (>= 64 channels on both sides);
-//                        0: the fp32-MFMA kernel
-struct ConvEnv {
-  int64_t sk_min_tiles, conv16_min_rows;
-  bool x3_on;
-};
-static ConvEnv conv_env() {
-  ConvEnv env;
-  const char* e = getenv("PCMI_SPCONV_STREAMK");
-  env.sk_min_tiles = e ? (int64_t)atoll(e) : (int64_t)kStreamKDefaultMinTiles;
-  e = getenv("PCMI_CONV16");
-  env.conv16_min_rows = e ? atoll(e) : 512;
-  e = getenv("PCMI_CONV16_X3");
-  env.x3_on = !e || atoi(e) != 0;
-  return env;
-}
-
 // resident workgroups of the unit-balanced launch (3 or 4 waves per SIMD, see kConv16Waves), multiple of 8
 static int sk_workgroups(int NT = 4) { return kConv16Waves(NT) * num_cu() / 8 * 8; }
-static int sk_workgroups_max() { return 4 * num_cu() / 8 * 8; }
-static bool sk_rows_eligible(const ConvEnv& env, int64_t rows, int K) {
-  const int64_t mt = env.sk_min_tiles;
-  return K > 1 && mt > 0 && rows >= 4096 /* kSortRowsMin: such maps carry tile units */ && ceil_div(rows, 128) >= mt;
-}
-static size_t sk_partial_bytes(const ConvEnv& env, int64_t rows, int N, int K) {
-  return sk_rows_eligible(env, rows, K) ? (size_t)sk_workgroups_max() * 2 * 128 * N * sizeof(float) : 0;
-}
-
-static bool conv16_enabled(const ConvEnv& env, int64_t n_rows, int64_t x_bytes) {
-  const int64_t min_rows = env.conv16_min_rows;
-  // the pipelined form addresses the gathered operand with 32-bit byte offsets (absent = 2^31)
-  return min_rows > 0 && n_rows >= min_rows && x_bytes <= 0x7FFFFF00ll;
-}
-
-static bool conv16_x3(const ConvEnv& env, int NT, int C, int N) { return env.x3_on && NT >= 2 && NT <= 4 && C >= 64 && N >= 64; }
 
 // The calling thread's conv precision mode (include/pcmi.h: pcmi_set_conv_precision).  It decides only the term count of
 // the split-precision launches below (x3_launch) and in spconv_wgrad_x3.hip; every plan -- which kernel, slice width,
@@ -896,20 +853,16 @@ static int launch16(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
   return PCMI_OK;
 }
 
-// 128-row tiles, narrow slices (NT <= 2, levels under 8192 rows): 64-channel chunks when the contraction size allows --
-// twice the matrix work and loads in flight per barrier (NT = 1 keeps 4 waves per SIMD, NT = 2 keeps 3; 128-channel
-// chunks cost a wave per SIMD and lost).  false = not taken.
+// 128-row tiles in 64-channel chunks (plan_conv: PCMI_CONV_KERNEL_DEEP)
 template <bool WT>
-static bool launch_deep(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
-  if (NT == 1 && a.C % 64 == 0) {
-    spconv_mfma_kernel<1, 4, WT, false, 64><<<grid, 256, 0, st>>>(a);
-    return true;
+static int launch_deep(int NT, const ConvArgs& a, dim3 grid, hipStream_t st) {
+  switch (NT) {
+    case 1: spconv_mfma_kernel<1, 4, WT, false, 64><<<grid, 256, 0, st>>>(a); break;
+    case 2: spconv_mfma_kernel<2, 4, WT, false, 64><<<grid, 256, 0, st>>>(a); break;
+    default: set_error("spconv: bad NT %d", NT); return PCMI_ERR_INVALID;
   }
-  if (NT == 2 && a.C % 64 == 0) {
-    spconv_mfma_kernel<2, 4, WT, false, 64><<<grid, 256, 0, st>>>(a);
-    return true;
-  }
-  return false;
+  PCMI_LAUNCH_CHECK();
+  return PCMI_OK;
 }
 
 template <int RW, bool WT, bool PAIR>
@@ -935,85 +888,12 @@ static int launch_rw(int RW, int NT, const ConvArgs& a, dim3 grid, hipStream_t s
   return PCMI_ERR_INVALID;
 }
 
-struct Plan {
-  int RW, NT, ksplit;
-};
-constexpr int kMaxKSplit = 27;
-
-// rows: output rows (or pairs in pair mode); N: output channels; K: offsets.
-// Row tiles stay as large as the row count allows (a tile streams its weight slice once, so small
-// tiles multiply the weight traffic: measured 10-20 TFLOP/s with 32-row tiles on the 256-channel
-// levels); the parallelism the small levels lack comes from splitting the offset range over
-// blockIdx.z into partial sums instead.
-// wide: the contraction has >= 64 channels (with N >= 64 the launch can take the split-precision kernel, whose slices
-// are at least 64 wide)
-// C: the contraction size when the caller knows it (0: the round-2 rule alone)
-static Plan make_plan(const ConvEnv& env, int64_t rows, int N, int K, bool pair, bool wide = false, int C = 0) {
-  Plan p;
-  const int nt_all = N / 32;
-  p.NT = nt_all % 4 == 0 ? 4 : (nt_all % 3 == 0 ? 3 : (nt_all % 2 == 0 ? 2 : 1));
-  p.ksplit = 1;
-  p.RW = rows >= 96 ? 4 : (rows >= 48 ? 2 : 1);
-  if (p.RW == 1 && p.NT > 2) p.NT = (nt_all % 2 == 0) ? 2 : 1;  // the cross-wave reduction lives in LDS
-  // small levels: narrow output slices partition the weights (no extra weight traffic) and multiply the
-  // number of resident workgroups; the re-gathered rows are L2-resident at these sizes
-  const int64_t min16 = env.conv16_min_rows;
-  if (rows < 2048)
-    p.NT = (wide && !pair && K > 1 && N >= 64 && nt_all % 2 == 0 && env.x3_on && min16 > 0 && rows >= min16 && p.RW == 4) ? 2 : 1;
-  else if (rows < 8192 && p.NT > 2)
-    p.NT = (nt_all % 2 == 0) ? 2 : 1;
-  if (!pair && K > 1) {
-    const int64_t wgs = ceil_div(rows, 32 * p.RW) * (nt_all / p.NT);
-    // workgroups aimed at: 2.5 per CU (measured again under the round-3 default: 1.0 -> 240.3, 1.5 -> 247.0, 2.5 -> 249.1,
-    // 4.0 -> 244.6 pairs/s, profiles/r03h_bench_ab_*.txt)
-    const int64_t target = (25 * (int64_t)num_cu()) / 10;
-    if (wgs < target) p.ksplit = (int)std::min<int64_t>(std::min<int64_t>(K, kMaxKSplit), ceil_div(target, wgs));
-    // Round 6: the split by RESIDENCY ROUNDS, for the launches of the 16-row split-precision kernel (whose residency is
-    // known: x3_workgroups).  The kernel's run time is that of its longest workgroup chain: rounds x (offsets per workgroup
-    // x chunks + a fixed share), and "2.5 workgroups per CU" ignores both factors -- on the bench batch it gives the
-    // stride-16 level (28 workgroups per split) ksplit 23, i.e. 4 of the 23 z-slices carry TWO offsets and every launch
-    // takes 16 chunk steps where ksplit 27 takes 8; the stride-4 128-channel launches (79 tiles) ksplit 9 = 711 workgroups
-    // on 512 slots, a full round and a 40 %-filled second one, where ksplit 6 is ONE round.  cost(ks), in chunk
-    // steps: rounds x (ceil(K / ks) C / 32 + 3) x (a penalty under 2 workgroups per CU: nobody hides a step's latency)
-    // + the partial tensors' write + read-back (8 B per element and split at ~3 TB/s against ~2 us per step).  Taken only
-    // when it beats the rule above by 10 % of its own estimate, and only under 16384 rows: on the stride-2 level it picks
-    // ksplit 2, which measured equal in the forward pass and 20 % SLOWER in the backward pass, beside the weight-gradient
-    // stream (profiles/r06d_*: 632 workgroups of 42 steps leave nothing for the other stream to slip into).
-    if (C >= 64 && wide && p.RW == 4 && wgs < target && rows < 16384 && conv16_x3(env, p.NT, C, N) && min16 > 0 && rows >= min16) {
-      const double slots = (double)x3_workgroups(p.NT, 3), nch = (double)(C / kKC);  // (the fp32 mode's plan in both modes)
-      const double traffic = (double)rows * N * 8.0 / 3.0e6 / 2.0;  // chunk steps per partial tensor
-      auto cost = [&](int ks) {
-        const double w = (double)wgs * ks;
-        const double rounds = std::ceil(w / slots);
-        const double thin = std::max(1.0, 2.0 * num_cu() / std::min(w, slots));
-        return rounds * ((double)ceil_div((int64_t)K, (int64_t)ks) * nch + 3.0) * thin + traffic * ks;
-      };
-      int best = p.ksplit;
-      const int kmax = (int)std::min<int64_t>(K, kMaxKSplit);
-      for (int ks = 1; ks <= kmax; ++ks)
-        if (cost(ks) < cost(best) - 1e-9) best = ks;
-      if (cost(best) < 0.9 * cost(p.ksplit)) p.ksplit = best;
-    }
-  }
-  return p;
-}
-
-static size_t partial_bytes(const ConvEnv& env, int64_t rows, int N, int K) {
-  if (K <= 1 || rows <= 0 || N % 32 != 0) return 0;
-  int ks = std::max(make_plan(env, rows, N, K, false, false).ksplit, make_plan(env, rows, N, K, false, true).ksplit);
-  for (int C = 64; C <= 512; C += 32) ks = std::max(ks, make_plan(env, rows, N, K, false, true, C).ksplit);  // (any contraction size)
-  return ks > 1 ? (size_t)ks * rows * N * sizeof(float) : 0;
-}
-
 // Output slice width (units of 32 channels) of the table launch over `rows` output rows if it takes the split-precision
 // kernel, else 0: what the executor packs the weights for ahead of the launches (engine.hip: x3_prepack).
 int x3_plan_nt(int64_t rows, int C, int N, int K) {
-  const ConvEnv env = conv_env();
-  if (C % 32 != 0 || N % 32 != 0 || C < 64 || N < 64 || K <= 1 || !env.x3_on) return 0;
-  const Plan p = make_plan(env, rows, N, K, false, true);
-  const int64_t min16 = env.conv16_min_rows;
-  if (p.RW != 4 || min16 <= 0 || rows < min16) return 0;
-  return conv16_x3(env, p.NT, C, N) ? p.NT : 0;
+  if (C % 32 != 0 || N % 32 != 0 || C < 64 || N < 64 || K <= 1) return 0;
+  const ConvPlan p = plan_conv(conv_env(), rows, 0, C, N, K, PCMI_CONV_FORM_TABLE);
+  return p.kernel == PCMI_CONV_KERNEL_TABLE_X3 ? p.NT : 0;
 }
 
 // One gathered GEMM:  out[rows, N] = sum_k x[idx_k(rows)] @ B_k
@@ -1029,8 +909,7 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
                    ((uintptr_t)out % 16 == 0),
                PCMI_ERR_INVALID, "spconv: operands must be 16-byte aligned with ld %% 4 == 0");
   if (n_rows == 0) return PCMI_OK;
-  const ConvEnv env = conv_env();
-  ConvArgs a;
+  ConvArgs a = {};  // (no permutation, no pair lists, no unit tables, no packed weights: set below where the plan wants them)
   a.x = x;
   a.x_ld = x_ld;
   a.C = C;
@@ -1048,100 +927,72 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
   for (int k = 0; k < PCMI_MAX_KERNEL_VOLUME; ++k) a.wsel[k] = wsel ? wsel[k] : k;
   a.n_rows = n_rows;
   a.bias = bias;
-  a.nbr = nullptr;
-  a.perm = nullptr;
-  a.pair_src = a.pair_dst = nullptr;
-  a.offs = nullptr;
+  a.nbr = !map || pair_mode ? nullptr : map->nbr;
   a.ksplit = 1;
-  a.split_stride = 0;
-  a.xcd_tiles = 0;
   a.accumulate = accumulate;
   a.out = out;
   a.out_ld = out_ld;
-  a.sk_mask = nullptr;
-  a.sk_pref = nullptr;
-  a.sk_tiles = 0;
-  a.sk_part = nullptr;
-  a.wpack = nullptr;
-  if (pair_mode) {
-    a.pair_src = swap_pairs ? map->pair_in : map->pair_out;
-    a.pair_dst = swap_pairs ? map->pair_out : map->pair_in;
-    a.offs = map->offs;
-    Plan p = make_plan(env, n_rows, N, a.K, true);
-    const int TM = 32 * p.RW;
-    // tiles of all offsets: exact when the map's counts are on the host, else their bound (every pair is one fine row
-    // and every offset adds at most one ragged tile); a workgroup past the last tile leaves at once
-    int64_t tiles = 0;
-    if (map->M >= 0)
-      for (int k = 0; k < a.K; ++k) tiles += ceil_div(map->offs_host[k + 1] - map->offs_host[k], TM);
-    else
-      tiles = ceil_div(kmap_pairs_bound(*map), TM) + a.K;
-    if (tiles == 0) return PCMI_OK;
-    dim3 grid((unsigned)tiles, (unsigned)(N / (32 * p.NT)), 1);
-    return w_transposed ? launch_rw<true, true>(p.RW, p.NT, a, grid, st)
-                        : launch_rw<false, true>(p.RW, p.NT, a, grid, st);
-  }
-  a.nbr = map ? map->nbr : nullptr;
-  if (map && map->perm && map->nbr_perm) {  // same results, rows visited in mask-sorted order
+  int form = !map ? PCMI_CONV_FORM_NONE : pair_mode ? PCMI_CONV_FORM_PAIRS : PCMI_CONV_FORM_TABLE;
+  if (form == PCMI_CONV_FORM_TABLE && map->perm && map->nbr_perm) {  // same results, rows visited in mask-sorted order
     a.nbr = map->nbr_perm;
     a.perm = map->perm;
+    if (map->tile_pref && map->n_tiles == ceil_div(n_rows, 128)) form = PCMI_CONV_FORM_TABLE_UNITS;
   }
-  // 32 -> 32 channels: all weight slices resident in LDS, a wave per 16-row group (spconv32r.hip)
-  if (conv32r_eligible(a, x_rows * x_ld * 4)) return conv32r_launch(w_transposed, a, st);
-  Plan p = make_plan(env, n_rows, N, a.K, false, C >= 64, C);
-  // (32-channel convs are HBM/latency-bound: the partial tiles cost them more than the balance gains -- measured)
-  // (the unit-balanced launch exists for the 16-row kernels: an operand of >= 2 GiB, which they cannot address, takes the
-  //  whole-tile launch of spconv_mfma_kernel below)
-  // (Round 6 measured this launch also on the levels that split their offsets over blockIdx.z -- ksplit > 1: the stride-2 level
-  //  of the bench batch, 316 tiles, neutral; the stride-4 level as well, 78 tiles cut into 3-10 pieces each, 0.5 ms per step
-  //  SLOWER: profiles/r06a_wgrad_stream_cost_and_sk_mid_ab.txt.  The offset split + split_reduce_kernel stays there.)
-  if (map && map->tile_pref && map->perm && p.RW == 4 && p.ksplit == 1 && sk_rows_eligible(env, n_rows, a.K) &&
-      map->n_tiles == ceil_div(n_rows, 128) && C >= 64 && N >= 64 && conv16_enabled(env, n_rows, x_rows * x_ld * 4)) {
-    const bool x3 = conv16_x3(env, p.NT, C, N);
-    const int terms = conv_terms();
-    const int G = x3 ? x3_workgroups(p.NT, terms) : sk_workgroups(p.NT);  // (<= sk_workgroups_max: the partial tiles fit)
-    const size_t part = sk_partial_bytes(env, n_rows, N, a.K);
-    const size_t need = part + (x3 ? x3_pack_bytes(a.K, C, N) : 0);
-    PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "spconv: workspace %zu < %zu bytes", ws_bytes, need);
-    a.sk_mask = map->tile_mask;
-    a.sk_pref = map->tile_pref;
-    a.sk_tiles = (int)map->n_tiles;
-    a.sk_part = (float*)ws;
-    dim3 grid((unsigned)G, (unsigned)(N / (32 * p.NT)), 1);
-    int rc;
-    if (x3) {
-      a.wpack = x3_find_prepacked(w, w_transposed, p.NT, terms);  // the executor's once-per-pass pack, if there is one
-      rc = PCMI_OK;
-      if (!a.wpack) {
-        a.wpack = (char*)ws + part;
-        rc = x3_pack_weights(a, p.NT, const_cast<void*>(a.wpack), st, terms);
-      }
-      if (rc == PCMI_OK) rc = x3_launch(p.NT, true, a, grid, st, terms);
-    } else
-      rc = w_transposed ? launch16<true, true>(p.NT, a, grid, st) : launch16<false, true>(p.NT, a, grid, st);
-    if (rc) return rc;
-    const int sub = C / kKC;  // the shares of both kernels are counted in chunk steps
-    sk_fixup_kernel<<<dim3((unsigned)a.sk_tiles), 256, 0, st>>>(a.sk_part, a.sk_pref, a.sk_tiles, G, a.perm, n_rows, N, bias,
-                                                              out, out_ld, accumulate, sub);
-    PCMI_LAUNCH_CHECK();
-    return PCMI_OK;
-  }
-  const bool x3 = p.RW == 4 && map && conv16_enabled(env, n_rows, x_rows * x_ld * 4) && conv16_x3(env, p.NT, C, N);
+  const ConvPlan p = plan_conv(conv_env(), n_rows, x_rows * x_ld * 4, C, N, a.K, form);
+  PCMI_REQUIRE(p.ws_bytes == 0 || (ws && ws_bytes >= p.ws_bytes), PCMI_ERR_WORKSPACE, "spconv: workspace %zu < %zu bytes",
+               ws_bytes, p.ws_bytes);
   const int terms = conv_terms();
-  const size_t split_bytes = p.ksplit > 1 ? align_up((size_t)p.ksplit * n_rows * N * sizeof(float), 256) : 0;
-  if (x3) {
-    PCMI_REQUIRE(ws && ws_bytes >= split_bytes + x3_pack_bytes(a.K, C, N), PCMI_ERR_WORKSPACE,
-                 "spconv: workspace %zu < %zu bytes", ws_bytes, split_bytes + x3_pack_bytes(a.K, C, N));
-    a.wpack = x3_find_prepacked(w, w_transposed, p.NT, terms);
+  if (p.pack_bytes) {
+    a.wpack = x3_find_prepacked(w, w_transposed, p.NT, terms);  // the executor's once-per-pass pack, if there is one
     if (!a.wpack) {
-      a.wpack = (char*)ws + split_bytes;
+      a.wpack = (char*)ws + p.pack_offset;
       const int rc_pack = x3_pack_weights(a, p.NT, const_cast<void*>(a.wpack), st, terms);
       if (rc_pack) return rc_pack;
     }
   }
+  int rc;
+  switch (p.kernel) {
+    case PCMI_CONV_KERNEL_PAIR: {
+      a.pair_src = swap_pairs ? map->pair_in : map->pair_out;
+      a.pair_dst = swap_pairs ? map->pair_out : map->pair_in;
+      a.offs = map->offs;
+      const int TM = 32 * p.RW;
+      // tiles of all offsets: exact when the map's counts are on the host, else their bound (every pair is one fine row
+      // and every offset adds at most one ragged tile); a workgroup past the last tile leaves at once
+      int64_t tiles = 0;
+      if (map->M >= 0)
+        for (int k = 0; k < a.K; ++k) tiles += ceil_div(map->offs_host[k + 1] - map->offs_host[k], TM);
+      else
+        tiles = ceil_div(kmap_pairs_bound(*map), TM) + a.K;
+      if (tiles == 0) return PCMI_OK;
+      dim3 grid((unsigned)tiles, (unsigned)(N / (32 * p.NT)), 1);
+      return w_transposed ? launch_rw<true, true>(p.RW, p.NT, a, grid, st) : launch_rw<false, true>(p.RW, p.NT, a, grid, st);
+    }
+    case PCMI_CONV_KERNEL_32R:
+      return conv32r_launch(w_transposed, a, st);
+    case PCMI_CONV_KERNEL_UNITS_16:
+    case PCMI_CONV_KERNEL_UNITS_X3: {
+      const bool x3 = p.kernel == PCMI_CONV_KERNEL_UNITS_X3;
+      const int G = x3 ? x3_workgroups(p.NT, terms) : sk_workgroups(p.NT);  // (<= sk_workgroups_max: the partial tiles fit)
+      a.sk_mask = map->tile_mask;
+      a.sk_pref = map->tile_pref;
+      a.sk_tiles = (int)map->n_tiles;
+      a.sk_part = (float*)ws;
+      dim3 grid((unsigned)G, (unsigned)(N / (32 * p.NT)), 1);
+      if (x3)
+        rc = x3_launch(p.NT, true, a, grid, st, terms);
+      else
+        rc = w_transposed ? launch16<true, true>(p.NT, a, grid, st) : launch16<false, true>(p.NT, a, grid, st);
+      if (rc) return rc;
+      const int sub = C / kKC;  // the shares of both kernels are counted in chunk steps
+      sk_fixup_kernel<<<dim3((unsigned)a.sk_tiles), 256, 0, st>>>(a.sk_part, a.sk_pref, a.sk_tiles, G, a.perm, n_rows, N, bias,
+                                                                out, out_ld, accumulate, sub);
+      PCMI_LAUNCH_CHECK();
+      return PCMI_OK;
+    }
+  }
+  // the tile-per-workgroup launches: offsets split over blockIdx.z write partial tensors, summed by split_reduce_kernel
   if (p.ksplit > 1) {
-    const size_t need = (size_t)p.ksplit * n_rows * N * sizeof(float);
-    PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "spconv: workspace %zu < %zu bytes", ws_bytes, need);
     a.ksplit = p.ksplit;
     a.split_stride = n_rows * N;
     a.out = (float*)ws;
@@ -1155,16 +1006,14 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
     tiles = (int64_t)a.xcd_tiles * 8;
   }
   dim3 grid((unsigned)tiles, (unsigned)(N / (32 * p.NT)), (unsigned)p.ksplit);
-  int rc;
-  if (x3) {
-    rc = x3_launch(p.NT, false, a, grid, st, terms);
-  } else if (p.RW == 4 && conv16_enabled(env, n_rows, x_rows * x_ld * 4)) {
-    rc = w_transposed ? launch16<true, false>(p.NT, a, grid, st) : launch16<false, false>(p.NT, a, grid, st);
-  } else if (p.RW == 4 && (w_transposed ? launch_deep<true>(p.NT, a, grid, st) : launch_deep<false>(p.NT, a, grid, st))) {
-    rc = PCMI_OK;
-    PCMI_LAUNCH_CHECK();
-  } else
-    rc = w_transposed ? launch_rw<true, false>(p.RW, p.NT, a, grid, st) : launch_rw<false, false>(p.RW, p.NT, a, grid, st);
+  switch (p.kernel) {
+    case PCMI_CONV_KERNEL_TABLE_X3: rc = x3_launch(p.NT, false, a, grid, st, terms); break;
+    case PCMI_CONV_KERNEL_TABLE_16:
+      rc = w_transposed ? launch16<true, false>(p.NT, a, grid, st) : launch16<false, false>(p.NT, a, grid, st);
+      break;
+    case PCMI_CONV_KERNEL_DEEP: rc = w_transposed ? launch_deep<true>(p.NT, a, grid, st) : launch_deep<false>(p.NT, a, grid, st); break;
+    default: rc = w_transposed ? launch_rw<true, false>(p.RW, p.NT, a, grid, st) : launch_rw<false, false>(p.RW, p.NT, a, grid, st);
+  }
   if (rc) return rc;
   if (p.ksplit > 1) {
     const int64_t n4 = n_rows * (N / 4);
@@ -1177,7 +1026,16 @@ static int run_gathered(const float* x, int64_t x_ld, int64_t x_rows, int C, con
 
 size_t spconv_fwd_bwd_workspace(int64_t n_in, int64_t n_out, int cin, int cout, int K) {
   const ConvEnv env = conv_env();
-  const size_t ks = std::max(partial_bytes(env, n_out, cout, K), partial_bytes(env, n_in, cin, K));
+  // the partial tensors of the forward (rows n_out, contracting cin) and the backward-data launch (rows n_in, contracting
+  // cout).  The query knows neither `transpose` nor the operands' strides, so it covers what a caller could bring: the
+  // table form with an operand under and over 2 GiB (over it spconv32r is out and its shapes split); the pair form and
+  // the dense one never split.  (Channel counts that are no multiples of 32 never reach run_gathered: the stem, widths.hip.)
+  auto split = [&](int64_t rows, int C, int N) -> size_t {
+    if (rows <= 0 || C % 32 != 0 || N % 32 != 0) return 0;
+    return std::max(plan_conv(env, rows, 0, C, N, K, PCMI_CONV_FORM_TABLE).split_bytes,
+                    plan_conv(env, rows, INT64_MAX, C, N, K, PCMI_CONV_FORM_TABLE).split_bytes);
+  };
+  const size_t ks = std::max(split(n_out, cin, cout), split(n_in, cout, cin));
   const size_t sk = n_in == n_out ? std::max(sk_partial_bytes(env, n_out, cout, K), sk_partial_bytes(env, n_in, cin, K)) : 0;
   // the packed weights of the split-precision form sit behind the partial tiles (whether or not it is switched on:
   // <= 10.6 MB for the widest layer)
@@ -1272,6 +1130,20 @@ int pcmi_spconv_bwd_data(const float* gout, int64_t gout_ld, int64_t n_out, int 
 }
 
 int pcmi_spconv_split_precision(void) { return conv_env().x3_on ? 1 : 0; }
+
+int pcmi_spconv_plan(int64_t rows, int64_t x_bytes, int C, int N, int K, int form, int* kernel, int* rows_per_wave, int* slice,
+                     int* ksplit, size_t* ws_bytes) {
+  PCMI_REQUIRE(rows > 0 && x_bytes >= 0 && C > 0 && N > 0 && C % 32 == 0 && N % 32 == 0 && K >= 1 && K <= PCMI_MAX_KERNEL_VOLUME &&
+                   form >= PCMI_CONV_FORM_NONE && form <= PCMI_CONV_FORM_PAIRS && (form != PCMI_CONV_FORM_NONE || K == 1),
+               PCMI_ERR_INVALID, "spconv_plan: bad shape (%lld rows, %d -> %d, K %d, form %d)", (long long)rows, C, N, K, form);
+  const ConvPlan p = plan_conv(conv_env(), rows, x_bytes, C, N, K, form);
+  if (kernel) *kernel = p.kernel;
+  if (rows_per_wave) *rows_per_wave = p.RW;
+  if (slice) *slice = p.NT;
+  if (ksplit) *ksplit = p.ksplit;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  return PCMI_OK;
+}
 
 int pcmi_set_conv_precision(int precision) {
   PCMI_REQUIRE(precision == PCMI_CONV_PRECISION_FP32 || precision == PCMI_CONV_PRECISION_BF16, PCMI_ERR_INVALID,

@@ -172,16 +172,9 @@ __global__ __launch_bounds__(kR32Waves * 64, 1) void spconv32r_kernel(ConvArgs a
   }
 }
 
-// PCMI_CONV32R: minimum number of output rows for this kernel (0 = never).  Read per call (parity tests compare both).
-static int64_t conv32r_min_rows() {
-  const char* e = getenv("PCMI_CONV32R");
-  return e ? (int64_t)atoll(e) : (int64_t)8192;
-}
-
-bool conv32r_eligible(const ConvArgs& a, int64_t x_bytes) {
-  const int64_t mr = conv32r_min_rows();
-  return mr > 0 && a.n_rows >= mr && a.C == 32 && a.N == 32 && a.nbr && a.K > 1 && a.K <= 27 && x_bytes <= 0x7FFFFF00ll &&
-         (a.w_sn == 1 || a.w_sc == 1);
+// min_rows: PCMI_CONV32R, the minimum number of output rows for this kernel (0 = never; spconv_plan.h: ConvEnv)
+bool conv32r_eligible(int64_t min_rows, int64_t rows, int64_t x_bytes, int C, int N, int K, bool table) {
+  return min_rows > 0 && rows >= min_rows && C == 32 && N == 32 && table && K > 1 && K <= 27 && x_bytes <= 0x7FFFFF00ll;
 }
 
 int conv32r_launch(bool w_transposed, const ConvArgs& a, hipStream_t st) {

@@ -54,7 +54,7 @@ int x3_workgroups(int NT, int terms);
 int x3_plan_nt(int64_t rows, int C, int N, int K);
 
 // ---- spconv32r.hip: 32 -> 32 channel table convolutions with the weights resident in LDS ---------------------------
-bool conv32r_eligible(const ConvArgs& a, int64_t x_bytes);  // a.nbr / a.perm / a.K / a.n_rows set
+bool conv32r_eligible(int64_t min_rows, int64_t rows, int64_t x_bytes, int C, int N, int K, bool table);  // table: gathers through a neighbour table
 int conv32r_launch(bool w_transposed, const ConvArgs& a, hipStream_t st);
 
 // ---- weights packed ahead of the launches (the network executor packs every eligible layer in ONE launch per forward

@@ -9,7 +9,7 @@ that form:
     never a fault, since the bands lie inside the same allocation);
   - inputs and outputs as [rows, c] slices of [rows, ld] buffers filled with a NaN sentinel: everything outside the
     slice must still hold the sentinel's bits afterwards;
-  - row counts one either side of every threshold where the planners (csrc/spconv.hip make_plan / run_gathered,
+  - row counts one either side of every threshold where the planners (csrc/spconv_plan.h plan_conv,
     csrc/spconv_wgrad.hip, csrc/norm.hip) change kernel, tile shape, slice width or reduction form.
 
 Criteria: none is new.  Convolutions: test_gpu_parity.py's (max|err| <= 1e-4 * max|ref|; feature / input-gradient
@@ -92,6 +92,20 @@ def _ok(lib, rc, what):
 
 def _dev(t):
   return t.to(DEV).contiguous()
+
+
+# include/pcmi.h: PCMI_CONV_FORM_* and PCMI_CONV_KERNEL_*
+FORM_NONE, FORM_TABLE, FORM_TABLE_UNITS, FORM_PAIRS = range(4)
+KERNEL_NAMES = ("pair", "32r", "units_16", "units_x3", "table_x3", "table_16", "deep", "plain")
+
+
+def _planned(lib, rows, x_bytes, c, n, k, form):
+  """pcmi_spconv_plan: (kernel, row tile / 32, slice width / 32, ksplit, ws_bytes) of one forward / backward-data launch."""
+  o = [C.c_int() for _ in range(4)]
+  ws = C.c_size_t()
+  rc = lib.pcmi_spconv_plan(rows, x_bytes, c, n, k, form, *[C.byref(v) for v in o], C.byref(ws))
+  assert rc == PCMI_OK, lib.pcmi_last_error().decode()
+  return tuple(v.value for v in o) + (ws.value,)
 
 
 class _Maps:
@@ -193,7 +207,7 @@ def _conv_contract(lib, maps, kind, cin, cout, forms=(0, 1), also_without_gbias=
 # ------------------------------------------------------------------------------------------------
 # A. convolution at every plan edge
 # ------------------------------------------------------------------------------------------------
-# make_plan / run_gathered thresholds: 48 and 96 rows (rows per wave), 512 (PCMI_CONV16 default: the 16-row kernels and
+# plan_conv's thresholds: 48 and 96 rows (rows per wave), 512 (PCMI_CONV16 default: the 16-row kernels and
 # the split-precision form), 2048 (slice width), 4096 (tile units: the unit-balanced launch), 8192 (slice width; the
 # weight gradient's wgrad_x3t), 16384 (the residency-round split).  Every row count keeps the narrow 32 -> 32 pair
 # (spconv32r), one wide pair that is eligible for the split-precision kernel, and one pair with an odd N / 32 on one
@@ -255,23 +269,24 @@ WIDE_CASES = [("k3", 544, 192, 12800, "mid", 12800), ("k3", 192, 544, 12800, "mi
 
 @pytest.mark.parametrize("kind,cin,cout,n,base,rows", WIDE_CASES)
 def test_workspace_query_covers_contractions_wider_than_512(lib, kind, cin, cout, n, base, rows):
-  """partial_bytes() in csrc/spconv.hip bounds the offset split of the forward / backward-data launch by sampling
-  contraction sizes 64..512, while run_gathered plans with the real one; for these shapes (3^3 stride-1 544 -> 192 at
-  12800 rows, whose forward contracts 544 channels, and its mirror 192 -> 544, whose backward-data does; stride-2
-  768 -> 128 onto 13092 coarse rows and the transposed 128 -> 768 from them) a restatement of make_plan finds a planned
-  split above the sampled bound.  pcmi_spconv_workspace_bytes is the maximum of that term and the weight gradient's
-  slab term (csrc/spconv_wgrad.hip: spconv_wgrad_workspace), and this test holds the COMBINED query to its word: every
-  call gets exactly the queried bytes between guard bands.
+  """The forward / backward-data term of the workspace query (csrc/spconv.hip: spconv_fwd_bwd_workspace) asks plan_conv
+  for the offset split at the REAL contraction size, as run_gathered does, so the forward's own term covers these shapes:
+  3^3 stride-1 544 -> 192 at 12800 rows, whose forward contracts 544 channels, and its mirror 192 -> 544, whose
+  backward-data does; stride-2 768 -> 128 onto 13092 coarse rows and the transposed 128 -> 768 from them.  (It used to
+  sample contraction sizes 64..512 and fell short of the planned split here -- 4 partial tensors against 7, 7 against 8 --
+  and the query held only through the weight gradient's larger term.)  pcmi_spconv_workspace_bytes is the maximum of that
+  term and the weight gradient's slab term (csrc/spconv_wgrad.hip: spconv_wgrad_workspace), and this test holds the
+  COMBINED query to its word: every call gets exactly the queried bytes between guard bands;
+  tests/test_conv_plan.py holds the query against the plan's own requirement on the CPU.
 
   Observed on an MI355X (256 CUs, default environment; the smallest ws_bytes each call accepts, found by bisection over
-  its PCMI_ERR_WORKSPACE returns): the sampled bound IS short and the weight gradient's term carries the query.
+  its PCMI_ERR_WORKSPACE returns):
     3^3 544 -> 192, 12800 rows: forward needs 85 733 376 B (7 partial tensors of 9 830 400 B + 16 920 576 B of packed
-      weights; the sampled bound of 4 gives 56 242 176 B), the weight gradient 564 805 632 B, the query is 564 805 888 B;
+      weights), the weight gradient 564 805 632 B, the query is 564 805 888 B;
       192 -> 544: the same 85 733 376 B in backward-data, query 566 247 680 B.
-    2^3 stride-2 768 -> 128 onto 13092 rows: forward needs 58 343 424 B (8 partial tensors of 6 703 104 B + 4 718 592 B;
-      the sampled bound of 7 gives 51 640 320 B), the weight gradient 57 147 392 B, the query is 164 102 400 B (its
-      chunk-slot bound); transposed 128 -> 768: the same 58 343 424 B in backward-data, query 166 723 840 B.
-  If the weight gradient's bound is ever tightened below the forward's need, this test is what fails."""
+    2^3 stride-2 768 -> 128 onto 13092 rows: forward needs 58 343 424 B (8 partial tensors of 6 703 104 B + 4 718 592 B),
+      the weight gradient 57 147 392 B, the query is 164 102 400 B (its chunk-slot bound); transposed 128 -> 768: the
+      same 58 343 424 B in backward-data, query 166 723 840 B."""
   maps = _maps(n, base)
   m = maps.get(kind)[0]
   assert rows in (int(m.n_in), int(m.n_out))

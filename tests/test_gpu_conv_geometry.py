@@ -18,9 +18,9 @@ import pytest
 import torch
 
 import geometry_cases as gc
-from c_contract import DEV, Guarded, conv_ref64, lds, strided
-from test_gpu_c_contract import (TOL, _Maps, _conv_contract, _conv_inputs, _dev, _ok, _stream, _vp, assert_close,
-                                 assert_rows_close, assert_slices_close)
+from c_contract import DEV, GUARD_BYTE, PCMI_ERR_WORKSPACE, Guarded, conv_ref64, lds, strided
+from test_gpu_c_contract import (FORM_PAIRS, FORM_TABLE, FORM_TABLE_UNITS, KERNEL_NAMES, TOL, _Maps, _conv_contract, _conv_inputs,
+                                 _dev, _maps, _ok, _planned, _stream, _vp, assert_close, assert_rows_close, assert_slices_close)
 from test_gpu_parity import _check_maps, _make_models
 from test_gpu_pretrain_edges import _read_i32
 
@@ -305,14 +305,15 @@ SK_CASES = [("iso11776", 224, 224, "16"), ("mixed20", 224, 224, "16"), ("mixed20
 
 
 @pytest.mark.parametrize("which,cin,cout,streamk", SK_CASES)
-def test_unit_balanced_launch_on_extreme_tiles(ME, which, cin, cout, streamk, monkeypatch):
+def test_unit_balanced_launch_on_extreme_tiles(lib, ME, which, cin, cout, streamk, monkeypatch):
   """Forward and backward-data through the unit-balanced launch against float64 from the oracle's neighbour table, rows
   at 1e-4, and against the one-tile-per-workgroup launch (PCMI_SPCONV_STREAMK=0) at
-  test_full_size_streamk_matches_plain's 1e-5.  No API reports which launch was taken.  A kernel trace of this test
-  alone (MI355X, 256 CUs) showed it: 20 launches of sk_fixup_kernel = 5 cases x 2 calls x (forward, backward-data), 12 of
+  test_full_size_streamk_matches_plain's 1e-5.  pcmi_spconv_plan reports which launch is taken: a unit-balanced kernel
+  in the first mode, a table kernel in the second, no offset split in either.  A kernel trace of this test
+  alone (MI355X, 256 CUs) showed the same: 20 launches of sk_fixup_kernel = 5 cases x 2 calls x (forward, backward-data), 12 of
   spconv16p_kernel<1, ., SK = true> and 16 of spconv16x_kernel<2, SK = true, ., 3> (8 per direction), against 12 + 16 of
-  the SK = false forms in the plain mode and no split_reduce_kernel.  Since then the test holds it itself: the shapes
-  are checked against make_plan's rule with the device's CU count, and wherever a tile is cut between workgroups the two
+  the SK = false forms in the plain mode and no split_reduce_kernel.  The test also holds it itself: the shapes
+  are checked against plan_conv's rule with the device's CU count, and wherever a tile is cut between workgroups the two
   modes must NOT be bit-equal (another summation order).  iso81920 is the exception: 1280 chunk steps over the 768
   workgroups of spconv16x_kernel<2> are 2 each = exactly one tile, so 640 workgroups write whole tiles, 128 return at
   once, the fix-up kernel finds nothing to sum and the result is bit-equal to the plain launch (observed)."""
@@ -321,8 +322,8 @@ def test_unit_balanced_launch_on_extreme_tiles(ME, which, cin, cout, streamk, mo
   coords = _sk_cloud(which)
   n = len(coords)
   n_tiles = -(-n // 128)
-  nt = 1 if cout == 224 else 2  # make_plan: N / 32 = 7 -> NT 1; N / 32 = 2 -> NT 2
-  target = 25 * torch.cuda.get_device_properties(0).multi_processor_count // 10  # make_plan: 2.5 workgroups per CU
+  nt = 1 if cout == 224 else 2  # plan_conv: N / 32 = 7 -> NT 1; N / 32 = 2 -> NT 2
+  target = 25 * torch.cuda.get_device_properties(0).multi_processor_count // 10  # plan_conv: 2.5 workgroups per CU
   # ksplit == 1, forward and backward-data alike (on a part with more CUs the shapes must grow: this then fails)
   assert cin == cout and n_tiles * (cout // 32 // nt) >= target, (n_tiles, target)
   rm = _oracle(coords).kernel_map(0, 0, 3, sr.HYBRID)
@@ -356,6 +357,10 @@ def test_unit_balanced_launch_on_extreme_tiles(ME, which, cin, cout, streamk, mo
       monkeypatch.setenv("PCMI_SPCONV_STREAMK", "0")
     elif streamk is not None:
       monkeypatch.setenv("PCMI_SPCONV_STREAMK", streamk)
+    # forward and backward-data are one plan (cin == cout, the same rows and map)
+    kernel, _, slice_, ksplit, _ = _planned(lib, n, n * cin * 4, cin, cout, 27, FORM_TABLE_UNITS)
+    want = ("units_16", "units_x3") if mode == "sk" else ("table_16", "table_x3")
+    assert KERNEL_NAMES[kernel] in want and ksplit == 1 and slice_ == nt, (which, mode, KERNEL_NAMES[kernel], slice_, ksplit)
     for rep in range(2):
       x = x0.clone().requires_grad_(True)
       y = PF.SparseConvFunction.apply(x, W, b, m, False, n, cm)
@@ -375,6 +380,64 @@ def test_unit_balanced_launch_on_extreme_tiles(ME, which, cin, cout, streamk, mo
     assert same == (which == "iso81920"), "%s %s: PCMI_SPCONV_STREAMK did not switch launches as expected" % (which, nm)
   assert_close(res[("sk", 0)][0], res[("0", 0)][0], 1e-5, which + " unit-balanced forward vs plain")
   assert_close(res[("sk", 0)][1], res[("0", 0)][1], 1e-5, which + " unit-balanced backward-data vs plain")
+
+
+# ------------------------------------------------------------------------------------------------
+# d2. every kernel family with exactly the workspace its plan names
+# ------------------------------------------------------------------------------------------------
+# (planned kernel, rows of test_gpu_c_contract's voxel set or a cloud of _sk_cloud, map, cin, cout, PCMI_SPCONV_STREAMK)
+PLAN_CASES = [("pair", 530, "up", 128, 64, None), ("deep", 256, "k3", 64, 64, None), ("plain", 47, "k3", 64, 64, None),
+              ("table_16", 512, "k3", 32, 64, None), ("table_x3", 512, "k3", 64, 64, None), ("32r", 8192, "k3", 32, 32, None),
+              ("units_16", "iso11776", "k3", 224, 224, "16"), ("units_x3", "iso81920", "k3", 64, 64, None)]
+
+
+@pytest.mark.parametrize("family,cloud,kind,cin,cout,streamk", PLAN_CASES)
+def test_forward_accepts_exactly_the_planned_workspace(lib, family, cloud, kind, cin, cout, streamk, monkeypatch):
+  """One forward per kernel family of plan_conv (csrc/spconv_plan.h): pcmi_spconv_plan names the family the case is meant
+  for (asserted first: a wrong shape fails, it does not pass vacuously) and the smallest workspace the call accepts.  With
+  exactly that many bytes between guard bands the call succeeds and matches float64 at TOL; with one byte less it returns
+  PCMI_ERR_WORKSPACE and writes nothing (a refused call enqueues nothing).  The pair tiles and spconv32r use no workspace:
+  their plan says 0 bytes and there is no shorter call."""
+  if streamk is not None:
+    monkeypatch.setenv("PCMI_SPCONV_STREAMK", streamk)
+  if isinstance(cloud, str):
+    coords = _sk_cloud(cloud)
+    maps = _Maps(len(coords), coords=coords)
+  else:
+    maps = _maps(cloud)
+  m, tr, n_in, n_out, pin, pout, offs = maps.get(kind)
+  K = m.K
+  (ild, ioff), (old, ooff) = lds(cin, 0), lds(cout, 0)
+  units = bool(m.tile_pref and m.perm and m.nbr_perm) and m.n_tiles == -(-n_out // 128)
+  form = FORM_PAIRS if tr else (FORM_TABLE_UNITS if units else FORM_TABLE)
+  kernel, _, _, ksplit, need = _planned(lib, n_out, n_in * ild * 4, cin, cout, K, form)
+  assert KERNEL_NAMES[kernel] == family, (KERNEL_NAMES[kernel], n_in, n_out, K, form)
+  if family == "plain":
+    assert ksplit == 27
+  assert (need == 0) == (family in ("pair", "32r")), need
+  x, W, bias, _ = _conv_inputs(n_in, n_out, cin, cout, K, 11 + n_in)
+  ref = conv_ref64(x, W, pin, pout, offs, n_out, transpose=bool(tr), bias=bias)
+  Wd, bd = _dev(W), _dev(bias)
+  ws = Guarded(need)
+  xin, out = strided(n_in, cin, ild, ioff, x), strided(n_out, cout, old, ooff)
+  st = _stream()
+  tag = "%s %s %d->%d rows %d" % (family, kind, cin, cout, n_out)
+
+  def fwd(nbytes):
+    return lib.pcmi_spconv_fwd(xin.vp, ild, n_in, cin, _vp(Wd), cout, C.byref(m), tr, _vp(bd), out.vp, old, n_out, ws.vp,
+                               C.c_size_t(nbytes), st)
+
+  if need > 0:
+    rc = fwd(need - 1)
+    torch.cuda.synchronize()
+    assert rc == PCMI_ERR_WORKSPACE, "%s: one byte short returned %d (%s)" % (tag, rc, lib.pcmi_last_error().decode())
+    assert out.untouched(), tag + ": the refused call wrote into the output"
+    assert bool((ws.buf == GUARD_BYTE).all()), tag + ": the refused call wrote into the workspace"
+  _ok(lib, fwd(need), tag + " fwd with the planned %d bytes" % need)
+  ws.check(tag + " workspace (%d bytes planned)" % need)
+  out.check(tag + " out")
+  xin.check(tag + " in")
+  assert_rows_close(out.cpu(), ref, TOL, tag + " out")
 
 
 # ------------------------------------------------------------------------------------------------
