@@ -1231,6 +1231,12 @@ int pcmi_net_stream_wait_bucket(pcmi_net_t* net, pcmi_stream_t stream);
 /* The convolution precision mode (PCMI_CONV_PRECISION_*, see pcmi_set_conv_precision) of every later forward and backward
  * pass of `net`; a backward pass uses the mode set when it is called.  Default fp32.  PCMI_ERR_INVALID for other values. */
 int pcmi_net_set_conv_precision(pcmi_net_t* net, int precision);
+/* Applies, on `stream` (ordered behind that forward), the running-estimate updates a forward of `pass` with
+ * PCMI_NET_DEFER_RUNNING_STATS left pending, once; with nothing pending it does nothing.  While they are pending the pass
+ * is closed: pcmi_net_forward of the same pass, in any mode, returns PCMI_ERR_INVALID before it enqueues or changes
+ * anything (it would overwrite the table and the updates would be lost).  Other passes are not affected, and
+ * pcmi_net_backward of the pass does not need the updates applied.  A forward that returns an error leaves nothing
+ * pending on its pass. */
 int pcmi_net_apply_running_stats(pcmi_net_t* net, int pass, pcmi_stream_t stream);
 /* The momentum of every BatchNorm op of `net` for later training forwards (the detection fine-tuning's BNMomentumScheduler,
  * vn/lib/train.py: a new value per epoch); a net that never calls it keeps the momenta it was created with.  Passes already

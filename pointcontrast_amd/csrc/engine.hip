@@ -1140,6 +1140,10 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
                      pcmi_stream_t stream) {
   PCMI_REQUIRE(net && coords && in_feats && params && out_feats, PCMI_ERR_INVALID, "net_forward: null argument");
   PCMI_REQUIRE(pass >= 0 && pass < (int)net->passes.size(), PCMI_ERR_INVALID, "net_forward: bad pass %d", pass);
+  // begin() starts a new table: a forward here would drop the deferred updates of the previous one without a word
+  PCMI_REQUIRE(net->passes[pass].upd_n == 0, PCMI_ERR_INVALID,
+               "net_forward: pass %d still holds %d deferred BatchNorm running-estimate updates; call "
+               "pcmi_net_apply_running_stats for it first", pass, net->passes[pass].upd_n);
   const ConvPrecisionScope precision(net->conv_precision);  // the net's mode for this pass, the thread's afterwards
   const X3TableScope x3_scope;  // the table of packed weights is this thread's only until the pass has been enqueued
   PassState& ps = net->passes[pass];
@@ -1152,8 +1156,13 @@ int pcmi_net_forward(pcmi_net_t* net, int pass, pcmi_coords_t* coords, const flo
   // an error return leaves no table behind that a later pass could mistake for this one's packs
   // (x3_bwd_pending stays: it is true only if THIS pass recorded the event, and the next forward of the pass must still
   //  wait for that side-stream pack before it rebuilds the job table)
-  if (rc) ps.x3_current = ps.x3_bwd_owed = false;
-  else ps.valid = train;
+  // nor pending running-estimate updates: the table is incomplete, and the pass would refuse every later forward
+  if (rc) {
+    ps.x3_current = ps.x3_bwd_owed = false;
+    ps.upd_n = 0;
+  } else {
+    ps.valid = train;
+  }
   return rc;
 }
 

@@ -234,7 +234,8 @@ class NativeEngine:
 
   def apply_running_stats(self, pass_id):
     """Applies the BatchNorm running-estimate updates a forward(..., defer_running_stats=True) of this pass left
-    pending (on the current stream, which must be ordered after that forward)."""
+    pending (on the current stream, which must be ordered after that forward).  Until then every forward of that
+    pass is refused (it would drop them); a forward that raises leaves nothing pending."""
     with torch.cuda.device(self.flat.w.device):
       check(lib.pcmi_net_apply_running_stats(self._h, pass_id, cur_stream(self.flat.w.device)))
 
@@ -258,7 +259,12 @@ class NativeEngine:
         ev[1].record(side)
     if ev:
       ev[2].record(cur)
-    f0 = self.forward(0, st0)
+    try:
+      f0 = self.forward(0, st0)
+    except BaseException:  # pass 1 did run: its updates are due, and a pass that holds pending updates refuses its next forward
+      cur.wait_stream(side)
+      self.apply_running_stats(1)
+      raise
     if ev:
       ev[3].record(cur)
       marks.append(ev)

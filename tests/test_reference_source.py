@@ -68,6 +68,43 @@ def test_model_ref_equals_reference_source_over_the_oracle(name):
     assert torch.equal(p.grad, gp[k].grad), k
   for (k, a), (_, b) in zip(ref.state_dict().items(), own.state_dict().items()):
     assert torch.equal(a, b), "state after two training forwards: " + k  # incl. the block-BN momentum quirk
+  # inference mode, which the GPU tests of the executor's inference forward trust: the running estimates have moved by
+  # now; one more forward of both clouds gives bit-identical features and leaves every buffer where it was
+  before = {k: v.clone() for k, v in own.state_dict().items()}
+  assert any(k.endswith("running_mean") and bool(v.abs().max() > 0) for k, v in before.items())
+  ref.eval()
+  own.eval()
+  with torch.no_grad():
+    Fe = [_oracle_forward(m) for m in (ref, own)]
+  for a, b, t in zip(Fe[0], Fe[1], outs[1][0]):
+    assert torch.equal(a, b), "inference-mode features differ: max |d| = %g" % float((a - b).abs().max())
+    assert not torch.equal(b, t.detach()), "inference mode computed the training-mode features"
+  for m in (ref, own):
+    after = m.state_dict()
+    assert list(after) == list(before)
+    for k, v in before.items():  # running estimates and num_batches_tracked included
+      assert torch.equal(after[k], v), "an inference forward moved " + k
+
+
+def test_model_ref_inference_mode_differs_from_training_mode():
+  """Runs everywhere.  The power of every comparison with the oracle's inference mode (tests/test_gpu_inference.py):
+  on the golden inputs, after two training forwards, the running estimates give other features than the batch
+  statistics do, by more than 1e-2 of the largest entry.  If both modes computed the same thing here, agreement with
+  the inference-mode oracle would not tell the two apart."""
+  from oracle import model_ref as mr
+  own = mr.MODELS["Res16UNet34C"](3, 32, bn_momentum=_cfg().opt.bn_momentum)
+  refsrc.fill_deterministic(own)
+  own.train()
+  with torch.no_grad():
+    Ft = _oracle_forward(own)  # the two training forwards: cloud 0, then cloud 1
+    state = {k: v.clone() for k, v in own.state_dict().items()}
+    own.eval()
+    Fe = _oracle_forward(own)
+  for k, v in own.state_dict().items():
+    assert torch.equal(v, state[k]), "an inference forward moved " + k
+  for t, e in zip(Ft, Fe):
+    d = float((t - e).abs().max() / t.abs().max())
+    assert d > 1e-2, "training- and inference-mode features differ by %.3e of the largest entry only" % d
 
 
 @needs_reference
