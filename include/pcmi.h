@@ -990,6 +990,85 @@ int pcmi_seg_color_augment(const float* feats_src, int64_t n_src, const int64_t*
                            pcmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The input of contrastive pre-training for a batch of frame pairs (csrc/pair_input.hip) -- what the reference runs per item on
+ * the host in pretrain/pointcontrast/lib/ddp_data_loaders.py ("pc/" below): ScanNetMatchPairDataset.__getitem__ (:196-265) and
+ * default_collate_pair_fn (:52-112).  The conventions of "The input of segmentation fine-tuning" above: every random quantity is
+ * an INPUT.  A batch holds B pairs = 2 B clouds; cloud c holds the rows [offsets[c], offsets[c + 1]) of one [n, 3] array (DEVICE
+ * int64 [2 B + 1], ascending, empty clouds allowed; a row outside [offsets[0], offsets[2 B]) belongs to no cloud and is dropped);
+ * clouds 2 b and 2 b + 1 are pair b.  1 <= B <= PCMI_PAIR_MAX_PAIRS, row counts < 2^31 - 256 (PCMI_ERR_INVALID beyond), and at
+ * most 2^29 rows where a table is built (PCMI_ERR_UNSUPPORTED beyond).  fp64 arithmetic, every product and sum rounded on its
+ * own in the stated order (no FMA contraction); integer atomics only; the same bits from run to run.  Contiguous tensors,
+ * everything on the caller's stream, no synchronisation, every kernel launched over all rows of the batch; a refused call
+ * enqueues nothing.  Data-dependent errors are ORed into flags [B] (device int32, one word per pair, zeroed by the CALLER so
+ * that the calls of a batch share it):
+ *   PCMI_PAIR_FLAG_NONFINITE  a point of the pair is not finite, raw, after its transform or after trans
+ *   PCMI_PAIR_FLAG_RANGE      a voxel index, or a radius-sized cell index, is outside +-(2^20 - 1) (or radius[b] is not positive)
+ *   PCMI_PAIR_FLAG_MATCHES    a source point has more than 96 matches
+ * -- the conditions under which pcmi_voxelize / pcmi_match_radius return PCMI_ERR_RANGE.  A pair whose word is not zero when a
+ * call writes its rows yields none there: no voxel (pcmi_pair_voxelize), no correspondence (pcmi_pair_match).  The rows and
+ * offsets of the other pairs are what they would be without it.
+ *
+ * pcmi_pair_transform = pc:196-225.  raw [n, 3] (fp32 if raw_is_f32, else fp64; widened to fp64 first), scale [B] (DEVICE fp64; 1
+ *   where the reference does not scale), rot [2 B, 9] (DEVICE fp64, row-major rotations R_c; read only if rotate != 0).
+ *   x' = scale[b] x.  rotate != 0: the centroid m_c = S_c / n_c (0 for an empty cloud) with S_c summed in this fixed order, which
+ *   depends on neither the launch geometry nor the number of compute units: the cloud's rows are cut into chunks of
+ *   PCMI_PAIR_CENTROID_CHUNK = 1024 rows from its first row.  Inside a chunk, lane t of 256 adds rows t, t + 256, t + 512, t + 768
+ *   to 0 in this order (a row past the cloud's end adds +0), then the 256 lane sums are folded as v[t] = v[t] + v[t + s] for
+ *   s = 128, 64 .. 1; S_c = the chunk sums added to 0 in chunk order.  t_c[r] = ((R[r,0] (-m0) + R[r,1] (-m1)) + R[r,2] (-m2)),
+ *   p = ((R[r,0] x' + R[r,1] y') + R[r,2] z') + t[r];  trans_b = T_{2b+1} inv(T_{2b}) in the closed form of a rigid matrix:
+ *   Rt[r][c] = ((R1[r,0] R0[c,0] + R1[r,1] R0[c,1]) + R1[r,2] R0[c,2]), tt[r] = t1[r] - ((Rt[r,0] t0[0] + Rt[r,1] t0[1]) + Rt[r,2] t0[2]).
+ *   rotate == 0: p = x', T = I, trans = I (no centring).  points [n, 3] (fp64), T [2 B, 16], trans [B, 16] (fp64, row-major 4 x 4).
+ *   ws: pcmi_pair_transform_workspace_bytes(n, B) (the chunk sums), 16-byte aligned.
+ * pcmi_pair_voxelize = pc:228-229, :238-239, :258-259 for all 2 B clouds: the FIRST point (lowest row) of every occupied voxel
+ *   floor(p / voxel_size) of each cloud (oracle/loader_ref.sparse_quantize_index per cloud), survivors in ascending row order.
+ *   out_points [n, 3] (fp64), coords [n, 3] (int32, floor(p / voxel_size)), first_index [n] (int32, the BATCH row of the point):
+ *   the first vox_offsets[2 B] rows are valid.  n_vox [2 B], vox_offsets [2 B + 1] (their prefix) and side_offsets [2, B + 1]
+ *   (side_offsets[s][b] = the voxels of clouds 2 b' + s, b' < b: the batch row at which side s of pair b starts in the collate),
+ *   all DEVICE int64.  Per cloud an open-addressing table segment of 2 n_c + 1 slots (a 63-bit voxel key has no room for a cloud).
+ *   ws: pcmi_pair_voxelize_workspace_bytes(n, B), 16-byte aligned.
+ * pcmi_pair_match = pc:36-49, :241 for all B pairs, count -> scan -> fill: every (i, j) with |trans_b p0_i - p1_j| <= radius[b] in
+ *   oracle/loader_ref.match_radius's arithmetic (apply_rigid's order, cells floor(. / r), 27-cell probe, (ex ex + ey ey) + ez ez
+ *   <= r r), on the voxelised rows: points [m_max, 3] with vox_offsets / side_offsets as pcmi_pair_voxelize left them (m_max >= the
+ *   valid rows: the host need not know their number).  radius [B] (DEVICE fp64; the caller's voxel_size * multiplier * scale[b]).
+ *   pairs [capacity, 2] (int32): the pairs of the batch concatenated, i and j carrying the batch row offsets side_offsets[0][b],
+ *   side_offsets[1][b], sorted by (i, j); a pair without a match contributes the one row (side_offsets[0][b], side_offsets[1][b])
+ *   (pc:81-83), a flagged pair none.  pair_counts [B] (DEVICE int64) = the rows per pair; totals [4] (DEVICE int64) = the rows
+ *   needed, n_queries (the distinct values of column 0), overflow (1 if the rows needed exceed capacity: then NOTHING is written
+ *   to pairs; call again with room for totals[0] rows), capacity.  The counts are exact whatever the capacity.
+ *   fill_only != 0 is that second call: it repeats only the per-pair pass and the fill, on the cells, counts and scan that the
+ *   call before left in ws -- same arguments but pairs and capacity, the same ws, nothing else run in ws in between, flags as
+ *   that call left them.
+ *   ws: pcmi_pair_match_workspace_bytes(m_max, B), 16-byte aligned.
+ * pcmi_pair_collate = pc:52-112 with pc:248-252 and FeatureJitter (pc/lib/transforms.py:21-30), one launch: voxel row r of cloud
+ *   2 b + s goes to row side_offsets[s][b] + (r - vox_offsets[2 b + s]) of side s: C{s} [out_rows, 4] (int32; b, x, y, z),
+ *   pcd{s} [out_rows, 3] = fp32(p), F{s} [out_rows, 3] = fp32(1 + (mu + sigma z)) where jitter_on[2 b + s] != 0 (DEVICE int32
+ *   [2 B]) and noise is given, else 1; z = noise [n_raw, 3] (fp32 standard normals, widened; NULL = no jitter) at the row
+ *   first_index[r] -- the noise belongs to the RAW point, so it is defined before the voxel counts are known.  T_gt [4 B, 4] =
+ *   fp32(trans).  A row that would fall outside out_rows is not written.  ws: unused (pcmi_pair_collate_workspace_bytes). */
+#define PCMI_PAIR_FLAG_NONFINITE 1
+#define PCMI_PAIR_FLAG_RANGE 2
+#define PCMI_PAIR_FLAG_MATCHES 4
+#define PCMI_PAIR_MAX_PAIRS 512
+#define PCMI_PAIR_CENTROID_CHUNK 1024
+size_t pcmi_pair_transform_workspace_bytes(int64_t n, int64_t B);
+int pcmi_pair_transform(const void* raw, int raw_is_f32, const int64_t* offsets, int64_t n, int64_t B, const double* scale,
+                        const double* rot, int rotate, double* points, double* T, double* trans, int32_t* flags, void* ws,
+                        size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_pair_voxelize_workspace_bytes(int64_t n, int64_t B);
+int pcmi_pair_voxelize(const double* points, const int64_t* offsets, int64_t n, int64_t B, double voxel_size, double* out_points,
+                       int32_t* coords, int32_t* first_index, int64_t* n_vox, int64_t* vox_offsets, int64_t* side_offsets,
+                       int32_t* flags, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_pair_match_workspace_bytes(int64_t m_max, int64_t B);
+int pcmi_pair_match(const double* points, int64_t m_max, const int64_t* vox_offsets, const int64_t* side_offsets, int64_t B,
+                    const double* trans, const double* radius, int32_t* pairs, int64_t capacity, int64_t* pair_counts,
+                    int64_t* totals, int32_t* flags, int fill_only, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_pair_collate_workspace_bytes(int64_t m_max, int64_t B);
+int pcmi_pair_collate(const double* points, const int32_t* coords, const int32_t* first_index, int64_t m_max,
+                      const int64_t* vox_offsets, const int64_t* side_offsets, int64_t B, const double* trans, const float* noise,
+                      int64_t n_raw, const int32_t* jitter_on, double mu, double sigma, int64_t out_rows, int32_t* C0, int32_t* C1,
+                      float* pcd0, float* pcd1, float* F0, float* F1, float* T_gt, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The input of VoteNet detection fine-tuning for a batch of scans (csrc/detect_input.hip) -- what the reference runs per scan on
  * the host in downstream/votenet_det_new: ScannetDetectionDataset.__getitem__
  * (lib/datasets/scannet/scannet_detection_dataset.py:60-172), SunrgbdDetectionVotesDataset.__getitem__

@@ -224,6 +224,15 @@ PROTOTYPES = {
     "pcmi_seg_color_augment_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_seg_color_augment": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, C.c_int, c_vp, c_i64, c_i32,
                                          c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_pair_transform_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_pair_transform": (C.c_int, [c_vp, C.c_int, c_vp, c_i64, c_i64, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_pair_voxelize_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_pair_voxelize": (C.c_int, [c_vp, c_vp, c_i64, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_pair_match_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_pair_match": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, C.c_int, c_vp, c_sz, c_vp]),
+    "pcmi_pair_collate_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_pair_collate": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_double, C.c_double, c_i64,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_det_sample_transform": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp]),
     "pcmi_det_votes_transform": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

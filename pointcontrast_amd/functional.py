@@ -1286,6 +1286,141 @@ def seg_color_augment(feats_src, coords, n_scenes, index=None, labels=None, para
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The input of contrastive pre-training (csrc/pair_input.hip): ScanNetMatchPairDataset.__getitem__ and default_collate_pair_fn
+# of the reference (pretrain/pointcontrast/lib/ddp_data_loaders.py) for a batch of B pairs = 2 B clouds.  None of these is
+# differentiable and none synchronises; errors arrive in `flags` (int32 [B], PAIR_FLAG_* bits per pair).
+# ---------------------------------------------------------------------------------------------------------------------
+PAIR_FLAG_NONFINITE, PAIR_FLAG_RANGE, PAIR_FLAG_MATCHES = 1, 2, 4
+PAIR_FLAG_NAMES = {PAIR_FLAG_NONFINITE: "a point is not finite (raw, after its transform or after trans)",
+                   PAIR_FLAG_RANGE: "a voxel or search-cell index is outside +-(2^20 - 1)",
+                   PAIR_FLAG_MATCHES: "a source point has more than 96 matches (is the search radius far above the voxel size?)"}
+PAIR_MAX_PAIRS = 512  # PCMI_PAIR_MAX_PAIRS
+
+
+def pair_flags_message(flags_host):
+  """The exception text for a read-back flags array (None if no bit is set): every flagged pair with its causes."""
+  bad = ["pair %d: %s" % (b, "; ".join(t for bit, t in PAIR_FLAG_NAMES.items() if int(f) & bit) or "flag %d" % int(f))
+         for b, f in enumerate(flags_host) if int(f)]
+  return "pre-training input: " + " | ".join(bad) if bad else None
+
+
+def _pair_offsets(offsets, dev, who):
+  offs = _offsets(offsets, dev)
+  assert offs.dim() == 1 and offs.shape[0] >= 3 and offs.shape[0] % 2 == 1, who + ": offsets [2 B + 1]"
+  return offs, (offs.shape[0] - 1) // 2
+
+
+def pair_transform(raw, offsets, scale, rot=None, flags=None):
+  """pcmi_pair_transform.  raw float32 or float64 [n, 3] (the clouds of the batch, pair b = clouds 2 b and 2 b + 1), offsets
+  [2 B + 1], scale float64 [B], rot float64 [2 B, 3, 3] or [2 B, 9] (None: no rotation and no centring, T = trans = I).  Returns
+  a dict of device tensors: points float64 [n, 3], T float64 [2 B, 4, 4], trans float64 [B, 4, 4], flags int32 [B] (ORed into the
+  one passed in)."""
+  require_cuda(raw, "pair_transform")
+  dev = raw.device
+  assert raw.dtype in (torch.float32, torch.float64) and raw.dim() == 2 and raw.shape[1] == 3, "pair_transform: raw float32 / float64 [n, 3]"
+  x = raw.contiguous()
+  offs, B = _pair_offsets(offsets, dev, "pair_transform")
+  sc = _f64c(scale, dev, "pair_transform").reshape(-1)
+  R = None if rot is None else _f64c(rot, dev, "pair_transform").reshape(-1, 9)
+  assert sc.shape[0] == B and (R is None or R.shape[0] == 2 * B), "pair_transform: scale [B], rot [2 B, 3, 3]"
+  flags = _seg_flags(flags, B, dev)
+  n = x.shape[0]
+  points = torch.empty((n, 3), dtype=torch.float64, device=dev)
+  T = torch.empty((2 * B, 4, 4), dtype=torch.float64, device=dev)
+  trans = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_pair_transform_workspace_bytes(n, B), dev)
+  check(lib.pcmi_pair_transform(ptr(x), 1 if x.dtype == torch.float32 else 0, ptr(offs), n, B, ptr(sc), ptr(R), 0 if R is None else 1,
+                                ptr(points), ptr(T), ptr(trans), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(points=points, T=T, trans=trans, flags=flags)
+
+
+def pair_voxelize(points, offsets, voxel_size, flags=None):
+  """pcmi_pair_voxelize: the first point of every occupied voxel of every cloud, in ascending row order.  points float64 [n, 3],
+  offsets [2 B + 1].  Returns a dict of device tensors whose first vox_offsets[2 B] rows are valid -- points float64 [n, 3],
+  coords int32 [n, 3], first_index int32 [n] (batch rows) -- and n_vox int64 [2 B], vox_offsets int64 [2 B + 1], side_offsets
+  int64 [2, B + 1], flags int32 [B].  Nothing is read back: slice after reading the counts."""
+  require_cuda(points, "pair_voxelize")
+  dev = points.device
+  p = _f64c(points, dev, "pair_voxelize")
+  assert p.dim() == 2 and p.shape[1] == 3, "pair_voxelize: points [n, 3]"
+  offs, B = _pair_offsets(offsets, dev, "pair_voxelize")
+  flags = _seg_flags(flags, B, dev)
+  n = p.shape[0]
+  out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+  coords = torch.empty((n, 3), dtype=torch.int32, device=dev)
+  first = torch.empty(n, dtype=torch.int32, device=dev)
+  n_vox = torch.empty(2 * B, dtype=torch.int64, device=dev)
+  voff = torch.empty(2 * B + 1, dtype=torch.int64, device=dev)
+  side = torch.empty((2, B + 1), dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_pair_voxelize_workspace_bytes(n, B), dev)
+  check(lib.pcmi_pair_voxelize(ptr(p), ptr(offs), n, B, float(voxel_size), ptr(out), ptr(coords), ptr(first), ptr(n_vox), ptr(voff),
+                               ptr(side), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(points=out, coords=coords, first_index=first, n_vox=n_vox, vox_offsets=voff, side_offsets=side, flags=flags)
+
+
+def pair_match(vox, trans, radius, capacity, flags=None, pairs=None, fill_only=False):
+  """pcmi_pair_match on pair_voxelize's result `vox`: trans float64 [B, 4, 4], radius float64 [B], room for `capacity` rows
+  (in `pairs`, int32 [>= capacity, 2], if given).
+  Returns a dict of device tensors: pairs int32 [capacity, 2] (the first totals[0] rows are valid unless totals[2] is set: then
+  nothing was written, call again with capacity >= totals[0]), pair_counts int64 [B], totals int64 [4] (rows needed, n_queries,
+  overflow, capacity), flags int32 [B].  Nothing is read back.  fill_only: the second call after an overflow -- only the fill
+  runs, on what the first call left in the shared workspace (no other op may have used the workspace in between), with the
+  flags tensor of that call."""
+  pts = vox["points"]
+  require_cuda(pts, "pair_match")
+  dev = pts.device
+  voff, side = vox["vox_offsets"], vox["side_offsets"]
+  B = side.shape[1] - 1
+  tr = _f64c(trans, dev, "pair_match").reshape(-1, 16)
+  rd = _f64c(radius, dev, "pair_match").reshape(-1)
+  assert tr.shape[0] == B and rd.shape[0] == B and voff.shape[0] == 2 * B + 1, "pair_match: trans [B, 4, 4], radius [B]"
+  flags = _seg_flags(flags, B, dev)
+  cap, m_max = int(capacity), pts.shape[0]
+  if pairs is None:
+    pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+  assert pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.shape[0] >= cap and pairs.is_contiguous() and \
+      pairs.device == dev, "pair_match: pairs int32 [>= capacity, 2] on the points' device, contiguous"
+  counts = torch.empty(B, dtype=torch.int64, device=dev)
+  totals = torch.empty(4, dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_pair_match_workspace_bytes(m_max, B), dev)
+  check(lib.pcmi_pair_match(ptr(pts), m_max, ptr(voff), ptr(side), B, ptr(tr), ptr(rd), ptr(pairs) if cap else None, cap, ptr(counts),
+                            ptr(totals), ptr(flags), 1 if fill_only else 0, ws, wsb, cur_stream(dev)))
+  return dict(pairs=pairs, pair_counts=counts, totals=totals, flags=flags)
+
+
+def pair_collate(vox, trans, noise=None, jitter_on=None, mu=0.0, sigma=0.01, out_rows=None):
+  """pcmi_pair_collate on pair_voxelize's result `vox`: the collated batch with room for out_rows rows per side (None: as many
+  as `vox` has).  noise float32 [n_raw, 3] standard normals (None: features are 1), jitter_on int32 [2 B].  Returns a dict of
+  device tensors: sinput{0,1}_C int32 [out_rows, 4], pcd{0,1} and sinput{0,1}_F float32 [out_rows, 3] (valid rows:
+  side_offsets[s][B]) and T_gt float32 [4 B, 4]."""
+  pts = vox["points"]
+  require_cuda(pts, "pair_collate")
+  dev = pts.device
+  voff, side = vox["vox_offsets"], vox["side_offsets"]
+  B = side.shape[1] - 1
+  tr = _f64c(trans, dev, "pair_collate").reshape(-1, 16)
+  assert tr.shape[0] == B, "pair_collate: trans [B, 4, 4]"
+  nz = None if noise is None else _f32c(noise.to(dev), "pair_collate")
+  assert nz is None or (nz.dim() == 2 and nz.shape[1] == 3), "pair_collate: noise [n_raw, 3]"
+  on = None if nz is None else _i32c(torch.as_tensor(jitter_on), dev).reshape(-1)
+  assert on is None or on.shape[0] == 2 * B, "pair_collate: jitter_on [2 B]"
+  m_max = pts.shape[0]
+  rows = m_max if out_rows is None else int(out_rows)
+  out = {}
+  for s in "01":
+    out["sinput%s_C" % s] = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+    out["pcd" + s] = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    out["sinput%s_F" % s] = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+  out["T_gt"] = torch.empty((4 * B, 4), dtype=torch.float32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_pair_collate_workspace_bytes(m_max, B), dev)
+  check(lib.pcmi_pair_collate(ptr(pts), ptr(vox["coords"]), ptr(vox["first_index"]), m_max, ptr(voff), ptr(side), B, ptr(tr), ptr(nz),
+                              0 if nz is None else nz.shape[0], ptr(on), float(mu), float(sigma), rows, ptr(out["sinput0_C"]),
+                              ptr(out["sinput1_C"]), ptr(out["pcd0"]), ptr(out["pcd1"]), ptr(out["sinput0_F"]), ptr(out["sinput1_F"]),
+                              ptr(out["T_gt"]), ws, wsb, cur_stream(dev)))
+  return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The input of detection fine-tuning (csrc/detect_input.hip): what ScannetDetectionDataset / SunrgbdDetectionVotesDataset
 # __getitem__ and VoxelizationDataset + collate_fn of the reference (downstream/votenet_det_new) do per scan on the host, for a
 # batch.  None of these is differentiable and none synchronises; errors arrive in `flags` (int32 [B], DET_FLAG_* bits per scene).

@@ -154,6 +154,11 @@ dataset_str_mapping = {d.__name__: d for d in ALL_DATASETS}
 
 
 def make_data_loader(config, batch_size, num_threads=0):
+  if config.data.get("device_batch", False):
+    # data.device_batch: the workers only read the raw frames; the batch -- transform, voxels, correspondences, collation -- is
+    # built on the device by the training process, one call per batch (lib/pair_input.py).  Any number of workers.
+    from .pair_input import DevicePairLoader
+    return DevicePairLoader(config, batch_size, num_threads=num_threads)
   if config.data.dataset not in dataset_str_mapping:
     raise ValueError("Dataset %s does not exist in %s" % (config.data.dataset, ", ".join(dataset_str_mapping)))
   Dataset = dataset_str_mapping[config.data.dataset]

@@ -191,7 +191,12 @@ class ContrastiveLossTrainer:
       sub = self._prep_mark  # misc.host_profile: where the preparation spends its host time
       sub(None)
       C0, C1 = input_dict["sinput0_C"], input_dict["sinput1_C"]
-      n_batch0 = int(C0[:, 0].max()) + 1 if C0.shape[0] else 0
+      if C0.is_cuda:
+        # a device batch (lib/pair_input.py): the number of pairs is on the host already, nothing is read back, and the clone,
+        # shift and concatenation below run on the device
+        n_batch0 = len(input_dict["len_batch"])
+      else:
+        n_batch0 = int(C0[:, 0].max()) + 1 if C0.shape[0] else 0
       C1 = C1.clone()
       C1[:, 0] += n_batch0
       Cj, Fj = torch.cat([C0, C1]), torch.cat([input_dict["sinput0_F"], input_dict["sinput1_F"]])
@@ -427,18 +432,23 @@ class HardestContrastiveLossTrainer(ContrastiveLossTrainer):
     buffers, on `stream` (None: the current one).  Round 3 had five pageable copies here -- each drains the compute
     stream before it returns -- and a 50 us insert kernel between the forward pass and the loss."""
     sel0, sel1, pos_sel = drawn
-    sample = pp if pos_sel is None else pp[np.asarray(pos_sel)]
+    on_device = torch.is_tensor(pp) and pp.is_cuda  # a device batch: the pairs never visit the host
     host = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dt)
     cur = torch.cuda.current_stream(self.cur_device)
     with torch.cuda.stream(stream if stream is not None else cur):
       up = lambda a, dt, name: self._upload_any(host(a, dt), ("hardest", name, slot))
-      out = dict(sel0=up(sel0, torch.int64, "sel0"), sel1=up(sel1, torch.int64, "sel1"),
-                 pos0=up(sample[:, 0], torch.int64, "pos0"), pos1=up(sample[:, 1], torch.int64, "pos1"))
+      out = dict(sel0=up(sel0, torch.int64, "sel0"), sel1=up(sel1, torch.int64, "sel1"))
+      if on_device:  # the positive sample is a device gather at the uploaded pos_sel
+        sample = pp if pos_sel is None else pp.index_select(0, up(pos_sel, torch.int64, "pos_sel"))
+        out["pos0"], out["pos1"] = sample[:, 0].long(), sample[:, 1].long()
+      else:
+        sample = pp if pos_sel is None else pp[np.asarray(pos_sel)]
+        out["pos0"], out["pos1"] = up(sample[:, 0], torch.int64, "pos0"), up(sample[:, 1], torch.int64, "pos1")
       # cloud 1's rows in the pair's ONE feature matrix (PF.GatherManyFunction; misc.joint_pair)
       out["sel1_joint"], out["pos1_joint"] = out["sel1"] + N0, out["pos1"] + N0
       held = [out["sel0"], out["sel1"], out["pos0"], out["pos1"], out["sel1_joint"], out["pos1_joint"]]
       if keys is None:
-        pairs_d = up(pp.reshape(-1), torch.int32, "pairs").view(-1, 2)
+        pairs_d = pp.contiguous() if on_device else up(pp.reshape(-1), torch.int32, "pairs").view(-1, 2)
         keys = PF.PairKeySet(pairs_d, max(N0, N1))
         held += [pairs_d, keys.buf]
       out.update(keys=keys, n=(N0, N1), event=None)
@@ -461,12 +471,18 @@ class HardestContrastiveLossTrainer(ContrastiveLossTrainer):
     self._slot = slot ^ 1  # two sets of staging buffers: a prefetched batch must not overwrite the live one
     inp = prep["input"]
     pp = inp["correspondences"]
-    pp = pp.numpy() if torch.is_tensor(pp) else np.asarray(pp)
+    on_device = torch.is_tensor(pp) and pp.is_cuda  # a device batch (lib/pair_input.py): the key set is built from the
+    if not on_device:                               # pairs where they are; P = len(pp) is known from the batch's read-back
+      pp = pp.numpy() if torch.is_tensor(pp) else np.asarray(pp)
     N0, N1 = int(inp["sinput0_C"].shape[0]), int(inp["sinput1_C"].shape[0])
     plan, cur = handle_pool.plan_stream(self.cur_device), torch.cuda.current_stream(self.cur_device)
     with torch.cuda.stream(plan):
-      pairs_d = self._upload_any(torch.as_tensor(np.ascontiguousarray(pp.reshape(-1))).to(torch.int32),
-                                 ("hardest", "pairs", slot)).view(-1, 2)
+      if on_device:
+        plan.wait_stream(cur)
+        pairs_d = pp.contiguous()
+      else:
+        pairs_d = self._upload_any(torch.as_tensor(np.ascontiguousarray(pp.reshape(-1))).to(torch.int32),
+                                   ("hardest", "pairs", slot)).view(-1, 2)
       keys = PF.PairKeySet(pairs_d, max(N0, N1))
       pairs_d.record_stream(cur)
       keys.buf.record_stream(cur)
@@ -494,14 +510,17 @@ class HardestContrastiveLossTrainer(ContrastiveLossTrainer):
 
   def contrastive_hardest_negative_loss(self, F0, F1, positive_pairs, num_pos=5192, num_hn_samples=2048,
                                         draws=None, prepared=None, joint=None):
-    """pc/lib/ddp_trainer.py:186-238.  positive_pairs: CPU int tensor / array [P,2].
+    """pc/lib/ddp_trainer.py:186-238.  positive_pairs: CPU int tensor / array [P,2], or the int32 device tensor of a device batch.
     draws: optional dict(sel0, sel1, pos_sel) replacing the np.random.choice calls.
     prepared: the samples / key set of _prepare_loss (then positive_pairs, num_*, draws are not looked at)."""
     N0, N1 = F0.shape[0], F1.shape[0]
     if prepared is None:
       if not hasattr(self, "cur_device"):  # (a bare instance, as the parity tests make one)
         self.cur_device = F0.device
-      pp = positive_pairs.numpy() if torch.is_tensor(positive_pairs) else np.asarray(positive_pairs)
+      if torch.is_tensor(positive_pairs) and positive_pairs.is_cuda:
+        pp = positive_pairs
+      else:
+        pp = positive_pairs.numpy() if torch.is_tensor(positive_pairs) else np.asarray(positive_pairs)
       prepared = self._upload_hardest(N0, N1, pp, self._draw_hardest(N0, N1, len(pp), num_pos, num_hn_samples, draws), None)
     elif "thread" in prepared:
       prepared = self._finish_prepared_loss(prepared)
@@ -598,20 +617,26 @@ class PointNCELossTrainer(ContrastiveLossTrainer):
       q_unique, k_sel = q_unique[si], k_sel[si]
     return q_unique, k_sel
 
-  def select_pairs_device(self, pos_pairs, npos, draws=None, slot=0, defer_wait=False):
+  def select_pairs_device(self, pos_pairs, npos, draws=None, slot=0, defer_wait=False, n_queries=None):
     """select_pairs with the run detection and the gathers on the device (csrc/pairs.hip): the host keeps what consumes
     the random-number streams -- torch.rand(n_unique), np.random.choice(n_unique, npos) -- in the same order as
     select_pairs, plus one native pass over column 0 for n_unique.  Returns device int64 (q_idx, k_idx); bit-identical
     to select_pairs (tests/test_gpu_parity.py::test_device_pair_selection_is_bit_identical).  None: the correspondences
     are not a sorted contiguous int32 tensor (the caller falls back to the host path).  defer_wait: also returns the event
     the consumer's stream has to wait for (the selection runs on the planning stream); otherwise the current stream
-    waits for it here."""
+    waits for it here.  Correspondences that are already on the device (a device batch, lib/pair_input.py: sorted by
+    construction) come with n_queries, the batch's count of distinct queries, in place of the host pass, and are not uploaded;
+    without n_queries they are refused like any other unsupported form."""
     pp = pos_pairs if torch.is_tensor(pos_pairs) else torch.from_numpy(np.asarray(pos_pairs))
-    if pp.is_cuda or pp.dtype != torch.int32 or pp.dim() != 2 or not pp.is_contiguous() or pp.shape[0] == 0:
+    on_device = pp.is_cuda
+    if (on_device and n_queries is None) or pp.dtype != torch.int32 or pp.dim() != 2 or not pp.is_contiguous() or pp.shape[0] == 0:
       return None
-    nq, is_sorted = PF.pairs_scan_host(pp)
-    if not is_sorted:
-      return None
+    if on_device:
+      nq = int(n_queries)
+    else:
+      nq, is_sorted = PF.pairs_scan_host(pp)
+      if not is_sorted:
+        return None
     draws = draws or {}
     uniform = draws["uniform"] if "uniform" in draws else torch.rand(nq)
     uniform = torch.as_tensor(uniform, dtype=torch.float32)
@@ -627,7 +652,11 @@ class PointNCELossTrainer(ContrastiveLossTrainer):
     from .._lib import lib
     plan, cur = handle_pool.plan_stream(self.cur_device), torch.cuda.current_stream(self.cur_device)
     with torch.cuda.stream(plan):
-      pairs_d = pp.to(self.cur_device, non_blocking=True) if pp.is_pinned() else self._upload_any(pp, ("pairs", slot)).view(pp.shape)
+      if on_device:
+        plan.wait_stream(cur)  # (the batch's producer ran on the current stream)
+        pairs_d = pp
+      else:
+        pairs_d = pp.to(self.cur_device, non_blocking=True) if pp.is_pinned() else self._upload_any(pp, ("pairs", slot)).view(pp.shape)
       u_d = self._upload_any(uniform, ("uniform", slot))
       si_d = self._upload_any(si, ("sampled", slot)) if si is not None else None
       need = lib.pcmi_pair_select_workspace_bytes(pp.shape[0])
@@ -651,7 +680,8 @@ class PointNCELossTrainer(ContrastiveLossTrainer):
     slot = getattr(self, "_slot", 0)
     self._slot = slot ^ 2  # two staging buffer pairs: the prefetched batch must not overwrite the live one
     if self.config.misc.get("device_pair_selection", True):
-      sel = self.select_pairs_device(prep["input"]["correspondences"], self.npos, draws, slot, defer_wait=True)
+      sel = self.select_pairs_device(prep["input"]["correspondences"], self.npos, draws, slot, defer_wait=True,
+                                     n_queries=prep["input"].get("n_queries"))
       if sel is not None:
         prep["q_idx"], prep["k_idx"], prep["sel_event"] = sel
         if "n0" in prep:  # the pair as one tensor: the keys' rows in it (PF.GatherPairFunction), still on the planning stream
@@ -663,7 +693,10 @@ class PointNCELossTrainer(ContrastiveLossTrainer):
             prep["sel_event"].record(plan)
           prep["k_idx_joint"].record_stream(cur)
         return
-    q_idx, k_idx = self.select_pairs(prep["input"]["correspondences"], self.npos, draws)
+    corr = prep["input"]["correspondences"]
+    if torch.is_tensor(corr) and corr.is_cuda:  # a device batch whose selection could not run on the device: one read-back
+      corr = corr.cpu()
+    q_idx, k_idx = self.select_pairs(corr, self.npos, draws)
     prep["q_idx"], prep["k_idx"] = self._upload(q_idx, slot), self._upload(k_idx, slot + 1)
     if "n0" in prep:
       prep["k_idx_joint"] = self._upload(k_idx + prep["n0"], slot + 4)
