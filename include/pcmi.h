@@ -1348,6 +1348,82 @@ int pcmi_net_timed_groups_ms(pcmi_net_t* net, int set, float* ms, int cap, int* 
  * -- groups != NULL after pcmi_net_time_all -- of its first groups_cap grouped weight-gradient launches. */
 int pcmi_net_timed_launches(pcmi_net_t* net, int set, int* fwd, int* bwd, int* wgrad, int n_ops, int* groups, int groups_cap);
 
+/* ------------------------------------------------------------------------------------------
+ * Validation of the pre-training on held-out pairs (csrc/featmatch.hip).  The reference has none: its trainers descend from
+ * FCGF's contrastive trainer, whose validation matches features between the two clouds of a pair and checks every match
+ * against the known relative pose; pc/lib/ddp_trainer.py dropped that step.  Pair b of B holds the rows [offsets[b],
+ * offsets[b + 1]) of each of its arrays (DEVICE int64 [B + 1], ascending, offsets[0] = 0, empty segments allowed; the kernels
+ * clamp every offset into its array, so a malformed table gives wrong answers, never an access outside).  1 <= B <= 1024
+ * (PCMI_ERR_UNSUPPORTED beyond), row counts < 2^31 - 256.  Nothing synchronises; every random quantity is an INPUT.
+ *
+ * pcmi_feat_nn: the nearest neighbour in feature space of every query, inside its own pair, for all pairs in one call.
+ *   qf [nq, c] (row stride q_ld) with q_offs, rf [nr, c] (r_ld) with r_offs.  query_rows == NULL: row i of qf is query i (Q =
+ *   nq).  Else query_rows [n_query_rows] (int32) with query_offs [B + 1]: query i of pair b (query_offs[b] <= i <
+ *   query_offs[b + 1]) is row query_rows[i] of qf, which must lie in [q_offs[b], q_offs[b + 1]); repeats and any order are
+ *   fine.  Per query: d2(j) = sum over c ascending of fma(a_c - b_c, a_c - b_c, d2) in fp32, over the rows j of rf in the
+ *   query's pair; nn = the row j (GLOBAL row of rf) with the smallest d2, the LOWEST row among equal d2; d2 = that minimum.
+ *     - a d2(j) that is not finite in fp32 is never chosen: a reference row with a NaN / inf feature never wins
+ *     - a query for which no row can be chosen gets nn = -1 and d2 = NaN: its pair has no reference rows, the query has a
+ *       non-finite feature, or query_rows[i] lies outside its pair's segment of qf (so -1 is a legal entry of query_rows)
+ *   c a multiple of 16 in 16 ... 128, else PCMI_ERR_UNSUPPORTED.  q_ld, r_ld >= c and multiples of 4, qf and rf 16-byte aligned
+ *   (PCMI_ERR_INVALID otherwise).  Launch: 64 queries per workgroup (4 x 4 distances per thread, fp32 FMAs on LDS tiles) times
+ *   nch chunks of every reference segment, nch = min(ceil(4 CUs / (ceil(Q / 64) + B)), ceil(nr / 256), 64), at least 1; the
+ *   chunks meet in an unsigned 64-bit minimum over (bits of d2) << 32 | row -- d2 >= +0, so its bits order like the number --
+ *   which makes the result independent of the order of arrival: the same bits from run to run.  ws: 8 Q bytes
+ *   (pcmi_feat_nn_workspace_bytes), 8-byte aligned, else PCMI_ERR_WORKSPACE.  Q == 0 enqueues nothing.
+ *
+ * pcmi_match_stats: the geometric check.  xyz0 [n0, 3], xyz1 [n1, 3] (fp64, voxel coordinate x voxel size), T_gt [B, 4, 4]
+ *   (fp64, DEVICE, row-major), queries as above (query_rows NULL: n_queries == n0 and query_offs are cloud 0's offsets; query_offs
+ *   is always given), nn01 [n_queries] (int32, rows of xyz1), nn10 [n_queries] (int32, nullable: the nearest row of cloud 0 of
+ *   the MATCHED row nn01[i]), has_gt [n0] (uint8, nullable), tau_host[n_tau], 1 <= n_tau <= PCMI_MATCH_MAX_TAU.  Per query i of
+ *   pair b with row r: valid = 0 <= r < n0 and 0 <= nn01[i] < n1; then y = T_gt[b] x0[r] as ((R0 x + R1 y) + R2 z) + t per
+ *   coordinate (lib/ddp_data_loaders.py: _apply_rigid), d = y - x1[nn01[i]], residual2[i] = (dx dx + dy dy) + dz dz, every
+ *   operation rounded on its own; residual2[i] = NaN if not valid.  counts [B, PCMI_MATCH_STAT_COLS] (int64) += per pair:
+ *     [PCMI_MATCH_N_QUERY] every query          [PCMI_MATCH_N_VALID] the valid ones       [PCMI_MATCH_N_MUTUAL] valid and nn10[i] == r
+ *     [PCMI_MATCH_N_GT] 0 <= r < n0 and has_gt[r] != 0                                    [PCMI_MATCH_HITS + t] valid and residual2 <= fl(tau_t tau_t)
+ *     [PCMI_MATCH_HITS_GT + t] both.  Columns of thresholds not given, and of inputs that are NULL, are left as they are.
+ *   Integer atomics only, so several calls add up.  A query outside [query_offs[0], query_offs[B]) counts nowhere.
+ *
+ * pcmi_ransac_score: src, dst [m, 3] (fp64: the matched points of cloud 0 and cloud 1) with offsets; triples [B, H, 3] (int32,
+ *   indices LOCAL to the pair's segment); 1 <= H <= 65536 (PCMI_ERR_UNSUPPORTED beyond); tau >= 0.  Hypothesis (b, h) with
+ *   p_k = src[offsets[b] + triples[b, h, k]], q_k likewise from dst.  The frame of a triangle (a0, a1, a2), every operation
+ *   rounded on its own, sums of three terms as (x + y) + z, a cross product a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx):
+ *     u = a1 - a0, lu = sqrt(u.u), e1 = u / lu;  n = e1 x (a2 - a0), ln = sqrt(n.n), e3 = n / ln;  e2 = e3 x e1.
+ *   With (e1, e2, e3) of p and (f1, f2, f3) of q: R[i][j] = (f1[i] e1[j] + f2[i] e2[j]) + f3[i] e3[j],
+ *   t[i] = q0[i] - ((R[i][0] p0x + R[i][1] p0y) + R[i][2] p0z).  Invalid, counts = -1: a repeated index, an index outside
+ *   [0, segment length), a segment of fewer than 3 matches, or lu or ln below 1e-9 (or NaN) in either cloud.  Else counts [B, H]
+ *   (int32) = the matches k of the segment with |R src_k + t - dst_k|^2 <= fl(tau tau), computed as in pcmi_match_stats.  best
+ *   [B] (int32) = the hypothesis of the highest count, the LOWEST among equals, -1 if none is valid; Rt [B, 12] (fp64) = its R
+ *   row-major, then t (NaN where best is -1).  Launch: one thread per hypothesis, 256 per workgroup, the segment's matches
+ *   staged through LDS 512 at a time (m is unbounded); then one workgroup per pair for best.
+ *
+ * pcmi_rigid_sums: over the inliers (the same test, against Rt[b]) of each pair's best hypothesis, sums [B, 16] (fp64) = n,
+ *   sum p (3), sum q (3), S (9, row-major) with S[i][j] = sum (p_i - pm_i)(q_j - qm_j).  TWO PASSES: the first gives n, sum p,
+ *   sum q and the means pm = sum p / n, qm = sum q / n; the second sums the products of the centred coordinates.  In both, lane
+ *   t of one 256-lane workgroup per pair adds the inliers among matches t, t + 256, ... in ascending order (from +0), and the
+ *   256 partials are folded by halving: x[t] = x[t] + x[t + s] for s = 128, 64, ... 1.  All zeros where best is -1.  The 3 x 3
+ *   SVD (Kabsch) is the caller's, on the host. */
+#define PCMI_MATCH_MAX_TAU 4
+#define PCMI_MATCH_N_QUERY 0
+#define PCMI_MATCH_N_VALID 1
+#define PCMI_MATCH_N_MUTUAL 2
+#define PCMI_MATCH_N_GT 3
+#define PCMI_MATCH_HITS 4
+#define PCMI_MATCH_HITS_GT 8
+#define PCMI_MATCH_STAT_COLS 12
+size_t pcmi_feat_nn_workspace_bytes(int64_t n_queries);
+int pcmi_feat_nn(const float* qf, int64_t q_ld, int64_t nq, const int64_t* q_offs, const float* rf, int64_t r_ld, int64_t nr,
+                 const int64_t* r_offs, int64_t B, int c, const int32_t* query_rows, const int64_t* query_offs,
+                 int64_t n_query_rows, int32_t* nn, float* d2, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_match_stats(const double* xyz0, int64_t n0, const double* xyz1, int64_t n1, const double* T_gt, int64_t B,
+                     const int32_t* query_rows, const int64_t* query_offs, int64_t n_queries, const int32_t* nn01,
+                     const int32_t* nn10, const uint8_t* has_gt, const double* tau_host, int n_tau, int64_t* counts,
+                     double* residual2, pcmi_stream_t stream);
+int pcmi_ransac_score(const double* src, const double* dst, int64_t m, const int64_t* offsets, int64_t B, const int32_t* triples,
+                      int64_t H, double tau, int32_t* counts, int32_t* best, double* Rt, pcmi_stream_t stream);
+int pcmi_rigid_sums(const double* src, const double* dst, int64_t m, const int64_t* offsets, int64_t B, const int32_t* best,
+                    const double* Rt, double tau, double* sums, pcmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -273,6 +273,13 @@ PROTOTYPES = {
     "pcmi_net_timed_launches": (C.c_int, [c_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                           C.POINTER(C.c_int), C.c_int]),
     "pcmi_net_timed_groups_ms": (C.c_int, [c_vp, C.c_int, C.POINTER(c_f32), C.c_int, C.POINTER(C.c_int)]),
+    "pcmi_feat_nn_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_feat_nn": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp,
+                               c_vp, c_sz, c_vp]),
+    "pcmi_match_stats": (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                   C.POINTER(C.c_double), C.c_int, c_vp, c_vp, c_vp]),
+    "pcmi_ransac_score": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp]),
+    "pcmi_rigid_sums": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, C.c_double, c_vp, c_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

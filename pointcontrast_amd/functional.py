@@ -1883,3 +1883,139 @@ def adam_step(w, g, m, v, lr, betas, eps, weight_decay, step):
   require_cuda(w, "adam step")
   check(lib.pcmi_adam_step(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps),
                            float(weight_decay), int(step), cur_stream(w.device)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Validation of the pre-training by feature matching (csrc/featmatch.hip; include/pcmi.h states every rule).  None of
+# these is differentiable and none synchronises.  Offsets are the [B + 1] ascending row offsets of the pairs.
+# ---------------------------------------------------------------------------------------------------------------------
+MATCH_STAT_COLS, MATCH_MAX_TAU = 12, 4
+MATCH_N_QUERY, MATCH_N_VALID, MATCH_N_MUTUAL, MATCH_N_GT, MATCH_HITS, MATCH_HITS_GT = 0, 1, 2, 3, 4, 8
+
+
+def _host_rows_in_segments(rows, row_offsets, seg_offsets, who):
+  """query_rows handed over from the HOST are checked there: every row inside its own pair's segment."""
+  import numpy as np
+  from ._lib import PcmiError
+  r, ro, so = np.asarray(rows).reshape(-1), np.asarray(row_offsets).reshape(-1), np.asarray(seg_offsets).reshape(-1)
+  seg = np.searchsorted(ro, np.arange(r.shape[0]), side="right") - 1
+  ok = (seg >= 0) & (seg < so.shape[0] - 1)
+  segc = np.clip(seg, 0, so.shape[0] - 2)
+  ok &= (r >= so[segc]) & (r < so[segc + 1])
+  if not ok.all():
+    i = int(np.flatnonzero(~ok)[0])
+    raise PcmiError("%s: query_rows[%d] = %d lies outside its pair's segment of the query features" % (who, i, int(r[i])))
+
+
+def _on_host(t):
+  return not (torch.is_tensor(t) and t.is_cuda)
+
+
+def feature_nn(qf, q_offsets, rf, r_offsets, query_rows=None, query_offsets=None):
+  """pcmi_feat_nn: for every query the row of rf, inside the query's own pair, that minimises |a - b|^2 in fp32 -- all pairs
+  in one call.  qf [Nq, C] with q_offsets [B + 1], rf [Nr, C] with r_offsets [B + 1]; C a multiple of 16 in 16 ... 128; rows may
+  be strided.  query_rows int32 [Q] with query_offsets [B + 1]: the rows of qf that are queries (repeats, any order), each in
+  its pair's segment; None: every row.  Returns (nn int32 [Q], the GLOBAL row of rf, the lowest among equal distances; d2
+  float32 [Q]).  nn = -1 and d2 = NaN where the pair has no reference row, the query has a non-finite feature or its row
+  lies outside its segment; a reference row with a non-finite feature is never chosen.  query_rows given from the host are
+  checked against their segments here (PcmiError); on the device the rule above holds.  Bit-identical from run to run."""
+  require_cuda(qf, "feature_nn")
+  require_cuda(rf, "feature_nn")
+  assert qf.dim() == 2 and rf.dim() == 2 and qf.dtype == torch.float32 and rf.dtype == torch.float32, \
+      "feature_nn: float32 [rows, C] features"
+  assert qf.shape[1] == rf.shape[1], "feature_nn: query width %d, reference width %d" % (qf.shape[1], rf.shape[1])
+  assert (query_rows is None) == (query_offsets is None), "feature_nn: query_rows and query_offsets go together"
+  dev = qf.device
+  if query_rows is not None and _on_host(query_rows) and _on_host(query_offsets) and _on_host(q_offsets):
+    _host_rows_in_segments(query_rows, query_offsets, q_offsets, "feature_nn")
+  qf, rf = _c(qf), _c(rf)
+  qo, ro = _offsets(q_offsets, dev), _offsets(r_offsets, dev)
+  assert qo.dim() == 1 and qo.shape == ro.shape and qo.shape[0] >= 2, "feature_nn: offsets [B + 1]"
+  B, c = qo.shape[0] - 1, qf.shape[1]
+  rows = offs = None
+  Q = qf.shape[0]
+  if query_rows is not None:
+    rows, offs = _i32c(torch.as_tensor(query_rows), dev).reshape(-1), _offsets(query_offsets, dev)
+    assert offs.shape == qo.shape, "feature_nn: query_offsets [B + 1]"
+    Q = rows.shape[0]
+  nn = torch.empty(Q, dtype=torch.int32, device=dev)
+  d2 = torch.empty(Q, dtype=torch.float32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_feat_nn_workspace_bytes(Q), dev)
+  check(lib.pcmi_feat_nn(ptr(qf), qf.stride(0), qf.shape[0], ptr(qo), ptr(rf), rf.stride(0), rf.shape[0], ptr(ro), B, c,
+                         ptr(rows), ptr(offs), Q, ptr(nn), ptr(d2), ws, wsb, cur_stream(dev)))
+  return nn, d2
+
+
+def match_stats(xyz0, xyz1, T_gt, query_offsets, nn01, taus, query_rows=None, nn10=None, has_gt=None, counts=None):
+  """pcmi_match_stats: the matches nn01 of the queries checked against the known pose.  xyz0 [N0, 3], xyz1 [N1, 3] float64;
+  T_gt float64 [B, 4, 4]; query_rows int32 [Q] (None: every row of cloud 0, query_offsets then cloud 0's offsets); nn01 int32
+  [Q]; nn10 int32 [Q] (optional: the nearest row of cloud 0 of each matched row, for the mutual check); has_gt uint8 [N0]
+  (optional); taus: 1 ... 4 thresholds.  Returns (counts int64 [B, 12] -- ADDED to the tensor passed in, a fresh one otherwise;
+  columns MATCH_N_QUERY, MATCH_N_VALID, MATCH_N_MUTUAL, MATCH_N_GT, MATCH_HITS + t, MATCH_HITS_GT + t -- and residual2
+  float64 [Q], NaN where the query has no match)."""
+  require_cuda(xyz0, "match_stats")
+  dev = xyz0.device
+  x0, x1 = _f64c(xyz0, dev, "match_stats"), _f64c(xyz1, dev, "match_stats")
+  T = _f64c(T_gt, dev, "match_stats").reshape(-1, 16)
+  qo = _offsets(query_offsets, dev)
+  assert x0.dim() == 2 and x0.shape[1] == 3 and x1.dim() == 2 and x1.shape[1] == 3, "match_stats: xyz0 [N0, 3], xyz1 [N1, 3]"
+  B = qo.shape[0] - 1
+  assert B >= 1 and T.shape[0] == B, "match_stats: T_gt [B, 4, 4] for query_offsets [B + 1]"
+  taus = [float(t) for t in taus]
+  assert 1 <= len(taus) <= MATCH_MAX_TAU, "match_stats: 1 ... %d thresholds" % MATCH_MAX_TAU
+  nn01 = _i32c(nn01, dev).reshape(-1)
+  Q = nn01.shape[0]
+  rows = None if query_rows is None else _i32c(query_rows, dev).reshape(-1)
+  assert (rows is None and Q == x0.shape[0]) or (rows is not None and rows.shape[0] == Q), "match_stats: one nn01 per query"
+  nn10 = None if nn10 is None else _i32c(nn10, dev).reshape(-1)
+  assert nn10 is None or nn10.shape[0] == Q, "match_stats: nn10 [Q]"
+  if has_gt is not None:
+    has_gt = has_gt.to(device=dev, dtype=torch.uint8).contiguous().reshape(-1)
+    assert has_gt.shape[0] == x0.shape[0], "match_stats: has_gt [N0]"
+  if counts is None:
+    counts = torch.zeros((B, MATCH_STAT_COLS), dtype=torch.int64, device=dev)
+  assert counts.shape == (B, MATCH_STAT_COLS) and counts.dtype == torch.int64 and counts.is_contiguous() and counts.device == dev, \
+      "match_stats: counts int64 [B, %d] on the clouds' device" % MATCH_STAT_COLS
+  residual2 = torch.empty(Q, dtype=torch.float64, device=dev)
+  tau_arr = (C.c_double * len(taus))(*taus)
+  check(lib.pcmi_match_stats(ptr(x0), x0.shape[0], ptr(x1), x1.shape[0], ptr(T), B, ptr(rows), ptr(qo), Q, ptr(nn01), ptr(nn10),
+                             ptr(has_gt), tau_arr, len(taus), ptr(counts), ptr(residual2), cur_stream(dev)))
+  return counts, residual2
+
+
+def ransac_score(src, dst, offsets, triples, tau):
+  """pcmi_ransac_score: src, dst float64 [M, 3] (matched points of cloud 0 / cloud 1) with offsets [B + 1]; triples int32
+  [B, H, 3], indices local to each pair's matches, H <= 65536.  Returns (counts int32 [B, H]: the inliers within tau of each
+  hypothesis' transform, -1 for an invalid one; best int32 [B]: the highest count, lowest hypothesis among equals, -1 if none;
+  Rt float64 [B, 12]: the winner's R row-major, then t)."""
+  require_cuda(src, "ransac_score")
+  dev = src.device
+  s, d = _f64c(src, dev, "ransac_score"), _f64c(dst, dev, "ransac_score")
+  assert s.dim() == 2 and s.shape[1] == 3 and s.shape == d.shape, "ransac_score: src, dst [M, 3]"
+  of = _offsets(offsets, dev)
+  B = of.shape[0] - 1
+  tr = _i32c(triples, dev)
+  assert tr.dim() == 3 and tr.shape[0] == B and tr.shape[2] == 3 and B >= 1, "ransac_score: triples [B, H, 3] for offsets [B + 1]"
+  H = tr.shape[1]
+  counts = torch.empty((B, H), dtype=torch.int32, device=dev)
+  best = torch.empty(B, dtype=torch.int32, device=dev)
+  Rt = torch.empty((B, 12), dtype=torch.float64, device=dev)
+  check(lib.pcmi_ransac_score(ptr(s), ptr(d), s.shape[0], ptr(of), B, ptr(tr), H, float(tau), ptr(counts), ptr(best), ptr(Rt),
+                              cur_stream(dev)))
+  return counts, best, Rt
+
+
+def rigid_sums(src, dst, offsets, best, Rt, tau):
+  """pcmi_rigid_sums: over the inliers of each pair's best hypothesis (ransac_score's best and Rt, the same tau) -> float64
+  [B, 16]: n, sum p (3), sum q (3) and the 3 x 3 sum of (p - mean p)(q - mean q)^T, row-major; zeros where best is -1."""
+  require_cuda(src, "rigid_sums")
+  dev = src.device
+  s, d = _f64c(src, dev, "rigid_sums"), _f64c(dst, dev, "rigid_sums")
+  assert s.dim() == 2 and s.shape[1] == 3 and s.shape == d.shape, "rigid_sums: src, dst [M, 3]"
+  of = _offsets(offsets, dev)
+  B = of.shape[0] - 1
+  best, Rt = _i32c(best, dev).reshape(-1), _f64c(Rt, dev, "rigid_sums").reshape(-1, 12)
+  assert B >= 1 and best.shape[0] == B and Rt.shape[0] == B, "rigid_sums: best [B], Rt [B, 12] for offsets [B + 1]"
+  out = torch.empty((B, 16), dtype=torch.float64, device=dev)
+  check(lib.pcmi_rigid_sums(ptr(s), ptr(d), s.shape[0], ptr(of), B, ptr(best), ptr(Rt), float(tau), ptr(out), cur_stream(dev)))
+  return out

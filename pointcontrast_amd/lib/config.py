@@ -17,6 +17,9 @@ DEFAULTS = {
         "use_random_scale": False, "min_scale": 0.8, "max_scale": 1.2,
         "use_random_rotation": True, "rotation_range": 360,
         "stat_freq": 40, "lr_update_freq": 1000, "positive_pair_search_voxel_size_multiplier": 1.5,
+        # not in the reference, which never validates: feature matching on held-out pairs every val_freq iterations
+        # (0 = off, the loop is the reference's), over at most val_max_batches batches (None = the whole list)
+        "val_freq": 0, "val_max_batches": None,
     },
     "net": {"model": "Res16UNet34C", "model_n_out": 32, "conv1_kernel_size": 3, "normalize_feature": True},
     "opt": {"optimizer": "SGD", "max_iter": 300000, "lr": 0.1, "momentum": 0.8, "weight_decay": 1e-4,
@@ -27,7 +30,9 @@ DEFAULTS = {
              # "fp32" or "bf16": the convolution precision mode ("Convolution precision")
              "conv_precision": "fp32"},
     "data": {"dataset": "SyntheticScanNetPairDataset", "voxel_size": 0.025, "dataset_root_dir": None,
-             "scannet_match_dir": None, "num_pairs": 64},
+             "scannet_match_dir": None, "num_pairs": 64,
+             # the held-out pair list of the validation, under dataset_root_dir (as scannet_match_dir)
+             "val_match_dir": None},
 }
 
 

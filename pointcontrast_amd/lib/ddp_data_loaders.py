@@ -179,6 +179,36 @@ def make_data_loader(config, batch_size, num_threads=0):
                                      drop_last=True)
 
 
+VAL_SEED_OFFSET = 7919  # the synthetic validation pairs: the generator's seed moved away from the training pairs'
+
+
+def make_val_data_loader(config, batch_size):
+  """The held-out pairs of trainer.validate (the reference has no counterpart): the training loader's dataset class and batch
+  form over a second pair list, data.val_match_dir under data.dataset_root_dir -- no random scale, no feature jitter,
+  rotations from the dataset's own generator seeded once, pairs in list order, one finite pass, produced in this process.
+  Nothing here draws from a global random generator, so validating does not move the training run's random streams.
+  SyntheticScanNetPairDataset needs no list: data.val_num_pairs (default 8) pairs from seeds the training set does not use."""
+  import copy
+  if config.data.dataset not in dataset_str_mapping:
+    raise ValueError("Dataset %s does not exist in %s" % (config.data.dataset, ", ".join(dataset_str_mapping)))
+  cfg = copy.deepcopy(config)
+  if config.data.dataset == "ScanNetMatchPairDataset":
+    if not config.data.get("val_match_dir", None):
+      raise ValueError("validation needs data.val_match_dir: a pair list under data.dataset_root_dir")
+    cfg.data.scannet_match_dir = config.data.val_match_dir
+    # (phase stays "train": the class defines no other, and the list is what makes the pairs held-out)
+    dset = ScanNetMatchPairDataset("train", transform=None, random_rotation=config.trainer.use_random_rotation, random_scale=False,
+                                   manual_seed=True, config=cfg)
+  else:
+    cfg.misc.seed = config.misc.get("seed", 0) + VAL_SEED_OFFSET
+    dset = SyntheticScanNetPairDataset(config=cfg, num_pairs=config.data.get("val_num_pairs", 8))
+  # batch_size: pairs per batch on the validating rank (the master validates alone).  generator: every iter() of a
+  # DataLoader draws a base seed, from torch's GLOBAL generator unless it has one of its own -- PointNCELossTrainer's
+  # torch.rand would then see a different stream after a validation.
+  return torch.utils.data.DataLoader(dset, batch_size=max(int(batch_size), 1), shuffle=False, num_workers=0, collate_fn=default_collate_pair_fn,
+                                     drop_last=False, generator=torch.Generator().manual_seed(config.misc.get("seed", 0)))
+
+
 class FixedBatchLoader:
   """Replays pre-generated batches forever (benchmarks / tests: inputs staged before timing)."""
 

@@ -12,7 +12,9 @@ checkpoint layout (:151-169) -- with these deliberate differences:
   * `_train_iter` returns the loss as a 0-dim device tensor; `.item()` happens only when the
     loop logs (stat_freq), so the host never waits on the GPU inside an iteration
     (the reference syncs every iteration at :316-318,433);
-  * no torch.cuda.empty_cache() per iteration (:321,437) and no autograd anomaly mode (:36).
+  * no torch.cuda.empty_cache() per iteration (:321,437) and no autograd anomaly mode (:36);
+  * `validate` (the reference has none): feature matching on held-out pairs, every trainer.val_freq iterations when that is
+    not 0 (lib/feature_match.py).  It reads the network and changes nothing the training step reads.
 """
 import logging
 import os
@@ -49,7 +51,7 @@ from .checkpoint import load_state  # noqa: E402,F401  (pc/lib/ddp_trainer.py:54
 
 class ContrastiveLossTrainer:
 
-  def __init__(self, config, data_loader):
+  def __init__(self, config, data_loader, val_data_loader=None):
     assert config.misc.use_gpu and torch.cuda.is_available(), "the pre-training path runs on a gfx950 GPU"
     num_feats = 3  # ones (+ jitter), pc/lib/ddp_data_loaders.py:248-252
     self.config = config
@@ -107,6 +109,9 @@ class ContrastiveLossTrainer:
     self.data_loader = data_loader
     self.neg_thresh, self.pos_thresh = config.trainer.neg_thresh, config.trainer.pos_thresh
     self.stat_freq, self.lr_update_freq = config.trainer.stat_freq, config.trainer.lr_update_freq
+    # trainer.val_freq: 0 (default) = no validation, the loop is the reference's; n > 0 = validate() every n iterations
+    self.val_freq = int(config.trainer.get("val_freq", 0) or 0)
+    self.val_data_loader, self.match_evaluator, self.val_metrics = val_data_loader, None, None
 
     if config.misc.weight:
       state = torch.load(config.misc.weight, map_location="cpu", weights_only=False)
@@ -386,6 +391,78 @@ class ContrastiveLossTrainer:
     finally:
       self._prefetch_drain()
 
+  # -- validation: feature matching on held-out pairs (lib/feature_match.py) -------------------------------------------
+  def _inference_features(self, input_dict):
+    """The features of both clouds of a batch from the inference forward: running BatchNorm estimates, which are not
+    updated; nothing of a training pass is held or changed."""
+    feats = []
+    for i in (0, 1):
+      st = ME.SparseTensor(input_dict["sinput%d_F" % i], coords=input_dict["sinput%d_C" % i]).to(self.cur_device)
+      if self.engine is not None:
+        feats.append(self.engine.forward(0, st, False))
+      else:
+        was_training = self.model.training
+        self.model.eval()
+        try:
+          with torch.no_grad(), ME.conv_precision(self.conv_precision):
+            feats.append(self.model(st).F)
+        finally:
+          self.model.train(was_training)
+    return feats
+
+  def validate(self, val_loader, max_batches=None, draws=None):
+    """Feature matching on the pairs of val_loader (batches of the training loader's form): hit ratio, feature-match recall,
+    mutual ratio and RANSAC registration recall -- the keys of FeatureMatchEvaluator.compute_metrics.  max_batches: stop
+    after that many batches (None: the whole loader; an infinite loader needs it).  draws: one MatchDraws per batch
+    (otherwise the evaluator's own seeded generator, the same draws in every call).  One read-back, at the end.  The
+    evaluator stays on self.match_evaluator; its `hit_thresholds` etc. come from the `val` group of the configuration."""
+    from .feature_match import FeatureMatchEvaluator
+    if self.match_evaluator is None:
+      opts = dict(self.config.get("val", {}) or {})
+      self.match_evaluator = FeatureMatchEvaluator(self.config.data.voxel_size, device=self.cur_device, **opts)
+    ev = self.match_evaluator
+    ev.reset()
+    dset = getattr(val_loader, "dataset", None)
+    if hasattr(dset, "reset_seed"):
+      dset.reset_seed()  # the same rotations in every pass: two validations are comparable
+    n = 0
+    for input_dict in val_loader:
+      if max_batches is not None and n >= max_batches:
+        break
+      F0, F1 = self._inference_features(input_dict)
+      ev.step(F0, F1, input_dict["sinput0_C"], input_dict["sinput1_C"], input_dict["T_gt"], input_dict["len_batch"],
+              correspondences=input_dict.get("correspondences"), draws=None if draws is None else draws[n])
+      n += 1
+    self.val_metrics = ev.compute_metrics()
+    return self.val_metrics
+
+  def _validate_in_loop(self, curr_iter):
+    """The master's validation between two iterations.  A helper thread that is still preparing the next batch is waited
+    for (its batch is kept): it shares the planning stream and the handle pool with the uploads below.  A helper that is
+    drawing from the global numpy generator is joined too, although validation never touches that generator."""
+    th = getattr(self, "_prefetch_thread", None)
+    if th is not None:
+      th.join()
+    self._join_draws()
+    if self.val_data_loader is None:
+      from .ddp_data_loaders import make_val_data_loader
+      self.val_data_loader = make_val_data_loader(self.config, self.batch_size)
+    # The training run's random streams -- `random`, numpy's and torch's global generators, which the loaders, the feature
+    # jitter and both trainers' draws consume -- are put back after the pass: the validation loader of this package draws
+    # from none of them, but a loader handed to the constructor may (every iter() of a torch DataLoader without a generator
+    # of its own takes a seed from torch's), and a validated run must stay bit-identical to one that is not.  Nobody else
+    # draws meanwhile: both helpers were joined above.
+    import random
+    saved = (random.getstate(), np.random.get_state(), torch.get_rng_state())
+    try:
+      m = self.validate(self.val_data_loader, self.config.trainer.get("val_max_batches", None))
+    finally:
+      random.setstate(saved[0])
+      np.random.set_state(saved[1])
+      torch.set_rng_state(saved[2])
+    logging.info("Validation [%d]: %s", curr_iter, {k: (round(v, 5) if isinstance(v, float) else v) for k, v in m.items() if k != "pairs"})
+    return m
+
   def _train_loop(self):
     curr_iter = self.curr_iter
     it = iter(self.data_loader)
@@ -409,6 +486,8 @@ class ContrastiveLossTrainer:
                      total_timer.avg - data_meter.avg, total_timer.avg, self.scheduler.get_last_lr())
         data_meter.reset()
         total_timer.reset()
+      if self.val_freq and curr_iter % self.val_freq == 0 and self.is_master:
+        self._validate_in_loop(curr_iter)
     self.curr_iter = curr_iter
 
 
@@ -579,8 +658,8 @@ class HardestContrastiveLossTrainer(ContrastiveLossTrainer):
 
 class PointNCELossTrainer(ContrastiveLossTrainer):
 
-  def __init__(self, config, data_loader):
-    super().__init__(config, data_loader)
+  def __init__(self, config, data_loader, val_data_loader=None):
+    super().__init__(config, data_loader, val_data_loader)
     self.T, self.npos = config.misc.nceT, config.misc.npos
 
   @staticmethod
