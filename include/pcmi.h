@@ -493,12 +493,33 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
  * pcmi_corpus_overlap_counts = the ordered-pair query loop of dp/compute_full_overlapping.py:63-73 for all pairs at
  *   once: counts [F, F] int32 (device, row-major, written whole), counts[i*F + j] = #{q in frame j : some p in frame i
  *   with ((ex ex + ey ey) + ez ez) <= radius^2, e = q - p} (pcmi_match_radius's test) for i != j; the diagonal is 0.
- * PCMI_ERR_RANGE: a point outside +-2^20 cells (voxels of its frame, or radius-sized cells of the overlap grid). */
+ * PCMI_ERR_RANGE: a point outside +-2^20 cells (voxels of its frame, or radius-sized cells of the overlap grid).
+ * pcmi_corpus_backproject_color = a colour for every row of pcmi_corpus_backproject (the reference exports the colour
+ *   frames, reader.py --export_color_images, but its preprocessing never reads them): the same depth stack, depth
+ *   intrinsic and depth_shift, with color_images uint8 [F, Hc, Wc, 3] (DEVICE), color_intrinsic_host = the 4x4
+ *   intrinsic_color.txt (fxc = Kc[0,0], fyc = Kc[1,1], cxc = Kc[0,2], cyc = Kc[1,2]) and depth_to_color_host = M, the
+ *   4x4 inv(extrinsic_color) extrinsic_depth (HOST, row-major; rows 0..2 are read).  Per pixel with depth != 0, fp64,
+ *   every operation rounded on its own (no FMA):
+ *     d, X, Y, Z = d as above (camera space, no pose);  q_r = ((X M[r,0] + Y M[r,1]) + Z M[r,2]) + M[r,3], r = 0, 1, 2;
+ *     uc = (fxc q0) / q2 + cxc, vc = (fyc q1) / q2 + cyc;  px = floor(uc + 0.5), py = floor(vc + 0.5);
+ *   the point takes color_images[f, py, px, :] if q2 > 0, uc and vc are finite, 0 <= px < Wc and 0 <= py < Hc (tested
+ *   on the doubles, before any conversion to an integer); otherwise it is (0, 0, 0) and adds 1 to uncolored[f].
+ *   color: uint8 [F*H*W, 3] capacity, row k = the colour of row k of pcmi_corpus_backproject's points (zero-depth pixels
+ *   dropped, the rest row-major, frame after frame); uncolored int64 [F] (DEVICE, integer atomics: the same bits from
+ *   run to run); offsets [F+1] (DEVICE) equal pcmi_corpus_backproject's.  offsets_host [F+1] may be NULL: then the
+ *   call does not wait for the stream at all; given, it is filled after the one wait pcmi_corpus_backproject has too.
+ *   F*H*W < 2^31, Hc, Wc >= 1, F*Hc*Wc < 2^40.  ws: pcmi_corpus_backproject_color_workspace_bytes(F, H, W). */
 size_t pcmi_corpus_backproject_workspace_bytes(int64_t n_frames, int64_t height, int64_t width);
 int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width,
                             const double* intrinsic_host, const double* poses, double depth_shift, double* points,
                             int64_t* offsets, int32_t* nan_count, int64_t* offsets_host, void* ws, size_t ws_bytes,
                             pcmi_stream_t stream);
+size_t pcmi_corpus_backproject_color_workspace_bytes(int64_t n_frames, int64_t height, int64_t width);
+int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width,
+                                  const double* intrinsic_host, double depth_shift, const uint8_t* color_images,
+                                  int64_t color_height, int64_t color_width, const double* color_intrinsic_host,
+                                  const double* depth_to_color_host, uint8_t* color, int64_t* uncolored, int64_t* offsets,
+                                  int64_t* offsets_host, void* ws, size_t ws_bytes, pcmi_stream_t stream);
 size_t pcmi_corpus_voxel_centroids_workspace_bytes(int64_t n_points, int64_t n_frames);
 int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, const int64_t* offsets_host,
                                 int64_t n_frames, double voxel_size, double* centroids, int64_t* voxel_offsets,
@@ -1044,7 +1065,15 @@ int pcmi_seg_color_augment(const float* feats_src, int64_t n_src, const int64_t*
  *   pcd{s} [out_rows, 3] = fp32(p), F{s} [out_rows, 3] = fp32(1 + (mu + sigma z)) where jitter_on[2 b + s] != 0 (DEVICE int32
  *   [2 B]) and noise is given, else 1; z = noise [n_raw, 3] (fp32 standard normals, widened; NULL = no jitter) at the row
  *   first_index[r] -- the noise belongs to the RAW point, so it is defined before the voxel counts are known.  T_gt [4 B, 4] =
- *   fp32(trans).  A row that would fall outside out_rows is not written.  ws: unused (pcmi_pair_collate_workspace_bytes). */
+ *   fp32(trans).  A row that would fall outside out_rows is not written.  ws: unused (pcmi_pair_collate_workspace_bytes).
+ * pcmi_pair_color_features = the features of a corpus built with colours (data.use_color; the reference has its "#dummy color"
+ *   here, pc:204-206, :248-249), one launch after pcmi_pair_collate in stream order, over the same F{s}: color [n_raw, 3] (uint8,
+ *   the RGB of the raw rows of the batch), first_index / m_max / vox_offsets / side_offsets / B as pcmi_pair_voxelize left them,
+ *   noise / n_raw / jitter_on / mu / sigma / out_rows as in pcmi_pair_collate.  Voxel row r of cloud 2 b + s goes to the row
+ *   pcmi_pair_collate sends it to; per channel k, F{s}[k] = fp32((c_k / 255 - 0.5) + (mu + sigma z_k)) where jitter_on[2 b + s] != 0
+ *   and noise is given, else fp32(c_k / 255 - 0.5): c (widened to fp64) and z at the raw row first_index[r] -- a voxel has the
+ *   colour of its first point, as it has that point's position.  A row outside out_rows, or whose first_index is outside
+ *   [0, n_raw), is not written.  Nothing but F0 and F1 is written.  ws: unused (pcmi_pair_color_features_workspace_bytes). */
 #define PCMI_PAIR_FLAG_NONFINITE 1
 #define PCMI_PAIR_FLAG_RANGE 2
 #define PCMI_PAIR_FLAG_MATCHES 4
@@ -1067,6 +1096,11 @@ int pcmi_pair_collate(const double* points, const int32_t* coords, const int32_t
                       const int64_t* vox_offsets, const int64_t* side_offsets, int64_t B, const double* trans, const float* noise,
                       int64_t n_raw, const int32_t* jitter_on, double mu, double sigma, int64_t out_rows, int32_t* C0, int32_t* C1,
                       float* pcd0, float* pcd1, float* F0, float* F1, float* T_gt, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_pair_color_features_workspace_bytes(int64_t m_max, int64_t B);
+int pcmi_pair_color_features(const uint8_t* color, const int32_t* first_index, int64_t m_max, const int64_t* vox_offsets,
+                             const int64_t* side_offsets, int64_t B, const float* noise, int64_t n_raw, const int32_t* jitter_on,
+                             double mu, double sigma, int64_t out_rows, float* F0, float* F1, void* ws, size_t ws_bytes,
+                             pcmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The input of VoteNet detection fine-tuning for a batch of scans (csrc/detect_input.hip) -- what the reference runs per scan on

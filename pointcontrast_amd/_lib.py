@@ -150,6 +150,10 @@ PROTOTYPES = {
     "pcmi_corpus_backproject_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "pcmi_corpus_backproject": (C.c_int, [c_vp, c_i64, c_i64, c_i64, C.POINTER(C.c_double), c_vp, C.c_double, c_vp, c_vp,
                                           c_vp, C.POINTER(c_i64), c_vp, c_sz, c_vp]),
+    "pcmi_corpus_backproject_color_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pcmi_corpus_backproject_color": (C.c_int, [c_vp, c_i64, c_i64, c_i64, C.POINTER(C.c_double), C.c_double, c_vp, c_i64, c_i64,
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double), c_vp, c_vp, c_vp, C.POINTER(c_i64), c_vp,
+                                                c_sz, c_vp]),
     "pcmi_corpus_voxel_centroids_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcmi_corpus_voxel_centroids": (C.c_int, [c_vp, c_vp, C.POINTER(c_i64), c_i64, C.c_double, c_vp, c_vp, C.POINTER(c_i64),
                                               c_vp, c_sz, c_vp]),
@@ -233,6 +237,9 @@ PROTOTYPES = {
     "pcmi_pair_collate_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcmi_pair_collate": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_double, C.c_double, c_i64,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_pair_color_features_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_pair_color_features": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, C.c_double, C.c_double, c_i64, c_vp,
+                                           c_vp, c_vp, c_sz, c_vp]),
     "pcmi_det_sample_transform": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp]),
     "pcmi_det_votes_transform": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

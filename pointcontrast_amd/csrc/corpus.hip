@@ -10,6 +10,9 @@
 //       -> pcmi_corpus_overlap_counts: one hash grid of r-sized cells over the centroids of all frames; every query point
 //          walks its 27 cells once per block of 64 frames and sets one bit per frame it meets; the bits are summed per
 //          workgroup in LDS and land in the integer matrix C with one integer atomic per (workgroup, frame).
+// Beyond the reference (its reader.py exports the colour frames, its preprocessing never reads them):
+//       -> pcmi_corpus_backproject_color: the colour of every back-projected point, from the frame's colour image through
+//          the colour intrinsic and the depth-to-colour extrinsic, in the row order of pcmi_corpus_backproject.
 // Everything is integer or exactly-rounded fp64 work with a fixed order (explicit round-to-nearest operations, no FMA
 // contraction, IEEE division), so the outputs are bit-identical to the numpy restatement in tests/pair_corpus_ref.py.
 #include <hipcub/hipcub.hpp>
@@ -116,6 +119,62 @@ __global__ void bp_offsets_kernel(const int32_t* __restrict__ flags, const int32
   const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (f < n_frames) offsets[f] = pos[f * hw];
   if (f == n_frames) offsets[f] = (int64_t)pos[n_frames * hw - 1] + flags[n_frames * hw - 1];
+}
+
+// ---- colour of every back-projected point --------------------------------------------------------------------------
+struct ColorCamera {
+  double fx, fy, cx, cy;
+  double M[12];  // rows 0..2 of depth_to_color, row-major
+};
+
+// One lane per depth pixel, the compaction of bp_points_kernel (pos = the same exclusive scan), so that colour row k is
+// point row k.  The camera-space point of the pixel goes through M into the colour camera and onto its image:
+//   q_r = ((X M[r,0] + Y M[r,1]) + Z M[r,2]) + M[r,3], uc = (fxc q0) / q2 + cxc, vc = (fyc q1) / q2 + cyc,
+//   px = floor(uc + 0.5), py = floor(vc + 0.5); everything is decided on the doubles, the integers come last.
+// Neighbouring lanes read neighbouring depth words and, where the depth has no holes, write neighbouring 3-byte rows
+// (a wave's rows are one run of at most 192 bytes); the colour fetch is a gather that follows the image's rows as long
+// as the two cameras look the same way.  uncolored[f]: one 64-bit integer add per (wave, frame).
+__global__ __launch_bounds__(kThreads) void bp_color_kernel(const uint16_t* __restrict__ depth, int64_t n_frames, int64_t height,
+                                                            int64_t width, Intrinsic K, double shift,
+                                                            const uint8_t* __restrict__ images, int64_t c_height, int64_t c_width,
+                                                            ColorCamera cam, const int32_t* __restrict__ pos,
+                                                            uint8_t* __restrict__ color, unsigned long long* uncolored) {
+  const int64_t hw = height * width;
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint16_t raw = k < n_frames * hw ? depth[k] : (uint16_t)0;
+  const int64_t f = raw != 0 ? k / hw : -1;
+  bool miss = false;
+  if (raw != 0) {
+    const int64_t pix = k - f * hw;
+    const double u = (double)(pix % width), v = (double)(pix / width);
+    const double d = div_rn((double)raw, shift);
+    const double X = add_rn(div_rn(mul_rn(add_rn(u, -K.cx), d), K.fx), K.bx);
+    const double Y = add_rn(div_rn(mul_rn(add_rn(v, -K.cy), d), K.fy), K.by);
+    double q[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+      q[r] = add_rn(add_rn(add_rn(mul_rn(X, cam.M[4 * r]), mul_rn(Y, cam.M[4 * r + 1])), mul_rn(d, cam.M[4 * r + 2])), cam.M[4 * r + 3]);
+    const double uc = add_rn(div_rn(mul_rn(cam.fx, q[0]), q[2]), cam.cx);
+    const double vc = add_rn(div_rn(mul_rn(cam.fy, q[1]), q[2]), cam.cy);
+    const double px = floor(add_rn(uc, 0.5)), py = floor(add_rn(vc, 0.5));
+    const bool hit = q[2] > 0.0 && isfinite(uc) && isfinite(vc) && px >= 0.0 && px < (double)c_width && py >= 0.0 && py < (double)c_height;
+    uint8_t c[3] = {0, 0, 0};
+    if (hit) {
+      const uint8_t* src = images + 3 * ((f * c_height + (int64_t)py) * c_width + (int64_t)px);
+      c[0] = src[0], c[1] = src[1], c[2] = src[2];
+    }
+    uint8_t* o = color + 3 * (int64_t)pos[k];
+    o[0] = c[0], o[1] = c[1], o[2] = c[2];
+    miss = !hit;
+  }
+  unsigned long long rem = __ballot(miss);  // (all lanes arrive here: nothing returned above)
+  while (rem) {
+    const int leader = __ffsll((long long)rem) - 1;
+    const int lf = __shfl((int)f, leader, 64);  // (n_frames < 2^31)
+    const unsigned long long same = __ballot(miss && (int)f == lf);
+    if ((int)(threadIdx.x & 63) == leader) atomicAdd(&uncolored[lf], (unsigned long long)__popcll(same));
+    rem &= ~same;
+  }
 }
 
 // ---- voxel centroids ---------------------------------------------------------------------------------------------
@@ -413,6 +472,54 @@ int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t hei
   PCMI_LAUNCH_CHECK();
   PCMI_HIP_CHECK(hipMemcpyAsync(offsets_host, offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  return PCMI_OK;
+}
+
+size_t pcmi_corpus_backproject_color_workspace_bytes(int64_t n_frames, int64_t height, int64_t width) {
+  return pcmi_corpus_backproject_workspace_bytes(n_frames, height, width);  // the flags, their scan and its temporary
+}
+
+int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width, const double* intrinsic_host,
+                                  double depth_shift, const uint8_t* color_images, int64_t color_height, int64_t color_width,
+                                  const double* color_intrinsic_host, const double* depth_to_color_host, uint8_t* color,
+                                  int64_t* uncolored, int64_t* offsets, int64_t* offsets_host, void* ws, size_t ws_bytes,
+                                  pcmi_stream_t stream) {
+  PCMI_REQUIRE(n_frames > 0 && height > 0 && width > 0 && n_frames * height * width < (1ll << 31) && intrinsic_host && depth && color &&
+                   uncolored && offsets && depth_shift > 0,
+               PCMI_ERR_INVALID, "corpus_backproject_color: bad argument (%lld frames of %lld x %lld)", (long long)n_frames,
+               (long long)height, (long long)width);
+  PCMI_REQUIRE(color_height > 0 && color_width > 0 && color_height < (1ll << 31) && color_width < (1ll << 31) &&
+                   n_frames * color_height * color_width < (1ll << 40) && color_images && color_intrinsic_host && depth_to_color_host,
+               PCMI_ERR_INVALID, "corpus_backproject_color: bad colour images (%lld frames of %lld x %lld x 3)", (long long)n_frames,
+               (long long)color_height, (long long)color_width);
+  const int64_t hw = height * width, n = n_frames * hw;
+  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_backproject_color_workspace_bytes(n_frames, height, width), PCMI_ERR_WORKSPACE,
+               "corpus_backproject_color: workspace too small");
+  hipStream_t st = as_stream(stream);
+  Carve cv{(char*)ws, ws_bytes};
+  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
+  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
+  size_t tb = scan_bytes(n);
+  void* temp = cv.take(tb);
+  PCMI_REQUIRE(flags && pos && temp, PCMI_ERR_WORKSPACE, "corpus_backproject_color: workspace too small");
+  const double *A = intrinsic_host, *Ac = color_intrinsic_host;  // 4x4 row-major (intrinsic_depth.txt, intrinsic_color.txt)
+  const Intrinsic K{A[0], A[5], A[2], A[6], A[3], A[7]};
+  ColorCamera cam{Ac[0], Ac[5], Ac[2], Ac[6], {}};
+  for (int q = 0; q < 12; ++q) cam.M[q] = depth_to_color_host[q];
+  PCMI_HIP_CHECK(hipMemsetAsync(uncolored, 0, (size_t)n_frames * 8, st));
+  const unsigned gn = (unsigned)ceil_div(n, kThreads);
+  bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, flags);
+  PCMI_LAUNCH_CHECK();
+  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, flags, pos, (int)n, st));
+  bp_color_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, depth_shift, color_images, color_height, color_width, cam,
+                                           pos, color, (unsigned long long*)uncolored);
+  PCMI_LAUNCH_CHECK();
+  bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(flags, pos, n_frames, hw, offsets);
+  PCMI_LAUNCH_CHECK();
+  if (offsets_host) {  // the one wait of pcmi_corpus_backproject; without offsets_host the call does not wait at all
+    PCMI_HIP_CHECK(hipMemcpyAsync(offsets_host, offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
+    PCMI_HIP_CHECK(hipStreamSynchronize(st));
+  }
   return PCMI_OK;
 }
 

@@ -4,6 +4,7 @@
 //   * ME.utils.sparse_quantize(xyz / voxel_size, return_index=True) of both frames, floor      (:228-239, :258-259)
 //   * get_matching_indices within voxel_size * multiplier * scale                             (:36-49, :241)
 //   * FeatureJitter and default_collate_pair_fn                                                (:52-112, :248-252)
+//   * and, where the reference has its "#dummy color" (:204-206, :248-249), the features of a corpus with colours
 // Written from the semantics in include/pcmi.h; gfx950, wave64.  Every random quantity is an input.  A batch of B pairs is
 // 2 B clouds in one row-major array; every kernel launches over all rows of the batch and looks its segment up.
 //
@@ -512,6 +513,34 @@ __global__ __launch_bounds__(kThreads) void co_kernel(const double* __restrict__
   }
 }
 
+// ---- colour features -------------------------------------------------------------------------------------------------------
+// co_kernel's rows once more: F = fp32((c / 255 - 0.5) + (mu + sigma z)), c and z of the voxel's first raw point.  A lane owns one
+// voxel row: 3 colour bytes and 3 noise words gathered at first_index (ascending inside a cloud, so neighbouring lanes read
+// forward through the raw rows), 12 contiguous bytes stored next to its neighbours'.
+__global__ __launch_bounds__(kThreads) void cf_kernel(const uint8_t* __restrict__ color, const int32_t* __restrict__ first_index, int64_t m_max,
+                                                      const int64_t* __restrict__ voff, int B, const int64_t* __restrict__ side,
+                                                      const float* __restrict__ noise, int64_t n_raw, const int32_t* __restrict__ jitter_on,
+                                                      double mu, double sigma, int64_t out_rows, float* __restrict__ F0, float* __restrict__ F1) {
+  const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (r >= m_max) return;
+  const int c = cloud_of(voff, 2 * B, r);
+  if (c < 0) return;
+  int64_t lo, hi;
+  cloud_rows(voff, c, m_max, lo, hi);
+  if (r < lo || r >= hi) return;
+  const int s = c & 1, b = c >> 1;
+  const int64_t dst = side[s * (B + 1) + b] + (r - lo);
+  const int64_t src = first_index[r];
+  if (dst < 0 || dst >= out_rows || src < 0 || src >= n_raw) return;
+  const bool on = noise && jitter_on[c] != 0;
+  float* F = (s ? F1 : F0) + 3 * dst;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double v = add_rn((double)color[3 * src + a] / 255.0, -0.5);
+    F[a] = (float)(on ? add_rn(v, add_rn(mu, mul_rn(sigma, (double)noise[3 * src + a]))) : v);
+  }
+}
+
 static bool batch_ok(int64_t n, int64_t B) { return n >= 0 && n < (1ll << 31) - kThreads && B >= 1 && B <= kMaxPairs; }
 
 static size_t scan_temp_bytes32(int64_t items) {
@@ -718,6 +747,30 @@ int pcmi_pair_collate(const double* points, const int32_t* coords, const int32_t
   co_kernel<<<(unsigned)ceil_div(threads, kThreads), kThreads, 0, as_stream(stream)>>>(points, coords, first_index, out_rows > 0 ? m_max : 0,
                                                                                        vox_offsets, (int)B, side_offsets, trans, noise, n_raw,
                                                                                        jitter_on, mu, sigma, out_rows, out, T_gt);
+  PCMI_LAUNCH_CHECK();
+  return PCMI_OK;
+}
+
+size_t pcmi_pair_color_features_workspace_bytes(int64_t m_max, int64_t B) { return batch_ok(m_max, B) ? 256 : 0; }
+
+// the features ScanNetMatchPairDataset builds with data.use_color (feats = color / 255 - 0.5 in front of FeatureJitter), where the
+// reference has its "#dummy color" (pretrain/pointcontrast/lib/ddp_data_loaders.py:204-206, :248-249)
+int pcmi_pair_color_features(const uint8_t* color, const int32_t* first_index, int64_t m_max, const int64_t* vox_offsets,
+                             const int64_t* side_offsets, int64_t B, const float* noise, int64_t n_raw, const int32_t* jitter_on, double mu,
+                             double sigma, int64_t out_rows, float* F0, float* F1, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
+  (void)ws;
+  (void)ws_bytes;
+  PCMI_REQUIRE(batch_ok(m_max, B) && n_raw >= 0 && out_rows >= 0, PCMI_ERR_INVALID,
+               "pair_color_features: bad shape (0 <= m_max %lld < 2^31 - 256; 1 <= B %lld <= %d; n_raw %lld, out_rows %lld >= 0)",
+               (long long)m_max, (long long)B, kMaxPairs, (long long)n_raw, (long long)out_rows);
+  PCMI_REQUIRE(mu == mu && sigma == sigma && fabs(mu) < 1e300 && fabs(sigma) < 1e300, PCMI_ERR_INVALID,
+               "pair_color_features: mu and sigma must be finite");
+  PCMI_REQUIRE(vox_offsets && side_offsets && (m_max == 0 || first_index) && (n_raw == 0 || color) && (out_rows == 0 || (F0 && F1)) &&
+                   (!noise || jitter_on), PCMI_ERR_INVALID, "pair_color_features: null pointer (noise needs jitter_on)");
+  if (m_max == 0 || out_rows == 0 || n_raw == 0) return PCMI_OK;  // no row to write
+  cf_kernel<<<(unsigned)ceil_div(m_max, kThreads), kThreads, 0, as_stream(stream)>>>(color, first_index, m_max, vox_offsets, (int)B,
+                                                                                     side_offsets, noise, n_raw, jitter_on, mu, sigma, out_rows,
+                                                                                     F0, F1);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -1420,6 +1420,32 @@ def pair_collate(vox, trans, noise=None, jitter_on=None, mu=0.0, sigma=0.01, out
   return out
 
 
+def pair_color_features(color, vox, collated, noise=None, jitter_on=None, mu=0.0, sigma=0.01):
+  """pcmi_pair_color_features: writes the colour features into sinput0_F / sinput1_F of pair_collate's result `collated`, in
+  place and after it in stream order.  color uint8 [n_raw, 3] (the RGB of the raw rows pair_voxelize's first_index points into),
+  noise / jitter_on / mu / sigma as in pair_collate.  F = fp32((c / 255 - 0.5) + (mu + sigma z)), or fp32(c / 255 - 0.5) without
+  jitter.  Returns `collated`."""
+  require_cuda(color, "pair_color_features")
+  dev = color.device
+  assert color.dtype == torch.uint8 and color.dim() == 2 and color.shape[1] == 3, "pair_color_features: color uint8 [n_raw, 3]"
+  col = color.contiguous()
+  voff, side, first = vox["vox_offsets"], vox["side_offsets"], vox["first_index"]
+  B = side.shape[1] - 1
+  nz = None if noise is None else _f32c(noise.to(dev), "pair_color_features")
+  assert nz is None or tuple(nz.shape) == (col.shape[0], 3), "pair_color_features: noise [n_raw, 3]"
+  on = None if nz is None else _i32c(torch.as_tensor(jitter_on), dev).reshape(-1)
+  assert on is None or on.shape[0] == 2 * B, "pair_color_features: jitter_on [2 B]"
+  F0, F1 = collated["sinput0_F"], collated["sinput1_F"]
+  for F in (F0, F1):
+    assert F.dtype == torch.float32 and F.dim() == 2 and F.shape[1] == 3 and F.is_contiguous() and F.device == dev and \
+        F.shape[0] == F0.shape[0], "pair_color_features: sinput{0,1}_F float32 [out_rows, 3] on the colours' device, contiguous"
+  m_max = first.shape[0]
+  ws, wsb = ws_args(lib.pcmi_pair_color_features_workspace_bytes(m_max, B), dev)
+  check(lib.pcmi_pair_color_features(ptr(col), ptr(first), m_max, ptr(voff), ptr(side), B, ptr(nz), col.shape[0], ptr(on), float(mu),
+                                     float(sigma), F0.shape[0], ptr(F0), ptr(F1), ws, wsb, cur_stream(dev)))
+  return collated
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The input of detection fine-tuning (csrc/detect_input.hip): what ScannetDetectionDataset / SunrgbdDetectionVotesDataset
 # __getitem__ and VoxelizationDataset + collate_fn of the reference (downstream/votenet_det_new) do per scan on the host, for a

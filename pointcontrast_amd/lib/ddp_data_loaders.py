@@ -59,8 +59,23 @@ def _apply_rigid(trans, xyz):
   return out
 
 
+def load_frame(path, use_color):
+  """'pcd' of one corpus file, and with use_color its 'color' (uint8 [n, 3], written by make_pair_corpus --color)."""
+  with np.load(path) as z:
+    xyz = z["pcd"]
+    if not use_color:
+      return xyz, None
+    if "color" not in z.files:
+      raise ValueError("%s has no 'color' member: data.use_color=True needs a corpus built with make_pair_corpus --color" % path)
+    rgb = z["color"]
+  if rgb.dtype != np.uint8 or rgb.shape != (len(xyz), 3):
+    raise ValueError("%s: 'color' is %s %s for %d points (uint8 [n, 3] expected)" % (path, rgb.dtype, rgb.shape, len(xyz)))
+  return xyz, rgb
+
+
 class ScanNetMatchPairDataset(torch.utils.data.Dataset):
-  """pc/lib/ddp_data_loaders.py:119-270."""
+  """pc/lib/ddp_data_loaders.py:119-270.  data.use_color (beyond the reference, whose released loader has a "#dummy color" of ones,
+  :204-206, :248-249): the features are the RGB of the voxel's first point, color / 255 - 0.5, in front of the transform."""
 
   def __init__(self, phase, transform=None, random_rotation=True, random_scale=True, manual_seed=False, config=None):
     if phase != "train":
@@ -78,6 +93,7 @@ class ScanNetMatchPairDataset(torch.utils.data.Dataset):
     # numpy / cKDTree on the host; identical results (both bit-exact against oracle/loader_ref.py).  The item is then
     # produced by the process that owns the GPU: use misc.train_num_thread=0.
     self.device_geometry = bool(config.data.get("device_geometry", False))
+    self.use_color = bool(config.data.get("use_color", False))  # needs a corpus built with make_pair_corpus --color
     self.root = config.data.dataset_root_dir
     if not self.root or not config.data.scannet_match_dir:
       raise ValueError("ScanNetMatchPairDataset needs data.dataset_root_dir and data.scannet_match_dir (the pair list)")
@@ -94,8 +110,8 @@ class ScanNetMatchPairDataset(torch.utils.data.Dataset):
 
   def __getitem__(self, idx):
     from .. import minkowski as ME
-    xyz0 = np.load(os.path.join(self.root, self.files[idx][0]))["pcd"]
-    xyz1 = np.load(os.path.join(self.root, self.files[idx][1]))["pcd"]
+    xyz0, rgb0 = load_frame(os.path.join(self.root, self.files[idx][0]), self.use_color)
+    xyz1, rgb1 = load_frame(os.path.join(self.root, self.files[idx][1]), self.use_color)
     radius = self.matching_search_voxel_size
     if self.random_scale and random.random() < 0.95:
       scale = self.min_scale + (self.max_scale - self.min_scale) * random.random()
@@ -111,14 +127,18 @@ class ScanNetMatchPairDataset(torch.utils.data.Dataset):
       trans = np.identity(4)
     if self.device_geometry:
       from . import device_loader as dl
-      xyz0 = xyz0[dl.sparse_quantize_index(xyz0, self.voxel_size)]
-      xyz1 = xyz1[dl.sparse_quantize_index(xyz1, self.voxel_size)]
+      sel0, sel1 = dl.sparse_quantize_index(xyz0, self.voxel_size), dl.sparse_quantize_index(xyz1, self.voxel_size)
+      xyz0, xyz1 = xyz0[sel0], xyz1[sel1]
       matches = dl.get_matching_indices(xyz0, xyz1, trans, radius)
     else:
-      xyz0 = xyz0[ME.utils.sparse_quantize(xyz0 / self.voxel_size, return_index=True)]
-      xyz1 = xyz1[ME.utils.sparse_quantize(xyz1 / self.voxel_size, return_index=True)]
+      sel0 = ME.utils.sparse_quantize(xyz0 / self.voxel_size, return_index=True)
+      sel1 = ME.utils.sparse_quantize(xyz1 / self.voxel_size, return_index=True)
+      xyz0, xyz1 = xyz0[sel0], xyz1[sel1]
       matches = get_matching_indices(xyz0, xyz1, trans, radius)
-    feats0, feats1 = np.ones((len(xyz0), 3)), np.ones((len(xyz1), 3))
+    if self.use_color:  # the colour of the voxel's first point, as its position
+      feats0, feats1 = rgb0[sel0].astype(np.float64) / 255.0 - 0.5, rgb1[sel1].astype(np.float64) / 255.0 - 0.5
+    else:
+      feats0, feats1 = np.ones((len(xyz0), 3)), np.ones((len(xyz1), 3))
     coords0, coords1 = np.floor(xyz0 / self.voxel_size), np.floor(xyz1 / self.voxel_size)
     if self.transform:
       coords0, feats0 = self.transform(coords0, feats0)
@@ -129,6 +149,9 @@ class ScanNetMatchPairDataset(torch.utils.data.Dataset):
 class SyntheticScanNetPairDataset(torch.utils.data.Dataset):
 
   def __init__(self, phase="train", config=None, num_pairs=None, crop=None, **_unused):
+    if config.data.get("use_color", False):
+      raise ValueError("data.use_color=True: SyntheticScanNetPairDataset has no colours (use ScanNetMatchPairDataset on a corpus "
+                       "built with make_pair_corpus --color)")
     self.voxel_size = config.data.voxel_size
     self.search_mult = config.trainer.positive_pair_search_voxel_size_multiplier
     self.num_pairs = num_pairs or config.data.get("num_pairs", 64)

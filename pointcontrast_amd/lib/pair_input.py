@@ -68,7 +68,9 @@ class PairInputPipeline:
   Returns the collate's dict as device tensors -- pcd0, pcd1, sinput0_C, sinput0_F, sinput1_C, sinput1_F, correspondences, T_gt
   -- with len_batch (a host list, from the read-back) and n_queries (the distinct values of column 0 of the correspondences).
   The tensors are views of buffers sized for the raw rows.  jitter = (mu, sigma) of the feature noise, None: features are 1.
-  One upload (raw rows and draws in one buffer), one blocking read-back (counts, flags, n_queries); a second one when the
+  Frames of a corpus built with colours are (xyz0, xyz1, rgb0, rgb1), rgb uint8 [n, 3] -- all frames of a batch or none: the
+  features are then rgb / 255 - 0.5 of the voxel's first point (+ the noise), as ScanNetMatchPairDataset's with data.use_color.
+  One upload (raw rows, colours and draws in one buffer), one blocking read-back (counts, flags, n_queries); a second one when the
   correspondences did not fit match_capacity and the fill ran again (last_readbacks)."""
 
   def __init__(self, voxel_size, search_multiplier, random_rotation=True, device=None, jitter=(0.0, 0.01), match_capacity=None):
@@ -123,12 +125,28 @@ class PairInputPipeline:
     dt = np.float32 if all(a.dtype == np.float32 for a in clouds) else np.float64
     lens = [a.shape[0] for a in clouds]
     n = sum(lens)
+    colored = [len(f) >= 4 for f in frames]
+    if any(colored) and not all(colored):
+      raise ValueError("PairInputPipeline: frames %s come with colours, the others without" % [b for b in range(B) if colored[b]])
+    sections = []
+    if colored[0]:  # the colours of the raw rows: one uint8 section in the same upload, padded to a multiple of 8 bytes
+      rgb = np.zeros((3 * n + 7) // 8 * 8, np.uint8)
+      at = 0
+      for b, f in enumerate(frames):
+        for s in range(2):
+          c = np.asarray(f[2 + s])
+          if c.dtype != np.uint8 or c.ndim != 2 or c.shape[1] != 3 or c.shape[0] != lens[2 * b + s]:
+            raise ValueError("PairInputPipeline: pair %d: rgb%d is %s %s for %d points (uint8 [n, 3] expected)" %
+                             (b, s, c.dtype, c.shape, lens[2 * b + s]))
+          rgb[at:at + c.size] = c.reshape(-1)
+          at += c.size
+      sections = [rgb]
     radius = np.float64(self.voxel_size * self.search_multiplier) * draws.scale  # radius *= scale, ddp_data_loaders.py
     on = np.zeros(2 * B, np.int32)  # (an even number of words: every section is a multiple of 8 bytes, the raw rows come last)
     on[:] = draws.jitter_on if self.jitter is not None else 0
     with torch.cuda.device(self.device):
-      offs_d, scale_d, radius_d, rot_d, on_d, raw_d = self._upload(
-          [np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), draws.scale, radius, draws.rot.reshape(-1, 9), on], clouds, dt)
+      offs_d, scale_d, radius_d, rot_d, on_d, *rgb_d, raw_d = self._upload(
+          [np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), draws.scale, radius, draws.rot.reshape(-1, 9), on] + sections, clouds, dt)
       noise = None
       if self.jitter is not None and draws.jitter_on.any():
         if draws.noise is not None:
@@ -148,6 +166,8 @@ class PairInputPipeline:
       cap = max(int(self.match_capacity), 1) if self.match_capacity is not None else min(max(16 * n, 1024), (1 << 31) - 1)
       mt = PF.pair_match(vx, tf["trans"], radius_d, cap, flags)
       co = PF.pair_collate(vx, tf["trans"], noise, on_d, mu, sigma)
+      if rgb_d:  # sinput{0,1}_F from the colours, over the collate's ones
+        PF.pair_color_features(rgb_d[0][:3 * n].view(n, 3), vx, co, noise, on_d, mu, sigma)
       back = torch.cat([vx["n_vox"], mt["pair_counts"], mt["totals"], flags.to(torch.int64)]).cpu().numpy()  # THE read-back
       self.last_readbacks = 1
       n_vox, totals, fl = back[:2 * B], back[3 * B:3 * B + 4], back[3 * B + 4:]
@@ -174,9 +194,10 @@ class PairInputPipeline:
 
 class RawPairFiles(torch.utils.data.Dataset):
   """The two raw 'pcd' arrays of every line of the pair list (data.dataset_root_dir / data.scannet_match_dir): all a loader
-  worker does with data.device_batch=True."""
+  worker does with data.device_batch=True.  data.use_color: the two 'color' arrays behind them, (xyz0, xyz1, rgb0, rgb1)."""
 
   def __init__(self, config):
+    self.use_color = bool(config.data.get("use_color", False))
     self.root = config.data.dataset_root_dir
     if not self.root or not config.data.scannet_match_dir:
       raise ValueError("data.device_batch=True needs data.dataset_root_dir and data.scannet_match_dir (the pair list)")
@@ -187,7 +208,11 @@ class RawPairFiles(torch.utils.data.Dataset):
     return len(self.files)
 
   def __getitem__(self, idx):
-    return tuple(np.load(os.path.join(self.root, p))["pcd"] for p in self.files[idx])
+    if not self.use_color:
+      return tuple(np.load(os.path.join(self.root, p))["pcd"] for p in self.files[idx])
+    from .ddp_data_loaders import load_frame
+    xyz, rgb = zip(*(load_frame(os.path.join(self.root, p), True) for p in self.files[idx]))
+    return xyz + rgb
 
 
 def _as_list(items):

@@ -5,7 +5,9 @@ depth frames, ~300k points each, as the pair corpus writes them) at 2.5 cm, rand
   host      ScanNetMatchPairDataset.__getitem__ x 4 + default_collate_pair_fn + the uploads the trainer makes (coordinates,
             features, correspondences), data.device_geometry off and on, wall clock, ms
 The figure to hold the device call against is the training step it has to hide behind (13.7 ms for this batch).
-Usage: python scripts/pair_input_bench.py [repetitions]"""
+--color: every raw point gets an RGB (as a corpus built with make_pair_corpus --color stores it); the whole call with 4-tuples
+(the colours in the same upload) is timed beside the call without, and pcmi_pair_color_features as a stage of its own.
+Usage: python scripts/pair_input_bench.py [repetitions] [--color]"""
 import json
 import os
 import random
@@ -23,7 +25,9 @@ from pointcontrast_amd.lib.config import get_config
 from pointcontrast_amd.lib.ddp_data_loaders import FeatureJitter, dataset_str_mapping, default_collate_pair_fn
 from pointcontrast_amd.lib.pair_input import PairDraws, PairInputPipeline
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+color = "--color" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--color"]
+reps = int(argv[0]) if argv else 10
 B, voxel, mult = 4, 0.025, 1.5
 dev = torch.device("cuda", 0)
 rng = np.random.RandomState(0)
@@ -62,6 +66,21 @@ with tempfile.TemporaryDirectory() as root:
   out["correspondences"] = int(batch["correspondences"].shape[0])
   print("device    %8.2f ms per batch (%d + %d voxels, %d correspondences, %d read-back)" %
         (out["device_call_ms"], out["voxels"][0], out["voxels"][1], out["correspondences"], pipe.last_readbacks), flush=True)
+  if color:
+    frames4 = [(a, b, rng.randint(0, 256, a.shape).astype(np.uint8), rng.randint(0, 256, b.shape).astype(np.uint8)) for a, b in frames]
+    saved = (random.getstate(), randg.get_state(), gen.get_state())  # the legs below see the draws they see without --color
+    for _ in range(2):
+      batch = pipe(frames4, PairDraws.sample(cfg, B, randg, gen))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+      batch = pipe(frames4, PairDraws.sample(cfg, B, randg, gen))
+    torch.cuda.synchronize()
+    out["device_call_color_ms"] = round((time.perf_counter() - t0) / reps * 1e3, 3)
+    print("device    %8.2f ms per batch with colours (%d read-back)" % (out["device_call_color_ms"], pipe.last_readbacks), flush=True)
+    random.setstate(saved[0])
+    randg.set_state(saved[1])
+    gen.set_state(saved[2])
 
   # ---- the stages between device events ----
   d = PairDraws.sample(cfg, B, randg, gen)
@@ -71,9 +90,10 @@ with tempfile.TemporaryDirectory() as root:
   radius = torch.from_numpy(np.float64(voxel * mult) * d.scale).to(dev)
   on = torch.from_numpy(d.jitter_on.astype(np.int32)).to(dev)
   cap = int(out["correspondences"] * 1.25) + 1024
-  acc = {k: 0.0 for k in ("noise", "transform", "voxelize", "match", "collate")}
+  acc = {k: 0.0 for k in ("noise", "transform", "voxelize", "match", "collate") + (("color_features",) if color else ())}
+  rgb = torch.from_numpy(np.concatenate([c for f in frames4 for c in f[2:]])).to(dev) if color else None
   for it in range(reps + 1):
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(acc) + 1)]
     flags = torch.zeros(B, dtype=torch.int32, device=dev)
     ev[0].record()
     noise = torch.randn((n, 3), generator=gen, dtype=torch.float32, device=dev)
@@ -84,8 +104,11 @@ with tempfile.TemporaryDirectory() as root:
     ev[3].record()
     mt = PF.pair_match(vx, tf["trans"], radius, cap, flags)
     ev[4].record()
-    PF.pair_collate(vx, tf["trans"], noise, on, 0.0, 0.01)
+    co = PF.pair_collate(vx, tf["trans"], noise, on, 0.0, 0.01)
     ev[5].record()
+    if color:
+      PF.pair_color_features(rgb, vx, co, noise, on, 0.0, 0.01)
+      ev[6].record()
     torch.cuda.synchronize()
     if it:  # (the first round warms up)
       for k, name in enumerate(acc):
