@@ -1458,6 +1458,56 @@ int pcmi_ransac_score(const double* src, const double* dst, int64_t m, const int
 int pcmi_rigid_sums(const double* src, const double* dst, int64_t m, const int64_t* offsets, int64_t B, const int32_t* best,
                     const double* Rt, double tau, double* sums, pcmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Spatially partitioned PointInfoNCE (csrc/nce_part.hip) -- the objective of Hou et al., "Exploring Data-Efficient 3D Scene
+ * Understanding with Contrastive Scene Contexts", stated here (the reference has no counterpart): the negatives of every anchor are
+ * partitioned by where they lie around it, one InfoNCE per partition.
+ *
+ * Inputs.  q, k [n, c] (fp32, c in {16, 32}, 16-byte aligned; row i of k is the positive of row i of q); xyz [n, 3] (int32, the
+ * voxel coordinates of the queries, 18-bit signed); scene [n] (int32, the batch index of each query); n_scenes B in 1..1024;
+ * inv_T; r1_sq <= r2_sq (int64 >= 0, squared radii in voxel units); A in {1, 2, 4, 8} azimuth sectors about the z axis; E in
+ * {1, 2} elevation halves; P = 2 E A <= 32.  Anything else: PCMI_ERR_INVALID (PCMI_ERR_UNSUPPORTED for c), nothing enqueued.
+ *
+ * part(i, j), the partition of column j as seen from row i -- all integers, d = xyz[j] - xyz[i], d2 = dx dx + dy dy + dz dz
+ * in int64:
+ *   part = -1 (j is a negative of i in no partition) if i == j, d2 == 0, d2 > r2_sq, scene[i] != scene[j], or either scene id
+ *   lies outside [0, B).  Otherwise
+ *   shell = 0 if d2 <= r1_sq, else 1;   el = 0 if E == 1 or dz >= 0, else 1;   the azimuth sector, on (dx, dy):
+ *     1. h = 0 if dy > 0 or (dy == 0 and dx > 0), else 1; if h == 1, (dx, dy) <- (-dx, -dy);
+ *     2. qd = 0 if dx > 0, else 1; if qd == 1, (dx, dy) <- (dy, -dx);
+ *     3. o = 0 if dy < dx, else 1;
+ *   az = 0, h, 2 h + qd, 4 h + 2 qd + o for A = 1, 2, 4, 8 (floor(atan2(dy, dx) mod 2 pi / (2 pi / A)) with half-open sectors;
+ *   dx == dy == 0 gives A - 1);   part = (shell E + el) A + az.   part(i, j) is not symmetric.
+ *
+ * Loss.  With l_ij = inv_T q_i.k_j:  lse[i, p] = log(exp(l_ii) + sum_{j: part(i, j) = p} exp(l_ij)).  Row i is live in p if at
+ * least one j has part(i, j) = p; R[s, p] = the live rows of scene s in partition p; p is live in s if R[s, p] is not empty;
+ * L_s = the live partitions of scene s; S = the scenes with L_s > 0:
+ *   loss = (1 / S) sum_{s: L_s > 0} (1 / L_s) sum_{p live in s} (1 / |R[s, p]|) sum_{i in R[s, p]} (lse[i, p] - l_ii),
+ * and 0 if S == 0.  With w[i, p] = 1 / (S L_s |R[s, p]|) for live (i, p), 0 otherwise:
+ *   G_ij = w[i, part(i, j)] exp(l_ij - lse[i, part(i, j)]) for part(i, j) >= 0,  G_ii = sum_p w[i, p] (exp(l_ii - lse[i, p]) - 1),
+ *   every other entry 0;  dq = gscale inv_T G k,  dk = gscale inv_T G^T q  (gscale: device scalar, nullable -> 1).
+ *
+ * pcmi_pnce_fwd writes lse [n, P], live [B, P] (int32: live[s, p] = |R[s, p]|, 0 for a dead partition) and *loss (device
+ * scalar).  lse of a (row, partition) that is NOT live is written as l_ii, the value of the definition over an empty set, in the
+ * bits the backward forms l_ii with (so its term exp(l_ii - lse) - 1 is exactly 0).  pcmi_pnce_bwd reads them back.
+ * The n x n logits and partitions are never written; fp32 products (one fmaf per channel, ascending), a maximum per (row,
+ * partition), no float atomics; the per-partition sums and the loss are reduced in float64 in a fixed order, counts are
+ * integers; every output is the same bits from run to run.  ws: pcmi_pnce_workspace_bytes(n, c, B, P) bytes, 16-byte aligned,
+ * else PCMI_ERR_WORKSPACE.  Any n >= 1.
+ *
+ * pcmi_pnce_partition: a test aid, n <= 4096 (PCMI_ERR_UNSUPPORTED beyond): part [n, n] (int8) = part(i, j) from the same device
+ * function as the loss kernels.
+ * ------------------------------------------------------------------------------------------ */
+size_t pcmi_pnce_workspace_bytes(int64_t n, int c, int n_scenes, int P);
+int pcmi_pnce_fwd(const float* q, const float* k, const int32_t* xyz, const int32_t* scene, int64_t n, int c, int n_scenes,
+                  float inv_T, int64_t r1_sq, int64_t r2_sq, int A, int E, float* lse, int32_t* live, float* loss, void* ws,
+                  size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_pnce_bwd(const float* q, const float* k, const int32_t* xyz, const int32_t* scene, const float* lse, const int32_t* live,
+                  int64_t n, int c, int n_scenes, float inv_T, int64_t r1_sq, int64_t r2_sq, int A, int E, const float* gscale,
+                  float* dq, float* dk, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_pnce_partition(const int32_t* xyz, const int32_t* scene, int64_t n, int n_scenes, int64_t r1_sq, int64_t r2_sq, int A,
+                        int E, int8_t* part, pcmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,12 @@ PROTOTYPES = {
                                    C.POINTER(C.c_double), C.c_int, c_vp, c_vp, c_vp]),
     "pcmi_ransac_score": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.c_double, c_vp, c_vp, c_vp, c_vp]),
     "pcmi_rigid_sums": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, C.c_double, c_vp, c_vp]),
+    "pcmi_pnce_workspace_bytes": (c_sz, [c_i64, C.c_int, C.c_int, C.c_int]),
+    "pcmi_pnce_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_f32, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp,
+                                c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_pnce_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_f32, c_i64, c_i64, C.c_int, C.c_int,
+                                c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_pnce_partition": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

@@ -27,6 +27,8 @@ def get_trainer(name):
     return ddp_trainer.HardestContrastiveLossTrainer
   if name == "PointNCELossTrainer":
     return ddp_trainer.PointNCELossTrainer
+  if name == "PartitionPointNCELossTrainer":
+    return ddp_trainer.PartitionPointNCELossTrainer
   raise ValueError("Trainer %s not found" % name)
 
 

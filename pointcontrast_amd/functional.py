@@ -320,6 +320,70 @@ class NCELossFunction(Function):
     return dq, dk, None
 
 
+def _partition_rule(r1_sq, r2_sq, azimuth, elevation, n_scenes):
+  r1_sq, r2_sq, A, E, B = int(r1_sq), int(r2_sq), int(azimuth), int(elevation), int(n_scenes)
+  return r1_sq, r2_sq, A, E, B, 2 * E * A
+
+
+class PartitionNCELossFunction(Function):
+  """The spatially partitioned PointInfoNCE of include/pcmi.h (csrc/nce_part.hip): one InfoNCE per partition (distance shell
+  x elevation half x azimuth sector around the anchor, from the integer voxel coordinates `xyz` of the queries, scenes kept
+  apart by `scene`), averaged over live rows, live partitions and live scenes.  One launch over the batch; the n x n logits
+  and partitions are never written.  Gradients go to q and k only."""
+
+  @staticmethod
+  def forward(ctx, q, k, xyz, scene, T, r1_sq, r2_sq, azimuth, elevation, n_scenes):
+    q, k = q.contiguous(), k.contiguous()
+    xyz, scene = xyz.to(torch.int32).contiguous(), scene.to(torch.int32).contiguous()
+    loss, lse, live = partition_nce_forward(q, k, xyz, scene, T, r1_sq, r2_sq, azimuth, elevation, n_scenes)
+    ctx.save_for_backward(q, k, xyz, scene, lse, live)
+    ctx.rule = (1.0 / float(T),) + _partition_rule(r1_sq, r2_sq, azimuth, elevation, n_scenes)
+    return loss
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gloss):
+    q, k, xyz, scene, lse, live = ctx.saved_tensors
+    inv_T, r1_sq, r2_sq, A, E, B, P = ctx.rule
+    n, c = q.shape
+    dq, dk = torch.empty_like(q), torch.empty_like(k)
+    g = gloss.to(torch.float32).contiguous()
+    ws, wsb = ws_args(lib.pcmi_pnce_workspace_bytes(n, c, B, P), q.device)
+    check(lib.pcmi_pnce_bwd(ptr(q), ptr(k), ptr(xyz), ptr(scene), ptr(lse), ptr(live), n, c, B, inv_T, r1_sq, r2_sq, A, E, ptr(g),
+                            ptr(dq), ptr(dk), ws, wsb, cur_stream(q.device)))
+    return (dq, dk) + (None,) * 8
+
+
+def partition_nce_forward(q, k, xyz, scene, T, r1_sq, r2_sq, azimuth, elevation, n_scenes):
+  """(loss, lse [n, P], live [n_scenes, P]) of the partitioned loss without autograd: lse of a (row, partition) that is not
+  live is l_ii; live[s, p] is the number of live rows of scene s in partition p."""
+  require_cuda(q, "partition nce loss")
+  q, k = q.detach().contiguous(), k.detach().contiguous()
+  xyz, scene = xyz.to(torch.int32).contiguous(), scene.to(torch.int32).contiguous()
+  n, c = q.shape
+  assert xyz.shape == (n, 3) and scene.shape == (n,), "xyz [n, 3] and scene [n] go with the n rows of q"
+  r1_sq, r2_sq, A, E, B, P = _partition_rule(r1_sq, r2_sq, azimuth, elevation, n_scenes)
+  lse = torch.empty((n, max(P, 1)), dtype=torch.float32, device=q.device)
+  live = torch.empty((max(B, 1), max(P, 1)), dtype=torch.int32, device=q.device)
+  loss = torch.empty((), dtype=torch.float32, device=q.device)
+  ws, wsb = ws_args(lib.pcmi_pnce_workspace_bytes(n, c, B, P), q.device)
+  check(lib.pcmi_pnce_fwd(ptr(q), ptr(k), ptr(xyz), ptr(scene), n, c, B, 1.0 / float(T), r1_sq, r2_sq, A, E, ptr(lse), ptr(live),
+                          ptr(loss), ws, wsb, cur_stream(q.device)))
+  return loss, lse, live
+
+
+def partition_matrix(xyz, scene, r1_sq, r2_sq, azimuth, elevation, n_scenes):
+  """part(i, j) of every pair as int8 [n, n] (-1: j is no negative of i) from the device function the loss kernels use; a test
+  aid, n <= 4096."""
+  require_cuda(xyz, "partition matrix")
+  xyz, scene = xyz.to(torch.int32).contiguous(), scene.to(torch.int32).contiguous()
+  n = xyz.shape[0]
+  r1_sq, r2_sq, A, E, B, _ = _partition_rule(r1_sq, r2_sq, azimuth, elevation, n_scenes)
+  part = torch.empty((n, n), dtype=torch.int8, device=xyz.device)
+  check(lib.pcmi_pnce_partition(ptr(xyz), ptr(scene), n, B, r1_sq, r2_sq, A, E, ptr(part), cur_stream(xyz.device)))
+  return part
+
+
 def pdist_argmin(a, b):
   """(min_s sqrt(|a_p - b_s|^2 + 1e-7), argmin) -- pc/lib/ddp_trainer.py:182-184,218-219."""
   require_cuda(a, "pdist_argmin")

@@ -20,6 +20,10 @@ DEFAULTS = {
         # not in the reference, which never validates: feature matching on held-out pairs every val_freq iterations
         # (0 = off, the loop is the reference's), over at most val_max_batches batches (None = the whole list)
         "val_freq": 0, "val_max_batches": None,
+        # PartitionPointNCELossTrainer only (not in the reference): the two shell radii in voxels (squared and floored to
+        # integers; 0.5 m and 2 m at 2.5 cm voxels), azimuth sectors (1, 2, 4, 8) and elevation halves (1, 2): P = 8.
+        # This project's choice, not tuned.
+        "partition_r1": 20.0, "partition_r2": 80.0, "partition_azimuth": 2, "partition_elevation": 2,
     },
     "net": {"model": "Res16UNet34C", "model_n_out": 32, "conv1_kernel_size": 3, "normalize_feature": True},
     "opt": {"optimizer": "SGD", "max_iter": 300000, "lr": 0.1, "momentum": 0.8, "weight_decay": 1e-4,

@@ -800,7 +800,7 @@ class PointNCELossTrainer(ContrastiveLossTrainer):
     else:
       q = PF.GatherRowsFunction.apply(F0, prep["q_idx"])
       k = PF.GatherRowsFunction.apply(F1, prep["k_idx"])
-    loss = PF.NCELossFunction.apply(q, k, self.T)
+    loss = self._pair_loss(q, k, prep)
     mark("loss")
     result = self._backward_and_step(loss, {"loss": loss.detach()})
     mark("backward_step")
@@ -809,3 +809,47 @@ class PointNCELossTrainer(ContrastiveLossTrainer):
     total_timer.toc()
     data_meter.update(data_time)
     return result
+
+  def _pair_loss(self, q, k, prep):
+    """The loss of the gathered pairs: q[i] / k[i] are the features at prep["q_idx"][i] / prep["k_idx"][i]."""
+    return PF.NCELossFunction.apply(q, k, self.T)
+
+
+class PartitionPointNCELossTrainer(PointNCELossTrainer):
+  """PointNCELossTrainer with the spatially partitioned PointInfoNCE (Hou et al., "Exploring Data-Efficient 3D Scene
+  Understanding with Contrastive Scene Contexts"; semantics in include/pcmi.h) in place of the plain one: the
+  negatives of a query are partitioned by where they lie around it in cloud 0 (trainer.partition_r1 / _r2 / _azimuth /
+  _elevation), one InfoNCE per partition.  Pair selection, validation, checkpoints, prefetch and the gradient buckets are the
+  parent's.  The loss is ONE launch over the batch with the scenes kept apart by their batch index (the published trainer loops
+  over the scenes); the coordinates and scene ids of the queries are gathered on the device."""
+
+  def __init__(self, config, data_loader, val_data_loader=None):
+    super().__init__(config, data_loader, val_data_loader)
+    self.r1_sq, self.r2_sq, self.azimuth, self.elevation = self.partition_rule(config)
+
+  @staticmethod
+  def partition_rule(config):
+    """(r1_sq, r2_sq, azimuth, elevation) of the configuration: the radii in voxels, squared and floored to integers."""
+    import math
+    t = config.trainer
+    r1_sq, r2_sq = (int(math.floor(float(r) * float(r))) for r in (t.partition_r1, t.partition_r2))
+    A, E = int(t.partition_azimuth), int(t.partition_elevation)
+    if A not in (1, 2, 4, 8) or E not in (1, 2) or not 0 <= r1_sq <= r2_sq:
+      raise ValueError("trainer.partition_*: azimuth in {1, 2, 4, 8}, elevation in {1, 2}, 0 <= r1 <= r2; got %r" % ((t.partition_r1, t.partition_r2, A, E),))
+    return r1_sq, r2_sq, A, E
+
+  def _query_coords(self, prep):
+    """Cloud 0's coordinates [N0, 4] (batch index, x, y, z) on the device: the batch's own tensor if it was built there, else the
+    copy the sparse tensor uploaded (the pair as one tensor: its first n0 rows)."""
+    C0 = prep["input"]["sinput0_C"]
+    if C0.is_cuda:
+      return C0
+    if "sj" in prep:
+      return prep["sj"].coords_dev[:prep["n0"]]
+    return prep["s0"].coords_dev
+
+  def _pair_loss(self, q, k, prep):
+    at = self._query_coords(prep).index_select(0, prep["q_idx"])
+    self._last_pairs = dict(q=q.detach(), k=k.detach(), xyz=at[:, 1:4], scene=at[:, 0])  # (what the loss saw: the parity test reads it back)
+    return PF.PartitionNCELossFunction.apply(q, k, at[:, 1:4], at[:, 0], self.T, self.r1_sq, self.r2_sq, self.azimuth, self.elevation,
+                                             len(prep["input"]["len_batch"]))

@@ -386,7 +386,9 @@ class SparseTensor:
       ev = torch.cuda.Event()
       ev.record(plan)
       f.record_stream(cur)
+      c.record_stream(cur)
       out = SparseTensor(f, coords_key=cm.key(0), coords_manager=cm)
+      out.coords_dev = c  # the uploaded [N, 4] coordinates (PartitionPointNCELossTrainer gathers the queries' from them)
       if getattr(_tls, "defer", False):
         out.upload_event = ev  # see deferred_upload_sync
       else:

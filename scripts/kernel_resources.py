@@ -41,11 +41,12 @@ def resources(src, extra=()):
 def main():
   args = [a for a in sys.argv[1:] if not a.startswith("-")]
   extra = [a for a in sys.argv[1:] if a.startswith("-")]
-  print("%-14s %-52s %5s %5s %7s %5s %4s" % ("source", "kernel", "VGPR", "AGPR", "LDS B", "SGPR", "occ"))
+  print("%-14s %-52s %5s %5s %7s %5s %4s %7s" % ("source", "kernel", "VGPR", "AGPR", "LDS B", "SGPR", "occ", "scratch"))
   for src in (args or B.SOURCES):
     for r in resources(src, extra):
-      print("%-14s %-52s %5s %5s %7s %5s %4s" % (src.replace(".hip", ""), r["name"][:52], r.get("VGPRs", "?"), r.get("AGPRs", "?"),
-                                                 r.get("LDS Size", "?"), r.get("SGPRs", "?"), r.get("Occupancy", "?")))
+      print("%-14s %-52s %5s %5s %7s %5s %4s %7s" % (src.replace(".hip", ""), r["name"][:52], r.get("VGPRs", "?"), r.get("AGPRs", "?"),
+                                                     r.get("LDS Size", "?"), r.get("SGPRs", "?"), r.get("Occupancy", "?"),
+                                                     r.get("ScratchSize", "?")))  # bytes per lane
 
 
 if __name__ == "__main__":
