@@ -207,16 +207,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3t_kernel(WgradTArgs a) {
 // (profiles/r04e_kernel_component_removal.txt): without the gathers it runs 25 % shorter, without the MFMAs 20 % -- it is
 // bound by the exposed staging phase, and its 248 registers leave no room to request the next unit's rows early (round 3
 // tried: 3 instead of 4 offsets per workgroup, slower).  Here the two jobs belong to different waves of an 8-wave workgroup
-// (one per CU): waves 0-3 only multiply (they own the accumulators), waves 4-7 only stage -- no accumulators, so a producer
+// (one per CU): waves 0-3 multiply (they own the accumulators), waves 4-7 only stage -- no accumulators, so a producer
 // keeps the rows of THREE units in flight in registers (the gathers of slot q + 3 are issued before slot q + 1 is converted)
 // and writes the packed image of the next unit into the other half of a double-buffered LDS while the consumers multiply
 // the current one.  One workgroup barrier per (tile, offset slot); absent slots cost a barrier and nothing else.
+// Round 7: the G rows are staged by the CONSUMERS, behind their products, in what was time at the slot barrier (the slot is
+// bound by the producers); the producers keep X, the row-offset tables and the presence flags.
 //   slots   q = tile * KG + s; X(q) lives in s_x[q & 1] (KG is even: = s & 1), G(tile) in s_g[tile & 1]
 //   tables  (row offsets of a tile's KG offsets, the G row offsets, which slots are present) for tile T are loaded by the
 //           producers during tile T - 2 into a ring of three -- visible long before anybody plans with them
-//   step q  producers: [s == 0: request the table of tile + 2] request X(q + 3); convert + write X(q + 1); [s == 1: convert +
-//           write G(tile + 1)]; [s == 2: write the table of tile + 2]; [s == 3: request G(tile + 2)]
-//           consumers: multiply slot q if present      all: barrier
+//   step q  producers: [s == 0: request the table of tile + 2] request X(q + 3); convert + write X(q + 1); [s == 2: write the
+//           table of tile + 2]
+//           consumers: multiply slot q if present; [s == 1 .. NTW: convert + write round s - 1 of G(tile + 1)]; [s == 0, 1:
+//           request round s + 1 of G(tile + 1)]; [s == 3: request round 0 of G(tile + 2)]      all: barrier
 // Same cells, same fragment reads, same six products in the same order per accumulator, same slabs as wgrad_x3t_kernel: the
 // results are bit-identical to it for the same row-block count.
 template <int MTW, int NTW, int KG>
@@ -247,11 +250,11 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
 
   if (producer) {
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, 0x7FFFFFFF, kRsrcFlags);
-    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.g), 0, 0x7FFFFFFF, kRsrcFlags);
     const int pt = t - 256;
     // tables of relative tile `tl` (tile t0 + tl; past the range: everything absent) into ring slot tl % 3, in two halves:
     // the global loads are issued in one step and their results written to LDS two steps later, so that the producer
-    // never waits for a table entry it has just requested (wave 4 + sx looks after offset slot sx; wave 4 also after G)
+    // never waits for a table entry it has just requested (wave 4 + sx looks after offset slot sx; wave 4 also after the
+    // row offsets of G, which the consumers gather with)
     int32_t tab_v[(KG + 3) / 4];
     int32_t tab_g = -1;
     auto table_issue = [&](int tl) {
@@ -319,15 +322,14 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
     };
     struct Row { float f[3]; };  // the (2 or 3) channels of one gathered row
     constexpr std::integral_constant<int, CB> kWX{};
-    constexpr std::integral_constant<int, NB> kWG{};
     constexpr std::integral_constant<int, 0> k0{};
     constexpr std::integral_constant<int, 8> k8{};
     // FOUR register sets for the gathered rows (the producers own no accumulators): the rows of slot q + 3 are requested in
     // step q and converted in step q + 2 -- two full steps in flight (with two sets / one step the step lasted as long as
     // a gather under load: 0.54 ms per level-0 launch, profiles/r04j_*); slot s of a tile uses set s (KG = 4).  The G rows
-    // of tile + 2 are requested in a tile's last step and converted in the next tile's second.
+    // are the consumers' (below).
     static_assert(KG == 4, "one register set per offset slot");
-    Row r0[8], r1[8], r2[8], r3[8], rgv[8];
+    Row r0[8], r1[8], r2[8], r3[8];
     // Requests and conversions are UNCONDITIONAL: an absent slot has nothing but out-of-range offsets in its table (no
     // memory traffic, zeros come back) and is converted like any other -- a few hundred wasted VALU cycles in waves that
     // have slack.  With the requests under `if (present)` the compiler cannot pair a request with its conversion (two
@@ -347,13 +349,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
     table_commit(1);
     __syncthreads();  // (B0) the first two tables are visible
     issue(r0, xr, s_xoff[0][0], c0, kWX, k0, k8);
-    issue(rgv, gr, s_goff[0], n0, kWG, k0, k8);
     issue(r1, xr, s_xoff[0][1], c0, kWX, k0, k8);
     issue(r2, xr, s_xoff[0][2], c0, kWX, k0, k8);
     finish(s_x[0], r0, kWX, k0, k8);
-    finish(s_g[0], rgv, kWG, k0, k8);
-    issue(rgv, gr, s_goff[1], n0, kWG, k0, k8);  // G rows of the second tile (converted in step 1)
-    __syncthreads();  // (B1) slot 0 and the G rows of the first tile are staged
+    __syncthreads();  // (B1) slot 0 is staged (and, by the consumers, the G rows of the first tile)
 #define PCMI_X3P_SET(j) ((j) == 0 ? r0 : ((j) == 1 ? r1 : ((j) == 2 ? r2 : r3)))
     for (int tl = 0; tl < nt_tiles; ++tl) {
 #pragma unroll
@@ -368,9 +367,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
         //  gathers queue on the CU's one address unit -- and neither the conversion first nor a channel's conversion behind
         //  every few requests hides that: 0.491 / 0.436 against 0.435 ms per level-1 launch, profiles/r06pq_*.)
         finish(s_x[(sx + 1) & 1], PCMI_X3P_SET((sx + 1) % KG), kWX, k0, k8);
-        if (sx == 1) finish(s_g[(tl + 1) & 1], rgv, kWG, k0, k8);
         if (sx == KG - 2) table_commit(tl + 2);  // (first read one step on: a barrier away)
-        if (sx == KG - 1) issue(rgv, gr, s_goff[(tl + 2) % 3], n0, kWG, k0, k8);  // (its table: written one step ago)
         __syncthreads();
       }
     }
@@ -388,7 +385,49 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
     for (int mt = 0; mt < MTW; ++mt)
 #pragma unroll
       for (int nt = 0; nt < NTW; ++nt) acc[sx][mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  // The consumers stage G (round 7).  A slot is bound by the producers' VALU work while a consumer waits ~1360 of its 3400
+  // cycles at the slot barrier, so the G rows -- NTW of a tile's NTW + 4 * MTW conversions -- are gathered, split and written
+  // by the waves that would wait.  The 8 * NB cells of a tile's G image are NTW rounds of 256: in round r thread t owns the
+  // cell (row group t / 32, channel 32 r + t % 32), gathers the 8 rows of that one channel (8 dword loads; half a wave
+  // reads the 128 contiguous bytes of one row) and writes one cell per term -- 8 consecutive lanes write 8 consecutive
+  // channels of one row group, which the XOR permutes inside an aligned group of 8 cells: conflict-free as the producers'
+  // writes.  A round differs from the next by constants only (128 bytes of a row, 32 cells), so the rounds share their
+  // address registers.  All four waves take part in every round: each SIMD carries NTW conversions per tile.
+  //   round r of G(tile + 1): requested in slot (r + 3) % KG -- round 0 in the LAST slot of tile - 1, the first in which the
+  //   row offsets of tile + 1 are visible (table_commit, one slot and a barrier earlier) -- and converted two slots on, in
+  //   slot r + 1 of `tile`, behind that slot's products; rounds 0 and 2 share a register set (round 2 is requested right
+  //   behind round 0's conversion).
+  // Every write of G(tile + 1) goes to s_g[(tile + 1) & 1], which nobody reads during `tile`, and precedes the barrier that
+  // ends slot NTW <= KG - 1 of `tile`: the LAST slot barrier of `tile` at the latest, which every consumer passes before
+  // its first fragment read of tile + 1.  Requests and conversions are unconditional, as the producers' (an absent row's
+  // offset is out of range: zeros, no traffic).
+  static_assert(NTW + 1 <= KG && NTW <= 3, "round r is converted in slot r + 1; two register sets");
+  const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.g), 0, 0x7FFFFFFF, kRsrcFlags);
+  float ga[8], gb[8];
+  const int rg_g = t >> 5, q_g = t & 31;
+  auto g_issue = [&](float (&v)[8], const uint32_t* offs, int r) {
+    const uint32_t col = (uint32_t)(n0 + q_g) * 4u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(gr, offs[8 * rg_g + e] + col + 128u * r, 0, 0));
+  };
+  auto g_finish = [&](u32x4* dst, const float (&v)[8], int r) {
+    const v4f x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
+    u32x4 h, m, l;
+    split3(x0, x1, h, m, l);
+    const int cell = rg_g * NB + (q_g ^ rg_g) + 32 * r;  // = rg * NB + ((32 r + q) ^ rg): rg < 8 flips the low three bits only
+    dst[cell] = h;
+    dst[RG * NB + cell] = m;
+    dst[2 * RG * NB + cell] = l;
+  };
   __syncthreads();  // (B0)
+  g_issue(ga, s_goff[0], 0);
+  g_issue(gb, s_goff[0], 1);
+  g_finish(s_g[0], ga, 0);
+  if constexpr (NTW == 3) g_issue(ga, s_goff[0], 2);
+  g_finish(s_g[0], gb, 1);
+  if constexpr (NTW == 3) g_finish(s_g[0], ga, 2);
+  g_issue(ga, s_goff[1], 0);  // round 0 of the second tile (converted in slot 1)
   __syncthreads();  // (B1)
   for (int tl = 0; tl < nt_tiles; ++tl) {
     const u32x4* sg = s_g[tl & 1];
@@ -449,7 +488,15 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
           }
         }
       }
-      __syncthreads();
+      // this slot's share of G(tile + 1), in what was waiting time (the schedule above).  Measured: the conversion in
+      // front of the products instead changes nothing (0.418 against 0.420 ms at level 1, 96 -> 96), the REQUESTS in front
+      // of them cost what the change gains (0.435 against the parent's 0.437): there they queue on the address unit with
+      // the producers' gathers (profiles/r07a_*)
+      if (sx >= 1 && sx <= NTW) g_finish(s_g[(tl + 1) & 1], sx == 2 ? gb : ga, sx - 1);
+      if (sx == 0) g_issue(gb, s_goff[(tl + 1) % 3], 1);
+      if (sx == 1 && NTW == 3) g_issue(ga, s_goff[(tl + 1) % 3], 2);
+      if (sx == KG - 1) g_issue(ga, s_goff[(tl + 2) % 3], 0);  // (its table: written one slot ago, a barrier away)
+      __syncthreads();  // (for slot NTW at the latest: G(tile + 1) is complete before anybody reads it)
     }
   }
   // ---- slabs: D[row = 4 kk + r][col = i] of every 16x16 tile; row = input channel, col = output channel ------------
@@ -482,6 +529,18 @@ __global__ __launch_bounds__(512, 2) void wgrad_x3p_kernel(WgradTArgs a) {
 //     per SIMD is the same whichever wave carries it, and the G rows are staged for twice as many offset groups.  Removed;
 //   * with NO producer work at all (split, gather traffic and LDS writes compiled out) the step gains 0.3 ms of 14.0
 //     (profiles/r06j_*): the bound on anything a pre-split operand image could buy, before its own passes are paid for.
+// Round 7 divided the work anew: the G rows (a tile's NTW conversions of its NTW + 4 MTW; in the producers they were lumped into
+// the s == 1 slot, ~4700 cycles against ~2970 for the other three) are gathered, split and written by the CONSUMERS behind their
+// products, NTW rounds of 256 cells over the tile's slots; the producers keep X, the tables and the presence flags.  Stand-alone
+// ms per launch, before -> after (profiles/r07a_*): level 1 128 -> 96 0.696 -> 0.627, 96 -> 96 0.436 -> 0.423; level 2
+// 128 -> 96 0.173 -> 0.158, 96 -> 96 0.115 -> 0.112; level 3 192 -> 128 0.101 -> 0.094, 128 -> 128 0.085 -> 0.074.  The stamps had
+// promised 13 % at 96 -> 96 (a staging-bound slot of ~2970 cycles); it is 3 %, and timing builds with parts of the consumers' G
+// work compiled out say why: with none of it the launch takes 0.383 ms (-12 %: the producers' side of the estimate holds), its
+// requests alone add 0.013 and its conversion alone 0.024 -- what the consumers spent at the barrier is not free, and WHERE in
+// the slot the conversion stands changes nothing: the picture of a slot that a round of G makes consumer-bound at <3, 3> (2050
+// cycles of products + 8 requests + 1 conversion; not stamped).  At <3, 3> the consumers hold 256 registers (144 accumulators, 60 of fragments, two
+// sets of 8 gathered values), so a share of X does not fit beside G there; the other instances (150 - 198) are balanced within
+// ~10 % after this change (consumers 1355 + G against producers ~2200 cycles at <2, 3>), so a share of X was not built.
 
 // gW[k][e] (+)= sum over the row blocks of slab[k][rb][e], in row-block order.  32 elements x 8 row-block lanes per
 // workgroup, folded through LDS (the chain of dependent loads is RB / 8 long).
