@@ -529,6 +529,44 @@ int pcmi_corpus_overlap_counts(const double* centroids, const int64_t* offsets, 
                                int64_t n_frames, double radius, int32_t* counts, void* ws, size_t ws_bytes,
                                pcmi_stream_t stream);
 
+/* ---- virtual views of a whole scan (csrc/views.hip) ---------------------------------------------------------------
+ * No counterpart in the reference: which points of a scan F pinhole cameras would see (frustum plus z-buffer occlusion),
+ * the stage in front of pcmi_corpus_voxel_centroids for a corpus built from reconstructions instead of depth frames.
+ * points fp64 [n, 3] world frame, row stride points_ld >= 3 doubles; w2c fp64 [F, 4, 4] world-to-camera (DEVICE; rows
+ * 0..2 are read; the caller inverts the poses); the camera is fx, fy, cx, cy with an image of height x width pixels.
+ * Per (view f, point i), M = w2c[f], fp64, every operation rounded on its own (no FMA), IEEE division:
+ *   X = ((x M00 + y M01) + z M02) + M03, Y and Z likewise from rows 1 and 2;
+ *   projectable iff X, Y, Z are finite and z_near <= Z <= z_far;
+ *   u = (X fx) / Z + cx, v = (Y fy) / Z + cy, px = floor(u + 0.5), py = floor(v + 0.5), zf = (float)Z.
+ * pcmi_views_zbuffer: zbuf float32 [F, H, W] (written whole, +inf where a pixel is empty) = the minimum zf over the
+ *   projectable points whose window of splat x splat pixels (odd, 1 ... 7) centred on (px, py), clipped at the image's
+ *   borders, covers the pixel.  A 32-bit integer atomic minimum on the bit pattern of the positive float: no float
+ *   atomics, the same bits whatever the order of execution.  No synchronisation.
+ * pcmi_views_visible: point i is visible in view f iff it is projectable, 0 <= px < W and 0 <= py < H (tested on the
+ *   doubles) and (double)zf <= (double)zbuf[f, py, px] * (1.0 + rel_tol) -- the float32-rounded depth on both sides, so
+ *   that with rel_tol = 0 the point that set a pixel's minimum sees itself.  nw = ceil(n / 64):
+ *     mask uint64 [F, nw]: bit l of mask[f, w] = point 64 w + l is visible in f (bits past n are 0);
+ *     word_start int64 [F, nw]: the exclusive prefix sum of the words' popcounts in (f, w) order = the row of
+ *       pcmi_views_rows' output where the points of word (f, w) begin;
+ *     offsets int64 [F + 1] (device) and offsets_host [F + 1]: offsets[f] = word_start[f, 0], offsets[F] = all rows;
+ *     pixels int64 [F]: the pixels of zbuf[f] that hold a depth (integer atomics: the same from run to run).
+ *   One synchronisation, behind the copy of offsets to the host.  ws: pcmi_views_visible_workspace_bytes(n, F).
+ * pcmi_views_rows: rows int32 [offsets[F]] = the visible points of every view, ascending inside a view, views in
+ *   order, from mask and word_start as pcmi_views_visible left them.  No synchronisation.
+ * n = 0 or F = 0: success with empty outputs (offsets all 0).  PCMI_ERR_RANGE: splat even or outside 1 ... 7, H or W < 1,
+ *   n >= 2^31, F > 4096, F H W >= 2^31, F ceil(n / 64) >= 2^31.  PCMI_ERR_INVALID: a camera with a non-finite entry,
+ *   fx or fy <= 0, not 0 < z_near <= z_far < inf, rel_tol negative or not finite, points_ld < 3, a null pointer. */
+int pcmi_views_zbuffer(const double* points, int64_t points_ld, int64_t n, const double* w2c, int64_t n_views, double fx,
+                       double fy, double cx, double cy, int64_t height, int64_t width, double z_near, double z_far,
+                       int splat, float* zbuf, pcmi_stream_t stream);
+size_t pcmi_views_visible_workspace_bytes(int64_t n, int64_t n_views);
+int pcmi_views_visible(const double* points, int64_t points_ld, int64_t n, const double* w2c, int64_t n_views, double fx,
+                       double fy, double cx, double cy, int64_t height, int64_t width, double z_near, double z_far,
+                       double rel_tol, const float* zbuf, uint64_t* mask, int64_t* word_start, int64_t* offsets,
+                       int64_t* offsets_host, int64_t* pixels, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_views_rows(const uint64_t* mask, const int64_t* word_start, int64_t n, int64_t n_views, int32_t* rows,
+                    pcmi_stream_t stream);
+
 /* ---- PointNet++ point-set ops (csrc/pointset.hip) -----------------------------------------------------------------
  * What the reference's detection fine-tuning ("vn/" = downstream/votenet_det_new/ of the reference) reaches through its
  * one native extension, vn/models/backbone/pointnet2/pointnet2_utils.py.  fp32 data, int32 indices; feature tensors are

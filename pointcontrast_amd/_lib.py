@@ -159,6 +159,13 @@ PROTOTYPES = {
                                               c_vp, c_sz, c_vp]),
     "pcmi_corpus_overlap_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pcmi_corpus_overlap_counts": (C.c_int, [c_vp, c_vp, C.POINTER(c_i64), c_i64, C.c_double, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_views_zbuffer": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_double, C.c_double, C.c_double, C.c_double, c_i64, c_i64,
+                                     C.c_double, C.c_double, C.c_int, c_vp, c_vp]),
+    "pcmi_views_visible_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_views_visible": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_double, C.c_double, C.c_double, C.c_double, c_i64, c_i64,
+                                     C.c_double, C.c_double, C.c_double, c_vp, c_vp, c_vp, c_vp, C.POINTER(c_i64), c_vp, c_vp, c_sz,
+                                     c_vp]),
+    "pcmi_views_rows": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pcmi_fps_workspace_bytes": (c_sz, [c_i64, c_i64, C.c_int]),
     "pcmi_fps": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_ball_query": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, C.c_int, c_vp, c_vp]),

@@ -2109,3 +2109,58 @@ def rigid_sums(src, dst, offsets, best, Rt, tau):
   out = torch.empty((B, 16), dtype=torch.float64, device=dev)
   check(lib.pcmi_rigid_sums(ptr(s), ptr(d), s.shape[0], ptr(of), B, ptr(best), ptr(Rt), float(tau), ptr(out), cur_stream(dev)))
   return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Virtual views of a whole scan (csrc/views.hip; no counterpart in the reference): which points F pinhole cameras see.
+# The rule -- projection, splat window, float32 depth comparison -- is include/pcmi.h's; nothing here is differentiable.
+# ---------------------------------------------------------------------------------------------------------------------
+def _view_args(points, w2c, who):
+  require_cuda(points, who)
+  assert points.dim() == 2 and points.shape[1] == 3 and points.dtype == torch.float64, "%s: points float64 [n, 3]" % who
+  dev = points.device
+  assert torch.is_tensor(w2c) and w2c.device == dev and w2c.dtype == torch.float64 and w2c.dim() == 3 and w2c.shape[1:] == (4, 4), \
+      "%s: w2c float64 [F, 4, 4] on the points' device" % who
+  return _c(points), w2c.contiguous(), dev
+
+
+def view_zbuffer(points, w2c, fx, fy, cx, cy, height, width, z_near=0.1, z_far=10.0, splat=3):
+  """pcmi_views_zbuffer: points float64 [n, 3] (world frame; rows may be strided), w2c float64 [F, 4, 4] world-to-camera ->
+  zbuf float32 [F, height, width], the smallest float32 depth among the projectable points whose splat x splat window (odd,
+  1 ... 7, clipped at the borders) covers the pixel, +inf where there is none.  Bit-identical from run to run; no
+  synchronisation."""
+  p, m, dev = _view_args(points, w2c, "view_zbuffer")
+  F, H, W = m.shape[0], int(height), int(width)
+  zbuf = torch.empty((F, max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+  check(lib.pcmi_views_zbuffer(ptr(p), p.stride(0), p.shape[0], ptr(m), F, float(fx), float(fy), float(cx), float(cy), H, W,
+                               float(z_near), float(z_far), int(splat), ptr(zbuf), cur_stream(dev)))
+  return zbuf
+
+
+def view_visible(points, w2c, fx, fy, cx, cy, zbuf, z_near=0.1, z_far=10.0, rel_tol=0.05):
+  """pcmi_views_visible + pcmi_views_rows against zbuf float32 [F, H, W] (view_zbuffer's, same points and cameras): a point is
+  visible in view f iff it is projectable, its pixel lies inside the image and (double)zf <= (double)zbuf[f, py, px] (1 +
+  rel_tol).  Returns (rows int32 [total], the visible rows of every view, ascending inside a view; offsets int64 [F + 1] on
+  the device; offsets_host, the same as a numpy array; pixels int64 [F], the occupied pixels of every view; mask int64 [F,
+  ceil(n / 64)], bit l of word w = point 64 w + l).  One synchronisation (the offsets)."""
+  import numpy as np
+  p, m, dev = _view_args(points, w2c, "view_visible")
+  n, F = p.shape[0], m.shape[0]
+  assert torch.is_tensor(zbuf) and zbuf.device == dev and zbuf.dtype == torch.float32 and zbuf.dim() == 3 and zbuf.shape[0] == F \
+      and zbuf.is_contiguous(), "view_visible: zbuf contiguous float32 [F, H, W] on the points' device"
+  H, W = zbuf.shape[1], zbuf.shape[2]
+  nw = (n + 63) // 64
+  mask = torch.empty((F, nw), dtype=torch.int64, device=dev)
+  start = torch.empty((F, nw), dtype=torch.int64, device=dev)
+  offsets = torch.empty(F + 1, dtype=torch.int64, device=dev)
+  pixels = torch.empty(F, dtype=torch.int64, device=dev)
+  offs_h = (C.c_int64 * (F + 1))()
+  ws, wsb = ws_args(lib.pcmi_views_visible_workspace_bytes(n, F), dev)
+  check(lib.pcmi_views_visible(ptr(p), p.stride(0), n, ptr(m), F, float(fx), float(fy), float(cx), float(cy), H, W, float(z_near),
+                               float(z_far), float(rel_tol), ptr(zbuf), ptr(mask), ptr(start), ptr(offsets), offs_h, ptr(pixels), ws, wsb,
+                               cur_stream(dev)))  # syncs
+  offs_np = np.frombuffer(offs_h, dtype=np.int64).copy()
+  rows = torch.empty(int(offs_np[-1]), dtype=torch.int32, device=dev)
+  if rows.shape[0]:
+    check(lib.pcmi_views_rows(ptr(mask), ptr(start), n, F, ptr(rows), cur_stream(dev)))
+  return rows, offsets, offs_np, pixels, mask

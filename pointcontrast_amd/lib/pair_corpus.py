@@ -133,22 +133,28 @@ def read_color_calibration(scene_dir):
   return _read_4x4(path), np.linalg.inv(ext["color"]) @ ext["depth"]
 
 
+def write_members(path, members):
+  """An npz of {name: array}, stored, with a fixed zip timestamp: identical inputs give byte-identical files."""
+  tmp = path + ".tmp"
+  with zipfile.ZipFile(tmp, "w", compression=zipfile.ZIP_STORED, allowZip64=True) as zf:
+    for name, a in members.items():
+      info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+      a = np.asarray(a)  # (scalars stay 0-d)
+      with zf.open(info, "w", force_zip64=True) as f:
+        np.lib.format.write_array(f, a if a.flags.c_contiguous else np.ascontiguousarray(a), allow_pickle=False)
+  os.replace(tmp, path)
+
+
 def write_npz(path, pcd, color=None):
   """np.savez(path, pcd=pcd) with a fixed zip timestamp, so that identical inputs give byte-identical files.  color (uint8
   [n, 3]): a second member 'color' behind it; without one the file is what it was before colours existed."""
-  tmp = path + ".tmp"
-  members = [("pcd.npy", np.ascontiguousarray(pcd, dtype=np.float64))]
+  members = dict(pcd=np.ascontiguousarray(pcd, dtype=np.float64))
   if color is not None:
     color = np.ascontiguousarray(color, dtype=np.uint8)
-    if color.shape != (len(members[0][1]), 3):
-      raise ValueError("%s: color is %s for %d points" % (path, color.shape, len(members[0][1])))
-    members.append(("color.npy", color))
-  with zipfile.ZipFile(tmp, "w", compression=zipfile.ZIP_STORED, allowZip64=True) as zf:
-    for name, a in members:
-      info = zipfile.ZipInfo(name, date_time=(1980, 1, 1, 0, 0, 0))
-      with zf.open(info, "w", force_zip64=True) as f:
-        np.lib.format.write_array(f, a, allow_pickle=False)
-  os.replace(tmp, path)
+    if color.shape != (len(members["pcd"]), 3):
+      raise ValueError("%s: color is %s for %d points" % (path, color.shape, len(members["pcd"])))
+    members["color"] = color
+  write_members(path, members)
 
 
 def format_overlap(x):
@@ -171,6 +177,47 @@ def select_lines(lines, threshold):
 
 
 # ---- one scene on the device ---------------------------------------------------------------------------------------
+def centroids_and_overlap(vpts, voffs_np, voxel_size, dev, gpu_s):
+  """What follows the points of V views, whatever made them (back-projected depth frames here, the visible vertices of a scan
+  in lib/scan_views.py): vpts fp64 [n, 3] on the device, view k's rows voffs_np[k] ... voffs_np[k + 1].  Voxel centroids and
+  overlap counts on the current device (the caller holds torch.cuda.device(dev)); returns dict(points, centroids, C, M) as
+  process_scene documents them and adds the stages' seconds to gpu_s."""
+  import torch
+  from .._lib import check, lib
+  from ..runtime import cur_stream, ptr, ws_args
+  st = cur_stream(dev)
+  V = len(voffs_np) - 1
+  voffs = torch.from_numpy(voffs_np).to(dev)
+  voffs_h = (C.c_int64 * (V + 1))(*voffs_np.tolist())
+  n = int(voffs_np[-1])
+
+  t0 = time.perf_counter()
+  cent = torch.empty((n, 3), dtype=torch.float64, device=dev)
+  coffs = torch.empty(V + 1, dtype=torch.int64, device=dev)
+  coffs_h = (C.c_int64 * (V + 1))()
+  ws, wsb = ws_args(lib.pcmi_corpus_voxel_centroids_workspace_bytes(n, V), dev)
+  check(lib.pcmi_corpus_voxel_centroids(ptr(vpts), ptr(voffs), voffs_h, V, float(voxel_size), ptr(cent), ptr(coffs), coffs_h,
+                                        ws, wsb, st))  # syncs
+  gpu_s["voxel_centroids"] = time.perf_counter() - t0
+
+  t0 = time.perf_counter()
+  counts = torch.empty((V, V), dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_corpus_overlap_workspace_bytes(int(coffs_h[V]), V), dev)
+  check(lib.pcmi_corpus_overlap_counts(ptr(cent), ptr(coffs), coffs_h, V, 1.5 * voxel_size, ptr(counts), ws, wsb, st))
+  Cm = counts.cpu().numpy().astype(np.int64)  # waits for the count kernel
+  gpu_s["overlap_counts"] = time.perf_counter() - t0
+
+  t0 = time.perf_counter()
+  coffs_np = np.frombuffer(coffs_h, dtype=np.int64).copy()
+  pts_h = vpts.cpu().numpy()
+  cent_h = cent[:coffs_np[-1]].cpu().numpy()
+  gpu_s["download"] = time.perf_counter() - t0
+  nv = np.diff(coffs_np)
+  return dict(points=[pts_h[voffs_np[k]:voffs_np[k + 1]] for k in range(V)],
+              centroids=[cent_h[coffs_np[k]:coffs_np[k + 1]] for k in range(V)],
+              C=Cm, M=Cm.astype(np.float64) / nv[None, :].astype(np.float64))
+
+
 def process_scene(depths, poses, intrinsic, voxel_size=0.05, depth_shift=1000.0, device=None, colors=None, color_intrinsic=None,
                   depth_to_color=None):
   """Back-projection, validity, voxel centroids and overlap counts of the F frames of one scene.
@@ -253,35 +300,7 @@ def process_scene(depths, poses, intrinsic, voxel_size=0.05, depth_shift=1000.0,
       col_h = col[:offs_np[-1]].cpu().numpy()
       out["colors"] = [col_h[offs_np[f]:offs_np[f + 1]] for f in frames]
       del col
-    voffs = torch.from_numpy(voffs_np).to(dev)
-    voffs_h = (C.c_int64 * (V + 1))(*voffs_np.tolist())
-    n = int(voffs_np[-1])
-
-    t0 = time.perf_counter()
-    cent = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    coffs = torch.empty(V + 1, dtype=torch.int64, device=dev)
-    coffs_h = (C.c_int64 * (V + 1))()
-    ws, wsb = ws_args(lib.pcmi_corpus_voxel_centroids_workspace_bytes(n, V), dev)
-    check(lib.pcmi_corpus_voxel_centroids(ptr(vpts), ptr(voffs), voffs_h, V, float(voxel_size), ptr(cent), ptr(coffs), coffs_h,
-                                          ws, wsb, st))  # syncs
-    gpu_s["voxel_centroids"] = time.perf_counter() - t0
-
-    t0 = time.perf_counter()
-    counts = torch.empty((V, V), dtype=torch.int32, device=dev)
-    ws, wsb = ws_args(lib.pcmi_corpus_overlap_workspace_bytes(int(coffs_h[V]), V), dev)
-    check(lib.pcmi_corpus_overlap_counts(ptr(cent), ptr(coffs), coffs_h, V, 1.5 * voxel_size, ptr(counts), ws, wsb, st))
-    Cm = counts.cpu().numpy().astype(np.int64)  # waits for the count kernel
-    gpu_s["overlap_counts"] = time.perf_counter() - t0
-
-    t0 = time.perf_counter()
-    coffs_np = np.frombuffer(coffs_h, dtype=np.int64).copy()
-    pts_h = vpts.cpu().numpy()
-    cent_h = cent[:coffs_np[-1]].cpu().numpy()
-    gpu_s["download"] = time.perf_counter() - t0
-  nv = np.diff(coffs_np)
-  out.update(points=[pts_h[voffs_np[k]:voffs_np[k + 1]] for k in range(V)],
-             centroids=[cent_h[coffs_np[k]:coffs_np[k + 1]] for k in range(V)],
-             C=Cm, M=Cm.astype(np.float64) / nv[None, :].astype(np.float64))
+    out.update(centroids_and_overlap(vpts, voffs_np, voxel_size, dev, gpu_s))
   return out
 
 
