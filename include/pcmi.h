@@ -281,6 +281,12 @@ int pcmi_get_conv_precision(void);
  *   L2 row normalisation of the output features   pc/model/res16unet.py:262-266
  * bn_fwd_train: batch statistics over the n rows (biased var for normalisation, unbiased
  * for the running estimate, as torch), y = relu?((x-mean)*invstd*gamma+beta (+ residual)).
+ * The variance is sum x^2 - (sum x)^2 / n only where that is well conditioned: a row block also
+ * sums d = x - K and d^2 with K the column's value in the block's first row, and a column whose
+ * M2 is below 1/256 of its sum x^2 (|mean| / std > 16) gets (K + sum d / n_b, sum d^2 -
+ * (sum d)^2 / n_b); the blocks are merged with Chan's update; up to 1536 rows the one launch
+ * takes a centred second pass.  Tested per column to 1e-4 of float64 at mean / std = 256 and on
+ * constant columns, whose mean is their value to the bit and whose variance is exactly 0.
  * bn_bwd: gradients of that fused expression; relu_mask_y (nullable) is the forward output
  * whose sign gives the ReLU mask; dres (nullable) receives the residual-branch gradient.
  * ------------------------------------------------------------------------------------------ */

@@ -87,8 +87,9 @@ __device__ inline void chan_merge(float& n, float4& mean, float4& m2, float on, 
   if (tot <= 0.f) return;
   const float wa = n / tot, wb = on / tot, cross = n * on / tot;
   const float4 d = make_float4(omean.x - mean.x, omean.y - mean.y, omean.z - mean.z, omean.w - mean.w);
-  mean = make_float4(wa * mean.x + wb * omean.x, wa * mean.y + wb * omean.y, wa * mean.z + wb * omean.z,
-                     wa * mean.w + wb * omean.w);
+  // (two sets of the same mean, the blocks of a constant column, keep it to the bit: wa + wb is 1 only to round-off)
+  mean = make_float4(d.x == 0.f ? mean.x : wa * mean.x + wb * omean.x, d.y == 0.f ? mean.y : wa * mean.y + wb * omean.y,
+                     d.z == 0.f ? mean.z : wa * mean.z + wb * omean.z, d.w == 0.f ? mean.w : wa * mean.w + wb * omean.w);
   m2 = make_float4(m2.x + om2.x + d.x * d.x * cross, m2.y + om2.y + d.y * d.y * cross, m2.z + om2.z + d.z * d.z * cross,
                    m2.w + om2.w + d.w * d.w * cross);
   n = tot;
@@ -145,7 +146,20 @@ __device__ __forceinline__ void colreduce_write(const RedFinal& fin, int t, cons
   }
 }
 
-// MODE 0: (sum x, sum x^2) per block -> (mean_b, M2_b)
+// LDS of the pivoted sums of colreduce_partial_kernel<0> (a function of its own: the MODE 1 instantiations declare none of it)
+__device__ __forceinline__ float4* pivot_sums_lds() {
+  __shared__ float4 s[512];
+  return s;
+}
+constexpr float kPlainCond = 256.f;
+__device__ __forceinline__ void pivot_or_plain(float& m, float& m2, float sxx, float pivot, float sd, float sdd, float nb) {
+  if (m2 * kPlainCond >= sxx) return;
+  const float md = sd / nb;
+  m = pivot + md;
+  m2 = fmaxf(sdd - sd * md, 0.f);
+}
+
+// MODE 0: (sum x, sum x^2) and (sum d, sum d^2), d = x - the column's value in the block's first row -> (mean_b, M2_b)
 // MODE 1: (sum dy_eff, sum dy_eff * xhat)
 // MASK (MODE 1): 0 no ReLU, 1 the pattern from y (fp32, `ymask`), 2 from `bits` (relu_bits).  A TEMPLATE parameter since
 // round 6: as a run-time `if (ymask)` around the load inside the 4-row batch, hipcc put every row's mask load in a branch
@@ -189,12 +203,18 @@ __global__ __launch_bounds__(256, MASK == 0 ? 8 : 1) void colreduce_partial_kern
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = min(r0 + (int64_t)rows_per_block, n);
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+  // MODE 0: beside (sum x, sum x^2) the block sums d = x - pivot and d^2, the pivot being the column's value in the block's
+  // first row (r0 < n: always a row of the block).  sum x^2 - (sum x)^2 / nb cancels to round-off of mean^2, the same expression
+  // of d to round-off of (mean - pivot)^2, which is of the size of the variance itself; a constant column has d = 0 in every
+  // row: M2 = 0 exactly.  Which pair the block writes is decided per column where the sums are complete (below).
+  float4 pivot = a, ad = a, bd = a;
   if (rl < rp) {
     float4 mu = a, is = a;
     if (MODE == 1) {
       mu = reinterpret_cast<const float4*>(mean)[col];
       is = reinterpret_cast<const float4*>(invstd)[col];
     }
+    if constexpr (MODE == 0) pivot = *reinterpret_cast<const float4*>(x + r0 * x_ld + col * 4);
     // rows in batches of kRowBatch: every load of a batch is issued before the first use (a row at a time was one
     // L2 / HBM latency per row and thread -- the small-activation BatchNorms were latency-, not bandwidth-bound)
     constexpr int kRowBatch = 4;
@@ -222,6 +242,11 @@ __global__ __launch_bounds__(256, MASK == 0 ? 8 : 1) void colreduce_partial_kern
           a.x += xq.x; a.y += xq.y; a.z += xq.z; a.w += xq.w;
           b.x = fmaf(xq.x, xq.x, b.x); b.y = fmaf(xq.y, xq.y, b.y);
           b.z = fmaf(xq.z, xq.z, b.z); b.w = fmaf(xq.w, xq.w, b.w);
+          // (a row past r1 adds nothing here either: its difference from the pivot is zeroed)
+          const float4 d = ok[u] ? make_float4(xq.x - pivot.x, xq.y - pivot.y, xq.z - pivot.z, xq.w - pivot.w) : zero4;
+          ad.x += d.x; ad.y += d.y; ad.z += d.z; ad.w += d.w;
+          bd.x = fmaf(d.x, d.x, bd.x); bd.y = fmaf(d.y, d.y, bd.y);
+          bd.z = fmaf(d.z, d.z, bd.z); bd.w = fmaf(d.w, d.w, bd.w);
         } else {
           float4 g = ok[u] ? gv[u] : zero4;
           if constexpr (MASK == 2) yv[u] = relu_bits_as_mask(wv[u], col);
@@ -238,6 +263,11 @@ __global__ __launch_bounds__(256, MASK == 0 ? 8 : 1) void colreduce_partial_kern
   }
   s_a[t] = a;
   s_b[t] = b;
+  float4* const s_d = MODE == 0 ? pivot_sums_lds() : nullptr;  // [2][256], MODE 0 only
+  if constexpr (MODE == 0) {
+    s_d[t] = ad;
+    s_d[256 + t] = bd;
+  }
   __syncthreads();
   if (t < c4) {
     float4 sa = s_a[t], sb = s_b[t];
@@ -247,12 +277,25 @@ __global__ __launch_bounds__(256, MASK == 0 ? 8 : 1) void colreduce_partial_kern
       sb.x += vb.x; sb.y += vb.y; sb.z += vb.z; sb.w += vb.w;
     }
     float* p0 = part + (int64_t)blockIdx.x * 2 * c;
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
       const float nb = (float)(r1 - r0);
       float4 m, m2;
       m.x = sa.x / nb; m.y = sa.y / nb; m.z = sa.z / nb; m.w = sa.w / nb;
       m2.x = fmaxf(sb.x - sa.x * m.x, 0.f); m2.y = fmaxf(sb.y - sa.y * m.y, 0.f);
       m2.z = fmaxf(sb.z - sa.z * m.z, 0.f); m2.w = fmaxf(sb.w - sa.w * m.w, 0.f);
+      // The same of d (t < c4: this thread's column is t, its pivot the column's): mean_b = pivot + sum d / nb.
+      float4 sad = s_d[t], sbd = s_d[256 + t];
+      for (int q = 1; q < rp; ++q) {
+        const float4 va = s_d[q * c4 + t], vb = s_d[256 + q * c4 + t];
+        sad.x += va.x; sad.y += va.y; sad.z += va.z; sad.w += va.w;
+        sbd.x += vb.x; sbd.y += vb.y; sbd.z += vb.z; sbd.w += vb.w;
+      }
+      // Per column, the better conditioned of the two.  While M2 is at least 1 / kPlainCond of sum x^2 (|mean| / std < 16)
+      // the plain sums lose at most kPlainCond x round-off of it and carry the more exact MEAN (the pivot is one draw of the
+      // column: sum d is of the size nb |pivot - mean|, which for |mean| << std is far more than sum x); below that the
+      // cancellation takes over and the sums of d are taken.  (A block of zeros: 0 >= 0, the plain sums, (0, 0).)
+      pivot_or_plain(m.x, m2.x, sb.x, pivot.x, sad.x, sbd.x, nb); pivot_or_plain(m.y, m2.y, sb.y, pivot.y, sad.y, sbd.y, nb);
+      pivot_or_plain(m.z, m2.z, sb.z, pivot.z, sad.z, sbd.z, nb); pivot_or_plain(m.w, m2.w, sb.w, pivot.w, sad.w, sbd.w, nb);
       reinterpret_cast<float4*>(p0)[t] = m;
       reinterpret_cast<float4*>(p0 + c)[t] = m2;
     } else {
@@ -465,9 +508,9 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float* __rest
     const float ocnt = __shfl_xor(cnt, d, 64), omean = __shfl_xor(mean, d, 64), om2 = __shfl_xor(m2, d, 64);
     const float tot = cnt + ocnt;
     if (tot > 0.f) {
-      // symmetric form so that both partners compute bit-identical results
+      // symmetric form so that both partners compute bit-identical results (equal means stay what they are to the bit)
       const float delta = omean - mean;
-      const float nmean = (cnt * mean + ocnt * omean) / tot;
+      const float nmean = delta == 0.f ? mean : (cnt * mean + ocnt * omean) / tot;
       m2 = m2 + om2 + delta * delta * (cnt * ocnt / tot);
       mean = nmean;
       cnt = tot;
@@ -581,6 +624,21 @@ __device__ __forceinline__ void small_store(__amdgpu_buffer_rsrc_t r, uint32_t v
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, t), r, voff, 0, 0);
 }
 
+// sum over the segment's rows of (x - mean)^2 of the register-resident rows, every thread the total of its column group
+template <int RPT, int RL>
+__device__ __forceinline__ float4 small_centred_m2(const float4 (&xv)[RPT], const float4& mean, int rl, int ns,
+                                                   float4 (*s_w)[kSmallCG], int t) {
+  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int j = 0; j < RPT; ++j) {
+    if (rl + j * RL < ns) {  // (rows past the segment were loaded as zeros: they must not count as -mean)
+      const float dx = xv[j].x - mean.x, dy = xv[j].y - mean.y, dz = xv[j].z - mean.z, dw = xv[j].w - mean.w;
+      q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
+    }
+  }
+  return small_block_sum(q, s_w, t);
+}
+
 template <int RPT, int THREADS>
 __global__ __launch_bounds__(THREADS) void bn_small_fwd_kernel(BnSmallFwd a) {
   __shared__ float4 s_w[16][kSmallCG];
@@ -610,16 +668,31 @@ __global__ __launch_bounds__(THREADS) void bn_small_fwd_kernel(BnSmallFwd a) {
   for (int j = 0; j < RPT; ++j) { s.x += xv[j].x; s.y += xv[j].y; s.z += xv[j].z; s.w += xv[j].w; }
   s = small_block_sum(s, s_w, t);
   const float cnt = (float)ns;
-  const float4 mean = make_float4(s.x / cnt, s.y / cnt, s.z / cnt, s.w / cnt);
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 mean = make_float4(s.x / cnt, s.y / cnt, s.z / cnt, s.w / cnt);
+  float4 q = small_centred_m2<RPT, RL>(xv, mean, rl, ns, s_w, t);
+  // A column whose spread is below 2^-8 of its mean (a constant one above all): sum x / n is a few ulp off the mean, which is
+  // then no longer small against the spread -- n equal values of 0.1f give a "mean" one ulp off 0.1f, and 1 / sqrt(eps) = 316
+  // times that reaches y and dgamma.  Such columns (rare; one barrier tells whether the workgroup has any) take the mean as
+  // pivot + mean(x - pivot), the pivot the segment's first row: a constant column keeps its value to the bit, M2 = 0.
+  const float kNear = 1.f / 65536.f;
+  const bool nx = q.x < cnt * kNear * mean.x * mean.x, ny = q.y < cnt * kNear * mean.y * mean.y,
+             nz = q.z < cnt * kNear * mean.z * mean.z, nw = q.w < cnt * kNear * mean.w * mean.w;
+  if (__syncthreads_or(nx || ny || nz || nw)) {
+    const float4 pv = small_load(xr, (uint32_t)cg * 16u, 0u);
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-  for (int j = 0; j < RPT; ++j) {
-    if (rl + j * RL < ns) {  // (rows past the segment were loaded as zeros: they must not count as -mean)
-      const float dx = xv[j].x - mean.x, dy = xv[j].y - mean.y, dz = xv[j].z - mean.z, dw = xv[j].w - mean.w;
-      q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
+    for (int j = 0; j < RPT; ++j) {
+      if (rl + j * RL < ns) {  // (rows past the segment were loaded as zeros)
+        r.x += xv[j].x - pv.x; r.y += xv[j].y - pv.y; r.z += xv[j].z - pv.z; r.w += xv[j].w - pv.w;
+      }
     }
+    r = small_block_sum(r, s_w, t);
+    const float4 mp = make_float4(nx ? pv.x + r.x / cnt : mean.x, ny ? pv.y + r.y / cnt : mean.y, nz ? pv.z + r.z / cnt : mean.z,
+                                  nw ? pv.w + r.w / cnt : mean.w);
+    const float4 qp = small_centred_m2<RPT, RL>(xv, mp, rl, ns, s_w, t);
+    mean = mp;
+    q = make_float4(nx ? qp.x : q.x, ny ? qp.y : q.y, nz ? qp.z : q.z, nw ? qp.w : q.w);
   }
-  q = small_block_sum(q, s_w, t);
   if (rl == 0) colreduce_write<0>(fin, col4, mean, q, cnt);  // mean, invstd, unbiased variance, running estimates
   const float4 is = bn_invstd(q, cnt, fin.eps);
   const float4 g = reinterpret_cast<const float4*>(a.gamma)[col4], b = reinterpret_cast<const float4*>(a.beta)[col4];

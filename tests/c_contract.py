@@ -179,4 +179,4 @@ def bn_ref64(x, gamma, beta, eps, res, relu, dy, relu_mask=None):
   y.backward(dy.double())
   n = x.shape[0]
   return dict(y=y_free, mean=mean.detach(), var=var.detach(), unbiased=(var * n / max(n - 1, 1)).detach(), dx=x64.grad,
-              dgamma=g64.grad, dbeta=b64.grad, flipped_max=flipped_max)
+              dgamma=g64.grad, dbeta=b64.grad, dres=r64.grad if r64 is not None else None, flipped_max=flipped_max)

@@ -76,18 +76,24 @@ def _net(ME, c):
   return Net()
 
 
-def _cloud(rng, n, c):
-  """n unique integer coordinates (batch index 0) and features with a mean (the batch means are then well off zero)."""
+def _cloud(rng, n, c, features=None, cloud=0):
+  """n unique integer coordinates (batch index 0) and features with a mean (the batch means are then well off zero).
+  features: (rng, n, c, cloud) -> float32 [n, c] instead of them (tests/test_gpu_norm_conditioning.py)."""
   cell = rng.choice(48 ** 3, n, replace=False)
   C = np.stack([np.zeros(n, np.int64), cell // (48 * 48) - 24, cell // 48 % 48 - 24, cell % 48 - 24], 1).astype(np.int32)
-  F = (rng.standard_normal((n, c)) * 2.0 + 0.7).astype(np.float32)
+  if features is None:
+    F = (rng.standard_normal((n, c)) * 2.0 + 0.7).astype(np.float32)
+  else:
+    F = np.ascontiguousarray(features(rng, n, c, cloud), dtype=np.float32)
+    assert F.shape == (n, c)
   return torch.from_numpy(C), torch.from_numpy(F)
 
 
-def run_case(ME, segs, c, seed=0):
+def run_case(ME, segs, c, seed=0, features=None, identity_conv0=False):
   """Runs the model on the device three ways and returns everything the checks (and a bit-for-bit comparison of two
   builds) need, on the CPU: {"params", "running0", "x", "g", "eps", "momentum", "runs": {run: {"bn_in", "bn_res",
-  "bn_out" (per layer), "running" (after the pass), "grad" (flat.g after its backward)}}}."""
+  "bn_out" (per layer), "running" (after the pass), "grad" (flat.g after its backward)}}}.
+  features: the feature generator of _cloud; identity_conv0: conv0.kernel = I, so that bn0 normalises the features themselves."""
   from pointcontrast_amd.engine import NativeEngine, OP_BN
   from pointcontrast_amd.lib.distributed import FlatParameters
   torch.manual_seed(seed)
@@ -100,13 +106,15 @@ def run_case(ME, segs, c, seed=0):
       bn.bias.uniform_(-0.5, 0.5)
       bn.running_mean.normal_()
       bn.running_var.uniform_(0.5, 1.5)
+    if identity_conv0:
+      model.conv0.kernel.copy_(torch.eye(c).view_as(model.conv0.kernel))
   model = model.to(DEV).train()
   flat = FlatParameters(model.parameters())
   eng = NativeEngine(model, flat, in_channels=c)
   bns = [getattr(model, "bn%d" % i).bn for i in range(3)]
   bn_ops = [o for o in eng._ops if o["type"] == OP_BN]
   assert len(bn_ops) == 3 and [o["relu"] for o in bn_ops] == [0, 1, 1] and bn_ops[2]["in2"] == bn_ops[0]["out"]
-  clouds = [_cloud(rng, n, c) for n in segs]
+  clouds = [_cloud(rng, n, c, features, k) for k, n in enumerate(segs)]
   g = [torch.randn(n, c) for n in segs]
   running0 = [(b.running_mean.clone(), b.running_var.clone()) for b in bns]
 
