@@ -256,6 +256,44 @@ int pcmi_spconv_split_precision(void);
 int pcmi_spconv_plan(int64_t rows, int64_t x_bytes, int C, int N, int K, int form, int* kernel, int* rows_per_wave,
                      int* slice, int* ksplit, size_t* ws_bytes);
 
+/* What one pcmi_spconv_bwd_weight call will do (csrc/spconv_wgrad_plan.h: plan_wgrad, the function the call itself
+ * executes): host code only, as pcmi_spconv_plan.  It reads the environment (PCMI_WGRAD_*) and the calling thread's
+ * convolution precision as the call does.
+ *   n_in, n_out, cin, cout, transpose, gbias (0 / 1: a bias gradient is wanted)   as in the call
+ *   K             offsets of the map (1 without one)
+ *   kernel_size, stride   of the map (3, 1 or 2, 2); kernel_size 0: no map (the dense 1x1 form)
+ *   map_tables    PCMI_WGRAD_MAP_NBR: the map carries nbr;  PCMI_WGRAD_MAP_PERM: it carries perm and nbr_perm
+ *   accumulate    1: the call adds to gweight (the executor's calls; pcmi_spconv_bwd_weight itself overwrites: 0)
+ *   x_bytes, g_bytes   size of `in` and `gout` (rows x leading dimension x 4)
+ *   aligned       1: both start 16-byte aligned and their leading dimensions are multiples of 4
+ *   counts_host   nullable [K + 1]: host prefix of the per-offset pair counts (pcmi_kmap_t::offs_host) when the map has
+ *                 them (M >= 0); NULL: the plan works with the bounds a launch takes in front of their arrival
+ *   slots_per_cu  resident workgroups per CU of the pair-list kernel's variant; 0: ask the HIP runtime, as a launch does
+ *                 (2 where it cannot be asked)
+ * Out (each nullable):  kernel PCMI_WGRAD_KERNEL_*;  tile_c, tile_n: per workgroup and axis, the 32-channel tiles of
+ * wgrad_mfma_kernel or the 16-wide tiles per wave of the tile-stationary kernels (0 for the stems);  chunk: pairs per
+ * workgroup, and slots_per_offset: chunk slots of an offset (0 without a map), of the pair-list kernels;  mode
+ * PCMI_WGRAD_MODE_*: how the chunks of an offset become gW;  address_bits: 32 or 64, how wgrad_mfma_kernel addresses its
+ * operands (0 for the other kernels);  row_blocks: of the tile-stationary kernels, or the workgroups of
+ * stem_wgrad_mfma_kernel;  groupable: 1 if the executor may put the layer into a grouped launch;  ws_bytes: the smallest
+ * workspace the call accepts (at most pcmi_spconv_workspace_bytes() of the convolution).
+ * PCMI_ERR_INVALID / PCMI_ERR_UNSUPPORTED for a shape no launch has, as the call itself returns them. */
+#define PCMI_WGRAD_MAP_NBR 1
+#define PCMI_WGRAD_MAP_PERM 2
+#define PCMI_WGRAD_KERNEL_NONE 0       /* no pairs: nothing to do but zeroing */
+#define PCMI_WGRAD_KERNEL_X3P 1        /* wgrad_x3p_kernel: tile-stationary split precision, producer / consumer */
+#define PCMI_WGRAD_KERNEL_X3T 2        /* wgrad_x3t_kernel: the one-role form, and everything in one-term (bf16) mode */
+#define PCMI_WGRAD_KERNEL_STEM_MFMA 3  /* stem_wgrad_mfma_kernel: the 3-channel stem on the matrix cores */
+#define PCMI_WGRAD_KERNEL_STEM 4       /* stem_wgrad_kernel: the 3-channel stem over the pair list */
+#define PCMI_WGRAD_KERNEL_PAIRS 5      /* wgrad_mfma_kernel: the pair list of one offset per workgroup, fp32 MFMA */
+#define PCMI_WGRAD_MODE_SLABS 0        /* every workgroup writes a slab, wgrad_reduce_kernel sums them */
+#define PCMI_WGRAD_MODE_DIRECT 1       /* one chunk per offset: the workgroup writes gW itself */
+#define PCMI_WGRAD_MODE_ARRIVE 2       /* slabs, summed by the last-arriving workgroup of the (offset, tile) */
+int pcmi_spconv_wgrad_plan(int64_t n_in, int64_t n_out, int cin, int cout, int K, int kernel_size, int stride, int map_tables,
+                           int transpose, int gbias, int accumulate, int64_t x_bytes, int64_t g_bytes, int aligned,
+                           const int64_t* counts_host, int slots_per_cu, int* kernel, int* tile_c, int* tile_n, int* chunk,
+                           int* slots_per_offset, int* mode, int* address_bits, int* row_blocks, int* groupable, size_t* ws_bytes);
+
 /* Convolution precision mode.  PCMI_CONV_PRECISION_FP32 (the default) is the arithmetic above.  In
  * PCMI_CONV_PRECISION_BF16 the launches the split-precision kernels take by default -- the forward / backward-data
  * launches of spconv16x (>= 64 channels on both sides, >= 512 rows, table and unit-balanced form) and the weight

@@ -99,6 +99,8 @@ PROTOTYPES = {
                                          c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_spconv_split_precision": (C.c_int, []),
     "pcmi_spconv_plan": (C.c_int, [c_i64, c_i64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(c_sz)]),
+    "pcmi_spconv_wgrad_plan": (C.c_int, [c_i64, c_i64] + [C.c_int] * 9 + [c_i64, c_i64, C.c_int, C.POINTER(c_i64), C.c_int] +
+                               [C.POINTER(C.c_int)] * 9 + [C.POINTER(c_sz)]),
     "pcmi_set_conv_precision": (C.c_int, [C.c_int]),
     "pcmi_get_conv_precision": (C.c_int, []),
     "pcmi_bn_workspace_bytes": (c_sz, [c_i64, C.c_int]),

@@ -40,7 +40,7 @@ def _digest(paths):
 
 
 def _headers():
-  return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "spconv_args.h"), os.path.join(CSRC, "spconv_plan.h"),
+  return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "spconv_args.h"), os.path.join(CSRC, "spconv_plan.h"), os.path.join(CSRC, "spconv_wgrad_plan.h"),
           os.path.join(CSRC, "x3_split.h"), os.path.join(HERE, "..", "include", "pcmi.h")]
 
 

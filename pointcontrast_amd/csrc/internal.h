@@ -132,10 +132,9 @@ struct ConvPrecisionScope {
 };
 
 // spconv_wgrad_x3.hip: weight gradients of the 3^3 / stride-1 convolutions, output-tile stationary on the bf16 matrix cores
-bool wgrad_x3t_eligible(const pcmi_kmap_t* map, int64_t n_in, int64_t n_out, int cin, int cout, int64_t in_ld, int64_t gout_ld);
-size_t wgrad_x3t_workspace(int64_t n_rows, int cin, int cout);
+struct WgradPlan;  // spconv_wgrad_plan.h: plan_wgrad decides which calls take these kernels and sizes their launches
 int wgrad_x3t_run(const float* in, int64_t in_ld, const float* gout, int64_t gout_ld, int64_t n_rows, int cin, int cout,
-                  const pcmi_kmap_t* map, float* gweight, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
+                  const pcmi_kmap_t* map, const WgradPlan& plan, float* gweight, int accumulate, void* ws, hipStream_t st);
 
 // nce_x3.hip: PointInfoNCE forward / backward on the bf16 matrix cores (three-term split); c in {16, 32}, q / k contiguous
 // and 16-byte aligned, ws of pcmi_nce_workspace_bytes and 16-byte aligned.  PCMI_NCE_X3=0 keeps the fp32 VALU kernels of loss.hip.

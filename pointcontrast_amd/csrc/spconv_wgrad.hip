@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "spconv_wgrad_plan.h"
 
 namespace pcmi {
 
@@ -47,7 +48,6 @@ struct WgradArgs {
   int accumulate;
   unsigned* counters;  // kArrive: one per (offset, tile-y, tile-z), zero on entry and on exit
 };
-enum { kSlabs = 0, kDirect = 1, kArrive = 2 };
 constexpr int kWgradGroupMax = 16;  // layers per grouped launch (WgradGroup travels in the kernel arguments: 16 x 128 B)
 
 template <int V>
@@ -667,7 +667,6 @@ __global__ __launch_bounds__(256) void stem_slab_reduce_kernel(const float* __re
   for (int q = 1; q < 32; ++q) s += s_p[q][el];
   gw[e] = accumulate ? gw[e] + s : s;
 }
-constexpr int kStemSlabs = 512;  // workgroups (= slabs) of stem_wgrad_mfma_kernel: two per CU
 
 // column sums (bias gradient): two-level, deterministic.  A workgroup sums its row block with 256 / c row lanes per
 // column (round 4 used one thread per column: 32 of 256 threads at c = 32, each walking its 171 rows alone -- 111 us
@@ -773,100 +772,51 @@ static int wgrad_occupancy(int CT, int NT, bool idx) {
   }
 }
 
-static int tiles_per_wg(int tiles32) {  // tiles (of 32 channels) a workgroup covers per axis
-  if (tiles32 % 3 == 0) return 3;
-  if (tiles32 % 2 == 0) return 2;
-  return 1;
-}
-
-// Pairs per workgroup.  Every chunk costs the same, so the launch runs in ceil(workgroups / resident slots) rounds of
-// equal length, and a round lasts as long as the wave with the most 64-pair groups: ceil(chunk / 256) groups.  Pick
-// the chunk with the smallest rounds x groups (ties: the larger chunk, fewer slabs).  Per-wave cycle accounting
-// (scripts/wgrad_prof.py) of the rule this replaces -- "the largest chunk that fills >= 92 % of a whole number of
-// rounds" -- on the level-1 96->96 gradient: 3200 pairs = 12.5 groups per wave, i.e. half the waves of every workgroup
-// waited one whole group (8 % of the loop) at the reduction barrier, and 480 workgroups on 512 slots.
-constexpr int kWgradMinChunk = 256, kWgradMaxChunks = 4096;
-// Longest chunk (pairs).  A workgroup of the level-1 gradients runs ~80 us per 1024 pairs and is never pre-empted: while
-// it holds its CU, the latency-critical kernels of the bwd-data chain (higher stream priority, but priority only orders
-// the DISPATCH of new workgroups) wait for a slot.
-static int wgrad_max_chunk() { return 4096; }
-
-static int wgrad_min_chunk(int64_t M) {
-  return (int)std::max<int64_t>(kWgradMinChunk, align_up((size_t)ceil_div(M, kWgradMaxChunks), 128));
-}
-
-// Pairs one offset of a map can have at most: a row takes part in at most one pair per offset on either side.
-static int64_t wgrad_offset_bound(int64_t n_in, int64_t n_out) { return std::min(n_in, n_out); }
-
-// Pairs of offset k as far as the host knows (only steers the chunk size): exact once the map's counts have arrived,
-// otherwise the typical occupancy of a surface (17 of 27 neighbours) / an even split of the fine rows over the 8 children.
-static int64_t wgrad_offset_len(const pcmi_kmap_t* map, int k) {
-  if (map->M >= 0) return map->offs_host[k + 1] - map->offs_host[k];
-  return map->stride == 1 ? map->n_out * 17 / 27 : ceil_div(map->n_in, map->K);
-}
-
-static int64_t wgrad_num_chunks(const pcmi_kmap_t* map, int64_t M, int chunk) {
-  if (!map) return ceil_div(M, chunk);
-  int64_t n = 0;
-  for (int k = 0; k < map->K; ++k) n += ceil_div(wgrad_offset_len(map, k), chunk);
-  return n;
-}
-
-// lo: smallest admissible chunk (keeps the number of chunk slots bounded, see spconv_wgrad_workspace)
-static int wgrad_chunk(const pcmi_kmap_t* map, int64_t M, int lo, int64_t wgs_per_chunk, int64_t slots) {
-  int64_t best_cost = -1;
-  for (int c = std::max(lo, wgrad_max_chunk()); c >= lo; c -= 128) {
-    const int64_t cost = ceil_div(wgrad_num_chunks(map, M, c) * wgs_per_chunk, slots) * ceil_div(c, 256);
-    if (best_cost < 0 || cost < best_cost) best_cost = cost;
-  }
-  // the largest chunk within 4 % of the best: fewer slabs to write and to sum
-  for (int c = std::max(lo, wgrad_max_chunk()); c >= lo; c -= 128) {
-    const int64_t cost = ceil_div(wgrad_num_chunks(map, M, c) * wgs_per_chunk, slots) * ceil_div(c, 256);
-    if (cost * 100 <= best_cost * 104) return c;
-  }
-  return lo;
-}
-
-// Slab slots of a launch: K * ceil(offset bound / chunk) for a map (WgradArgs::mpk), ceil(M / chunk) for the dense case;
-// the smallest chunk a launch may pick keeps them under ~4096 + K.
-static int wgrad_lo_chunk(int64_t n_in, int64_t n_out, int K, int64_t M) {
-  return K > 1 ? wgrad_min_chunk(wgrad_offset_bound(n_in, n_out) * K) : wgrad_min_chunk(M);
-}
-
 size_t spconv_wgrad_workspace(int64_t n_in, int64_t n_out, int cin, int cout, int K, int64_t M) {
-  if (M <= 0) M = std::max(n_in, n_out);
-  const int lo = wgrad_lo_chunk(n_in, n_out, K, M);
-  const int64_t nchunks = K > 1 ? (int64_t)K * ceil_div(wgrad_offset_bound(n_in, n_out), lo) : ceil_div(M, lo);
-  const size_t pairwise = (size_t)std::max<int64_t>(nchunks, 1) * cin * cout * sizeof(float);
-  // spconv_wgrad_x3.hip (K = 1: the dense 1x1 form of the same kernel, up to 128 row blocks of one slab each)
-  const size_t tiled = (K == 27 && n_in == n_out) ? wgrad_x3t_workspace(n_out, cin, cout)
-                                                  : ((K == 1 && n_in == n_out) ? (size_t)128 * cin * cout * sizeof(float) : 0);
-  const size_t stem_slabs = cin == 3 ? (size_t)kStemSlabs * K * cin * cout * sizeof(float) : 0;  // stem_wgrad_mfma_kernel
-  return std::max(std::max(pairwise, tiled), stem_slabs) + (size_t)1024 * cout * sizeof(float);
+  return wgrad_workspace_bound(wgrad_env(), n_in, n_out, cin, cout, K, M);
 }
 
-}  // namespace pcmi
-
-using namespace pcmi;
-
-namespace pcmi {
 size_t spconv_fwd_bwd_workspace(int64_t n_in, int64_t n_out, int cin, int cout, int K);
-}
 
-namespace pcmi {
 size_t spconv_workspace_m32(int64_t n_in, int64_t n_out, int cin, int cout, int K, int64_t M) {
   return std::max(spconv_fwd_bwd_workspace(n_in, n_out, cin, cout, K),
                   spconv_wgrad_workspace(n_in, n_out, cin, cout, K, M)) + 256;
 }
-}  // namespace pcmi
 
-namespace pcmi {
-// Everything a pair-list launch needs besides the launch itself: operands, chunk size, chunk slots per offset, how the
-// chunks of an offset become gW (mode), the tile shape.  Shared by the single launch and the grouped one.
-static int wgrad_plan(const float* in, int64_t in_ld, int64_t n_in, int cin, const float* gout, int64_t gout_ld, int64_t n_out,
-                      int cout, const pcmi_kmap_t* map, int transpose, float* gweight, int accumulate, int64_t M, hipStream_t st,
-                      WgradArgs* out, int* CT_out, int* NT_out, int64_t* nchunks_out) {
-  const int K = map ? map->K : 1;
+// The call as plan_wgrad sees it.  What the plan of a pair-list launch needs from the HIP runtime, the residency of the
+// variant the channels select, is asked here (cached per variant; the other families ignore it).
+static WgradShape wgrad_shape(const float* in, int64_t in_ld, int64_t n_in, int cin, const float* gout, int64_t gout_ld,
+                              int64_t n_out, int cout, const pcmi_kmap_t* map, int transpose, bool gbias, int accumulate, int64_t M) {
+  WgradShape s = {};
+  s.n_in = n_in;
+  s.n_out = n_out;
+  s.cin = cin;
+  s.cout = cout;
+  s.K = map ? map->K : 1;
+  s.has_map = map != nullptr;
+  s.kernel_size = map ? map->kernel_size : 0;
+  s.stride = map ? map->stride : 0;
+  s.has_nbr = map && map->nbr;
+  s.has_perm = map && map->perm && map->nbr_perm;
+  s.transpose = transpose != 0;
+  s.gbias = gbias;
+  s.accumulate = accumulate != 0;
+  s.x_bytes = n_in * in_ld * 4;
+  s.g_bytes = n_out * gout_ld * 4;
+  s.aligned = in_ld % 4 == 0 && gout_ld % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)gout % 16 == 0;
+  s.M = M;
+  s.counts = (map && map->M >= 0) ? map->offs_host : nullptr;
+  s.terms = conv_terms();
+  if (M != 0 && cin % 32 == 0 && cout % 32 == 0)
+    s.slots_per_cu = wgrad_occupancy(wgrad_pair_tiles(cin), wgrad_pair_tiles(cout), map != nullptr);
+  return s;
+}
+
+// The arguments of a pair-list launch, the single one and a layer of the grouped one: operands, and the chunk size, chunk
+// slots per offset and mode its plan gives it.  Slabs and arrival counters are the caller's.
+static WgradArgs wgrad_args(const float* in, int64_t in_ld, int cin, const float* gout, int64_t gout_ld, int cout,
+                            const pcmi_kmap_t* map, int transpose, float* gweight, int accumulate, int64_t M, int chunk, int mpk,
+                            int mode) {
   WgradArgs a;
   a.x = in;
   a.x_ld = in_ld;
@@ -876,54 +826,20 @@ static int wgrad_plan(const float* in, int64_t in_ld, int64_t n_in, int cin, con
   a.idx_g = map ? (transpose ? map->pair_in : map->pair_out) : nullptr;
   a.offs = map ? map->offs : nullptr;
   a.M = M;
-  a.K = K;
+  a.K = map ? map->K : 1;
   a.cin = cin;
   a.cout = cout;
-  const bool stem = cin < 8;
-  int CT = 1, NT = 1;
-  int64_t slots = 8 * (int64_t)num_cu(), wgs_per_chunk = 1;
-  if (stem) {
-    PCMI_REQUIRE(cin == 3 && cout % 32 == 0, PCMI_ERR_UNSUPPORTED, "spconv_bwd_weight: cin=%d only supported as the 3-channel stem", cin);
-  } else {
-    PCMI_REQUIRE(cin % 32 == 0 && cout % 32 == 0, PCMI_ERR_UNSUPPORTED,
-                 "spconv_bwd_weight: channels (%d, %d) must be multiples of 32", cin, cout);
-    PCMI_REQUIRE(in_ld % 4 == 0 && gout_ld % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)gout % 16 == 0,
-                 PCMI_ERR_INVALID, "spconv_bwd_weight: operands must be 16-byte aligned with ld %% 4 == 0");
-    CT = tiles_per_wg(cin / 32);
-    NT = tiles_per_wg(cout / 32);
-    wgs_per_chunk = (int64_t)(cin / (32 * CT)) * (cout / (32 * NT));
-    slots = (int64_t)wgrad_occupancy(CT, NT, a.idx_x != nullptr) * num_cu();
-  }
-  // The launch is sized WITHOUT the per-offset pair counts (pcmi_coords_plan_unet leaves them on the device): every
-  // offset gets mpk = ceil(bound / chunk) chunk slots and a workgroup whose slot lies behind the offset's last pair
-  // leaves at once (WgradArgs::mpk).  The counts, when the host has them, only steer the chunk size.
-  a.chunk = wgrad_chunk(map, M, wgrad_lo_chunk(n_in, n_out, K, M), wgs_per_chunk, slots);
-  a.mpk = map ? (int)ceil_div(wgrad_offset_bound(n_in, n_out), a.chunk) : 0;
-  const int64_t nchunks = map ? (int64_t)K * a.mpk : ceil_div(M, a.chunk);
-  const int64_t max_per_k = map ? a.mpk : nchunks;  // bound of the chunks of one offset
-  constexpr int kArriveMax = 8;  // most chunks per offset the in-kernel (last-arriver) reduction takes
-  a.mode = stem ? kSlabs : (max_per_k <= 1 ? kDirect : (max_per_k <= kArriveMax ? kArrive : kSlabs));
+  a.chunk = chunk;
+  a.mpk = mpk;
+  a.slabs = nullptr;
+  a.mode = mode;
   a.gw = gweight;
   a.accumulate = accumulate;
   a.counters = nullptr;
-  if (a.mode == kArrive) {
-    a.counters = stream_counters(st, (size_t)K * (cin / (32 * CT)) * (cout / (32 * NT)));
-    if (!a.counters) return PCMI_ERR_HIP;
-  }
-  *out = a;
-  *CT_out = CT;
-  *NT_out = NT;
-  *nchunks_out = nchunks;
-  return PCMI_OK;
+  return a;
 }
 
 // ---- grouped launches (wgrad_mfma_group_kernel) ------------------------------------------------------------------------
-// PCMI_WGRAD_GROUP=0: every layer its own launch (round 4's form; A/B).  Read per call.
-static bool wgrad_group_on() {
-  const char* e = getenv("PCMI_WGRAD_GROUP");
-  return !(e && e[0] == '0');
-}
-
 struct WgradGroupBuilder {
   WgradGroup g;
   int CT = 0, NT = 0;
@@ -946,44 +862,27 @@ void wgrad_group_drop(WgradGroupBuilder* b) {
 
 // true: the layer's weight gradient will be enqueued by the next wgrad_group_flush (its operands must stay as they are
 // until then); false: not a candidate (the caller launches it by itself -- after flushing if the order matters to it).
-// Candidates: 3^3 / stride-1 table maps in "direct" mode (every offset one chunk: the coarse levels), accumulating,
-// 32-multiples of channels, 32-bit addressable operands, not taken by the split-precision tile kernel, and the tile
-// shape of the layers already collected.
+// Candidates: the layers whose plan is groupable (plan_wgrad) and has the tile shape of the layers already collected.
 bool wgrad_group_add(WgradGroupBuilder* b, const float* in, int64_t in_ld, int64_t n_in, int cin, const float* gout,
                      int64_t gout_ld, int64_t n_out, int cout, const pcmi_kmap_t* map, float* gweight, int accumulate,
                      hipStream_t st) {
-  if (!b || !wgrad_group_on() || !map || !in || !gout || !gweight || !accumulate) return false;
-  if (map->kernel_size != 3 || map->stride != 1 || map->K > PCMI_MAX_KERNEL_VOLUME || n_in != n_out || map->n_in != n_in) return false;
-  if (cin < 32 || cin % 32 != 0 || cout % 32 != 0 || in_ld % 4 != 0 || gout_ld % 4 != 0 || (uintptr_t)in % 16 != 0 ||
-      (uintptr_t)gout % 16 != 0)
-    return false;
-  if (n_in * in_ld * 4 > 0x7FFFFF00ll || n_out * gout_ld * 4 > 0x7FFFFF00ll) return false;
-  if (wgrad_x3t_eligible(map, n_in, n_out, cin, cout, in_ld, gout_ld)) return false;
+  (void)st;
+  if (!b || !map || !in || !gout || !gweight || cin <= 0 || cout <= 0 || map->n_in != n_in || !map->pair_in) return false;
+  if (b->g.n >= kWgradGroupMax) return false;
+  const WgradEnv env = wgrad_env();
+  if (!env.group) return false;
   const int64_t M = kmap_pairs_bound(*map);
-  if (M <= 0 || b->g.n >= kWgradGroupMax) return false;
-  WgradArgs a;
-  int CT = 1, NT = 1;
-  int64_t nchunks = 0;
-  if (wgrad_plan(in, in_ld, n_in, cin, gout, gout_ld, n_out, cout, map, 0, gweight, accumulate, M, st, &a, &CT, &NT, &nchunks) != PCMI_OK)
-    return false;
-  if (!a.idx_x) return false;
-  // In a group every offset is ONE chunk (the workgroup adds its tile straight into the flat gradient: no slabs, no
-  // arrival counters): a single launch cuts a 2700-row offset into several chunks to get enough workgroups, a group has
-  // them from its other layers.  Up to 4096 pairs per offset (the longest chunk a single launch may take, wgrad_max_chunk).
-  const int64_t bound = wgrad_offset_bound(n_in, n_out);
-  if (bound > wgrad_max_chunk()) return false;
-  a.chunk = (int)align_up((size_t)bound, 128);
-  a.mpk = 1;
-  a.mode = kDirect;
-  a.counters = nullptr;
-  nchunks = a.K;
-  if (b->g.n > 0 && (CT != b->CT || NT != b->NT)) return false;
-  a.slabs = nullptr;
-  const int64_t wgs = nchunks * (cin / (32 * CT)) * (cout / (32 * NT));
+  const WgradShape s = wgrad_shape(in, in_ld, n_in, cin, gout, gout_ld, n_out, cout, map, 0, false, accumulate, M);
+  // (what a launch refuses with an error is no candidate here, and no error: it is not planned)
+  if (cin % 32 != 0 || cout % 32 != 0 || !s.aligned) return false;
+  WgradPlan p;
+  if (plan_wgrad_family(env, s, &p) != PCMI_OK || !p.groupable) return false;
+  if (b->g.n > 0 && (p.tile_c != b->CT || p.tile_n != b->NT)) return false;
+  const int64_t wgs = (int64_t)map->K * p.grid_y * p.grid_z;  // one chunk per offset
   if ((int64_t)b->g.first[b->g.n] + wgs > 0x3FFFFFFF) return false;
-  b->CT = CT;
-  b->NT = NT;
-  b->g.job[b->g.n] = a;
+  b->CT = p.tile_c;
+  b->NT = p.tile_n;
+  b->g.job[b->g.n] = wgrad_args(in, in_ld, cin, gout, gout_ld, cout, map, 0, gweight, accumulate, M, p.group_chunk, 1, kDirect);
   b->g.first[b->g.n + 1] = b->g.first[b->g.n] + (int)wgs;
   ++b->g.n;
   return true;
@@ -1015,6 +914,7 @@ int wgrad_group_flush(WgradGroupBuilder* b, hipStream_t st) {
   return rc;
 }
 
+// Validates, plans (plan_wgrad), checks the workspace against the plan and only then enqueues: a refused call writes nothing.
 int spconv_backward_weight_m32(const float* in, int64_t in_ld, int64_t n_in, int cin, const float* gout,
                                int64_t gout_ld, int64_t n_out, int cout, const pcmi_kmap_t* map, int transpose,
                                float* gweight, float* gbias, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -1029,78 +929,66 @@ int spconv_backward_weight_m32(const float* in, int64_t in_ld, int64_t n_in, int
     PCMI_REQUIRE(n_in == n_out, PCMI_ERR_INVALID, "spconv_bwd_weight: dense path needs n_in == n_out");
     M = n_in;
   }
+  WgradPlan p;
+  {
+    const int rc = plan_wgrad(wgrad_env(), wgrad_shape(in, in_ld, n_in, cin, gout, gout_ld, n_out, cout, map, transpose, gbias != nullptr,
+                                                       accumulate, M), &p);
+    if (rc) return rc;
+  }
   const int64_t per_k = (int64_t)cin * cout;
-  if (M == 0) {
+  if (p.kernel == PCMI_WGRAD_KERNEL_NONE) {
     if (!accumulate) {
       PCMI_HIP_CHECK(hipMemsetAsync(gweight, 0, sizeof(float) * K * per_k, st));
       if (gbias) PCMI_HIP_CHECK(hipMemsetAsync(gbias, 0, sizeof(float) * cout, st));
     }
     return PCMI_OK;
   }
-  if (!transpose && !gbias && wgrad_x3t_eligible(map, n_in, n_out, cin, cout, in_ld, gout_ld) && in_ld % 4 == 0 &&
-      gout_ld % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)gout % 16 == 0)
-    return wgrad_x3t_run(in, in_ld, gout, gout_ld, n_out, cin, cout, map, gweight, accumulate, ws, ws_bytes, st);
-  // the stem's gradient on the matrix cores; the shapes it refuses take the pair-list form (stem_wgrad_kernel, below)
-  if (cin == 3 && K == 27 && map && map->nbr && !transpose && map->stride == 1 && n_in == n_out && cout % 32 == 0 && !gbias) {
-    const int64_t n_blocks = ceil_div(n_out, 64);
-    const int n_wg = (int)std::min<int64_t>(kStemSlabs, n_blocks);
-    PCMI_REQUIRE(ws && ws_bytes >= (size_t)n_wg * K * per_k * sizeof(float), PCMI_ERR_WORKSPACE,
-                 "spconv_bwd_weight (stem): workspace %zu < %zu bytes", ws_bytes, (size_t)n_wg * K * per_k * sizeof(float));
-    stem_wgrad_mfma_kernel<3, 27><<<dim3((unsigned)n_wg, (unsigned)(cout / 32)), 256, 0, st>>>(in, in_ld, gout, gout_ld, map->nbr, n_out,
-                                                                                            cout, n_blocks, (float*)ws);
-    PCMI_LAUNCH_CHECK();
-    stem_slab_reduce_kernel<<<(unsigned)ceil_div(K * per_k, 8), 256, 0, st>>>((const float*)ws, n_wg, K * per_k, gweight, accumulate);
-    PCMI_LAUNCH_CHECK();
-    return PCMI_OK;
+  PCMI_REQUIRE(ws && ws_bytes >= p.ws_bytes, PCMI_ERR_WORKSPACE, "spconv_bwd_weight: workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
+  switch (p.kernel) {
+    case PCMI_WGRAD_KERNEL_X3P:
+    case PCMI_WGRAD_KERNEL_X3T: return wgrad_x3t_run(in, in_ld, gout, gout_ld, n_out, cin, cout, map, p, gweight, accumulate, ws, st);
+    case PCMI_WGRAD_KERNEL_STEM_MFMA: {
+      stem_wgrad_mfma_kernel<3, 27><<<dim3((unsigned)p.stem_wgs, (unsigned)p.grid_z), 256, 0, st>>>(
+          in, in_ld, gout, gout_ld, map->nbr, n_out, cout, ceil_div(n_out, 64), (float*)ws);
+      PCMI_LAUNCH_CHECK();
+      stem_slab_reduce_kernel<<<(unsigned)ceil_div(K * per_k, 8), 256, 0, st>>>((const float*)ws, p.stem_wgs, K * per_k, gweight, accumulate);
+      PCMI_LAUNCH_CHECK();
+      return PCMI_OK;
+    }
+    default: break;  // the pair-list kernels, below
   }
-  WgradArgs a;
-  int CT = 1, NT = 1;
-  int64_t nchunks = 0;
-  const bool stem = cin < 8;
-  {
-    const int rc = wgrad_plan(in, in_ld, n_in, cin, gout, gout_ld, n_out, cout, map, transpose, gweight, accumulate, M, st, &a, &CT,
-                              &NT, &nchunks);
-    if (rc) return rc;
-  }
-  // (checked before anything is enqueued: a refused call writes nothing; the column sums start at the next 256 bytes)
-  const size_t slab_bytes = a.mode == kDirect ? 0 : (size_t)nchunks * per_k * sizeof(float);
-  const size_t bias_bytes = gbias ? (size_t)1024 * cout * sizeof(float) : 0;
-  const size_t ws_need = gbias ? align_up(slab_bytes, 256) + bias_bytes : slab_bytes;
-  PCMI_REQUIRE(ws && ws_bytes >= ws_need, PCMI_ERR_WORKSPACE, "spconv_bwd_weight: workspace %zu < %zu bytes", ws_bytes, ws_need);
-  if (a.mode != kSlabs && map && !accumulate)  // an offset without pairs gets no workgroup: its slice must read zero
-    PCMI_HIP_CHECK(hipMemsetAsync(gweight, 0, sizeof(float) * K * per_k, st));
+  WgradArgs a = wgrad_args(in, in_ld, cin, gout, gout_ld, cout, map, transpose, gweight, accumulate, M, p.chunk, p.mpk, p.mode);
   a.slabs = (float*)ws;
-  const int64_t grid_x = nchunks;
-  if (stem) {
-    stem_wgrad_kernel<3><<<dim3((unsigned)nchunks), 256, 0, st>>>(a);
+  if (p.counters) {
+    a.counters = stream_counters(st, p.counters);
+    if (!a.counters) return PCMI_ERR_HIP;
+  }
+  if (p.mode != kSlabs && map && !accumulate)  // an offset without pairs gets no workgroup: its slice must read zero
+    PCMI_HIP_CHECK(hipMemsetAsync(gweight, 0, sizeof(float) * K * per_k, st));
+  if (p.kernel == PCMI_WGRAD_KERNEL_STEM) {
+    stem_wgrad_kernel<3><<<dim3((unsigned)p.nchunks), 256, 0, st>>>(a);
     PCMI_LAUNCH_CHECK();
   } else {
-    dim3 grid((unsigned)grid_x, (unsigned)(cin / (32 * CT)), (unsigned)(cout / (32 * NT)));
-    const bool buf_ok = [] {  // PCMI_WGRAD_BUF=0: always the 64-bit-address form (A/B, parity of the two; read per call)
-      const char* e = getenv("PCMI_WGRAD_BUF");
-      return !(e && e[0] == '0');
-    }();
-    const bool buf = buf_ok && n_in * in_ld * 4 <= 0x7FFFFF00ll && n_out * gout_ld * 4 <= 0x7FFFFF00ll;
+    const dim3 grid((unsigned)p.nchunks, (unsigned)p.grid_y, (unsigned)p.grid_z);
     int rc;
-    switch (CT) {
-      case 1: rc = launch_wg_nt<1>(NT, a, grid, buf, st); break;
-      case 2: rc = launch_wg_nt<2>(NT, a, grid, buf, st); break;
-      default: rc = launch_wg_nt<3>(NT, a, grid, buf, st); break;
+    switch (p.tile_c) {
+      case 1: rc = launch_wg_nt<1>(p.tile_n, a, grid, p.buf, st); break;
+      case 2: rc = launch_wg_nt<2>(p.tile_n, a, grid, p.buf, st); break;
+      default: rc = launch_wg_nt<3>(p.tile_n, a, grid, p.buf, st); break;
     }
     if (rc) return rc;
   }
-  if (a.mode != kSlabs) {
-    // gW is complete when the launch is
-  } else if (nchunks > 16 * (int64_t)K)
+  if (p.reduce_lanes == 8)
     wgrad_reduce_kernel<8><<<dim3((unsigned)ceil_div(per_k, 32), (unsigned)K), 256, 0, st>>>(a.slabs, a.offs, a.mpk, M, a.chunk,
                                                                                           per_k, gweight, accumulate);
-  else
+  else if (p.reduce_lanes == 1)
     wgrad_reduce_kernel<1><<<dim3((unsigned)ceil_div(per_k, 256), (unsigned)K), 256, 0, st>>>(a.slabs, a.offs, a.mpk, M, a.chunk,
                                                                                            per_k, gweight, accumulate);
+  // (else gW is complete when the launch is)
   PCMI_LAUNCH_CHECK();
   if (gbias) {
-    float* part = (float*)((char*)ws + align_up(slab_bytes, 256));
-    const int nblocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ceil_div(n_out, 64)));
+    float* part = (float*)((char*)ws + p.colsum_offset);
+    const int nblocks = (int)std::min<int64_t>(kColsumBlocks, std::max<int64_t>(1, ceil_div(n_out, 64)));
     const int rows_per_block = (int)ceil_div(n_out, nblocks);
     colsum_partial_kernel<<<nblocks, 256, 0, st>>>(gout, gout_ld, n_out, cout, rows_per_block, part);
     PCMI_LAUNCH_CHECK();
@@ -1112,14 +1000,72 @@ int spconv_backward_weight_m32(const float* in, int64_t in_ld, int64_t n_in, int
 
 }  // namespace pcmi
 
-extern "C" {
+using namespace pcmi;
 
+extern "C" {
 
 int pcmi_spconv_bwd_weight(const float* in, int64_t in_ld, int64_t n_in, int cin, const float* gout,
                            int64_t gout_ld, int64_t n_out, int cout, const pcmi_kmap_t* map, int transpose,
                            float* gweight, float* gbias, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
   return spconv_backward_weight(in, in_ld, n_in, cin, gout, gout_ld, n_out, cout, map, transpose, gweight, gbias, 0, ws,
                                 ws_bytes, as_stream(stream));
+}
+
+int pcmi_spconv_wgrad_plan(int64_t n_in, int64_t n_out, int cin, int cout, int K, int kernel_size, int stride, int map_tables,
+                           int transpose, int gbias, int accumulate, int64_t x_bytes, int64_t g_bytes, int aligned,
+                           const int64_t* counts_host, int slots_per_cu, int* kernel, int* tile_c, int* tile_n, int* chunk,
+                           int* slots_per_offset, int* mode, int* address_bits, int* row_blocks, int* groupable, size_t* ws_bytes) {
+  const bool has_map = kernel_size != 0;
+  PCMI_REQUIRE(n_in >= 0 && n_out >= 0 && cin > 0 && cout > 0 && K >= 1 && K <= PCMI_MAX_KERNEL_VOLUME && x_bytes >= 0 && g_bytes >= 0 &&
+                   slots_per_cu >= 0 && (has_map ? ((kernel_size == 3 && stride == 1) || (kernel_size == 2 && stride == 2))
+                                                 : (K == 1 && n_in == n_out && !transpose && !counts_host && !map_tables)),
+               PCMI_ERR_INVALID, "spconv_wgrad_plan: bad shape (%lld -> %lld rows, %d -> %d, K %d, kernel size %d, stride %d)",
+               (long long)n_in, (long long)n_out, cin, cout, K, kernel_size, stride);
+  WgradShape s = {};
+  s.n_in = n_in;
+  s.n_out = n_out;
+  s.cin = cin;
+  s.cout = cout;
+  s.K = K;
+  s.has_map = has_map;
+  s.kernel_size = kernel_size;
+  s.stride = stride;
+  s.has_nbr = (map_tables & PCMI_WGRAD_MAP_NBR) != 0;
+  s.has_perm = (map_tables & PCMI_WGRAD_MAP_PERM) != 0;
+  s.transpose = transpose != 0;
+  s.gbias = gbias != 0;
+  s.accumulate = accumulate != 0;
+  s.x_bytes = x_bytes;
+  s.g_bytes = g_bytes;
+  s.aligned = aligned != 0;
+  s.counts = counts_host;
+  if (!has_map) {
+    s.M = n_in;
+  } else if (counts_host) {
+    s.M = counts_host[K] - counts_host[0];
+  } else {  // kmap_pairs_bound of a map whose counts have not arrived
+    const int64_t map_in = transpose ? n_out : n_in, map_out = transpose ? n_in : n_out;
+    s.M = stride == 1 ? (int64_t)K * map_out : map_in;
+  }
+  s.terms = conv_terms();
+  s.slots_per_cu = slots_per_cu;
+  if (slots_per_cu == 0 && s.M != 0 && cin % 32 == 0 && cout % 32 == 0)
+    s.slots_per_cu = wgrad_occupancy(wgrad_pair_tiles(cin), wgrad_pair_tiles(cout), has_map);
+  WgradPlan p;
+  const int rc = plan_wgrad(wgrad_env(), s, &p);
+  if (rc) return rc;
+  const bool pairs = p.kernel == PCMI_WGRAD_KERNEL_PAIRS, tiled = p.kernel == PCMI_WGRAD_KERNEL_X3P || p.kernel == PCMI_WGRAD_KERNEL_X3T;
+  if (kernel) *kernel = p.kernel;
+  if (tile_c) *tile_c = p.tile_c;
+  if (tile_n) *tile_n = p.tile_n;
+  if (chunk) *chunk = p.chunk;
+  if (slots_per_offset) *slots_per_offset = p.mpk;
+  if (mode) *mode = p.mode;
+  if (address_bits) *address_bits = pairs ? (p.buf ? 32 : 64) : 0;
+  if (row_blocks) *row_blocks = tiled ? p.RB : p.stem_wgs;
+  if (groupable) *groupable = p.groupable ? 1 : 0;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  return PCMI_OK;
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 // one stages while the other multiplies.
 // wgrad_x3t_kernel takes the term count as a template argument: TERMS = 3 is the above; TERMS = 1 (the bf16 conv
 // precision mode, pcmi_set_conv_precision) stages h alone -- a third of the LDS image and of the cell writes, no residual
-// VALU work -- and issues ONE MFMA per tile.  The one-term mode always takes that kernel (wgrad_x3t_run says why).
+// VALU work -- and issues ONE MFMA per tile.  The one-term mode always takes that kernel (plan_wgrad says why).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "spconv_wgrad_plan.h"
 #include "x3_split.h"
 
 namespace pcmi {
@@ -563,116 +564,41 @@ __global__ __launch_bounds__(256) void wgrad_slab_sum_kernel(const float* __rest
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-constexpr int kWgradTKG = 4;     // offsets whose accumulators a workgroup holds
-constexpr int kWgradTMaxRB = 128;
-
-static int wgrad_x3t_tw(int c) { return c % 96 == 0 ? 3 : (c % 64 == 0 ? 2 : 0); }  // 16-wide tiles per wave and axis
-
-// PCMI_WGRAD_X3T: minimum number of rows for the tile-stationary split-precision kernel (0 = never; 1 = every size).
-// Read per call: the parity test runs both kernels in one process.
-// Measured on the bench batch, ms per launch stand-alone, pair-list fp32 kernel -> this one (profiles/r03b_kbench_*):
-//   40k rows   96->96 0.205 -> 0.139, 128->96 0.253 -> 0.223
-//   175k rows  96->96 0.509 -> 0.514, 128->96 0.732 -> 0.901   (both kernels are bound by the gathered-row traffic there:
-//              2.3 GB at 4.4 TB/s against 1.8 GB at 3.4 TB/s; this one re-stages the G tile once per offset group)
-//   9.9k rows  64->64 0.026 -> 0.048, 128->128 0.073 -> 0.098, 192->128 0.160 -> 0.121
-// and in the training step, where it shares the chip with the backward chain (profiles/r03i_bench_ab_x3t_window.txt, 3
-// processes each): rows in [16384, 100000] 248.7-250.3 pairs/s, >= 8192 251.4-252.5, >= 16384 **252.0-252.9** -- at 175k
-// rows it is no faster alone but asks a quarter less of the memory system, which the chain's kernels get.
-// Round 4, with the producer / consumer form (profiles/r04n_*, 2 processes each): >= 100000 rows 256.0, >= 16384 257.9,
-// >= 8192 **258.5**, >= 2048 255.7 pairs/s.
-static int64_t wgrad_x3t_min_rows() {
-  const char* e = getenv("PCMI_WGRAD_X3T");
-  return e ? (int64_t)atoll(e) : (int64_t)8192;
-}
-
-// PCMI_WGRAD_X3T_DENSE=0: the 1x1 convolutions (no map: K = 1, identity table) stay on the pair-list kernel (A/B)
-static bool wgrad_x3t_dense_on() {
-  const char* e = getenv("PCMI_WGRAD_X3T_DENSE");
-  return !(e && e[0] == '0');
-}
-
-// map == nullptr: a 1x1 convolution, gW = X^T G over all rows -- the same kernel with K = 1 and the identity table
-// (round 5: the level-1 128 -> 96 downsample gradient took 350 us in the step on the fp32 pair-list kernel, 12 TFLOP/s).
-bool wgrad_x3t_eligible(const pcmi_kmap_t* map, int64_t n_in, int64_t n_out, int cin, int cout, int64_t in_ld, int64_t gout_ld) {
-  const int64_t mr = wgrad_x3t_min_rows();
-  const bool shape = map ? (map->kernel_size == 3 && map->stride == 1) : wgrad_x3t_dense_on();
-  return shape && mr > 0 && n_out >= mr && n_in == n_out && cin >= 64 && cout >= 64 &&
-         wgrad_x3t_tw(cin) > 0 && wgrad_x3t_tw(cout) > 0 && n_in * in_ld * 4 <= 0x7FFFFF00ll && n_out * gout_ld * 4 <= 0x7FFFFF00ll;
-}
-
-// PCMI_WGRAD_X3P: 1 = the producer / consumer form (wgrad_x3p_kernel: 8 waves, one workgroup per CU; default), 0 = one role
-// (wgrad_x3t_kernel); read per call
-static int wgrad_x3p_mode() {
-  const char* e = getenv("PCMI_WGRAD_X3P");
-  return e ? (atoi(e) != 0 ? 1 : 0) : 1;
-}
-
-static int wgrad_x3t_rb(int64_t n_rows, int gy, int gz, int per_cu = 2, int K = PCMI_MAX_KERNEL_VOLUME, int kg = kWgradTKG) {
-  const int NG = (K + kg - 1) / kg;
-  const int64_t n_tiles = ceil_div(n_rows, 64);
-  // `per_cu` resident workgroups per CU (wgrad_x3t_kernel: two -- one per CU: 238.6 against 240 pairs/s in the step; the
-  // producer / consumer form is one 8-wave workgroup per CU); one round of them, at least 4 tiles per workgroup, a
-  // multiple of 8 row blocks
-  int64_t rb = (int64_t)per_cu * num_cu() / ((int64_t)NG * gy * gz);
-  rb = std::min<int64_t>(rb, n_tiles / 4);
-  rb = std::max<int64_t>(8, std::min<int64_t>(kWgradTMaxRB, rb / 8 * 8));
-  return (int)rb;
-}
-
-size_t wgrad_x3t_workspace(int64_t n_rows, int cin, int cout) {
-  const int MTW = wgrad_x3t_tw(cin), NTW = wgrad_x3t_tw(cout);
-  const int64_t mr = wgrad_x3t_min_rows();
-  if (MTW == 0 || NTW == 0 || mr <= 0 || n_rows < mr || cin < 64 || cout < 64) return 0;
-  return (size_t)PCMI_MAX_KERNEL_VOLUME * wgrad_x3t_rb(n_rows, cin / (32 * MTW), cout / (32 * NTW)) * cin * cout * sizeof(float);
-}
-
+// Which launches take these kernels, with what tile shape and how many row blocks: plan_wgrad (spconv_wgrad_plan.h).
+// (the plan names the kernel; its terms only select the instance of the one-role kernel)
 template <int MTW, int NTW>
-static void launch_x3t(const WgradTArgs& a, dim3 grid, int mode, int terms, hipStream_t st) {
-  if (terms == 1) wgrad_x3t_kernel<MTW, NTW, kWgradTKG, 1><<<grid, 256, 0, st>>>(a);  // (one role: see wgrad_x3t_run)
-  else if (mode == 1) wgrad_x3p_kernel<MTW, NTW, kWgradTKG><<<grid, 512, 0, st>>>(a);
+static void launch_x3t(const WgradTArgs& a, dim3 grid, const WgradPlan& p, hipStream_t st) {
+  const bool one_role = p.kernel == PCMI_WGRAD_KERNEL_X3T;
+  if (one_role && p.terms == 1) wgrad_x3t_kernel<MTW, NTW, kWgradTKG, 1><<<grid, 256, 0, st>>>(a);
+  else if (!one_role) wgrad_x3p_kernel<MTW, NTW, kWgradTKG><<<grid, 512, 0, st>>>(a);
   else wgrad_x3t_kernel<MTW, NTW, kWgradTKG, 3><<<grid, 256, 0, st>>>(a);
 }
 
+// ws: the plan's slab_bytes (checked by the caller)
 int wgrad_x3t_run(const float* in, int64_t in_ld, const float* gout, int64_t gout_ld, int64_t n_rows, int cin, int cout,
-                  const pcmi_kmap_t* map, float* gweight, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-  const int MTW = wgrad_x3t_tw(cin), NTW = wgrad_x3t_tw(cout);
-  PCMI_REQUIRE(MTW > 0 && NTW > 0 && (!map || map->K <= PCMI_MAX_KERNEL_VOLUME), PCMI_ERR_UNSUPPORTED, "wgrad x3t: channels (%d, %d)", cin, cout);
+                  const pcmi_kmap_t* map, const WgradPlan& p, float* gweight, int accumulate, void* ws, hipStream_t st) {
   WgradTArgs a;
   a.x = in;
   a.x_ld = in_ld;
   a.g = gout;
   a.g_ld = gout_ld;
-  a.nbr = !map ? nullptr : ((map->perm && map->nbr_perm) ? map->nbr_perm : map->nbr);
-  a.perm = (map && map->perm && map->nbr_perm) ? map->perm : nullptr;
+  a.nbr = !map ? nullptr : (p.sorted_order ? map->nbr_perm : map->nbr);
+  a.perm = p.sorted_order ? map->perm : nullptr;
   a.n_rows = n_rows;
   const int K = map ? map->K : 1;
   a.K = K;
   a.C = cin;
   a.N = cout;
-  const int gy = cin / (32 * MTW), gz = cout / (32 * NTW);
-  const int terms = conv_terms();  // the calling thread's conv precision mode
-  // The one-term mode takes the one-role kernel: wgrad_x3p_kernel<..., 1> compiles with its producers' register sets on
-  // the stack (.private_segment_fixed_size 480 B, scratch loads and stores; the three-term form has none) and measured
-  // 1.03 against 0.44 ms for the three-term kernel on the level-1 96 -> 96 launch.
-  const int mode = terms == 1 ? 0 : wgrad_x3p_mode();
-  [[maybe_unused]] const bool pc = mode == 1;
-  const int kg = kWgradTKG;
-  a.NG = (K + kg - 1) / kg;
-  a.RB = wgrad_x3t_rb(n_rows, gy, gz, mode >= 1 ? 1 : 2, K, kg);
-  // (the producer / consumer form takes 8 x NG x (RB / 8) = 224 of the 256 CUs at NG = 7: with every CU used -- 36 row
-  //  blocks, 252 workgroups -- it is 11 % faster alone (0.501 against 0.560 ms) and SLOWER in the step (253.1-254.6 against
-  //  256.6-256.9 pairs/s): the CUs it leaves are where the backward chain's kernels run meanwhile; fewer row blocks lose
-  //  again -- 24: 254.6, 16: 252.7.  profiles/r04jk_wgrad_producer_consumer.txt)
-  a.tiles_per_rb = (int)ceil_div(ceil_div(n_rows, 64), a.RB);
-  const size_t need = (size_t)K * a.RB * cin * cout * sizeof(float);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "wgrad x3t: workspace %zu < %zu bytes", ws_bytes, need);
+  a.NG = p.NG;
+  a.RB = p.RB;
+  a.tiles_per_rb = p.tiles_per_rb;
   a.slabs = (float*)ws;
-  const dim3 grid((unsigned)(a.RB * a.NG), (unsigned)gy, (unsigned)gz);
-  switch (MTW * 4 + NTW) {
-    case 3 * 4 + 3: launch_x3t<3, 3>(a, grid, mode, terms, st); break;
-    case 3 * 4 + 2: launch_x3t<3, 2>(a, grid, mode, terms, st); break;
-    case 2 * 4 + 3: launch_x3t<2, 3>(a, grid, mode, terms, st); break;
-    default: launch_x3t<2, 2>(a, grid, mode, terms, st); break;
+  const dim3 grid((unsigned)(a.RB * a.NG), (unsigned)p.grid_y, (unsigned)p.grid_z);
+  switch (p.tile_c * 4 + p.tile_n) {
+    case 3 * 4 + 3: launch_x3t<3, 3>(a, grid, p, st); break;
+    case 3 * 4 + 2: launch_x3t<3, 2>(a, grid, p, st); break;
+    case 2 * 4 + 3: launch_x3t<2, 3>(a, grid, p, st); break;
+    default: launch_x3t<2, 2>(a, grid, p, st); break;
   }
   PCMI_LAUNCH_CHECK();
   const int64_t per_k = (int64_t)cin * cout;

@@ -27,6 +27,7 @@ import torch
 import geometry_cases as gc
 from c_contract import DEV
 from test_gpu_c_contract import _Maps, _ok, _stream, _vp, rel_err
+from test_gpu_wgrad_plan import _planned
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +68,7 @@ def _tw(c):
 
 
 def _row_blocks(n_rows, cin, cout, per_cu, K):
-  """wgrad_x3t_rb of csrc/spconv_wgrad_x3.hip restated."""
+  """wgrad_x3t_rb of csrc/spconv_wgrad_plan.h restated; _check holds pcmi_spconv_wgrad_plan to it."""
   gy, gz = cin // (32 * _tw(cin)), cout // (32 * _tw(cout))
   n_cu = torch.cuda.get_device_properties(DEV).multi_processor_count
   rb = per_cu * n_cu // (-(-K // 4) * gy * gz)
@@ -109,6 +110,11 @@ def _check(lib, monkeypatch, x, g, m, K, g64_fn, what):
   assert not torch.equal(pair, p1) and not torch.equal(pair, t1), what + ": PCMI_WGRAD_X3T did not switch kernels"
   assert torch.equal(_bits(p1), _bits(p2)), what + ": two runs of the producer / consumer form differ"
   rb_p, rb_t = _row_blocks(n, cin, cout, 1, K), _row_blocks(n, cin, cout, 2, K)
+  for x3p, kernel, rb in (("1", 1, rb_p), ("0", 2, rb_t)):  # PCMI_WGRAD_KERNEL_X3P / _X3T: the library plans the same row blocks
+    monkeypatch.setenv("PCMI_WGRAD_X3T", "1")
+    monkeypatch.setenv("PCMI_WGRAD_X3P", x3p)
+    plan = _planned(lib, m, n, n, cin, cout, False, cin, cout)
+    assert (plan[0], plan[7]) == (kernel, rb), "%s: PCMI_WGRAD_X3P=%s planned %s, restated %d row blocks" % (what, x3p, plan, rb)
   print("%s: row blocks %d (producer / consumer) and %d (one role)" % (what, rb_p, rb_t))
   if rb_p == rb_t:
     assert torch.equal(_bits(p1), _bits(t1)), what + ": the two forms differ at the same row-block count (%d)" % rb_p
