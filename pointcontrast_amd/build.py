@@ -41,7 +41,8 @@ def _digest(paths):
 
 def _headers():
   return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "spconv_args.h"), os.path.join(CSRC, "spconv_plan.h"), os.path.join(CSRC, "spconv_wgrad_plan.h"),
-          os.path.join(CSRC, "x3_split.h"), os.path.join(HERE, "..", "include", "pcmi.h")]
+          os.path.join(CSRC, "x3_split.h"), os.path.join(CSRC, "exact.h"), os.path.join(CSRC, "cellgrid.h"), os.path.join(CSRC, "blockscan.h"),
+          os.path.join(HERE, "..", "include", "pcmi.h")]
 
 
 def sources_digest():

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "blockscan.h"
 #include "internal.h"
 
 namespace pcmi {
@@ -1071,36 +1072,21 @@ __global__ __launch_bounds__(kSegBlock) void seg_hist_kernel(const int32_t* __re
   for (int b = threadIdx.x; b < kSegBins; b += kSegBlock) cnt[(int64_t)b * nblk + blockIdx.x] = hist[b];
 }
 
-// inclusive scan of one value per thread over a kSegBins-thread workgroup
-__device__ inline int32_t seg_block_scan(int32_t v, int32_t* s) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kSegBins; d <<= 1) {
-    const int32_t add = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += add;
-    __syncthreads();
-  }
-  const int32_t r = s[t];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(kSegBins) void seg_bins_kernel(const int32_t* __restrict__ base, int64_t n, int64_t nblk,
                                                             int32_t* __restrict__ inst_of_bin, int32_t* __restrict__ offs,
                                                             int32_t* __restrict__ chunk_offs, int32_t* __restrict__ inst_batch,
                                                             int64_t* __restrict__ totals) {
-  __shared__ int32_t s[kSegBins];
+  __shared__ int s_wave[kSegBins / 64];
   const int b = threadIdx.x;
   const int32_t start = n > 0 ? base[(int64_t)b * nblk] : 0;
   const int32_t end = b + 1 < kSegBins ? (n > 0 ? base[(int64_t)(b + 1) * nblk] : 0) : (int32_t)n;
   const int32_t rows = end - start;
   const int32_t flag = rows > 0 ? 1 : 0;
-  const int32_t inst_incl = seg_block_scan(flag, s);
+  int total;
+  const int32_t inst_incl = block_scan_add<kSegBins / 64>(flag, s_wave, &total);
   const int32_t inst = inst_incl - flag;
   const int32_t chunks = flag ? (rows + PCMI_SEGMENT_CHUNK - 1) / PCMI_SEGMENT_CHUNK : 0;
-  const int32_t chunk_incl = seg_block_scan(chunks, s);
+  const int32_t chunk_incl = block_scan_add<kSegBins / 64>(chunks, s_wave, &total);
   inst_of_bin[b] = flag ? inst : -1;
   if (flag) {
     offs[inst] = start;

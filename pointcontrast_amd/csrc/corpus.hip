@@ -19,57 +19,19 @@
 
 #include <algorithm>
 
+#include "cellgrid.h"
 #include "common.h"
+#include "exact.h"
 #include "internal.h"
 
-// hipcc contracts a * b + c into an FMA by default, and __dmul_rn / __dadd_rn are plain operators in a system header
-// where this file's pragma does not reach: the operators are written here, under the pragma, so that every product
-// and sum is rounded on its own
 #pragma clang fp contract(off)
 
 namespace pcmi {
 namespace corpus {
 
-constexpr int kBias = 1 << 20;  // |cell index| < 2^20 per axis (the loader's range, csrc/loader.hip)
 constexpr int kThreads = 256;
 constexpr int kMinChunk = 4096;  // points per workgroup of the min-bound partials
 
-__device__ inline double mul_rn(double a, double b) { return a * b; }
-__device__ inline double add_rn(double a, double b) { return a + b; }
-__device__ inline double div_rn(double a, double b) { return a / b; }
-
-// floor(v) as a cell index, or false when it is not strictly inside +-2^20 (NaN included)
-__device__ inline bool cell_of(double v, int64_t* c) {
-  const double f = floor(v);
-  if (!(f > -(double)kBias && f < (double)kBias)) return false;
-  *c = (int64_t)f;
-  return true;
-}
-__device__ inline uint64_t cell_key(int64_t x, int64_t y, int64_t z) {
-  return ((uint64_t)(x + kBias) << 42) | ((uint64_t)(y + kBias) << 21) | (uint64_t)(z + kBias);
-}
-__device__ inline bool cell_ok(int64_t x, int64_t y, int64_t z) {
-  return x > -kBias && x < kBias && y > -kBias && y < kBias && z > -kBias && z < kBias;
-}
-// open addressing, linear probing; the tables are sized >= 2x their keys, so a probe always meets an empty slot
-__device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t base, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {
-    const unsigned long long prev =
-        atomicCAS((unsigned long long*)&keys[base + slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
-    if (prev == kEmptyKey || prev == key) return base + slot;
-    slot = (slot + 1) & mask;
-  }
-}
-__device__ inline int64_t find_slot(const uint64_t* keys, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {
-    const uint64_t k = keys[slot];
-    if (k == key) return slot;
-    if (k == kEmptyKey) return -1;
-    slot = (slot + 1) & mask;
-  }
-}
 __host__ __device__ inline uint32_t pow2_at_least(int64_t n) {
   uint32_t c = 64;
   while ((int64_t)c < n) c <<= 1;
@@ -101,16 +63,12 @@ __global__ void bp_points_kernel(const uint16_t* __restrict__ depth, int64_t n_f
   const double d = div_rn((double)raw, shift);
   const double X = add_rn(div_rn(mul_rn(add_rn(u, -K.cx), d), K.fx), K.bx);
   const double Y = add_rn(div_rn(mul_rn(add_rn(v, -K.cy), d), K.fy), K.by);
-  const double* P = poses + 16 * f;
+  const double c[3] = {X, Y, d};
+  double w[3];
+  rigid_apply(poses + 16 * f, 4, c, w);
   double* o = points + 3 * (int64_t)pos[k];
-  bool nan = false;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double w = add_rn(add_rn(add_rn(mul_rn(X, P[4 * r]), mul_rn(Y, P[4 * r + 1])), mul_rn(d, P[4 * r + 2])), P[4 * r + 3]);
-    nan |= isnan(w);
-    o[r] = w;
-  }
-  if (nan) atomicAdd(&nan_count[f], 1);
+  o[0] = w[0], o[1] = w[1], o[2] = w[2];
+  if (isnan(w[0]) || isnan(w[1]) || isnan(w[2])) atomicAdd(&nan_count[f], 1);
 }
 
 // offsets[f] = first output row of frame f (f < F), offsets[F] = total
@@ -150,10 +108,9 @@ __global__ __launch_bounds__(kThreads) void bp_color_kernel(const uint16_t* __re
     const double d = div_rn((double)raw, shift);
     const double X = add_rn(div_rn(mul_rn(add_rn(u, -K.cx), d), K.fx), K.bx);
     const double Y = add_rn(div_rn(mul_rn(add_rn(v, -K.cy), d), K.fy), K.by);
+    const double p[3] = {X, Y, d};
     double q[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      q[r] = add_rn(add_rn(add_rn(mul_rn(X, cam.M[4 * r]), mul_rn(Y, cam.M[4 * r + 1])), mul_rn(d, cam.M[4 * r + 2])), cam.M[4 * r + 3]);
+    rigid_apply(cam.M, 4, p, q);
     const double uc = add_rn(div_rn(mul_rn(cam.fx, q[0]), q[2]), cam.cx);
     const double vc = add_rn(div_rn(mul_rn(cam.fy, q[1]), q[2]), cam.cy);
     const double px = floor(add_rn(uc, 0.5)), py = floor(add_rn(vc, 0.5));
@@ -240,16 +197,14 @@ __global__ void vc_insert_kernel(const double* __restrict__ pts, const int64_t* 
   const int64_t f = blockIdx.y;
   const int64_t b = offsets[f], e = offsets[f + 1];
   for (int64_t i = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
+    const double d[3] = {add_rn(pts[3 * i], -origin[3 * f]), add_rn(pts[3 * i + 1], -origin[3 * f + 1]), add_rn(pts[3 * i + 2], -origin[3 * f + 2])};
     int64_t c[3];
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) ok &= cell_of(div_rn(add_rn(pts[3 * i + a], -origin[3 * f + a]), voxel), &c[a]);
-    if (!ok) {
+    if (!cells_of(d, voxel, c)) {
       atomicAdd(err, 1);
       slot_of[i] = 0xffffffffu;
       continue;
     }
-    const uint32_t slot = claim_slot(keys, tbase[f], tmask[f], cell_key(c[0], c[1], c[2]));
+    const uint32_t slot = claim_slot(keys, tbase[f], tmask[f] + 1, cell_key(c[0], c[1], c[2]));
     atomicMin(&first[slot], (int32_t)i);
     slot_of[i] = slot;
   }
@@ -329,15 +284,12 @@ __global__ void ov_insert_kernel(const double* __restrict__ pts, const int64_t* 
   for (int64_t i = b + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < e; i += (int64_t)gridDim.x * blockDim.x) {
     frame_of[i] = (int32_t)f;
     int64_t c[3];
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) ok &= cell_of(div_rn(pts[3 * i + a], radius), &c[a]);
-    if (!ok) {
+    if (!cells_of(pts + 3 * i, radius, c)) {
       atomicAdd(err, 1);
       next[i] = -1;
       continue;
     }
-    const uint32_t slot = claim_slot(keys, 0, mask, cell_key(c[0], c[1], c[2]));
+    const uint32_t slot = claim_slot(keys, 0, mask + 1, cell_key(c[0], c[1], c[2]));
     next[i] = atomicExch(&head[slot], (int32_t)i);
   }
 }
@@ -363,19 +315,17 @@ __global__ void __launch_bounds__(kThreads) ov_count_kernel(const double* __rest
     const double r2 = mul_rn(radius, radius);
     int64_t c[3];
     // a query outside the grid's range met no cell: ov_insert_kernel counted it as an error already
-    if (cell_of(div_rn(q[0], radius), &c[0]) && cell_of(div_rn(q[1], radius), &c[1]) && cell_of(div_rn(q[2], radius), &c[2])) {
+    if (cells_of(q, radius, c)) {
       for (int dz = -1; dz <= 1; ++dz)
         for (int dy = -1; dy <= 1; ++dy)
           for (int dx = -1; dx <= 1; ++dx) {
             if (!cell_ok(c[0] + dx, c[1] + dy, c[2] + dz)) continue;
-            const int64_t slot = find_slot(keys, mask, cell_key(c[0] + dx, c[1] + dy, c[2] + dz));
+            const int64_t slot = find_slot(keys, 0, mask + 1, cell_key(c[0] + dx, c[1] + dy, c[2] + dz));
             if (slot < 0) continue;
             for (int32_t p = head[slot]; p >= 0; p = next[p]) {
               const int64_t bit = (int64_t)frame_of[p] - t0;
               if (bit < 0 || bit >= 64 || ((bits >> bit) & 1ull)) continue;
-              const double ex = add_rn(q[0], -pts[3 * p]), ey = add_rn(q[1], -pts[3 * p + 1]), ez = add_rn(q[2], -pts[3 * p + 2]);
-              const double d2 = add_rn(add_rn(mul_rn(ex, ex), mul_rn(ey, ey)), mul_rn(ez, ez));
-              if (d2 <= r2) bits |= 1ull << bit;
+              if (dist2_rn(q, pts + 3 * (int64_t)p) <= r2) bits |= 1ull << bit;
             }
           }
     }
@@ -390,19 +340,6 @@ __global__ void __launch_bounds__(kThreads) ov_count_kernel(const double* __rest
   if (threadIdx.x < 64 && t0 + threadIdx.x < n_frames && acc[threadIdx.x] != 0)
     atomicAdd(&counts[(t0 + threadIdx.x) * n_frames + j], acc[threadIdx.x]);
 }
-
-struct Carve {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
 
 static size_t scan_bytes(int64_t n) {
   size_t b = 0;

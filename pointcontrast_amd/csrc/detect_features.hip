@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "exact.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -30,12 +31,6 @@ constexpr int kChunkThreads = 256;        // larger scenes: one workgroup per ch
 constexpr int kChunk = 8192;
 constexpr int kSceneWords = kPasses * kBins + 4;  // per scene in ws: four histograms, the minimum above, the non-finite mark
 constexpr int kThreads = 256;
-
-__device__ inline uint32_t ord32(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float unord32(uint32_t u) { return __uint_as_float((u >> 31) ? (u & 0x7fffffffu) : ~u); }
 
 struct QuantArgs {
   const float* values;

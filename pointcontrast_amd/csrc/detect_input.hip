@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "exact.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -30,12 +31,6 @@ constexpr int kMaxValid = 1024;
 constexpr int kVoxelLimit = 1 << 20;
 constexpr int64_t kMaxRows = 1ll << 29;  // pcmi_seg_quantize's limit
 constexpr double kPi = 3.141592653589793;  // numpy's np.pi
-
-__device__ inline uint32_t ord32(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float unord32(uint32_t u) { return __uint_as_float((u >> 31) ? (u & 0x7fffffffu) : ~u); }
 
 // ---- sample, flip, rotate, scale (and the stored votes of SUN RGB-D) -----------------------------------------------------------
 struct SampleArgs {

@@ -9,6 +9,7 @@
 // bit for bit.
 #include <algorithm>
 
+#include "blockscan.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -225,51 +226,6 @@ __global__ __launch_bounds__(256) void ap_claim_kernel(const float* __restrict__
   if (ap_candidate(best_iou, gt_id, d, n_gt, thr.t[t])) atomicMin(&claim[(int64_t)t * n_gt + gt_id[d]], (int32_t)d);
 }
 
-// inclusive sum over the workgroup of one int per thread (thread order); total: the sum over all threads
-__device__ __forceinline__ int block_scan_add(int v, int* s_wave /* [4] */, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  __syncthreads();  // the previous call's readers are done
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kApThreads / 64; ++w) {
-    const int x = s_wave[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  *total = all;
-  return v + before;
-}
-
-// maximum over the threads strictly AFTER this one (0 for the last: precisions are >= 0); all: over all threads
-__device__ __forceinline__ double block_rscan_max_excl(double v, double* s_wave /* [4] */, double* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_down(v, o, 64);
-    if (lane + o < 64) v = fmax(v, u);
-  }
-  const double next = __shfl_down(v, 1, 64);
-  __syncthreads();  // the previous call's readers are done
-  if (lane == 0) s_wave[wave] = v;
-  __syncthreads();
-  double after = lane < 63 ? next : 0.0, m = 0.0;
-#pragma unroll
-  for (int w = 0; w < kApThreads / 64; ++w) {
-    const double x = s_wave[w];
-    after = w > wave ? fmax(after, x) : after;
-    m = fmax(m, x);
-  }
-  *all = m;
-  return after;
-}
-
 // grid (class, threshold), one workgroup each, over the class's detections [offs[c], offs[c + 1]) in rank order.
 // Forward pass, kApChunk detections at a time with a carry (so a class may hold any number of them): tp flag = "my bid won",
 // inclusive count of true positives -> tp_cum (workspace), rec / prec / flags on request.  Backward pass, again in chunks
@@ -311,7 +267,7 @@ __global__ __launch_bounds__(kApThreads) void ap_curve_kernel(const int32_t* __r
       local += f[q];
     }
     int total;
-    int run = carry + block_scan_add(local, s_int, &total) - local;
+    int run = carry + block_scan_add<kApThreads / 64>(local, s_int, &total) - local;
 #pragma unroll
     for (int q = 0; q < kApItems; ++q) {
       const int64_t i = base + (int64_t)tid * kApItems + q;
@@ -350,7 +306,7 @@ __global__ __launch_bounds__(kApThreads) void ap_curve_kernel(const int32_t* __r
     }
     double all;
     // the envelope behind this thread's items: the threads after it in the chunk and everything in the later chunks
-    double env = fmax(env_carry, block_rscan_max_excl(local, s_dbl, &all));
+    double env = fmax(env_carry, block_rscan_max_excl<kApThreads / 64>(local, s_dbl, &all));
 #pragma unroll
     for (int q = kApItems - 1; q >= 0; --q) {
       const int64_t i = base + (int64_t)tid * kApItems + q;

@@ -10,6 +10,8 @@
 // only atomics are integer ones.
 #include <algorithm>
 
+#include "cellgrid.h"
+#include "exact.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -28,7 +30,6 @@ constexpr int kLdsMatches = 512;         // matches staged per step by ransac_sc
 constexpr double kDegenerate = 1e-9;
 
 __device__ inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ inline double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---- segmented nearest neighbour in feature space ------------------------------------------------------------------------
 // grid.x: the query tiles of all segments, one after the other (ceil(Q / 64) + B bounds their number; a workgroup past the
@@ -145,31 +146,11 @@ __global__ __launch_bounds__(kThreads) void feat_nn_final_kernel(const unsigned 
   d2[i] = k == kNoKey ? __uint_as_float(0x7fc00000u) : __uint_as_float((uint32_t)(k >> 32));
 }
 
-// the segment of position i: offs[b] <= i < offs[b + 1]; -1 if there is none
-__device__ inline int segment_of(const int64_t* __restrict__ offs, int B, int64_t i) {
-  int lo = 0, hi = B + 1;  // first position with offs[pos] > i
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (offs[mid] <= i) lo = mid + 1; else hi = mid;
-  }
-  return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
-
 // ---- the geometric check ---------------------------------------------------------------------------------------------------
 struct Taus {
   double t2[PCMI_MATCH_MAX_TAU];
   int n;
 };
-
-// y = ((R0 x + R1 y) + R2 z) + t per row of a 3 x 4 block laid out with row stride `ld`
-__device__ inline void apply_rigid(const double* __restrict__ m, int ld, double x, double y, double z, double* out) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) out[r] = ((m[ld * r] * x + m[ld * r + 1] * y) + m[ld * r + 2] * z) + m[ld * r + 3];
-}
-__device__ inline double dist2(const double* a, double bx, double by, double bz) {
-  const double dx = a[0] - bx, dy = a[1] - by, dz = a[2] - bz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
 
 __global__ __launch_bounds__(kThreads) void match_stats_kernel(const double* __restrict__ xyz0, int64_t n0,
                                                                const double* __restrict__ xyz1, int64_t n1,
@@ -201,8 +182,8 @@ __global__ __launch_bounds__(kThreads) void match_stats_kernel(const double* __r
       if (row_ok && j >= 0 && j < n1) {
         bits |= 1u << PCMI_MATCH_N_VALID;
         double y[3];
-        apply_rigid(T + 16 * b, 4, xyz0[3 * row], xyz0[3 * row + 1], xyz0[3 * row + 2], y);
-        r2 = dist2(y, xyz1[3 * j], xyz1[3 * j + 1], xyz1[3 * j + 2]);
+        rigid_apply(T + 16 * b, 4, xyz0 + 3 * row, y);
+        r2 = dist2_rn(y, xyz1 + 3 * j);
         for (int k = 0; k < taus.n; ++k)
           if (r2 <= taus.t2[k]) bits |= (1u << (PCMI_MATCH_HITS + k)) | (gt ? 1u << (PCMI_MATCH_HITS_GT + k) : 0u);
         if (nn10 && (int64_t)nn10[q] == row) bits |= 1u << PCMI_MATCH_N_MUTUAL;
@@ -257,7 +238,7 @@ __device__ inline double match_r2(const double* Rt, const double* p, const doubl
   double y[3];
 #pragma unroll
   for (int r = 0; r < 3; ++r) y[r] = ((Rt[3 * r] * p[0] + Rt[3 * r + 1] * p[1]) + Rt[3 * r + 2] * p[2]) + Rt[9 + r];
-  return dist2(y, q[0], q[1], q[2]);
+  return dist2_rn(y, q);
 }
 
 // the hypothesis h of segment [lo, lo + m): false if it is invalid

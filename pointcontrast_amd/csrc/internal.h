@@ -164,6 +164,20 @@ int inverse_lists(const char* who, const int32_t* idx, int64_t B, int64_t L, int
 // on a stream are serialised and every kernel leaves its counters at zero.  nullptr on allocation failure.
 unsigned* stream_counters(hipStream_t st, size_t n);
 
+// bump allocator over a caller's workspace: 256-byte aligned pieces, nullptr once it is exhausted
+struct Carve {
+  char* p;
+  size_t left;
+  void* take(size_t bytes) {
+    const size_t b = align_up(bytes, 256);
+    if (b > left) return nullptr;
+    void* r = p;
+    p += b;
+    left -= b;
+    return r;
+  }
+};
+
 // compute units of the current device (cached; 256 on MI355X)
 static inline int num_cu() {
   static int n = 0;

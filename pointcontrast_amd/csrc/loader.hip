@@ -12,57 +12,28 @@
 
 #include <algorithm>
 
+#include "cellgrid.h"
 #include "common.h"
+#include "exact.h"
 #include "internal.h"
+
+#pragma clang fp contract(off)
 
 namespace pcmi {
 
-constexpr int kCellBias = 1 << 20;   // |cell index| < 2^20 per axis
-constexpr int kMaxMatches = 96;      // per source point (r = 1.5 voxels, one target per voxel: <= ~30)
-
-__device__ inline uint64_t cell_key(int64_t x, int64_t y, int64_t z) {
-  return ((uint64_t)(x + kCellBias) << 42) | ((uint64_t)(y + kCellBias) << 21) | (uint64_t)(z + kCellBias);
-}
-__device__ inline bool cell_ok(int64_t x, int64_t y, int64_t z) {
-  return x > -kCellBias && x < kCellBias && y > -kCellBias && y < kCellBias && z > -kCellBias && z < kCellBias;
-}
-// floor(v / cell) as an integer is defined only for a finite point: a NaN or an infinity is refused before the conversion
-// (PCMI_ERR_RANGE, as a point outside +-2^20 cells), whatever the hardware's conversion would have made of it
-__device__ inline bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// slot of `key` (claimed if absent): open addressing, linear probing
-__device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {
-    const unsigned long long prev = atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
-    if (prev == kEmptyKey || prev == key) return slot;
-    slot = (slot + 1) & mask;
-  }
-}
-__device__ inline int64_t find_slot(const uint64_t* keys, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {
-    const uint64_t k = keys[slot];
-    if (k == key) return slot;
-    if (k == kEmptyKey) return -1;
-    slot = (slot + 1) & mask;
-  }
-}
-
 // ---- voxelisation ----------------------------------------------------------------------------------------------
+// A point that is not finite or falls outside +-2^20 voxels has no voxel (cells_of): PCMI_ERR_RANGE.
 __global__ void vox_insert_kernel(const double* __restrict__ xyz, int64_t n, double voxel, uint64_t* keys, int32_t* vals,
-                                  uint32_t mask, uint32_t* slot_of, int32_t* err) {
+                                  uint32_t cap, uint32_t* slot_of, int32_t* err) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool fin = finite3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
-  const int64_t x = fin ? (int64_t)floor(xyz[3 * i] / voxel) : 0, y = fin ? (int64_t)floor(xyz[3 * i + 1] / voxel) : 0,
-                z = fin ? (int64_t)floor(xyz[3 * i + 2] / voxel) : 0;
-  if (!fin || !cell_ok(x, y, z)) {
+  int64_t c[3];
+  if (!cells_of(xyz + 3 * i, voxel, c)) {
     atomicAdd(err, 1);
     slot_of[i] = 0xffffffffu;
     return;
   }
-  const uint32_t slot = claim_slot(keys, mask, cell_key(x, y, z));
+  const uint32_t slot = claim_slot(keys, 0, cap, cell_key(c[0], c[1], c[2]));
   atomicMin(&vals[slot], (int32_t)i);  // first occurrence = smallest point index of the voxel
   slot_of[i] = slot;
 }
@@ -89,44 +60,35 @@ __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
 }
 
 // ---- radius matching -------------------------------------------------------------------------------------------
-struct Rigid {  // row-major 3x4: p' = R p + t, evaluated as ((R0 x + R1 y) + R2 z) + t with separately rounded ops
+struct Rigid {  // row-major 3x4: p' = R p + t (rigid_apply)
   double m[12];
 };
-__device__ inline double mul_rn(double a, double b) { return __dmul_rn(a, b); }
-__device__ inline double add_rn(double a, double b) { return __dadd_rn(a, b); }
-__device__ inline void apply_rigid(const Rigid& T, const double* p, double* o) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    o[r] = add_rn(add_rn(add_rn(mul_rn(T.m[4 * r], p[0]), mul_rn(T.m[4 * r + 1], p[1])), mul_rn(T.m[4 * r + 2], p[2])), T.m[4 * r + 3]);
-}
 
 __global__ void grid_insert_kernel(const double* __restrict__ dst, int64_t n1, double radius, uint64_t* keys, int32_t* head,
-                                   uint32_t mask, int32_t* __restrict__ next, int32_t* err) {
+                                   uint32_t cap, int32_t* __restrict__ next, int32_t* err) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n1) return;
-  const bool fin = finite3(dst[3 * j], dst[3 * j + 1], dst[3 * j + 2]);
-  const int64_t x = fin ? (int64_t)floor(dst[3 * j] / radius) : 0, y = fin ? (int64_t)floor(dst[3 * j + 1] / radius) : 0,
-                z = fin ? (int64_t)floor(dst[3 * j + 2] / radius) : 0;
-  if (!fin || !cell_ok(x, y, z)) {
+  int64_t c[3];
+  if (!cells_of(dst + 3 * j, radius, c)) {
     atomicAdd(err, 1);
     next[j] = -1;
     return;
   }
-  const uint32_t slot = claim_slot(keys, mask, cell_key(x, y, z));
+  const uint32_t slot = claim_slot(keys, 0, cap, cell_key(c[0], c[1], c[2]));
   next[j] = atomicExch(&head[slot], (int32_t)j);  // list order is arbitrary: the matches are sorted per source point
 }
 
 // FILL = false: count[i] = number of targets within the radius; FILL = true: pairs[offs[i] ..] = (i, j), j ascending
 template <bool FILL>
-__global__ void match_kernel(const double* __restrict__ src, int64_t n0, Rigid T, const double* __restrict__ dst, double radius,
-                             const uint64_t* __restrict__ keys, const int32_t* __restrict__ head, uint32_t mask,
+__global__ void match_kernel(const double* __restrict__ src, int64_t n0, Rigid T, const double* __restrict__ dst, int64_t n1, double radius,
+                             const uint64_t* __restrict__ keys, const int32_t* __restrict__ head, uint32_t cap,
                              const int32_t* __restrict__ next, int64_t* __restrict__ count, const int64_t* __restrict__ offs,
                              int32_t* __restrict__ pairs, int32_t* err) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n0) return;
   const double p[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
   double q[3];
-  apply_rigid(T, p, q);
+  rigid_apply(T.m, 4, p, q);
   if (!finite3(q[0], q[1], q[2])) {  // a non-finite source point, or one the transform made non-finite
     if (!FILL) {
       atomicAdd(err, 1);
@@ -134,25 +96,10 @@ __global__ void match_kernel(const double* __restrict__ src, int64_t n0, Rigid T
     }
     return;
   }
-  const int64_t cx = (int64_t)floor(q[0] / radius), cy = (int64_t)floor(q[1] / radius), cz = (int64_t)floor(q[2] / radius);
-  const double r2 = mul_rn(radius, radius);
-  int32_t found[kMaxMatches];
-  int nf = 0;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy)
-      for (int dx = -1; dx <= 1; ++dx) {
-        if (!cell_ok(cx + dx, cy + dy, cz + dz)) continue;
-        const int64_t slot = find_slot(keys, mask, cell_key(cx + dx, cy + dy, cz + dz));
-        if (slot < 0) continue;
-        for (int32_t j = head[slot]; j >= 0; j = next[j]) {
-          const double ex = add_rn(q[0], -dst[3 * j]), ey = add_rn(q[1], -dst[3 * j + 1]), ez = add_rn(q[2], -dst[3 * j + 2]);
-          const double d2 = add_rn(add_rn(mul_rn(ex, ex), mul_rn(ey, ey)), mul_rn(ez, ez));
-          if (d2 <= r2) {
-            if (FILL && nf < kMaxMatches) found[nf] = j;
-            ++nf;
-          }
-        }
-      }
+  // (a source outside the grid's range meets only the cells cell_ok admits: no error, the oracle has no range either)
+  const int64_t cell[3] = {(int64_t)floor(q[0] / radius), (int64_t)floor(q[1] / radius), (int64_t)floor(q[2] / radius)};
+  int32_t found[FILL ? kMaxMatches : 1];
+  int nf = radius_probe(dst, n1, q, cell, radius, keys, head, next, 0, cap, FILL ? found : nullptr);
   if (nf > kMaxMatches) atomicAdd(err, 1);
   if (!FILL) {
     count[i] = nf;
@@ -181,19 +128,6 @@ static uint32_t table_cap(int64_t n) {
   return c;
 }
 
-struct Carve2 {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
-
 static size_t scan_temp_bytes(int64_t n) {
   size_t b = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr, (int)std::max<int64_t>(n, 1));
@@ -219,7 +153,7 @@ int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* firs
   if (n == 0) return PCMI_OK;
   hipStream_t st = as_stream(stream);
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_voxelize_workspace_bytes(n), PCMI_ERR_WORKSPACE, "voxelize: workspace too small");
-  Carve2 cv{(char*)ws, ws_bytes};
+  Carve cv{(char*)ws, ws_bytes};
   const uint32_t cap = table_cap(n);
   uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
   int32_t* vals = (int32_t*)cv.take((size_t)cap * 4);
@@ -235,7 +169,7 @@ int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* firs
   const unsigned gc = (unsigned)ceil_div(cap, 256), gn = (unsigned)ceil_div(n, 256);
   fill_i32_kernel<<<gc, 256, 0, st>>>(vals, cap, 0x7fffffff);
   PCMI_LAUNCH_CHECK();
-  vox_insert_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, keys, vals, cap - 1, slot_of, err);
+  vox_insert_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, keys, vals, cap, slot_of, err);
   PCMI_LAUNCH_CHECK();
   vox_flag_kernel<<<gn, 256, 0, st>>>(n, vals, slot_of, flags);
   PCMI_LAUNCH_CHECK();
@@ -267,7 +201,7 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   if (n0 == 0 || n1 == 0) return PCMI_OK;
   hipStream_t st = as_stream(stream);
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_match_radius_workspace_bytes(n0, n1), PCMI_ERR_WORKSPACE, "match_radius: workspace too small");
-  Carve2 cv{(char*)ws, ws_bytes};
+  Carve cv{(char*)ws, ws_bytes};
   const uint32_t cap = table_cap(n1);
   uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
   int32_t* head = (int32_t*)cv.take((size_t)cap * 4);
@@ -284,9 +218,9 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   PCMI_HIP_CHECK(hipMemsetAsync(head, 0xff, (size_t)cap * 4, st));  // -1
   PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
   const unsigned g0 = (unsigned)ceil_div(n0, 128), g1 = (unsigned)ceil_div(n1, 256);
-  grid_insert_kernel<<<g1, 256, 0, st>>>(dst, n1, radius, keys, head, cap - 1, next, err);
+  grid_insert_kernel<<<g1, 256, 0, st>>>(dst, n1, radius, keys, head, cap, next, err);
   PCMI_LAUNCH_CHECK();
-  match_kernel<false><<<g0, 128, 0, st>>>(src, n0, T, dst, radius, keys, head, cap - 1, next, count, nullptr, nullptr, err);
+  match_kernel<false><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, keys, head, cap, next, count, nullptr, nullptr, err);
   PCMI_LAUNCH_CHECK();
   size_t tb2 = tb;
   PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, count, offs, (int)n0, st));
@@ -303,7 +237,7 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   if (!pairs || *n_pairs_host == 0) return PCMI_OK;  // count-only call
   PCMI_REQUIRE(pairs_capacity >= *n_pairs_host, PCMI_ERR_WORKSPACE, "match_radius: %lld pairs but room for %lld",
                (long long)*n_pairs_host, (long long)pairs_capacity);
-  match_kernel<true><<<g0, 128, 0, st>>>(src, n0, T, dst, radius, keys, head, cap - 1, next, nullptr, offs, pairs, err);
+  match_kernel<true><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, keys, head, cap, next, nullptr, offs, pairs, err);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -29,6 +29,8 @@
 
 #include <algorithm>
 
+#include "cellgrid.h"
+#include "exact.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -44,15 +46,6 @@ constexpr int64_t kMaxRef = 1ll << 29; // table of 2 m slots, scanned with 32-bi
 constexpr int kMaxClasses = 64;        // as segeval.hip: 64 x 64 x 4 bytes = 16 KB of LDS
 constexpr int kFallbackGrid = 2048;    // workgroups of the fallback launch (each walks the list with this stride)
 constexpr uint32_t kNoSlot = 0xffffffffu;
-
-// Plain operators under this file's `fp contract(off)`: each is one IEEE round-to-nearest operation.  (Not __dmul_rn /
-// __dadd_rn: those are inline functions of a header compiled with contraction allowed, and once inlined their product and sum
-// may be fused again.)
-__device__ inline double mul_rn(double a, double b) { return a * b; }
-__device__ inline double add_rn(double a, double b) { return a + b; }
-__device__ inline double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline double pinf() { return __longlong_as_double(0x7ff0000000000000ll); }
-__device__ inline bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // ---- voxel centres -------------------------------------------------------------------------------------------------------------
 constexpr int kMatPerLaunch = 32;  // 32 x 12 doubles = 3 KB of kernel arguments
@@ -71,11 +64,8 @@ __global__ __launch_bounds__(kThreads) void voxel_centers_kernel(const int32_t* 
     return;
   }
   if (b < b0 || b >= b0 + nb) return;
-  const double X = (double)coords[4 * i + 1] + 0.5, Y = (double)coords[4 * i + 2] + 0.5, Z = (double)coords[4 * i + 3] + 0.5;
-  const double* m = T.m[b - b0];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    centers[3 * i + r] = add_rn(add_rn(add_rn(mul_rn(X, m[4 * r]), mul_rn(Y, m[4 * r + 1])), mul_rn(Z, m[4 * r + 2])), m[4 * r + 3]);
+  const double c[3] = {(double)coords[4 * i + 1] + 0.5, (double)coords[4 * i + 2] + 0.5, (double)coords[4 * i + 3] + 0.5};
+  rigid_apply(T.m[b - b0], 4, c, centers + 3 * i);
 }
 
 // ---- nearest reference row -----------------------------------------------------------------------------------------------------
@@ -83,16 +73,6 @@ struct Rec {  // one binned reference: 32 bytes, two 16-byte loads, the records 
   double x, y, z;
   int64_t row;
 };
-
-// the scene of row i: offs[b] <= i < offs[b + 1] (offs ascending, empty scenes allowed); -1 if there is none
-__device__ inline int scene_of(const int64_t* __restrict__ offs, int B, int64_t i) {
-  int lo = 0, hi = B + 1;  // first position with offs[pos] > i
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (offs[mid] <= i) lo = mid + 1; else hi = mid;
-  }
-  return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
 
 // the cell of a finite point; false if an index does not fit the key (or h is no usable cell size)
 __device__ inline bool cell_of(double x, double y, double z, double h, int* cx, int* cy, int* cz) {
@@ -103,24 +83,6 @@ __device__ inline bool cell_of(double x, double y, double z, double h, int* cx, 
   *cy = (int)fy;
   *cz = (int)fz;
   return true;
-}
-
-__device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {  // ends: the table has at least twice as many slots as there are rows
-    const unsigned long long prev = atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
-    if (prev == kEmptyKey || prev == key) return slot;
-    slot = (slot + 1) & mask;
-  }
-}
-__device__ inline int64_t find_slot(const uint64_t* __restrict__ keys, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {
-    const uint64_t k = keys[slot];
-    if (k == key) return slot;
-    if (k == kEmptyKey) return -1;
-    slot = (slot + 1) & mask;
-  }
 }
 
 __device__ inline double cell_size(double cell, const double* cell_dev) { return cell_dev ? *cell_dev : cell; }
@@ -134,12 +96,12 @@ __global__ __launch_bounds__(kThreads) void nn_count_kernel(const double* __rest
   const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (j >= m) return;
   uint32_t slot = kNoSlot;
-  const int b = scene_of(roffs, B, j);
+  const int b = segment_of(roffs, B, j);
   const double x = ref[3 * j], y = ref[3 * j + 1], z = ref[3 * j + 2];
   if (b >= 0 && finite3(x, y, z)) {
     int cx, cy, cz;
     if (cell_of(x, y, z, cell_size(cell, cell_dev), &cx, &cy, &cz)) {
-      slot = claim_slot(keys, mask, pack_key(b, cx, cy, cz));
+      slot = claim_slot(keys, 0, mask + 1, pack_key(b, cx, cy, cz));
       atomicAdd(&count[slot], 1);
     } else {
       atomicOr(&scene_flag[b], 1);
@@ -169,8 +131,8 @@ struct Best {
   int64_t row;  // INT64_MAX: none yet
 };
 __device__ inline void consider(Best& best, double qx, double qy, double qz, double rx, double ry, double rz, int64_t row) {
-  const double dx = add_rn(qx, -rx), dy = add_rn(qy, -ry), dz = add_rn(qz, -rz);
-  const double d2 = add_rn(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)), mul_rn(dz, dz));
+  const double q[3] = {qx, qy, qz}, r[3] = {rx, ry, rz};
+  const double d2 = dist2_rn(q, r);
   if (d2 < best.d2 || (d2 == best.d2 && row < best.row)) {
     best.d2 = d2;
     best.row = row;
@@ -193,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void nn_query_kernel(const double* __rest
     if (dist2) dist2[i] = qnan();
     return;
   }
-  const int b = scene_of(qoffs, B, i);
+  const int b = segment_of(qoffs, B, i);
   const int64_t lo = b >= 0 ? std::max<int64_t>(roffs[b], 0) : 0, hi = b >= 0 ? std::min<int64_t>(roffs[b + 1], m) : 0;
   if (lo >= hi) {  // no scene, or a scene without references
     idx[i] = -1;
@@ -210,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void nn_query_kernel(const double* __rest
         for (int dy = -r; dy <= r; ++dy)
           for (int dx = -r; dx <= r; ++dx) {
             if (r > 1 && abs(dx) < r && abs(dy) < r && abs(dz) < r) continue;  // searched at a smaller radius
-            const int64_t slot = find_slot(keys, mask, pack_key(b, cx + dx, cy + dy, cz + dz));
+            const int64_t slot = find_slot(keys, 0, mask + 1, pack_key(b, cx + dx, cy + dy, cz + dz));
             if (slot < 0) continue;
             const int32_t e = start[slot + 1];
             for (int32_t p = start[slot]; p < e; ++p) {
@@ -245,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void nn_fallback_kernel(const double* __r
   for (int32_t f = blockIdx.x; f < n_fb; f += gridDim.x) {
     const int64_t i = fb_list[f];
     const double qx = query[3 * i], qy = query[3 * i + 1], qz = query[3 * i + 2];
-    const int b = scene_of(qoffs, B, i);  // (listed queries have a scene with references)
+    const int b = segment_of(qoffs, B, i);  // (listed queries have a scene with references)
     const int64_t lo = std::max<int64_t>(roffs[b], 0), hi = std::min<int64_t>(roffs[b + 1], m);
     Best best{pinf(), INT64_MAX};
     for (int64_t j = lo + tid; j < hi; j += kThreads) {
@@ -323,19 +285,6 @@ static size_t scan_temp_bytes(int64_t items) {
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)items);
   return align_up(b + 256, 256);
 }
-
-struct Carve {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
 
 static bool nn_shape_ok(int64_t m, int64_t n, int64_t B) {
   return m >= 0 && n >= 0 && m < (1ll << 31) && n < (1ll << 31) && B >= 1 && B <= kMaxScenes;

@@ -17,6 +17,8 @@
 #include <algorithm>
 #include <climits>
 
+#include "cellgrid.h"
+#include "exact.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -28,73 +30,20 @@ constexpr int kThreads = 256;
 constexpr int kMaxPairs = PCMI_PAIR_MAX_PAIRS;
 constexpr int kChunk = PCMI_PAIR_CENTROID_CHUNK;
 constexpr int kPerThread = kChunk / kThreads;
-constexpr int kCellBias = 1 << 20;       // |voxel or cell index| < 2^20 per axis (csrc/loader.hip)
-constexpr int kMaxMatches = 96;          // per source point (csrc/loader.hip)
 constexpr int64_t kMaxRows = 1ll << 29;  // segmented tables of 2 n + 2 B slots, addressed with 32 bits
 constexpr uint32_t kNoSlot = 0xffffffffu;
 
 static_assert(kChunk % kThreads == 0 && (kThreads & (kThreads - 1)) == 0, "one workgroup sums a chunk: whole rounds, then a binary tree");
-
-__device__ inline double mul_rn(double a, double b) { return a * b; }
-__device__ inline double add_rn(double a, double b) { return a + b; }
-__device__ inline bool finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-__device__ inline uint64_t cell_key(int64_t x, int64_t y, int64_t z) {
-  return ((uint64_t)(x + kCellBias) << 42) | ((uint64_t)(y + kCellBias) << 21) | (uint64_t)(z + kCellBias);
-}
-__device__ inline bool cell_ok(int64_t x, int64_t y, int64_t z) {
-  return x > -kCellBias && x < kCellBias && y > -kCellBias && y < kCellBias && z > -kCellBias && z < kCellBias;
-}
-// floor(v / cell) per axis as integers inside +-(2^20 - 1); false (nothing converted) for anything else, a NaN included
-__device__ inline bool cells_of(const double* p, double cell, int64_t* out) {
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double f = floor(p[a] / cell);
-    ok = ok && fabs(f) < (double)kCellBias;
-    out[a] = ok ? (int64_t)f : 0;
-  }
-  return ok;
-}
 
 // rows [lo, hi) of cloud c, clipped to [0, n] (offs ascending; a cloud may be empty)
 __device__ inline void cloud_rows(const int64_t* __restrict__ offs, int c, int64_t n, int64_t& lo, int64_t& hi) {
   lo = std::min<int64_t>(std::max<int64_t>(offs[c], 0), n);
   hi = std::min<int64_t>(std::max<int64_t>(offs[c + 1], lo), n);
 }
-// the cloud of row i: offs[c] <= i < offs[c + 1]; -1 if there is none
-__device__ inline int cloud_of(const int64_t* __restrict__ offs, int nc, int64_t i) {
-  int lo = 0, hi = nc + 1;  // first position with offs[pos] > i
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (offs[mid] <= i) lo = mid + 1; else hi = mid;
-  }
-  return (lo == 0 || lo == nc + 1) ? -1 : lo - 1;
-}
 __device__ inline int64_t chunks_of(int64_t rows) { return (rows + kChunk - 1) / kChunk; }
 
 __device__ inline double raw_at(const void* __restrict__ raw, int f32, int64_t k) {
   return f32 ? (double)((const float*)raw)[k] : ((const double*)raw)[k];
-}
-
-// the slot of `key` in the table segment [base, base + size) of one cloud (claimed if absent): open addressing, linear probing;
-// ends, since a segment has more than twice as many slots as its cloud has rows
-__device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t base, uint32_t size, uint64_t key) {
-  uint32_t s = hash_key(key) % size;
-  while (true) {
-    const unsigned long long prev = atomicCAS((unsigned long long*)&keys[base + s], (unsigned long long)kEmptyKey, (unsigned long long)key);
-    if (prev == kEmptyKey || prev == key) return base + s;
-    if (++s == size) s = 0;
-  }
-}
-__device__ inline int64_t find_slot(const uint64_t* __restrict__ keys, uint32_t base, uint32_t size, uint64_t key) {
-  uint32_t s = hash_key(key) % size;
-  for (uint32_t step = 0; step < size; ++step) {  // (a segment always has an empty slot; the bound is for a table that is not one)
-    const uint64_t k = keys[base + s];
-    if (k == key) return (int64_t)base + s;
-    if (k == kEmptyKey) return -1;
-    if (++s == size) s = 0;
-  }
-  return -1;
 }
 
 // ---- transform -------------------------------------------------------------------------------------------------------------
@@ -204,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void tf_point_kernel(const void* __restri
                                                             double* __restrict__ out, int32_t* flags) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
-  const int c = cloud_of(offs, nc, i);
+  const int c = segment_of(offs, nc, i);
   if (c < 0) {  // a row of no cloud: dropped by pcmi_pair_voxelize
     out[3 * i] = out[3 * i + 1] = out[3 * i + 2] = 0.0;
     return;
@@ -213,11 +162,8 @@ __global__ __launch_bounds__(kThreads) void tf_point_kernel(const void* __restri
   const double x[3] = {raw_at(raw, f32, 3 * i), raw_at(raw, f32, 3 * i + 1), raw_at(raw, f32, 3 * i + 2)};
   double p[3] = {mul_rn(sc, x[0]), mul_rn(sc, x[1]), mul_rn(sc, x[2])};
   if (rotate) {
-    const double* m = T + 16 * c;
     double q[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      q[r] = add_rn(add_rn(add_rn(mul_rn(m[4 * r], p[0]), mul_rn(m[4 * r + 1], p[1])), mul_rn(m[4 * r + 2], p[2])), m[4 * r + 3]);
+    rigid_apply(T + 16 * c, 4, p, q);
     p[0] = q[0], p[1] = q[1], p[2] = q[2];
   }
   if (!finite3(x[0], x[1], x[2]) || !finite3(p[0], p[1], p[2])) atomicOr(&flags[c >> 1], PCMI_PAIR_FLAG_NONFINITE);
@@ -232,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void vx_insert_kernel(const double* __res
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   uint32_t slot = kNoSlot;
-  const int c = cloud_of(offs, nc, i);
+  const int c = segment_of(offs, nc, i);
   int64_t lo = 0, hi = 0;
   if (c >= 0) cloud_rows(offs, c, n, lo, hi);
   if (c >= 0 && i >= lo && i < hi) {  // (always, for ascending offsets: a segment never takes more rows than it was sized for)
@@ -258,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void vx_first_kernel(int64_t n, const int
   int f = 0;
   if (i < n) {
     const uint32_t slot = slot_of[i];
-    if (slot != kNoSlot && first[slot] == (uint32_t)i) f = flags[cloud_of(offs, nc, i) >> 1] == 0 ? 1 : 0;  // a flagged pair yields no rows
+    if (slot != kNoSlot && first[slot] == (uint32_t)i) f = flags[segment_of(offs, nc, i) >> 1] == 0 ? 1 : 0;  // a flagged pair yields no rows
   }
   is_first[i] = f;  // (is_first[n] = 0: the scan over n + 1 items ends in the total)
 }
@@ -309,7 +255,7 @@ __global__ __launch_bounds__(kThreads) void mt_insert_kernel(const double* __res
   const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (j >= m_max) return;
   next[j] = -1;
-  const int c = cloud_of(voff, nc, j);
+  const int c = segment_of(voff, nc, j);
   if (c < 0 || !(c & 1)) return;
   int64_t lo, hi;
   cloud_rows(voff, c, m_max, lo, hi);
@@ -328,36 +274,6 @@ __global__ __launch_bounds__(kThreads) void mt_insert_kernel(const double* __res
   }
 }
 
-// the targets within radius of source row i (cloud 2 b), in `found` (the first kMaxMatches of them) if given; returns their number
-__device__ inline int probe(const double* __restrict__ pts, int64_t m_max, const double* q, const int64_t* cell, double r, const uint64_t* __restrict__ keys,
-                            const int32_t* __restrict__ head, const int32_t* __restrict__ next, uint32_t base, uint32_t size, int32_t* found) {
-  const double r2 = mul_rn(r, r);
-  int nf = 0;
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy)
-      for (int dx = -1; dx <= 1; ++dx) {
-        if (!cell_ok(cell[0] + dx, cell[1] + dy, cell[2] + dz)) continue;
-        const int64_t slot = find_slot(keys, base, size, cell_key(cell[0] + dx, cell[1] + dy, cell[2] + dz));
-        if (slot < 0) continue;
-        int64_t steps = 0;  // (a list is acyclic and inside the rows; the bounds are for a workspace that holds no lists)
-        for (int32_t j = head[slot]; j >= 0 && j < m_max && steps < m_max; j = next[j], ++steps) {
-          const double ex = add_rn(q[0], -pts[3 * (int64_t)j]), ey = add_rn(q[1], -pts[3 * (int64_t)j + 1]), ez = add_rn(q[2], -pts[3 * (int64_t)j + 2]);
-          const double d2 = add_rn(add_rn(mul_rn(ex, ex), mul_rn(ey, ey)), mul_rn(ez, ez));
-          if (d2 <= r2) {
-            if (found && nf < kMaxMatches) found[nf] = j;
-            ++nf;
-          }
-        }
-      }
-  return nf;
-}
-
-__device__ inline void apply_rigid(const double* __restrict__ T, const double* p, double* o) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    o[r] = add_rn(add_rn(add_rn(mul_rn(T[4 * r], p[0]), mul_rn(T[4 * r + 1], p[1])), mul_rn(T[4 * r + 2], p[2])), T[4 * r + 3]);
-}
-
 // FILL = false: count[i] = the matches of source row i (0 for every other row, count[m_max] = 0), nq[b] += rows with a match;
 // FILL = true: the rows of the pairs that are not flagged, (i, j) with the batch row offsets, j ascending
 template <bool FILL>
@@ -374,7 +290,7 @@ __global__ __launch_bounds__(128) void mt_match_kernel(const double* __restrict_
   int32_t found[FILL ? kMaxMatches : 1];
   int64_t lo0 = 0, lo1 = 0;
   if (i < m_max) {
-    const int c = cloud_of(voff, nc, i);
+    const int c = segment_of(voff, nc, i);
     int64_t hi0 = 0, hi1 = 0;
     if (c >= 0 && !(c & 1)) {
       cloud_rows(voff, c, m_max, lo0, hi0);
@@ -386,13 +302,13 @@ __global__ __launch_bounds__(128) void mt_match_kernel(const double* __restrict_
       const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
       double q[3];
       int64_t cell[3];
-      apply_rigid(trans + 16 * b, p, q);
+      rigid_apply(trans + 16 * b, 4, p, q);
       if (!finite3(q[0], q[1], q[2])) {  // a source point the transform made non-finite
         if (!FILL) atomicOr(&flags[b], PCMI_PAIR_FLAG_NONFINITE);
       } else if (!(r > 0.0) || !cells_of(q, r, cell)) {
         if (!FILL) atomicOr(&flags[b], PCMI_PAIR_FLAG_RANGE);
       } else if (hi1 > lo1) {
-        nf = probe(pts, m_max, q, cell, r, keys, head, next, (uint32_t)(2 * lo1 + 2 * b + 1), (uint32_t)(2 * (hi1 - lo1) + 1), FILL ? found : nullptr);
+        nf = radius_probe(pts, m_max, q, cell, r, keys, head, next, (uint32_t)(2 * lo1 + 2 * b + 1), (uint32_t)(2 * (hi1 - lo1) + 1), FILL ? found : nullptr);
       }
       if (!FILL && nf > kMaxMatches) atomicOr(&flags[b], PCMI_PAIR_FLAG_MATCHES);
     }
@@ -493,7 +409,7 @@ __global__ __launch_bounds__(kThreads) void co_kernel(const double* __restrict__
   const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (r < 16 * (int64_t)B) T_gt[r] = (float)trans[r];
   if (r >= m_max) return;
-  const int c = cloud_of(voff, 2 * B, r);
+  const int c = segment_of(voff, 2 * B, r);
   if (c < 0) return;
   int64_t lo, hi;
   cloud_rows(voff, c, m_max, lo, hi);
@@ -523,7 +439,7 @@ __global__ __launch_bounds__(kThreads) void cf_kernel(const uint8_t* __restrict_
                                                       double mu, double sigma, int64_t out_rows, float* __restrict__ F0, float* __restrict__ F1) {
   const int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (r >= m_max) return;
-  const int c = cloud_of(voff, 2 * B, r);
+  const int c = segment_of(voff, 2 * B, r);
   if (c < 0) return;
   int64_t lo, hi;
   cloud_rows(voff, c, m_max, lo, hi);
@@ -553,19 +469,6 @@ static size_t scan_temp_bytes64(int64_t items) {
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr, (int)items);
   return align_up(b + 256, 256);
 }
-
-struct Carve {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
 
 static int64_t max_chunks(int64_t n, int64_t B) { return ceil_div(n, kChunk) + 2 * B; }
 static int64_t table_slots(int64_t n, int64_t B) { return 2 * n + 2 * B; }

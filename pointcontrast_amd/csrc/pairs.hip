@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "blockscan.h"
 #include "common.h"
 #include "internal.h"
 
@@ -23,27 +24,6 @@ __device__ inline int run_flag(const int32_t* __restrict__ pairs, int64_t i, int
   return (i == 0 || pairs[2 * i] != pairs[2 * (i - 1)]) ? 1 : 0;
 }
 
-// block sum of per-thread counts; returns the exclusive prefix of this thread and the block total
-__device__ inline int block_exclusive(int v, int* s_wave /* [4] */, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) base += s_wave[w];
-    tot += s_wave[w];
-  }
-  *total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(256) void runs_count_kernel(const int32_t* __restrict__ pairs, int64_t P, int32_t* __restrict__ block_counts) {
   __shared__ int s_wave[4];
   const int64_t i0 = (int64_t)blockIdx.x * kRunBlock + (int64_t)threadIdx.x * kRunItems;
@@ -51,7 +31,7 @@ __global__ __launch_bounds__(256) void runs_count_kernel(const int32_t* __restri
 #pragma unroll
   for (int e = 0; e < kRunItems; ++e) c += run_flag(pairs, i0 + e, P);
   int tot;
-  (void)block_exclusive(c, s_wave, &tot);
+  (void)block_scan_add<4>(c, s_wave, &tot);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = tot;
 }
 
@@ -66,7 +46,7 @@ __global__ __launch_bounds__(256) void runs_scan_kernel(const int32_t* __restric
     const int b = b0 + (int)threadIdx.x;
     const int v = b < n_blocks ? block_counts[b] : 0;
     int tot;
-    const int ex = block_exclusive(v, s_wave, &tot);
+    const int ex = block_scan_add<4>(v, s_wave, &tot) - v;
     const int carry = s_carry;
     if (b < n_blocks) block_offs[b] = carry + ex;
     __syncthreads();
@@ -87,7 +67,7 @@ __global__ __launch_bounds__(256) void runs_write_kernel(const int32_t* __restri
     c += f[e];
   }
   int tot;
-  int pos = block_offs[blockIdx.x] + block_exclusive(c, s_wave, &tot);
+  int pos = block_offs[blockIdx.x] + block_scan_add<4>(c, s_wave, &tot) - c;
 #pragma unroll
   for (int e = 0; e < kRunItems; ++e)
     if (f[e]) starts[pos++] = (int32_t)(i0 + e);

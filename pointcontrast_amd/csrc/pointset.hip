@@ -403,19 +403,6 @@ __global__ void scatter_accumulate_kernel(const float* __restrict__ gout, const 
   gin[bc * N + t] = acc;
 }
 
-struct Carve {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
-
 static size_t scan_bytes(int64_t n) {
   size_t b = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)std::max<int64_t>(n, 1));

@@ -10,6 +10,7 @@
 // output is reproducible bit for bit.
 #include <algorithm>
 
+#include "blockscan.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -154,51 +155,6 @@ __global__ __launch_bounds__(256) void seg_npos_kernel(const int32_t* __restrict
   if (tid < c && s_cnt[tid]) atomicAdd(&npos[tid], s_cnt[tid]);
 }
 
-// inclusive sum over the workgroup of one int per thread (thread order); total: the sum over all threads
-__device__ __forceinline__ int block_scan_add(int v, int* s_wave /* [kApWaves] */, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  __syncthreads();  // the previous call's readers are done
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kApWaves; ++w) {
-    const int x = s_wave[w];
-    before += w < wave ? x : 0;
-    all += x;
-  }
-  *total = all;
-  return v + before;
-}
-
-// maximum over the threads strictly BEFORE this one (0 for the first: the values are >= 0); all: over all threads
-__device__ __forceinline__ int block_scan_max_excl(int v, int* s_wave /* [kApWaves] */, int* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v = max(v, u);
-  }
-  const int prev = __shfl_up(v, 1, 64);
-  __syncthreads();  // the previous call's readers are done
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  int before = lane > 0 ? prev : 0, m = 0;
-#pragma unroll
-  for (int w = 0; w < kApWaves; ++w) {
-    const int x = s_wave[w];
-    before = w < wave ? max(before, x) : before;
-    m = max(m, x);
-  }
-  *all = m;
-  return before;
-}
-
 // grid (class), one workgroup each, over the class's n scores in descending order, kApChunk at a time with a carry (so n may
 // be anything): positive flag = "the row's label is this class", inclusive count of positives tp; an element is a threshold
 // if it is the last of its run of equal scores (it differs from its successor, or is the last of all); a threshold where tp
@@ -233,7 +189,7 @@ __global__ __launch_bounds__(kApThreads) void seg_ap_kernel(const float* __restr
       local += f[q];
     }
     int total, top;
-    int tp = carry_tp + block_scan_add(local, s_int, &total) - local;
+    int tp = carry_tp + block_scan_add<kApWaves>(local, s_int, &total) - local;
     int tpq[kApItems], last_end = 0;
 #pragma unroll
     for (int q = 0; q < kApItems; ++q) {
@@ -241,7 +197,7 @@ __global__ __launch_bounds__(kApThreads) void seg_ap_kernel(const float* __restr
       tpq[q] = tp;
       last_end = end[q] ? tp : last_end;
     }
-    int prev = max(carry_prev, block_scan_max_excl(last_end, s_int, &top));
+    int prev = max(carry_prev, block_scan_max_excl<kApWaves>(last_end, s_int, &top));
 #pragma unroll
     for (int q = 0; q < kApItems; ++q) {
       const int64_t i = base + (int64_t)tid * kApItems + q;

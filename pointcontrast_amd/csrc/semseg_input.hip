@@ -17,6 +17,8 @@
 #include <algorithm>
 #include <climits>
 
+#include "cellgrid.h"
+#include "exact.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -30,34 +32,6 @@ constexpr int kVoxelLimit = 1 << 20;    // |voxel coordinate| < 2^20 (the loader
 constexpr int kSpan = 1 << 18;          // 0 <= x - min < 2^18: pack_key's 18-bit fields
 constexpr int64_t kMaxRows = 1ll << 29; // table of 2 n slots, scanned with 32-bit counts
 constexpr uint32_t kNoSlot = 0xffffffffu;
-
-__device__ inline double mul_rn(double a, double b) { return a * b; }
-__device__ inline double add_rn(double a, double b) { return a + b; }
-
-// the scene of row i: offs[b] <= i < offs[b + 1] (offs ascending, empty scenes allowed); -1 if there is none
-__device__ inline int scene_of(const int64_t* __restrict__ offs, int B, int64_t i) {
-  int lo = 0, hi = B + 1;  // first position with offs[pos] > i
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (offs[mid] <= i) lo = mid + 1; else hi = mid;
-  }
-  return (lo == 0 || lo == B + 1) ? -1 : lo - 1;
-}
-
-// order-preserving integer images: a < b  <=>  image(a) < image(b), for every pair of non-NaN values.  -0.0 sorts below +0.0
-// here, where numpy's min may return either zero; every use subtracts or compares the extreme, which the sign of zero cannot change
-__device__ inline unsigned long long ord64(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ inline double unord64(unsigned long long u) {
-  return __longlong_as_double((long long)((u >> 63) ? (u & 0x7fffffffffffffffull) : ~u));
-}
-__device__ inline uint32_t ord32(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float unord32(uint32_t u) { return __uint_as_float((u >> 31) ? (u & 0x7fffffffu) : ~u); }
 
 // true when every lane of the wave is active and carries the same scene b >= 0: one lane then speaks for all
 __device__ inline bool wave_uniform(int b, bool active) {
@@ -77,7 +51,7 @@ __global__ __launch_bounds__(kThreads) void tf_box_kernel(const double* __restri
                                                           unsigned long long* box) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool in = i < n;
-  const int b = in ? scene_of(offs, B, i) : -1;
+  const int b = in ? segment_of(offs, B, i) : -1;
   double p[3] = {0.0, 0.0, 0.0};
   bool ok = false;
   if (b >= 0) {
@@ -121,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void tf_point_kernel(const double* __rest
                                                             int32_t* flags) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool in = i < n;
-  const int b = in ? scene_of(offs, B, i) : -1;
+  const int b = in ? segment_of(offs, B, i) : -1;
   bool kept = false;
   int v[3] = {INT_MAX, INT_MAX, INT_MAX};
   if (b >= 0) {
@@ -149,10 +123,11 @@ __global__ __launch_bounds__(kThreads) void tf_point_kernel(const double* __rest
       }
     }
     if (ok) {
-      const double* m = mats + 16 * b;
+      double t[3];
+      rigid_apply(mats + 16 * b, 4, p, t);
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const double f = floor(add_rn(add_rn(add_rn(mul_rn(p[0], m[4 * r]), mul_rn(p[1], m[4 * r + 1])), mul_rn(p[2], m[4 * r + 2])), m[4 * r + 3]));
+        const double f = floor(t[r]);
         if (!(fabs(f) < (double)kVoxelLimit)) {  // NaN included
           bad = true;
           ok = false;
@@ -203,15 +178,6 @@ __global__ __launch_bounds__(kThreads) void tf_final_kernel(const double* __rest
 }
 
 // ---- quantize --------------------------------------------------------------------------------------------------------------
-__device__ inline uint32_t claim_slot(uint64_t* keys, uint32_t mask, uint64_t key) {
-  uint32_t slot = hash_key(key) & mask;
-  while (true) {  // ends: the table has at least twice as many slots as there are rows
-    const unsigned long long prev = atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)kEmptyKey, (unsigned long long)key);
-    if (prev == kEmptyKey || prev == key) return slot;
-    slot = (slot + 1) & mask;
-  }
-}
-
 // pass 1: the row's voxel claims its slot; first[slot] = the lowest row of the voxel
 __global__ __launch_bounds__(kThreads) void q_insert_kernel(const int32_t* __restrict__ vox, const uint8_t* __restrict__ keep, int64_t n,
                                                             const int64_t* __restrict__ offs, int B, const int32_t* __restrict__ scene_min,
@@ -220,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void q_insert_kernel(const int32_t* __res
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   uint32_t slot = kNoSlot;
-  const int b = scene_of(offs, B, i);
+  const int b = segment_of(offs, B, i);
   if (b >= 0 && (!keep || keep[i])) {
     int64_t d[3];
     bool ok = true;
@@ -230,7 +196,7 @@ __global__ __launch_bounds__(kThreads) void q_insert_kernel(const int32_t* __res
       ok = ok && d[a] >= 0 && d[a] < kSpan;
     }
     if (ok) {
-      slot = claim_slot(keys, mask, pack_key(b, (int)d[0] - kCoordBias, (int)d[1] - kCoordBias, (int)d[2] - kCoordBias));
+      slot = claim_slot(keys, 0, mask + 1, pack_key(b, (int)d[0] - kCoordBias, (int)d[1] - kCoordBias, (int)d[2] - kCoordBias));
       atomicMin(&first[slot], (uint32_t)i);
     } else {
       atomicOr(&flags[b], PCMI_SEG_FLAG_SPAN);
@@ -271,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void q_write_kernel(const int32_t* __rest
     }
   }
   if (i >= n || !is_first[i]) return;
-  const int b = scene_of(offs, B, i);
+  const int b = segment_of(offs, B, i);
   const int64_t p = pos[i];
   coords[4 * p] = b;
 #pragma unroll
@@ -291,19 +257,6 @@ static size_t scan_temp_bytes(int64_t items) {
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)items);
   return align_up(b + 256, 256);
 }
-
-struct Carve {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
 
 // ---- flip, colour, label map -------------------------------------------------------------------------------------------------
 // ws of pcmi_seg_color_augment: per scene 9 words -- max x, y, z (int32), then the order images of min r, g, b and max r, g, b
@@ -481,7 +434,7 @@ __global__ __launch_bounds__(kThreads) void el_apply_kernel(double* __restrict__
                                                             const double* __restrict__ grid_min) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
-  const int b = scene_of(offs, B, i);
+  const int b = segment_of(offs, B, i);
   if (b < 0 || !grid_dims[4 * b + 3]) return;
   const int cap[3] = {cx, cy, cz};
 #pragma unroll

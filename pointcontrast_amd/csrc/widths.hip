@@ -44,19 +44,6 @@ static int pad2d(const float* src, int64_t src_ld, int64_t rows_src, int c_src, 
   return PCMI_OK;
 }
 
-struct Carve {  // bump allocator over the caller's workspace (256-byte aligned pieces)
-  char* p;
-  size_t left;
-  float* take(size_t n_floats) {
-    const size_t b = align_up(n_floats * sizeof(float), 256);
-    if (b > left) return nullptr;
-    float* r = (float*)p;
-    p += b;
-    left -= b;
-    return r;
-  }
-};
-
 static bool needs_padding(int cin, int cout) { return cin >= 8 && (cin % 32 != 0 || cout % 32 != 0); }
 
 static size_t pad_bytes(int64_t n_in, int64_t n_out, int cin, int cout, int K) {
@@ -75,10 +62,10 @@ int spconv_forward(const float* in, int64_t in_ld, int64_t n_in, int cin, const 
   PCMI_REQUIRE(in && weight && out, PCMI_ERR_INVALID, "spconv_fwd: null argument");
   const int K = map ? map->K : 1, Cp = up32(cin), Np = up32(cout);
   Carve cv{(char*)ws, ws ? ws_bytes : 0};
-  float* wp = cv.take((size_t)K * Cp * Np);
-  float* bp = bias ? cv.take(Np) : nullptr;
-  float* xp = Cp != cin ? cv.take((size_t)n_in * Cp) : nullptr;
-  float* yp = Np != cout ? cv.take((size_t)n_out * Np) : nullptr;
+  float* wp = (float*)cv.take((size_t)K * Cp * Np * sizeof(float));
+  float* bp = bias ? (float*)cv.take(Np * sizeof(float)) : nullptr;
+  float* xp = Cp != cin ? (float*)cv.take((size_t)n_in * Cp * sizeof(float)) : nullptr;
+  float* yp = Np != cout ? (float*)cv.take((size_t)n_out * Np * sizeof(float)) : nullptr;
   PCMI_REQUIRE(wp && (!bias || bp) && (Cp == cin || xp) && (Np == cout || yp), PCMI_ERR_WORKSPACE,
                "spconv_fwd: workspace too small for the padded widths (%d -> %d)", cin, cout);
   int rc = pad2d(weight, cout, cin, cout, (int64_t)cin * cout, wp, Np, Cp, Np, (int64_t)Cp * Np, K, 0, st);
@@ -101,9 +88,9 @@ int spconv_backward_data(const float* gout, int64_t gout_ld, int64_t n_out, int 
   PCMI_REQUIRE(gout && weight && gin, PCMI_ERR_INVALID, "spconv_bwd_data: null argument");
   const int K = map ? map->K : 1, Cp = up32(cin), Np = up32(cout);
   Carve cv{(char*)ws, ws ? ws_bytes : 0};
-  float* wp = cv.take((size_t)K * Cp * Np);
-  float* gp = Np != cout ? cv.take((size_t)n_out * Np) : nullptr;
-  float* dxp = Cp != cin ? cv.take((size_t)n_in * Cp) : nullptr;
+  float* wp = (float*)cv.take((size_t)K * Cp * Np * sizeof(float));
+  float* gp = Np != cout ? (float*)cv.take((size_t)n_out * Np * sizeof(float)) : nullptr;
+  float* dxp = Cp != cin ? (float*)cv.take((size_t)n_in * Cp * sizeof(float)) : nullptr;
   PCMI_REQUIRE(wp && (Np == cout || gp) && (Cp == cin || dxp), PCMI_ERR_WORKSPACE,
                "spconv_bwd_data: workspace too small for the padded widths (%d -> %d)", cin, cout);
   int rc = pad2d(weight, cout, cin, cout, (int64_t)cin * cout, wp, Np, Cp, Np, (int64_t)Cp * Np, K, 0, st);
@@ -125,10 +112,10 @@ int spconv_backward_weight(const float* in, int64_t in_ld, int64_t n_in, int cin
   PCMI_REQUIRE(in && gout && gweight, PCMI_ERR_INVALID, "spconv_bwd_weight: null argument");
   const int K = map ? map->K : 1, Cp = up32(cin), Np = up32(cout);
   Carve cv{(char*)ws, ws ? ws_bytes : 0};
-  float* gwp = cv.take((size_t)K * Cp * Np);
-  float* gbp = gbias ? cv.take(Np) : nullptr;
-  float* xp = Cp != cin ? cv.take((size_t)n_in * Cp) : nullptr;
-  float* gp = Np != cout ? cv.take((size_t)n_out * Np) : nullptr;
+  float* gwp = (float*)cv.take((size_t)K * Cp * Np * sizeof(float));
+  float* gbp = gbias ? (float*)cv.take(Np * sizeof(float)) : nullptr;
+  float* xp = Cp != cin ? (float*)cv.take((size_t)n_in * Cp * sizeof(float)) : nullptr;
+  float* gp = Np != cout ? (float*)cv.take((size_t)n_out * Np * sizeof(float)) : nullptr;
   PCMI_REQUIRE(gwp && (!gbias || gbp) && (Cp == cin || xp) && (Np == cout || gp), PCMI_ERR_WORKSPACE,
                "spconv_bwd_weight: workspace too small for the padded widths (%d -> %d)", cin, cout);
   int rc = PCMI_OK;

@@ -91,3 +91,18 @@ def test_reference_dataset_with_device_geometry(tmp_path):
   for x, y in zip(*items):
     assert np.asarray(x).shape == np.asarray(y).shape and (np.asarray(x) == np.asarray(y)).all()
   assert len(items[0][6]) > 10000
+
+
+def test_matches_on_the_radius_are_the_oracles():
+  """Every (i, i) pair of the boundary fixture lies on the radius up to round-off (test_oracle_loader shows that the
+  oracle keeps about half of them and that a fused evaluation decides hundreds differently): the device's pairs are the
+  oracle's, exactly."""
+  from oracle import loader_ref as lf
+  from pointcontrast_amd.lib import device_loader as dl
+  from test_oracle_loader import boundary_fixture
+  p, T, q, r = boundary_fixture()
+  got = dl.get_matching_indices(p, q, T, r)
+  want = lf.match_radius(p, T, q, r)
+  gs, ws = set(map(tuple, got.tolist())), set(map(tuple, want.tolist()))
+  print("device %d pairs, oracle %d pairs, %d in one set only" % (len(got), len(want), len(gs ^ ws)))
+  assert got.shape == want.shape and (got == want).all()

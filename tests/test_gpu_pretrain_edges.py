@@ -137,6 +137,22 @@ def test_segments_and_origin_with_sparse_batch_indices(ME, counts):
   assert okey.tensor_stride == 0 and origin.tolist() == [[0, 0, 0, 0], [511, 0, 0, 0], [1022, 0, 0, 0]]
 
 
+def test_segments_with_every_batch_index_in_use(ME):
+  """pcmi_coords_segments with all 1023 admissible batch indices present (1 to 3 rows each, interleaved; bin 1023 is the
+  one the insert refuses): every wave of the one-workgroup scan over the 1024 bins carries a count into the next."""
+  rng = np.random.RandomState(7)
+  batch = rng.permutation(np.repeat(np.arange(1023), rng.randint(1, 4, 1023))).astype(np.int32)
+  n = len(batch)
+  coords = np.stack([batch, np.arange(n, dtype=np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)], 1)
+  st = _device_tensor(ME, coords, np.zeros((n, 4), np.float32))
+  seg = st.coords_man.segments(st.coords_key)
+  want = er.segments_ref(batch)
+  assert int(seg.n) == n and int(seg.n_inst) == want["n_inst"] == 1023
+  assert (_read_i32(seg.rows, n) == want["rows"]).all()
+  assert (_read_i32(seg.offs, 1024) == want["offs"]).all()
+  assert (_read_i32(seg.inst, n) == want["inst"]).all()
+
+
 # ------------------------------------------------------------------------------------------------
 # B. pdist_argmin: every instantiation, tile boundaries, exact ties, non-finite rows
 # ------------------------------------------------------------------------------------------------
