@@ -1590,6 +1590,85 @@ int pcmi_pnce_bwd(const float* q, const float* k, const int32_t* xyz, const int3
 int pcmi_pnce_partition(const int32_t* xyz, const int32_t* scene, int64_t n, int n_scenes, int64_t r1_sq, int64_t r2_sq, int A,
                         int E, int8_t* part, pcmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Instance segmentation (csrc/cluster.hip) -- the downstream task of Hou et al., "Contrastive Scene Contexts", in PointGroup's
+ * recipe, stated here (the reference has no counterpart): the network predicts a class and an offset to its instance's centre
+ * per voxel, the voxels are shifted by their offsets, and shifted voxels of one class within a radius of each other are grouped.
+ * Every call: one stream, no host synchronisation; a refused call enqueues nothing; integer atomics only, float64 sums in a
+ * fixed order: every output is the same bits from run to run.  Every `offs` is DEVICE int64 [B + 1], ascending, inside [0, n]:
+ * scene b holds the rows [offs[b], offs[b + 1]) (empty scenes allowed).  n == 0 reads nothing.
+ *
+ * pcmi_radius_components = the connected components of a radius graph.  xyz [n, 3] (fp32, leading dimension ld >= 3 floats),
+ *   group [n] (int32), r > 0 and finite (PCMI_ERR_INVALID otherwise).  A row is ACTIVE if it lies in a scene, group >= 0, its
+ *   three coordinates are finite and |floor(x / r)| < 2^20 on every axis (x widened to fp64, the quotient rounded once).  Two
+ *   active rows i != j are joined by an edge if they share their scene and their group and
+ *     d2 = (dx dx + dy dy) + dz dz <= r r,   d = p_i - p_j,
+ *   the coordinates widened to fp64 and every difference, product and sum rounded on its own (dist2_rn / mul_rn of
+ *   csrc/exact.h: the rule of the radius probe).  label [n] (int32) = the LOWEST row of the row's connected component, -1 for a
+ *   row that is not active.  dropped [1] (int64, nullable) += the finite in-scene rows with group >= 0 whose cell does not fit.
+ *   Against PointGroup's ball query + breadth-first search: no cap on the neighbours of a row (theirs: 50, which makes the
+ *   result depend on the row order) and <= where they have <.  This rule defines the result for every input: it equals a
+ *   brute-force scan of all pairs.
+ *   The rows are binned into cells of side r (1 + 2^-30) (the margin makes the 27 cells around a row hold every neighbour: see
+ *   the source) in an open-addressing table with one segment per scene; one lane per binned row unites itself, in a lock-free
+ *   union-find kept in `label`, first with the first row of its own cell and then with every lower row in the 27 cells that
+ *   passes the test.  A root is only ever hooked under a smaller root (compare-and-swap), so parent[i] <= i always, every walk
+ *   descends, every retry lowers the larger root, nothing waits for another lane, and the final root is the component's lowest
+ *   row whatever the interleaving.  1 <= B <= 2^20; n <= 2^29 (PCMI_ERR_UNSUPPORTED beyond: 2 n + B table slots, int32 rows).
+ *   ws: pcmi_radius_components_workspace_bytes(n, B), 16-byte aligned.
+ * pcmi_components_compact: label [n] as above (any value outside [0, n) is a row of no component), group [n] (nullable) ->
+ *   the components with at least min_points >= 1 rows, numbered 0 .. P - 1 in ascending order of their lowest row (scene-major,
+ *   the rows being so).  inst [n] (int32) = the row's number, -1 for every other row; count [1] (int32) = P, the true number even
+ *   beyond max_inst: components numbered >= max_inst are written nowhere and their rows get -1.  inst_root / inst_size /
+ *   inst_scene / inst_group [max_inst] (int32) = the component's lowest row, its rows, the scene and the group of that row;
+ *   entries from min(P, max_inst) on are -1 (size: 0).  Sizes by integer atomics, the numbering by a scan in row order.
+ *   ws: pcmi_components_compact_workspace_bytes(n), 4-byte aligned.
+ * pcmi_instance_scores: out [P] (fp64) = the mean of score [n] (fp32) over the rows with inst == k, in fixed point:
+ *   q = (int64) rint((double) min(max(score, 0), 1) 2^30), a non-finite score counting as 0, summed by 64-bit integer atomics;
+ *   out = (double) sum / ((double) inst_size[k] 2^30), 0 where inst_size[k] <= 0.  Ids outside [0, P) count nowhere.
+ *   ws: pcmi_instance_scores_workspace_bytes(P), 8-byte aligned.
+ * pcmi_instance_overlap: pred_inst / gt_inst [n] (int32) -> inter [P, G], pred_size [P], gt_size [G] (int32), all zeroed by the
+ *   call: the rows per id and per pair of ids; an id outside [0, P) / [0, G) counts nowhere.  P G < 2^31.
+ * pcmi_instance_match: per predicted instance the ground-truth instance g with gt_scene[g] == pred_scene[p] and gt_class[g] ==
+ *   pred_class[p] that maximises inter / (pred_size + gt_size - inter), the quotient of the two integers in fp64 (0 where the
+ *   denominator is 0), the LOWEST g among equal quotients; best_gt [P] (int32) = g, best_iou [P] (fp32) = the quotient rounded
+ *   once; -1 and -inf without such a g: the contract of pcmi_det_match, so pcmi_det_ap consumes the result unchanged.
+ * pcmi_instance_centroids: coords [n, 4] (int32: b, x, y, z), inst [n] -> sum [G, 3] (int64) = the sums of x, y, z over the
+ *   rows with inst == k and cnt [G] (int64) their number, both zeroed by the call; ids outside [0, G) count nowhere.
+ * pcmi_offset_loss_fwd / _bwd: PointGroup's two offset losses on p [n, 3] (fp32, leading dimension ld: a column slice of the
+ *   logits), g [n, 3] (fp32, contiguous: the targets) and inst [n] (a row is valid iff inst >= 0), V = the valid rows:
+ *     norm = sum_valid ((|p0 - g0| + |p1 - g1|) + |p2 - g2|) / (V + 1e-6)
+ *     dir  = sum_valid -((gh0 ph0 + gh1 ph1) + gh2 ph2) / (V + 1e-6),   gh = g / (|g| + 1e-8), ph = p / (|p| + 1e-8),
+ *     |v| = sqrt((v0 v0 + v1 v1) + v2 v2),
+ *   per row in fp64 from the fp32 inputs, every operation rounded on its own in this order; the sums are fp64 partials per 256
+ *   rows merged in a fixed order.  out3 [3] (fp64) = norm, dir, V.  _bwd: dp [n, 3] (fp32, leading dimension dp_ld) =
+ *   (gloss2[0] sign(p - g) + gloss2[1] d(row's dir term)/dp) / (V + 1e-6) rounded once, 0 for an invalid row; sign(0) = 0 and the
+ *   gradient of |p| at p = 0 is 0 (torch's conventions).  gloss2 [2] (fp64, device): the two upstream gradients; out3 as _fwd
+ *   wrote it.  ws: pcmi_offset_loss_workspace_bytes(n), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+size_t pcmi_radius_components_workspace_bytes(int64_t n, int64_t B);
+int pcmi_radius_components(const float* xyz, int64_t ld, int64_t n, const int64_t* offs, int64_t B, const int32_t* group, double r,
+                           int32_t* label, int64_t* dropped, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_components_compact_workspace_bytes(int64_t n);
+int pcmi_components_compact(const int32_t* label, const int64_t* offs, int64_t B, int64_t n, const int32_t* group, int min_points,
+                            int64_t max_inst, int32_t* inst, int32_t* count, int32_t* inst_root, int32_t* inst_size,
+                            int32_t* inst_scene, int32_t* inst_group, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_instance_scores_workspace_bytes(int64_t P);
+int pcmi_instance_scores(const float* score, const int32_t* inst, int64_t n, int64_t P, const int32_t* inst_size, double* out,
+                         void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_instance_overlap(const int32_t* pred_inst, const int32_t* gt_inst, int64_t n, int64_t P, int64_t G, int32_t* inter,
+                          int32_t* pred_size, int32_t* gt_size, pcmi_stream_t stream);
+int pcmi_instance_match(const int32_t* inter, const int32_t* pred_size, const int32_t* gt_size, const int32_t* pred_scene,
+                        const int32_t* pred_class, const int32_t* gt_scene, const int32_t* gt_class, int64_t P, int64_t G,
+                        int32_t* best_gt, float* best_iou, pcmi_stream_t stream);
+int pcmi_instance_centroids(const int32_t* coords, const int32_t* inst, int64_t n, int64_t G, int64_t* sum, int64_t* cnt,
+                            pcmi_stream_t stream);
+size_t pcmi_offset_loss_workspace_bytes(int64_t n);
+int pcmi_offset_loss_fwd(const float* p, int64_t ld, const float* g, const int32_t* inst, int64_t n, double* out3, void* ws,
+                         size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_offset_loss_bwd(const float* p, int64_t ld, const float* g, const int32_t* inst, int64_t n, const double* out3,
+                         const double* gloss2, float* dp, int64_t dp_ld, pcmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -302,6 +302,19 @@ PROTOTYPES = {
     "pcmi_pnce_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_f32, c_i64, c_i64, C.c_int, C.c_int,
                                 c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_pnce_partition": (C.c_int, [c_vp, c_vp, c_i64, C.c_int, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp]),
+    "pcmi_radius_components_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_radius_components": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, C.c_double, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_components_compact_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_components_compact": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                          c_vp]),
+    "pcmi_instance_scores_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_instance_scores": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_instance_overlap": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "pcmi_instance_match": (C.c_int, [c_vp] * 7 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pcmi_instance_centroids": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pcmi_offset_loss_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_offset_loss_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_offset_loss_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

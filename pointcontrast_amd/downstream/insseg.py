@@ -1,0 +1,221 @@
+"""Instance-segmentation fine-tuning on the pre-training backbone: the third downstream task of Hou et al., "Exploring
+Data-Efficient 3D Scene Understanding with Contrastive Scene Contexts", in PointGroup's recipe (Jiang et al., "PointGroup:
+Dual-Set Point Grouping for 3D Instance Segmentation").  The reference has no counterpart; the rules are include/pcmi.h's.
+
+  model       the SAME sparse U-Net with num_labels + 3 outputs: a class and a 3-vector offset to the instance centre per voxel
+  loss        cross-entropy on logits[:, :C] (pcmi_softmax_ce_*) + PointGroup's two offset losses on logits[:, C:C + 3]
+              (pcmi_offset_loss_*) against centroid - voxel in metres (pcmi_instance_centroids: exact integer sums)
+  clustering  voxels shifted by their offsets; shifted voxels of one class within `radius` of each other are one instance:
+              connected components of a radius graph (pcmi_radius_components, a lock-free union-find over a cell hash grid),
+              pcmi_components_compact, pcmi_instance_scores -> cluster_instances
+  metrics     mask AP at IoU 0.25, 0.5 and 0.5:0.95:0.05 (pcmi_instance_overlap, pcmi_instance_match, pcmi_det_ap)
+              -> InstanceEvaluator
+
+Stated differences from PointGroup: no cap on the neighbours of a row (theirs: 50, which makes the result
+depend on the row order), <= radius where they have <, ONE clustering on the shifted coordinates (no second one on the
+unshifted ones) and no ScoreNet (an instance's score is the mean softmax probability of its rows for their class).  The
+AP is VOC-style -- each prediction is matched to its best ground truth, the rule of APCalculator -- and NOT ScanNet's
+benchmark script, which has void-overlap and minimum-region rules.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from .. import functional as PF
+from .semseg import SegmentationTrainer, precision_at_one
+
+# 0.25, then 0.50, 0.55, ... 0.95
+AP_THRESHOLDS = (0.25,) + tuple((10 + k) / 20.0 for k in range(10))
+
+
+def scene_offsets_of(coords):
+  """int64 [B + 1] on coords' device: the row offsets of the scenes of coords [n, 4] (batch index first, rows scene-major as
+  the collate functions leave them).  B comes from the last row: free for a host tensor, one read-back for a device one."""
+  b = coords[:, 0].contiguous()
+  B = int(b[-1]) + 1 if b.numel() else 1
+  return torch.searchsorted(b, torch.arange(B + 1, dtype=b.dtype, device=b.device)).to(torch.int64)
+
+
+def cluster_instances(coords, offsets, logits, scene_offsets, voxel_size, radius=0.03, min_points=50, stuff_classes=(0, 1),
+                      max_instances=4096, shifted=True):
+  """Instances from a network's output, on the device without a read-back.  coords int32 [n, 4] (b, x, y, z; rows scene-major),
+  offsets float32 [n, 3] (predicted offsets in metres; may be a column slice), logits float32 [n, C] (may be a column slice),
+  scene_offsets [B + 1].  The semantic arg-max (the lowest class of equal logits) is the row's group, -1 for stuff_classes;
+  xyz = coords[:, 1:4] voxel_size (+ offsets if shifted) in float32; then radius_components -> components_compact (at least
+  min_points rows, numbered by lowest row) -> instance_scores of the row's softmax probability of its own class.
+  radius 0.03, min_points 50 and the two stuff classes (ScanNet's wall and floor) are PointGroup's numbers, untuned here.
+  Returns device tensors: instance int32 [n] (-1: in none), count int32 [1] (the true number, also beyond max_instances),
+  inst_class, inst_size, inst_scene int32 [max_instances] (-1 / 0 from the count on), inst_score float64 [max_instances], and
+  scene_offsets int64 [B + 1] as given."""
+  PF.require_cuda(logits, "cluster_instances")
+  dev = logits.device
+  n, C = logits.shape
+  c = coords.to(device=dev, dtype=torch.int32)
+  offs = torch.as_tensor(scene_offsets).to(device=dev, dtype=torch.int64).contiguous()
+  rows = PF.seg_eval_rows(logits, torch.full((n,), -1, dtype=torch.int32, device=dev), -1)
+  pred = rows["pred"]
+  score = rows["prob_t"].gather(0, pred.long().reshape(1, n)).reshape(n) if n else torch.zeros(0, dtype=torch.float32, device=dev)
+  group = pred
+  for s in stuff_classes:
+    group = torch.where(pred == int(s), torch.full_like(pred, -1), group)
+  xyz = c[:, 1:4].to(torch.float32) * float(voxel_size)
+  if shifted:
+    xyz = xyz + offsets.to(device=dev, dtype=torch.float32)
+  label = PF.radius_components(xyz, offs, group, radius)
+  out = PF.components_compact(label, offs, group, min_points, max_instances)
+  return dict(instance=out["instance"], count=out["count"], inst_class=out["group"], inst_size=out["size"], inst_scene=out["scene"],
+              inst_score=PF.instance_scores(score, out["instance"], out["size"]), scene_offsets=offs)
+
+
+class InstanceSegmentationTrainer(SegmentationTrainer):
+  """SegmentationTrainer with a head of num_labels + 3 outputs.  train_iter(coords, feats, target, instance) = forward,
+  cross-entropy + the two offset losses, ONE backward, SGD + PolyLR step; predict(coords, feats) = cluster_instances of the
+  inference forward.  An inference forward returns the num_labels class columns, so evaluate / validate /
+  test_original_pointcloud of the parent score the semantic head unchanged.  A pre-training checkpoint loads as in the parent:
+  by name and shape, so the head stays random.  **Nobody has trained a network with this head to a benchmark number yet.**"""
+
+  def __init__(self, num_labels, voxel_size=0.02, radius=0.03, min_points=50, stuff_classes=(0, 1), max_instances=4096, **kw):
+    super().__init__(num_labels + 3, **kw)
+    self.num_labels = num_labels  # the classes; the model has num_labels + 3 outputs
+    self.voxel_size, self.radius, self.min_points = float(voxel_size), float(radius), int(min_points)
+    self.stuff_classes, self.max_instances = tuple(stuff_classes), int(max_instances)
+    self._full_width = False
+
+  def forward(self, coords, feats, training=True):
+    out = super().forward(coords, feats, training)
+    return out if (training or self._full_width) else out[:, :self.num_labels]
+
+  def offset_targets(self, coords, instance, n_instances):
+    """float32 [n, 3]: centroid of the row's instance - the row's voxel, in metres (rows with instance < 0: unused)."""
+    c = coords.to(device=self.device, dtype=torch.int32).contiguous()
+    inst = instance.to(device=self.device, dtype=torch.int32)
+    s, cnt = PF.instance_centroids(c, inst, n_instances)
+    centre = s.double() / cnt.clamp(min=1).double().reshape(-1, 1)
+    picked = centre[inst.clamp(min=0).long()] if n_instances else torch.zeros((c.shape[0], 3), dtype=torch.float64, device=self.device)
+    return ((picked - c[:, 1:4].double()) * self.voxel_size).float()
+
+  def train_iter(self, coords, feats, target, instance, n_instances=None):
+    """instance [n]: the row's ground-truth instance as an index into the batch's instances (unique across its scenes), -1 for
+    none; n_instances: their number (None: instance.max() + 1, free for a host tensor)."""
+    self.model.train()
+    self.optimizer.zero_grad()
+    C = self.num_labels
+    if torch.is_tensor(target) and not target.is_cuda and target.numel():  # free on the host; as torch's CrossEntropyLoss
+      bad = (target != self.ignore_label) & ((target < 0) | (target >= C))
+      if bool(bad.any()):
+        raise IndexError("Target %d is out of bounds (classes 0..%d, ignore label %d)" % (int(target[bad][0]), C - 1, self.ignore_label))
+    if n_instances is None:
+      n_instances = int(instance.max()) + 1 if instance.numel() else 0
+    logits = self.forward(coords, feats).requires_grad_(True)
+    tgt = target.to(self.device)
+    inst = instance.to(device=self.device, dtype=torch.int32)
+    goal = self.offset_targets(coords, inst, max(int(n_instances), 0))
+    loss_sem = PF.SoftmaxCrossEntropyFunction.apply(logits[:, :C], tgt, self.ignore_label)
+    loss_norm, loss_dir = PF.OffsetLossFunction.apply(logits[:, C:C + 3], goal, inst)
+    loss = loss_sem + loss_norm + loss_dir
+    loss.backward()
+    self.engine.backward(0, logits.grad)
+    self.optimizer.step()
+    self.scheduler.step()
+    self.curr_iter += 1
+    pred = logits.detach()[:, :C].max(1)[1]
+    return {"loss": loss.detach(), "loss_sem": loss_sem.detach(), "loss_norm": loss_norm.detach(), "loss_dir": loss_dir.detach(),
+            "score": precision_at_one(pred, tgt, self.ignore_label), "pred": pred}
+
+  @torch.no_grad()
+  def predict(self, coords, feats):
+    """cluster_instances of the inference forward (eval mode): its dict."""
+    self.model.eval()
+    self._full_width = True
+    try:
+      out = self.forward(coords, feats, training=False)
+    finally:
+      self._full_width = False
+    C = self.num_labels
+    return cluster_instances(coords, out[:, C:C + 3], out[:, :C], scene_offsets_of(coords), self.voxel_size, self.radius, self.min_points,
+                             self.stuff_classes, self.max_instances)
+
+
+class InstanceEvaluator:
+  """Mask AP of predicted instances (cluster_instances' dict) against ground-truth instances, accumulated on the device.
+
+  step(pred, gt_instance, gt_class) adds one batch: pcmi_instance_overlap and pcmi_instance_match (per prediction its best
+  ground-truth instance of the same scene and class).  compute_metrics() sorts every prediction by (class, descending score)
+  with a stable torch.sort, runs PF.det_ap ONCE for all thresholds and reads back once.  This is VOC-style matching, the rule
+  APCalculator already uses -- NOT ScanNet's benchmark script, which has void-overlap and minimum-region rules."""
+
+  def __init__(self, num_labels, stuff_classes=(0, 1), thresholds=AP_THRESHOLDS, device=None):
+    self.num_labels, self.stuff_classes = int(num_labels), tuple(int(s) for s in stuff_classes)
+    self.thresholds = tuple(float(t) for t in thresholds)
+    self.device = None if device is None else torch.device(device)
+    self.reset()
+
+  def reset(self):
+    self._iou, self._gid, self._cls, self._score, self.npos, self.n_gt = [], [], [], [], None, 0
+
+  def step(self, pred, gt_instance, gt_class, n_instances=None):
+    """pred: cluster_instances' dict; gt_instance [n]: the row's ground-truth instance as an index into the batch's instances,
+    -1 for none; gt_class [n]: the row's ground-truth class (an instance takes the largest class among its rows; instances of
+    stuff_classes or of a class outside [0, num_labels) are not scored).  n_instances None: gt_instance.max() + 1."""
+    dev = pred["instance"].device
+    if self.device is None:
+      self.device = dev
+    gi_any = torch.as_tensor(gt_instance).reshape(-1)
+    G = int(n_instances) if n_instances is not None else (int(gi_any.max()) + 1 if gi_any.numel() else 0)
+    G = max(G, 0)
+    gi = gi_any.to(device=dev, dtype=torch.int64)
+    gc = torch.as_tensor(gt_class).reshape(-1).to(device=dev, dtype=torch.int64)
+    n, C = gi.shape[0], self.num_labels
+    row_scene = torch.searchsorted(pred["scene_offsets"], torch.arange(n, device=dev), right=True) - 1
+    ok = (gi >= 0) & (gi < G)
+    cls = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], gc[ok], "amax", include_self=True)
+    scene = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], row_scene[ok], "amax", include_self=True)
+    scored = (cls >= 0) & (cls < C)
+    for s in self.stuff_classes:
+      scored = scored & (cls != s)
+    cls = torch.where(scored, cls, torch.full_like(cls, -1))
+    P = pred["inst_size"].shape[0]
+    inter, ps, gs = PF.instance_overlap(pred["instance"], gi, P, G)
+    best_gt, best_iou = PF.instance_match(inter, ps, gs, pred["inst_scene"], pred["inst_class"], scene, cls)
+    self._iou.append(best_iou)
+    self._gid.append(torch.where(best_gt >= 0, best_gt + self.n_gt, best_gt))
+    self._cls.append(pred["inst_class"])
+    self._score.append(pred["inst_score"])
+    npos = torch.bincount(cls[scored], minlength=C)[:C]
+    self.npos = npos if self.npos is None else self.npos + npos
+    self.n_gt += G
+
+  def compute_metrics(self, keep_curves=False):
+    """One read-back.  AP (the mean over 0.50:0.95:0.05), AP50, AP25: nanmeans over the classes with ground truth of
+    ap_class / ap50_class / ap25_class (per class, NaN without ground truth); ap [T, classes]; n_gt per class.  keep_curves:
+    self.last_ap keeps det_ap's device tensors (rec, prec, tp [T, nd]) and `order`, the accumulated predictions in list order."""
+    C, T = self.num_labels, len(self.thresholds)
+    if not self._iou:
+      nan = np.full(C, np.nan)
+      return dict(AP=float("nan"), AP50=float("nan"), AP25=float("nan"), ap_class=nan, ap50_class=nan.copy(), ap25_class=nan.copy(),
+                  n_gt=np.zeros(C, np.int64), ap=np.full((T, C), np.nan))
+    iou, gid, cls, score = torch.cat(self._iou), torch.cat(self._gid), torch.cat(self._cls).long(), torch.cat(self._score)
+    cls = torch.where((cls >= 0) & (cls < C), cls, torch.full_like(cls, C))  # unused slots and foreign classes: behind every range
+    by_score = torch.sort(score, descending=True, stable=True).indices
+    order = by_score[torch.sort(cls[by_score], stable=True).indices]
+    cls_offs = torch.searchsorted(cls[order].contiguous(), torch.arange(C + 1, device=cls.device)).to(torch.int32)
+    out = PF.det_ap(iou[order], gid[order].to(torch.int32), cls_offs, self.npos.to(torch.int32), self.n_gt, self.thresholds,
+                    curves=keep_curves)
+    self.last_ap = dict(out, order=order) if keep_curves else None
+    flat = torch.cat([out["ap"].reshape(-1), self.npos.double()]).cpu().numpy()
+    ap, n_gt = flat[:T * C].reshape(T, C), np.rint(flat[T * C:]).astype(np.int64)
+    ap[:, n_gt == 0] = np.nan
+    thr = np.asarray(self.thresholds)
+    coco = thr >= 0.5 - 1e-9
+
+    def at(t):
+      hit = np.flatnonzero(np.abs(thr - t) < 1e-9)
+      return ap[hit[0]] if len(hit) else np.full(C, np.nan)
+
+    with warnings.catch_warnings():  # a class that never occurred: nanmean of nothing but NaN
+      warnings.simplefilter("ignore", category=RuntimeWarning)
+      ap_class = ap[coco].mean(0) if coco.any() else np.full(C, np.nan)
+      ap50, ap25 = at(0.5), at(0.25)
+      return dict(AP=float(np.nanmean(ap_class)), AP50=float(np.nanmean(ap50)), AP25=float(np.nanmean(ap25)), ap_class=ap_class,
+                  ap50_class=ap50, ap25_class=ap25, n_gt=n_gt, ap=ap)

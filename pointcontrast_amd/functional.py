@@ -2164,3 +2164,147 @@ def view_visible(points, w2c, fx, fy, cx, cy, zbuf, z_near=0.1, z_far=10.0, rel_
   if rows.shape[0]:
     check(lib.pcmi_views_rows(ptr(mask), ptr(start), n, F, ptr(rows), cur_stream(dev)))
   return rows, offsets, offs_np, pixels, mask
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Instance segmentation (csrc/cluster.hip; the rules are include/pcmi.h's): radius components of the shifted voxels, their
+# compaction into instances, per-instance scores, overlap / matching for pcmi_det_ap, integer centroids, the offset losses.
+# Only OffsetLossFunction is differentiable; nothing synchronises.
+# ---------------------------------------------------------------------------------------------------------------------
+def _xyz_rows(xyz, who):
+  require_cuda(xyz, who)
+  assert xyz.dim() == 2 and xyz.shape[1] == 3, "%s: [n, 3]" % who
+  x = xyz if xyz.dtype == torch.float32 else xyz.float()
+  return x if (x.stride(1) == 1 and x.stride(0) >= 3) or x.shape[0] == 0 else x.contiguous()
+
+
+def radius_components(xyz, offsets, group, radius, dropped=None):
+  """pcmi_radius_components: xyz float32 [n, 3] (rows may be a column slice), offsets [B + 1] (ascending row offsets of the
+  scenes), group [n] -> label int32 [n]: the LOWEST row of the connected component of the row in the graph whose edges join
+  rows of one scene and one group with (dx dx + dy dy) + dz dz <= radius radius in float64; -1 for a row outside every scene,
+  with group < 0, a non-finite coordinate or |floor(x / radius)| >= 2^20.  dropped int64 [1] (optional) += the rows lost to
+  the last condition."""
+  x = _xyz_rows(xyz, "radius_components")
+  dev = x.device
+  offs, g = _offsets(offsets, dev), _i32c(group, dev).reshape(-1)
+  n, B = x.shape[0], offs.shape[0] - 1
+  assert offs.dim() == 1 and B >= 1 and g.shape[0] == n, "radius_components: offsets [B + 1], group [n]"
+  assert dropped is None or (dropped.dtype == torch.int64 and dropped.numel() == 1 and dropped.device == dev), \
+      "radius_components: dropped int64 [1]"
+  label = torch.empty(n, dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_radius_components_workspace_bytes(n, B), dev)
+  check(lib.pcmi_radius_components(ptr(x), x.stride(0) if n else 3, n, ptr(offs), B, ptr(g), float(radius), ptr(label), ptr(dropped),
+                                   ws, wsb, cur_stream(dev)))
+  return label
+
+
+def components_compact(label, offsets, group, min_points, max_instances):
+  """pcmi_components_compact: the components of label int32 [n] (radius_components') with at least min_points rows, numbered
+  in ascending order of their lowest row -> a dict of device tensors: instance int32 [n] (-1: in none), count int32 [1] (the
+  true number, even beyond max_instances: components numbered >= max_instances are written nowhere), and root, size, scene,
+  group int32 [max_instances] (-1 / size 0 from the count on)."""
+  require_cuda(label, "components_compact")
+  dev = label.device
+  lb, offs = _i32c(label, dev).reshape(-1), _offsets(offsets, dev)
+  g = None if group is None else _i32c(group, dev).reshape(-1)
+  n, B, M = lb.shape[0], offs.shape[0] - 1, int(max_instances)
+  assert B >= 1 and (g is None or g.shape[0] == n), "components_compact: offsets [B + 1], group [n]"
+  inst = torch.empty(n, dtype=torch.int32, device=dev)
+  count = torch.empty(1, dtype=torch.int32, device=dev)
+  root, size, scene, grp = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(4))
+  ws, wsb = ws_args(lib.pcmi_components_compact_workspace_bytes(n), dev)
+  check(lib.pcmi_components_compact(ptr(lb), ptr(offs), B, n, ptr(g), int(min_points), M, ptr(inst), ptr(count), ptr(root), ptr(size),
+                                    ptr(scene), ptr(grp), ws, wsb, cur_stream(dev)))
+  return dict(instance=inst, count=count, root=root, size=size, scene=scene, group=grp)
+
+
+def instance_scores(score, instance, inst_size):
+  """pcmi_instance_scores: the mean of score float32 [n] (clamped to [0, 1], non-finite -> 0) over the rows of each instance,
+  exact in 2^-30 fixed point -> float64 [P], P = len(inst_size); 0 for an instance without rows."""
+  s = _f32c(score, "instance_scores").reshape(-1)
+  dev = s.device
+  inst, size = _i32c(instance, dev).reshape(-1), _i32c(inst_size, dev).reshape(-1)
+  n, P = s.shape[0], size.shape[0]
+  assert inst.shape[0] == n, "instance_scores: score [n], instance [n]"
+  out = torch.empty(P, dtype=torch.float64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_instance_scores_workspace_bytes(P), dev)
+  check(lib.pcmi_instance_scores(ptr(s), ptr(inst), n, P, ptr(size), ptr(out), ws, wsb, cur_stream(dev)))
+  return out
+
+
+def instance_overlap(pred_instance, gt_instance, n_pred, n_gt):
+  """pcmi_instance_overlap: pred_instance / gt_instance [n] -> (inter int32 [P, G], pred_size int32 [P], gt_size int32 [G]);
+  ids outside [0, P) / [0, G) count nowhere."""
+  require_cuda(pred_instance, "instance_overlap")
+  dev = pred_instance.device
+  p, g = _i32c(pred_instance, dev).reshape(-1), _i32c(gt_instance, dev).reshape(-1)
+  P, G = int(n_pred), int(n_gt)
+  assert p.shape == g.shape, "instance_overlap: pred_instance [n], gt_instance [n]"
+  inter = torch.empty((P, G), dtype=torch.int32, device=dev)
+  ps, gs = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.int32, device=dev)
+  check(lib.pcmi_instance_overlap(ptr(p), ptr(g), p.shape[0], P, G, ptr(inter), ptr(ps), ptr(gs), cur_stream(dev)))
+  return inter, ps, gs
+
+
+def instance_match(inter, pred_size, gt_size, pred_scene, pred_class, gt_scene, gt_class):
+  """pcmi_instance_match: per predicted instance the ground-truth instance of its scene and class with the largest
+  inter / (pred_size + gt_size - inter) (float64, the lowest index of equal ones) -> (best_gt int32 [P], best_iou float32 [P]);
+  -1 / -inf without one: what det_ap consumes."""
+  require_cuda(inter, "instance_match")
+  dev = inter.device
+  it = _i32c(inter, dev)
+  assert it.dim() == 2, "instance_match: inter [P, G]"
+  P, G = it.shape
+  ps, psc, pcl = (_i32c(t, dev).reshape(-1) for t in (pred_size, pred_scene, pred_class))
+  gs, gsc, gcl = (_i32c(t, dev).reshape(-1) for t in (gt_size, gt_scene, gt_class))
+  assert ps.shape[0] == psc.shape[0] == pcl.shape[0] == P and gs.shape[0] == gsc.shape[0] == gcl.shape[0] == G, \
+      "instance_match: pred_* [P], gt_* [G]"
+  best_gt = torch.empty(P, dtype=torch.int32, device=dev)
+  best_iou = torch.empty(P, dtype=torch.float32, device=dev)
+  check(lib.pcmi_instance_match(ptr(it), ptr(ps), ptr(gs), ptr(psc), ptr(pcl), ptr(gsc), ptr(gcl), P, G, ptr(best_gt), ptr(best_iou),
+                                cur_stream(dev)))
+  return best_gt, best_iou
+
+
+def instance_centroids(coords, instance, n_instances):
+  """pcmi_instance_centroids: coords int32 [n, 4] (b, x, y, z), instance [n] -> (sum int64 [G, 3], cnt int64 [G]): the exact
+  sums of the voxel coordinates of each instance and their number."""
+  require_cuda(coords, "instance_centroids")
+  dev = coords.device
+  assert coords.dim() == 2 and coords.shape[1] == 4, "instance_centroids: coords [n, 4]"
+  c, inst = _i32c(coords, dev), _i32c(instance, dev).reshape(-1)
+  n, G = c.shape[0], int(n_instances)
+  assert inst.shape[0] == n, "instance_centroids: instance [n]"
+  s, cnt = torch.empty((G, 3), dtype=torch.int64, device=dev), torch.empty(G, dtype=torch.int64, device=dev)
+  check(lib.pcmi_instance_centroids(ptr(c), ptr(inst), n, G, ptr(s), ptr(cnt), cur_stream(dev)))
+  return s, cnt
+
+
+class OffsetLossFunction(Function):
+  """PointGroup's two offset losses (pcmi_offset_loss_fwd / _bwd): pred float32 [n, 3] (may be a column slice of the logits),
+  target float32 [n, 3], instance [n] (a row counts iff instance >= 0) -> (norm_loss, dir_loss), float64 scalars."""
+
+  @staticmethod
+  def forward(ctx, pred, target, instance):
+    require_cuda(pred, "offset loss")
+    assert pred.dim() == 2 and pred.shape[1] == 3 and target.shape == pred.shape, "offset loss: pred [n, 3], target [n, 3]"
+    p = pred if (pred.stride(1) == 1 and pred.dtype == torch.float32 and pred.stride(0) >= 3) else pred.float().contiguous()
+    dev = p.device
+    g, inst = _f32c(target.to(dev), "offset loss"), _i32c(instance, dev).reshape(-1)
+    n = p.shape[0]
+    assert inst.shape[0] == n, "offset loss: instance [n]"
+    out3 = torch.empty(3, dtype=torch.float64, device=dev)
+    ws, wsb = ws_args(lib.pcmi_offset_loss_workspace_bytes(n), dev)
+    check(lib.pcmi_offset_loss_fwd(ptr(p), p.stride(0) if n else 3, ptr(g), ptr(inst), n, ptr(out3), ws, wsb, cur_stream(dev)))
+    ctx.save_for_backward(p, g, inst, out3)
+    return out3[0], out3[1]
+
+  @staticmethod
+  @once_differentiable
+  def backward(ctx, gnorm, gdir):
+    p, g, inst, out3 = ctx.saved_tensors
+    n, dev = p.shape[0], p.device
+    gl = torch.stack([gnorm.reshape(()), gdir.reshape(())]).to(device=dev, dtype=torch.float64).contiguous()
+    dp = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    check(lib.pcmi_offset_loss_bwd(ptr(p), p.stride(0) if n else 3, ptr(g), ptr(inst), n, ptr(out3), ptr(gl), ptr(dp), 3, cur_stream(dev)))
+    return dp, None, None
