@@ -1669,6 +1669,71 @@ int pcmi_offset_loss_fwd(const float* p, int64_t ld, const float* g, const int32
 int pcmi_offset_loss_bwd(const float* p, int64_t ld, const float* g, const int32_t* inst, int64_t n, const double* out3,
                          const double* gloss2, float* dp, int64_t dp_ld, pcmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Active labelling (csrc/kmeans.hip) -- the point selection of the data-efficient benchmark of Hou et al., "Contrastive
+ * Scene Contexts", stated here (the reference has no counterpart): k-means with K = the annotation budget on the per-voxel
+ * features of every scene, the voxel nearest to each centre is annotated.  All scenes of a batch in one launch sequence.
+ * Every call: one stream, no read-back, no host synchronisation; a refused call enqueues nothing; integer atomics only;
+ * every output is the same bits from run to run.
+ *
+ * Common.  feat [n, C] (fp32, leading dimension ld >= C, ld a multiple of 4, base 16-byte aligned), C a multiple of 16 in
+ * 16..128 (pcmi_feat_nn's rule, PCMI_ERR_UNSUPPORTED otherwise).  offs: DEVICE int64 [B + 1], ascending; scene b holds the
+ * rows [offs[b], offs[b + 1]) clamped into [0, n] and CUT to its first max_scene_rows rows (a host number: the caller's bound
+ * on the rows of a scene; rows beyond it lie in no scene).  max_scene_rows <= PCMI_KMEANS_MAX_SCENE_ROWS = 2^20 and
+ * 1 <= K <= PCMI_KMEANS_MAX_K = 1024 clusters per scene, PCMI_ERR_UNSUPPORTED beyond; 1 <= B <= 65535.
+ *   A row is ACTIVE if it lies in a scene and every channel has |x| <= 1024 (which a NaN or an infinity fails).
+ *   Cluster k of scene b is LIVE if live[b, k] >= 0 (int32 [B, K], as pcmi_kmeans_init writes it).  A dead cluster is never
+ *   assigned and its centroid is written as 0.
+ *   Distance: the fp32 chain of pcmi_feat_nn, d2 = fma(a_c - b_c, a_c - b_c, d2) over ascending c.  An active row goes to the
+ *   live cluster of its scene with the smallest d2, the LOWEST k among equal d2 (a d2 that is not finite -- a centroid given
+ *   with a NaN -- is never chosen): the choice pcmi_feat_nn makes among the scene's centroids, bit for bit.  A row that is not
+ *   active, or has no cluster to go to, gets assign = -1 (d2 = NaN); skipped [B] (int64) = the rows of the scene that are not active
+ *   PLUS the rows of its segment that max_scene_rows cut off (so a cut shows: those rows get assign = -1 like rows in no scene).
+ *   Sums: q = (int64) rint((double) x 2^32) per channel of an assigned row (exact for |x| >= 2^-8), added by 64-bit integer
+ *   atomics; at most 2^20 rows of 2^42 each: 2^62.  centroid = (float) ((double) sum / ((double) cnt 2^32)), the product and the
+ *   quotient rounded once each; a live cluster with cnt == 0 keeps its previous centroid.
+ *
+ * pcmi_kmeans_init: centroid [B, K, C] = the feature rows init_rows [B, K] (int32, GLOBAL rows; -1: a dead cluster).
+ *   live [B, K] = init_rows where the row lies in scene b and is active, else -1 (centroid 0); flags [B] (int64) = the entries
+ *   >= 0 that were refused so.  live must not alias init_rows.
+ * pcmi_kmeans_step: one Lloyd iteration.  Assigns every row against centroid_in -> assign [n] (int32; not aliasing assign_prev),
+ *   sum [B, K, C] (int64), cnt [B, K] (int32), centroid_out [B, K, C], changed [B] (int64) = the rows of the scene whose
+ *   assignment differs from assign_prev (nullable: all -1), skipped [B].  One pass over feat does the assignment and the sums
+ *   (no [n, K] distance matrix): sums and counts are kept in LDS and flushed once per workgroup where K (8 C + 4) bytes fit
+ *   beside the tiles (80 KiB per workgroup in all), else added to memory directly.
+ * pcmi_kmeans_assign: the final pass.  assign [n], d2 [n] (fp32), cnt [B, K], skipped [B];  nearest [B, K] (int32) = the
+ *   GLOBAL row of the member nearest to the cluster's centroid, a 64-bit minimum on (d2 bits << 32 | row): the lowest row among
+ *   equal d2; -1 for a cluster without members.  inertia [B] (fp64) = the sum of the members' d2 widened to fp64: partial p of a
+ *   scene covers its rows [256 p, 256 (p + 1)), one per lane (non-members as 0), summed by a butterfly inside each wave of 64
+ *   (v += v[lane ^ d], d = 1 ... 32) and the four waves in ascending order; lane t of one workgroup adds the partials t,
+ *   t + 256, ... in that order from 0, and the 256 lanes are summed the same way (pcmi_offset_loss_fwd's rule, per scene).
+ *   ws: pcmi_kmeans_assign_workspace_bytes(B, K), 8-byte aligned.
+ * pcmi_kmeans_pp_step: one step of k-means++ seeding with the draw as data, in integers.  mind2 [n] (fp32, >= 0; +inf before
+ *   the first step), last [B] (int32, nullable: the centre chosen last, a global row), draw [B] (uint64).  Where last[b] is an
+ *   active row of scene b, mind2 of every active row of the scene is lowered to min(mind2, d2 to that row) (otherwise the
+ *   scene's mind2 stays).  w = (uint64) floor(min(mind2, 2^20) 2^20) for an active row, 0 otherwise; total = sum w (<= 2^60);
+ *   target = the high 64 bits of total x draw[b];  next [B] (int32) = the first row of the scene, in row order, whose inclusive
+ *   cumulative weight exceeds target; the lowest active row if total == 0; -1 if the scene has no active row.  The FIRST
+ *   centre is a step with last = NULL (or -1) and mind2 = +inf: every active row weighs 2^40, so the draw picks uniformly.
+ *   Weights and totals are integers (a block scan per 256 rows, integer atomics per 4096): no order changes the result.
+ *   n < 0x7f7f7f7f (PCMI_ERR_UNSUPPORTED beyond).  ws: pcmi_kmeans_pp_step_workspace_bytes(B), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+#define PCMI_KMEANS_MAX_K 1024
+#define PCMI_KMEANS_MAX_SCENE_ROWS (1 << 20)
+int pcmi_kmeans_init(const float* feat, int64_t ld, int64_t n, const int64_t* offs, int64_t B, int K, int c, int64_t max_scene_rows,
+                     const int32_t* init_rows, float* centroid, int32_t* live, int64_t* flags, pcmi_stream_t stream);
+int pcmi_kmeans_step(const float* feat, int64_t ld, int64_t n, const int64_t* offs, int64_t B, int K, int c, int64_t max_scene_rows,
+                     const float* centroid_in, const int32_t* live, const int32_t* assign_prev, int32_t* assign, int64_t* sum,
+                     int32_t* cnt, float* centroid_out, int64_t* changed, int64_t* skipped, pcmi_stream_t stream);
+size_t pcmi_kmeans_assign_workspace_bytes(int64_t B, int K);
+int pcmi_kmeans_assign(const float* feat, int64_t ld, int64_t n, const int64_t* offs, int64_t B, int K, int c, int64_t max_scene_rows,
+                       const float* centroid, const int32_t* live, int32_t* assign, float* d2, int32_t* nearest, double* inertia,
+                       int32_t* cnt, int64_t* skipped, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+size_t pcmi_kmeans_pp_step_workspace_bytes(int64_t B);
+int pcmi_kmeans_pp_step(const float* feat, int64_t ld, int64_t n, const int64_t* offs, int64_t B, int c, int64_t max_scene_rows,
+                        const int32_t* last, const uint64_t* draw, float* mind2, int32_t* next, void* ws, size_t ws_bytes,
+                        pcmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,6 +315,12 @@ PROTOTYPES = {
     "pcmi_offset_loss_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_offset_loss_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_offset_loss_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "pcmi_kmeans_init": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pcmi_kmeans_step": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_i64] + [c_vp] * 10),
+    "pcmi_kmeans_assign_workspace_bytes": (c_sz, [c_i64, C.c_int]),
+    "pcmi_kmeans_assign": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_i64] + [c_vp] * 9 + [c_sz, c_vp]),
+    "pcmi_kmeans_pp_step_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_kmeans_pp_step": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

@@ -29,6 +29,29 @@ __device__ __forceinline__ int block_scan_add(int v, int* s_wave, int* total) {
   return v + before;
 }
 
+// the same inclusive sum over unsigned 64-bit values (weights in fixed point: no order of evaluation changes the result)
+template <int WAVES>
+__device__ __forceinline__ unsigned long long block_scan_add64(unsigned long long v, unsigned long long* s_wave, unsigned long long* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  __syncthreads();  // the previous call's readers are done
+  if (lane == 63) s_wave[wave] = v;
+  __syncthreads();
+  unsigned long long before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    const unsigned long long x = s_wave[w];
+    before += w < wave ? x : 0;
+    all += x;
+  }
+  *total = all;
+  return v + before;
+}
+
 // maximum over the threads strictly BEFORE this one (0 for the first: the values are >= 0); all: over all threads
 template <int WAVES>
 __device__ __forceinline__ int block_scan_max_excl(int v, int* s_wave, int* all) {

@@ -18,6 +18,9 @@ What the reference's downstream/semseg does per iteration (downstream/semseg/lib
              map and collation (lib/dataset.py:289-298, lib/voxelizer.py, lib/transforms.py) for a batch of raw scans ->
              SegmentationInputPipeline (pcmi_seg_transform, pcmi_seg_quantize, pcmi_seg_color_augment),
              SegmentationTrainer.train_iter_scenes; every random draw is data (AugmentationDraws)
+  limited    the data-efficient setting of Hou et al. (no code in the reference): which `budget` voxels of a scene carry a label
+             is decided by k-means on features -> AnnotationSelector (csrc/kmeans.hip), limited_annotation_target,
+             SegmentationTrainer.train_iter(annotated=rows)
 Dataset classes, the elastic distortion and random dropout, PLY / txt files and colour maps, tensorboard and checkpoint
 bookkeeping of the downstream trainer are not provided.
 """
@@ -251,9 +254,15 @@ class SegmentationTrainer:
     st = ME.SparseTensor(feats, coords=coords).to(self.device)
     return self.engine.forward(0, st, training=training)
 
-  def train_iter(self, coords, feats, target):
+  def train_iter(self, coords, feats, target, annotated=None):
+    """annotated: rows int32 [B, budget] (AnnotationSelector's result; -1 entries are skipped) -- the limited-annotation
+    setting: every label but those of these rows becomes ignore_label (limited_annotation_target) where the target lies: on
+    the device for a device target; a host target is masked on the host, so the range check below still sees the labels
+    that count -- exactly train_iter on the masked target."""
     self.model.train()
     self.optimizer.zero_grad()
+    if annotated is not None:
+      target = limited_annotation_target(torch.as_tensor(target), annotated, self.ignore_label)
     if torch.is_tensor(target) and not target.is_cuda and target.numel():  # free on the host; as torch's CrossEntropyLoss
       bad = (target != self.ignore_label) & ((target < 0) | (target >= self.num_labels))
       if bool(bad.any()):
@@ -324,6 +333,104 @@ class SegmentationTrainer:
     out = self.train_iter(coords, feats, target)
     out["transformation"] = transformation
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Limited annotations (the data-efficient benchmark of Hou et al., "Contrastive Scene Contexts"): a scene gets `budget`
+# annotated voxels, chosen by active labelling -- k-means with K = budget on per-voxel features, the voxel nearest to each
+# centre (csrc/kmeans.hip, PF.kmeans_select).  The paper's procedure is restated in INTEGRATION.md; the reference has no code.
+# ---------------------------------------------------------------------------------------------------------------------
+def limited_annotation_target(target, rows, ignore_label=255):
+  """target [n] with every label replaced by ignore_label except at rows (any shape; entries < 0 are skipped): what
+  SegmentationTrainer.train_iter takes.  Stays on target's device."""
+  target = torch.as_tensor(target)
+  r = torch.as_tensor(rows).to(device=target.device, dtype=torch.int64).reshape(-1)
+  r = r[r >= 0]
+  out = torch.full_like(target, ignore_label)
+  out[r] = target[r]
+  return out
+
+
+def scene_offsets(coords):
+  """int64 [B + 1] (host) from the batch column of coords [n, 4]; the rows of a scene must stand together, scenes ascending."""
+  b = torch.as_tensor(coords)[:, 0].cpu().to(torch.int64)
+  if b.numel() == 0:
+    return torch.zeros(2, dtype=torch.int64)
+  assert bool((b[1:] >= b[:-1]).all()) and int(b[0]) >= 0, "the rows of a batch must be grouped by scene, scenes ascending"
+  counts = torch.bincount(b, minlength=int(b[-1]) + 1)
+  return torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)])
+
+
+class AnnotationSelector:
+  """Chooses the `budget` voxels of every scene of a batch that get a label.  features:
+    "net"     k-means on the output of the pre-training network (inference forward, normalised 32-channel features);
+              pretrained: its checkpoint (path or state dict), None keeps the random initialisation
+    "xyzrgb"  k-means on the voxel coordinates in metres (coords * voxel_size) and the colour columns of feats
+    "random"  budget distinct rows per scene, drawn without replacement from the draws
+  __call__(coords [n, 4] (b, x, y, z), feats [n, 3], draws=None) -> rows int32 [B, budget] on the host: global rows, -1 where
+  the scene has fewer voxels than the budget or a cluster stayed empty.  draws: PF.KMeansDraws [B, budget] (None: sampled).
+  `last` keeps kmeans_select's whole result of the last call."""
+
+  def __init__(self, budget, features="net", pretrained=None, model="Res16UNet34C", iters=10, device=None, in_channels=3,
+               voxel_size=0.05, kernel_order="hybrid"):
+    assert features in ("net", "xyzrgb", "random"), "features: 'net', 'xyzrgb' or 'random'"
+    assert 1 <= int(budget) <= PF.KMEANS_MAX_K, "budget: 1 .. %d annotated voxels per scene" % PF.KMEANS_MAX_K
+    self.budget, self.features, self.iters, self.voxel_size, self.last = int(budget), features, int(iters), float(voxel_size), None
+    if features == "random":
+      self.device = None
+      return
+    assert torch.cuda.is_available(), "the selection runs on a gfx950 GPU (no CPU path)"
+    self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if features == "net":
+      cfg = get_config(["net.normalize_feature=True"])
+      self.model = load_model(model)(in_channels, cfg.net.model_n_out, cfg, D=3).to(self.device)
+      if pretrained is not None:
+        state = torch.load(pretrained, map_location="cpu", weights_only=False) if isinstance(pretrained, str) else pretrained
+        weights = ck.convert_kernel_order(self.model, ck.strip_prefixes(state.get("state_dict", state)), kernel_order)
+        own = self.model.state_dict()
+        own.update(ck.load_state_with_same_shape(self.model, weights))
+        self.model.load_state_dict(own)
+      self.model.eval()
+      self.flat = FlatParameters(self.model.parameters())
+      self.engine = NativeEngine(self.model, self.flat, in_channels=in_channels, n_passes=1)
+
+  @torch.no_grad()
+  def point_features(self, coords, feats):
+    """float32 [n, C] on the device: what the k-means runs on."""
+    if self.features == "net":
+      st = ME.SparseTensor(torch.as_tensor(feats).float(), coords=torch.as_tensor(coords)).to(self.device)
+      return self.engine.forward(0, st, training=False)
+    xyz = torch.as_tensor(coords)[:, 1:4].to(self.device).float() * self.voxel_size
+    return torch.cat([xyz, torch.as_tensor(feats).to(self.device).float()], 1)
+
+  def __call__(self, coords, feats, draws=None):
+    offs = scene_offsets(coords)
+    B = offs.shape[0] - 1
+    if draws is None:
+      draws = PF.KMeansDraws.sample(B, self.budget)
+    elif not isinstance(draws, PF.KMeansDraws):
+      draws = PF.KMeansDraws(draws)
+    assert tuple(draws.bits.shape) == (B, self.budget), "draws [B, budget]"
+    if self.features == "random":
+      return random_rows(offs, draws)
+    self.last = PF.kmeans_select(self.point_features(coords, feats), offs, self.budget, draws, iters=self.iters)
+    return self.last["rows"]
+
+
+def random_rows(offsets, draws):
+  """int32 [B, K] (host): K distinct rows per scene, a partial Fisher-Yates shuffle whose step k takes position
+  k + floor((m - k) draw[b, k] / 2^64) of the scene's m rows; -1 from the m-th on."""
+  bits = (draws.bits if isinstance(draws, PF.KMeansDraws) else PF.KMeansDraws(draws).bits).cpu().numpy().view(np.uint64)
+  offs = np.asarray(offsets, dtype=np.int64)
+  B, K = bits.shape
+  rows = np.full((B, K), -1, dtype=np.int32)
+  for b in range(B):
+    lo, m, moved = int(offs[b]), int(offs[b + 1] - offs[b]), {}
+    for k in range(min(K, m)):
+      j = k + (((m - k) * int(bits[b, k])) >> 64)
+      rows[b, k] = lo + moved.get(j, j)
+      moved[j] = moved.get(k, k)
+  return torch.from_numpy(rows)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

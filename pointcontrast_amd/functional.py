@@ -2308,3 +2308,185 @@ class OffsetLossFunction(Function):
     dp = torch.empty((n, 3), dtype=torch.float32, device=dev)
     check(lib.pcmi_offset_loss_bwd(ptr(p), p.stride(0) if n else 3, ptr(g), ptr(inst), n, ptr(out3), ptr(gl), ptr(dp), 3, cur_stream(dev)))
     return dp, None, None
+
+
+# ---- active labelling: batched k-means on features (csrc/kmeans.hip) ----------------------------------------------------------
+KMEANS_MAX_K, KMEANS_MAX_SCENE_ROWS = 1024, 1 << 20
+
+
+class KMeansDraws:
+  """The uint64 draws [B, K] of the k-means++ seeding (column k: the draw of step k), kept as the int64 tensor with the same
+  bits.  Every random quantity of kmeans_select is in here: the same draws give the same rows."""
+
+  def __init__(self, bits):
+    import numpy as np
+    if not torch.is_tensor(bits):
+      a = np.asarray(bits)
+      bits = torch.from_numpy(np.ascontiguousarray(a.astype(np.uint64) if a.dtype != np.int64 else a).view(np.int64))
+    assert bits.dim() == 2 and bits.dtype == torch.int64, "KMeansDraws: uint64 [B, K] (or an int64 tensor holding those bits)"
+    self.bits = bits
+
+  @staticmethod
+  def sample(B, K, generator=None):
+    """Uniform draws from torch.randint over the int64 range, whose upper bound is exclusive: the bit pattern 2^63 - 1 is
+    never drawn (one of the 2^64 values; a target moves by at most total / 2^64 < 1 weight unit)."""
+    return KMeansDraws(torch.randint(-(1 << 63), (1 << 63) - 1, (int(B), int(K)), dtype=torch.int64, generator=generator))
+
+  def to(self, device):
+    return self.bits.to(device).contiguous()
+
+
+def _km_feat(feat, who):
+  """float32 [n, C] rows the kernels take as they are (a column slice with a stride of a multiple of 4 floats too); a width
+  that is not a multiple of 16 is zero-padded (zeros add nothing to a distance)."""
+  require_cuda(feat, who)
+  assert feat.dim() == 2 and feat.dtype == torch.float32, "%s: float32 [n, C] features" % who
+  c = feat.shape[1]
+  cp = pad_width(c, 16)
+  if cp != c:
+    padded = torch.zeros((feat.shape[0], cp), dtype=torch.float32, device=feat.device)
+    padded[:, :c] = feat
+    return padded
+  return _c(feat) if feat.shape[0] else feat.contiguous()
+
+
+def _km_scene_rows(offsets, n, max_scene_rows):
+  """The bound on the rows of a scene that the C calls take: the largest segment where the offsets are on the host; for
+  offsets on the device min(n, 2^20) without looking at them (a longer scene is cut to its first 2^20 rows; the rows cut off
+  get assign = -1 and are counted in `skipped`, so the cut shows in what the caller reads back)."""
+  if max_scene_rows is not None:
+    return int(max_scene_rows)
+  if _on_host(offsets):
+    import numpy as np
+    o = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    return int(max(0, np.diff(o).max())) if o.shape[0] >= 2 else 0
+  return min(int(n), KMEANS_MAX_SCENE_ROWS)
+
+
+def _km_common(feat, offsets, max_scene_rows, who):
+  f = _km_feat(feat, who)
+  offs = _offsets(offsets, f.device)
+  assert offs.dim() == 1 and offs.shape[0] >= 2, "%s: offsets [B + 1]" % who
+  n = f.shape[0]
+  return f, offs, n, offs.shape[0] - 1, f.shape[1], f.stride(0) if n else f.shape[1], _km_scene_rows(offsets, n, max_scene_rows)
+
+
+def kmeans_init(feat, offsets, init_rows, max_scene_rows=None):
+  """pcmi_kmeans_init: the centroids of all scenes from the feature rows init_rows int32 [B, K] (global rows; -1: a dead
+  cluster).  Returns (centroid float32 [B, K, C], live int32 [B, K]: init_rows with every row outside its scene or inactive
+  replaced by -1, flags int64 [B]: how many were replaced).  No synchronisation."""
+  f, offs, n, B, c, ld, msr = _km_common(feat, offsets, max_scene_rows, "kmeans_init")
+  rows = _i32c(torch.as_tensor(init_rows), f.device)
+  assert rows.dim() == 2 and rows.shape[0] == B, "kmeans_init: init_rows [B, K]"
+  K = rows.shape[1]
+  cen = torch.empty((B, K, c), dtype=torch.float32, device=f.device)
+  live = torch.empty((B, K), dtype=torch.int32, device=f.device)
+  flags = torch.empty(B, dtype=torch.int64, device=f.device)
+  check(lib.pcmi_kmeans_init(ptr(f), ld, n, ptr(offs), B, K, c, msr, ptr(rows), ptr(cen), ptr(live), ptr(flags), cur_stream(f.device)))
+  return cen, live, flags
+
+
+def kmeans_step(feat, offsets, centroid, live, assign_prev=None, max_scene_rows=None):
+  """pcmi_kmeans_step: one Lloyd iteration of all scenes -- assignment against centroid [B, K, C] and the fixed-point sums in
+  one pass over feat.  Returns a dict: assign int32 [n] (-1: inactive), sum int64 [B, K, C] (2^-32 fixed point), cnt int32
+  [B, K], centroid float32 [B, K, C] (the new ones), changed int64 [B] (against assign_prev; None: all -1), skipped int64 [B].
+  No synchronisation; bit-identical from run to run."""
+  f, offs, n, B, c, ld, msr = _km_common(feat, offsets, max_scene_rows, "kmeans_step")
+  dev = f.device
+  cen, lv = _f32c(centroid, "kmeans_step"), _i32c(live, dev)
+  assert cen.dim() == 3 and cen.shape[0] == B and cen.shape[2] == c and lv.shape == cen.shape[:2], \
+      "kmeans_step: centroid [B, K, C] of the (padded) feature width, live [B, K]"
+  K = cen.shape[1]
+  prev = None if assign_prev is None else _i32c(assign_prev, dev).reshape(-1)
+  assert prev is None or prev.shape[0] == n, "kmeans_step: assign_prev [n]"
+  assign = torch.empty(n, dtype=torch.int32, device=dev)
+  s = torch.empty((B, K, c), dtype=torch.int64, device=dev)
+  cnt = torch.empty((B, K), dtype=torch.int32, device=dev)
+  out = torch.empty((B, K, c), dtype=torch.float32, device=dev)
+  changed, skipped = torch.empty(B, dtype=torch.int64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+  check(lib.pcmi_kmeans_step(ptr(f), ld, n, ptr(offs), B, K, c, msr, ptr(cen), ptr(lv), ptr(prev), ptr(assign), ptr(s), ptr(cnt),
+                             ptr(out), ptr(changed), ptr(skipped), cur_stream(dev)))
+  return dict(assign=assign, sum=s, cnt=cnt, centroid=out, changed=changed, skipped=skipped)
+
+
+def kmeans_assign(feat, offsets, centroid, live, max_scene_rows=None):
+  """pcmi_kmeans_assign: the final pass.  Returns a dict: assign int32 [n], d2 float32 [n] (NaN: inactive), nearest int32
+  [B, K] (the global row of the member nearest to its centre, the lowest among equals; -1: no member), inertia float64 [B],
+  cnt int32 [B, K], skipped int64 [B].  assign / d2 equal feature_nn(feat, offsets, centroids of the live clusters) bit for
+  bit.  No synchronisation."""
+  f, offs, n, B, c, ld, msr = _km_common(feat, offsets, max_scene_rows, "kmeans_assign")
+  dev = f.device
+  cen, lv = _f32c(centroid, "kmeans_assign"), _i32c(live, dev)
+  assert cen.dim() == 3 and cen.shape[0] == B and cen.shape[2] == c and lv.shape == cen.shape[:2], \
+      "kmeans_assign: centroid [B, K, C] of the (padded) feature width, live [B, K]"
+  K = cen.shape[1]
+  assign, d2 = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+  nearest, cnt = torch.empty((B, K), dtype=torch.int32, device=dev), torch.empty((B, K), dtype=torch.int32, device=dev)
+  inertia, skipped = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_kmeans_assign_workspace_bytes(B, K), dev)
+  check(lib.pcmi_kmeans_assign(ptr(f), ld, n, ptr(offs), B, K, c, msr, ptr(cen), ptr(lv), ptr(assign), ptr(d2), ptr(nearest),
+                               ptr(inertia), ptr(cnt), ptr(skipped), ws, wsb, cur_stream(dev)))
+  return dict(assign=assign, d2=d2, nearest=nearest, inertia=inertia, cnt=cnt, skipped=skipped)
+
+
+def kmeans_pp_step(feat, offsets, mind2, last, draw, max_scene_rows=None):
+  """pcmi_kmeans_pp_step: one step of k-means++ seeding for all scenes.  mind2 float32 [n] is lowered IN PLACE to the distance
+  to the centres `last` int32 [B] (None / -1: nothing to lower -- the first step, with mind2 = +inf, picks uniformly among the
+  active rows); draw: uint64 [B] as int64 bits.  Returns next int32 [B] (global rows; -1: no active row).  No synchronisation."""
+  f, offs, n, B, c, ld, msr = _km_common(feat, offsets, max_scene_rows, "kmeans_pp_step")
+  dev = f.device
+  assert torch.is_tensor(mind2) and mind2.is_cuda and mind2.dtype == torch.float32 and mind2.is_contiguous() and mind2.shape == (n,), \
+      "kmeans_pp_step: mind2 float32 [n] on the device (updated in place)"
+  lst = None if last is None else _i32c(last, dev).reshape(-1)
+  dr = torch.as_tensor(draw).to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+  assert dr.shape[0] == B and (lst is None or lst.shape[0] == B), "kmeans_pp_step: last [B], draw [B]"
+  nxt = torch.empty(B, dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_kmeans_pp_step_workspace_bytes(B), dev)
+  check(lib.pcmi_kmeans_pp_step(ptr(f), ld, n, ptr(offs), B, c, msr, ptr(lst), ptr(dr), ptr(mind2), ptr(nxt), ws, wsb, cur_stream(dev)))
+  return nxt
+
+
+def kmeans_pp_init(feat, offsets, K, draws, max_scene_rows=None):
+  """k-means++ seeding of all scenes: K kmeans_pp_step calls, no read-back.  draws: KMeansDraws (or its int64 bits) [B, K].
+  Returns init_rows int32 [B, K]; a row picked a second time (only when no weight is left: fewer distinct active rows than
+  K) is -1, a dead cluster."""
+  f = _km_feat(feat, "kmeans_pp_init")
+  dev = f.device
+  bits = (draws if isinstance(draws, KMeansDraws) else KMeansDraws(draws)).to(dev)
+  K = int(K)
+  assert bits.shape[1] >= K, "kmeans_pp_init: draws [B, >= K]"
+  msr = _km_scene_rows(offsets, f.shape[0], max_scene_rows)
+  offs = _offsets(offsets, dev)
+  mind2 = torch.full((f.shape[0],), float("inf"), dtype=torch.float32, device=dev)
+  picks, last = [], None
+  for k in range(K):
+    last = kmeans_pp_step(f, offs, mind2, last, bits[:, k], msr)
+    picks.append(last)
+  rows = torch.stack(picks, 1)
+  again = (rows[:, :, None] == rows[:, None, :]) & torch.ones((K, K), dtype=torch.bool, device=dev).tril(-1)
+  return torch.where(again.any(2), torch.full_like(rows, -1), rows)
+
+
+def kmeans_select(feat, offsets, K, draws=None, iters=10, init_rows=None, max_scene_rows=None):
+  """Active labelling of a batch of scenes: k-means++ seeding (or init_rows int32 [B, K]), `iters` Lloyd iterations and the
+  final pass, all on the device with one read-back at the end (`rows`).  Returns a dict: rows int32 [B, K] ON THE HOST (the
+  row to annotate per cluster: the member nearest to its centre; -1 for a cluster that is dead or stayed empty), and on the
+  device assign int32 [n], centroid float32 [B, K, C], cnt int32 [B, K], inertia float64 [B], changed int64 [iters, B],
+  skipped int64 [B], live int32 [B, K].  draws None: sampled from torch's default generator."""
+  f = _km_feat(feat, "kmeans_select")
+  dev = f.device
+  offs = _offsets(offsets, dev)
+  B, K = offs.shape[0] - 1, int(K)
+  msr = _km_scene_rows(offsets, f.shape[0], max_scene_rows)
+  if init_rows is None:
+    init_rows = kmeans_pp_init(f, offs, K, KMeansDraws.sample(B, K) if draws is None else draws, msr)
+  cen, live, _ = kmeans_init(f, offs, init_rows, msr)
+  prev, changed = None, []
+  for _ in range(int(iters)):
+    st = kmeans_step(f, offs, cen, live, prev, msr)
+    cen, prev = st["centroid"], st["assign"]
+    changed.append(st["changed"])
+  fin = kmeans_assign(f, offs, cen, live, msr)
+  return dict(rows=fin["nearest"].cpu(), assign=fin["assign"], centroid=cen, cnt=fin["cnt"], inertia=fin["inertia"],
+              changed=torch.stack(changed) if changed else torch.zeros((0, B), dtype=torch.int64, device=dev),
+              skipped=fin["skipped"], live=live)
