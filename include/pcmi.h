@@ -1670,6 +1670,76 @@ int pcmi_offset_loss_bwd(const float* p, int64_t ld, const float* g, const int32
                          const double* gloss2, float* dp, int64_t dp_ld, pcmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Instance masks by the benchmark protocol (csrc/insbench.hip) -- the scoring rules of ScanNet's
+ * evaluate_semantic_instance.py, RESTATED FROM THE SCRIPT'S RULES, NEVER RUN AGAINST THE SCRIPT (the reference has no instance
+ * segmentation).  They differ from pcmi_instance_match + pcmi_det_ap (VOC-style) in four ways: predictions below a minimum
+ * region size are dropped, unmatched predictions that lie mostly on void or on small regions are ignored, duplicate
+ * predictions claim by the script's own rule, and the precision-recall curve is integrated in the script's way.
+ * Every call: one stream, no host synchronisation; a refused call enqueues nothing; integer atomics only, no workgroup waits
+ * for another, float64 operations rounded one by one in the stated order: every output is the same bits from run to run.
+ * NULL is accepted for an array without elements.
+ *
+ * pcmi_instance_void_overlap: pred_inst / gt_inst [n] (int32), gt_valid [G] (int32) -> void_inter [P] (int32, zeroed by the
+ *   call) = the rows of prediction p that are VOID: gt_inst outside [0, G), or gt_valid[gt_inst] == 0 (the caller sets
+ *   gt_valid = gt_class >= 0).  An id outside [0, P) counts nowhere.  One pass over the rows; a wave whose rows agree adds
+ *   once (pcmi_instance_overlap's aggregation).  The overlap matrix is pcmi_instance_overlap's.
+ *
+ * pcmi_instance_bench_match.  One batch of B scenes: inter [P, G], pred_size [P], gt_size [G] (pcmi_instance_overlap),
+ *   void_inter [P], pred_scene / pred_class [P] (int32), pred_score [P] (fp64, not NaN: a NaN score is never `best`),
+ *   gt_scene / gt_class [G] (int32; gt_class = -1: an instance that is not scored), min_region >= 1 (the benchmark: 100),
+ *   thresholds: a HOST array of 1 <= T <= 16 values in [0.25, 1) (PCMI_ERR_INVALID otherwise).
+ *     kept prediction       0 <= class < Cls, 0 <= scene < B, pred_size >= min_region; any other produces nothing
+ *     counted ground truth  0 <= class < Cls, 0 <= scene < B, gt_size >= min_region;  npos[c] += their number per class
+ *     small ground truth    gt_class >= 0 and gt_size < min_region
+ *     iou(p, g) = (double) inter / (double) (gt_size + pred_size - inter), ONE division, compared with a strict > against the
+ *       threshold; defined where inter > 0 and p and g share scene and class
+ *   Per scene, class and threshold th, independently:
+ *     visited = {}
+ *     for g ascending over the counted ground truths:
+ *       claim = [p ascending over the kept predictions: inter[p, g] > 0, p not visited, iou(p, g) > th]
+ *       if claim is not empty: visited += claim[0] (ONLY the first claimant, whatever its score -- the script's behaviour: at
+ *         0.25 a duplicate claimant may claim the next instance too); best = the claimant of the highest score, the lowest p
+ *         among equal scores; every p of claim emits an entry (score[p], true = (p == best))
+ *     for p over the kept predictions with no ground truth g of ANY size (same scene and class) with iou(p, g) > th:
+ *       ignore = void_inter[p] + the sum of inter[p, g] over the SMALL ground truths of p's scene and class
+ *       p emits (score[p], false) if (double) ignore / (double) pred_size[p] <= th, and is ignored otherwise
+ *   The multiset of entries is the script's (its running max / min of confidences gives the true positive the highest
+ *   claimant's score).  Disjoint ground truths above th each cover more than th pred_size rows, so a prediction claims fewer
+ *   than 1 / th <= 4 times: at most 3 entries (a prediction holding 3 claims no further -- unreachable with overlaps counted by
+ *   pcmi_instance_overlap).  At th >= 0.5 a prediction claims once and `visited` never acts.
+ *   entry_flag [T, P, 3] (int8): -1 none, 0 false positive, 1 true positive; slot s of p is its s-th claim in walk order, the
+ *   unmatched false positive goes into slot 0.  gt_state [T, G] (int32): 1 matched, 0 counted and unmatched, -1 not counted.
+ *   Both are written in full; npos [Cls] (int32) is INCREMENTED.
+ *   One wave per (threshold, scene, class) walks that unit's ground truths in order -- sequential by definition, tens of
+ *   instances per scene -- with its lanes over the predictions and two wave reductions per claim (first, best).
+ *   Limits: P G < 2^31 (the overlap matrix), 1 <= B <= 65535, 1 <= Cls <= 64.
+ *
+ * pcmi_instance_bench_ap: the entries of all accumulated batches, listed by the caller class by class in descending score as
+ *   pcmi_det_ap's detections: entry_flag [T, E] (int8), score [E] (fp64), class c at [cls_offs[c], cls_offs[c + 1]) (int32
+ *   [Cls + 1]), npos [Cls] (int32) -> ap [T, Cls] (fp64).  Flags of -1 are skipped, wherever they stand.
+ *     npos <= 0: NaN.  Otherwise the K remaining entries in list order, equal scores (== on the doubles) forming one group,
+ *     groups j = 1 .. m; tp_j / fp_j = the counts up to the end of group j; P_j = tp_j / (tp_j + fp_j), R_j = tp_j / npos;
+ *     P_0 = 1, R_0 = 0, R_-1 = 0, R_m+1 = R_m;
+ *       ap = sum over j = 0 .. m of P_j (0.5 (R_j+1 - R_j-1)),  from 0 in ascending j
+ *     -- the script's np.convolve(recall, [-0.5, 0, 0.5], 'valid') written out; K = 0 gives 0.
+ *   prec / rec [T, E] (fp64, nullable): P_j and R_j at the LAST entry of group j, NaN (all bits set) everywhere else.
+ *   One workgroup per (class, threshold) walks its range in blocks of 1024 with a carry (a class may hold any number of
+ *   entries, a group may straddle blocks), then adds the terms in order.  E < 2^30, 1 <= Cls <= 64, 1 <= T <= 16.
+ *   ws: pcmi_instance_bench_ap_workspace_bytes(E, Cls, n_thresholds), 4-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int pcmi_instance_void_overlap(const int32_t* pred_inst, const int32_t* gt_inst, const int32_t* gt_valid, int64_t n, int64_t P,
+                               int64_t G, int32_t* void_inter, pcmi_stream_t stream);
+int pcmi_instance_bench_match(const int32_t* inter, const int32_t* pred_size, const int32_t* gt_size, const int32_t* void_inter,
+                              const int32_t* pred_scene, const int32_t* pred_class, const double* pred_score,
+                              const int32_t* gt_scene, const int32_t* gt_class, int64_t P, int64_t G, int64_t B, int Cls,
+                              int min_region, const double* thresholds, int n_thresholds, int8_t* entry_flag, int32_t* gt_state,
+                              int32_t* npos, pcmi_stream_t stream);
+size_t pcmi_instance_bench_ap_workspace_bytes(int64_t E, int Cls, int n_thresholds);
+int pcmi_instance_bench_ap(const int8_t* entry_flag, const double* score, const int32_t* cls_offs, const int32_t* npos, int64_t E,
+                           int Cls, int n_thresholds, double* ap, double* prec, double* rec, void* ws, size_t ws_bytes,
+                           pcmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Active labelling (csrc/kmeans.hip) -- the point selection of the data-efficient benchmark of Hou et al., "Contrastive
  * Scene Contexts", stated here (the reference has no counterpart): k-means with K = the annotation budget on the per-voxel
  * features of every scene, the voxel nearest to each centre is annotated.  All scenes of a batch in one launch sequence.

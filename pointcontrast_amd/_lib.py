@@ -312,6 +312,11 @@ PROTOTYPES = {
     "pcmi_instance_overlap": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "pcmi_instance_match": (C.c_int, [c_vp] * 7 + [c_i64, c_i64, c_vp, c_vp, c_vp]),
     "pcmi_instance_centroids": (C.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pcmi_instance_void_overlap": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "pcmi_instance_bench_match": (C.c_int, [c_vp] * 9 + [c_i64, c_i64, c_i64, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, c_vp, c_vp,
+                                            c_vp, c_vp]),
+    "pcmi_instance_bench_ap_workspace_bytes": (c_sz, [c_i64, C.c_int, C.c_int]),
+    "pcmi_instance_bench_ap": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_offset_loss_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_offset_loss_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_offset_loss_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),

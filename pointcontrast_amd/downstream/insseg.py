@@ -16,6 +16,11 @@ depend on the row order), <= radius where they have <, ONE clustering on the shi
 unshifted ones) and no ScoreNet (an instance's score is the mean softmax probability of its rows for their class).  The
 AP is VOC-style -- each prediction is matched to its best ground truth, the rule of APCalculator -- and NOT ScanNet's
 benchmark script, which has void-overlap and minimum-region rules.
+
+  benchmark   those rules -- minimum region size, void and small-region overlap, the script's claim rule and its integration
+              of the curve -- on the voxels or on the original vertices (pcmi_instance_void_overlap,
+              pcmi_instance_bench_match, pcmi_instance_bench_ap) -> InstanceBenchmarkEvaluator.  Restated from the script's
+              rules, never run against the script (INTEGRATION.md lists the differences).
 """
 import warnings
 
@@ -27,6 +32,8 @@ from .semseg import SegmentationTrainer, precision_at_one
 
 # 0.25, then 0.50, 0.55, ... 0.95
 AP_THRESHOLDS = (0.25,) + tuple((10 + k) / 20.0 for k in range(10))
+# the benchmark script's own doubles: np.arange(0.5, 0.95, 0.05) (nine values, several a few bits away from k / 20), then 0.25
+BENCHMARK_THRESHOLDS = tuple(float(t) for t in np.append(np.arange(0.5, 0.95, 0.05), 0.25))
 
 
 def scene_offsets_of(coords):
@@ -136,6 +143,30 @@ class InstanceSegmentationTrainer(SegmentationTrainer):
     return cluster_instances(coords, out[:, C:C + 3], out[:, :C], scene_offsets_of(coords), self.voxel_size, self.radius, self.min_points,
                              self.stuff_classes, self.max_instances)
 
+  def benchmark_original_pointcloud(self, batches, min_region=100):
+    """The benchmark protocol on the ORIGINAL vertices (InstanceBenchmarkEvaluator: restated from the rules of ScanNet's
+    script, never run against the script) over an iterable of (coords, feats, transformation, points, point_instance,
+    point_class): predict per batch, the voxels' instance ids carried onto the vertices by step_points, one read-back at the
+    end.  points / point_instance / point_class: one array per scene of the batch (a list), or a single array for a batch of
+    one scene, as test_original_pointcloud takes them; point_instance numbers the batch's instances (-1: none).  Returns the
+    metrics dict; the evaluator stays on self.benchmark_evaluator and the per-vertex instance ids of every batch (device
+    tensors) on self.benchmark_predictions."""
+    self.benchmark_evaluator = InstanceBenchmarkEvaluator(self.num_labels, self.stuff_classes, min_region, device=self.device)
+    self.benchmark_predictions = []
+    for coords, feats, transformation, points, point_instance, point_class in batches:
+      if isinstance(points, (list, tuple)):
+        sizes = [len(p) for p in points]
+        points = torch.cat([torch.as_tensor(p).reshape(-1, 3) for p in points])
+        point_instance = torch.cat([torch.as_tensor(np.asarray(i)).reshape(-1) for i in point_instance])
+        point_class = torch.cat([torch.as_tensor(np.asarray(c)).reshape(-1) for c in point_class])
+      else:
+        sizes = [len(points)]
+      offsets = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64)
+      pred = self.predict(coords, feats)
+      self.benchmark_predictions.append(
+          self.benchmark_evaluator.step_points(coords, pred, transformation, points, point_instance, point_class, offsets))
+    return self.benchmark_evaluator.compute_metrics()
+
 
 class InstanceEvaluator:
   """Mask AP of predicted instances (cluster_instances' dict) against ground-truth instances, accumulated on the device.
@@ -219,3 +250,137 @@ class InstanceEvaluator:
       ap50, ap25 = at(0.5), at(0.25)
       return dict(AP=float(np.nanmean(ap_class)), AP50=float(np.nanmean(ap50)), AP25=float(np.nanmean(ap25)), ap_class=ap_class,
                   ap50_class=ap50, ap25_class=ap25, n_gt=n_gt, ap=ap)
+
+
+class InstanceBenchmarkEvaluator:
+  """Mask AP by the protocol of ScanNet's benchmark script (evaluate_semantic_instance.py), accumulated on the device --
+  **restated from the script's rules, never run against the script** (include/pcmi.h states them; INTEGRATION.md lists the
+  differences).  Beside InstanceEvaluator's VOC-style matching it drops predictions of fewer than min_region rows, does not
+  count ground truths that small, ignores an unmatched prediction that lies mostly on void (no instance, or an instance of an
+  unscored class) or on small ground truths, lets duplicate predictions claim by the script's rule and integrates the
+  precision-recall curve as the script does.  Figures of the two evaluators are not comparable.
+
+  step(pred, gt_instance, gt_class) adds one batch on the rows it is given; step_points(...) carries the voxels' instance ids
+  onto the original vertices first, as PointCloudEvaluator.step carries classes, which is where published numbers are taken.
+  compute_metrics() sorts the predictions once by descending score and once by class (stable torch.sorts), runs
+  PF.instance_bench_ap ONCE for all thresholds and reads back once."""
+
+  def __init__(self, num_labels, stuff_classes=(0, 1), min_region=100, thresholds=BENCHMARK_THRESHOLDS, device=None):
+    self.num_labels, self.stuff_classes = int(num_labels), tuple(int(s) for s in stuff_classes)
+    self.min_region = int(min_region)
+    self.thresholds = tuple(float(t) for t in thresholds)
+    self.device = None if device is None else torch.device(device)
+    self.reset()
+
+  def reset(self):
+    self._flag, self._cls, self._score, self.npos = [], [], [], None
+
+  def step(self, pred, gt_instance, gt_class, n_instances=None):
+    """pred: cluster_instances' dict (instance [n], inst_class, inst_scene, inst_score [P], scene_offsets [B + 1] over the n
+    rows); gt_instance [n]: the row's ground-truth instance as an index into the batch's instances, -1 for none; gt_class [n]:
+    the row's ground-truth class (an instance takes the largest class among its rows and the scene of its last row; instances of
+    stuff_classes or of a class outside [0, num_labels) are not scored: their rows are void).  n_instances None:
+    gt_instance.max() + 1.  The size of a prediction is its rows among the n given, NOT pred["inst_size"]; a score that is not
+    finite counts as 0.  Nothing is read back."""
+    dev = pred["instance"].device
+    if self.device is None:
+      self.device = dev
+    gi_any = torch.as_tensor(gt_instance).reshape(-1)
+    G = int(n_instances) if n_instances is not None else (int(gi_any.max()) + 1 if gi_any.numel() else 0)
+    G = max(G, 0)
+    gi = gi_any.to(device=dev, dtype=torch.int64)
+    gc = torch.as_tensor(gt_class).reshape(-1).to(device=dev, dtype=torch.int64)
+    n, C = gi.shape[0], self.num_labels
+    offs = pred["scene_offsets"].to(device=dev, dtype=torch.int64)
+    B = offs.shape[0] - 1
+    row_scene = torch.searchsorted(offs, torch.arange(n, device=dev), right=True) - 1
+    ok = (gi >= 0) & (gi < G)
+    cls = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], gc[ok], "amax", include_self=True)
+    scene = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], row_scene[ok], "amax", include_self=True)
+    scored = (cls >= 0) & (cls < C)
+    for s in self.stuff_classes:
+      scored = scored & (cls != s)
+    cls = torch.where(scored, cls, torch.full_like(cls, -1))
+    P = pred["inst_class"].shape[0]
+    inter, ps, gs = PF.instance_overlap(pred["instance"], gi, P, G)
+    void = PF.instance_void_overlap(pred["instance"], gi, scored, P)
+    score = pred["inst_score"].to(device=dev, dtype=torch.float64)
+    score = torch.where(torch.isfinite(score), score, torch.zeros_like(score))
+    if self.npos is None:
+      self.npos = torch.zeros(C, dtype=torch.int32, device=dev)
+    flag, _, _ = PF.instance_bench_match(inter, ps, gs, void, pred["inst_scene"], pred["inst_class"], score, scene, cls, B, C,
+                                         self.thresholds, self.min_region, npos=self.npos)
+    self._flag.append(flag)
+    self._cls.append(pred["inst_class"])
+    self._score.append(score)
+
+  def step_points(self, coords, pred, transformation, points, point_instance, point_class, point_offsets):
+    """coords int32 [nv, 4] (b, x, y, z) and pred (cluster_instances' dict on those voxels); transformation [B, 16]: the
+    voxelizer matrices as the loader returns them (host); points float64 [n, 3]: the original vertices, scene b at rows
+    [point_offsets[b], point_offsets[b + 1]); point_instance / point_class [n]: their ground truth as step takes it.  A vertex
+    takes the instance id of the voxel whose centre is nearest (voxel_centers, nearest_point with a cell of two voxel edges,
+    after a stable sort of the voxels by batch index: PointCloudEvaluator.step's carry), -1 where there is none (a scene
+    without voxels, a non-finite vertex); then step on the vertices.  Returns the per-vertex instance id (int32 [n], device)."""
+    dev = pred["instance"].device
+    T = np.asarray(transformation.cpu() if torch.is_tensor(transformation) else transformation, dtype=np.float64)
+    T = T[:, :16] if T.ndim == 2 else T.reshape(-1, 16)
+    B = T.shape[0]
+    c = torch.as_tensor(coords).to(dev).to(torch.int32)
+    order = torch.sort(c[:, 0], stable=True)[1]
+    c, vi = c[order].contiguous(), pred["instance"].reshape(-1).to(torch.int32)[order]
+    ref_offs = torch.searchsorted(c[:, 0].contiguous(), torch.arange(B + 1, dtype=torch.int32, device=dev)).to(torch.int64)
+    centers = PF.voxel_centers(c, T)
+    edge = float(max(np.linalg.norm(np.linalg.inv(T.reshape(-1, 4, 4))[:, :3, 0], axis=1).max(), 0.0))
+    cell = 2.0 * edge if np.isfinite(edge) and edge > 0 else None
+    pts = torch.as_tensor(points)
+    assert pts.dtype == torch.float64, "points: float64 [n, 3] (the original vertices, unrounded)"
+    offs = torch.as_tensor(point_offsets).to(device=dev, dtype=torch.int64)
+    idx = PF.nearest_point(centers, ref_offs, pts.to(dev), offs, cell=cell).long()
+    if vi.numel():
+      inst = torch.where(idx >= 0, vi[idx.clamp(min=0)], torch.full_like(idx, -1, dtype=torch.int32))
+    else:
+      inst = torch.full((idx.shape[0],), -1, dtype=torch.int32, device=dev)
+    self.step(dict(pred, instance=inst, scene_offsets=offs), point_instance, point_class)
+    return inst
+
+  def compute_metrics(self, keep_curves=False):
+    """One read-back.  The keys of InstanceEvaluator.compute_metrics: AP (the mean over the thresholds not close to 0.25, the
+    script's all_ap), AP50, AP25: nanmeans over the classes with counted ground truth of ap_class / ap50_class / ap25_class
+    (per class, NaN without ground truth, 0 with ground truth and no entry); ap [T, classes]; n_gt per class.  keep_curves:
+    self.last_ap keeps instance_bench_ap's device tensors (prec, rec [T, 3 nd]) and `order`, the accumulated predictions in
+    list order: entry 3 k + s is slot s of prediction order[k]."""
+    C, T = self.num_labels, len(self.thresholds)
+    if not self._flag:
+      nan = np.full(C, np.nan)
+      return dict(AP=float("nan"), AP50=float("nan"), AP25=float("nan"), ap_class=nan, ap50_class=nan.copy(), ap25_class=nan.copy(),
+                  n_gt=np.zeros(C, np.int64), ap=np.full((T, C), np.nan))
+    flag, cls, score = torch.cat(self._flag, 1), torch.cat(self._cls).long(), torch.cat(self._score)
+    cls = torch.where((cls >= 0) & (cls < C), cls, torch.full_like(cls, C))  # unused slots and foreign classes: behind every range
+    by_score = torch.sort(score, descending=True, stable=True).indices
+    order = by_score[torch.sort(cls[by_score], stable=True).indices]
+    cls_offs = (3 * torch.searchsorted(cls[order].contiguous(), torch.arange(C + 1, device=cls.device))).to(torch.int32)
+    out = PF.instance_bench_ap(flag[:, order, :].reshape(T, -1), score[order].repeat_interleave(3), cls_offs, self.npos,
+                               curves=keep_curves)
+    self.last_ap = dict(out, order=order) if keep_curves else None
+    flat = torch.cat([out["ap"].reshape(-1), self.npos.double()]).cpu().numpy()
+    ap, n_gt = flat[:T * C].reshape(T, C), np.rint(flat[T * C:]).astype(np.int64)
+    ap[:, n_gt == 0] = np.nan
+    return metrics_from_ap(ap, n_gt, self.thresholds)
+
+
+def metrics_from_ap(ap, n_gt, thresholds):
+  """The metrics dict of InstanceBenchmarkEvaluator from ap [T, classes] (NaN: a class without counted ground truth)."""
+  C = ap.shape[1]
+  thr = np.asarray(thresholds, dtype=np.float64)
+  rest = ~np.isclose(thr, 0.25)
+
+  def at(t):
+    hit = np.flatnonzero(np.isclose(thr, t))
+    return ap[hit[0]] if len(hit) else np.full(C, np.nan)
+
+  with warnings.catch_warnings():  # a class that never occurred: nanmean of nothing but NaN
+    warnings.simplefilter("ignore", category=RuntimeWarning)
+    ap_class = ap[rest].mean(0) if rest.any() else np.full(C, np.nan)
+    ap50, ap25 = at(0.5), at(0.25)
+    return dict(AP=float(np.nanmean(ap_class)), AP50=float(np.nanmean(ap50)), AP25=float(np.nanmean(ap25)), ap_class=ap_class,
+                ap50_class=ap50, ap25_class=ap25, n_gt=n_gt, ap=ap)

@@ -2280,6 +2280,75 @@ def instance_centroids(coords, instance, n_instances):
   return s, cnt
 
 
+# ---- instance masks by the benchmark protocol (csrc/insbench.hip): restated from the rules of ScanNet's script, never run
+# against the script; include/pcmi.h states them ---------------------------------------------------------------------------------
+def instance_void_overlap(pred_instance, gt_instance, gt_valid, n_pred):
+  """pcmi_instance_void_overlap: pred_instance / gt_instance [n], gt_valid [G] (non-zero: a scored ground-truth instance) ->
+  void_inter int32 [P]: the rows of each prediction whose ground-truth id is outside [0, G) or not valid; a prediction id
+  outside [0, P) counts nowhere.  The overlap matrix beside it is instance_overlap's."""
+  require_cuda(pred_instance, "instance_void_overlap")
+  dev = pred_instance.device
+  p, g, v = _i32c(pred_instance, dev).reshape(-1), _i32c(gt_instance, dev).reshape(-1), _i32c(gt_valid, dev).reshape(-1)
+  assert p.shape == g.shape, "instance_void_overlap: pred_instance [n], gt_instance [n]"
+  P = int(n_pred)
+  out = torch.empty(P, dtype=torch.int32, device=dev)
+  check(lib.pcmi_instance_void_overlap(ptr(p), ptr(g), ptr(v), p.shape[0], P, v.shape[0], ptr(out), cur_stream(dev)))
+  return out
+
+
+def instance_bench_match(inter, pred_size, gt_size, void_inter, pred_scene, pred_class, pred_score, gt_scene, gt_class, n_scenes,
+                         num_classes, thresholds, min_region=100, npos=None):
+  """pcmi_instance_bench_match: the benchmark protocol's matching of one batch.  inter int32 [P, G], pred_size [P], gt_size [G]
+  (instance_overlap's), void_inter [P] (instance_void_overlap's), pred_scene / pred_class [P], pred_score float64 [P] (not
+  NaN), gt_scene / gt_class [G] (class -1: not scored); thresholds: a sequence of at most 16 floats in [0.25, 1) (host).
+  Returns (entry_flag int8 [T, P, 3]: -1 none, 0 false positive, 1 true positive, slot s = the prediction's s-th claim;
+  gt_state int32 [T, G]: 1 matched, 0 counted and unmatched, -1 not counted; npos int32 [num_classes]: the counted ground
+  truths ADDED to the tensor passed in, a fresh one otherwise).  No host synchronisation."""
+  require_cuda(inter, "instance_bench_match")
+  dev = inter.device
+  it = _i32c(inter, dev)
+  assert it.dim() == 2, "instance_bench_match: inter [P, G]"
+  P, G = it.shape
+  ps, vi, psc, pcl = (_i32c(t, dev).reshape(-1) for t in (pred_size, void_inter, pred_scene, pred_class))
+  gs, gsc, gcl = (_i32c(t, dev).reshape(-1) for t in (gt_size, gt_scene, gt_class))
+  score = _f64c(pred_score, dev, "instance_bench_match").reshape(-1)
+  assert ps.shape[0] == vi.shape[0] == psc.shape[0] == pcl.shape[0] == score.shape[0] == P and \
+      gs.shape[0] == gsc.shape[0] == gcl.shape[0] == G, "instance_bench_match: pred_* [P], gt_* [G]"
+  T, Cls = len(thresholds), int(num_classes)
+  thr = (C.c_double * max(T, 1))(*[float(t) for t in thresholds])
+  if npos is None:
+    npos = torch.zeros(Cls, dtype=torch.int32, device=dev)
+  assert npos.dtype == torch.int32 and npos.shape == (Cls,) and npos.is_contiguous() and npos.device == dev, \
+      "instance_bench_match: npos int32 [num_classes] on inter's device"
+  flag = torch.empty((T, P, 3), dtype=torch.int8, device=dev)
+  state = torch.empty((T, G), dtype=torch.int32, device=dev)
+  check(lib.pcmi_instance_bench_match(ptr(it), ptr(ps), ptr(gs), ptr(vi), ptr(psc), ptr(pcl), ptr(score), ptr(gsc), ptr(gcl), P, G,
+                                      int(n_scenes), Cls, int(min_region), thr, T, ptr(flag), ptr(state), ptr(npos), cur_stream(dev)))
+  return flag, state, npos
+
+
+def instance_bench_ap(entry_flag, score, cls_offs, npos, curves=False):
+  """pcmi_instance_bench_ap.  entry_flag int8 [T, E] / score float64 [E]: the entries class by class in descending score, class
+  c at [cls_offs[c], cls_offs[c + 1]) (int32 [Cls + 1]); flags of -1 are skipped; npos int32 [Cls].  Returns a dict of device
+  tensors: ap float64 [T, Cls] (NaN where npos is 0) in the benchmark script's convolution form, equal scores forming one
+  group, and with curves prec, rec float64 [T, E]: the curve at the last entry of each group, NaN elsewhere.  No host
+  synchronisation."""
+  require_cuda(entry_flag, "instance_bench_ap")
+  dev = entry_flag.device
+  fl = entry_flag.to(torch.int8).contiguous()
+  assert fl.dim() == 2, "instance_bench_ap: entry_flag [T, E]"
+  T, E = fl.shape
+  sc, offs, np_ = _f64c(score, dev, "instance_bench_ap").reshape(-1), _i32c(cls_offs, dev), _i32c(npos, dev)
+  Cls = np_.shape[0]
+  assert sc.shape[0] == E and offs.shape == (Cls + 1,), "instance_bench_ap: score [E], cls_offs [Cls + 1], npos [Cls]"
+  ap = torch.empty((T, Cls), dtype=torch.float64, device=dev)
+  prec = torch.empty((T, E), dtype=torch.float64, device=dev) if curves else None
+  rec = torch.empty((T, E), dtype=torch.float64, device=dev) if curves else None
+  ws, wsb = ws_args(lib.pcmi_instance_bench_ap_workspace_bytes(E, Cls, T), dev)
+  check(lib.pcmi_instance_bench_ap(ptr(fl), ptr(sc), ptr(offs), ptr(np_), E, Cls, T, ptr(ap), ptr(prec), ptr(rec), ws, wsb, cur_stream(dev)))
+  return dict(ap=ap, prec=prec, rec=rec)
+
+
 class OffsetLossFunction(Function):
   """PointGroup's two offset losses (pcmi_offset_loss_fwd / _bwd): pred float32 [n, 3] (may be a column slice of the logits),
   target float32 [n, 3], instance [n] (a row counts iff instance >= 0) -> (norm_loss, dir_loss), float64 scalars."""
