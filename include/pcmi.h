@@ -1011,7 +1011,9 @@ int pcmi_seg_hist(const int32_t* pred, int64_t m, const int32_t* idx, const int3
  *   PCMI_SEG_FLAG_RANGE  a point of the scene is not finite, or a voxel coordinate is not inside +-2^20 (pcmi_seg_transform)
  *   PCMI_SEG_FLAG_SPAN   a voxel coordinate minus the scene's minimum is outside [0, 2^18)           (pcmi_seg_quantize)
  *   PCMI_SEG_FLAG_ELASTIC a scene's noise grid does not fit the capacity block; the scene is not distorted  (pcmi_elastic_blur)
- * The offending rows are dropped.
+ *   PCMI_SEG_FLAG_CROP   no step of the crop ladder brings the scene within max_voxels; it has the last step's window
+ *                        (pcmi_seg_crop_ladder, csrc/insseg_input.hip, below)
+ * The offending rows are dropped (a scene flagged CROP keeps the rows of its last window).
  *
  * pcmi_seg_transform = voxelizer.py:81-142.  xyz [n, 3] (fp64); mats [B, 16] (DEVICE fp64, row-major 4 x 4: M_r M_v, or M_v
  *   alone without augmentation, voxelizer.py:128-132; the caller builds it).  Clip (voxelizer.py:81-111), if clip_mode != 0,
@@ -1071,6 +1073,7 @@ int pcmi_seg_hist(const int32_t* pred, int64_t m, const int32_t* idx, const int3
 #define PCMI_SEG_FLAG_RANGE 1
 #define PCMI_SEG_FLAG_SPAN 2
 #define PCMI_SEG_FLAG_ELASTIC 4
+#define PCMI_SEG_FLAG_CROP 8
 size_t pcmi_elastic_blur_workspace_bytes(int64_t B, int cx, int cy, int cz);
 int pcmi_elastic_blur(const double* xyz, const int64_t* offsets, int64_t n, int64_t B, double granularity, const int32_t* active,
                       float* noise, int cx, int cy, int cz, int32_t* grid_dims, double* grid_min, int32_t* flags, void* ws,
@@ -1668,6 +1671,65 @@ int pcmi_offset_loss_fwd(const float* p, int64_t ld, const float* g, const int32
                          size_t ws_bytes, pcmi_stream_t stream);
 int pcmi_offset_loss_bwd(const float* p, int64_t ld, const float* g, const int32_t* inst, int64_t n, const double* out3,
                          const double* gloss2, float* dp, int64_t dp_ld, pcmi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The input of instance-segmentation fine-tuning (csrc/insseg_input.hip): what stands between pcmi_seg_quantize and a batch
+ * that InstanceSegmentationTrainer.train_iter takes -- ground-truth instance indices that are unique across the scenes of a
+ * batch, the per-instance table both instance evaluators need, and a per-scene crop.  The reference has no counterpart; the
+ * rules are stated here.  All arithmetic is integer; integer atomics only (sums, minima, maxima, ors, and the compare-and-swap
+ * that claims a table slot, whose outcome reaches no output); every output is the same bits from run to run.  One stream, no
+ * host synchronisation, a refused call enqueues nothing.
+ * In all three calls offsets [B + 1] is DEVICE int64, ascending: scene b holds the rows [offsets[b], offsets[b + 1]).  The
+ * arrays hold n rows of capacity; a row outside every scene -- at or beyond offsets[B], or below offsets[0] -- is neither read
+ * nor written, so the calls chain behind pcmi_seg_quantize (offsets = the running sums of its counts) before those counts are
+ * read back.  1 <= B <= 1023; n < 2^31 - 256 (PCMI_ERR_INVALID beyond) and n <= 2^29 (PCMI_ERR_UNSUPPORTED beyond, as
+ * pcmi_seg_quantize).  n == 0 enqueues nothing beyond zeroing the counts.
+ *
+ * pcmi_instance_relabel: raw [n] (int32) = per-scene instance ids as datasets store them: arbitrary non-negative integers,
+ *   the same id in two scenes meaning two instances; keep [n] (uint8, NULL = all).  A row with raw < 0 or keep == 0 belongs to
+ *   no instance.  Two remaining rows are the same instance iff they share their scene and their raw id.  Instances are numbered
+ *   0, 1, ... in ascending order of their LOWEST row: scenes in order, within a scene the order of first occurrence -- the
+ *   convention of pcmi_components_compact.  instance [n] (int32) = the row's number, -1 for a row in no instance; first_row [n]
+ *   (int32): the lowest row of instance g at position g, valid up to the count; inst_counts [B + 1] (DEVICE int64) = the
+ *   instances whose lowest row lies in each scene, then their sum.  Ids are always < n: there is no capacity to exceed.
+ *   An open-addressing table of 2 n slots keyed by (scene << 32) | raw, an atomic minimum of the row per slot, a flag per row
+ *   that is its key's minimum, the three-launch scan of the flags (csrc/rowscan.h, shared with pcmi_components_compact), one
+ *   lookup per row.  ws: pcmi_instance_relabel_workspace_bytes(n), 16-byte aligned.
+ * pcmi_instance_table: instance [n] (int32), klass [n] (int32, nullable together with cls), coords [n, 4] (int32: b, x, y, z;
+ *   nullable together with sum, box_min and box_max) -> per instance g in [0, G), all initialised by the call:
+ *     size [G] (int32)      its rows
+ *     scene [G] (int32)     the largest scene among its rows, -1 without rows
+ *     cls [G] (int32)       max(-1, the maximum of klass over its rows), any value of klass included -- what
+ *                           scatter_reduce("amax", include_self=True) into a tensor of -1 gives
+ *     sum [G, 3] (int64)    the exact sums of coords[:, 1:4]: pcmi_instance_centroids' sum, as size is its cnt
+ *     box_min / box_max [G, 3] (int32)  the extremes of coords[:, 1:4]; INT32_MAX / INT32_MIN without rows
+ *   An id outside [0, G) counts nowhere.  0 <= G < 2^31; G == 0 enqueues nothing.  No workspace.
+ * pcmi_seg_crop_ladder: a window per scene that bounds its voxels.  THIS RULE IS THE PROJECT'S OWN: it is in the spirit of the
+ *   crop in PointGroup's recipe, NOT a restatement of it, and its parameters are untuned.  It works on voxel rows after
+ *   quantization.  coords [n, 4] (int32; the min-shifted coordinates pcmi_seg_quantize writes), axis0 != axis1 in 1 ... 3 (the
+ *   horizontal columns of coords), sides [S, 2] (HOST int32, 1 <= S <= 32, window sides in voxels, every side >= 1, each
+ *   column non-increasing), draws [B, S, 2] (DEVICE uint32), max_voxels >= 1; anything else: PCMI_ERR_INVALID.  Per scene, with
+ *   ext_a = the maximum of column a over its rows: a scene of at most max_voxels rows keeps all of them, step = -1.  Otherwise,
+ *   for step s,
+ *     slack_a = max(ext_a + 1 - side[s][a], 0),   origin_a = (uint64(draw[b][s][a]) (slack_a + 1)) >> 32,
+ *     a row is inside iff origin_a <= c_a < origin_a + side[s][a] on both axes,
+ *   and the scene takes the LOWEST s whose inside count is <= max_voxels; if no step fits it takes step S - 1 and gets
+ *   PCMI_SEG_FLAG_CROP (flags [B], ORed in).  Coordinates are NOT shifted again, so the batch's transformation stays valid.
+ *   rows [n] (int64) = the kept rows in ascending order; kept_counts [B + 1] (DEVICE int64) = the kept rows per scene, then
+ *   their sum; step [B] (int32).  Launches: the scene extents; the origins; one pass in which every row of a scene above
+ *   max_voxels tests all S windows (a 32-bit mask per row) and the per-step counts are gathered per scene in LDS; the choice;
+ *   the scan and scatter of the kept rows.  ws: pcmi_seg_crop_ladder_workspace_bytes(n, B), 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+size_t pcmi_instance_relabel_workspace_bytes(int64_t n);
+int pcmi_instance_relabel(const int32_t* raw, const uint8_t* keep, const int64_t* offsets, int64_t n, int64_t B, int32_t* instance,
+                          int32_t* first_row, int64_t* inst_counts, void* ws, size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_instance_table(const int32_t* instance, const int32_t* klass, const int32_t* coords, const int64_t* offsets, int64_t n,
+                        int64_t B, int64_t G, int32_t* size, int32_t* scene, int32_t* cls, int64_t* sum, int32_t* box_min,
+                        int32_t* box_max, pcmi_stream_t stream);
+size_t pcmi_seg_crop_ladder_workspace_bytes(int64_t n, int64_t B);
+int pcmi_seg_crop_ladder(const int32_t* coords, const int64_t* offsets, int64_t n, int64_t B, int axis0, int axis1,
+                         const int32_t* sides_host, int S, const uint32_t* draws, int64_t max_voxels, int64_t* rows,
+                         int64_t* kept_counts, int32_t* step, int32_t* flags, void* ws, size_t ws_bytes, pcmi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Instance masks by the benchmark protocol (csrc/insbench.hip) -- the scoring rules of ScanNet's

@@ -320,6 +320,12 @@ PROTOTYPES = {
     "pcmi_offset_loss_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_offset_loss_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_offset_loss_bwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "pcmi_instance_relabel_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_instance_relabel": (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_instance_table": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64] + [c_vp] * 6 + [c_vp]),
+    "pcmi_seg_crop_ladder_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pcmi_seg_crop_ladder": (C.c_int, [c_vp, c_vp, c_i64, c_i64, C.c_int, C.c_int, C.POINTER(c_i32), C.c_int, c_vp, c_i64, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pcmi_kmeans_init": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pcmi_kmeans_step": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_i64] + [c_vp] * 10),
     "pcmi_kmeans_assign_workspace_bytes": (c_sz, [c_i64, C.c_int]),

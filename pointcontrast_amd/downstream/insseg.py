@@ -21,6 +21,10 @@ benchmark script, which has void-overlap and minimum-region rules.
               of the curve -- on the voxels or on the original vertices (pcmi_instance_void_overlap,
               pcmi_instance_bench_match, pcmi_instance_bench_ap) -> InstanceBenchmarkEvaluator.  Restated from the script's
               rules, never run against the script (INTEGRATION.md lists the differences).
+  input       raw scans (xyz, colours, labels, per-scene instance ids) -> a batch with instance indices that are unique across
+              its scenes: SegmentationInputPipeline's stages, the voxel's instance id by a second pcmi_seg_quantize, an optional
+              per-scene crop (pcmi_seg_crop_ladder: this project's own rule, untuned), pcmi_instance_relabel
+              -> InstanceInputPipeline, train_iter_scenes, validate_scenes
 """
 import warnings
 
@@ -28,7 +32,7 @@ import numpy as np
 import torch
 
 from .. import functional as PF
-from .semseg import SegmentationTrainer, precision_at_one
+from .semseg import SegmentationInputPipeline, SegmentationTrainer, precision_at_one
 
 # 0.25, then 0.50, 0.55, ... 0.95
 AP_THRESHOLDS = (0.25,) + tuple((10 + k) / 20.0 for k in range(10))
@@ -73,6 +77,101 @@ def cluster_instances(coords, offsets, logits, scene_offsets, voxel_size, radius
   out = PF.components_compact(label, offs, group, min_points, max_instances)
   return dict(instance=out["instance"], count=out["count"], inst_class=out["group"], inst_size=out["size"], inst_scene=out["scene"],
               inst_score=PF.instance_scores(score, out["instance"], out["size"]), scene_offsets=offs)
+
+
+class InstanceInputPipeline(SegmentationInputPipeline):
+  """scenes of (xyz, colours, labels, instance_ids) -> (coords, feats, target, instance, n_instances, transformation) on the
+  device, with ONE read-back per batch: the parent's stages, and between its quantizer and its read-back
+
+    the voxel's raw instance id   the common id of all its points, else -1: a second pcmi_seg_quantize with the ids as labels
+                                  and -1 as the ignore label (the same voxels in the same order)
+    the crop, if any              crop = (sides, max_voxels): pcmi_seg_crop_ladder on the two horizontal axes; every row array
+                                  is gathered by its rows.  THIS PROJECT'S OWN RULE, in the spirit of PointGroup's crop, not a
+                                  restatement of it; the ladder and max_voxels are untuned.  Coordinates are not shifted again,
+                                  so `transformation` stays valid.  A scene that no step brings within max_voxels raises.
+    pcmi_instance_relabel         over the voxels whose target after aug.label_map is neither the ignore label nor one of
+                                  stuff_classes: those are in no instance
+
+  Dropout and limit_numpoints only remove rows afterwards: the ids stay unique and ordered, some may be left without rows
+  (legal for the loss and both evaluators).  n_instances counts the instances of the scenes that survive limit_numpoints.
+  dropout_keys and normals of the draws are read by voxel row AFTER the crop.  Without crop, and with the same draws, coords,
+  feats, target and transformation are SegmentationInputPipeline's bit for bit.  last_crop_step: step int64 [B] of the last
+  batch (-1: the scene was not cropped), from its read-back."""
+
+  def __init__(self, aug, device=None, stuff_classes=(0, 1), crop=None):
+    super().__init__(aug, device)
+    self.stuff_classes = tuple(int(s) for s in stuff_classes)
+    self.crop = None if crop is None else (np.asarray(crop[0], dtype=np.int64).reshape(-1, 2), int(crop[1]))
+    self.last_crop_step = None
+
+  @staticmethod
+  def sample_crop_draws(crop, n_scenes, rng):
+    """uint32-valued int64 [B, S, 2] from rng (numpy.random.RandomState): one draw per scene, step and axis."""
+    return rng.randint(0, 2**32, size=(int(n_scenes), len(np.asarray(crop[0]).reshape(-1, 2)), 2), dtype=np.int64)
+
+  def __call__(self, scenes, draws=None, limit_numpoints=0, crop_draws=None):
+    st = self.stage_upload(scenes, draws, crop_draws=crop_draws)
+    self.stage_voxelize(st)
+    self.stage_instances(st)
+    counts, tail = self.stage_read_back(st, st["read"])
+    return self.stage_finish(st, counts, tail, limit_numpoints)
+
+  def stage_upload(self, scenes, draws=None, extra_labels=(3,), crop_draws=None):
+    st = super().stage_upload(scenes, draws, extra_labels)
+    st["crop_draws"] = None
+    if self.crop is not None:
+      assert crop_draws is not None, "a cropping pipeline needs its draws (InstanceInputPipeline.sample_crop_draws)"
+      st["crop_draws"] = torch.as_tensor(np.asarray(crop_draws, dtype=np.int64)).reshape(st["B"], len(self.crop[0]), 2).to(self.device)
+    return st
+
+  def stage_instances(self, st):
+    """The voxel's raw id, the crop, the relabelling: st["rows"] (coords, index, target), st["instance"], st["read"]."""
+    aug, dev, B, t, q = self.aug, self.device, st["B"], st["t"], st["q"]
+    raw = PF.seg_quantize(t["vox"], st["offs_dev"], st["extra"][3], t["keep"], t["scene_min"], -1, flags=st["flags"])["labels"]
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    voffs = torch.cat([zero, q["counts"][:B].cumsum(0)])
+    coords, index, target, read = q["coords"], q["index"], q["labels"], []
+    if self.crop is not None:
+      cr = PF.seg_crop_ladder(coords, voffs, [1 + a for a in aug.horizontal_axes], self.crop[0], st["crop_draws"], self.crop[1], st["flags"])
+      rows = cr["rows"]
+      coords, index, target, raw = coords[rows].contiguous(), index[rows].contiguous(), target[rows].contiguous(), raw[rows].contiguous()
+      voffs = torch.cat([zero, cr["counts"][:B].cumsum(0)])
+      read += [cr["counts"], cr["step"]]
+    mapped = target
+    if self._lut is not None:  # pcmi_seg_color_augment's rule, which the target itself meets after the read-back
+      L = self._lut.shape[0]
+      mapped = torch.where((target >= 0) & (target < L), self._lut[target.clamp(0, L - 1).long()], torch.full_like(target, aug.ignore_label))
+    keep = mapped != aug.ignore_label
+    for s in self.stuff_classes:
+      keep = keep & (mapped != s)
+    rl = PF.instance_relabel(raw, voffs, keep)
+    st["rows"], st["instance"], st["read"] = (coords, index, target), rl["instance"], read + [rl["counts"]]
+
+  def stage_finish(self, st, counts, tail, limit_numpoints=0):
+    """Dropout, the batch limit and the colour stage from the read-back -> the call's result."""
+    B = st["B"]
+    if self.crop is not None:
+      counts, self.last_crop_step, tail = [int(c) for c in tail[:B]], tail[B + 1:2 * B + 1].copy(), tail[2 * B + 1:]
+    else:
+      self.last_crop_step = None
+    pick, nb, total = self.stage_select(st, counts, limit_numpoints)
+    coords, feats, target, transformation = self.stage_colour(st, pick, nb, total, *st["rows"])
+    return coords, feats, target, pick(st["instance"]), int(tail[:nb].sum()), transformation
+
+
+def batch_instance_ids(per_scene_raw_ids, device=None):
+  """The point_instance numbering benchmark_original_pointcloud asks its caller for, from the raw per-scene instance ids of a
+  batch's vertices (a list of integer arrays; < 0: no instance): PF.instance_relabel over the concatenated vertices, so the
+  indices are unique across the scenes and ordered by first occurrence.  Returns (one int32 array per scene on the host, the
+  number of instances); one read-back."""
+  dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+  sizes = [len(r) for r in per_scene_raw_ids]
+  offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64)
+  raw = torch.cat([torch.as_tensor(np.asarray(r)).reshape(-1).to(torch.int32) for r in per_scene_raw_ids]).to(dev)
+  out = PF.instance_relabel(raw, offs.to(dev))
+  host = torch.cat([out["instance"].to(torch.int64), out["counts"][-1:]]).cpu().numpy()
+  inst = host[:-1].astype(np.int32)
+  return [inst[int(offs[b]):int(offs[b + 1])] for b in range(len(sizes))], int(host[-1])
 
 
 class InstanceSegmentationTrainer(SegmentationTrainer):
@@ -143,6 +242,32 @@ class InstanceSegmentationTrainer(SegmentationTrainer):
     return cluster_instances(coords, out[:, C:C + 3], out[:, :C], scene_offsets_of(coords), self.voxel_size, self.radius, self.min_points,
                              self.stuff_classes, self.max_instances)
 
+  def train_iter_scenes(self, scenes, draws=None, limit_numpoints=0, crop_draws=None):
+    """One iteration from raw scans of (xyz, colours, labels, instance_ids): self.input_pipeline (an InstanceInputPipeline, the
+    constructor's argument), then train_iter on its device tensors.  The result carries the batch's `transformation` too."""
+    assert isinstance(self.input_pipeline, InstanceInputPipeline), "construct the trainer with input_pipeline=InstanceInputPipeline(aug, device)"
+    coords, feats, target, instance, n_instances, transformation = self.input_pipeline(scenes, draws, limit_numpoints, crop_draws)
+    out = self.train_iter(coords, feats, target, instance, n_instances)
+    out["transformation"] = transformation
+    return out
+
+  @torch.no_grad()
+  def validate_scenes(self, batches, benchmark=False):
+    """Mask AP over an iterable of scene lists (each a batch of (xyz, colours, labels, instance_ids)): a non-augmenting, non-
+    cropping InstanceInputPipeline on self.input_pipeline's constants, predict, PF.instance_table (the ground truth's class and
+    scene per instance, which the evaluator then does not derive), InstanceEvaluator.step -- InstanceBenchmarkEvaluator.step
+    with benchmark=True -- and compute_metrics().  Returns its dict; the evaluator stays on self.instance_evaluator."""
+    assert isinstance(self.input_pipeline, InstanceInputPipeline), "construct the trainer with input_pipeline=InstanceInputPipeline(aug, device)"
+    pipe = InstanceInputPipeline(self.input_pipeline.aug.replace(augment=False), self.device, self.input_pipeline.stuff_classes)
+    ev = (InstanceBenchmarkEvaluator if benchmark else InstanceEvaluator)(self.num_labels, self.stuff_classes, device=self.device)
+    self.instance_evaluator = ev
+    for scenes in batches:
+      coords, feats, target, instance, n_instances, _ = pipe(scenes)
+      pred = self.predict(coords, feats)
+      table = PF.instance_table(instance, target, None, pred["scene_offsets"], n_instances)
+      ev.step(pred, instance, target, n_instances, table=table)
+    return ev.compute_metrics()
+
   def benchmark_original_pointcloud(self, batches, min_region=100):
     """The benchmark protocol on the ORIGINAL vertices (InstanceBenchmarkEvaluator: restated from the rules of ScanNet's
     script, never run against the script) over an iterable of (coords, feats, transformation, points, point_instance,
@@ -168,6 +293,12 @@ class InstanceSegmentationTrainer(SegmentationTrainer):
     return self.benchmark_evaluator.compute_metrics()
 
 
+def _table_cls_scene(table, G):
+  """(cls, scene) int64 [G] of PF.instance_table's dict: what the evaluators' scatter_reduce derivation gives."""
+  assert table["cls"] is not None and table["cls"].shape[0] == G and table["scene"].shape[0] == G, "table: instance_table's dict with klass, for G"
+  return table["cls"].to(torch.int64), table["scene"].to(torch.int64)
+
+
 class InstanceEvaluator:
   """Mask AP of predicted instances (cluster_instances' dict) against ground-truth instances, accumulated on the device.
 
@@ -185,10 +316,12 @@ class InstanceEvaluator:
   def reset(self):
     self._iou, self._gid, self._cls, self._score, self.npos, self.n_gt = [], [], [], [], None, 0
 
-  def step(self, pred, gt_instance, gt_class, n_instances=None):
+  def step(self, pred, gt_instance, gt_class, n_instances=None, table=None):
     """pred: cluster_instances' dict; gt_instance [n]: the row's ground-truth instance as an index into the batch's instances,
     -1 for none; gt_class [n]: the row's ground-truth class (an instance takes the largest class among its rows; instances of
-    stuff_classes or of a class outside [0, num_labels) are not scored).  n_instances None: gt_instance.max() + 1."""
+    stuff_classes or of a class outside [0, num_labels) are not scored).  n_instances None: gt_instance.max() + 1.  table:
+    PF.instance_table's dict for (gt_instance, gt_class, pred["scene_offsets"], n_instances) -- its cls and scene are then taken
+    instead of being derived here; the metrics are the same bits."""
     dev = pred["instance"].device
     if self.device is None:
       self.device = dev
@@ -198,10 +331,13 @@ class InstanceEvaluator:
     gi = gi_any.to(device=dev, dtype=torch.int64)
     gc = torch.as_tensor(gt_class).reshape(-1).to(device=dev, dtype=torch.int64)
     n, C = gi.shape[0], self.num_labels
-    row_scene = torch.searchsorted(pred["scene_offsets"], torch.arange(n, device=dev), right=True) - 1
-    ok = (gi >= 0) & (gi < G)
-    cls = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], gc[ok], "amax", include_self=True)
-    scene = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], row_scene[ok], "amax", include_self=True)
+    if table is not None:
+      cls, scene = _table_cls_scene(table, G)
+    else:
+      row_scene = torch.searchsorted(pred["scene_offsets"], torch.arange(n, device=dev), right=True) - 1
+      ok = (gi >= 0) & (gi < G)
+      cls = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], gc[ok], "amax", include_self=True)
+      scene = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], row_scene[ok], "amax", include_self=True)
     scored = (cls >= 0) & (cls < C)
     for s in self.stuff_classes:
       scored = scored & (cls != s)
@@ -275,13 +411,14 @@ class InstanceBenchmarkEvaluator:
   def reset(self):
     self._flag, self._cls, self._score, self.npos = [], [], [], None
 
-  def step(self, pred, gt_instance, gt_class, n_instances=None):
+  def step(self, pred, gt_instance, gt_class, n_instances=None, table=None):
     """pred: cluster_instances' dict (instance [n], inst_class, inst_scene, inst_score [P], scene_offsets [B + 1] over the n
     rows); gt_instance [n]: the row's ground-truth instance as an index into the batch's instances, -1 for none; gt_class [n]:
     the row's ground-truth class (an instance takes the largest class among its rows and the scene of its last row; instances of
     stuff_classes or of a class outside [0, num_labels) are not scored: their rows are void).  n_instances None:
     gt_instance.max() + 1.  The size of a prediction is its rows among the n given, NOT pred["inst_size"]; a score that is not
-    finite counts as 0.  Nothing is read back."""
+    finite counts as 0.  table: PF.instance_table's dict for (gt_instance, gt_class, pred["scene_offsets"], n_instances) -- its
+    cls and scene are then taken instead of being derived here; the metrics are the same bits.  Nothing is read back."""
     dev = pred["instance"].device
     if self.device is None:
       self.device = dev
@@ -293,10 +430,13 @@ class InstanceBenchmarkEvaluator:
     n, C = gi.shape[0], self.num_labels
     offs = pred["scene_offsets"].to(device=dev, dtype=torch.int64)
     B = offs.shape[0] - 1
-    row_scene = torch.searchsorted(offs, torch.arange(n, device=dev), right=True) - 1
-    ok = (gi >= 0) & (gi < G)
-    cls = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], gc[ok], "amax", include_self=True)
-    scene = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], row_scene[ok], "amax", include_self=True)
+    if table is not None:
+      cls, scene = _table_cls_scene(table, G)
+    else:
+      row_scene = torch.searchsorted(offs, torch.arange(n, device=dev), right=True) - 1
+      ok = (gi >= 0) & (gi < G)
+      cls = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], gc[ok], "amax", include_self=True)
+      scene = torch.full((G,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, gi[ok], row_scene[ok], "amax", include_self=True)
     scored = (cls >= 0) & (cls < C)
     for s in self.stuff_classes:
       scored = scored & (cls != s)

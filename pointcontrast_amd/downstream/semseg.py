@@ -583,6 +583,17 @@ class SegmentationInputPipeline:
     """scenes: a list of (xyz float64 [n, 3], feats [n, 3] in 0..255, labels [n]).  draws None: AugmentationDraws.identity
     (requires aug.augment False).  Returns coords int32 [M, 4], feats float32 [M, 3], target int32 [M], transformation float64
     [B', 16]; limit_numpoints > 0 keeps the leading scenes whose voxels fit (cfl_collate_fn, transforms.py:251-283)."""
+    st = self.stage_upload(scenes, draws)
+    self.stage_voxelize(st)
+    counts, _ = self.stage_read_back(st)
+    pick, nb, total = self.stage_select(st, counts, limit_numpoints)
+    return self.stage_colour(st, pick, nb, total)
+
+  # The stages of a call, in order (downstream.insseg.InstanceInputPipeline runs the same ones with its own in between).  Every
+  # host-to-device copy of a batch is in stage_upload, its ONE device-to-host copy in stage_read_back; the others only enqueue.
+  def stage_upload(self, scenes, draws=None, extra_labels=()):
+    """The batch on the device: a dict with B, draws, offs (host) / offs_dev, xyz, feats, labels, flags, mats, trans_ratio,
+    elastic_on, params ([B, 12] or None) and, per index k of extra_labels, extra[k] = column k of the scenes as int32 [n]."""
     aug, dev, B = self.aug, self.device, len(scenes)
     assert B >= 1, "at least one scene"
     if draws is None:
@@ -593,29 +604,52 @@ class SegmentationInputPipeline:
     offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int64)
     for s in scenes:
       assert torch.as_tensor(s[0]).dtype == torch.float64, "xyz: float64 [n, 3]"
-    xyz = torch.cat([torch.as_tensor(s[0]).reshape(-1, 3) for s in scenes]).to(dev)
-    feats = torch.cat([torch.as_tensor(s[1]).reshape(-1, 3).float() for s in scenes]).to(dev)
-    labels = torch.cat([torch.as_tensor(np.asarray(s[2])).reshape(-1).to(torch.int32) for s in scenes]).to(dev)
-    flags = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def column(k):
+      return torch.cat([torch.as_tensor(np.asarray(s[k])).reshape(-1).to(torch.int32) for s in scenes]).to(dev)
+    st = dict(B=B, draws=draws, offs=offs, offs_dev=offs.to(dev),
+              xyz=torch.cat([torch.as_tensor(s[0]).reshape(-1, 3) for s in scenes]).to(dev),
+              feats=torch.cat([torch.as_tensor(s[1]).reshape(-1, 3).float() for s in scenes]).to(dev), labels=column(2),
+              extra={k: column(k) for k in extra_labels}, flags=torch.zeros(B, dtype=torch.int32, device=dev),
+              mats=torch.from_numpy(draws.mats.reshape(B, 16)).to(dev),
+              trans_ratio=torch.from_numpy(draws.trans_ratio).to(dev) if aug.clip_bound is not None else None,
+              elastic_on=None, params=None)
+    if draws.elastic_noise is not None and draws.elastic_on is not None:
+      st["elastic_on"] = torch.tensor([int(bool(v)) for v in draws.elastic_on], dtype=torch.int32).to(dev)
+    if any(x is not None for x in (draws.flip, draws.contrast, draws.translation, draws.jitter_std)):
+      st["params"] = torch.from_numpy(PF.seg_color_params(B, draws.flip, draws.contrast, draws.translation, draws.jitter_std)).to(dev)
+    return st
+
+  def stage_voxelize(self, st):
+    """Elastic distortion, pcmi_seg_transform and pcmi_seg_quantize: st["t"], st["q"]."""
+    aug, draws, xyz, flags = self.aug, st["draws"], st["xyz"], st["flags"]
     if draws.elastic_noise is not None:  # the stages chain on the device: each reads the extents the one before left in xyz
       assert aug.elastic_params and len(draws.elastic_noise) == len(aug.elastic_params), "one noise block per elastic stage"
-      offs_dev = offs.to(dev)
-      active = None if draws.elastic_on is None else torch.tensor([int(bool(v)) for v in draws.elastic_on], dtype=torch.int32)
       for (g, mag), noise in zip(aug.elastic_params, draws.elastic_noise):
         noise = noise.clone()  # smoothed in place
-        grid = PF.elastic_blur(xyz, offs_dev, g, noise, active, flags)
-        PF.elastic_apply(xyz, offs_dev, g, mag, noise, grid)
-    t = PF.seg_transform(xyz, offs, torch.from_numpy(draws.mats.reshape(B, 16)), aug.clip_bound,
-                         torch.from_numpy(draws.trans_ratio) if aug.clip_bound is not None else None, flags=flags)
-    q = PF.seg_quantize(t["vox"], offs, labels, t["keep"], t["scene_min"], aug.ignore_label, flags=flags)
-    # the batch's one read-back: counts [B + 1], flags [B], per-scene minima [3 B]
-    host = torch.cat([q["counts"], flags.to(torch.int64), t["scene_min"].reshape(-1).to(torch.int64)]).cpu().numpy()
+        grid = PF.elastic_blur(xyz, st["offs_dev"], g, noise, st["elastic_on"], flags)
+        PF.elastic_apply(xyz, st["offs_dev"], g, mag, noise, grid)
+    st["t"] = PF.seg_transform(xyz, st["offs_dev"], st["mats"], aug.clip_bound, st["trans_ratio"], flags=flags)
+    st["q"] = PF.seg_quantize(st["t"]["vox"], st["offs_dev"], st["labels"], st["t"]["keep"], st["t"]["scene_min"], aug.ignore_label,
+                              flags=flags)
+
+  def stage_read_back(self, st, extra=()):
+    """The batch's one read-back: counts [B + 1], flags [B], per-scene minima [3 B], then the int64 device tensors of `extra`.
+    Raises on a flagged scene.  Returns (the voxels per scene as a list, the host values of `extra` as one array)."""
+    B, t = st["B"], st["t"]
+    host = torch.cat([st["q"]["counts"], st["flags"].to(torch.int64), t["scene_min"].reshape(-1).to(torch.int64)] +
+                     [e.reshape(-1).to(torch.int64) for e in extra]).cpu().numpy()
     msg = PF.seg_flags_message(host[B + 1:2 * B + 1])
     if msg:
       raise ValueError(msg)
-    self.last_scene_min = host[2 * B + 1:].reshape(B, 3)
-    counts = [int(c) for c in host[:B]]
-    coords, index, target = q["coords"], q["index"], q["labels"]
+    self.last_scene_min = host[2 * B + 1:5 * B + 1].reshape(B, 3)
+    return [int(c) for c in host[:B]], host[5 * B + 1:]
+
+  def stage_select(self, st, counts, limit_numpoints=0):
+    """RandomDropout and the batch limit on the voxel rows, from the counts on the host.  Returns (pick, nb, total): pick(t) =
+    the surviving rows of a row array t, nb the scenes kept, total their rows."""
+    aug, dev, B, draws = self.aug, self.device, st["B"], st["draws"]
+    counts, kept = list(counts), None
     if draws.dropout_on is not None and any(draws.dropout_on):
       # RandomDropout on the voxel rows (transforms.py:153-158): the int(m (1 - ratio)) rows of the scene with the smallest keys,
       # in row order (a stable sort of the keys, then a sort of the winners); the counts are already on the host
@@ -631,18 +665,24 @@ class SegmentationInputPipeline:
         start += counts[b]
         counts[b] = len(rows)
       kept = torch.cat(kept)
-      coords, index, target = coords[kept].contiguous(), index[kept].contiguous(), target[kept].contiguous()
     nb, total = B, 0
     for b in range(B):  # cfl_collate_fn: stop before the scene that would exceed the limit
       if limit_numpoints and total + counts[b] > limit_numpoints:
         nb = b
         break
       total += counts[b]
-    coords, index, target = coords[:total], index[:total], target[:total]
-    params = None
-    if any(x is not None for x in (draws.flip, draws.contrast, draws.translation, draws.jitter_std)):
-      params = torch.from_numpy(PF.seg_color_params(B, draws.flip, draws.contrast, draws.translation, draws.jitter_std)[:max(nb, 1)])
+
+    def pick(t):
+      return (t if kept is None else t[kept].contiguous())[:total]
+    return pick, nb, total
+
+  def stage_colour(self, st, pick, nb, total, coords=None, index=None, target=None):
+    """pcmi_seg_color_augment on the surviving rows of the quantizer's arrays (or of the ones given) -> the call's result."""
+    aug, draws, q = self.aug, st["draws"], st["q"]
+    coords = pick(q["coords"] if coords is None else coords)
+    index, target = pick(q["index"] if index is None else index), pick(q["labels"] if target is None else target)
+    params = None if st["params"] is None else st["params"][:max(nb, 1)]
     normals = None if draws.normals is None else draws.normals[:total]
-    out = PF.seg_color_augment(feats, coords, max(nb, 1), index, target, params, normals, aug.normalize_color,
+    out = PF.seg_color_augment(st["feats"], coords, max(nb, 1), index, target, params, normals, aug.normalize_color,
                                self._lut, aug.ignore_label)
-    return coords, out, target, t["aligned"][:nb]
+    return coords, out, target, st["t"]["aligned"][:nb]

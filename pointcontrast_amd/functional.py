@@ -1185,10 +1185,11 @@ def seg_hist(pred, idx, labels, num_labels, hist=None, missing=None, want_point_
 # augmentations of the reference (downstream/semseg/lib/voxelizer.py, lib/transforms.py) for a batch of scans.  None of these
 # is differentiable and none synchronises; errors arrive in `flags` (int32 [B], SEG_FLAG_* bits per scene).
 # ---------------------------------------------------------------------------------------------------------------------
-SEG_FLAG_RANGE, SEG_FLAG_SPAN, SEG_FLAG_ELASTIC = 1, 2, 4
+SEG_FLAG_RANGE, SEG_FLAG_SPAN, SEG_FLAG_ELASTIC, SEG_FLAG_CROP = 1, 2, 4, 8
 SEG_FLAG_NAMES = {SEG_FLAG_RANGE: "a point is not finite or its voxel coordinate is outside +-2^20",
                   SEG_FLAG_SPAN: "a voxel coordinate lies 2^18 or more above the scene's minimum",
-                  SEG_FLAG_ELASTIC: "the elastic noise grid does not fit its capacity block"}
+                  SEG_FLAG_ELASTIC: "the elastic noise grid does not fit its capacity block",
+                  SEG_FLAG_CROP: "no step of the crop ladder brings the scene within max_voxels (it has the last step's window)"}
 
 
 def seg_flags_message(flags_host):
@@ -2278,6 +2279,91 @@ def instance_centroids(coords, instance, n_instances):
   s, cnt = torch.empty((G, 3), dtype=torch.int64, device=dev), torch.empty(G, dtype=torch.int64, device=dev)
   check(lib.pcmi_instance_centroids(ptr(c), ptr(inst), n, G, ptr(s), ptr(cnt), cur_stream(dev)))
   return s, cnt
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The input of instance-segmentation fine-tuning (csrc/insseg_input.hip; the rules are include/pcmi.h's): batch-unique
+# instance indices from per-scene raw ids, the per-instance table, the per-scene crop.  Integer arithmetic, bit-exact against
+# tests/insseg_input_ref.py.  offsets stays on the device and nothing synchronises: the arrays hold n rows of capacity and a
+# row outside every scene is neither read nor written, so the calls chain behind seg_quantize before its counts are read.
+# ---------------------------------------------------------------------------------------------------------------------
+ROW_SCAN_BLOCK = 2048              # kScanBlock of csrc/rowscan.h: the rows one workgroup of the numbering scan covers
+ROW_SCAN_LEVEL = 256 * 2048        # kThreads kScanBlock: the rows from which its second level takes another round
+CROP_MAX_STEPS = 32                # kMaxSteps of insseg_input.hip
+
+
+def instance_relabel(raw, offsets, keep=None):
+  """pcmi_instance_relabel: raw int32 [n] (per-scene instance ids, any non-negative integers; the same id in two scenes is two
+  instances), offsets [B + 1], keep uint8 / bool [n] (None: all).  A row with raw < 0 or keep == 0 is in no instance; instances
+  are numbered in ascending order of their lowest row (components_compact's convention).  Returns a dict of device tensors:
+  instance int32 [n] (-1: in none), first_row int32 [n] (the lowest row of instance g at g, valid up to the count), counts
+  int64 [B + 1] (the instances that begin in each scene, then their sum)."""
+  require_cuda(raw, "instance_relabel")
+  dev = raw.device
+  r, offs = _i32c(raw, dev).reshape(-1), _offsets(offsets, dev)
+  n, B = r.shape[0], offs.shape[0] - 1
+  kp = None if keep is None else keep.to(device=dev, dtype=torch.uint8).contiguous()
+  assert offs.dim() == 1 and B >= 1 and (kp is None or kp.shape == (n,)), "instance_relabel: offsets [B + 1], keep [n]"
+  inst = torch.empty(n, dtype=torch.int32, device=dev)
+  first = torch.empty(n, dtype=torch.int32, device=dev)
+  counts = torch.empty(B + 1, dtype=torch.int64, device=dev)
+  ws, wsb = ws_args(lib.pcmi_instance_relabel_workspace_bytes(n), dev)
+  check(lib.pcmi_instance_relabel(ptr(r), ptr(kp), ptr(offs), n, B, ptr(inst), ptr(first), ptr(counts), ws, wsb, cur_stream(dev)))
+  return dict(instance=inst, first_row=first, counts=counts)
+
+
+def instance_table(instance, klass, coords, offsets, n_instances):
+  """pcmi_instance_table: instance [n], klass [n] or None, coords int32 [n, 4] or None, offsets [B + 1], G = n_instances (a
+  host integer) -> a dict of device tensors per instance: size, scene int32 [G] (the largest scene among its rows, -1 without
+  rows), cls int32 [G] (max(-1, max klass); None without klass), sum int64 [G, 3], box_min, box_max int32 [G, 3] (None without
+  coords).  sum / size are instance_centroids' outputs; cls / scene what both instance evaluators derive (their table=)."""
+  require_cuda(instance, "instance_table")
+  dev = instance.device
+  inst, offs = _i32c(instance, dev).reshape(-1), _offsets(offsets, dev)
+  n, B, G = inst.shape[0], offs.shape[0] - 1, int(n_instances)
+  kl = None if klass is None else _i32c(klass, dev).reshape(-1)
+  c = None if coords is None else _i32c(coords, dev)
+  assert offs.dim() == 1 and B >= 1 and G >= 0 and (kl is None or kl.shape[0] == n) and (c is None or c.shape == (n, 4)), \
+      "instance_table: offsets [B + 1], klass [n], coords [n, 4]"
+  size, scene = torch.empty(G, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.int32, device=dev)
+  cls = None if kl is None else torch.empty(G, dtype=torch.int32, device=dev)
+  s = None if c is None else torch.empty((G, 3), dtype=torch.int64, device=dev)
+  lo, hi = (None, None) if c is None else (torch.empty((G, 3), dtype=torch.int32, device=dev) for _ in range(2))
+  check(lib.pcmi_instance_table(ptr(inst), ptr(kl), ptr(c), ptr(offs), n, B, G, ptr(size), ptr(scene), ptr(cls), ptr(s), ptr(lo), ptr(hi),
+                                cur_stream(dev)))
+  return dict(size=size, scene=scene, cls=cls, sum=s, box_min=lo, box_max=hi)
+
+
+def seg_crop_ladder(coords, offsets, axes, sides, draws, max_voxels, flags=None):
+  """pcmi_seg_crop_ladder -- this project's own rule, in the spirit of PointGroup's crop, not a restatement, untuned.  coords
+  int32 [n, 4] (seg_quantize's), offsets [B + 1] over its rows, axes: the two horizontal columns (1 ... 3), sides: [S, 2] host
+  integers (window sides in voxels, each column non-increasing), draws uint32-valued [B, S, 2] (an int64 or int32 tensor of
+  values in [0, 2^32)), max_voxels.  A scene above max_voxels rows takes the lowest step whose window holds at most max_voxels
+  of its rows, else the last one and SEG_FLAG_CROP.  Returns a dict of device tensors: rows int64 [n] (the kept rows, ascending;
+  0 beyond the count), counts int64 [B + 1], step int32 [B] (-1: not cropped), flags int32 [B] (ORed into the one passed in)."""
+  import numpy as np
+  require_cuda(coords, "seg_crop_ladder")
+  dev = coords.device
+  c, offs = _i32c(coords, dev), _offsets(offsets, dev)
+  assert c.dim() == 2 and c.shape[1] == 4 and offs.dim() == 1 and offs.shape[0] >= 2, "seg_crop_ladder: coords [n, 4], offsets [B + 1]"
+  n, B = c.shape[0], offs.shape[0] - 1
+  sd = np.ascontiguousarray(np.asarray(sides, dtype=np.int64).reshape(-1, 2))
+  assert np.all(np.abs(sd) < 2**31), "seg_crop_ladder: sides fit int32"
+  sd, S = sd.astype(np.int32), sd.shape[0]
+  d = torch.as_tensor(draws)
+  if d.dtype != torch.int32:  # values in [0, 2^32) -> their 32 bits
+    d = d.to(torch.int64).bitwise_and(0xFFFFFFFF)
+    d = torch.where(d >= 2**31, d - 2**32, d).to(torch.int32)
+  d = d.to(dev).contiguous()
+  assert d.numel() == B * S * 2, "seg_crop_ladder: draws [B, S, 2]"
+  flags = _seg_flags(flags, B, dev)
+  rows = torch.zeros(n, dtype=torch.int64, device=dev)
+  counts = torch.empty(B + 1, dtype=torch.int64, device=dev)
+  step = torch.full((B,), -1, dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_seg_crop_ladder_workspace_bytes(n, B), dev)
+  check(lib.pcmi_seg_crop_ladder(ptr(c), ptr(offs), n, B, int(axes[0]), int(axes[1]), sd.ctypes.data_as(C.POINTER(C.c_int32)), S, ptr(d),
+                                 int(max_voxels), ptr(rows), ptr(counts), ptr(step), ptr(flags), ws, wsb, cur_stream(dev)))
+  return dict(rows=rows, counts=counts, step=step, flags=flags)
 
 
 # ---- instance masks by the benchmark protocol (csrc/insbench.hip): restated from the rules of ScanNet's script, never run
