@@ -1866,6 +1866,51 @@ int pcmi_kmeans_pp_step(const float* feat, int64_t ld, int64_t n, const int64_t*
                         const int32_t* last, const uint64_t* draw, float* mind2, int32_t* next, void* ws, size_t ws_bytes,
                         pcmi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Dual-set instance proposals (csrc/proposals.hip) -- the second half of PointGroup's grouping: the voxels are clustered where
+ * they are AND where their offsets send them, the union of the sets is reduced by non-maximum suppression on mask IoU, and
+ * the survivors are OVERLAPPING masks.  The reference has no counterpart; the rules are stated here.
+ * Overlapping proposals are a membership matrix member [n, S] (int32, leading dimension ld >= S): column s is one partition
+ * of the rows into proposals, -1 for none; 1 <= S <= 4 (PCMI_ERR_INVALID otherwise).  By the convention of cluster_proposals
+ * column s names the slots [s M, (s + 1) M) of the per-proposal arrays [P = S M]; the two calls below only need the values
+ * to lie in [0, P).  prop_scene [P] (int32): the proposal's scene, a value outside [0, B) for an unused slot.
+ * Every call: one stream, no host synchronisation; a refused call enqueues nothing; integer atomics only; every output is the
+ * same bits from run to run.  1 <= B <= 65535, 1 <= Kmax (a HOST bound on the proposals of one scene), B Kmax^2 < 2^31
+ * (PCMI_ERR_INVALID otherwise); Kmax > 1024: PCMI_ERR_UNSUPPORTED (Kmax x Kmax suppression bits are 128 KiB of LDS).
+ *
+ * pcmi_proposal_overlap -> all outputs initialised by the call but `dropped`:
+ *     size [P] (int32)         the entries of member equal to p (a row naming p in two columns counts twice)
+ *     scene_count [B] (int32)  the USED slots of scene b: the p with prop_scene[p] == b -- the true number, also beyond Kmax
+ *     local [P] (int32)        the proposal's index within its scene: its rank among the used slots of that scene in
+ *                              ascending slot order; -1 for an unused slot and for every slot of rank >= Kmax: a scene with
+ *                              more than Kmax used slots keeps its first Kmax, and dropped [1] (int64, nullable) += the rest
+ *     inter [B, Kmax, Kmax] (int32)  inter[b, i, j] = the rows that name both proposal i and proposal j of scene b (by
+ *                              `local`) in two DIFFERENT columns: symmetric, the diagonal zero
+ *   A member value outside [0, P) counts nowhere; a pair of proposals of different scenes, a pair with a dropped or unused
+ *   proposal and a pair (a, a) count nowhere.
+ *   Launches: one workgroup per scene scans prop_scene in slot order (a block scan per 256 slots with a carry); one lane per
+ *   row adds its S sizes and its at most S (S - 1) / 2 pairs (both orientations).  Rows of one object stand together, so a
+ *   wave's lanes mostly hold one value per column: where a column is uniform over the wave's rows its first lane adds the lane
+ *   count, and so for a pair of uniform columns (pcmi_instance_overlap's aggregation); any other wave adds lane by lane.
+ *   n < 2^31 - 256.  ws: pcmi_proposal_overlap_workspace_bytes(P), 4-byte aligned.
+ * pcmi_proposal_nms: inter, size, local, scene_count as above, prop_class [P] (int32), score [P] (fp64) -> keep [P] (int32): 1
+ *   for a kept proposal, 0 for every other slot (suppressed, not a candidate, unused, dropped).  Per scene:
+ *     candidates  local >= 0, size >= 1, class >= 0, score finite and >= min_score
+ *     rank        descending score (compared as fp64), ascending slot among equal scores
+ *     in rank order, a candidate that is still alive is kept and clears every LATER candidate j with
+ *       (double) inter / (double) (size_i + size_j - inter) > nms_iou
+ *     -- one fp64 division, a strict comparison, a NaN quotient suppresses nothing.  A suppressed candidate suppresses nobody.
+ *   The test does not look at classes (PointGroup's rule).  One workgroup per scene: ranks by counting, the suppression matrix
+ *   as bits in LDS, one wave sweeping it (pcmi_box_nms's scheme); 256 threads for Kmax <= 256, 1024 beyond.
+ * ------------------------------------------------------------------------------------------ */
+size_t pcmi_proposal_overlap_workspace_bytes(int64_t P);
+int pcmi_proposal_overlap(const int32_t* member, int64_t ld, int64_t n, int S, const int32_t* prop_scene, int64_t P, int64_t B,
+                          int Kmax, int32_t* size, int32_t* local, int32_t* scene_count, int32_t* inter, int64_t* dropped, void* ws,
+                          size_t ws_bytes, pcmi_stream_t stream);
+int pcmi_proposal_nms(const int32_t* inter, const int32_t* size, const int32_t* local, const int32_t* scene_count,
+                      const int32_t* prop_scene, const int32_t* prop_class, const double* score, int64_t P, int64_t B, int Kmax,
+                      double nms_iou, double min_score, int32_t* keep, pcmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -332,6 +332,10 @@ PROTOTYPES = {
     "pcmi_kmeans_assign": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, C.c_int, c_i64] + [c_vp] * 9 + [c_sz, c_vp]),
     "pcmi_kmeans_pp_step_workspace_bytes": (c_sz, [c_i64]),
     "pcmi_kmeans_pp_step": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, C.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pcmi_proposal_overlap_workspace_bytes": (c_sz, [c_i64]),
+    "pcmi_proposal_overlap": (C.c_int, [c_vp, c_i64, c_i64, C.c_int, c_vp, c_i64, c_i64, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                        c_vp]),
+    "pcmi_proposal_nms": (C.c_int, [c_vp] * 7 + [c_i64, c_i64, C.c_int, C.c_double, C.c_double, c_vp, c_vp]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():

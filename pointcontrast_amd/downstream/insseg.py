@@ -11,10 +11,15 @@ Dual-Set Point Grouping for 3D Instance Segmentation").  The reference has no co
   metrics     mask AP at IoU 0.25, 0.5 and 0.5:0.95:0.05 (pcmi_instance_overlap, pcmi_instance_match, pcmi_det_ap)
               -> InstanceEvaluator
 
+  proposals   PointGroup's dual set: BOTH coordinate sets clustered (the voxels where they are, and shifted), the union reduced by
+              non-maximum suppression on mask IoU (pcmi_proposal_overlap, pcmi_proposal_nms) -> cluster_proposals: overlapping
+              masks as a membership matrix member [n, S], which both evaluators take; the trainer's dual_set=True
+
 Stated differences from PointGroup: no cap on the neighbours of a row (theirs: 50, which makes the result
-depend on the row order), <= radius where they have <, ONE clustering on the shifted coordinates (no second one on the
-unshifted ones) and no ScoreNet (an instance's score is the mean softmax probability of its rows for their class).  The
-AP is VOC-style -- each prediction is matched to its best ground truth, the rule of APCalculator -- and NOT ScanNet's
+depend on the row order), <= radius where they have <, and no ScoreNet (an instance's score is the mean softmax probability of
+its rows for their class, and the non-maximum suppression ranks by it); cluster_instances alone (dual_set=False, the default)
+is moreover ONE clustering on the shifted coordinates with disjoint masks.  nms_iou, min_score and max_per_scene are untuned.
+The AP is VOC-style -- each prediction is matched to its best ground truth, the rule of APCalculator -- and NOT ScanNet's
 benchmark script, which has void-overlap and minimum-region rules.
 
   benchmark   those rules -- minimum region size, void and small-region overlap, the script's claim rule and its integration
@@ -60,8 +65,20 @@ def cluster_instances(coords, offsets, logits, scene_offsets, voxel_size, radius
   inst_class, inst_size, inst_scene int32 [max_instances] (-1 / 0 from the count on), inst_score float64 [max_instances], and
   scene_offsets int64 [B + 1] as given."""
   PF.require_cuda(logits, "cluster_instances")
+  xyz, offs, group, score = _semantic_rows(coords, logits, scene_offsets, voxel_size, stuff_classes)
+  if shifted:
+    xyz = xyz + offsets.to(device=logits.device, dtype=torch.float32)
+  label = PF.radius_components(xyz, offs, group, radius)
+  out = PF.components_compact(label, offs, group, min_points, max_instances)
+  return dict(instance=out["instance"], count=out["count"], inst_class=out["group"], inst_size=out["size"], inst_scene=out["scene"],
+              inst_score=PF.instance_scores(score, out["instance"], out["size"]), scene_offsets=offs)
+
+
+def _semantic_rows(coords, logits, scene_offsets, voxel_size, stuff_classes):
+  """The semantic pass both clusterings share -> (xyz float32 [n, 3] unshifted, scene_offsets int64 [B + 1] on the device,
+  group int32 [n]: the arg-max class, -1 for stuff_classes; score float32 [n]: the row's softmax probability of that class)."""
   dev = logits.device
-  n, C = logits.shape
+  n = logits.shape[0]
   c = coords.to(device=dev, dtype=torch.int32)
   offs = torch.as_tensor(scene_offsets).to(device=dev, dtype=torch.int64).contiguous()
   rows = PF.seg_eval_rows(logits, torch.full((n,), -1, dtype=torch.int32, device=dev), -1)
@@ -70,13 +87,62 @@ def cluster_instances(coords, offsets, logits, scene_offsets, voxel_size, radius
   group = pred
   for s in stuff_classes:
     group = torch.where(pred == int(s), torch.full_like(pred, -1), group)
-  xyz = c[:, 1:4].to(torch.float32) * float(voxel_size)
-  if shifted:
-    xyz = xyz + offsets.to(device=dev, dtype=torch.float32)
-  label = PF.radius_components(xyz, offs, group, radius)
-  out = PF.components_compact(label, offs, group, min_points, max_instances)
-  return dict(instance=out["instance"], count=out["count"], inst_class=out["group"], inst_size=out["size"], inst_scene=out["scene"],
-              inst_score=PF.instance_scores(score, out["instance"], out["size"]), scene_offsets=offs)
+  return c[:, 1:4].to(torch.float32) * float(voxel_size), offs, group, score
+
+
+PROPOSAL_SETS = ("unshifted", "shifted")  # PointGroup's P and Q
+
+
+def cluster_proposals(coords, offsets, logits, scene_offsets, voxel_size, radius=0.03, min_points=50, stuff_classes=(0, 1),
+                      max_instances=4096, sets=PROPOSAL_SETS, nms_iou=0.3, min_score=0.0, max_per_scene=1024):
+  """PointGroup's dual-set grouping: OVERLAPPING proposals from a network's output, on the device without a read-back.  The
+  arguments of cluster_instances; sets: 1 to 4 of "unshifted" (the voxels where they are: PointGroup's set P, which keeps
+  objects whose offsets are poor) and "shifted" (where their offsets send them: set Q, which separates objects that touch).
+  The semantic pass runs once; per set radius_components -> components_compact -> instance_scores as in cluster_instances; then
+  pcmi_proposal_overlap and pcmi_proposal_nms over the union (per scene, descending score, a kept proposal clears every later
+  one with mask IoU > nms_iou; classes are not looked at).  With M = max_instances and S = len(sets), set s owns the proposal
+  slots [s M, (s + 1) M) of every per-proposal array [P = S M]; the sets are never packed together.
+  nms_iou 0.3 is PointGroup's number, untuned here; min_score 0 because PointGroup's 0.09 belongs to ScoreNet's scores, not
+  to a mean softmax probability; max_per_scene (<= 1024) bounds the proposals of ONE scene over all sets: the first in slot
+  order stay, the rest are counted in `dropped` and never kept.  All three are untuned.
+  Returns cluster_instances' keys --
+    instance int32 [n]        the kept proposal of the highest rank (score, then lowest slot) among the row's columns, -1: none
+    count int32 [S]           components_compact's count per set (the true number, also beyond max_instances)
+    inst_class int32 [P]      -1 for an unused AND for a suppressed slot (what the evaluators skip)
+    inst_size int32 [P]       the size BEFORE suppression;  inst_scene int32 [P], inst_score float64 [P], scene_offsets
+  -- plus member int32 [n, S] (the row's proposal per set, -1 none or suppressed), keep int32 [P] (pcmi_proposal_nms's) and
+  dropped int64 [1]."""
+  PF.require_cuda(logits, "cluster_proposals")
+  sets = tuple(sets)
+  assert 1 <= len(sets) <= PF.PROPOSAL_MAX_SETS and all(s in PROPOSAL_SETS for s in sets), \
+      "cluster_proposals: sets: 1 to %d of %s" % (PF.PROPOSAL_MAX_SETS, PROPOSAL_SETS)
+  dev, M = logits.device, int(max_instances)
+  xyz, offs, group, score = _semantic_rows(coords, logits, scene_offsets, voxel_size, stuff_classes)
+  moved = xyz + offsets.to(device=dev, dtype=torch.float32) if "shifted" in sets else None
+  parts = []
+  for s, name in enumerate(sets):
+    label = PF.radius_components(moved if name == "shifted" else xyz, offs, group, radius)
+    out = PF.components_compact(label, offs, group, min_points, M)
+    out["score"] = PF.instance_scores(score, out["instance"], out["size"])
+    out["member"] = torch.where(out["instance"] >= 0, out["instance"] + s * M, out["instance"])
+    parts.append(out)
+  cat = lambda k: torch.cat([p[k] for p in parts])  # noqa: E731
+  member = torch.stack([p["member"] for p in parts], 1)
+  cls, scene, inst_score = cat("group"), cat("scene"), cat("score")
+  dropped = torch.zeros(1, dtype=torch.int64, device=dev)
+  ov = PF.proposal_overlap(member, scene, offs.shape[0] - 1, max_per_scene, dropped)
+  keep = PF.proposal_nms(ov, scene, cls, inst_score, nms_iou, min_score)
+  kept = keep > 0
+  if member.numel():
+    member = torch.where((member >= 0) & kept[member.clamp(min=0).long()], member, torch.full_like(member, -1))
+  best, best_score = member[:, 0], inst_score[member[:, 0].clamp(min=0).long()] if member.numel() else inst_score[:0]
+  for s in range(1, len(sets)):  # a later column has the higher slots: it wins only with a strictly higher score
+    m = member[:, s]
+    sc = inst_score[m.clamp(min=0).long()]
+    take = (m >= 0) & ((best < 0) | (sc > best_score))
+    best, best_score = torch.where(take, m, best), torch.where(take, sc, best_score)
+  return dict(instance=best.contiguous(), count=cat("count"), inst_class=torch.where(kept, cls, torch.full_like(cls, -1)), inst_size=cat("size"),
+              inst_scene=scene, inst_score=inst_score, scene_offsets=offs, member=member, keep=keep, dropped=dropped)
 
 
 class InstanceInputPipeline(SegmentationInputPipeline):
@@ -177,12 +243,15 @@ def batch_instance_ids(per_scene_raw_ids, device=None):
 class InstanceSegmentationTrainer(SegmentationTrainer):
   """SegmentationTrainer with a head of num_labels + 3 outputs.  train_iter(coords, feats, target, instance) = forward,
   cross-entropy + the two offset losses, ONE backward, SGD + PolyLR step; predict(coords, feats) = cluster_instances of the
-  inference forward.  An inference forward returns the num_labels class columns, so evaluate / validate /
+  inference forward -- with dual_set=True cluster_proposals (PointGroup's dual set: overlapping masks after mask NMS at nms_iou,
+  0.3 being PointGroup's number, untuned here), which validate_scenes and benchmark_original_pointcloud then score.  An inference forward returns the num_labels class columns, so evaluate / validate /
   test_original_pointcloud of the parent score the semantic head unchanged.  A pre-training checkpoint loads as in the parent:
   by name and shape, so the head stays random.  **Nobody has trained a network with this head to a benchmark number yet.**"""
 
-  def __init__(self, num_labels, voxel_size=0.02, radius=0.03, min_points=50, stuff_classes=(0, 1), max_instances=4096, **kw):
+  def __init__(self, num_labels, voxel_size=0.02, radius=0.03, min_points=50, stuff_classes=(0, 1), max_instances=4096, dual_set=False,
+               nms_iou=0.3, **kw):
     super().__init__(num_labels + 3, **kw)
+    self.dual_set, self.nms_iou = bool(dual_set), float(nms_iou)
     self.num_labels = num_labels  # the classes; the model has num_labels + 3 outputs
     self.voxel_size, self.radius, self.min_points = float(voxel_size), float(radius), int(min_points)
     self.stuff_classes, self.max_instances = tuple(stuff_classes), int(max_instances)
@@ -231,7 +300,8 @@ class InstanceSegmentationTrainer(SegmentationTrainer):
 
   @torch.no_grad()
   def predict(self, coords, feats):
-    """cluster_instances of the inference forward (eval mode): its dict."""
+    """cluster_instances of the inference forward (eval mode): its dict.  With dual_set: cluster_proposals' dict (overlapping
+    masks after non-maximum suppression at nms_iou), which both evaluators and step_points take as well."""
     self.model.eval()
     self._full_width = True
     try:
@@ -239,6 +309,9 @@ class InstanceSegmentationTrainer(SegmentationTrainer):
     finally:
       self._full_width = False
     C = self.num_labels
+    if self.dual_set:
+      return cluster_proposals(coords, out[:, C:C + 3], out[:, :C], scene_offsets_of(coords), self.voxel_size, self.radius, self.min_points,
+                               self.stuff_classes, self.max_instances, nms_iou=self.nms_iou)
     return cluster_instances(coords, out[:, C:C + 3], out[:, :C], scene_offsets_of(coords), self.voxel_size, self.radius, self.min_points,
                              self.stuff_classes, self.max_instances)
 
@@ -293,6 +366,16 @@ class InstanceSegmentationTrainer(SegmentationTrainer):
     return self.benchmark_evaluator.compute_metrics()
 
 
+def _member_overlap(member, gi, P, G):
+  """instance_overlap for overlapping masks: member int32 [n, S] (cluster_proposals'), gi int64 [n] -> (inter [P, G], pred_size
+  [P], gt_size [G]).  The predictions' side is taken over the n S ENTRIES -- member.reshape(-1) against the ground truth repeated
+  per column -- and the ground truth's sizes over the n ROWS: every row stands S times among the entries, so the entry count
+  is exactly S times the row count, and a row in two masks does not count its ground truth twice."""
+  S = member.shape[1]
+  inter, ps, gs = PF.instance_overlap(member.reshape(-1), gi.repeat_interleave(S), P, G)
+  return inter, ps, torch.div(gs, S, rounding_mode="floor")
+
+
 def _table_cls_scene(table, G):
   """(cls, scene) int64 [G] of PF.instance_table's dict: what the evaluators' scatter_reduce derivation gives."""
   assert table["cls"] is not None and table["cls"].shape[0] == G and table["scene"].shape[0] == G, "table: instance_table's dict with klass, for G"
@@ -321,7 +404,8 @@ class InstanceEvaluator:
     -1 for none; gt_class [n]: the row's ground-truth class (an instance takes the largest class among its rows; instances of
     stuff_classes or of a class outside [0, num_labels) are not scored).  n_instances None: gt_instance.max() + 1.  table:
     PF.instance_table's dict for (gt_instance, gt_class, pred["scene_offsets"], n_instances) -- its cls and scene are then taken
-    instead of being derived here; the metrics are the same bits."""
+    instead of being derived here; the metrics are the same bits.  A pred with `member` [n, S] (cluster_proposals' dict:
+    overlapping masks) is scored on its entries instead of `instance`: _member_overlap."""
     dev = pred["instance"].device
     if self.device is None:
       self.device = dev
@@ -343,7 +427,10 @@ class InstanceEvaluator:
       scored = scored & (cls != s)
     cls = torch.where(scored, cls, torch.full_like(cls, -1))
     P = pred["inst_size"].shape[0]
-    inter, ps, gs = PF.instance_overlap(pred["instance"], gi, P, G)
+    if "member" in pred:
+      inter, ps, gs = _member_overlap(pred["member"], gi, P, G)
+    else:
+      inter, ps, gs = PF.instance_overlap(pred["instance"], gi, P, G)
     best_gt, best_iou = PF.instance_match(inter, ps, gs, pred["inst_scene"], pred["inst_class"], scene, cls)
     self._iou.append(best_iou)
     self._gid.append(torch.where(best_gt >= 0, best_gt + self.n_gt, best_gt))
@@ -418,7 +505,9 @@ class InstanceBenchmarkEvaluator:
     stuff_classes or of a class outside [0, num_labels) are not scored: their rows are void).  n_instances None:
     gt_instance.max() + 1.  The size of a prediction is its rows among the n given, NOT pred["inst_size"]; a score that is not
     finite counts as 0.  table: PF.instance_table's dict for (gt_instance, gt_class, pred["scene_offsets"], n_instances) -- its
-    cls and scene are then taken instead of being derived here; the metrics are the same bits.  Nothing is read back."""
+    cls and scene are then taken instead of being derived here; the metrics are the same bits.  A pred with `member` [n, S]
+    (cluster_proposals' dict: overlapping masks) is scored on its entries instead of `instance`: overlaps, sizes and void
+    overlaps of the predictions over the n S entries, the ground truth's sizes over the n rows.  Nothing is read back."""
     dev = pred["instance"].device
     if self.device is None:
       self.device = dev
@@ -442,8 +531,13 @@ class InstanceBenchmarkEvaluator:
       scored = scored & (cls != s)
     cls = torch.where(scored, cls, torch.full_like(cls, -1))
     P = pred["inst_class"].shape[0]
-    inter, ps, gs = PF.instance_overlap(pred["instance"], gi, P, G)
-    void = PF.instance_void_overlap(pred["instance"], gi, scored, P)
+    if "member" in pred:
+      inter, ps, gs = _member_overlap(pred["member"], gi, P, G)
+      S = pred["member"].shape[1]
+      void = PF.instance_void_overlap(pred["member"].reshape(-1), gi.repeat_interleave(S), scored, P)
+    else:
+      inter, ps, gs = PF.instance_overlap(pred["instance"], gi, P, G)
+      void = PF.instance_void_overlap(pred["instance"], gi, scored, P)
     score = pred["inst_score"].to(device=dev, dtype=torch.float64)
     score = torch.where(torch.isfinite(score), score, torch.zeros_like(score))
     if self.npos is None:
@@ -480,7 +574,12 @@ class InstanceBenchmarkEvaluator:
       inst = torch.where(idx >= 0, vi[idx.clamp(min=0)], torch.full_like(idx, -1, dtype=torch.int32))
     else:
       inst = torch.full((idx.shape[0],), -1, dtype=torch.int32, device=dev)
-    self.step(dict(pred, instance=inst, scene_offsets=offs), point_instance, point_class)
+    carried = dict(pred, instance=inst, scene_offsets=offs)
+    if "member" in pred:  # overlapping masks: every column of the voxel's row, by the same gather
+      vm = pred["member"].to(torch.int32)[order]
+      none = torch.full((idx.shape[0], vm.shape[1]), -1, dtype=torch.int32, device=dev)
+      carried["member"] = torch.where((idx >= 0).reshape(-1, 1), vm[idx.clamp(min=0)], none) if vm.shape[0] else none
+    self.step(carried, point_instance, point_class)
     return inst
 
   def compute_metrics(self, keep_curves=False):

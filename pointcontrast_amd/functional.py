@@ -2435,6 +2435,65 @@ def instance_bench_ap(entry_flag, score, cls_offs, npos, curves=False):
   return dict(ap=ap, prec=prec, rec=rec)
 
 
+# ---- dual-set instance proposals (csrc/proposals.hip; the rules are include/pcmi.h's): overlapping proposals as a membership
+# matrix, their pairwise intersections per scene, non-maximum suppression on mask IoU.  Nothing synchronises. ---------------------
+PROPOSAL_MAX_SETS = 4         # kMaxSets of proposals.hip
+PROPOSAL_MAX_PER_SCENE = 1024  # kMaxK
+
+
+def _member_rows(member, who):
+  require_cuda(member, who)
+  assert member.dim() == 2 and 1 <= member.shape[1] <= PROPOSAL_MAX_SETS, "%s: member [n, S], 1 <= S <= %d" % (who, PROPOSAL_MAX_SETS)
+  m = member if member.dtype == torch.int32 else member.to(torch.int32)
+  return m if (m.stride(1) == 1 and m.stride(0) >= m.shape[1]) or m.shape[0] == 0 else m.contiguous()
+
+
+def proposal_overlap(member, prop_scene, n_scenes, max_per_scene=PROPOSAL_MAX_PER_SCENE, dropped=None):
+  """pcmi_proposal_overlap: member int32 [n, S] (column s: one partition of the rows into proposals, -1 none; may be a column
+  slice of a wider tensor), prop_scene [P] (outside [0, n_scenes): an unused slot), max_per_scene: a host bound <= 1024 on the
+  proposals of one scene -> a dict of device tensors: size int32 [P] (the entries of member naming p), local int32 [P] (the
+  proposal's index within its scene in ascending slot order; -1 unused, or beyond max_per_scene), scene_count int32 [B] (the
+  used slots of each scene, the true number), inter int32 [B, Kmax, Kmax] (the rows naming both proposals in two different
+  columns, by local index: symmetric, zero diagonal).  dropped int64 [1] (optional) += the proposals beyond max_per_scene."""
+  m = _member_rows(member, "proposal_overlap")
+  dev = m.device
+  sc = _i32c(prop_scene, dev).reshape(-1)
+  n, S, P, B, K = m.shape[0], m.shape[1], sc.shape[0], int(n_scenes), int(max_per_scene)
+  assert dropped is None or (dropped.dtype == torch.int64 and dropped.numel() == 1 and dropped.device == dev), \
+      "proposal_overlap: dropped int64 [1]"
+  size, local = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.int32, device=dev)
+  count = torch.empty(max(B, 0), dtype=torch.int32, device=dev)
+  ok = B >= 1 and 1 <= K <= PROPOSAL_MAX_PER_SCENE and B * K * K < 2**31  # (the call refuses anything else before it touches inter)
+  inter = torch.empty((B, K, K) if ok else (0, 0, 0), dtype=torch.int32, device=dev)
+  ws, wsb = ws_args(lib.pcmi_proposal_overlap_workspace_bytes(P), dev)
+  check(lib.pcmi_proposal_overlap(ptr(m), m.stride(0) if n else S, n, S, ptr(sc), P, B, K, ptr(size), ptr(local), ptr(count), ptr(inter),
+                                  ptr(dropped), ws, wsb, cur_stream(dev)))
+  return dict(size=size, local=local, scene_count=count, inter=inter)
+
+
+def proposal_nms(overlap, prop_scene, prop_class, score, nms_iou, min_score=0.0):
+  """pcmi_proposal_nms: overlap = proposal_overlap's dict for the same prop_scene; prop_class int32 [P], score float64 [P] ->
+  keep int32 [P]: per scene, the candidates (local >= 0, size >= 1, class >= 0, a finite score >= min_score) in descending score
+  (equal scores: ascending slot); one still alive is kept and clears every later one with inter / (size_i + size_j - inter) >
+  nms_iou in float64 (strict; classes are not looked at).  0 for every slot that is not kept."""
+  inter = overlap["inter"]
+  require_cuda(inter, "proposal_nms")
+  dev = inter.device
+  assert inter.dim() == 3 and inter.shape[1] == inter.shape[2] and inter.dtype == torch.int32 and inter.is_contiguous(), \
+      "proposal_nms: inter int32 [B, Kmax, Kmax]"
+  B, K = inter.shape[0], inter.shape[1]
+  size, local, count = (_i32c(overlap[k], dev).reshape(-1) for k in ("size", "local", "scene_count"))
+  sc, cl = _i32c(prop_scene, dev).reshape(-1), _i32c(prop_class, dev).reshape(-1)
+  s = _f64c(score, dev, "proposal_nms").reshape(-1)
+  P = sc.shape[0]
+  assert size.shape[0] == local.shape[0] == cl.shape[0] == s.shape[0] == P and count.shape[0] == B, \
+      "proposal_nms: size, local, prop_scene, prop_class, score [P], scene_count [B]"
+  keep = torch.empty(P, dtype=torch.int32, device=dev)
+  check(lib.pcmi_proposal_nms(ptr(inter), ptr(size), ptr(local), ptr(count), ptr(sc), ptr(cl), ptr(s), P, B, K, float(nms_iou),
+                              float(min_score), ptr(keep), cur_stream(dev)))
+  return keep
+
+
 class OffsetLossFunction(Function):
   """PointGroup's two offset losses (pcmi_offset_loss_fwd / _bwd): pred float32 [n, 3] (may be a column slice of the logits),
   target float32 [n, 3], instance [n] (a row counts iff instance >= 0) -> (norm_loss, dir_loss), float64 scalars."""
