@@ -4,6 +4,7 @@ hipcc cross-compiles without a GPU, so this runs in the build container as well
 as on the GPU box.  Objects go to pointcontrast_amd/csrc/_build/, the library to
 pointcontrast_amd/libpcmi.so (git-ignored, but it travels with gpurun).
 """
+import glob
 import hashlib
 import os
 import subprocess
@@ -40,9 +41,7 @@ def _digest(paths):
 
 
 def _headers():
-  return [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "spconv_args.h"), os.path.join(CSRC, "spconv_plan.h"), os.path.join(CSRC, "spconv_wgrad_plan.h"),
-          os.path.join(CSRC, "x3_split.h"), os.path.join(CSRC, "exact.h"), os.path.join(CSRC, "cellgrid.h"), os.path.join(CSRC, "blockscan.h"), os.path.join(CSRC, "rowscan.h"),
-          os.path.join(HERE, "..", "include", "pcmi.h")]
+  return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "pcmi.h")]
 
 
 def sources_digest():

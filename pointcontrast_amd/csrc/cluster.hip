@@ -29,8 +29,8 @@
 #include <algorithm>
 
 #include "blockscan.h"
-#include "cellgrid.h"
 #include "exact.h"
+#include "firstrow.h"
 #include "internal.h"
 #include "rowscan.h"
 
@@ -43,7 +43,6 @@ constexpr int kThreads = 256;  // 4 waves: one per SIMD of a CU
 constexpr int kWaves = kThreads / 64;
 constexpr int64_t kMaxRows = 1ll << 29;    // the table has 2 n + B slots, indexed with 32 bits
 constexpr int64_t kMaxScenes = 1ll << 20;
-constexpr uint32_t kNoSlot = 0xffffffffu;
 constexpr double kFix = 1073741824.0;      // 2^30: the fixed point of pcmi_instance_scores
 
 // the exclusive scan of int32 values in row order (three launches): rowscan.h

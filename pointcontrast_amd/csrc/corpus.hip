@@ -19,9 +19,10 @@
 
 #include <algorithm>
 
-#include "cellgrid.h"
 #include "common.h"
+#include "cubscan.h"
 #include "exact.h"
+#include "firstrow.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -192,7 +193,7 @@ __global__ void vc_origin_kernel(const double* __restrict__ partial, int64_t n_c
 // voxel index floor((p - origin) / voxel) per axis; first[slot] = smallest point index of the voxel (grid: chunks x frames)
 __global__ void vc_insert_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offsets,
                                  const double* __restrict__ origin, double voxel, const uint32_t* __restrict__ tbase,
-                                 const uint32_t* __restrict__ tmask, uint64_t* keys, int32_t* first, uint32_t* __restrict__ slot_of,
+                                 const uint32_t* __restrict__ tmask, uint64_t* keys, uint32_t* first, uint32_t* __restrict__ slot_of,
                                  int32_t* err) {
   const int64_t f = blockIdx.y;
   const int64_t b = offsets[f], e = offsets[f + 1];
@@ -201,25 +202,23 @@ __global__ void vc_insert_kernel(const double* __restrict__ pts, const int64_t* 
     int64_t c[3];
     if (!cells_of(d, voxel, c)) {
       atomicAdd(err, 1);
-      slot_of[i] = 0xffffffffu;
+      slot_of[i] = kNoSlot;
       continue;
     }
-    const uint32_t slot = claim_slot(keys, tbase[f], tmask[f] + 1, cell_key(c[0], c[1], c[2]));
-    atomicMin(&first[slot], (int32_t)i);
-    slot_of[i] = slot;
+    slot_of[i] = claim_first(keys, tbase[f], tmask[f] + 1, cell_key(c[0], c[1], c[2]), first, i);
   }
 }
 
-__global__ void vc_flag_kernel(int64_t n, const int32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
+__global__ void vc_flag_kernel(int64_t n, const uint32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
                                int32_t* __restrict__ flags, int32_t* __restrict__ iota) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  flags[i] = first[slot_of[i]] == (int32_t)i ? 1 : 0;
+  flags[i] = is_first_row(slot_of[i], first, i) ? 1 : 0;
   iota[i] = (int32_t)i;
 }
 
 // vid[i] = output row of the voxel of point i (= number of first occurrences before the voxel's first point)
-__global__ void vc_vid_kernel(int64_t n, const int32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
+__global__ void vc_vid_kernel(int64_t n, const uint32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
                               const int32_t* __restrict__ pos, int32_t* __restrict__ vid) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) vid[i] = pos[first[slot_of[i]]];
@@ -341,11 +340,6 @@ __global__ void __launch_bounds__(kThreads) ov_count_kernel(const double* __rest
     atomicAdd(&counts[(t0 + threadIdx.x) * n_frames + j], acc[threadIdx.x]);
 }
 
-static size_t scan_bytes(int64_t n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)std::max<int64_t>(n, 1));
-  return b;
-}
 static size_t sort_bytes(int64_t n) {
   size_t b = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr,
@@ -376,7 +370,7 @@ extern "C" {
 
 size_t pcmi_corpus_backproject_workspace_bytes(int64_t n_frames, int64_t height, int64_t width) {
   const int64_t n = std::max<int64_t>(n_frames * height * width, 1);
-  return 2 * align_up((size_t)n * 4, 256) + align_up(scan_bytes(n), 256) + 1024;
+  return 2 * align_up((size_t)n * 4, 256) + cub_scan_bytes<int32_t>(n) + 1024;
 }
 
 int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width, const double* intrinsic_host,
@@ -393,7 +387,7 @@ int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t hei
   Carve cv{(char*)ws, ws_bytes};
   int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
   int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
-  size_t tb = scan_bytes(n);
+  const size_t tb = cub_scan_bytes<int32_t>(n);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(flags && pos && temp, PCMI_ERR_WORKSPACE, "corpus_backproject: workspace too small");
   const double* A = intrinsic_host;  // 4x4 row-major (intrinsic_depth.txt)
@@ -402,7 +396,7 @@ int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t hei
   const unsigned gn = (unsigned)ceil_div(n, kThreads);
   bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, flags);
   PCMI_LAUNCH_CHECK();
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, flags, pos, (int)n, st));
+  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
   bp_points_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, poses, depth_shift, pos, points, nan_count);
   PCMI_LAUNCH_CHECK();
   bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(flags, pos, n_frames, hw, offsets);
@@ -436,7 +430,7 @@ int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64
   Carve cv{(char*)ws, ws_bytes};
   int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
   int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
-  size_t tb = scan_bytes(n);
+  const size_t tb = cub_scan_bytes<int32_t>(n);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(flags && pos && temp, PCMI_ERR_WORKSPACE, "corpus_backproject_color: workspace too small");
   const double *A = intrinsic_host, *Ac = color_intrinsic_host;  // 4x4 row-major (intrinsic_depth.txt, intrinsic_color.txt)
@@ -447,7 +441,7 @@ int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64
   const unsigned gn = (unsigned)ceil_div(n, kThreads);
   bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, flags);
   PCMI_LAUNCH_CHECK();
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, flags, pos, (int)n, st));
+  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
   bp_color_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, depth_shift, color_images, color_height, color_width, cam,
                                            pos, color, (unsigned long long*)uncolored);
   PCMI_LAUNCH_CHECK();
@@ -466,7 +460,7 @@ size_t pcmi_corpus_voxel_centroids_workspace_bytes(int64_t n_points, int64_t n_f
   const size_t slots = (size_t)vc_table_slots(n, F);
   return align_up(slots * 8, 256) + align_up(slots * 4, 256) + 7 * align_up((size_t)n * 4, 256) +
          align_up((size_t)(n + 1) * 4, 256) + align_up((size_t)F * chunks * 24, 256) + align_up((size_t)F * 24, 256) +
-         2 * align_up((size_t)F * 4, 256) + align_up(std::max(scan_bytes(n), sort_bytes(n)), 256) + 256 + 1024;
+         2 * align_up((size_t)F * 4, 256) + align_up(std::max(cub_scan_bytes<int32_t>(n), sort_bytes(n)), 256) + 256 + 1024;
 }
 
 int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, const int64_t* offsets_host, int64_t n_frames,
@@ -490,7 +484,7 @@ int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, co
   const size_t slots = (size_t)vc_table_slots(n, n_frames);
   Carve cv{(char*)ws, ws_bytes};
   uint64_t* keys = (uint64_t*)cv.take(slots * 8);
-  int32_t* first = (int32_t*)cv.take(slots * 4);
+  uint32_t* first = (uint32_t*)cv.take(slots * 4);
   uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
   int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
   int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
@@ -504,13 +498,13 @@ int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, co
   uint32_t* tbase = (uint32_t*)cv.take((size_t)n_frames * 4);
   uint32_t* tmask = (uint32_t*)cv.take((size_t)n_frames * 4);
   int32_t* err = (int32_t*)cv.take(256);
-  size_t tb = std::max(scan_bytes(n), sort_bytes(n));
+  size_t tb = std::max(cub_scan_bytes<int32_t>(n), sort_bytes(n));
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && first && slot_of && flags && pos && vid && iota && svid && sidx && start && partial && origin && tbase &&
                    tmask && err && temp,
                PCMI_ERR_WORKSPACE, "corpus_voxel_centroids: workspace too small");
   PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, slots * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(first, 0x7f, slots * 4, st));  // 0x7f7f7f7f > any point index
+  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, slots * 4, st));
   PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
   vc_min_partial_kernel<<<dim3((unsigned)n_chunks, (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, n_chunks, partial);
   PCMI_LAUNCH_CHECK();
@@ -528,8 +522,7 @@ int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, co
                "corpus_voxel_centroids: %d points fall outside 2^20 voxels of their frame's min bound (or are not finite)", herr);
   vc_flag_kernel<<<gn, kThreads, 0, st>>>(n, first, slot_of, flags, iota);
   PCMI_LAUNCH_CHECK();
-  size_t tb2 = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, flags, pos, (int)n, st));
+  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
   int32_t last[2] = {0, 0};
   PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], flags + n - 1, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipMemcpyAsync(&last[1], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
@@ -542,7 +535,7 @@ int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, co
   PCMI_LAUNCH_CHECK();
   int end_bit = 1;
   while ((1ll << end_bit) < n_vox) ++end_bit;
-  tb2 = tb;  // stable LSD radix sort: the points of a voxel keep ascending index order
+  size_t tb2 = tb;  // stable LSD radix sort: the points of a voxel keep ascending index order
   PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, tb2, vid, svid, iota, sidx, (int)n, 0, end_bit, st));
   vc_starts_kernel<<<gn, kThreads, 0, st>>>(svid, n, n_vox, start);
   PCMI_LAUNCH_CHECK();

@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <climits>
 
-#include "cellgrid.h"
+#include "firstrow.h"
 #include "internal.h"
 #include "rowscan.h"
 
@@ -27,32 +27,14 @@ constexpr int kMaxScenes = 1023;        // as pcmi_seg_quantize
 constexpr int64_t kMaxRows = 1ll << 29; // table of 2 n slots, scanned with 32-bit counts
 constexpr int kMaxSteps = 32;           // steps of a crop ladder: one bit each in a row's mask
 constexpr int kLdsScenes = 4;           // scenes from a workgroup's first on whose step counts are gathered in LDS
-constexpr uint32_t kNoSlot = 0xffffffffu;   // a row of a scene that belongs to no instance
+// slot_of: kNoSlot for a row of a scene that belongs to no instance, and
 constexpr uint32_t kOutside = 0xfffffffeu;  // a row outside every scene (the table has at most 2^30 slots)
 
 static bool batch_ok(int64_t n, int64_t B) { return n >= 0 && n < (1ll << 31) - kThreads && B >= 1 && B <= kMaxScenes; }
 static unsigned grid_for(int64_t n) { return (unsigned)ceil_div(std::max<int64_t>(n, 1), kThreads); }
-static int64_t table_cap(int64_t n) {
-  int64_t c = 1024;
-  while (c < 2 * n) c <<= 1;
-  return c;
-}
 
 // true when every lane of the wave holds the same key: one lane then speaks for all.  Every lane must call.
 __device__ inline bool wave_same(int key) { return __ballot(key == __shfl(key, 0, 64)) == ~0ull; }
-
-// counts[b] = pos[offs[b + 1]] - pos[offs[b]] with the offsets clamped into [0, n]; counts[B] = pos[n]: pos is the exclusive
-// scan over n + 1 flags of which the last, and those of rows outside every scene, are 0
-__device__ inline void write_counts(int64_t t, const int64_t* __restrict__ offs, int B, int64_t n, const int32_t* __restrict__ pos,
-                                    int64_t* __restrict__ counts) {
-  if (t > B) return;
-  if (t == B) {
-    counts[B] = pos[n];
-  } else {
-    const int64_t lo = std::min<int64_t>(std::max<int64_t>(offs[t], 0), n), hi = std::min<int64_t>(std::max<int64_t>(offs[t + 1], lo), n);
-    counts[t] = pos[hi] - pos[lo];
-  }
-}
 
 // ---- relabel ---------------------------------------------------------------------------------------------------------------
 // pass 1: the row's (scene, raw id) claims its slot; first[slot] = the lowest row of the instance
@@ -65,10 +47,7 @@ __global__ __launch_bounds__(kThreads) void rl_insert_kernel(const int32_t* __re
   uint32_t slot = b < 0 ? kOutside : kNoSlot;
   if (b >= 0) {
     const int32_t r = raw[i];
-    if (r >= 0 && (!keep || keep[i])) {
-      slot = claim_slot(keys, 0, cap, ((uint64_t)(uint32_t)b << 32) | (uint32_t)r);
-      atomicMin(&first[slot], (uint32_t)i);
-    }
+    if (r >= 0 && (!keep || keep[i])) slot = claim_first(keys, 0, cap, ((uint64_t)(uint32_t)b << 32) | (uint32_t)r, first, i);
   }
   slot_of[i] = slot;
 }
@@ -92,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void rl_write_kernel(int64_t n, const int
                                                             const int32_t* __restrict__ pos, int32_t* __restrict__ instance,
                                                             int32_t* __restrict__ first_row, int64_t* __restrict__ counts) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  write_counts(i, offs, B, n, pos, counts);
+  segment_counts(i, offs, B, n, pos, counts);
   if (i >= n) return;
   const uint32_t slot = slot_of[i];
   if (slot == kOutside) return;
@@ -313,7 +292,7 @@ __global__ __launch_bounds__(kThreads) void cr_write_kernel(int64_t n, const int
                                                             const int32_t* __restrict__ pos, int64_t* __restrict__ rows,
                                                             int64_t* __restrict__ counts) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  write_counts(i, offs, B, n, pos, counts);
+  segment_counts(i, offs, B, n, pos, counts);
   if (i < n && kept[i]) rows[pos[i]] = i;
 }
 

@@ -8,13 +8,12 @@
 //          source point.  Pairs leave sorted by (i, j) -- the order the trainer relies on (sorted by column 0).
 // Both are integer / exactly-rounded fp64 work and bit-exact against oracle/loader_ref.py: every product and sum is an
 // explicit round-to-nearest operation in a fixed order (no FMA contraction), divisions are IEEE.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
-#include "cellgrid.h"
 #include "common.h"
+#include "cubscan.h"
 #include "exact.h"
+#include "firstrow.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -23,24 +22,22 @@ namespace pcmi {
 
 // ---- voxelisation ----------------------------------------------------------------------------------------------
 // A point that is not finite or falls outside +-2^20 voxels has no voxel (cells_of): PCMI_ERR_RANGE.
-__global__ void vox_insert_kernel(const double* __restrict__ xyz, int64_t n, double voxel, uint64_t* keys, int32_t* vals,
+__global__ void vox_insert_kernel(const double* __restrict__ xyz, int64_t n, double voxel, uint64_t* keys, uint32_t* first,
                                   uint32_t cap, uint32_t* slot_of, int32_t* err) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int64_t c[3];
   if (!cells_of(xyz + 3 * i, voxel, c)) {
     atomicAdd(err, 1);
-    slot_of[i] = 0xffffffffu;
+    slot_of[i] = kNoSlot;
     return;
   }
-  const uint32_t slot = claim_slot(keys, 0, cap, cell_key(c[0], c[1], c[2]));
-  atomicMin(&vals[slot], (int32_t)i);  // first occurrence = smallest point index of the voxel
-  slot_of[i] = slot;
+  slot_of[i] = claim_first(keys, 0, cap, cell_key(c[0], c[1], c[2]), first, i);  // first occurrence = smallest point index of the voxel
 }
-__global__ void vox_flag_kernel(int64_t n, const int32_t* __restrict__ vals, const uint32_t* __restrict__ slot_of,
+__global__ void vox_flag_kernel(int64_t n, const uint32_t* __restrict__ first, const uint32_t* __restrict__ slot_of,
                                 int32_t* __restrict__ flags) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) flags[i] = (slot_of[i] != 0xffffffffu && vals[slot_of[i]] == (int32_t)i) ? 1 : 0;
+  if (i < n) flags[i] = is_first_row(slot_of[i], first, i) ? 1 : 0;
 }
 __global__ void vox_compact_kernel(const double* __restrict__ xyz, int64_t n, double voxel, const int32_t* __restrict__ flags,
                                    const int32_t* __restrict__ pos, int32_t* __restrict__ first_idx, int32_t* __restrict__ coords) {
@@ -53,10 +50,6 @@ __global__ void vox_compact_kernel(const double* __restrict__ xyz, int64_t n, do
     coords[3 * p + 1] = (int32_t)floor(xyz[3 * i + 1] / voxel);
     coords[3 * p + 2] = (int32_t)floor(xyz[3 * i + 2] / voxel);
   }
-}
-__global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
 }
 
 // ---- radius matching -------------------------------------------------------------------------------------------
@@ -122,18 +115,6 @@ __global__ void match_kernel(const double* __restrict__ src, int64_t n0, Rigid T
   }
 }
 
-static uint32_t table_cap(int64_t n) {
-  uint32_t c = 1024;
-  while ((int64_t)c < 2 * n) c <<= 1;
-  return c;
-}
-
-static size_t scan_temp_bytes(int64_t n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr, (int)std::max<int64_t>(n, 1));
-  return b + 256;
-}
-
 }  // namespace pcmi
 
 using namespace pcmi;
@@ -141,8 +122,8 @@ using namespace pcmi;
 extern "C" {
 
 size_t pcmi_voxelize_workspace_bytes(int64_t n) {
-  const uint32_t cap = table_cap(n);
-  return (size_t)cap * 12 + (size_t)n * 12 + 2 * (size_t)n * 8 + scan_temp_bytes(n) + 8 * 256 + 1024;
+  const uint32_t cap = (uint32_t)table_cap(n);
+  return (size_t)cap * 12 + (size_t)n * 12 + 2 * (size_t)n * 8 + cub_scan_bytes<int32_t>(n) + 8 * 256 + 1024;
 }
 
 int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* first_index, int32_t* coords,
@@ -154,27 +135,25 @@ int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* firs
   hipStream_t st = as_stream(stream);
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_voxelize_workspace_bytes(n), PCMI_ERR_WORKSPACE, "voxelize: workspace too small");
   Carve cv{(char*)ws, ws_bytes};
-  const uint32_t cap = table_cap(n);
+  const uint32_t cap = (uint32_t)table_cap(n);
   uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  int32_t* vals = (int32_t*)cv.take((size_t)cap * 4);
+  uint32_t* first = (uint32_t*)cv.take((size_t)cap * 4);
   uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
   int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
   int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
   int32_t* err = (int32_t*)cv.take(256);
-  const size_t tb = scan_temp_bytes(n);
+  const size_t tb = cub_scan_bytes<int32_t>(n);
   void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && vals && slot_of && flags && pos && err && temp, PCMI_ERR_WORKSPACE, "voxelize: workspace too small");
+  PCMI_REQUIRE(keys && first && slot_of && flags && pos && err && temp, PCMI_ERR_WORKSPACE, "voxelize: workspace too small");
   PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, (size_t)cap * 4, st));
   PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
-  const unsigned gc = (unsigned)ceil_div(cap, 256), gn = (unsigned)ceil_div(n, 256);
-  fill_i32_kernel<<<gc, 256, 0, st>>>(vals, cap, 0x7fffffff);
+  const unsigned gn = (unsigned)ceil_div(n, 256);
+  vox_insert_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, keys, first, cap, slot_of, err);
   PCMI_LAUNCH_CHECK();
-  vox_insert_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, keys, vals, cap, slot_of, err);
+  vox_flag_kernel<<<gn, 256, 0, st>>>(n, first, slot_of, flags);
   PCMI_LAUNCH_CHECK();
-  vox_flag_kernel<<<gn, 256, 0, st>>>(n, vals, slot_of, flags);
-  PCMI_LAUNCH_CHECK();
-  size_t tb2 = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, flags, pos, (int)n, st));
+  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
   int32_t host[3] = {0, 0, 0};  // last flag, last pos, error count
   PCMI_HIP_CHECK(hipMemcpyAsync(&host[0], flags + n - 1, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipMemcpyAsync(&host[1], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
@@ -188,8 +167,8 @@ int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* firs
 }
 
 size_t pcmi_match_radius_workspace_bytes(int64_t n0, int64_t n1) {
-  const uint32_t cap = table_cap(n1);
-  return (size_t)cap * 12 + (size_t)n1 * 4 + 2 * (size_t)n0 * 8 + scan_temp_bytes(n0) + 8 * 256 + 1024;
+  const uint32_t cap = (uint32_t)table_cap(n1);
+  return (size_t)cap * 12 + (size_t)n1 * 4 + 2 * (size_t)n0 * 8 + cub_scan_bytes<int64_t>(n0) + 8 * 256 + 1024;
 }
 
 int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host, const double* dst, int64_t n1, double radius,
@@ -202,14 +181,14 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   hipStream_t st = as_stream(stream);
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_match_radius_workspace_bytes(n0, n1), PCMI_ERR_WORKSPACE, "match_radius: workspace too small");
   Carve cv{(char*)ws, ws_bytes};
-  const uint32_t cap = table_cap(n1);
+  const uint32_t cap = (uint32_t)table_cap(n1);
   uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
   int32_t* head = (int32_t*)cv.take((size_t)cap * 4);
   int32_t* next = (int32_t*)cv.take((size_t)n1 * 4);
   int64_t* count = (int64_t*)cv.take((size_t)n0 * 8);
   int64_t* offs = (int64_t*)cv.take((size_t)n0 * 8);
   int32_t* err = (int32_t*)cv.take(256);
-  const size_t tb = scan_temp_bytes(n0);
+  const size_t tb = cub_scan_bytes<int64_t>(n0);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && head && next && count && offs && err && temp, PCMI_ERR_WORKSPACE, "match_radius: workspace too small");
   Rigid T;
@@ -222,8 +201,7 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   PCMI_LAUNCH_CHECK();
   match_kernel<false><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, keys, head, cap, next, count, nullptr, nullptr, err);
   PCMI_LAUNCH_CHECK();
-  size_t tb2 = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, count, offs, (int)n0, st));
+  if (int rc = cub_scan_excl(temp, tb, count, offs, n0, st)) return rc;
   int64_t last[2] = {0, 0};
   int32_t herr = 0;
   PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], count + n0 - 1, 8, hipMemcpyDeviceToHost, st));

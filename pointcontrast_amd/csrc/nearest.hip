@@ -25,12 +25,11 @@
 // holds with room to spare, and where the product under- or overflows the comparison below can only fail to stop.  The walk
 // stops at radius r only if it HAS a candidate and best_d2 < bound2(r), strictly: nothing outside can then win, nor tie and
 // win by its lower row.  Whoever has not stopped after kMaxRing goes to the fallback scan, which is the rule itself.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
-#include "cellgrid.h"
+#include "cubscan.h"
 #include "exact.h"
+#include "firstrow.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -45,7 +44,6 @@ constexpr int kMaxScenes = 1024;       // pack_key's 10-bit batch field
 constexpr int64_t kMaxRef = 1ll << 29; // table of 2 m slots, scanned with 32-bit counts
 constexpr int kMaxClasses = 64;        // as segeval.hip: 64 x 64 x 4 bytes = 16 KB of LDS
 constexpr int kFallbackGrid = 2048;    // workgroups of the fallback launch (each walks the list with this stride)
-constexpr uint32_t kNoSlot = 0xffffffffu;
 
 // ---- voxel centres -------------------------------------------------------------------------------------------------------------
 constexpr int kMatPerLaunch = 32;  // 32 x 12 doubles = 3 KB of kernel arguments
@@ -274,18 +272,6 @@ __global__ __launch_bounds__(kThreads) void seg_hist_kernel(const int32_t* __res
   if (tid == 0 && missing && s_missing) atomicAdd(missing, (unsigned long long)s_missing);
 }
 
-static int64_t table_cap(int64_t m) {
-  int64_t c = 1024;
-  while (c < 2 * m) c <<= 1;
-  return c;
-}
-
-static size_t scan_temp_bytes(int64_t items) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)items);
-  return align_up(b + 256, 256);
-}
-
 static bool nn_shape_ok(int64_t m, int64_t n, int64_t B) {
   return m >= 0 && n >= 0 && m < (1ll << 31) && n < (1ll << 31) && B >= 1 && B <= kMaxScenes;
 }
@@ -322,7 +308,7 @@ size_t pcmi_nearest_point_workspace_bytes(int64_t m, int64_t n, int64_t B) {
   const int64_t cap = table_cap(m);
   return align_up((size_t)cap * 8, 256) + 2 * align_up((size_t)(cap + 1) * 4, 256) + align_up((size_t)std::max<int64_t>(m, 1) * 4, 256) +
          align_up((size_t)std::max<int64_t>(m, 1) * sizeof(Rec), 256) + align_up((size_t)(B + 1) * 4, 256) +
-         align_up((size_t)std::max<int64_t>(n, 1) * 4, 256) + scan_temp_bytes(cap + 1);
+         align_up((size_t)std::max<int64_t>(n, 1) * 4, 256) + cub_scan_bytes<int32_t>(cap + 1);
 }
 
 int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, const double* query, const int64_t* query_offs, int64_t n,
@@ -346,7 +332,7 @@ int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, co
   Rec* rec = (Rec*)cv.take((size_t)std::max<int64_t>(m, 1) * sizeof(Rec));
   int32_t* flags = (int32_t*)cv.take((size_t)(B + 1) * 4);  // [B] scene flags, then the fallback list's length
   int32_t* fb_list = (int32_t*)cv.take((size_t)n * 4);
-  const size_t tb = scan_temp_bytes(cap + 1);
+  const size_t tb = cub_scan_bytes<int32_t>(cap + 1);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && count && start && slot_of && rec && flags && fb_list && temp, PCMI_ERR_WORKSPACE,
                "nearest_point: workspace too small");
@@ -360,8 +346,7 @@ int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, co
                                                                            flags);
     PCMI_LAUNCH_CHECK();
   }
-  size_t tb2 = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, count, start, (int)(cap + 1), st));
+  if (int rc = cub_scan_excl(temp, tb, count, start, cap + 1, st)) return rc;
   if (m > 0) {
     nn_fill_kernel<<<(unsigned)ceil_div(m, kThreads), kThreads, 0, st>>>(ref, m, slot_of, start, count, rec);
     PCMI_LAUNCH_CHECK();

@@ -12,13 +12,12 @@
 // order pcmi.h states (no FMA contraction).  The only atomics are integer ones whose result does not depend on the order of
 // arrival (min, or, add), the compare-and-swap that claims a table slot and the exchange that links a target into its cell's
 // list -- neither of which reaches an output: voxels leave in the order of an exclusive scan, matches are sorted per source.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <climits>
 
-#include "cellgrid.h"
+#include "cubscan.h"
 #include "exact.h"
+#include "firstrow.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -31,15 +30,9 @@ constexpr int kMaxPairs = PCMI_PAIR_MAX_PAIRS;
 constexpr int kChunk = PCMI_PAIR_CENTROID_CHUNK;
 constexpr int kPerThread = kChunk / kThreads;
 constexpr int64_t kMaxRows = 1ll << 29;  // segmented tables of 2 n + 2 B slots, addressed with 32 bits
-constexpr uint32_t kNoSlot = 0xffffffffu;
 
 static_assert(kChunk % kThreads == 0 && (kThreads & (kThreads - 1)) == 0, "one workgroup sums a chunk: whole rounds, then a binary tree");
 
-// rows [lo, hi) of cloud c, clipped to [0, n] (offs ascending; a cloud may be empty)
-__device__ inline void cloud_rows(const int64_t* __restrict__ offs, int c, int64_t n, int64_t& lo, int64_t& hi) {
-  lo = std::min<int64_t>(std::max<int64_t>(offs[c], 0), n);
-  hi = std::min<int64_t>(std::max<int64_t>(offs[c + 1], lo), n);
-}
 __device__ inline int64_t chunks_of(int64_t rows) { return (rows + kChunk - 1) / kChunk; }
 
 __device__ inline double raw_at(const void* __restrict__ raw, int f32, int64_t k) {
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void tf_partial_kernel(const void* __rest
     int64_t k = blockIdx.x, lo = 0, hi = 0;
     int c = 0;
     for (; c < nc; ++c) {
-      cloud_rows(offs, c, n, lo, hi);
+      segment_rows(offs, c, n, lo, hi);
       const int64_t cnt = chunks_of(hi - lo);
       if (k < cnt) break;
       k -= cnt;
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void tf_final_kernel(const int64_t* __res
   if (rotate) {
     for (int c = 0; c < 2 * b; ++c) {
       int64_t lo, hi;
-      cloud_rows(offs, c, n, lo, hi);
+      segment_rows(offs, c, n, lo, hi);
       base += chunks_of(hi - lo);
     }
   }
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void tf_final_kernel(const int64_t* __res
     const int c = 2 * b + s;
     if (rotate) {
       int64_t lo, hi;
-      cloud_rows(offs, c, n, lo, hi);
+      segment_rows(offs, c, n, lo, hi);
       const int64_t cnt = chunks_of(hi - lo);
       double m[3] = {0.0, 0.0, 0.0};
       for (int64_t k = 0; k < cnt; ++k)
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void vx_insert_kernel(const double* __res
   uint32_t slot = kNoSlot;
   const int c = segment_of(offs, nc, i);
   int64_t lo = 0, hi = 0;
-  if (c >= 0) cloud_rows(offs, c, n, lo, hi);
+  if (c >= 0) segment_rows(offs, c, n, lo, hi);
   if (c >= 0 && i >= lo && i < hi) {  // (always, for ascending offsets: a segment never takes more rows than it was sized for)
     const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
     int64_t v[3];
@@ -189,8 +182,8 @@ __global__ __launch_bounds__(kThreads) void vx_insert_kernel(const double* __res
     } else if (!cells_of(p, voxel, v)) {
       atomicOr(&flags[c >> 1], PCMI_PAIR_FLAG_RANGE);
     } else {
-      slot = claim_slot(keys, (uint32_t)(2 * lo + c), (uint32_t)(2 * (hi - lo) + 1), cell_key(v[0], v[1], v[2]));
-      atomicMin(&first[slot], (uint32_t)i);  // the first point of the voxel = its lowest row
+      // the first point of the voxel = its lowest row
+      slot = claim_first(keys, (uint32_t)(2 * lo + c), (uint32_t)(2 * (hi - lo) + 1), cell_key(v[0], v[1], v[2]), first, i);
     }
   }
   slot_of[i] = slot;
@@ -203,8 +196,7 @@ __global__ __launch_bounds__(kThreads) void vx_first_kernel(int64_t n, const int
   if (i > n) return;
   int f = 0;
   if (i < n) {
-    const uint32_t slot = slot_of[i];
-    if (slot != kNoSlot && first[slot] == (uint32_t)i) f = flags[segment_of(offs, nc, i) >> 1] == 0 ? 1 : 0;  // a flagged pair yields no rows
+    if (is_first_row(slot_of[i], first, i)) f = flags[segment_of(offs, nc, i) >> 1] == 0 ? 1 : 0;  // a flagged pair yields no rows
   }
   is_first[i] = f;  // (is_first[n] = 0: the scan over n + 1 items ends in the total)
 }
@@ -219,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void vx_write_kernel(const double* __rest
       vox_offsets[nc] = pos[n];
     } else {
       int64_t lo, hi;
-      cloud_rows(offs, (int)i, n, lo, hi);
+      segment_rows(offs, (int)i, n, lo, hi);
       n_vox[i] = pos[hi] - pos[lo];
       vox_offsets[i] = pos[lo];
     }
@@ -258,7 +250,7 @@ __global__ __launch_bounds__(kThreads) void mt_insert_kernel(const double* __res
   const int c = segment_of(voff, nc, j);
   if (c < 0 || !(c & 1)) return;
   int64_t lo, hi;
-  cloud_rows(voff, c, m_max, lo, hi);
+  segment_rows(voff, c, m_max, lo, hi);
   if (j < lo || j >= hi) return;
   const int b = c >> 1;
   const double r = radius[b];
@@ -293,8 +285,8 @@ __global__ __launch_bounds__(128) void mt_match_kernel(const double* __restrict_
     const int c = segment_of(voff, nc, i);
     int64_t hi0 = 0, hi1 = 0;
     if (c >= 0 && !(c & 1)) {
-      cloud_rows(voff, c, m_max, lo0, hi0);
-      cloud_rows(voff, c + 1, m_max, lo1, hi1);
+      segment_rows(voff, c, m_max, lo0, hi0);
+      segment_rows(voff, c + 1, m_max, lo1, hi1);
       if (i >= lo0 && i < hi0 && (!FILL || (flags[c >> 1] == 0 && count[i] > 0))) b = c >> 1;
     }
     if (b >= 0) {
@@ -359,7 +351,7 @@ __global__ __launch_bounds__(kMaxPairs) void mt_pair_kernel(const int64_t* __res
   int64_t rows = 0, q = 0, pc = 0;
   if (b < B) {
     int64_t lo, hi;
-    cloud_rows(voff, 2 * b, m_max, lo, hi);
+    segment_rows(voff, 2 * b, m_max, lo, hi);
     pc = offs[hi] - offs[lo];
     const bool flagged = flags[b] != 0;
     rows = flagged ? 0 : (pc > 0 ? pc : 1);
@@ -412,7 +404,7 @@ __global__ __launch_bounds__(kThreads) void co_kernel(const double* __restrict__
   const int c = segment_of(voff, 2 * B, r);
   if (c < 0) return;
   int64_t lo, hi;
-  cloud_rows(voff, c, m_max, lo, hi);
+  segment_rows(voff, c, m_max, lo, hi);
   if (r < lo || r >= hi) return;
   const int s = c & 1, b = c >> 1;
   const int64_t dst = side[s * (B + 1) + b] + (r - lo);
@@ -442,7 +434,7 @@ __global__ __launch_bounds__(kThreads) void cf_kernel(const uint8_t* __restrict_
   const int c = segment_of(voff, 2 * B, r);
   if (c < 0) return;
   int64_t lo, hi;
-  cloud_rows(voff, c, m_max, lo, hi);
+  segment_rows(voff, c, m_max, lo, hi);
   if (r < lo || r >= hi) return;
   const int s = c & 1, b = c >> 1;
   const int64_t dst = side[s * (B + 1) + b] + (r - lo);
@@ -458,17 +450,6 @@ __global__ __launch_bounds__(kThreads) void cf_kernel(const uint8_t* __restrict_
 }
 
 static bool batch_ok(int64_t n, int64_t B) { return n >= 0 && n < (1ll << 31) - kThreads && B >= 1 && B <= kMaxPairs; }
-
-static size_t scan_temp_bytes32(int64_t items) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)items);
-  return align_up(b + 256, 256);
-}
-static size_t scan_temp_bytes64(int64_t items) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr, (int)items);
-  return align_up(b + 256, 256);
-}
 
 static int64_t max_chunks(int64_t n, int64_t B) { return ceil_div(n, kChunk) + 2 * B; }
 static int64_t table_slots(int64_t n, int64_t B) { return 2 * n + 2 * B; }
@@ -517,7 +498,7 @@ size_t pcmi_pair_voxelize_workspace_bytes(int64_t n, int64_t B) {
   if (!batch_ok(n, B) || n > kMaxRows) return 0;
   const int64_t slots = table_slots(n, B), n1 = std::max<int64_t>(n, 1);
   return align_up((size_t)slots * 8, 256) + align_up((size_t)slots * 4, 256) + align_up((size_t)n1 * 4, 256) +
-         2 * align_up((size_t)(n + 1) * 4, 256) + scan_temp_bytes32(n + 1);
+         2 * align_up((size_t)(n + 1) * 4, 256) + cub_scan_bytes<int32_t>(n + 1);
 }
 
 // replaces pretrain/pointcontrast/lib/ddp_data_loaders.py:228-229, :238-239, :258-259 (sparse_quantize of both frames, floor)
@@ -548,7 +529,7 @@ int pcmi_pair_voxelize(const double* points, const int64_t* offsets, int64_t n, 
   uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
   int32_t* is_first = (int32_t*)cv.take((size_t)(n + 1) * 4);
   int32_t* pos = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  const size_t tb = scan_temp_bytes32(n + 1);
+  const size_t tb = cub_scan_bytes<int32_t>(n + 1);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && first && slot_of && is_first && pos && temp, PCMI_ERR_WORKSPACE, "pair_voxelize: workspace too small");
   PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)slots * 8, st));
@@ -558,8 +539,7 @@ int pcmi_pair_voxelize(const double* points, const int64_t* offsets, int64_t n, 
   PCMI_LAUNCH_CHECK();
   vx_first_kernel<<<(unsigned)ceil_div(n + 1, kThreads), kThreads, 0, st>>>(n, offsets, nc, slot_of, first, flags, is_first);
   PCMI_LAUNCH_CHECK();
-  size_t tb2 = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, is_first, pos, (int)(n + 1), st));
+  if (int rc = cub_scan_excl(temp, tb, is_first, pos, n + 1, st)) return rc;
   vx_write_kernel<<<(unsigned)ceil_div(std::max<int64_t>(n, nc + 1), kThreads), kThreads, 0, st>>>(points, n, offsets, nc, voxel_size, is_first, pos,
                                                                                                   out_points, coords, first_index, n_vox, vox_offsets);
   PCMI_LAUNCH_CHECK();
@@ -572,7 +552,7 @@ size_t pcmi_pair_match_workspace_bytes(int64_t m_max, int64_t B) {
   if (!batch_ok(m_max, B) || m_max > kMaxRows) return 0;
   const int64_t slots = table_slots(m_max, B), m1 = std::max<int64_t>(m_max, 1);
   return align_up((size_t)slots * 8, 256) + align_up((size_t)slots * 4, 256) + align_up((size_t)m1 * 4, 256) +
-         2 * align_up((size_t)(m_max + 1) * 8, 256) + 2 * align_up((size_t)B * 8, 256) + scan_temp_bytes64(m_max + 1);
+         2 * align_up((size_t)(m_max + 1) * 8, 256) + 2 * align_up((size_t)B * 8, 256) + cub_scan_bytes<int64_t>(m_max + 1);
 }
 
 // replaces pretrain/pointcontrast/lib/ddp_data_loaders.py:36-49, :241 (get_matching_indices) and the offsets of :76-83
@@ -599,7 +579,7 @@ int pcmi_pair_match(const double* points, int64_t m_max, const int64_t* vox_offs
   int64_t* offs = (int64_t*)cv.take((size_t)(m_max + 1) * 8);
   int64_t* pair_base = (int64_t*)cv.take((size_t)B * 8);
   int32_t* nq = (int32_t*)cv.take((size_t)B * 8);
-  const size_t tb = scan_temp_bytes64(m_max + 1);
+  const size_t tb = cub_scan_bytes<int64_t>(m_max + 1);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && head && next && count && offs && pair_base && nq && temp, PCMI_ERR_WORKSPACE, "pair_match: workspace too small");
   const unsigned g128 = (unsigned)ceil_div(m_max + 1, 128);
@@ -614,8 +594,7 @@ int pcmi_pair_match(const double* points, int64_t m_max, const int64_t* vox_offs
     mt_match_kernel<false><<<g128, 128, 0, st>>>(points, m_max, vox_offsets, nc, trans, radius, keys, head, next, count, nq, nullptr, nullptr,
                                                 nullptr, nullptr, nullptr, flags);
     PCMI_LAUNCH_CHECK();
-    size_t tb2 = tb;
-    PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, count, offs, (int)(m_max + 1), st));
+    if (int rc = cub_scan_excl(temp, tb, count, offs, m_max + 1, st)) return rc;
   }
   mt_pair_kernel<<<1, kMaxPairs, 0, st>>>(vox_offsets, m_max, (int)B, offs, nq, flags, side_offsets, capacity, pair_counts, pair_base, totals, pairs);
   PCMI_LAUNCH_CHECK();

@@ -11,73 +11,56 @@
 #include <thread>
 #include <vector>
 
-#include "blockscan.h"
 #include "common.h"
 #include "internal.h"
+#include "rowscan.h"
 
 namespace pcmi {
 
-constexpr int kRunItems = 8, kRunBlock = 256 * kRunItems;  // pairs per thread / per workgroup
+// pairs per thread / per workgroup, and the one-workgroup scan of the block counts: rowscan.h
+using rowscan::kScanBlock;
+using rowscan::kScanItems;
+using rowscan::kThreads;
+using rowscan::kWaves;
 
 __device__ inline int run_flag(const int32_t* __restrict__ pairs, int64_t i, int64_t P) {
   if (i >= P) return 0;
   return (i == 0 || pairs[2 * i] != pairs[2 * (i - 1)]) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void runs_count_kernel(const int32_t* __restrict__ pairs, int64_t P, int32_t* __restrict__ block_counts) {
-  __shared__ int s_wave[4];
-  const int64_t i0 = (int64_t)blockIdx.x * kRunBlock + (int64_t)threadIdx.x * kRunItems;
+__global__ __launch_bounds__(kThreads) void runs_count_kernel(const int32_t* __restrict__ pairs, int64_t P, int32_t* __restrict__ block_counts) {
+  __shared__ int s_wave[kWaves];
+  const int64_t i0 = (int64_t)blockIdx.x * kScanBlock + (int64_t)threadIdx.x * kScanItems;
   int c = 0;
 #pragma unroll
-  for (int e = 0; e < kRunItems; ++e) c += run_flag(pairs, i0 + e, P);
+  for (int e = 0; e < kScanItems; ++e) c += run_flag(pairs, i0 + e, P);
   int tot;
-  (void)block_scan_add<4>(c, s_wave, &tot);
+  (void)block_scan_add<kWaves>(c, s_wave, &tot);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = tot;
 }
 
-// exclusive scan of the block counts by one workgroup (<= a few thousand blocks); *n_runs = total
-__global__ __launch_bounds__(256) void runs_scan_kernel(const int32_t* __restrict__ block_counts, int n_blocks, int32_t* __restrict__ block_offs,
-                                                        int64_t* __restrict__ n_runs) {
-  __shared__ int s_wave[4];
-  __shared__ int s_carry;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (int b0 = 0; b0 < n_blocks; b0 += 256) {
-    const int b = b0 + (int)threadIdx.x;
-    const int v = b < n_blocks ? block_counts[b] : 0;
-    int tot;
-    const int ex = block_scan_add<4>(v, s_wave, &tot) - v;
-    const int carry = s_carry;
-    if (b < n_blocks) block_offs[b] = carry + ex;
-    __syncthreads();
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *n_runs = s_carry;
-}
-
-__global__ __launch_bounds__(256) void runs_write_kernel(const int32_t* __restrict__ pairs, int64_t P, const int32_t* __restrict__ block_offs,
-                                                         int32_t* __restrict__ starts) {
-  __shared__ int s_wave[4];
-  const int64_t i0 = (int64_t)blockIdx.x * kRunBlock + (int64_t)threadIdx.x * kRunItems;
-  int f[kRunItems], c = 0;
+__global__ __launch_bounds__(kThreads) void runs_write_kernel(const int32_t* __restrict__ pairs, int64_t P, const int32_t* __restrict__ block_offs,
+                                                              int32_t* __restrict__ starts) {
+  __shared__ int s_wave[kWaves];
+  const int64_t i0 = (int64_t)blockIdx.x * kScanBlock + (int64_t)threadIdx.x * kScanItems;
+  int f[kScanItems], c = 0;
 #pragma unroll
-  for (int e = 0; e < kRunItems; ++e) {
+  for (int e = 0; e < kScanItems; ++e) {
     f[e] = run_flag(pairs, i0 + e, P);
     c += f[e];
   }
   int tot;
-  int pos = block_offs[blockIdx.x] + block_scan_add<4>(c, s_wave, &tot) - c;
+  int pos = block_offs[blockIdx.x] + block_scan_add<kWaves>(c, s_wave, &tot) - c;
 #pragma unroll
-  for (int e = 0; e < kRunItems; ++e)
+  for (int e = 0; e < kScanItems; ++e)
     if (f[e]) starts[pos++] = (int32_t)(i0 + e);
 }
 
 // j-th selected pair: run qi = sampled[j] (or j), key = the floor(u * count)-th pair of that run
-__global__ __launch_bounds__(256) void pair_pick_kernel(const int32_t* __restrict__ pairs, int64_t P, const int32_t* __restrict__ starts,
-                                                        int64_t nq, const float* __restrict__ uniform, const int64_t* __restrict__ sampled,
-                                                        int64_t n_sel, int64_t* __restrict__ q_idx, int64_t* __restrict__ k_idx) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void pair_pick_kernel(const int32_t* __restrict__ pairs, int64_t P, const int32_t* __restrict__ starts,
+                                                             int64_t nq, const float* __restrict__ uniform, const int64_t* __restrict__ sampled,
+                                                             int64_t n_sel, int64_t* __restrict__ q_idx, int64_t* __restrict__ k_idx) {
+  const int64_t j = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (j >= n_sel) return;
   const int64_t qi = sampled ? sampled[j] : j;
   if (qi < 0 || qi >= nq) {  // (an index the host drew for a different n_unique: never with consistent arguments)
@@ -98,7 +81,7 @@ using namespace pcmi;
 extern "C" {
 
 size_t pcmi_pair_select_workspace_bytes(int64_t n_pairs) {
-  const int64_t blocks = ceil_div(std::max<int64_t>(n_pairs, 1), kRunBlock);
+  const int64_t blocks = ceil_div(std::max<int64_t>(n_pairs, 1), kScanBlock);
   return align_up(sizeof(int32_t) * (size_t)std::max<int64_t>(n_pairs, 1), 256) + 2 * align_up(sizeof(int32_t) * (size_t)blocks, 256) + 256;
 }
 
@@ -109,7 +92,7 @@ int pcmi_pair_select(const int32_t* pairs, int64_t n_pairs, int64_t n_unique, co
   PCMI_REQUIRE(ws && ws_bytes >= pcmi_pair_select_workspace_bytes(n_pairs), PCMI_ERR_WORKSPACE, "pair_select: workspace too small");
   if (n_sel == 0) return PCMI_OK;
   hipStream_t st = as_stream(stream);
-  const int64_t blocks = ceil_div(n_pairs, kRunBlock);
+  const int64_t blocks = ceil_div(n_pairs, kScanBlock);
   char* p = (char*)ws;
   int32_t* starts = (int32_t*)p;
   p += align_up(sizeof(int32_t) * (size_t)n_pairs, 256);
@@ -117,14 +100,14 @@ int pcmi_pair_select(const int32_t* pairs, int64_t n_pairs, int64_t n_unique, co
   p += align_up(sizeof(int32_t) * (size_t)blocks, 256);
   int32_t* block_offs = (int32_t*)p;
   p += align_up(sizeof(int32_t) * (size_t)blocks, 256);
-  int64_t* n_runs = (int64_t*)p;
-  runs_count_kernel<<<dim3((unsigned)blocks), 256, 0, st>>>(pairs, n_pairs, block_counts);
+  int32_t* n_runs = (int32_t*)p;  // (written, never read: the host passes n_unique)
+  runs_count_kernel<<<dim3((unsigned)blocks), kThreads, 0, st>>>(pairs, n_pairs, block_counts);
   PCMI_LAUNCH_CHECK();
-  runs_scan_kernel<<<1, 256, 0, st>>>(block_counts, (int)blocks, block_offs, n_runs);
+  rowscan::scan_blocks_kernel<<<1, kThreads, 0, st>>>(block_counts, (int)blocks, block_offs, n_runs);
   PCMI_LAUNCH_CHECK();
-  runs_write_kernel<<<dim3((unsigned)blocks), 256, 0, st>>>(pairs, n_pairs, block_offs, starts);
+  runs_write_kernel<<<dim3((unsigned)blocks), kThreads, 0, st>>>(pairs, n_pairs, block_offs, starts);
   PCMI_LAUNCH_CHECK();
-  pair_pick_kernel<<<dim3((unsigned)ceil_div(n_sel, 256)), 256, 0, st>>>(pairs, n_pairs, starts, n_unique, uniform, sampled, n_sel, q_idx, k_idx);
+  pair_pick_kernel<<<dim3((unsigned)ceil_div(n_sel, kThreads)), kThreads, 0, st>>>(pairs, n_pairs, starts, n_unique, uniform, sampled, n_sel, q_idx, k_idx);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 
+#include "cubscan.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -403,11 +404,6 @@ __global__ void scatter_accumulate_kernel(const float* __restrict__ gout, const 
   gin[bc * N + t] = acc;
 }
 
-static size_t scan_bytes(int64_t n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)std::max<int64_t>(n, 1));
-  return b;
-}
 static size_t sort_bytes(int64_t n) {
   size_t b = 0;
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr,
@@ -451,7 +447,7 @@ static size_t scatter_workspace(int64_t n_idx, int64_t n_targets) {
   n_idx = std::max<int64_t>(n_idx, 1);
   n_targets = std::max<int64_t>(n_targets, 1);
   return 4 * align_up((size_t)n_idx * 4, 256) + 2 * align_up((size_t)(n_targets + 1) * 4, 256) +
-         align_up(std::max(scan_bytes(n_targets + 1), sort_bytes(n_idx)), 256) + 256;
+         align_up(std::max(cub_scan_bytes<int32_t>(n_targets + 1), sort_bytes(n_idx)), 256) + 256;
 }
 
 // The inverse lists of idx [B, L] (targets in [0, N)): the flat source positions p = b L + l of target (b, t) are
@@ -467,7 +463,7 @@ static int build_inverse_lists(const char* who, const int32_t* idx, int64_t B, i
   int32_t* pos = (int32_t*)cv.take((size_t)n_idx * 4);
   int32_t* count = (int32_t*)cv.take((size_t)(n_targets + 1) * 4);
   int32_t* start = (int32_t*)cv.take((size_t)(n_targets + 1) * 4);
-  const size_t tb = std::max(scan_bytes(n_targets + 1), sort_bytes(n_idx));
+  const size_t tb = std::max(cub_scan_bytes<int32_t>(n_targets + 1), sort_bytes(n_idx));
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && keys_sorted && iota && pos && count && start && temp, PCMI_ERR_WORKSPACE, "%s: workspace too small", who);
   unsigned* flag = nullptr;
@@ -485,12 +481,11 @@ static int build_inverse_lists(const char* who, const int32_t* idx, int64_t B, i
     PCMI_HIP_CHECK(hipStreamSynchronize(st));
     PCMI_REQUIRE(!bad, PCMI_ERR_RANGE, "%s: an index is outside [0, %lld)", who, (long long)N);
   }
-  size_t stb = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, stb, count, start, (int)(n_targets + 1), st));
+  if (int rc = cub_scan_excl(temp, tb, count, start, n_targets + 1, st)) return rc;
   int bits = 1;
   while (bits < 31 && (1ll << bits) <= n_targets) ++bits;  // keys 0 .. n_targets
   // a stable sort of (key, flat position): the sources of a target end up in ascending position
-  stb = tb;
+  size_t stb = tb;
   PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, stb, keys, keys_sorted, iota, pos, (int)n_idx, 0, bits, st));
   *start_out = start;
   *pos_out = pos;

@@ -12,13 +12,12 @@
 // order-preserving integer image), whose result does not depend on the order of arrival, and the compare-and-swap that
 // claims a table slot, whose outcome -- WHICH slot a voxel gets -- never reaches an output: rows leave in the order of
 // an exclusive scan over "is the lowest row of its voxel".  Every output is the same bits from run to run.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <climits>
 
-#include "cellgrid.h"
+#include "cubscan.h"
 #include "exact.h"
+#include "firstrow.h"
 #include "internal.h"
 
 #pragma clang fp contract(off)
@@ -31,7 +30,6 @@ constexpr int kMaxScenes = 1023;        // pack_key's 10-bit batch field, minus 
 constexpr int kVoxelLimit = 1 << 20;    // |voxel coordinate| < 2^20 (the loader's range, csrc/loader.hip)
 constexpr int kSpan = 1 << 18;          // 0 <= x - min < 2^18: pack_key's 18-bit fields
 constexpr int64_t kMaxRows = 1ll << 29; // table of 2 n slots, scanned with 32-bit counts
-constexpr uint32_t kNoSlot = 0xffffffffu;
 
 // true when every lane of the wave is active and carries the same scene b >= 0: one lane then speaks for all
 __device__ inline bool wave_uniform(int b, bool active) {
@@ -196,8 +194,7 @@ __global__ __launch_bounds__(kThreads) void q_insert_kernel(const int32_t* __res
       ok = ok && d[a] >= 0 && d[a] < kSpan;
     }
     if (ok) {
-      slot = claim_slot(keys, 0, mask + 1, pack_key(b, (int)d[0] - kCoordBias, (int)d[1] - kCoordBias, (int)d[2] - kCoordBias));
-      atomicMin(&first[slot], (uint32_t)i);
+      slot = claim_first(keys, 0, mask + 1, pack_key(b, (int)d[0] - kCoordBias, (int)d[1] - kCoordBias, (int)d[2] - kCoordBias), first, i);
     } else {
       atomicOr(&flags[b], PCMI_SEG_FLAG_SPAN);
     }
@@ -211,12 +208,8 @@ __global__ __launch_bounds__(kThreads) void q_label_kernel(int64_t n, const uint
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   const uint32_t slot = slot_of[i];
-  int f = 0;
-  if (slot != kNoSlot) {
-    const uint32_t r = first[slot];
-    f = r == (uint32_t)i ? 1 : 0;
-    if (labels && !f && labels[i] != labels[r]) atomicOr(&mixed[slot], 1);
-  }
+  const int f = is_first_row(slot, first, i) ? 1 : 0;
+  if (labels && !f && slot != kNoSlot && labels[i] != labels[first[slot]]) atomicOr(&mixed[slot], 1);
   is_first[i] = f;
 }
 
@@ -228,14 +221,7 @@ __global__ __launch_bounds__(kThreads) void q_write_kernel(const int32_t* __rest
                                                            int32_t ignore_label, int32_t* __restrict__ coords, int64_t* __restrict__ index,
                                                            int32_t* __restrict__ out_labels, int64_t* __restrict__ counts) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i <= B) {  // counts[b] = voxels of scene b; counts[B] = all
-    if (i == B) {
-      counts[B] = pos[n];
-    } else {
-      const int64_t lo = std::min<int64_t>(std::max<int64_t>(offs[i], 0), n), hi = std::min<int64_t>(std::max<int64_t>(offs[i + 1], lo), n);
-      counts[i] = pos[hi] - pos[lo];
-    }
-  }
+  segment_counts(i, offs, B, n, pos, counts);  // counts[b] = voxels of scene b; counts[B] = all
   if (i >= n || !is_first[i]) return;
   const int b = segment_of(offs, B, i);
   const int64_t p = pos[i];
@@ -244,18 +230,6 @@ __global__ __launch_bounds__(kThreads) void q_write_kernel(const int32_t* __rest
   for (int a = 0; a < 3; ++a) coords[4 * p + 1 + a] = vox[3 * i + a] - (scene_min ? scene_min[3 * b + a] : 0);
   index[p] = i;
   if (out_labels) out_labels[p] = mixed[slot_of[i]] ? ignore_label : labels[i];
-}
-
-static int64_t table_cap(int64_t n) {
-  int64_t c = 1024;
-  while (c < 2 * n) c <<= 1;
-  return c;
-}
-
-static size_t scan_temp_bytes(int64_t items) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)items);
-  return align_up(b + 256, 256);
 }
 
 // ---- flip, colour, label map -------------------------------------------------------------------------------------------------
@@ -587,7 +561,7 @@ size_t pcmi_seg_quantize_workspace_bytes(int64_t n) {
   if (n < 0 || n > kMaxRows) return 0;
   const int64_t cap = table_cap(n), n1 = std::max<int64_t>(n, 1);
   return align_up((size_t)cap * 8, 256) + 2 * align_up((size_t)cap * 4, 256) + align_up((size_t)n1 * 4, 256) +
-         2 * align_up((size_t)(n + 1) * 4, 256) + scan_temp_bytes(n + 1);
+         2 * align_up((size_t)(n + 1) * 4, 256) + cub_scan_bytes<int32_t>(n + 1);
 }
 
 int pcmi_seg_quantize(const int32_t* vox, const uint8_t* keep, const int32_t* labels, const int64_t* offsets, const int32_t* scene_min,
@@ -614,7 +588,7 @@ int pcmi_seg_quantize(const int32_t* vox, const uint8_t* keep, const int32_t* la
   uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
   int32_t* is_first = (int32_t*)cv.take((size_t)(n + 1) * 4);
   int32_t* pos = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  const size_t tb = scan_temp_bytes(n + 1);
+  const size_t tb = cub_scan_bytes<int32_t>(n + 1);
   void* temp = cv.take(tb);
   PCMI_REQUIRE(keys && first && mixed && slot_of && is_first && pos && temp, PCMI_ERR_WORKSPACE, "seg_quantize: workspace too small");
   const uint32_t mask = (uint32_t)(cap - 1);
@@ -627,8 +601,7 @@ int pcmi_seg_quantize(const int32_t* vox, const uint8_t* keep, const int32_t* la
   PCMI_LAUNCH_CHECK();
   q_label_kernel<<<grid, kThreads, 0, st>>>(n, slot_of, first, labels, mixed, is_first);
   PCMI_LAUNCH_CHECK();
-  size_t tb2 = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb2, is_first, pos, (int)(n + 1), st));
+  if (int rc = cub_scan_excl(temp, tb, is_first, pos, n + 1, st)) return rc;
   q_write_kernel<<<(unsigned)ceil_div(std::max<int64_t>(n, B + 1), kThreads), kThreads, 0, st>>>(
       vox, n, offsets, (int)B, scene_min, slot_of, is_first, pos, labels, mixed, ignore_label, coords, index, out_labels, counts);
   PCMI_LAUNCH_CHECK();

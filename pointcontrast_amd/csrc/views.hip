@@ -11,12 +11,11 @@
 //     of the bits below l, so a view's rows ascend and neighbouring lanes write neighbouring rows.
 // The arithmetic is fp64 with a fixed order (no FMA contraction, IEEE division), so the outputs are bit-identical to the
 // numpy restatement in tests/views_ref.py.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
+#include "cubscan.h"
 #include "internal.h"
 
 // every product and sum is rounded on its own (see csrc/corpus.hip)
@@ -154,12 +153,6 @@ __global__ __launch_bounds__(kThreads) void views_rows_kernel(const unsigned lon
   if ((m >> lane) & 1ull) rows[word_start[w] + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
 }
 
-static size_t scan_bytes(int64_t n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int64_t*)nullptr, (int64_t*)nullptr, (int)std::max<int64_t>(n, 1));
-  return b;
-}
-
 static bool camera_ok(double fx, double fy, double cx, double cy, double z_near, double z_far) {
   return std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy) && fx > 0 && fy > 0 && z_near > 0 &&
          z_near <= z_far && std::isfinite(z_far);
@@ -208,7 +201,7 @@ int pcmi_views_zbuffer(const double* points, int64_t points_ld, int64_t n, const
 
 size_t pcmi_views_visible_workspace_bytes(int64_t n, int64_t n_views) {
   const int64_t items = std::max<int64_t>(n_views, 1) * ceil_div(std::max<int64_t>(n, 1), 64);
-  return align_up((size_t)items * 8, 256) + align_up(scan_bytes(items), 256) + 1024;
+  return align_up((size_t)items * 8, 256) + cub_scan_bytes<int64_t>(items) + 1024;
 }
 
 int pcmi_views_visible(const double* points, int64_t points_ld, int64_t n, const double* w2c, int64_t n_views, double fx, double fy,
@@ -236,14 +229,14 @@ int pcmi_views_visible(const double* points, int64_t points_ld, int64_t n, const
   char* p = (char*)ws;
   int64_t* count = (int64_t*)p;
   p += align_up((size_t)items * 8, 256);
-  size_t tb = scan_bytes(items);
+  const size_t tb = cub_scan_bytes<int64_t>(items);
   void* temp = p;
   const Camera cam{fx, fy, cx, cy, z_near, z_far, (int)height, (int)width};
   const dim3 grid((unsigned)ceil_div(n, kThreads), (unsigned)ceil_div(n_views, kViewsPerBlock));
   views_visible_kernel<<<grid, kThreads, 0, st>>>(points, points_ld, n, w2c, (int)n_views, cam, 1.0 + rel_tol, zbuf, n_words,
                                                   (unsigned long long*)mask, count);
   PCMI_LAUNCH_CHECK();
-  PCMI_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, count, word_start, (int)items, st));
+  if (int scan_rc = cub_scan_excl(temp, tb, count, word_start, items, st)) return scan_rc;
   views_offsets_kernel<<<(unsigned)ceil_div(n_views + 1, kThreads), kThreads, 0, st>>>(count, word_start, n_views, n_words, offsets);
   PCMI_LAUNCH_CHECK();
   PCMI_HIP_CHECK(hipMemsetAsync(pixels, 0, (size_t)n_views * 8, st));
