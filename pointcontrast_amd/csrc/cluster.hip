@@ -190,22 +190,6 @@ __global__ __launch_bounds__(kThreads) void rc_flatten_kernel(int32_t* label, in
   atomicMin(&label[i], find_root(label, (int32_t)i, n));
 }
 
-struct RcLayout {
-  int64_t cap, nb;
-  size_t keys, count, start, slot_of, rec, block_sums, block_offs, total;  // bytes of each piece
-};
-static RcLayout rc_layout(int64_t n, int64_t B) {
-  RcLayout L;
-  L.cap = 2 * n + B;
-  L.nb = scan_blocks(L.cap + 1);
-  L.keys = align_up((size_t)L.cap * 8, 256);
-  L.count = L.start = align_up((size_t)(L.cap + 1) * 4, 256);
-  L.slot_of = align_up((size_t)std::max<int64_t>(n, 1) * 4, 256);
-  L.rec = align_up((size_t)std::max<int64_t>(n, 1) * sizeof(Rec), 256);
-  L.block_sums = L.block_offs = align_up((size_t)L.nb * 4, 256);
-  L.total = 256;
-  return L;
-}
 static bool rc_shape_ok(int64_t n, int64_t B) { return n >= 0 && n < (1ll << 31) && B >= 1 && B <= kMaxScenes; }
 
 // ---- compaction ----------------------------------------------------------------------------------------------------------------
@@ -462,10 +446,29 @@ static unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n, kThreads); }
 
 extern "C" {
 
+// cells of the hash grid
+struct RcWs { int64_t cap; uint64_t* keys; int32_t *count, *start; uint32_t* slot_of; Rec* rec; int32_t *sums, *boffs, *total; size_t bytes; };
+static RcWs rc_ws(void* ws, int64_t n, int64_t B) {
+  const size_t n1 = (size_t)std::max<int64_t>(n, 1);
+  Carve cv{(char*)ws};
+  RcWs w;
+  w.cap = 2 * n + B;
+  const size_t nb = (size_t)scan_blocks(w.cap + 1);
+  w.keys = cv.take<uint64_t>((size_t)w.cap);
+  w.count = cv.take<int32_t>((size_t)w.cap + 1);
+  w.start = cv.take<int32_t>((size_t)w.cap + 1);
+  w.slot_of = cv.take<uint32_t>(n1);
+  w.rec = cv.take<Rec>(n1);
+  w.sums = cv.take<int32_t>(nb);
+  w.boffs = cv.take<int32_t>(nb);
+  w.total = cv.take<int32_t>(1);
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_radius_components_workspace_bytes(int64_t n, int64_t B) {
   if (!rc_shape_ok(n, B) || n > kMaxRows) return 0;
-  const RcLayout L = rc_layout(n, B);
-  return L.keys + L.count + L.start + L.slot_of + L.rec + L.block_sums + L.block_offs + L.total;
+  return rc_ws(nullptr, n, B).bytes;
 }
 
 int pcmi_radius_components(const float* xyz, int64_t ld, int64_t n, const int64_t* offs, int64_t B, const int32_t* group, double r,
@@ -478,45 +481,45 @@ int pcmi_radius_components(const float* xyz, int64_t ld, int64_t n, const int64_
   PCMI_REQUIRE(r > 0.0 && h < __builtin_inf(), PCMI_ERR_INVALID, "radius_components: r must be positive and finite");
   if (n == 0) return PCMI_OK;
   PCMI_REQUIRE(xyz && offs && group && label, PCMI_ERR_INVALID, "radius_components: null pointer");
-  const size_t need = pcmi_radius_components_workspace_bytes(n, B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "radius_components: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "radius_components: workspace must be 16-byte aligned");
-  const RcLayout L = rc_layout(n, B);
-  Carve cv{(char*)ws, need};
-  uint64_t* keys = (uint64_t*)cv.take(L.keys);
-  int32_t* count = (int32_t*)cv.take(L.count);
-  int32_t* start = (int32_t*)cv.take(L.start);
-  uint32_t* slot_of = (uint32_t*)cv.take(L.slot_of);
-  Rec* rec = (Rec*)cv.take(L.rec);
-  int32_t* sums = (int32_t*)cv.take(L.block_sums);
-  int32_t* boffs = (int32_t*)cv.take(L.block_offs);
-  int32_t* total = (int32_t*)cv.take(L.total);
-  PCMI_REQUIRE(keys && count && start && slot_of && rec && sums && boffs && total, PCMI_ERR_WORKSPACE, "radius_components: workspace too small");
+  if (int rc = require_ws("radius_components", ws, ws_bytes, rc_ws(nullptr, n, B).bytes, 16)) return rc;
+  const RcWs L = rc_ws(ws, n, B);
   hipStream_t st = as_stream(stream);
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)L.cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(count, 0, (size_t)(L.cap + 1) * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.keys, 0xff, (size_t)L.cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.count, 0, (size_t)(L.cap + 1) * 4, st));
   const unsigned grid = grid_for(n);
-  rc_count_kernel<<<grid, kThreads, 0, st>>>(xyz, ld, n, offs, (int)B, group, r, h, keys, count, slot_of, label,
+  rc_count_kernel<<<grid, kThreads, 0, st>>>(xyz, ld, n, offs, (int)B, group, r, h, L.keys, L.count, L.slot_of, label,
                                              reinterpret_cast<unsigned long long*>(dropped));
   PCMI_LAUNCH_CHECK();
-  if (int rc = scan_excl(count, L.cap + 1, start, sums, boffs, total, st)) return rc;
-  rc_fill_kernel<<<grid, kThreads, 0, st>>>(xyz, ld, n, group, slot_of, start, count, rec);
+  if (int rc = scan_excl(L.count, L.cap + 1, L.start, L.sums, L.boffs, L.total, st)) return rc;
+  rc_fill_kernel<<<grid, kThreads, 0, st>>>(xyz, ld, n, group, L.slot_of, L.start, L.count, L.rec);
   PCMI_LAUNCH_CHECK();
-  rc_unite_kernel<0><<<grid, kThreads, 0, st>>>(rec, total, n, offs, (int)B, r, h, keys, start, label);
+  rc_unite_kernel<0><<<grid, kThreads, 0, st>>>(L.rec, L.total, n, offs, (int)B, r, h, L.keys, L.start, label);
   PCMI_LAUNCH_CHECK();
   rc_flatten_kernel<<<grid, kThreads, 0, st>>>(label, n);
   PCMI_LAUNCH_CHECK();
-  rc_unite_kernel<1><<<grid, kThreads, 0, st>>>(rec, total, n, offs, (int)B, r, h, keys, start, label);
+  rc_unite_kernel<1><<<grid, kThreads, 0, st>>>(L.rec, L.total, n, offs, (int)B, r, h, L.keys, L.start, label);
   PCMI_LAUNCH_CHECK();
   rc_flatten_kernel<<<grid, kThreads, 0, st>>>(label, n);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
 
+struct CompactWs { int32_t *size, *id, *sums, *boffs; size_t bytes; };
+static CompactWs compact_ws(void* ws, int64_t n) {
+  const int64_t m = std::max<int64_t>(n, 1);
+  Carve cv{(char*)ws};
+  CompactWs w;
+  w.size = cv.take<int32_t>((size_t)m);
+  w.id = cv.take<int32_t>((size_t)m);
+  w.sums = cv.take<int32_t>((size_t)scan_blocks(m));
+  w.boffs = cv.take<int32_t>((size_t)scan_blocks(m));
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_components_compact_workspace_bytes(int64_t n) {
   if (n < 0 || n >= (1ll << 31)) return 0;
-  const int64_t m = std::max<int64_t>(n, 1);
-  return 2 * align_up((size_t)m * 4, 256) + 2 * align_up((size_t)scan_blocks(m) * 4, 256);
+  return compact_ws(nullptr, n).bytes;
 }
 
 int pcmi_components_compact(const int32_t* label, const int64_t* offs, int64_t B, int64_t n, const int32_t* group, int min_points,
@@ -537,29 +540,23 @@ int pcmi_components_compact(const int32_t* label, const int64_t* offs, int64_t B
     return PCMI_OK;
   }
   PCMI_REQUIRE(label && offs && inst, PCMI_ERR_INVALID, "components_compact: null pointer");
-  const size_t need = pcmi_components_compact_workspace_bytes(n);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "components_compact: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  Carve cv{(char*)ws, need};
-  int32_t* size = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* id = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* sums = (int32_t*)cv.take((size_t)scan_blocks(n) * 4);
-  int32_t* boffs = (int32_t*)cv.take((size_t)scan_blocks(n) * 4);
-  PCMI_REQUIRE(size && id && sums && boffs, PCMI_ERR_WORKSPACE, "components_compact: workspace too small");
+  if (int rc = require_ws("components_compact", ws, ws_bytes, compact_ws(nullptr, n).bytes, 1)) return rc;
+  const CompactWs w = compact_ws(ws, n);
   const unsigned grid = grid_for(n);
-  PCMI_HIP_CHECK(hipMemsetAsync(size, 0, (size_t)n * 4, st));
-  cc_size_kernel<<<grid, kThreads, 0, st>>>(label, n, size);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.size, 0, (size_t)n * 4, st));
+  cc_size_kernel<<<grid, kThreads, 0, st>>>(label, n, w.size);
   PCMI_LAUNCH_CHECK();
-  cc_flag_kernel<<<grid, kThreads, 0, st>>>(label, n, size, min_points, id);
+  cc_flag_kernel<<<grid, kThreads, 0, st>>>(label, n, w.size, min_points, w.id);
   PCMI_LAUNCH_CHECK();
-  if (int rc = scan_excl(id, n, id, sums, boffs, count, st)) return rc;
+  if (int rc = scan_excl(w.id, n, w.id, w.sums, w.boffs, count, st)) return rc;
   if (max_inst > 0) {
-    cc_roots_kernel<<<grid, kThreads, 0, st>>>(label, n, size, min_points, id, offs, (int)B, group, max_inst, inst_root, inst_size, inst_scene,
+    cc_roots_kernel<<<grid, kThreads, 0, st>>>(label, n, w.size, min_points, w.id, offs, (int)B, group, max_inst, inst_root, inst_size, inst_scene,
                                                inst_group);
     PCMI_LAUNCH_CHECK();
     cc_tail_kernel<<<grid_for(max_inst), kThreads, 0, st>>>(count, max_inst, inst_root, inst_size, inst_scene, inst_group);
     PCMI_LAUNCH_CHECK();
   }
-  cc_rows_kernel<<<grid, kThreads, 0, st>>>(label, n, size, min_points, id, max_inst, inst);
+  cc_rows_kernel<<<grid, kThreads, 0, st>>>(label, n, w.size, min_points, w.id, max_inst, inst);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
@@ -572,11 +569,9 @@ int pcmi_instance_scores(const float* score, const int32_t* inst, int64_t n, int
                (long long)n, (long long)P);
   if (P == 0) return PCMI_OK;
   PCMI_REQUIRE(inst_size && out && (n == 0 || (score && inst)), PCMI_ERR_INVALID, "instance_scores: null pointer");
-  const size_t need = pcmi_instance_scores_workspace_bytes(P);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "instance_scores: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 8 == 0, PCMI_ERR_INVALID, "instance_scores: workspace must be 8-byte aligned");
+  if (int rc = require_ws("instance_scores", ws, ws_bytes, pcmi_instance_scores_workspace_bytes(P), 8)) return rc;
   hipStream_t st = as_stream(stream);
-  unsigned long long* sum = (unsigned long long*)ws;
+  unsigned long long* sum = static_cast<unsigned long long*>(ws);
   PCMI_HIP_CHECK(hipMemsetAsync(sum, 0, (size_t)P * 8, st));
   if (n > 0) {
     is_sum_kernel<<<grid_for(n), kThreads, 0, st>>>(score, inst, n, P, sum);
@@ -649,9 +644,7 @@ int pcmi_offset_loss_fwd(const float* p, int64_t ld, const float* g, const int32
     PCMI_HIP_CHECK(hipMemsetAsync(out3, 0, 24, st));
     return PCMI_OK;
   }
-  const size_t need = pcmi_offset_loss_workspace_bytes(n);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "offset_loss_fwd: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 8 == 0, PCMI_ERR_INVALID, "offset_loss_fwd: workspace must be 8-byte aligned");
+  if (int rc = require_ws("offset_loss_fwd", ws, ws_bytes, pcmi_offset_loss_workspace_bytes(n), 8)) return rc;
   const int64_t nb = ceil_div(n, kThreads);
   ol_partial_kernel<<<(unsigned)nb, kThreads, 0, st>>>(p, ld, g, inst, n, (double*)ws);
   PCMI_LAUNCH_CHECK();

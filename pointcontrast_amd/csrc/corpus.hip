@@ -368,9 +368,23 @@ using namespace pcmi::corpus;
 
 extern "C" {
 
+// the flags of the valid depth pixels, their scan and its temporary: both backprojections
+struct BackprojectWs { int32_t *flags, *pos; void* temp; size_t temp_bytes, bytes; };
+static BackprojectWs backproject_ws(void* ws, int64_t n_pixels) {
+  const int64_t n = std::max<int64_t>(n_pixels, 1);
+  Carve cv{(char*)ws};
+  BackprojectWs w;
+  w.flags = cv.take<int32_t>((size_t)n);
+  w.pos = cv.take<int32_t>((size_t)n);
+  w.temp_bytes = cub_scan_bytes<int32_t>(n);
+  w.temp = cv.take<char>(w.temp_bytes);
+  cv.take<char>(1024);  // (unused tail the query has always counted)
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_corpus_backproject_workspace_bytes(int64_t n_frames, int64_t height, int64_t width) {
-  const int64_t n = std::max<int64_t>(n_frames * height * width, 1);
-  return 2 * align_up((size_t)n * 4, 256) + cub_scan_bytes<int32_t>(n) + 1024;
+  return backproject_ws(nullptr, n_frames * height * width).bytes;
 }
 
 int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width, const double* intrinsic_host,
@@ -381,25 +395,19 @@ int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t hei
                PCMI_ERR_INVALID, "corpus_backproject: bad argument (%lld frames of %lld x %lld)", (long long)n_frames,
                (long long)height, (long long)width);
   const int64_t hw = height * width, n = n_frames * hw;
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_backproject_workspace_bytes(n_frames, height, width), PCMI_ERR_WORKSPACE,
-               "corpus_backproject: workspace too small");
+  if (int rc = require_ws("corpus_backproject", ws, ws_bytes, backproject_ws(nullptr, n).bytes, 1)) return rc;
   hipStream_t st = as_stream(stream);
-  Carve cv{(char*)ws, ws_bytes};
-  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
-  const size_t tb = cub_scan_bytes<int32_t>(n);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(flags && pos && temp, PCMI_ERR_WORKSPACE, "corpus_backproject: workspace too small");
+  const BackprojectWs w = backproject_ws(ws, n);
   const double* A = intrinsic_host;  // 4x4 row-major (intrinsic_depth.txt)
   const Intrinsic K{A[0], A[5], A[2], A[6], A[3], A[7]};
   PCMI_HIP_CHECK(hipMemsetAsync(nan_count, 0, (size_t)n_frames * 4, st));
   const unsigned gn = (unsigned)ceil_div(n, kThreads);
-  bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, flags);
+  bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, w.flags);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
-  bp_points_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, poses, depth_shift, pos, points, nan_count);
+  if (int rc = cub_scan_excl(w.temp, w.temp_bytes, w.flags, w.pos, n, st)) return rc;
+  bp_points_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, poses, depth_shift, w.pos, points, nan_count);
   PCMI_LAUNCH_CHECK();
-  bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(flags, pos, n_frames, hw, offsets);
+  bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(w.flags, w.pos, n_frames, hw, offsets);
   PCMI_LAUNCH_CHECK();
   PCMI_HIP_CHECK(hipMemcpyAsync(offsets_host, offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
@@ -407,7 +415,7 @@ int pcmi_corpus_backproject(const uint16_t* depth, int64_t n_frames, int64_t hei
 }
 
 size_t pcmi_corpus_backproject_color_workspace_bytes(int64_t n_frames, int64_t height, int64_t width) {
-  return pcmi_corpus_backproject_workspace_bytes(n_frames, height, width);  // the flags, their scan and its temporary
+  return backproject_ws(nullptr, n_frames * height * width).bytes;
 }
 
 int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64_t height, int64_t width, const double* intrinsic_host,
@@ -424,28 +432,22 @@ int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64
                PCMI_ERR_INVALID, "corpus_backproject_color: bad colour images (%lld frames of %lld x %lld x 3)", (long long)n_frames,
                (long long)color_height, (long long)color_width);
   const int64_t hw = height * width, n = n_frames * hw;
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_backproject_color_workspace_bytes(n_frames, height, width), PCMI_ERR_WORKSPACE,
-               "corpus_backproject_color: workspace too small");
+  if (int rc = require_ws("corpus_backproject_color", ws, ws_bytes, backproject_ws(nullptr, n).bytes, 1)) return rc;
   hipStream_t st = as_stream(stream);
-  Carve cv{(char*)ws, ws_bytes};
-  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
-  const size_t tb = cub_scan_bytes<int32_t>(n);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(flags && pos && temp, PCMI_ERR_WORKSPACE, "corpus_backproject_color: workspace too small");
+  const BackprojectWs w = backproject_ws(ws, n);
   const double *A = intrinsic_host, *Ac = color_intrinsic_host;  // 4x4 row-major (intrinsic_depth.txt, intrinsic_color.txt)
   const Intrinsic K{A[0], A[5], A[2], A[6], A[3], A[7]};
   ColorCamera cam{Ac[0], Ac[5], Ac[2], Ac[6], {}};
   for (int q = 0; q < 12; ++q) cam.M[q] = depth_to_color_host[q];
   PCMI_HIP_CHECK(hipMemsetAsync(uncolored, 0, (size_t)n_frames * 8, st));
   const unsigned gn = (unsigned)ceil_div(n, kThreads);
-  bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, flags);
+  bp_flag_kernel<<<gn, kThreads, 0, st>>>(depth, n, w.flags);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
+  if (int rc = cub_scan_excl(w.temp, w.temp_bytes, w.flags, w.pos, n, st)) return rc;
   bp_color_kernel<<<gn, kThreads, 0, st>>>(depth, n_frames, height, width, K, depth_shift, color_images, color_height, color_width, cam,
-                                           pos, color, (unsigned long long*)uncolored);
+                                           w.pos, color, (unsigned long long*)uncolored);
   PCMI_LAUNCH_CHECK();
-  bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(flags, pos, n_frames, hw, offsets);
+  bp_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(w.flags, w.pos, n_frames, hw, offsets);
   PCMI_LAUNCH_CHECK();
   if (offsets_host) {  // the one wait of pcmi_corpus_backproject; without offsets_host the call does not wait at all
     PCMI_HIP_CHECK(hipMemcpyAsync(offsets_host, offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -454,13 +456,46 @@ int pcmi_corpus_backproject_color(const uint16_t* depth, int64_t n_frames, int64
   return PCMI_OK;
 }
 
+struct CentroidsWs {
+  uint64_t* keys;
+  uint32_t *first, *slot_of;
+  int32_t *flags, *pos, *vid, *iota, *svid, *sidx, *start;
+  double *partial, *origin;
+  uint32_t *tbase, *tmask;
+  int32_t* err;
+  void* temp;
+  size_t temp_bytes, bytes;
+};
+// n_chunks: the chunks of the longest frame (the entry, which has the offsets on the host) or a bound on them (the query)
+static CentroidsWs centroids_ws(void* ws, int64_t n, int64_t n_frames, int64_t n_chunks) {
+  const size_t slots = (size_t)vc_table_slots(n, n_frames);
+  Carve cv{(char*)ws};
+  CentroidsWs w;
+  w.keys = cv.take<uint64_t>(slots);
+  w.first = cv.take<uint32_t>(slots);
+  w.slot_of = cv.take<uint32_t>((size_t)n);
+  w.flags = cv.take<int32_t>((size_t)n);
+  w.pos = cv.take<int32_t>((size_t)n);
+  w.vid = cv.take<int32_t>((size_t)n);
+  w.iota = cv.take<int32_t>((size_t)n);
+  w.svid = cv.take<int32_t>((size_t)n);
+  w.sidx = cv.take<int32_t>((size_t)n);
+  w.start = cv.take<int32_t>((size_t)n + 1);
+  w.partial = cv.take<double>((size_t)n_frames * n_chunks * 3);
+  w.origin = cv.take<double>((size_t)n_frames * 3);
+  w.tbase = cv.take<uint32_t>((size_t)n_frames);
+  w.tmask = cv.take<uint32_t>((size_t)n_frames);
+  w.err = cv.take<int32_t>(64);
+  w.temp_bytes = std::max(cub_scan_bytes<int32_t>(n), sort_bytes(n));
+  w.temp = cv.take<char>(w.temp_bytes);
+  cv.take<char>(1024);  // (unused tail the query has always counted)
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_corpus_voxel_centroids_workspace_bytes(int64_t n_points, int64_t n_frames) {
   const int64_t n = std::max<int64_t>(n_points, 1), F = std::max<int64_t>(n_frames, 1);
-  const int64_t chunks = ceil_div(n, kMinChunk) + F;  // bound on sum over frames of ceil(n_f / kMinChunk)
-  const size_t slots = (size_t)vc_table_slots(n, F);
-  return align_up(slots * 8, 256) + align_up(slots * 4, 256) + 7 * align_up((size_t)n * 4, 256) +
-         align_up((size_t)(n + 1) * 4, 256) + align_up((size_t)F * chunks * 24, 256) + align_up((size_t)F * 24, 256) +
-         2 * align_up((size_t)F * 4, 256) + align_up(std::max(cub_scan_bytes<int32_t>(n), sort_bytes(n)), 256) + 256 + 1024;
+  return centroids_ws(nullptr, n, F, ceil_div(n, kMinChunk) + F).bytes;  // a bound on the chunks of any one frame
 }
 
 int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, const int64_t* offsets_host, int64_t n_frames,
@@ -478,79 +513,74 @@ int pcmi_corpus_voxel_centroids(const double* points, const int64_t* offsets, co
     PCMI_HIP_CHECK(hipMemsetAsync(voxel_offsets, 0, (size_t)(n_frames + 1) * 8, st));
     return PCMI_OK;
   }
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_voxel_centroids_workspace_bytes(n, n_frames), PCMI_ERR_WORKSPACE,
-               "corpus_voxel_centroids: workspace too small");
+  if (int rc = require_ws("corpus_voxel_centroids", ws, ws_bytes, pcmi_corpus_voxel_centroids_workspace_bytes(n, n_frames), 1)) return rc;
   const int64_t mf = max_frame(offsets_host, n_frames), n_chunks = std::max<int64_t>(ceil_div(mf, kMinChunk), 1);
   const size_t slots = (size_t)vc_table_slots(n, n_frames);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take(slots * 8);
-  uint32_t* first = (uint32_t*)cv.take(slots * 4);
-  uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
-  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* vid = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* iota = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* svid = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* sidx = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* start = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  double* partial = (double*)cv.take((size_t)n_frames * n_chunks * 24);
-  double* origin = (double*)cv.take((size_t)n_frames * 24);
-  uint32_t* tbase = (uint32_t*)cv.take((size_t)n_frames * 4);
-  uint32_t* tmask = (uint32_t*)cv.take((size_t)n_frames * 4);
-  int32_t* err = (int32_t*)cv.take(256);
-  size_t tb = std::max(cub_scan_bytes<int32_t>(n), sort_bytes(n));
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && first && slot_of && flags && pos && vid && iota && svid && sidx && start && partial && origin && tbase &&
-                   tmask && err && temp,
-               PCMI_ERR_WORKSPACE, "corpus_voxel_centroids: workspace too small");
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, slots * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, slots * 4, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
-  vc_min_partial_kernel<<<dim3((unsigned)n_chunks, (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, n_chunks, partial);
+  const CentroidsWs w = centroids_ws(ws, n, n_frames, n_chunks);
+  void* temp = w.temp;
+  const size_t tb = w.temp_bytes;
+  PCMI_HIP_CHECK(hipMemsetAsync(w.keys, 0xff, slots * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.first, 0xff, slots * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.err, 0, 256, st));
+  vc_min_partial_kernel<<<dim3((unsigned)n_chunks, (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, n_chunks, w.partial);
   PCMI_LAUNCH_CHECK();
-  vc_origin_kernel<<<(unsigned)n_frames, kThreads, 0, st>>>(partial, n_chunks, 0.5 * voxel_size, offsets, n_frames, origin,
-                                                             tbase, tmask);
+  vc_origin_kernel<<<(unsigned)n_frames, kThreads, 0, st>>>(w.partial, n_chunks, 0.5 * voxel_size, offsets, n_frames, w.origin,
+                                                             w.tbase, w.tmask);
   PCMI_LAUNCH_CHECK();
   const unsigned gx = (unsigned)std::min<int64_t>(ceil_div(mf, kThreads), 1024), gn = (unsigned)ceil_div(n, kThreads);
-  vc_insert_kernel<<<dim3(std::max(gx, 1u), (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, origin, voxel_size, tbase,
-                                                                                    tmask, keys, first, slot_of, err);
+  vc_insert_kernel<<<dim3(std::max(gx, 1u), (unsigned)n_frames), kThreads, 0, st>>>(points, offsets, w.origin, voxel_size, w.tbase,
+                                                                                    w.tmask, w.keys, w.first, w.slot_of, w.err);
   PCMI_LAUNCH_CHECK();
   int32_t herr = 0;
-  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   PCMI_REQUIRE(herr == 0, PCMI_ERR_RANGE,
                "corpus_voxel_centroids: %d points fall outside 2^20 voxels of their frame's min bound (or are not finite)", herr);
-  vc_flag_kernel<<<gn, kThreads, 0, st>>>(n, first, slot_of, flags, iota);
+  vc_flag_kernel<<<gn, kThreads, 0, st>>>(n, w.first, w.slot_of, w.flags, w.iota);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
+  if (int rc = cub_scan_excl(temp, tb, w.flags, w.pos, n, st)) return rc;
   int32_t last[2] = {0, 0};
-  PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], flags + n - 1, 4, hipMemcpyDeviceToHost, st));
-  PCMI_HIP_CHECK(hipMemcpyAsync(&last[1], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], w.flags + n - 1, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&last[1], w.pos + n - 1, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   const int64_t n_vox = (int64_t)last[0] + last[1];
-  vc_vid_kernel<<<gn, kThreads, 0, st>>>(n, first, slot_of, pos, vid);
+  vc_vid_kernel<<<gn, kThreads, 0, st>>>(n, w.first, w.slot_of, w.pos, w.vid);
   PCMI_LAUNCH_CHECK();
-  vc_voxel_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(pos, offsets, n_frames, n, n_vox,
+  vc_voxel_offsets_kernel<<<(unsigned)ceil_div(n_frames + 1, kThreads), kThreads, 0, st>>>(w.pos, offsets, n_frames, n, n_vox,
                                                                                           voxel_offsets);
   PCMI_LAUNCH_CHECK();
   int end_bit = 1;
   while ((1ll << end_bit) < n_vox) ++end_bit;
   size_t tb2 = tb;  // stable LSD radix sort: the points of a voxel keep ascending index order
-  PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, tb2, vid, svid, iota, sidx, (int)n, 0, end_bit, st));
-  vc_starts_kernel<<<gn, kThreads, 0, st>>>(svid, n, n_vox, start);
+  PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, tb2, w.vid, w.svid, w.iota, w.sidx, (int)n, 0, end_bit, st));
+  vc_starts_kernel<<<gn, kThreads, 0, st>>>(w.svid, n, n_vox, w.start);
   PCMI_LAUNCH_CHECK();
-  vc_centroid_kernel<<<(unsigned)ceil_div(n_vox, kThreads), kThreads, 0, st>>>(points, sidx, start, n_vox, centroids);
+  vc_centroid_kernel<<<(unsigned)ceil_div(n_vox, kThreads), kThreads, 0, st>>>(points, w.sidx, w.start, n_vox, centroids);
   PCMI_LAUNCH_CHECK();
   PCMI_HIP_CHECK(hipMemcpyAsync(voxel_offsets_host, voxel_offsets, (size_t)(n_frames + 1) * 8, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   return PCMI_OK;
 }
 
-size_t pcmi_corpus_overlap_workspace_bytes(int64_t n_points, int64_t n_frames) {
-  (void)n_frames;
+struct OverlapWs { uint64_t* keys; int32_t *head, *next, *frame_of, *err; size_t bytes; };
+static OverlapWs overlap_ws(void* ws, int64_t n_points) {
   const int64_t n = std::max<int64_t>(n_points, 1);
   const size_t cap = pow2_at_least(2 * n);
-  return align_up(cap * 8, 256) + align_up(cap * 4, 256) + 2 * align_up((size_t)n * 4, 256) + 256 + 1024;
+  Carve cv{(char*)ws};
+  OverlapWs w;
+  w.keys = cv.take<uint64_t>(cap);
+  w.head = cv.take<int32_t>(cap);
+  w.next = cv.take<int32_t>((size_t)n);
+  w.frame_of = cv.take<int32_t>((size_t)n);
+  w.err = cv.take<int32_t>(64);
+  cv.take<char>(1024);  // (unused tail the query has always counted)
+  w.bytes = cv.used;
+  return w;
+}
+
+size_t pcmi_corpus_overlap_workspace_bytes(int64_t n_points, int64_t n_frames) {
+  (void)n_frames;
+  return overlap_ws(nullptr, n_points).bytes;
 }
 
 int pcmi_corpus_overlap_counts(const double* centroids, const int64_t* offsets, const int64_t* offsets_host, int64_t n_frames,
@@ -564,32 +594,25 @@ int pcmi_corpus_overlap_counts(const double* centroids, const int64_t* offsets, 
   hipStream_t st = as_stream(stream);
   PCMI_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n_frames * n_frames * 4, st));
   if (n == 0) return PCMI_OK;
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_corpus_overlap_workspace_bytes(n, n_frames), PCMI_ERR_WORKSPACE,
-               "corpus_overlap_counts: workspace too small");
+  if (int rc = require_ws("corpus_overlap_counts", ws, ws_bytes, overlap_ws(nullptr, n).bytes, 1)) return rc;
   const uint32_t cap = pow2_at_least(2 * n);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  int32_t* head = (int32_t*)cv.take((size_t)cap * 4);
-  int32_t* next = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* frame_of = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* err = (int32_t*)cv.take(256);
-  PCMI_REQUIRE(keys && head && next && frame_of && err, PCMI_ERR_WORKSPACE, "corpus_overlap_counts: workspace too small");
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(head, 0xff, (size_t)cap * 4, st));  // -1
-  PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
+  const OverlapWs w = overlap_ws(ws, n);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.head, 0xff, (size_t)cap * 4, st));  // -1
+  PCMI_HIP_CHECK(hipMemsetAsync(w.err, 0, 256, st));
   const int64_t mf = max_frame(offsets_host, n_frames);
   const unsigned gx = (unsigned)std::max<int64_t>(ceil_div(mf, kThreads), 1);
-  ov_insert_kernel<<<dim3(std::min(gx, 1024u), (unsigned)n_frames), kThreads, 0, st>>>(centroids, offsets, radius, keys, head,
-                                                                                      cap - 1, next, frame_of, err);
+  ov_insert_kernel<<<dim3(std::min(gx, 1024u), (unsigned)n_frames), kThreads, 0, st>>>(centroids, offsets, radius, w.keys, w.head,
+                                                                                      cap - 1, w.next, w.frame_of, w.err);
   PCMI_LAUNCH_CHECK();
   int32_t herr = 0;
-  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   PCMI_REQUIRE(herr == 0, PCMI_ERR_RANGE,
                "corpus_overlap_counts: %d points fall outside +-2^20 cells of size %g (or are not finite)", herr, radius);
   const unsigned tiles = (unsigned)ceil_div(n_frames, 64);
-  ov_count_kernel<<<dim3(gx, (unsigned)n_frames, tiles), kThreads, 0, st>>>(centroids, offsets, n_frames, radius, keys, head,
-                                                                           cap - 1, next, frame_of, counts);
+  ov_count_kernel<<<dim3(gx, (unsigned)n_frames, tiles), kThreads, 0, st>>>(centroids, offsets, n_frames, radius, w.keys, w.head,
+                                                                           cap - 1, w.next, w.frame_of, counts);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -551,9 +551,9 @@ int pcmi_nn_distance_bwd(const float* pc1, const float* pc2, const int32_t* idx1
   PCMI_REQUIRE(mode >= 0 && mode <= 2, PCMI_ERR_INVALID, "nn_distance_bwd: mode %d is none of 0 (L2), 1 (L1), 2 (Huber)", mode);
   if (B == 0) return PCMI_OK;
   PCMI_REQUIRE(pc1 && pc2 && idx1 && idx2 && gdist1 && gdist2 && gpc1 && gpc2, PCMI_ERR_INVALID, "nn_distance_bwd: null pointer");
-  const size_t need = pcmi_nn_distance_bwd_workspace_bytes(B, N, M);
-  PCMI_REQUIRE(need == 0 || (ws && ws_bytes >= need), PCMI_ERR_WORKSPACE, "nn_distance_bwd: workspace too small (%zu bytes, %zu needed)",
-               ws_bytes, need);
+  const size_t need = pcmi_nn_distance_bwd_workspace_bytes(B, N, M);  // 0: neither direction builds inverse lists
+  if (need != 0)
+    if (int rc = require_ws("nn_distance_bwd", ws, ws_bytes, need, 1)) return rc;
   hipStream_t st = as_stream(stream);
   if (mode == 0) return nn_bwd_mode<0>(pc1, pc2, idx1, idx2, gdist1, gdist2, B, N, M, delta, gpc1, gpc2, ws, ws_bytes, st);
   if (mode == 1) return nn_bwd_mode<1>(pc1, pc2, idx1, idx2, gdist1, gdist2, B, N, M, delta, gpc1, gpc2, ws, ws_bytes, st);

@@ -363,11 +363,9 @@ int pcmi_segment_quantile(const float* values, int64_t stride, const int64_t* of
   PCMI_REQUIRE((uintptr_t)offsets % 8 == 0 && (uintptr_t)out % 8 == 0 && (uintptr_t)values % 4 == 0 && (uintptr_t)out_stats % 4 == 0 &&
                    (uintptr_t)flags % 4 == 0,
                PCMI_ERR_INVALID, "segment_quantile: misaligned pointer (8 bytes for fp64 and int64, 4 for fp32 and int32)");
-  const size_t need = pcmi_segment_quantile_workspace_bytes(B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "segment_quantile: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "segment_quantile: workspace must be 16-byte aligned");
+  if (int rc = require_ws("segment_quantile", ws, ws_bytes, pcmi_segment_quantile_workspace_bytes(B), 16)) return rc;
   hipStream_t st = as_stream(stream);
-  QuantArgs a{values, stride, offsets, n, (int)B, q, out, out_stats, flags, (uint32_t*)ws};
+  QuantArgs a{values, stride, offsets, n, (int)B, q, out, out_stats, flags, static_cast<uint32_t*>(ws)};
   quantile_scene_kernel<<<(unsigned)B, kSingleThreads, 0, st>>>(a);
   PCMI_LAUNCH_CHECK();
   if (n > kSingleMax) {  // no scene can be larger otherwise

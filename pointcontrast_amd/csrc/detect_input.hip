@@ -518,12 +518,9 @@ int pcmi_det_votes_from_instances(const float* point_clouds, const int32_t* inst
                PCMI_ERR_INVALID, "det_votes_from_instances: null pointer");
   PCMI_REQUIRE((uintptr_t)vote_label_mask % 8 == 0 && (uintptr_t)point_clouds % 4 == 0 && (uintptr_t)vote_label % 4 == 0, PCMI_ERR_INVALID,
                "det_votes_from_instances: misaligned pointer");
-  const size_t need = pcmi_det_votes_from_instances_workspace_bytes(B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "det_votes_from_instances: workspace too small (%zu bytes, %zu needed)", ws_bytes,
-               need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "det_votes_from_instances: workspace must be 16-byte aligned");
+  if (int rc = require_ws("det_votes_from_instances", ws, ws_bytes, pcmi_det_votes_from_instances_workspace_bytes(B), 16)) return rc;
   hipStream_t st = as_stream(stream);
-  uint32_t* tab = (uint32_t*)ws;
+  uint32_t* tab = static_cast<uint32_t*>(ws);
   const int64_t total = B * kMaxInst * 7;
   vi_init_kernel<<<(unsigned)ceil_div(total, kThreads), kThreads, 0, st>>>(tab, total);
   PCMI_LAUNCH_CHECK();
@@ -564,11 +561,26 @@ int pcmi_det_box_labels(const double* boxes, const int32_t* n_boxes, int64_t B, 
   return PCMI_OK;
 }
 
+// the workspace of the pcmi_seg_quantize call inside
+struct DetVoxWs { int32_t* vox; uint8_t* keep; int32_t* scene_min; int64_t *offs, *index; void* quantize; size_t quantize_bytes, bytes; };
+static DetVoxWs det_vox_ws(void* ws, int64_t B, int64_t num_points) {
+  const size_t N = (size_t)(B * num_points);
+  Carve cv{(char*)ws};
+  DetVoxWs w;
+  w.vox = cv.take<int32_t>(N * 3);
+  w.keep = cv.take<uint8_t>(N);
+  w.scene_min = cv.take<int32_t>((size_t)B * 3);
+  w.offs = cv.take<int64_t>((size_t)B + 1);
+  w.index = cv.take<int64_t>(N);
+  w.quantize_bytes = pcmi_seg_quantize_workspace_bytes((int64_t)N);
+  w.quantize = cv.take<char>(w.quantize_bytes);
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_det_voxelize_workspace_bytes(int64_t B, int64_t num_points) {
   if (!shape_ok(B, num_points)) return 0;
-  const int64_t N = B * num_points;
-  return align_up((size_t)N * 12, 256) + align_up((size_t)N, 256) + align_up((size_t)B * 12, 256) + align_up((size_t)(B + 1) * 8, 256) +
-         align_up((size_t)N * 8, 256) + pcmi_seg_quantize_workspace_bytes(N);
+  return det_vox_ws(nullptr, B, num_points).bytes;
 }
 
 int pcmi_det_voxelize(const float* point_clouds, int64_t B, int64_t num_points, double voxel_size, int32_t* voxel_coords, int32_t* voxel_inds,
@@ -581,33 +593,21 @@ int pcmi_det_voxelize(const float* point_clouds, int64_t B, int64_t num_points, 
   PCMI_REQUIRE(point_clouds && voxel_coords && voxel_inds && voxel_feats && counts && flags, PCMI_ERR_INVALID, "det_voxelize: null pointer");
   PCMI_REQUIRE((uintptr_t)counts % 8 == 0 && (uintptr_t)point_clouds % 4 == 0 && (uintptr_t)voxel_coords % 4 == 0, PCMI_ERR_INVALID,
                "det_voxelize: misaligned pointer");
-  const size_t need = pcmi_det_voxelize_workspace_bytes(B, num_points);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "det_voxelize: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "det_voxelize: workspace must be 16-byte aligned");
+  if (int rc = require_ws("det_voxelize", ws, ws_bytes, det_vox_ws(nullptr, B, num_points).bytes, 16)) return rc;
   const int64_t N = B * num_points;
-  char* p = (char*)ws;
-  int32_t* vox = (int32_t*)p;
-  p += align_up((size_t)N * 12, 256);
-  uint8_t* keep = (uint8_t*)p;
-  p += align_up((size_t)N, 256);
-  int32_t* scene_min = (int32_t*)p;
-  p += align_up((size_t)B * 12, 256);
-  int64_t* offs = (int64_t*)p;
-  p += align_up((size_t)(B + 1) * 8, 256);
-  int64_t* index = (int64_t*)p;
-  p += align_up((size_t)N * 8, 256);
-  const size_t qbytes = pcmi_seg_quantize_workspace_bytes(N);
+  const DetVoxWs w = det_vox_ws(ws, B, num_points);
   hipStream_t st = as_stream(stream);
   const unsigned grid = (unsigned)ceil_div(N, kThreads);
-  vx_init_kernel<<<(unsigned)ceil_div(3 * B + 1, kThreads), kThreads, 0, st>>>(scene_min, offs, (int)B, num_points);
+  vx_init_kernel<<<(unsigned)ceil_div(3 * B + 1, kThreads), kThreads, 0, st>>>(w.scene_min, w.offs, (int)B, num_points);
   PCMI_LAUNCH_CHECK();
-  vx_point_kernel<<<grid, kThreads, 0, st>>>(point_clouds, num_points, (int)B, vs, vox, keep, scene_min, flags);
+  vx_point_kernel<<<grid, kThreads, 0, st>>>(point_clouds, num_points, (int)B, vs, w.vox, w.keep, w.scene_min, flags);
   PCMI_LAUNCH_CHECK();
-  vx_min_kernel<<<(unsigned)ceil_div(3 * B, kThreads), kThreads, 0, st>>>(scene_min, (int)B);
+  vx_min_kernel<<<(unsigned)ceil_div(3 * B, kThreads), kThreads, 0, st>>>(w.scene_min, (int)B);
   PCMI_LAUNCH_CHECK();
-  const int rc = pcmi_seg_quantize(vox, keep, nullptr, offs, scene_min, N, B, 0, voxel_coords, index, nullptr, counts, flags, p, qbytes, stream);
+  const int rc = pcmi_seg_quantize(w.vox, w.keep, nullptr, w.offs, w.scene_min, N, B, 0, voxel_coords, w.index, nullptr, counts, flags, w.quantize,
+                                   w.quantize_bytes, stream);
   if (rc != PCMI_OK) return rc;
-  vx_close_kernel<<<grid, kThreads, 0, st>>>(voxel_coords, index, counts, scene_min, (int)B, num_points, voxel_inds, voxel_feats);
+  vx_close_kernel<<<grid, kThreads, 0, st>>>(voxel_coords, w.index, counts, w.scene_min, (int)B, num_points, voxel_inds, voxel_feats);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -392,9 +392,20 @@ int pcmi_det_match(const float* pred_corners, const float* gt_corners, const int
   return PCMI_OK;
 }
 
+struct ApWs { int32_t *claim, *tp_cum; size_t bytes; };
+static ApWs ap_ws(void* ws, int64_t nd, int64_t n_gt, int n_thresholds) {
+  Carve cv{(char*)ws};
+  ApWs w;
+  w.claim = cv.take<int32_t>((size_t)n_thresholds * (size_t)n_gt);
+  cv.align = 1;  // the last piece is not padded
+  w.tp_cum = cv.take<int32_t>((size_t)n_thresholds * (size_t)nd);
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_det_ap_workspace_bytes(int64_t nd, int64_t n_gt, int n_thresholds) {
   if (!ap_shape_ok(nd, n_gt, 1, n_thresholds)) return 0;
-  return align_up((size_t)n_thresholds * (size_t)n_gt * 4, 256) + (size_t)n_thresholds * (size_t)nd * 4;
+  return ap_ws(nullptr, nd, n_gt, n_thresholds).bytes;
 }
 
 int pcmi_det_ap(const float* best_iou, const int32_t* gt_id, const int32_t* cls_offs, const int32_t* npos, int64_t nd, int64_t n_gt,
@@ -405,21 +416,20 @@ int pcmi_det_ap(const float* best_iou, const int32_t* gt_id, const int32_t* cls_
                n_thresholds, kApMaxThresholds);
   PCMI_REQUIRE(thresholds && cls_offs && npos && ap && last_rec && (nd == 0 || (best_iou && gt_id)), PCMI_ERR_INVALID,
                "det_ap: null pointer");
-  const size_t need = pcmi_det_ap_workspace_bytes(nd, n_gt, n_thresholds);
-  PCMI_REQUIRE(need == 0 || (ws && ws_bytes >= need), PCMI_ERR_WORKSPACE, "det_ap: workspace too small (%zu bytes, %zu needed)", ws_bytes,
-               need);
+  const size_t need = ap_ws(nullptr, nd, n_gt, n_thresholds).bytes;  // 0 with no detection and no box: no workspace at all
+  if (need != 0)
+    if (int rc = require_ws("det_ap", ws, ws_bytes, need, 1)) return rc;
   hipStream_t st = as_stream(stream);
   ApThresholds thr;
   for (int t = 0; t < kApMaxThresholds; ++t) thr.t[t] = t < n_thresholds ? thresholds[t] : 0.0;
-  int32_t* claim = static_cast<int32_t*>(ws);
-  int32_t* tp_cum = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + align_up((size_t)n_thresholds * (size_t)n_gt * 4, 256));
+  const ApWs w = ap_ws(ws, nd, n_gt, n_thresholds);
   if (nd > 0 && n_gt > 0) {
-    PCMI_HIP_CHECK(hipMemsetAsync(claim, 0x7f, (size_t)n_thresholds * (size_t)n_gt * 4, st));
-    ap_claim_kernel<<<dim3((unsigned)ceil_div(nd, 256), (unsigned)n_thresholds), 256, 0, st>>>(best_iou, gt_id, nd, n_gt, thr, claim);
+    PCMI_HIP_CHECK(hipMemsetAsync(w.claim, 0x7f, (size_t)n_thresholds * (size_t)n_gt * 4, st));
+    ap_claim_kernel<<<dim3((unsigned)ceil_div(nd, 256), (unsigned)n_thresholds), 256, 0, st>>>(best_iou, gt_id, nd, n_gt, thr, w.claim);
     PCMI_LAUNCH_CHECK();
   }
-  ap_curve_kernel<<<dim3((unsigned)Cls, (unsigned)n_thresholds), kApThreads, 0, st>>>(gt_id, cls_offs, npos, claim, nd, n_gt, Cls,
-                                                                                      use_07_metric != 0, tp_cum, ap, last_rec, rec, prec,
+  ap_curve_kernel<<<dim3((unsigned)Cls, (unsigned)n_thresholds), kApThreads, 0, st>>>(gt_id, cls_offs, npos, w.claim, nd, n_gt, Cls,
+                                                                                      use_07_metric != 0, w.tp_cum, ap, last_rec, rec, prec,
                                                                                       tp_flag);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;

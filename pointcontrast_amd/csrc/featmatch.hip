@@ -425,8 +425,9 @@ int pcmi_feat_nn(const float* qf, int64_t q_ld, int64_t nq, const int64_t* q_off
   PCMI_REQUIRE(nn && d2 && (nq == 0 || qf) && (nr == 0 || rf), PCMI_ERR_INVALID, "feat_nn: null pointer");
   PCMI_REQUIRE(q_ld >= c && r_ld >= c && q_ld % 4 == 0 && r_ld % 4 == 0 && (uintptr_t)qf % 16 == 0 && (uintptr_t)rf % 16 == 0,
                PCMI_ERR_INVALID, "feat_nn: rows need a stride >= C that is a multiple of 4 floats, and a 16-byte aligned base");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_feat_nn_workspace_bytes(Q) && (uintptr_t)ws % 8 == 0, PCMI_ERR_WORKSPACE,
-               "feat_nn: workspace of %zu bytes, %zu needed (8-byte aligned)", ws_bytes, pcmi_feat_nn_workspace_bytes(Q));
+  if (int rc = require_ws("feat_nn", ws, ws_bytes, pcmi_feat_nn_workspace_bytes(Q), 1)) return rc;
+  // (this entry reports a misaligned base as a workspace error, not as an invalid argument)
+  PCMI_REQUIRE((uintptr_t)ws % 8 == 0, PCMI_ERR_WORKSPACE, "feat_nn: workspace must be 8-byte aligned");
   hipStream_t st = as_stream(stream);
   unsigned long long* keys = static_cast<unsigned long long*>(ws);
   PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)Q * sizeof(unsigned long long), st));

@@ -378,14 +378,12 @@ int pcmi_instance_bench_ap(const int8_t* entry_flag, const double* score, const 
   PCMI_REQUIRE(ap_shape_ok(E, Cls, n_thresholds), PCMI_ERR_INVALID, "instance_bench_ap: bad shape (E %lld < 2^30, 1 <= Cls %d <= %d, 1 <= %d "
                "thresholds <= %d)", (long long)E, Cls, kMaxClasses, n_thresholds, kMaxThresholds);
   PCMI_REQUIRE(cls_offs && npos && ap && (E == 0 || (entry_flag && score)), PCMI_ERR_INVALID, "instance_bench_ap: null pointer");
-  const size_t need = pcmi_instance_bench_ap_workspace_bytes(E, Cls, n_thresholds);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "instance_bench_ap: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 4 == 0, PCMI_ERR_INVALID, "instance_bench_ap: workspace must be 4-byte aligned");
+  if (int rc = require_ws("instance_bench_ap", ws, ws_bytes, pcmi_instance_bench_ap_workspace_bytes(E, Cls, n_thresholds), 4)) return rc;
   hipStream_t st = as_stream(stream);
   const size_t curve = (size_t)n_thresholds * (size_t)E * 8;
   if (prec && curve) PCMI_HIP_CHECK(hipMemsetAsync(prec, 0xff, curve, st));  // NaN wherever no group ends
   if (rec && curve) PCMI_HIP_CHECK(hipMemsetAsync(rec, 0xff, curve, st));
-  ib_ap_kernel<<<dim3((unsigned)Cls, (unsigned)n_thresholds), kThreads, 0, st>>>(entry_flag, score, cls_offs, npos, E, Cls, (int32_t*)ws, ap,
+  ib_ap_kernel<<<dim3((unsigned)Cls, (unsigned)n_thresholds), kThreads, 0, st>>>(entry_flag, score, cls_offs, npos, E, Cls, static_cast<int32_t*>(ws), ap,
                                                                                  prec, rec);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;

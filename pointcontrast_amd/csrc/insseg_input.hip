@@ -304,11 +304,25 @@ using namespace pcmi::insinput;
 
 extern "C" {
 
+struct RelabelWs { uint64_t* keys; uint32_t *first, *slot_of; int32_t *pos, *sums, *boffs, *total; size_t bytes; };
+static RelabelWs relabel_ws(void* ws, int64_t n) {
+  const size_t cap = (size_t)table_cap(n), nb = (size_t)scan_blocks(n + 1);
+  Carve cv{(char*)ws};
+  RelabelWs w;
+  w.keys = cv.take<uint64_t>(cap);
+  w.first = cv.take<uint32_t>(cap);
+  w.slot_of = cv.take<uint32_t>((size_t)std::max<int64_t>(n, 1));
+  w.pos = cv.take<int32_t>((size_t)n + 1);
+  w.sums = cv.take<int32_t>(nb);
+  w.boffs = cv.take<int32_t>(nb);
+  w.total = cv.take<int32_t>(1);
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_instance_relabel_workspace_bytes(int64_t n) {
   if (n < 0 || n > kMaxRows) return 0;
-  const int64_t cap = table_cap(n), n1 = std::max<int64_t>(n, 1);
-  return align_up((size_t)cap * 8, 256) + align_up((size_t)cap * 4, 256) + align_up((size_t)n1 * 4, 256) + align_up((size_t)(n + 1) * 4, 256) +
-         2 * align_up((size_t)scan_blocks(n + 1) * 4, 256) + 256;
+  return relabel_ws(nullptr, n).bytes;
 }
 
 int pcmi_instance_relabel(const int32_t* raw, const uint8_t* keep, const int64_t* offsets, int64_t n, int64_t B, int32_t* instance,
@@ -317,32 +331,22 @@ int pcmi_instance_relabel(const int32_t* raw, const uint8_t* keep, const int64_t
                (long long)B, kMaxScenes);
   PCMI_REQUIRE(n <= kMaxRows, PCMI_ERR_UNSUPPORTED, "instance_relabel: %lld rows, at most 2^29", (long long)n);
   PCMI_REQUIRE(offsets && inst_counts && (n == 0 || (raw && instance && first_row)), PCMI_ERR_INVALID, "instance_relabel: null pointer");
-  const size_t need = pcmi_instance_relabel_workspace_bytes(n);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "instance_relabel: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "instance_relabel: workspace must be 16-byte aligned");
+  if (int rc = require_ws("instance_relabel", ws, ws_bytes, relabel_ws(nullptr, n).bytes, 16)) return rc;
   hipStream_t st = as_stream(stream);
   if (n == 0) {
     PCMI_HIP_CHECK(hipMemsetAsync(inst_counts, 0, (size_t)(B + 1) * 8, st));
     return PCMI_OK;
   }
-  const int64_t cap = table_cap(n), nb = scan_blocks(n + 1);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  uint32_t* first = (uint32_t*)cv.take((size_t)cap * 4);
-  uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  int32_t* sums = (int32_t*)cv.take((size_t)nb * 4);
-  int32_t* boffs = (int32_t*)cv.take((size_t)nb * 4);
-  int32_t* total = (int32_t*)cv.take(4);
-  PCMI_REQUIRE(keys && first && slot_of && pos && sums && boffs && total, PCMI_ERR_WORKSPACE, "instance_relabel: workspace too small");
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, (size_t)cap * 4, st));
-  rl_insert_kernel<<<grid_for(n), kThreads, 0, st>>>(raw, keep, n, offsets, (int)B, keys, (uint32_t)cap, first, slot_of);
+  const int64_t cap = table_cap(n);
+  const RelabelWs w = relabel_ws(ws, n);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.first, 0xff, (size_t)cap * 4, st));
+  rl_insert_kernel<<<grid_for(n), kThreads, 0, st>>>(raw, keep, n, offsets, (int)B, w.keys, (uint32_t)cap, w.first, w.slot_of);
   PCMI_LAUNCH_CHECK();
-  rl_flag_kernel<<<grid_for(n + 1), kThreads, 0, st>>>(n, slot_of, first, pos);
+  rl_flag_kernel<<<grid_for(n + 1), kThreads, 0, st>>>(n, w.slot_of, w.first, w.pos);
   PCMI_LAUNCH_CHECK();
-  if (int rc = scan_excl(pos, n + 1, pos, sums, boffs, total, st)) return rc;
-  rl_write_kernel<<<grid_for(std::max<int64_t>(n, B + 1)), kThreads, 0, st>>>(n, offsets, (int)B, slot_of, first, pos, instance, first_row,
+  if (int rc = scan_excl(w.pos, n + 1, w.pos, w.sums, w.boffs, w.total, st)) return rc;
+  rl_write_kernel<<<grid_for(std::max<int64_t>(n, B + 1)), kThreads, 0, st>>>(n, offsets, (int)B, w.slot_of, w.first, w.pos, instance, first_row,
                                                                                inst_counts);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
@@ -371,11 +375,27 @@ int pcmi_instance_table(const int32_t* instance, const int32_t* klass, const int
   return PCMI_OK;
 }
 
+struct CropWs { int32_t *ext, *cnt, *origin; uint32_t* mask; int32_t *kept, *pos, *sums, *boffs, *total; size_t bytes; };
+static CropWs crop_ws(void* ws, int64_t n, int64_t B) {
+  const size_t nb = (size_t)scan_blocks(n + 1);
+  Carve cv{(char*)ws};
+  CropWs w;
+  w.ext = cv.take<int32_t>((size_t)B * 2);
+  w.cnt = cv.take<int32_t>((size_t)B * kMaxSteps);
+  w.origin = cv.take<int32_t>((size_t)B * kMaxSteps * 2);
+  w.mask = cv.take<uint32_t>((size_t)std::max<int64_t>(n, 1));
+  w.kept = cv.take<int32_t>((size_t)n + 1);
+  w.pos = cv.take<int32_t>((size_t)n + 1);
+  w.sums = cv.take<int32_t>(nb);
+  w.boffs = cv.take<int32_t>(nb);
+  w.total = cv.take<int32_t>(1);
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_seg_crop_ladder_workspace_bytes(int64_t n, int64_t B) {
   if (n < 0 || n > kMaxRows || B < 1 || B > kMaxScenes) return 0;
-  const int64_t n1 = std::max<int64_t>(n, 1);
-  return align_up((size_t)B * 2 * 4, 256) + align_up((size_t)B * kMaxSteps * 4, 256) + align_up((size_t)B * kMaxSteps * 2 * 4, 256) +
-         align_up((size_t)n1 * 4, 256) + 2 * align_up((size_t)(n + 1) * 4, 256) + 2 * align_up((size_t)scan_blocks(n + 1) * 4, 256) + 256;
+  return crop_ws(nullptr, n, B).bytes;
 }
 
 int pcmi_seg_crop_ladder(const int32_t* coords, const int64_t* offsets, int64_t n, int64_t B, int axis0, int axis1, const int32_t* sides_host,
@@ -398,41 +418,28 @@ int pcmi_seg_crop_ladder(const int32_t* coords, const int64_t* offsets, int64_t 
       PCMI_REQUIRE(L.side[s][a] >= 1 && (s == 0 || s >= S || L.side[s][a] <= L.side[s - 1][a]), PCMI_ERR_INVALID,
                    "seg_crop_ladder: side [%d][%d] = %d: every side at least 1, each column non-increasing", s, a, L.side[s][a]);
     }
-  const size_t need = pcmi_seg_crop_ladder_workspace_bytes(n, B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "seg_crop_ladder: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "seg_crop_ladder: workspace must be 16-byte aligned");
+  if (int rc = require_ws("seg_crop_ladder", ws, ws_bytes, crop_ws(nullptr, n, B).bytes, 16)) return rc;
   hipStream_t st = as_stream(stream);
   if (n == 0) {
     PCMI_HIP_CHECK(hipMemsetAsync(kept_counts, 0, (size_t)(B + 1) * 8, st));
     return PCMI_OK;
   }
-  const int64_t nb = scan_blocks(n + 1);
-  Carve cv{(char*)ws, ws_bytes};
-  int32_t* ext = (int32_t*)cv.take((size_t)B * 2 * 4);
-  int32_t* cnt = (int32_t*)cv.take((size_t)B * kMaxSteps * 4);
-  int32_t* origin = (int32_t*)cv.take((size_t)B * kMaxSteps * 2 * 4);
-  uint32_t* mask = (uint32_t*)cv.take((size_t)n * 4);
-  int32_t* kept = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  int32_t* sums = (int32_t*)cv.take((size_t)nb * 4);
-  int32_t* boffs = (int32_t*)cv.take((size_t)nb * 4);
-  int32_t* total = (int32_t*)cv.take(4);
-  PCMI_REQUIRE(ext && cnt && origin && mask && kept && pos && sums && boffs && total, PCMI_ERR_WORKSPACE, "seg_crop_ladder: workspace too small");
+  const CropWs w = crop_ws(ws, n, B);
   const unsigned grid = grid_for(n);
-  cr_init_kernel<<<grid_for(B * kMaxSteps), kThreads, 0, st>>>((int)B, ext, cnt);
+  cr_init_kernel<<<grid_for(B * kMaxSteps), kThreads, 0, st>>>((int)B, w.ext, w.cnt);
   PCMI_LAUNCH_CHECK();
-  cr_extent_kernel<<<grid, kThreads, 0, st>>>(coords, n, offsets, (int)B, axis0, axis1, ext);
+  cr_extent_kernel<<<grid, kThreads, 0, st>>>(coords, n, offsets, (int)B, axis0, axis1, w.ext);
   PCMI_LAUNCH_CHECK();
-  cr_origin_kernel<<<grid_for(B * S * 2), kThreads, 0, st>>>((int)B, L, ext, draws, origin);
+  cr_origin_kernel<<<grid_for(B * S * 2), kThreads, 0, st>>>((int)B, L, w.ext, draws, w.origin);
   PCMI_LAUNCH_CHECK();
-  cr_count_kernel<<<grid, kThreads, 0, st>>>(coords, n, offsets, (int)B, L, max_voxels, origin, mask, cnt);
+  cr_count_kernel<<<grid, kThreads, 0, st>>>(coords, n, offsets, (int)B, L, max_voxels, w.origin, w.mask, w.cnt);
   PCMI_LAUNCH_CHECK();
-  cr_choose_kernel<<<grid_for(B), kThreads, 0, st>>>(offsets, (int)B, S, max_voxels, cnt, step, flags);
+  cr_choose_kernel<<<grid_for(B), kThreads, 0, st>>>(offsets, (int)B, S, max_voxels, w.cnt, step, flags);
   PCMI_LAUNCH_CHECK();
-  cr_flag_kernel<<<grid_for(n + 1), kThreads, 0, st>>>(n, offsets, (int)B, mask, step, kept);
+  cr_flag_kernel<<<grid_for(n + 1), kThreads, 0, st>>>(n, offsets, (int)B, w.mask, step, w.kept);
   PCMI_LAUNCH_CHECK();
-  if (int rc = scan_excl(kept, n + 1, pos, sums, boffs, total, st)) return rc;
-  cr_write_kernel<<<grid_for(std::max<int64_t>(n, B + 1)), kThreads, 0, st>>>(n, offsets, (int)B, kept, pos, rows, kept_counts);
+  if (int rc = scan_excl(w.kept, n + 1, w.pos, w.sums, w.boffs, w.total, st)) return rc;
+  cr_write_kernel<<<grid_for(std::max<int64_t>(n, B + 1)), kThreads, 0, st>>>(n, offsets, (int)B, w.kept, w.pos, rows, kept_counts);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

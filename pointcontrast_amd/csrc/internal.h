@@ -164,19 +164,30 @@ int inverse_lists(const char* who, const int32_t* idx, int64_t B, int64_t L, int
 // on a stream are serialised and every kernel leaves its counters at zero.  nullptr on allocation failure.
 unsigned* stream_counters(hipStream_t st, size_t n);
 
-// bump allocator over a caller's workspace: 256-byte aligned pieces, nullptr once it is exhausted
+// A caller's workspace cut into typed pieces, each rounded up to `align` bytes.  A null base measures: take() returns
+// nullptr and only `used` advances.  Every entry point that carves two or more pieces has ONE static layout function
+// beside it, layout(base, shape...) -> a struct of typed pointers plus `bytes` (= used): the size query is
+// layout(nullptr, shape...).bytes and the entry point checks that many bytes (require_ws) before it calls layout(ws, ...),
+// so the byte count and the pointers come out of the same lines.
 struct Carve {
-  char* p;
-  size_t left;
-  void* take(size_t bytes) {
-    const size_t b = align_up(bytes, 256);
-    if (b > left) return nullptr;
-    void* r = p;
-    p += b;
-    left -= b;
+  char* base;
+  size_t align = 256;
+  size_t used = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* r = base ? reinterpret_cast<T*>(base + used) : nullptr;
+    used += align_up(count * sizeof(T), align);
     return r;
   }
 };
+
+// The workspace check of the C entry points (`if (int rc = require_ws(...)) return rc;`): null or short -> PCMI_ERR_WORKSPACE,
+// then a base that is not `align`-byte aligned -> PCMI_ERR_INVALID (align 1: no requirement).
+static inline int require_ws(const char* who, const void* ws, size_t ws_bytes, size_t need, size_t align) {
+  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who, ws_bytes, need);
+  PCMI_REQUIRE((uintptr_t)ws % align == 0, PCMI_ERR_INVALID, "%s: workspace must be %zu-byte aligned", who, align);
+  return PCMI_OK;
+}
 
 // compute units of the current device (cached; 256 on MI355X)
 static inline int num_cu() {

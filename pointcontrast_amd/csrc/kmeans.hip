@@ -559,9 +559,18 @@ int pcmi_kmeans_step(const float* feat, int64_t ld, int64_t n, const int64_t* of
   return PCMI_OK;
 }
 
-size_t pcmi_kmeans_assign_workspace_bytes(int64_t B, int K) {
-  return B < 1 || K < 1 ? 0 : align_up((size_t)B * K * 8, 256) + (size_t)B * kParts * 8;
+struct AssignWs { unsigned long long* near; double* part; size_t bytes; };
+static AssignWs assign_ws(void* ws, int64_t B, int K) {
+  Carve cv{(char*)ws};
+  AssignWs w;
+  w.near = cv.take<unsigned long long>((size_t)B * K);
+  cv.align = 1;  // the last piece is not padded
+  w.part = cv.take<double>((size_t)B * kParts);
+  w.bytes = cv.used;
+  return w;
 }
+
+size_t pcmi_kmeans_assign_workspace_bytes(int64_t B, int K) { return B < 1 || K < 1 ? 0 : assign_ws(nullptr, B, K).bytes; }
 
 int pcmi_kmeans_assign(const float* feat, int64_t ld, int64_t n, const int64_t* offs, int64_t B, int K, int c, int64_t max_scene_rows,
                        const float* centroid, const int32_t* live, int32_t* assign, float* d2, int32_t* nearest, double* inertia,
@@ -571,13 +580,10 @@ int pcmi_kmeans_assign(const float* feat, int64_t ld, int64_t n, const int64_t* 
   PCMI_REQUIRE(centroid && live && nearest && inertia && cnt && skipped && (n == 0 || (assign && d2)), PCMI_ERR_INVALID,
                "kmeans_assign: null pointer");
   PCMI_REQUIRE((uintptr_t)centroid % 16 == 0, PCMI_ERR_INVALID, "kmeans_assign: centroids need a 16-byte aligned base");
-  const size_t need = pcmi_kmeans_assign_workspace_bytes(B, K);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "kmeans_assign: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 8 == 0, PCMI_ERR_INVALID, "kmeans_assign: workspace must be 8-byte aligned");
+  if (int ws_rc = require_ws("kmeans_assign", ws, ws_bytes, assign_ws(nullptr, B, K).bytes, 8)) return ws_rc;
   hipStream_t st = as_stream(stream);
-  unsigned long long* near = static_cast<unsigned long long*>(ws);
-  double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + align_up((size_t)B * K * 8, 256));
-  PCMI_HIP_CHECK(hipMemsetAsync(near, 0xff, (size_t)B * K * 8, st));
+  const AssignWs w = assign_ws(ws, B, K);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.near, 0xff, (size_t)B * K * 8, st));
   PCMI_HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)B * K * 4, st));
   PCMI_HIP_CHECK(hipMemsetAsync(skipped, 0, (size_t)B * 8, st));
   if (n > 0) {
@@ -586,18 +592,28 @@ int pcmi_kmeans_assign(const float* feat, int64_t ld, int64_t n, const int64_t* 
     TileArgs a = {};
     a.feat = feat; a.ld = ld; a.n = n; a.offs = offs; a.K = K; a.nch = row_chunks(n, B); a.max_rows = max_scene_rows;
     a.centroid = centroid; a.live = live; a.assign = assign; a.d2 = d2; a.cnt = cnt;
-    a.skipped = reinterpret_cast<unsigned long long*>(skipped); a.near = near;
+    a.skipped = reinterpret_cast<unsigned long long*>(skipped); a.near = w.near;
     const int r2 = dispatch_tile<true>(c, dim3((unsigned)B, (unsigned)a.nch), 0, st, a);
     if (r2 != PCMI_OK) return r2;
-    km_inertia_partial_kernel<<<dim3(kPartBlocks, (unsigned)B), kThreads, 0, st>>>(assign, d2, n, offs, max_scene_rows, part);
+    km_inertia_partial_kernel<<<dim3(kPartBlocks, (unsigned)B), kThreads, 0, st>>>(assign, d2, n, offs, max_scene_rows, w.part);
     PCMI_LAUNCH_CHECK();
   }
-  km_final_kernel<<<(unsigned)B, kThreads, 0, st>>>(part, n, offs, max_scene_rows, K, near, inertia, nearest);
+  km_final_kernel<<<(unsigned)B, kThreads, 0, st>>>(w.part, n, offs, max_scene_rows, K, w.near, inertia, nearest);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
 
-size_t pcmi_kmeans_pp_step_workspace_bytes(int64_t B) { return B < 1 ? 0 : (size_t)B * kSeedChunks * 8 + (size_t)B * kSeedChunks * 4; }
+struct SeedWs { unsigned long long* tot; int32_t* firstc; size_t bytes; };
+static SeedWs seed_ws(void* ws, int64_t B) {
+  Carve cv{(char*)ws, 1};  // packed: the 8-byte array, then the 4-byte one
+  SeedWs w;
+  w.tot = cv.take<unsigned long long>((size_t)B * kSeedChunks);
+  w.firstc = cv.take<int32_t>((size_t)B * kSeedChunks);
+  w.bytes = cv.used;
+  return w;
+}
+
+size_t pcmi_kmeans_pp_step_workspace_bytes(int64_t B) { return B < 1 ? 0 : seed_ws(nullptr, B).bytes; }
 
 int pcmi_kmeans_pp_step(const float* feat, int64_t ld, int64_t n, const int64_t* offs, int64_t B, int c, int64_t max_scene_rows,
                         const int32_t* last, const uint64_t* draw, float* mind2, int32_t* next, void* ws, size_t ws_bytes,
@@ -606,18 +622,15 @@ int pcmi_kmeans_pp_step(const float* feat, int64_t ld, int64_t n, const int64_t*
   if (rc != PCMI_OK) return rc;
   PCMI_REQUIRE(draw && next && (n == 0 || mind2), PCMI_ERR_INVALID, "kmeans_pp_step: null pointer");
   PCMI_REQUIRE(n < kNoRow, PCMI_ERR_UNSUPPORTED, "kmeans_pp_step: %lld rows, fewer than %d are supported", (long long)n, kNoRow);
-  const size_t need = pcmi_kmeans_pp_step_workspace_bytes(B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "kmeans_pp_step: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 8 == 0, PCMI_ERR_INVALID, "kmeans_pp_step: workspace must be 8-byte aligned");
+  if (int ws_rc = require_ws("kmeans_pp_step", ws, ws_bytes, seed_ws(nullptr, B).bytes, 8)) return ws_rc;
   hipStream_t st = as_stream(stream);
-  unsigned long long* tot = static_cast<unsigned long long*>(ws);
-  int32_t* firstc = reinterpret_cast<int32_t*>(tot + (size_t)B * kSeedChunks);
-  PCMI_HIP_CHECK(hipMemsetAsync(tot, 0, (size_t)B * kSeedChunks * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(firstc, 0x7f, (size_t)B * kSeedChunks * 4, st));
+  const SeedWs w = seed_ws(ws, B);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.tot, 0, (size_t)B * kSeedChunks * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.firstc, 0x7f, (size_t)B * kSeedChunks * 4, st));
   const int slabs = (int)std::min<int64_t>(kMaxSceneRows / kThreads, ceil_div(std::max<int64_t>(std::min(n, max_scene_rows), 1), kThreads));  // no scene has more
-  km_seed_weights_kernel<<<dim3((unsigned)slabs, (unsigned)B), kThreads, 0, st>>>(feat, ld, n, offs, c, max_scene_rows, last, mind2, tot, firstc);
+  km_seed_weights_kernel<<<dim3((unsigned)slabs, (unsigned)B), kThreads, 0, st>>>(feat, ld, n, offs, c, max_scene_rows, last, mind2, w.tot, w.firstc);
   PCMI_LAUNCH_CHECK();
-  km_seed_pick_kernel<<<(unsigned)B, kThreads, 0, st>>>(feat, ld, n, offs, c, max_scene_rows, mind2, tot, firstc,
+  km_seed_pick_kernel<<<(unsigned)B, kThreads, 0, st>>>(feat, ld, n, offs, c, max_scene_rows, mind2, w.tot, w.firstc,
                                                        reinterpret_cast<const unsigned long long*>(draw), next);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;

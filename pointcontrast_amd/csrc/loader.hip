@@ -121,10 +121,29 @@ using namespace pcmi;
 
 extern "C" {
 
-size_t pcmi_voxelize_workspace_bytes(int64_t n) {
+// The two queries of this file are bounds, not sums of padded pieces: measuring (null base) packs the pieces, piece
+// alignment 1, and adds kPadSlack, which covers the 256-byte padding of the at most eight pieces the entry carves.
+constexpr size_t kPadSlack = 7 * 256 + 1024;
+
+struct VoxWs { uint64_t* keys; uint32_t *first, *slot_of; int32_t *flags, *pos, *err; void* temp; size_t temp_bytes, bytes; };
+static VoxWs vox_ws(void* ws, int64_t n) {
   const uint32_t cap = (uint32_t)table_cap(n);
-  return (size_t)cap * 12 + (size_t)n * 12 + 2 * (size_t)n * 8 + cub_scan_bytes<int32_t>(n) + 8 * 256 + 1024;
+  Carve cv{(char*)ws, ws ? (size_t)256 : (size_t)1};
+  VoxWs w;
+  w.keys = cv.take<uint64_t>(cap);
+  w.first = cv.take<uint32_t>(cap);
+  w.slot_of = cv.take<uint32_t>((size_t)n);
+  w.flags = cv.take<int32_t>((size_t)n);
+  w.pos = cv.take<int32_t>((size_t)n);
+  w.err = cv.take<int32_t>(64);
+  w.temp_bytes = cub_scan_bytes<int32_t>(n);
+  w.temp = cv.take<char>(w.temp_bytes);
+  cv.take<int64_t>(2 * (size_t)n);  // (unused: 16 n bytes the query has counted since it was written)
+  w.bytes = cv.used + kPadSlack;
+  return w;
 }
+
+size_t pcmi_voxelize_workspace_bytes(int64_t n) { return vox_ws(nullptr, n).bytes; }
 
 int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* first_index, int32_t* coords,
                   int64_t* n_unique_host, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
@@ -133,43 +152,48 @@ int pcmi_voxelize(const double* xyz, int64_t n, double voxel_size, int32_t* firs
   *n_unique_host = 0;
   if (n == 0) return PCMI_OK;
   hipStream_t st = as_stream(stream);
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_voxelize_workspace_bytes(n), PCMI_ERR_WORKSPACE, "voxelize: workspace too small");
-  Carve cv{(char*)ws, ws_bytes};
+  if (int rc = require_ws("voxelize", ws, ws_bytes, vox_ws(nullptr, n).bytes, 1)) return rc;
   const uint32_t cap = (uint32_t)table_cap(n);
-  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  uint32_t* first = (uint32_t*)cv.take((size_t)cap * 4);
-  uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
-  int32_t* flags = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)n * 4);
-  int32_t* err = (int32_t*)cv.take(256);
-  const size_t tb = cub_scan_bytes<int32_t>(n);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && first && slot_of && flags && pos && err && temp, PCMI_ERR_WORKSPACE, "voxelize: workspace too small");
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, (size_t)cap * 4, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
+  const VoxWs w = vox_ws(ws, n);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.first, 0xff, (size_t)cap * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.err, 0, 256, st));
   const unsigned gn = (unsigned)ceil_div(n, 256);
-  vox_insert_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, keys, first, cap, slot_of, err);
+  vox_insert_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, w.keys, w.first, cap, w.slot_of, w.err);
   PCMI_LAUNCH_CHECK();
-  vox_flag_kernel<<<gn, 256, 0, st>>>(n, first, slot_of, flags);
+  vox_flag_kernel<<<gn, 256, 0, st>>>(n, w.first, w.slot_of, w.flags);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, flags, pos, n, st)) return rc;
+  if (int rc = cub_scan_excl(w.temp, w.temp_bytes, w.flags, w.pos, n, st)) return rc;
   int32_t host[3] = {0, 0, 0};  // last flag, last pos, error count
-  PCMI_HIP_CHECK(hipMemcpyAsync(&host[0], flags + n - 1, 4, hipMemcpyDeviceToHost, st));
-  PCMI_HIP_CHECK(hipMemcpyAsync(&host[1], pos + n - 1, 4, hipMemcpyDeviceToHost, st));
-  PCMI_HIP_CHECK(hipMemcpyAsync(&host[2], err, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&host[0], w.flags + n - 1, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&host[1], w.pos + n - 1, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&host[2], w.err, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   PCMI_REQUIRE(host[2] == 0, PCMI_ERR_RANGE, "voxelize: %d points are not finite or fall outside +-2^20 voxels", host[2]);
   *n_unique_host = (int64_t)host[0] + host[1];
-  vox_compact_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, flags, pos, first_index, coords);
+  vox_compact_kernel<<<gn, 256, 0, st>>>(xyz, n, voxel_size, w.flags, w.pos, first_index, coords);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
 
-size_t pcmi_match_radius_workspace_bytes(int64_t n0, int64_t n1) {
+struct MatchWs { uint64_t* keys; int32_t *head, *next; int64_t *count, *offs; int32_t* err; void* temp; size_t temp_bytes, bytes; };
+static MatchWs match_ws(void* ws, int64_t n0, int64_t n1) {
   const uint32_t cap = (uint32_t)table_cap(n1);
-  return (size_t)cap * 12 + (size_t)n1 * 4 + 2 * (size_t)n0 * 8 + cub_scan_bytes<int64_t>(n0) + 8 * 256 + 1024;
+  Carve cv{(char*)ws, ws ? (size_t)256 : (size_t)1};
+  MatchWs w;
+  w.keys = cv.take<uint64_t>(cap);
+  w.head = cv.take<int32_t>(cap);
+  w.next = cv.take<int32_t>((size_t)n1);
+  w.count = cv.take<int64_t>((size_t)n0);
+  w.offs = cv.take<int64_t>((size_t)n0);
+  w.err = cv.take<int32_t>(64);
+  w.temp_bytes = cub_scan_bytes<int64_t>(n0);
+  w.temp = cv.take<char>(w.temp_bytes);
+  w.bytes = cv.used + kPadSlack;
+  return w;
 }
+
+size_t pcmi_match_radius_workspace_bytes(int64_t n0, int64_t n1) { return match_ws(nullptr, n0, n1).bytes; }
 
 int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host, const double* dst, int64_t n1, double radius,
                       int32_t* pairs, int64_t pairs_capacity, int64_t* n_pairs_host, void* ws, size_t ws_bytes,
@@ -179,34 +203,25 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   *n_pairs_host = 0;
   if (n0 == 0 || n1 == 0) return PCMI_OK;
   hipStream_t st = as_stream(stream);
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_match_radius_workspace_bytes(n0, n1), PCMI_ERR_WORKSPACE, "match_radius: workspace too small");
-  Carve cv{(char*)ws, ws_bytes};
+  if (int rc = require_ws("match_radius", ws, ws_bytes, match_ws(nullptr, n0, n1).bytes, 1)) return rc;
   const uint32_t cap = (uint32_t)table_cap(n1);
-  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  int32_t* head = (int32_t*)cv.take((size_t)cap * 4);
-  int32_t* next = (int32_t*)cv.take((size_t)n1 * 4);
-  int64_t* count = (int64_t*)cv.take((size_t)n0 * 8);
-  int64_t* offs = (int64_t*)cv.take((size_t)n0 * 8);
-  int32_t* err = (int32_t*)cv.take(256);
-  const size_t tb = cub_scan_bytes<int64_t>(n0);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && head && next && count && offs && err && temp, PCMI_ERR_WORKSPACE, "match_radius: workspace too small");
+  const MatchWs w = match_ws(ws, n0, n1);
   Rigid T;
   for (int q = 0; q < 12; ++q) T.m[q] = rigid3x4_host[q];
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(head, 0xff, (size_t)cap * 4, st));  // -1
-  PCMI_HIP_CHECK(hipMemsetAsync(err, 0, 256, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.head, 0xff, (size_t)cap * 4, st));  // -1
+  PCMI_HIP_CHECK(hipMemsetAsync(w.err, 0, 256, st));
   const unsigned g0 = (unsigned)ceil_div(n0, 128), g1 = (unsigned)ceil_div(n1, 256);
-  grid_insert_kernel<<<g1, 256, 0, st>>>(dst, n1, radius, keys, head, cap, next, err);
+  grid_insert_kernel<<<g1, 256, 0, st>>>(dst, n1, radius, w.keys, w.head, cap, w.next, w.err);
   PCMI_LAUNCH_CHECK();
-  match_kernel<false><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, keys, head, cap, next, count, nullptr, nullptr, err);
+  match_kernel<false><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, w.keys, w.head, cap, w.next, w.count, nullptr, nullptr, w.err);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, count, offs, n0, st)) return rc;
+  if (int rc = cub_scan_excl(w.temp, w.temp_bytes, w.count, w.offs, n0, st)) return rc;
   int64_t last[2] = {0, 0};
   int32_t herr = 0;
-  PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], count + n0 - 1, 8, hipMemcpyDeviceToHost, st));
-  PCMI_HIP_CHECK(hipMemcpyAsync(&last[1], offs + n0 - 1, 8, hipMemcpyDeviceToHost, st));
-  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&last[0], w.count + n0 - 1, 8, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&last[1], w.offs + n0 - 1, 8, hipMemcpyDeviceToHost, st));
+  PCMI_HIP_CHECK(hipMemcpyAsync(&herr, w.err, 4, hipMemcpyDeviceToHost, st));
   PCMI_HIP_CHECK(hipStreamSynchronize(st));
   PCMI_REQUIRE(herr == 0, PCMI_ERR_RANGE,
                "match_radius: %d points not finite, outside +-2^20 cells or with more than %d matches (is the radius far above the voxel size?)",
@@ -215,7 +230,7 @@ int pcmi_match_radius(const double* src, int64_t n0, const double* rigid3x4_host
   if (!pairs || *n_pairs_host == 0) return PCMI_OK;  // count-only call
   PCMI_REQUIRE(pairs_capacity >= *n_pairs_host, PCMI_ERR_WORKSPACE, "match_radius: %lld pairs but room for %lld",
                (long long)*n_pairs_host, (long long)pairs_capacity);
-  match_kernel<true><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, keys, head, cap, next, nullptr, offs, pairs, err);
+  match_kernel<true><<<g0, 128, 0, st>>>(src, n0, T, dst, n1, radius, w.keys, w.head, cap, w.next, nullptr, w.offs, pairs, w.err);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

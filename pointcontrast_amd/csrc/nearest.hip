@@ -303,12 +303,35 @@ int pcmi_voxel_centers(const int32_t* coords, int64_t n, const double* inv_T_hos
   return PCMI_OK;
 }
 
+struct NearestWs {
+  uint64_t* keys;
+  int32_t *count, *start;
+  uint32_t* slot_of;
+  Rec* rec;
+  int32_t *flags, *fb_list;  // flags: [B] scene flags, then the fallback list's length
+  void* temp;
+  size_t temp_bytes, bytes;
+};
+static NearestWs nearest_ws(void* ws, int64_t m, int64_t n, int64_t B) {
+  const size_t cap = (size_t)table_cap(m), m1 = (size_t)std::max<int64_t>(m, 1);
+  Carve cv{(char*)ws};
+  NearestWs w;
+  w.keys = cv.take<uint64_t>(cap);
+  w.count = cv.take<int32_t>(cap + 1);
+  w.start = cv.take<int32_t>(cap + 1);
+  w.slot_of = cv.take<uint32_t>(m1);
+  w.rec = cv.take<Rec>(m1);
+  w.flags = cv.take<int32_t>((size_t)B + 1);
+  w.fb_list = cv.take<int32_t>((size_t)std::max<int64_t>(n, 1));
+  w.temp_bytes = cub_scan_bytes<int32_t>((int64_t)cap + 1);
+  w.temp = cv.take<char>(w.temp_bytes);
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_nearest_point_workspace_bytes(int64_t m, int64_t n, int64_t B) {
   if (!nn_shape_ok(m, n, B) || m > kMaxRef) return 0;
-  const int64_t cap = table_cap(m);
-  return align_up((size_t)cap * 8, 256) + 2 * align_up((size_t)(cap + 1) * 4, 256) + align_up((size_t)std::max<int64_t>(m, 1) * 4, 256) +
-         align_up((size_t)std::max<int64_t>(m, 1) * sizeof(Rec), 256) + align_up((size_t)(B + 1) * 4, 256) +
-         align_up((size_t)std::max<int64_t>(n, 1) * 4, 256) + cub_scan_bytes<int32_t>(cap + 1);
+  return nearest_ws(nullptr, m, n, B).bytes;
 }
 
 int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, const double* query, const int64_t* query_offs, int64_t n,
@@ -320,42 +343,29 @@ int pcmi_nearest_point(const double* ref, const int64_t* ref_offs, int64_t m, co
   PCMI_REQUIRE(cell_dev || (cell > 0.0 && cell < __builtin_inf()), PCMI_ERR_INVALID, "nearest_point: cell must be positive and finite");
   if (n == 0) return PCMI_OK;
   PCMI_REQUIRE(query && query_offs && ref_offs && idx && (m == 0 || ref), PCMI_ERR_INVALID, "nearest_point: null pointer");
-  const size_t need = pcmi_nearest_point_workspace_bytes(m, n, B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "nearest_point: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "nearest_point: workspace must be 16-byte aligned");
+  if (int rc = require_ws("nearest_point", ws, ws_bytes, nearest_ws(nullptr, m, n, B).bytes, 16)) return rc;
   const int64_t cap = table_cap(m);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  int32_t* count = (int32_t*)cv.take((size_t)(cap + 1) * 4);
-  int32_t* start = (int32_t*)cv.take((size_t)(cap + 1) * 4);
-  uint32_t* slot_of = (uint32_t*)cv.take((size_t)std::max<int64_t>(m, 1) * 4);
-  Rec* rec = (Rec*)cv.take((size_t)std::max<int64_t>(m, 1) * sizeof(Rec));
-  int32_t* flags = (int32_t*)cv.take((size_t)(B + 1) * 4);  // [B] scene flags, then the fallback list's length
-  int32_t* fb_list = (int32_t*)cv.take((size_t)n * 4);
-  const size_t tb = cub_scan_bytes<int32_t>(cap + 1);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && count && start && slot_of && rec && flags && fb_list && temp, PCMI_ERR_WORKSPACE,
-               "nearest_point: workspace too small");
+  const NearestWs w = nearest_ws(ws, m, n, B);
   hipStream_t st = as_stream(stream);
   const uint32_t mask = (uint32_t)(cap - 1);
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(count, 0, (size_t)(cap + 1) * 4, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)(B + 1) * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.count, 0, (size_t)(cap + 1) * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(w.flags, 0, (size_t)(B + 1) * 4, st));
   if (m > 0) {
-    nn_count_kernel<<<(unsigned)ceil_div(m, kThreads), kThreads, 0, st>>>(ref, m, ref_offs, (int)B, cell, cell_dev, keys, mask, count, slot_of,
-                                                                           flags);
+    nn_count_kernel<<<(unsigned)ceil_div(m, kThreads), kThreads, 0, st>>>(ref, m, ref_offs, (int)B, cell, cell_dev, w.keys, mask, w.count, w.slot_of,
+                                                                           w.flags);
     PCMI_LAUNCH_CHECK();
   }
-  if (int rc = cub_scan_excl(temp, tb, count, start, cap + 1, st)) return rc;
+  if (int rc = cub_scan_excl(w.temp, w.temp_bytes, w.count, w.start, cap + 1, st)) return rc;
   if (m > 0) {
-    nn_fill_kernel<<<(unsigned)ceil_div(m, kThreads), kThreads, 0, st>>>(ref, m, slot_of, start, count, rec);
+    nn_fill_kernel<<<(unsigned)ceil_div(m, kThreads), kThreads, 0, st>>>(ref, m, w.slot_of, w.start, w.count, w.rec);
     PCMI_LAUNCH_CHECK();
   }
-  nn_query_kernel<<<(unsigned)ceil_div(n, kThreads), kThreads, 0, st>>>(query, n, query_offs, ref_offs, m, (int)B, cell, cell_dev, keys, mask,
-                                                                         start, rec, flags, idx, dist2, flags + B, fb_list);
+  nn_query_kernel<<<(unsigned)ceil_div(n, kThreads), kThreads, 0, st>>>(query, n, query_offs, ref_offs, m, (int)B, cell, cell_dev, w.keys, mask,
+                                                                         w.start, w.rec, w.flags, idx, dist2, w.flags + B, w.fb_list);
   PCMI_LAUNCH_CHECK();
   nn_fallback_kernel<<<(unsigned)std::min<int64_t>(n, kFallbackGrid), kThreads, 0, st>>>(
-      ref, m, ref_offs, query, query_offs, (int)B, flags + B, fb_list, idx, dist2, reinterpret_cast<unsigned long long*>(fallback_count));
+      ref, m, ref_offs, query, query_offs, (int)B, w.flags + B, w.fb_list, idx, dist2, reinterpret_cast<unsigned long long*>(fallback_count));
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -475,11 +475,9 @@ int pcmi_pair_transform(const void* raw, int raw_is_f32, const int64_t* offsets,
                (long long)B, kMaxPairs);
   PCMI_REQUIRE(offsets && scale && T && trans && flags && (n == 0 || (raw && points)) && (!rotate || rot), PCMI_ERR_INVALID,
                "pair_transform: null pointer");
-  const size_t need = pcmi_pair_transform_workspace_bytes(n, B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "pair_transform: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "pair_transform: workspace must be 16-byte aligned");
+  if (int rc = require_ws("pair_transform", ws, ws_bytes, pcmi_pair_transform_workspace_bytes(n, B), 16)) return rc;
   hipStream_t st = as_stream(stream);
-  double* partial = (double*)ws;
+  double* partial = static_cast<double*>(ws);
   const int f32 = raw_is_f32 ? 1 : 0, rt = rotate ? 1 : 0;
   if (rt && n > 0) {
     tf_partial_kernel<<<(unsigned)max_chunks(n, B), kThreads, 0, st>>>(raw, f32, n, offsets, (int)(2 * B), scale, partial);
@@ -494,11 +492,25 @@ int pcmi_pair_transform(const void* raw, int raw_is_f32, const int64_t* offsets,
   return PCMI_OK;
 }
 
+struct VoxelizeWs { uint64_t* keys; uint32_t *first, *slot_of; int32_t *is_first, *pos; void* temp; size_t temp_bytes, bytes; };
+static VoxelizeWs voxelize_ws(void* ws, int64_t n, int64_t B) {
+  const size_t slots = (size_t)table_slots(n, B);
+  Carve cv{(char*)ws};
+  VoxelizeWs L;
+  L.keys = cv.take<uint64_t>(slots);
+  L.first = cv.take<uint32_t>(slots);
+  L.slot_of = cv.take<uint32_t>((size_t)std::max<int64_t>(n, 1));
+  L.is_first = cv.take<int32_t>((size_t)n + 1);
+  L.pos = cv.take<int32_t>((size_t)n + 1);
+  L.temp_bytes = cub_scan_bytes<int32_t>(n + 1);
+  L.temp = cv.take<char>(L.temp_bytes);
+  L.bytes = cv.used;
+  return L;
+}
+
 size_t pcmi_pair_voxelize_workspace_bytes(int64_t n, int64_t B) {
   if (!batch_ok(n, B) || n > kMaxRows) return 0;
-  const int64_t slots = table_slots(n, B), n1 = std::max<int64_t>(n, 1);
-  return align_up((size_t)slots * 8, 256) + align_up((size_t)slots * 4, 256) + align_up((size_t)n1 * 4, 256) +
-         2 * align_up((size_t)(n + 1) * 4, 256) + cub_scan_bytes<int32_t>(n + 1);
+  return voxelize_ws(nullptr, n, B).bytes;
 }
 
 // replaces pretrain/pointcontrast/lib/ddp_data_loaders.py:228-229, :238-239, :258-259 (sparse_quantize of both frames, floor)
@@ -511,9 +523,7 @@ int pcmi_pair_voxelize(const double* points, const int64_t* offsets, int64_t n, 
   PCMI_REQUIRE(voxel_size > 0.0 && voxel_size < 1e300, PCMI_ERR_INVALID, "pair_voxelize: voxel_size must be positive and finite");
   PCMI_REQUIRE(offsets && n_vox && vox_offsets && side_offsets && flags && (n == 0 || (points && out_points && coords && first_index)),
                PCMI_ERR_INVALID, "pair_voxelize: null pointer");
-  const size_t need = pcmi_pair_voxelize_workspace_bytes(n, B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "pair_voxelize: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "pair_voxelize: workspace must be 16-byte aligned");
+  if (int rc = require_ws("pair_voxelize", ws, ws_bytes, voxelize_ws(nullptr, n, B).bytes, 16)) return rc;
   hipStream_t st = as_stream(stream);
   const int nc = (int)(2 * B);
   if (n == 0) {
@@ -523,24 +533,16 @@ int pcmi_pair_voxelize(const double* points, const int64_t* offsets, int64_t n, 
     return PCMI_OK;
   }
   const int64_t slots = table_slots(n, B);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take((size_t)slots * 8);
-  uint32_t* first = (uint32_t*)cv.take((size_t)slots * 4);
-  uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
-  int32_t* is_first = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  const size_t tb = cub_scan_bytes<int32_t>(n + 1);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && first && slot_of && is_first && pos && temp, PCMI_ERR_WORKSPACE, "pair_voxelize: workspace too small");
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)slots * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, (size_t)slots * 4, st));
+  const VoxelizeWs L = voxelize_ws(ws, n, B);
+  PCMI_HIP_CHECK(hipMemsetAsync(L.keys, 0xff, (size_t)slots * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.first, 0xff, (size_t)slots * 4, st));
   const unsigned grid = (unsigned)ceil_div(n, kThreads);
-  vx_insert_kernel<<<grid, kThreads, 0, st>>>(points, n, offsets, nc, voxel_size, keys, first, slot_of, flags);
+  vx_insert_kernel<<<grid, kThreads, 0, st>>>(points, n, offsets, nc, voxel_size, L.keys, L.first, L.slot_of, flags);
   PCMI_LAUNCH_CHECK();
-  vx_first_kernel<<<(unsigned)ceil_div(n + 1, kThreads), kThreads, 0, st>>>(n, offsets, nc, slot_of, first, flags, is_first);
+  vx_first_kernel<<<(unsigned)ceil_div(n + 1, kThreads), kThreads, 0, st>>>(n, offsets, nc, L.slot_of, L.first, flags, L.is_first);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, is_first, pos, n + 1, st)) return rc;
-  vx_write_kernel<<<(unsigned)ceil_div(std::max<int64_t>(n, nc + 1), kThreads), kThreads, 0, st>>>(points, n, offsets, nc, voxel_size, is_first, pos,
+  if (int rc = cub_scan_excl(L.temp, L.temp_bytes, L.is_first, L.pos, n + 1, st)) return rc;
+  vx_write_kernel<<<(unsigned)ceil_div(std::max<int64_t>(n, nc + 1), kThreads), kThreads, 0, st>>>(points, n, offsets, nc, voxel_size, L.is_first, L.pos,
                                                                                                   out_points, coords, first_index, n_vox, vox_offsets);
   PCMI_LAUNCH_CHECK();
   vx_side_kernel<<<1, 64, 0, st>>>(n_vox, (int)B, side_offsets);
@@ -548,11 +550,27 @@ int pcmi_pair_voxelize(const double* points, const int64_t* offsets, int64_t n, 
   return PCMI_OK;
 }
 
+struct MatchWs { uint64_t* keys; int32_t *head, *next; int64_t *count, *offs, *pair_base; int32_t* nq; void* temp; size_t temp_bytes, bytes; };
+static MatchWs match_ws(void* ws, int64_t m_max, int64_t B) {
+  const size_t slots = (size_t)table_slots(m_max, B);
+  Carve cv{(char*)ws};
+  MatchWs L;
+  L.keys = cv.take<uint64_t>(slots);
+  L.head = cv.take<int32_t>(slots);
+  L.next = cv.take<int32_t>((size_t)std::max<int64_t>(m_max, 1));
+  L.count = cv.take<int64_t>((size_t)m_max + 1);
+  L.offs = cv.take<int64_t>((size_t)m_max + 1);
+  L.pair_base = cv.take<int64_t>((size_t)B);
+  L.nq = cv.take<int32_t>(2 * (size_t)B);  // B values are used; sized as B 8-byte words since the entry was written
+  L.temp_bytes = cub_scan_bytes<int64_t>(m_max + 1);
+  L.temp = cv.take<char>(L.temp_bytes);
+  L.bytes = cv.used;
+  return L;
+}
+
 size_t pcmi_pair_match_workspace_bytes(int64_t m_max, int64_t B) {
   if (!batch_ok(m_max, B) || m_max > kMaxRows) return 0;
-  const int64_t slots = table_slots(m_max, B), m1 = std::max<int64_t>(m_max, 1);
-  return align_up((size_t)slots * 8, 256) + align_up((size_t)slots * 4, 256) + align_up((size_t)m1 * 4, 256) +
-         2 * align_up((size_t)(m_max + 1) * 8, 256) + 2 * align_up((size_t)B * 8, 256) + cub_scan_bytes<int64_t>(m_max + 1);
+  return match_ws(nullptr, m_max, B).bytes;
 }
 
 // replaces pretrain/pointcontrast/lib/ddp_data_loaders.py:36-49, :241 (get_matching_indices) and the offsets of :76-83
@@ -565,41 +583,29 @@ int pcmi_pair_match(const double* points, int64_t m_max, const int64_t* vox_offs
   PCMI_REQUIRE(capacity >= 0 && capacity < (1ll << 31), PCMI_ERR_INVALID, "pair_match: capacity %lld outside [0, 2^31)", (long long)capacity);
   PCMI_REQUIRE(vox_offsets && side_offsets && trans && radius && pair_counts && totals && flags && (m_max == 0 || points) &&
                    (capacity == 0 || pairs), PCMI_ERR_INVALID, "pair_match: null pointer");
-  const size_t need = pcmi_pair_match_workspace_bytes(m_max, B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "pair_match: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "pair_match: workspace must be 16-byte aligned");
+  if (int rc = require_ws("pair_match", ws, ws_bytes, match_ws(nullptr, m_max, B).bytes, 16)) return rc;
   hipStream_t st = as_stream(stream);
   const int nc = (int)(2 * B);
   const int64_t slots = table_slots(m_max, B);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take((size_t)slots * 8);
-  int32_t* head = (int32_t*)cv.take((size_t)slots * 4);
-  int32_t* next = (int32_t*)cv.take((size_t)std::max<int64_t>(m_max, 1) * 4);
-  int64_t* count = (int64_t*)cv.take((size_t)(m_max + 1) * 8);
-  int64_t* offs = (int64_t*)cv.take((size_t)(m_max + 1) * 8);
-  int64_t* pair_base = (int64_t*)cv.take((size_t)B * 8);
-  int32_t* nq = (int32_t*)cv.take((size_t)B * 8);
-  const size_t tb = cub_scan_bytes<int64_t>(m_max + 1);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && head && next && count && offs && pair_base && nq && temp, PCMI_ERR_WORKSPACE, "pair_match: workspace too small");
+  const MatchWs L = match_ws(ws, m_max, B);
   const unsigned g128 = (unsigned)ceil_div(m_max + 1, 128);
   if (!fill_only) {  // (fill_only: the cells, the counts and their scan are in ws, as the call before left them)
-    PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)slots * 8, st));
-    PCMI_HIP_CHECK(hipMemsetAsync(head, 0xff, (size_t)slots * 4, st));  // -1
-    PCMI_HIP_CHECK(hipMemsetAsync(nq, 0, (size_t)B * 4, st));
+    PCMI_HIP_CHECK(hipMemsetAsync(L.keys, 0xff, (size_t)slots * 8, st));
+    PCMI_HIP_CHECK(hipMemsetAsync(L.head, 0xff, (size_t)slots * 4, st));  // -1
+    PCMI_HIP_CHECK(hipMemsetAsync(L.nq, 0, (size_t)B * 4, st));
     if (m_max > 0) {
-      mt_insert_kernel<<<(unsigned)ceil_div(m_max, kThreads), kThreads, 0, st>>>(points, m_max, vox_offsets, nc, radius, keys, head, next, flags);
+      mt_insert_kernel<<<(unsigned)ceil_div(m_max, kThreads), kThreads, 0, st>>>(points, m_max, vox_offsets, nc, radius, L.keys, L.head, L.next, flags);
       PCMI_LAUNCH_CHECK();
     }
-    mt_match_kernel<false><<<g128, 128, 0, st>>>(points, m_max, vox_offsets, nc, trans, radius, keys, head, next, count, nq, nullptr, nullptr,
+    mt_match_kernel<false><<<g128, 128, 0, st>>>(points, m_max, vox_offsets, nc, trans, radius, L.keys, L.head, L.next, L.count, L.nq, nullptr, nullptr,
                                                 nullptr, nullptr, nullptr, flags);
     PCMI_LAUNCH_CHECK();
-    if (int rc = cub_scan_excl(temp, tb, count, offs, m_max + 1, st)) return rc;
+    if (int rc = cub_scan_excl(L.temp, L.temp_bytes, L.count, L.offs, m_max + 1, st)) return rc;
   }
-  mt_pair_kernel<<<1, kMaxPairs, 0, st>>>(vox_offsets, m_max, (int)B, offs, nq, flags, side_offsets, capacity, pair_counts, pair_base, totals, pairs);
+  mt_pair_kernel<<<1, kMaxPairs, 0, st>>>(vox_offsets, m_max, (int)B, L.offs, L.nq, flags, side_offsets, capacity, pair_counts, L.pair_base, totals, pairs);
   PCMI_LAUNCH_CHECK();
   if (m_max > 0 && capacity > 0) {
-    mt_match_kernel<true><<<g128, 128, 0, st>>>(points, m_max, vox_offsets, nc, trans, radius, keys, head, next, count, nq, offs, pair_base,
+    mt_match_kernel<true><<<g128, 128, 0, st>>>(points, m_max, vox_offsets, nc, trans, radius, L.keys, L.head, L.next, L.count, L.nq, L.offs, L.pair_base,
                                                side_offsets, totals, pairs, flags);
     PCMI_LAUNCH_CHECK();
   }

@@ -80,34 +80,37 @@ using namespace pcmi;
 
 extern "C" {
 
-size_t pcmi_pair_select_workspace_bytes(int64_t n_pairs) {
-  const int64_t blocks = ceil_div(std::max<int64_t>(n_pairs, 1), kScanBlock);
-  return align_up(sizeof(int32_t) * (size_t)std::max<int64_t>(n_pairs, 1), 256) + 2 * align_up(sizeof(int32_t) * (size_t)blocks, 256) + 256;
+struct SelectWs { int32_t *starts, *block_counts, *block_offs, *n_runs; size_t bytes; };
+static SelectWs select_ws(void* ws, int64_t n_pairs) {
+  const size_t n = (size_t)std::max<int64_t>(n_pairs, 1), blocks = (size_t)ceil_div((int64_t)n, kScanBlock);
+  Carve cv{(char*)ws};
+  SelectWs w;
+  w.starts = cv.take<int32_t>(n);
+  w.block_counts = cv.take<int32_t>(blocks);
+  w.block_offs = cv.take<int32_t>(blocks);
+  w.n_runs = cv.take<int32_t>(1);  // (written, never read: the host passes n_unique)
+  w.bytes = cv.used;
+  return w;
 }
+
+size_t pcmi_pair_select_workspace_bytes(int64_t n_pairs) { return select_ws(nullptr, n_pairs).bytes; }
 
 int pcmi_pair_select(const int32_t* pairs, int64_t n_pairs, int64_t n_unique, const float* uniform, const int64_t* sampled,
                      int64_t n_sel, int64_t* q_idx, int64_t* k_idx, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
   PCMI_REQUIRE(pairs && uniform && ((q_idx && k_idx) || n_sel == 0) && n_pairs > 0 && n_pairs < (1ll << 31) && n_unique > 0 && n_sel >= 0, PCMI_ERR_INVALID,
                "pair_select: bad argument");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_pair_select_workspace_bytes(n_pairs), PCMI_ERR_WORKSPACE, "pair_select: workspace too small");
+  if (int rc = require_ws("pair_select", ws, ws_bytes, select_ws(nullptr, n_pairs).bytes, 1)) return rc;
   if (n_sel == 0) return PCMI_OK;
   hipStream_t st = as_stream(stream);
   const int64_t blocks = ceil_div(n_pairs, kScanBlock);
-  char* p = (char*)ws;
-  int32_t* starts = (int32_t*)p;
-  p += align_up(sizeof(int32_t) * (size_t)n_pairs, 256);
-  int32_t* block_counts = (int32_t*)p;
-  p += align_up(sizeof(int32_t) * (size_t)blocks, 256);
-  int32_t* block_offs = (int32_t*)p;
-  p += align_up(sizeof(int32_t) * (size_t)blocks, 256);
-  int32_t* n_runs = (int32_t*)p;  // (written, never read: the host passes n_unique)
-  runs_count_kernel<<<dim3((unsigned)blocks), kThreads, 0, st>>>(pairs, n_pairs, block_counts);
+  const SelectWs w = select_ws(ws, n_pairs);
+  runs_count_kernel<<<dim3((unsigned)blocks), kThreads, 0, st>>>(pairs, n_pairs, w.block_counts);
   PCMI_LAUNCH_CHECK();
-  rowscan::scan_blocks_kernel<<<1, kThreads, 0, st>>>(block_counts, (int)blocks, block_offs, n_runs);
+  rowscan::scan_blocks_kernel<<<1, kThreads, 0, st>>>(w.block_counts, (int)blocks, w.block_offs, w.n_runs);
   PCMI_LAUNCH_CHECK();
-  runs_write_kernel<<<dim3((unsigned)blocks), kThreads, 0, st>>>(pairs, n_pairs, block_offs, starts);
+  runs_write_kernel<<<dim3((unsigned)blocks), kThreads, 0, st>>>(pairs, n_pairs, w.block_offs, w.starts);
   PCMI_LAUNCH_CHECK();
-  pair_pick_kernel<<<dim3((unsigned)ceil_div(n_sel, kThreads)), kThreads, 0, st>>>(pairs, n_pairs, starts, n_unique, uniform, sampled, n_sel, q_idx, k_idx);
+  pair_pick_kernel<<<dim3((unsigned)ceil_div(n_sel, kThreads)), kThreads, 0, st>>>(pairs, n_pairs, w.starts, n_unique, uniform, sampled, n_sel, q_idx, k_idx);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }

@@ -443,36 +443,42 @@ static int gather_fwd(const char* who, const float* feat, const int32_t* idx, in
   return PCMI_OK;
 }
 
-static size_t scatter_workspace(int64_t n_idx, int64_t n_targets) {
+struct ScatterWs { int32_t *keys, *keys_sorted, *iota, *pos, *count, *start; void* temp; size_t temp_bytes, bytes; };
+static ScatterWs scatter_ws(void* ws, int64_t n_idx, int64_t n_targets) {
   n_idx = std::max<int64_t>(n_idx, 1);
   n_targets = std::max<int64_t>(n_targets, 1);
-  return 4 * align_up((size_t)n_idx * 4, 256) + 2 * align_up((size_t)(n_targets + 1) * 4, 256) +
-         align_up(std::max(cub_scan_bytes<int32_t>(n_targets + 1), sort_bytes(n_idx)), 256) + 256;
+  Carve cv{(char*)ws};
+  ScatterWs w;
+  w.keys = cv.take<int32_t>((size_t)n_idx);
+  w.keys_sorted = cv.take<int32_t>((size_t)n_idx);
+  w.iota = cv.take<int32_t>((size_t)n_idx);
+  w.pos = cv.take<int32_t>((size_t)n_idx);
+  w.count = cv.take<int32_t>((size_t)n_targets + 1);
+  w.start = cv.take<int32_t>((size_t)n_targets + 1);
+  w.temp_bytes = std::max(cub_scan_bytes<int32_t>(n_targets + 1), sort_bytes(n_idx));
+  w.temp = cv.take<char>(w.temp_bytes);
+  cv.take<char>(256);  // (unused tail the query has always counted)
+  w.bytes = cv.used;
+  return w;
 }
+static size_t scatter_workspace(int64_t n_idx, int64_t n_targets) { return scatter_ws(nullptr, n_idx, n_targets).bytes; }
 
 // The inverse lists of idx [B, L] (targets in [0, N)): the flat source positions p = b L + l of target (b, t) are
 // pos[start[b N + t] .. start[b N + t + 1]), in ascending p.  n_idx = B L > 0, n_targets = B N > 0; both < 2^31 - 1.
 static int build_inverse_lists(const char* who, const int32_t* idx, int64_t B, int64_t L, int64_t N, int validate, void* ws,
                                size_t ws_bytes, const int32_t** start_out, const int32_t** pos_out, hipStream_t st) {
   const int64_t n_idx = B * L, n_targets = B * N;
-  PCMI_REQUIRE(ws && ws_bytes >= scatter_workspace(n_idx, n_targets), PCMI_ERR_WORKSPACE, "%s: workspace too small", who);
-  Carve cv{(char*)ws, ws_bytes};
-  int32_t* keys = (int32_t*)cv.take((size_t)n_idx * 4);
-  int32_t* keys_sorted = (int32_t*)cv.take((size_t)n_idx * 4);
-  int32_t* iota = (int32_t*)cv.take((size_t)n_idx * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)n_idx * 4);
-  int32_t* count = (int32_t*)cv.take((size_t)(n_targets + 1) * 4);
-  int32_t* start = (int32_t*)cv.take((size_t)(n_targets + 1) * 4);
-  const size_t tb = std::max(cub_scan_bytes<int32_t>(n_targets + 1), sort_bytes(n_idx));
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && keys_sorted && iota && pos && count && start && temp, PCMI_ERR_WORKSPACE, "%s: workspace too small", who);
+  if (int rc = require_ws(who, ws, ws_bytes, scatter_workspace(n_idx, n_targets), 1)) return rc;
+  const ScatterWs w = scatter_ws(ws, n_idx, n_targets);
+  void* temp = w.temp;
+  const size_t tb = w.temp_bytes;
   unsigned* flag = nullptr;
   if (validate) {
     flag = stream_counters(st, 1);
     if (!flag) return PCMI_ERR_HIP;
   }
-  PCMI_HIP_CHECK(hipMemsetAsync(count, 0, (size_t)(n_targets + 1) * 4, st));
-  scatter_keys_kernel<<<(unsigned)ceil_div(n_idx, 256), 256, 0, st>>>(idx, n_idx, L, N, n_targets, keys, iota, count, flag);
+  PCMI_HIP_CHECK(hipMemsetAsync(w.count, 0, (size_t)(n_targets + 1) * 4, st));
+  scatter_keys_kernel<<<(unsigned)ceil_div(n_idx, 256), 256, 0, st>>>(idx, n_idx, L, N, n_targets, w.keys, w.iota, w.count, flag);
   PCMI_LAUNCH_CHECK();
   if (validate) {
     unsigned bad = 0;
@@ -481,14 +487,14 @@ static int build_inverse_lists(const char* who, const int32_t* idx, int64_t B, i
     PCMI_HIP_CHECK(hipStreamSynchronize(st));
     PCMI_REQUIRE(!bad, PCMI_ERR_RANGE, "%s: an index is outside [0, %lld)", who, (long long)N);
   }
-  if (int rc = cub_scan_excl(temp, tb, count, start, n_targets + 1, st)) return rc;
+  if (int rc = cub_scan_excl(temp, tb, w.count, w.start, n_targets + 1, st)) return rc;
   int bits = 1;
   while (bits < 31 && (1ll << bits) <= n_targets) ++bits;  // keys 0 .. n_targets
   // a stable sort of (key, flat position): the sources of a target end up in ascending position
   size_t stb = tb;
-  PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, stb, keys, keys_sorted, iota, pos, (int)n_idx, 0, bits, st));
-  *start_out = start;
-  *pos_out = pos;
+  PCMI_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(temp, stb, w.keys, w.keys_sorted, w.iota, w.pos, (int)n_idx, 0, bits, st));
+  *start_out = w.start;
+  *pos_out = w.pos;
   return PCMI_OK;
 }
 
@@ -526,9 +532,20 @@ using namespace pcmi::pointset;
 
 extern "C" {
 
+// null: a batch without a row list / no cloud beyond the register-resident tiers
+struct FpsWs { float *compact, *mind; size_t bytes; };
+static FpsWs fps_ws(void* ws, int64_t n_points, int64_t max_cloud, bool with_rows) {
+  const size_t n = (size_t)std::max<int64_t>(n_points, 0);
+  Carve cv{(char*)ws};
+  FpsWs w;
+  w.compact = with_rows ? cv.take<float>(n * 3) : nullptr;
+  w.mind = max_cloud > kFpsRegCoordPoints ? cv.take<float>(n) : nullptr;
+  w.bytes = cv.used;
+  return w;
+}
+
 size_t pcmi_fps_workspace_bytes(int64_t n_points, int64_t max_cloud, int with_rows) {
-  n_points = std::max<int64_t>(n_points, 0);
-  return (with_rows ? align_up((size_t)n_points * 12, 256) : 0) + (max_cloud > kFpsRegCoordPoints ? align_up((size_t)n_points * 4, 256) : 0);
+  return fps_ws(nullptr, n_points, max_cloud, with_rows != 0).bytes;
 }
 
 int pcmi_fps(const float* xyz, int64_t n_points, const int32_t* rows, const int32_t* offs, int64_t n_clouds, int64_t max_cloud,
@@ -541,23 +558,18 @@ int pcmi_fps(const float* xyz, int64_t n_points, const int32_t* rows, const int3
                "fps: a dense batch has no row list and n_clouds * max_cloud == n_points");
   if (n_clouds == 0) return PCMI_OK;
   PCMI_REQUIRE(out && (xyz || n_points == 0), PCMI_ERR_INVALID, "fps: null pointer");
-  const size_t need = pcmi_fps_workspace_bytes(n_points, max_cloud, rows != nullptr);
-  PCMI_REQUIRE(need == 0 || (ws && ws_bytes >= need), PCMI_ERR_WORKSPACE, "fps: workspace too small");
+  const size_t need = fps_ws(nullptr, n_points, max_cloud, rows != nullptr).bytes;  // 0: no piece, or no point
+  if (need != 0)
+    if (int rc = require_ws("fps", ws, ws_bytes, need, 1)) return rc;
   hipStream_t st = as_stream(stream);
-  Carve cv{(char*)ws, need ? ws_bytes : 0};
+  const FpsWs w = fps_ws(ws, n_points, max_cloud, rows != nullptr);
   const float* pts = xyz;
   if (rows && n_points > 0) {
-    float* compact = (float*)cv.take((size_t)n_points * 12);
-    PCMI_REQUIRE(compact, PCMI_ERR_WORKSPACE, "fps: workspace too small");
-    fps_compact_kernel<<<(unsigned)ceil_div(n_points, 256), 256, 0, st>>>(xyz, rows, offs, n_clouds, n_points, compact);
+    fps_compact_kernel<<<(unsigned)ceil_div(n_points, 256), 256, 0, st>>>(xyz, rows, offs, n_clouds, n_points, w.compact);
     PCMI_LAUNCH_CHECK();
-    pts = compact;
+    pts = w.compact;
   }
-  float* mind_ws = nullptr;
-  if (max_cloud > kFpsRegCoordPoints) {
-    mind_ws = (float*)cv.take((size_t)n_points * 4);
-    PCMI_REQUIRE(mind_ws, PCMI_ERR_WORKSPACE, "fps: workspace too small");
-  }
+  float* mind_ws = w.mind;
   const int nd = offs ? 0 : (int)max_cloud;
   if (offs) {  // a cloud larger than the caller's bound belongs to no launched tier: it reads as empty
     PCMI_HIP_CHECK(hipMemsetAsync(out, 0xff, (size_t)n_clouds * m * 4, st));

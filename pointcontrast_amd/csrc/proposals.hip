@@ -241,11 +241,9 @@ int pcmi_proposal_overlap(const int32_t* member, int64_t ld, int64_t n, int S, c
   PCMI_REQUIRE(Kmax <= kMaxK, PCMI_ERR_UNSUPPORTED, "proposal_overlap: %d proposals per scene, at most %d are supported", Kmax, kMaxK);
   PCMI_REQUIRE(scene_count && inter && (P == 0 || (prop_scene && size && local)) && (n == 0 || member), PCMI_ERR_INVALID,
                "proposal_overlap: null pointer");
-  const size_t need = pcmi_proposal_overlap_workspace_bytes(P);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "proposal_overlap: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 4 == 0, PCMI_ERR_INVALID, "proposal_overlap: workspace must be 4-byte aligned");
+  if (int rc = require_ws("proposal_overlap", ws, ws_bytes, pcmi_proposal_overlap_workspace_bytes(P), 4)) return rc;
   hipStream_t st = as_stream(stream);
-  int32_t* code = (int32_t*)ws;
+  int32_t* code = static_cast<int32_t*>(ws);
   PCMI_HIP_CHECK(hipMemsetAsync(inter, 0, (size_t)(B * Kmax * Kmax) * 4, st));
   if (P == 0) {
     PCMI_HIP_CHECK(hipMemsetAsync(scene_count, 0, (size_t)B * 4, st));

@@ -484,11 +484,11 @@ int pcmi_bn_maxpool_fwd_train(const float* x, int64_t x_ld, int64_t R, int ns, i
                "bn_maxpool_fwd_train: running_mean and running_var are given together or not at all");
   if (R == 0 || C == 0) return PCMI_OK;
   PCMI_REQUIRE(x && gamma && beta && out && arg && save_mean && save_invstd, PCMI_ERR_INVALID, "bn_maxpool_fwd_train: null pointer");
-  PCMI_REQUIRE(ws && ws_bytes >= maxpool_workspace(R, ns, C), PCMI_ERR_WORKSPACE, "bn_maxpool_fwd_train: workspace too small");
+  if (int ws_rc = require_ws("bn_maxpool_fwd_train", ws, ws_bytes, maxpool_workspace(R, ns, C), 1)) return ws_rc;
   hipStream_t st = as_stream(stream);
   const int64_t n = R * ns;
   const bool vx = C % 4 == 0 && x_ld % 4 == 0 && aligned16(x);
-  double* part = (double*)ws;
+  double* part = static_cast<double*>(ws);
   int64_t chunks = 0;
   const int rc2 = colsum(StatsOp{x, x_ld}, vx, n, C, part, &chunks, st);
   if (rc2 != PCMI_OK) return rc2;
@@ -534,11 +534,11 @@ int pcmi_bn_maxpool_bwd(const float* gout, int64_t gout_ld, const float* x, int6
   if (R == 0 || C == 0) return PCMI_OK;
   PCMI_REQUIRE(gout && x && out && arg && gamma && save_mean && save_invstd && dx && dgamma && dbeta, PCMI_ERR_INVALID,
                "bn_maxpool_bwd: null pointer");
-  PCMI_REQUIRE(ws && ws_bytes >= maxpool_workspace(R, ns, C), PCMI_ERR_WORKSPACE, "bn_maxpool_bwd: workspace too small");
+  if (int ws_rc = require_ws("bn_maxpool_bwd", ws, ws_bytes, maxpool_workspace(R, ns, C), 1)) return ws_rc;
   hipStream_t st = as_stream(stream);
   const bool vec = C % 4 == 0 && x_ld % 4 == 0 && out_ld % 4 == 0 && gout_ld % 4 == 0 && dx_ld % 4 == 0 && aligned16(x) && aligned16(out) &&
                    aligned16(gout) && aligned16(dx) && ((uintptr_t)arg & 3) == 0;
-  double* part = (double*)ws;
+  double* part = static_cast<double*>(ws);
   int64_t chunks = 0;
   const int rc2 = colsum(GradOp{gout, gout_ld, out, out_ld, arg, x, x_ld, save_mean, save_invstd, ns, C}, vec, R, C, part, &chunks, st);
   if (rc2 != PCMI_OK) return rc2;

@@ -247,10 +247,7 @@ int pcmi_seg_eval_rows(const float* logits, int64_t ld, int64_t n, int c, const 
   PCMI_REQUIRE(ld >= c, PCMI_ERR_INVALID, "seg_eval_rows: leading dimension %lld below the %d classes", (long long)ld, c);
   if (n == 0) return PCMI_OK;
   PCMI_REQUIRE(logits && labels && pred && hist && batch4, PCMI_ERR_INVALID, "seg_eval_rows: null pointer");
-  const size_t need = pcmi_seg_eval_rows_workspace_bytes(n);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "seg_eval_rows: workspace too small (%zu bytes, %zu needed)", ws_bytes,
-               need);
-  PCMI_REQUIRE((uintptr_t)ws % 8 == 0, PCMI_ERR_INVALID, "seg_eval_rows: workspace must be 8-byte aligned");
+  if (int rc = require_ws("seg_eval_rows", ws, ws_bytes, pcmi_seg_eval_rows_workspace_bytes(n), 8)) return rc;
   hipStream_t st = as_stream(stream);
   unsigned* counter = stream_counters(st, 1);
   if (!counter) return PCMI_ERR_HIP;
@@ -270,9 +267,7 @@ int pcmi_seg_ap(const float* sorted_prob, const int64_t* order, const int32_t* l
                 int64_t* ap_cnt, void* ws, size_t ws_bytes, pcmi_stream_t stream) {
   PCMI_REQUIRE(rows_shape_ok(n, c), PCMI_ERR_INVALID, "seg_ap: bad shape (n %lld, c %d; 1 <= c <= %d)", (long long)n, c, kMaxClasses);
   PCMI_REQUIRE(ap && (n == 0 || (sorted_prob && order && labels)), PCMI_ERR_INVALID, "seg_ap: null pointer");
-  const size_t need = pcmi_seg_ap_workspace_bytes(c);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "seg_ap: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 4 == 0, PCMI_ERR_INVALID, "seg_ap: workspace must be 4-byte aligned");
+  if (int rc = require_ws("seg_ap", ws, ws_bytes, pcmi_seg_ap_workspace_bytes(c), 4)) return rc;
   hipStream_t st = as_stream(stream);
   int32_t* npos = static_cast<int32_t*>(ws);
   PCMI_HIP_CHECK(hipMemsetAsync(npos, 0, (size_t)c * sizeof(int32_t), st));

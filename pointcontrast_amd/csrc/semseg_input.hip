@@ -457,9 +457,19 @@ using namespace pcmi::seginput;
 
 extern "C" {
 
+struct BlurWs { unsigned long long* box; float* tmp; size_t bytes; };
+static BlurWs blur_ws(void* ws, int64_t B, int cx, int cy, int cz) {
+  Carve cv{(char*)ws};
+  BlurWs L;
+  L.box = cv.take<unsigned long long>((size_t)B * 6);
+  L.tmp = cv.take<float>((size_t)B * cx * cy * cz * 3);
+  L.bytes = cv.used;
+  return L;
+}
+
 size_t pcmi_elastic_blur_workspace_bytes(int64_t B, int cx, int cy, int cz) {
   if (B < 1 || B > kMaxScenes || !cap_ok(B, cx, cy, cz)) return 0;
-  return align_up((size_t)B * 6 * 8, 256) + align_up((size_t)B * cx * cy * cz * 3 * 4, 256);
+  return blur_ws(nullptr, B, cx, cy, cz).bytes;
 }
 
 int pcmi_elastic_blur(const double* xyz, const int64_t* offsets, int64_t n, int64_t B, double granularity, const int32_t* active,
@@ -470,25 +480,22 @@ int pcmi_elastic_blur(const double* xyz, const int64_t* offsets, int64_t n, int6
   PCMI_REQUIRE(cap_ok(B, cx, cy, cz), PCMI_ERR_INVALID, "elastic_blur: capacity (%d, %d, %d): 3..4096 each, B cx cy cz 3 < 2^31", cx, cy, cz);
   PCMI_REQUIRE(granularity > 0.0 && granularity < 1e300, PCMI_ERR_INVALID, "elastic_blur: granularity must be positive and finite");
   PCMI_REQUIRE(offsets && noise && grid_dims && grid_min && flags && (n == 0 || xyz), PCMI_ERR_INVALID, "elastic_blur: null pointer");
-  const size_t need = pcmi_elastic_blur_workspace_bytes(B, cx, cy, cz);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "elastic_blur: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "elastic_blur: workspace must be 16-byte aligned");
+  if (int rc = require_ws("elastic_blur", ws, ws_bytes, blur_ws(nullptr, B, cx, cy, cz).bytes, 16)) return rc;
   hipStream_t st = as_stream(stream);
-  unsigned long long* box = (unsigned long long*)ws;
-  float* tmp = (float*)((char*)ws + align_up((size_t)B * 6 * 8, 256));
-  el_box_reset_kernel<<<(unsigned)ceil_div(6 * B, kThreads), kThreads, 0, st>>>(box, (int)B);
+  const BlurWs L = blur_ws(ws, B, cx, cy, cz);
+  el_box_reset_kernel<<<(unsigned)ceil_div(6 * B, kThreads), kThreads, 0, st>>>(L.box, (int)B);
   PCMI_LAUNCH_CHECK();
   if (n > 0) {
-    tf_box_kernel<<<(unsigned)ceil_div(n, kThreads), kThreads, 0, st>>>(xyz, n, offsets, (int)B, box);
+    tf_box_kernel<<<(unsigned)ceil_div(n, kThreads), kThreads, 0, st>>>(xyz, n, offsets, (int)B, L.box);
     PCMI_LAUNCH_CHECK();
   }
-  el_dims_kernel<<<(unsigned)ceil_div(B, kThreads), kThreads, 0, st>>>(box, (int)B, granularity, active, cx, cy, cz, grid_dims, grid_min, flags);
+  el_dims_kernel<<<(unsigned)ceil_div(B, kThreads), kThreads, 0, st>>>(L.box, (int)B, granularity, active, cx, cy, cz, grid_dims, grid_min, flags);
   PCMI_LAUNCH_CHECK();
   const int64_t total = B * cx * cy * cz * 3;
   const unsigned grid = (unsigned)ceil_div(total, kThreads);
   for (int pass = 0; pass < 6; ++pass) {  // two rounds of x, y, z; an even number of passes ends in `noise`
-    const float* src = (pass & 1) ? tmp : noise;
-    float* dst = (pass & 1) ? noise : tmp;
+    const float* src = (pass & 1) ? L.tmp : noise;
+    float* dst = (pass & 1) ? noise : L.tmp;
     el_blur_kernel<<<grid, kThreads, 0, st>>>(src, dst, total, cx, cy, cz, grid_dims, pass % 3);
     PCMI_LAUNCH_CHECK();
   }
@@ -524,9 +531,7 @@ int pcmi_seg_transform(const double* xyz, const int64_t* offsets, int64_t n, int
   PCMI_REQUIRE(clip_mode >= 0 && clip_mode <= 2, PCMI_ERR_INVALID, "seg_transform: clip_mode %d (0 none, 1 numeric, 2 per axis)", clip_mode);
   PCMI_REQUIRE(offsets && mats && scene_min && aligned && flags && (n == 0 || (xyz && vox && keep)) && (clip_mode == 0 || clip_host),
                PCMI_ERR_INVALID, "seg_transform: null pointer");
-  const size_t need = pcmi_seg_transform_workspace_bytes(B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "seg_transform: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "seg_transform: workspace must be 16-byte aligned");
+  if (int rc = require_ws("seg_transform", ws, ws_bytes, pcmi_seg_transform_workspace_bytes(B), 16)) return rc;
   Clip clip;
   clip.mode = clip_mode;
   for (int q = 0; q < 6; ++q) clip.lim[q] = 0.0;
@@ -540,7 +545,7 @@ int pcmi_seg_transform(const double* xyz, const int64_t* offsets, int64_t n, int
     }
   }
   hipStream_t st = as_stream(stream);
-  unsigned long long* box = (unsigned long long*)ws;
+  unsigned long long* box = static_cast<unsigned long long*>(ws);
   tf_init_kernel<<<(unsigned)ceil_div(6 * B, kThreads), kThreads, 0, st>>>(box, scene_min, (int)B);
   PCMI_LAUNCH_CHECK();
   if (n > 0) {
@@ -557,11 +562,26 @@ int pcmi_seg_transform(const double* xyz, const int64_t* offsets, int64_t n, int
   return PCMI_OK;
 }
 
+struct QuantizeWs { uint64_t* keys; uint32_t *first, *slot_of; int32_t *mixed, *is_first, *pos; void* temp; size_t temp_bytes, bytes; };
+static QuantizeWs quantize_ws(void* ws, int64_t n) {
+  const size_t cap = (size_t)table_cap(n);
+  Carve cv{(char*)ws};
+  QuantizeWs L;
+  L.keys = cv.take<uint64_t>(cap);
+  L.first = cv.take<uint32_t>(cap);
+  L.mixed = cv.take<int32_t>(cap);
+  L.slot_of = cv.take<uint32_t>((size_t)std::max<int64_t>(n, 1));
+  L.is_first = cv.take<int32_t>((size_t)n + 1);
+  L.pos = cv.take<int32_t>((size_t)n + 1);
+  L.temp_bytes = cub_scan_bytes<int32_t>(n + 1);
+  L.temp = cv.take<char>(L.temp_bytes);
+  L.bytes = cv.used;
+  return L;
+}
+
 size_t pcmi_seg_quantize_workspace_bytes(int64_t n) {
   if (n < 0 || n > kMaxRows) return 0;
-  const int64_t cap = table_cap(n), n1 = std::max<int64_t>(n, 1);
-  return align_up((size_t)cap * 8, 256) + 2 * align_up((size_t)cap * 4, 256) + align_up((size_t)n1 * 4, 256) +
-         2 * align_up((size_t)(n + 1) * 4, 256) + cub_scan_bytes<int32_t>(n + 1);
+  return quantize_ws(nullptr, n).bytes;
 }
 
 int pcmi_seg_quantize(const int32_t* vox, const uint8_t* keep, const int32_t* labels, const int64_t* offsets, const int32_t* scene_min,
@@ -572,38 +592,27 @@ int pcmi_seg_quantize(const int32_t* vox, const uint8_t* keep, const int32_t* la
   PCMI_REQUIRE(n <= kMaxRows, PCMI_ERR_UNSUPPORTED, "seg_quantize: %lld rows, at most 2^29", (long long)n);
   PCMI_REQUIRE(offsets && counts && flags && (n == 0 || (vox && coords && index)) && ((labels == nullptr) == (out_labels == nullptr)),
                PCMI_ERR_INVALID, "seg_quantize: null pointer (labels and out_labels go together)");
-  const size_t need = pcmi_seg_quantize_workspace_bytes(n);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "seg_quantize: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "seg_quantize: workspace must be 16-byte aligned");
+  if (int rc = require_ws("seg_quantize", ws, ws_bytes, quantize_ws(nullptr, n).bytes, 16)) return rc;
   hipStream_t st = as_stream(stream);
   if (n == 0) {
     PCMI_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)(B + 1) * 8, st));
     return PCMI_OK;
   }
   const int64_t cap = table_cap(n);
-  Carve cv{(char*)ws, ws_bytes};
-  uint64_t* keys = (uint64_t*)cv.take((size_t)cap * 8);
-  uint32_t* first = (uint32_t*)cv.take((size_t)cap * 4);
-  int32_t* mixed = (int32_t*)cv.take((size_t)cap * 4);
-  uint32_t* slot_of = (uint32_t*)cv.take((size_t)n * 4);
-  int32_t* is_first = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  int32_t* pos = (int32_t*)cv.take((size_t)(n + 1) * 4);
-  const size_t tb = cub_scan_bytes<int32_t>(n + 1);
-  void* temp = cv.take(tb);
-  PCMI_REQUIRE(keys && first && mixed && slot_of && is_first && pos && temp, PCMI_ERR_WORKSPACE, "seg_quantize: workspace too small");
+  const QuantizeWs L = quantize_ws(ws, n);
   const uint32_t mask = (uint32_t)(cap - 1);
-  PCMI_HIP_CHECK(hipMemsetAsync(keys, 0xff, (size_t)cap * 8, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(first, 0xff, (size_t)cap * 4, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(mixed, 0, (size_t)cap * 4, st));
-  PCMI_HIP_CHECK(hipMemsetAsync(is_first + n, 0, 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.keys, 0xff, (size_t)cap * 8, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.first, 0xff, (size_t)cap * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.mixed, 0, (size_t)cap * 4, st));
+  PCMI_HIP_CHECK(hipMemsetAsync(L.is_first + n, 0, 4, st));
   const unsigned grid = (unsigned)ceil_div(n, kThreads);
-  q_insert_kernel<<<grid, kThreads, 0, st>>>(vox, keep, n, offsets, (int)B, scene_min, keys, mask, first, slot_of, flags);
+  q_insert_kernel<<<grid, kThreads, 0, st>>>(vox, keep, n, offsets, (int)B, scene_min, L.keys, mask, L.first, L.slot_of, flags);
   PCMI_LAUNCH_CHECK();
-  q_label_kernel<<<grid, kThreads, 0, st>>>(n, slot_of, first, labels, mixed, is_first);
+  q_label_kernel<<<grid, kThreads, 0, st>>>(n, L.slot_of, L.first, labels, L.mixed, L.is_first);
   PCMI_LAUNCH_CHECK();
-  if (int rc = cub_scan_excl(temp, tb, is_first, pos, n + 1, st)) return rc;
+  if (int rc = cub_scan_excl(L.temp, L.temp_bytes, L.is_first, L.pos, n + 1, st)) return rc;
   q_write_kernel<<<(unsigned)ceil_div(std::max<int64_t>(n, B + 1), kThreads), kThreads, 0, st>>>(
-      vox, n, offsets, (int)B, scene_min, slot_of, is_first, pos, labels, mixed, ignore_label, coords, index, out_labels, counts);
+      vox, n, offsets, (int)B, scene_min, L.slot_of, L.is_first, L.pos, labels, L.mixed, ignore_label, coords, index, out_labels, counts);
   PCMI_LAUNCH_CHECK();
   return PCMI_OK;
 }
@@ -621,11 +630,9 @@ int pcmi_seg_color_augment(const float* feats_src, int64_t n_src, const int64_t*
                (long long)B, kMaxScenes, (long long)n_src, (long long)lut_n);
   if (m == 0) return PCMI_OK;
   PCMI_REQUIRE(coords && feats_out && (n_src == 0 || feats_src) && (lut_n == 0 || lut), PCMI_ERR_INVALID, "seg_color_augment: null pointer");
-  const size_t need = pcmi_seg_color_augment_workspace_bytes(B);
-  PCMI_REQUIRE(ws && ws_bytes >= need, PCMI_ERR_WORKSPACE, "seg_color_augment: workspace too small (%zu bytes, %zu needed)", ws_bytes, need);
-  PCMI_REQUIRE((uintptr_t)ws % 16 == 0, PCMI_ERR_INVALID, "seg_color_augment: workspace must be 16-byte aligned");
+  if (int rc = require_ws("seg_color_augment", ws, ws_bytes, pcmi_seg_color_augment_workspace_bytes(B), 16)) return rc;
   hipStream_t st = as_stream(stream);
-  uint32_t* red = (uint32_t*)ws;
+  uint32_t* red = static_cast<uint32_t*>(ws);
   const unsigned grid = (unsigned)ceil_div(m, kThreads);
   if (params) {
     ca_init_kernel<<<(unsigned)ceil_div(9 * B, kThreads), kThreads, 0, st>>>(red, (int)B);

@@ -199,10 +199,20 @@ int pcmi_views_zbuffer(const double* points, int64_t points_ld, int64_t n, const
   return PCMI_OK;
 }
 
-size_t pcmi_views_visible_workspace_bytes(int64_t n, int64_t n_views) {
+struct VisibleWs { int64_t* count; void* temp; size_t temp_bytes, bytes; };
+static VisibleWs visible_ws(void* ws, int64_t n, int64_t n_views) {
   const int64_t items = std::max<int64_t>(n_views, 1) * ceil_div(std::max<int64_t>(n, 1), 64);
-  return align_up((size_t)items * 8, 256) + cub_scan_bytes<int64_t>(items) + 1024;
+  Carve cv{(char*)ws};
+  VisibleWs w;
+  w.count = cv.take<int64_t>((size_t)items);
+  w.temp_bytes = cub_scan_bytes<int64_t>(items);
+  w.temp = cv.take<char>(w.temp_bytes);
+  cv.take<char>(1024);  // (unused tail the query has always counted)
+  w.bytes = cv.used;
+  return w;
 }
+
+size_t pcmi_views_visible_workspace_bytes(int64_t n, int64_t n_views) { return visible_ws(nullptr, n, n_views).bytes; }
 
 int pcmi_views_visible(const double* points, int64_t points_ld, int64_t n, const double* w2c, int64_t n_views, double fx, double fy,
                        double cx, double cy, int64_t height, int64_t width, double z_near, double z_far, double rel_tol,
@@ -224,20 +234,16 @@ int pcmi_views_visible(const double* points, int64_t points_ld, int64_t n, const
     return PCMI_OK;
   }
   PCMI_REQUIRE(points && w2c && zbuf && mask && word_start && pixels, PCMI_ERR_INVALID, "views_visible: null pointer");
-  PCMI_REQUIRE(ws && ws_bytes >= pcmi_views_visible_workspace_bytes(n, n_views), PCMI_ERR_WORKSPACE, "views_visible: workspace too small");
+  if (int ws_rc = require_ws("views_visible", ws, ws_bytes, visible_ws(nullptr, n, n_views).bytes, 1)) return ws_rc;
   const int64_t n_words = ceil_div(n, 64), items = n_views * n_words, hw = height * width;
-  char* p = (char*)ws;
-  int64_t* count = (int64_t*)p;
-  p += align_up((size_t)items * 8, 256);
-  const size_t tb = cub_scan_bytes<int64_t>(items);
-  void* temp = p;
+  const VisibleWs w = visible_ws(ws, n, n_views);
   const Camera cam{fx, fy, cx, cy, z_near, z_far, (int)height, (int)width};
   const dim3 grid((unsigned)ceil_div(n, kThreads), (unsigned)ceil_div(n_views, kViewsPerBlock));
   views_visible_kernel<<<grid, kThreads, 0, st>>>(points, points_ld, n, w2c, (int)n_views, cam, 1.0 + rel_tol, zbuf, n_words,
-                                                  (unsigned long long*)mask, count);
+                                                  (unsigned long long*)mask, w.count);
   PCMI_LAUNCH_CHECK();
-  if (int scan_rc = cub_scan_excl(temp, tb, count, word_start, items, st)) return scan_rc;
-  views_offsets_kernel<<<(unsigned)ceil_div(n_views + 1, kThreads), kThreads, 0, st>>>(count, word_start, n_views, n_words, offsets);
+  if (int scan_rc = cub_scan_excl(w.temp, w.temp_bytes, w.count, word_start, items, st)) return scan_rc;
+  views_offsets_kernel<<<(unsigned)ceil_div(n_views + 1, kThreads), kThreads, 0, st>>>(w.count, word_start, n_views, n_words, offsets);
   PCMI_LAUNCH_CHECK();
   PCMI_HIP_CHECK(hipMemsetAsync(pixels, 0, (size_t)n_views * 8, st));
   const dim3 pgrid((unsigned)std::min<int64_t>(ceil_div(hw, kThreads), 64), (unsigned)n_views);

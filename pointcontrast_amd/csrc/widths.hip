@@ -61,19 +61,19 @@ int spconv_forward(const float* in, int64_t in_ld, int64_t n_in, int cin, const 
                               ws_bytes, st);
   PCMI_REQUIRE(in && weight && out, PCMI_ERR_INVALID, "spconv_fwd: null argument");
   const int K = map ? map->K : 1, Cp = up32(cin), Np = up32(cout);
-  Carve cv{(char*)ws, ws ? ws_bytes : 0};
-  float* wp = (float*)cv.take((size_t)K * Cp * Np * sizeof(float));
-  float* bp = bias ? (float*)cv.take(Np * sizeof(float)) : nullptr;
-  float* xp = Cp != cin ? (float*)cv.take((size_t)n_in * Cp * sizeof(float)) : nullptr;
-  float* yp = Np != cout ? (float*)cv.take((size_t)n_out * Np * sizeof(float)) : nullptr;
-  PCMI_REQUIRE(wp && (!bias || bp) && (Cp == cin || xp) && (Np == cout || yp), PCMI_ERR_WORKSPACE,
+  Carve cv{(char*)ws};
+  float* wp = cv.take<float>((size_t)K * Cp * Np);
+  float* bp = bias ? cv.take<float>(Np) : nullptr;
+  float* xp = Cp != cin ? cv.take<float>((size_t)n_in * Cp) : nullptr;
+  float* yp = Np != cout ? cv.take<float>((size_t)n_out * Np) : nullptr;
+  PCMI_REQUIRE(ws && cv.used <= ws_bytes, PCMI_ERR_WORKSPACE,
                "spconv_fwd: workspace too small for the padded widths (%d -> %d)", cin, cout);
   int rc = pad2d(weight, cout, cin, cout, (int64_t)cin * cout, wp, Np, Cp, Np, (int64_t)Cp * Np, K, 0, st);
   if (rc) return rc;
   if (bp && (rc = pad2d(bias, cout, 1, cout, 0, bp, Np, 1, Np, 0, 1, 0, st))) return rc;
   if (xp && (rc = pad2d(in, in_ld, n_in, cin, 0, xp, Cp, n_in, Cp, 0, 1, 0, st))) return rc;
   rc = spconv_forward_m32(xp ? xp : in, xp ? Cp : in_ld, n_in, Cp, wp, Np, map, transpose, bp, yp ? yp : out,
-                          yp ? Np : out_ld, n_out, yp ? 0 : accumulate, cv.p, cv.left, st);
+                          yp ? Np : out_ld, n_out, yp ? 0 : accumulate, cv.base + cv.used, ws_bytes - cv.used, st);
   if (rc) return rc;
   if (yp) rc = pad2d(yp, Np, n_out, Np, 0, out, out_ld, n_out, cout, 0, 1, accumulate, st);
   return rc;
@@ -87,17 +87,17 @@ int spconv_backward_data(const float* gout, int64_t gout_ld, int64_t n_out, int 
                                     ws, ws_bytes, st);
   PCMI_REQUIRE(gout && weight && gin, PCMI_ERR_INVALID, "spconv_bwd_data: null argument");
   const int K = map ? map->K : 1, Cp = up32(cin), Np = up32(cout);
-  Carve cv{(char*)ws, ws ? ws_bytes : 0};
-  float* wp = (float*)cv.take((size_t)K * Cp * Np * sizeof(float));
-  float* gp = Np != cout ? (float*)cv.take((size_t)n_out * Np * sizeof(float)) : nullptr;
-  float* dxp = Cp != cin ? (float*)cv.take((size_t)n_in * Cp * sizeof(float)) : nullptr;
-  PCMI_REQUIRE(wp && (Np == cout || gp) && (Cp == cin || dxp), PCMI_ERR_WORKSPACE,
+  Carve cv{(char*)ws};
+  float* wp = cv.take<float>((size_t)K * Cp * Np);
+  float* gp = Np != cout ? cv.take<float>((size_t)n_out * Np) : nullptr;
+  float* dxp = Cp != cin ? cv.take<float>((size_t)n_in * Cp) : nullptr;
+  PCMI_REQUIRE(ws && cv.used <= ws_bytes, PCMI_ERR_WORKSPACE,
                "spconv_bwd_data: workspace too small for the padded widths (%d -> %d)", cin, cout);
   int rc = pad2d(weight, cout, cin, cout, (int64_t)cin * cout, wp, Np, Cp, Np, (int64_t)Cp * Np, K, 0, st);
   if (rc) return rc;
   if (gp && (rc = pad2d(gout, gout_ld, n_out, cout, 0, gp, Np, n_out, Np, 0, 1, 0, st))) return rc;
   rc = spconv_backward_data_m32(gp ? gp : gout, gp ? Np : gout_ld, n_out, Np, wp, Cp, map, transpose, dxp ? dxp : gin,
-                                dxp ? Cp : gin_ld, n_in, dxp ? 0 : accumulate, cv.p, cv.left, st);
+                                dxp ? Cp : gin_ld, n_in, dxp ? 0 : accumulate, cv.base + cv.used, ws_bytes - cv.used, st);
   if (rc) return rc;
   if (dxp) rc = pad2d(dxp, Cp, n_in, Cp, 0, gin, gin_ld, n_in, cin, 0, 1, accumulate, st);
   return rc;
@@ -111,18 +111,18 @@ int spconv_backward_weight(const float* in, int64_t in_ld, int64_t n_in, int cin
                                       accumulate, ws, ws_bytes, st);
   PCMI_REQUIRE(in && gout && gweight, PCMI_ERR_INVALID, "spconv_bwd_weight: null argument");
   const int K = map ? map->K : 1, Cp = up32(cin), Np = up32(cout);
-  Carve cv{(char*)ws, ws ? ws_bytes : 0};
-  float* gwp = (float*)cv.take((size_t)K * Cp * Np * sizeof(float));
-  float* gbp = gbias ? (float*)cv.take(Np * sizeof(float)) : nullptr;
-  float* xp = Cp != cin ? (float*)cv.take((size_t)n_in * Cp * sizeof(float)) : nullptr;
-  float* gp = Np != cout ? (float*)cv.take((size_t)n_out * Np * sizeof(float)) : nullptr;
-  PCMI_REQUIRE(gwp && (!gbias || gbp) && (Cp == cin || xp) && (Np == cout || gp), PCMI_ERR_WORKSPACE,
+  Carve cv{(char*)ws};
+  float* gwp = cv.take<float>((size_t)K * Cp * Np);
+  float* gbp = gbias ? cv.take<float>(Np) : nullptr;
+  float* xp = Cp != cin ? cv.take<float>((size_t)n_in * Cp) : nullptr;
+  float* gp = Np != cout ? cv.take<float>((size_t)n_out * Np) : nullptr;
+  PCMI_REQUIRE(ws && cv.used <= ws_bytes, PCMI_ERR_WORKSPACE,
                "spconv_bwd_weight: workspace too small for the padded widths (%d -> %d)", cin, cout);
   int rc = PCMI_OK;
   if (xp && (rc = pad2d(in, in_ld, n_in, cin, 0, xp, Cp, n_in, Cp, 0, 1, 0, st))) return rc;
   if (gp && (rc = pad2d(gout, gout_ld, n_out, cout, 0, gp, Np, n_out, Np, 0, 1, 0, st))) return rc;
   rc = spconv_backward_weight_m32(xp ? xp : in, xp ? Cp : in_ld, n_in, Cp, gp ? gp : gout, gp ? Np : gout_ld, n_out, Np, map,
-                                  transpose, gwp, gbp, 0, cv.p, cv.left, st);
+                                  transpose, gwp, gbp, 0, cv.base + cv.used, ws_bytes - cv.used, st);
   if (rc) return rc;
   rc = pad2d(gwp, Np, Cp, Np, (int64_t)Cp * Np, gweight, cout, cin, cout, (int64_t)cin * cout, K, accumulate, st);
   if (rc) return rc;

@@ -6,6 +6,7 @@ overrun into a failed assertion (every band lies inside the allocation it guards
 import ctypes as C
 
 import numpy as np
+import pytest
 import torch
 
 from helpers import surface_coords
@@ -180,3 +181,72 @@ def bn_ref64(x, gamma, beta, eps, res, relu, dy, relu_mask=None):
   n = x.shape[0]
   return dict(y=y_free, mean=mean.detach(), var=var.detach(), unbiased=(var * n / max(n - 1, 1)).detach(), dx=x64.grad,
               dgamma=g64.grad, dbeta=b64.grad, dres=r64.grad if r64 is not None else None, flipped_max=flipped_max)
+
+
+# ---- a workspace of exactly the queried size, and one byte less, under the Python wrappers ---------------------------------------
+class _ExactWorkspace:
+  """Stands in for runtime.ws_args: every call gets a guarded buffer of exactly the queried size, the `short_at`-th one a byte
+  less.  `untouched()`: no byte of any buffer, guard bands included, was written."""
+
+  def __init__(self, short_at=None):
+    self.short_at, self.bufs = short_at, []
+
+  def __call__(self, nbytes, device):
+    g = Guarded(nbytes, device)
+    short = 1 if self.short_at == len(self.bufs) else 0
+    self.bufs.append(g)
+    return g.vp, C.c_size_t(g.nbytes - short)
+
+  def check(self):
+    torch.cuda.synchronize()
+    assert self.bufs and all(g.nbytes > 0 for g in self.bufs)
+    for g in self.bufs:
+      g.check("workspace of %d bytes" % g.nbytes)
+
+  def untouched(self):
+    torch.cuda.synchronize()
+    return all(bool((g.buf == GUARD_BYTE).all()) for g in self.bufs)
+
+
+@pytest.fixture
+def exact_ws(monkeypatch):
+  """installs an _ExactWorkspace wherever the wrappers look ws_args up; restore=True puts the shared workspace back"""
+  from pointcontrast_amd import functional, runtime
+  from pointcontrast_amd.lib import device_loader
+
+  def install(short_at=None, restore=False):
+    monkeypatch.undo()
+    if restore:
+      return None
+    ws = _ExactWorkspace(short_at)
+    for mod in (functional, runtime, device_loader):
+      monkeypatch.setattr(mod, "ws_args", ws)
+    return ws
+  return install
+
+
+def _pcmi_error():
+  from pointcontrast_amd._lib import PcmiError
+  return PcmiError
+
+
+def _exact_and_short(exact_ws, run, same, calls=1, short_at=(0,)):
+  """run() with the wrappers' shared (generous) workspace, with exactly the queried bytes, and with one byte less at call k"""
+  want = run()
+  ws = exact_ws()
+  got = run()
+  ws.check()
+  assert len(ws.bufs) == calls
+  same(got, want)
+  for k in short_at:
+    ws = exact_ws(short_at=k)
+    with pytest.raises(_pcmi_error(), match="error -7"):
+      run()
+    assert len(ws.bufs) == k + 1 and bool((ws.bufs[k].buf == GUARD_BYTE).all()), "the refused call wrote nothing"
+  exact_ws(restore=True)
+
+
+def _same_arrays(got, want):
+  assert len(got) == len(want)
+  for g, w in zip(got, want):
+    assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes()

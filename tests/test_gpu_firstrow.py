@@ -5,14 +5,11 @@ np.unique(return_index=True).  Integer-valued points in a cube of side 6: at mos
 workgroup (256) +- 1, rowscan.h's block (2048) +- 1, the first size with more than two scan blocks.  Then the per-segment
 bookkeeping (an empty scene, offsets that stop short of n) and, for every *_workspace_bytes whose formula goes through
 cub_scan_bytes and that no other test file holds to it, a workspace of exactly the queried size and one byte less."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from c_contract import DEV, GUARD_BYTE, Guarded
-from pointcontrast_amd._lib import PcmiError
+from c_contract import DEV, _exact_and_short, _same_arrays, exact_ws  # noqa: F401  (exact_ws is a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -77,47 +74,6 @@ def test_families_agree_on_the_first_rows(PF, n):
     assert np.array_equal(rows, want), name
 
 
-class _ExactWorkspace:
-  """Stands in for runtime.ws_args: every call gets a guarded buffer of exactly the queried size, the `short_at`-th one a byte
-  less.  `untouched()`: no byte of any buffer, guard bands included, was written."""
-
-  def __init__(self, short_at=None):
-    self.short_at, self.bufs = short_at, []
-
-  def __call__(self, nbytes, device):
-    g = Guarded(nbytes, device)
-    short = 1 if self.short_at == len(self.bufs) else 0
-    self.bufs.append(g)
-    return g.vp, C.c_size_t(g.nbytes - short)
-
-  def check(self):
-    torch.cuda.synchronize()
-    assert self.bufs and all(g.nbytes > 0 for g in self.bufs)
-    for g in self.bufs:
-      g.check("workspace of %d bytes" % g.nbytes)
-
-  def untouched(self):
-    torch.cuda.synchronize()
-    return all(bool((g.buf == GUARD_BYTE).all()) for g in self.bufs)
-
-
-@pytest.fixture
-def exact_ws(monkeypatch):
-  """installs an _ExactWorkspace wherever the wrappers look ws_args up; restore=True puts the shared workspace back"""
-  from pointcontrast_amd import functional, runtime
-  from pointcontrast_amd.lib import device_loader
-
-  def install(short_at=None, restore=False):
-    monkeypatch.undo()
-    if restore:
-      return None
-    ws = _ExactWorkspace(short_at)
-    for mod in (functional, runtime, device_loader):
-      monkeypatch.setattr(mod, "ws_args", ws)
-    return ws
-  return install
-
-
 def test_no_rows(PF, exact_ws):
   """n = 0 where the entry accepts it: zero counts, and nothing enqueued that touches the workspace"""
   from pointcontrast_amd.lib import device_loader
@@ -174,28 +130,6 @@ N = 257
 
 def _points(seed, n=N):
   return np.random.RandomState(seed).rand(n, 3) * SIDE
-
-
-def _exact_and_short(exact_ws, run, same, calls=1, short_at=(0,)):
-  """run() with the wrappers' shared (generous) workspace, with exactly the queried bytes, and with one byte less at call k"""
-  want = run()
-  ws = exact_ws()
-  got = run()
-  ws.check()
-  assert len(ws.bufs) == calls
-  same(got, want)
-  for k in short_at:
-    ws = exact_ws(short_at=k)
-    with pytest.raises(PcmiError, match="error -7"):
-      run()
-    assert len(ws.bufs) == k + 1 and bool((ws.bufs[k].buf == GUARD_BYTE).all()), "the refused call wrote nothing"
-  exact_ws(restore=True)
-
-
-def _same_arrays(got, want):
-  assert len(got) == len(want)
-  for g, w in zip(got, want):
-    assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes()
 
 
 def test_voxelize_and_match_radius_workspace(exact_ws):
